@@ -38,6 +38,22 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict):
+    """--dump-outputs: what the timed path computed in its last step, one DIR/<name>.npy per array (float32 / float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes exceed {DUMP_MAX_BYTES}"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"[dump] {', '.join(f'{k} {tuple(np.shape(v))}' for k, v in arrays.items())} -> {out_dir} ({total} bytes)")
+
+
 def build_problem(cfg_name: str, **kw):
     """The synthetic problems of BASELINE.json's configs (surfh_amd/synth.py).  Config 4 (12 sub-bands, 8000 planes) runs on the
     reference driver's default 501 x 501 image (scripts/main_fusion.py:217): channel 4's field of view does not fit 251 pixels
@@ -165,6 +181,12 @@ def main_config5(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     rr1 = mb.cg_rr()
+    if args.dump_outputs and rank == 0:
+        # the iterate is 4 * planes * N^2 bytes (2 GB for one rank): a fixed, seeded sample of its planes
+        n_keep = min(hi - lo, DUMP_MAX_BYTES // 2 // (4 * N * N))
+        sel = np.sort(np.random.default_rng(0).choice(hi - lo, size=n_keep, replace=False))
+        dump_outputs(args.dump_outputs, {"x_planes_sample": x[torch.as_tensor(sel, device=dev)].cpu().numpy(),
+                                         "x_planes_sample_index": sel.astype(np.float64) + lo, "rr": rr1})
     if rank == 0:
         for name, (cnt, ms) in sorted(prof_all.items(), key=lambda kv: -kv[1][1]):
             log(f"[prof warm-up] {name:28s} launches {cnt:5d}  avg {ms / max(cnt, 1):8.4f} ms  per-step {ms / n_all:8.4f} ms")
@@ -242,9 +264,14 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=25.0, help="budget of the CPU baseline leg (0 = skip)")
     ap.add_argument("--no-profile", action="store_true", help="do not record per-kernel HIP events in the timed region")
     ap.add_argument("--no-verify", action="store_true", help="skip the randn dot test on the float64-accumulating verification plan")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (config 5: a seeded "
+                         "sample of the iterate's planes; at most 64 MB in all)")
     ap.add_argument("--plan-only", action="store_true", help="no GPU: print the unit assignment and the predicted per-rank cost "
                     "imbalance for --gpus N on the chosen config (gate <= 15 %%, SURVEY.md 8e) and exit")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.plan_only:
         from surfh_amd import synth
         from surfh_amd.fusion import plan_assignment
@@ -343,6 +370,12 @@ def main():
         t = torch.tensor([el], dtype=torch.float64, device="cpu" if rehearsal else f"cuda:{local}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if args.dump_outputs:
+        # what QuadCriterion_MRS.run_method('lcg') hands back after the last step: the iterate as maps [T, Na, Nb] and the
+        # r.r trace of every iterate (warm-up steps included); every rank holds the whole iterate
+        x_maps = fus.x_maps().cpu().numpy()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"x": x_maps, "grad_norm": np.asarray(fus.grad_norm, dtype=np.float64)})
 
     # parity gate reported with the number: the dot test of this rank's operator at benchmark size, inner
     # products accumulated in float64, non-negative test vectors (the physical regime; gate < 1e-6).  Outside the timed region.

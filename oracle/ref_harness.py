@@ -5,9 +5,9 @@ box).  Used by ``tests/golden/make_golden.py`` to generate the golden vectors th
 ``tests/test_oracle_golden.py`` holds ``oracle/surfh_oracle.py`` to, stage by stage.
 Nothing is copied: the reference's modules are imported from where they lie, and its
 one native file (``surfh/ToolsDir/cythons_files.pyx``) is cythonized + compiled from
-that path with outputs only under a scratch directory OUTSIDE the repository
-(``$SURFH_REF_BUILD`` or ``<tmp>/surfh_ref_build``): nothing compiled from the reference
-is committed or travels to the GPU box.
+that path with outputs only under ``oracle/_ref/`` (git-ignored; ``$SURFH_REF_BUILD``
+overrides it): nothing compiled from the reference is committed, and nothing on the
+GPU side reads it.
 
 The snapshot is mid-refactor and depends on packages that are not installed
 (SURVEY.md 8c).  What this harness supplies so that the surviving modules import:
@@ -38,9 +38,7 @@ import numpy as np
 
 REF = "/root/reference"
 HERE = os.path.dirname(os.path.abspath(__file__))
-import tempfile  # noqa: E402
-
-OUT = os.environ.get("SURFH_REF_BUILD") or os.path.join(tempfile.gettempdir(), "surfh_ref_build")
+OUT = os.environ.get("SURFH_REF_BUILD") or os.path.join(HERE, "_ref")
 
 
 def available() -> bool:
@@ -48,7 +46,7 @@ def available() -> bool:
 
 
 def build_cython(force=False) -> str:
-    """cythonize + gcc the reference's cythons_files.pyx into the scratch directory OUT (build.py:12-13 flags)."""
+    """cythonize + gcc the reference's cythons_files.pyx into OUT (build.py:12-13 flags)."""
     os.makedirs(OUT, exist_ok=True)
     import sysconfig
     so = os.path.join(OUT, "cythons_files" + sysconfig.get_config_var("EXT_SUFFIX"))
