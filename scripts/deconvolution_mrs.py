@@ -13,6 +13,13 @@ PSF of surfh/ToolsDir/utils.py:40-50 at the chosen wavelength, the 1C field of v
 pointings) or come from ``--input`` (an .npz with ``maps [4,N,N]``, ``psf [n,n]`` and optionally ``pointings [P,2]`` in
 degrees).  ``--planes L`` solves L wavelength planes at once (BASELINE.json configs[4]).  Results: ``res_x.npy``,
 ``criterion.npy``, ``data.npy`` under ``--out``.
+
+``--angle DEG`` (nonzero) runs the reference scripts' actual operator, the rotated-field ``spectro_blind.MRSBlurred``
+(scripts/simulate_deconvolution_mrs_rectangle.py:125-155, scripts/deconvolution_mrs_single_wavelength.py:119-155: the 1C field
+of view at ``8.2 - rotation_ref`` degrees, bilinear gridding, so ``--input`` pointings may be fractional); the solver uses the
+exact transpose of that operator.  ``--data_to_img`` also writes the quick-look back-projection ``data_to_img`` of the data
+(``adj_mean.npy``, ``adj.npy``, deconvolution_mrs_single_wavelength.py:159) and of the result's forward (``adj_mean_fit.npy``,
+``adj_fit.npy``, :194), single image only.
 """
 from __future__ import annotations
 
@@ -30,7 +37,7 @@ if ROOT not in sys.path:
 STEP = 0.025                       # arcsec per pixel (simulate_deconvolution_mrs_rectangle.py:66)
 
 
-def build_problem(npix: int, planes: int, seed: int, inp: str | None):
+def build_problem(npix: int, planes: int, seed: int, inp: str | None, angle: float = 0.0):
     from surfh_amd import instru, synth
     step_deg = STEP / 3600
     wl_1c = synth.band_wavelengths("1c")
@@ -52,7 +59,7 @@ def build_problem(npix: int, planes: int, seed: int, inp: str | None):
         pts = [(0.0, 0.0), (2 * s, -3 * s), (-4 * s, 1 * s), (3 * s, 5 * s)]
     mixed = (0.4 * maps[0] + 0.5 * maps[1] + 0.4 * maps[2] + 0.3 * maps[3]) * 10000          # :135
     ax = synth.axes(npix, step_deg)
-    ch1c = instru.IFU(fov=instru.FOV(3.2 / 3600, 3.7 / 3600, origin=instru.Coord(0, 0), angle=0.0), det_pix_size=0.196,
+    ch1c = instru.IFU(fov=instru.FOV(3.2 / 3600, 3.7 / 3600, origin=instru.Coord(0, 0), angle=angle), det_pix_size=0.196,
                       n_slit=21, w_blur=instru.SpectralBlur(float(np.mean([3100, 3610]))), pce=None, wavel_axis=wl_1c, name="1C")
     sotf = synth.ir2fr(psfs, (npix, npix))
     if planes == 1:
@@ -76,9 +83,17 @@ def build_problem(npix: int, planes: int, seed: int, inp: str | None):
 @click.option("--quiet", is_flag=True, help="no per-iteration prints (the reference prints every iteration)")
 @click.option("--seed", default=19940407, type=int)
 @click.option("--device", default=0, type=int)
-def main(npix, hyper_parameter, niter, method, value_init, planes, inp, out, quiet, seed, device):
-    from surfh_amd.spectro_blind_rectangle import MRSBlurred, QuadCriterion_MRS_2D
-    prob = build_problem(npix, planes, seed, inp)
+@click.option("--angle", default=0.0, type=float,
+              help="field-of-view angle in degrees; nonzero: the rotated-field operator spectro_blind.MRSBlurred (reference: 8.2)")
+@click.option("--data_to_img", is_flag=True, help="also write data_to_img of the data and of the result's forward")
+def main(npix, hyper_parameter, niter, method, value_init, planes, inp, out, quiet, seed, device, angle, data_to_img):
+    if angle:
+        from surfh_amd.spectro_blind import MRSBlurred, QuadCriterion_MRS_2D
+    else:
+        from surfh_amd.spectro_blind_rectangle import MRSBlurred, QuadCriterion_MRS_2D
+    if data_to_img and planes != 1:
+        raise click.UsageError("--data_to_img is defined for a single image (--planes 1)")
+    prob = build_problem(npix, planes, seed, inp, angle)
     model = MRSBlurred(prob["sotf"], prob["alpha_axis"], prob["beta_axis"], prob["ifu"], prob["step_deg"], prob["pointings"],
                        device=device)
     simulated_data = model.forward(prob["truth"])
@@ -99,6 +114,11 @@ def main(npix, hyper_parameter, niter, method, value_init, planes, inp, out, qui
     np.save(os.path.join(out, "res_x.npy"), x)
     np.save(os.path.join(out, "criterion.npy"), np.asarray(crit.L_crit_val))
     np.save(os.path.join(out, "data.npy"), simulated_data)
+    if data_to_img:
+        for suffix, d in (("", simulated_data), ("_fit", model.forward(x))):
+            adj_mean, adj = model.data_to_img(np.copy(d))
+            np.save(os.path.join(out, f"adj_mean{suffix}.npy"), adj_mean)
+            np.save(os.path.join(out, f"adj{suffix}.npy"), adj)
     model.close()
 
 
