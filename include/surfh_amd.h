@@ -305,6 +305,26 @@ int surfh_tst_adjoint(surfh_tst *t, const float *cube, float *maps);     /* mixi
 int surfh_tst_fwadj(surfh_tst *t, const float *maps, float *out);        /* mixing.py:316-317 */
 const char *surfh_tst_last_error(void);
 
+/* ---- exponential modified-Shepard resampling (surfh/ToolsDir/shepard_interpolation.pyx:78-141), the resampling step of
+ * the slit distortion correction (surfh/Preprocessing/distorsion_correction.py:108-178) ----
+ * n_seg independent segments (e.g. the slits of one or several exposures) in one call.  Segment s owns the samples
+ * [pt_off[s], pt_off[s+1]) of pt_alpha / pt_lambda / pt_value and an n_lambda[s] x n_alpha[s] block of query points,
+ * whose outputs are consecutive in `out` (row-major, segment after segment).  separable != 0: q_alpha holds the
+ * concatenated per-segment alpha axes (n_alpha[s] each) and q_lambda the concatenated lambda axes (n_lambda[s] each);
+ * separable == 0: q_alpha / q_lambda hold one coordinate pair per query point, in the layout of `out`.
+ * Per pair:  d = sqrtf(((a_k - a_g) inv_alpha_res[s])^2 + ((l_k - l_g) inv_lambda_res[s])^2) + epsilon, included when
+ * d <= pixel_cutoff with weight exp(-alpha d^p); out = sum w v / sum w (0 without any neighbour), the reference's
+ * float32 arithmetic.  neighbours (optional): number of included samples per query point.
+ * pt_off / n_alpha / n_lambda / inv_*_res are host arrays; the others are device pointers if device_ptrs != 0 (work on
+ * `stream`), host arrays otherwise.  kernel_ms (optional): device time from the first kernel to the last.
+ * Returns 0, or non-zero with the message in surfh_shepard_last_error().                                             */
+int surfh_shepard(int32_t n_seg, const int64_t *pt_off, const float *pt_alpha, const float *pt_lambda,
+                  const float *pt_value, const int32_t *n_alpha, const int32_t *n_lambda, int32_t separable,
+                  const float *q_alpha, const float *q_lambda, const float *inv_alpha_res, const float *inv_lambda_res,
+                  float p, float alpha, float pixel_cutoff, float epsilon, float *out, int32_t *neighbours,
+                  int32_t device_ptrs, void *stream, float *kernel_ms);
+const char *surfh_shepard_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,7 @@ EXPORTS = [
     "surfh_cg_begin_dev", "surfh_cg_iter_nosync_dev", "surfh_cg_xupdate_nosync_dev", "surfh_cg_refresh_nosync_dev", "surfh_cg_trace",
     "surfh_profile_enable", "surfh_profile_filter", "surfh_profile_count", "surfh_profile_get", "surfh_profile_reset", "surfh_debug_copy",
     "surfh_debug_dims", "surfh_gemm_selftest", "surfh_gemm_selftest_ksteps", "surfh_klist_classify",
+    "surfh_shepard", "surfh_shepard_last_error",
 ]
 
 _lib = None
@@ -136,6 +137,10 @@ def load():
     L.surfh_gemm_selftest_ksteps.argtypes = [C.POINTER(C.c_int64)]
     L.surfh_klist_classify.argtypes = [c_float_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64]
     L.surfh_klist_classify.restype = C.c_int32
+    L.surfh_shepard.argtypes = [C.c_int32, C.POINTER(C.c_int64), vp, vp, vp, c_int32_p, c_int32_p, C.c_int32, vp, vp,
+                                c_float_p, c_float_p, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, C.c_int32, vp,
+                                c_float_p]
+    L.surfh_shepard_last_error.restype = C.c_char_p
     _lib = L
     return L
 

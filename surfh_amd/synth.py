@@ -128,3 +128,73 @@ def config3(**kw) -> dict:
 def config4(**kw) -> dict:
     """BASELINE.json configs[3]: all 12 sub-bands, 251x251x8000 on [4.90, 28.70] um."""
     return problem(list(BANDS), 8000, (4.90, 28.70), **kw)
+
+
+def synthetic_mrs_exposure(band: str = "1a", n_rows: int = 1024, n_slit: int = None, slit_px: int = 24, gap_px: int = 4,
+                           ra: float = 83.8221, dec: float = -5.3911, nan_fraction: float = 0.002, seed: int = 0,
+                           lam_shift=None) -> dict:
+    """A synthetic MRS detector exposure for the distortion correction (surfh_amd.preprocessing).
+
+    ``n_slit`` vertical slit bands (default: the band's) of ``slit_px`` columns, ``gap_px`` NaN columns apart; the bands
+    bend by up to 2 columns over the detector height.  The analytic ``detector2world(x, y)`` gives absolute sky
+    coordinates: alpha runs across a band (the slit length, ``fov_alpha`` of the band) with a tilted, curved trace,
+    beta is the slit's position, lambda runs down the rows over the band's axis (a margin of 2 % each side) with a
+    slight tilt across the slit.  The scene is the smooth ``scene(alpha, lam)``; a random ``nan_fraction`` of the
+    slit pixels is NaN.  ``lam_shift``: {slit index: offset in um} moves a slit's wavelengths (to exercise the skip
+    rules of the correction).
+
+    Returns a dict: data [n_rows, n_cols] (NaN off the slits), alpha / beta / lam per pixel (NaN off the slits),
+    detector2world, scene, wavelengths (the band's axis), n_slit, ra, dec."""
+    ns, _, _, _, fa, fb, _ = BANDS[band.lower()]
+    n_slit = ns if n_slit is None else int(n_slit)
+    wl = band_wavelengths(band.lower())
+    lam_shift = dict(lam_shift or {})
+    pitch = slit_px + gap_px
+    n_cols = n_slit * pitch + gap_px
+    rows = np.arange(n_rows, dtype=np.float64)
+    t = rows / max(n_rows - 1, 1) - 0.5                               # -0.5 .. 0.5 down the detector
+    bend = np.rint(8.0 * t * t).astype(np.int64)                      # 0 .. 2 columns: curved bands
+    da = fa / 3600.0 / slit_px                                        # alpha per detector column [deg]
+    db = fb / 3600.0 / n_slit                                         # slit width [deg]
+    lo, hi = wl[0], wl[-1]
+    lo, hi = lo - 0.02 * (hi - lo), hi + 0.02 * (hi - lo)
+
+    def slit_and_u(x, y):
+        """slit index (-1 off the slits) and the position across it (columns from the band's centre)."""
+        x = np.asarray(x, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        yi = np.clip(np.rint(y).astype(np.int64), 0, n_rows - 1)
+        xr = x - gap_px - bend[yi]
+        s = np.floor(xr / pitch).astype(np.int64)
+        r = xr - s * pitch
+        on = (s >= 0) & (s < n_slit) & (r > -0.5) & (r < slit_px - 0.5)
+        return np.where(on, s, -1), r - 0.5 * (slit_px - 1)
+
+    def detector2world(x, y):
+        y = np.asarray(y, dtype=np.float64)
+        s, u = slit_and_u(x, y)
+        ty = y / max(n_rows - 1, 1) - 0.5
+        trace = u + 0.6 * ty + 0.8 * ty * ty                          # tilted, curved iso-alpha lines
+        alpha = ra + trace * da / np.cos(np.radians(dec))
+        beta = dec + (s - 0.5 * (n_slit - 1)) * db
+        shift = np.array([lam_shift.get(k, 0.0) for k in range(n_slit)] + [0.0])[s]
+        lam = lo + (hi - lo) * (y + 0.15 * u) / max(n_rows - 1, 1) + shift
+        off = s < 0
+        return tuple(np.where(off, np.nan, v) for v in (alpha, beta, lam))
+
+    a0 = ra
+
+    def scene(alpha, lam):
+        """smooth scene: one slow wave along alpha (period 1.5 slit lengths) times one along lambda (0.15 um)."""
+        xa = (np.asarray(alpha) - a0) * np.cos(np.radians(dec)) * 3600.0 / (1.5 * fa)
+        return 1.0 + 0.4 * np.sin(2 * np.pi * xa + 0.3) * np.cos(2 * np.pi * (np.asarray(lam) - lo) / 0.15)
+
+    yy, xx = np.meshgrid(np.arange(n_rows), np.arange(n_cols), indexing="ij")
+    alpha, beta, lam = detector2world(xx, yy)
+    data = scene(alpha, lam)
+    rng = np.random.default_rng(seed)
+    on = ~np.isnan(alpha)
+    data[on & (rng.random(data.shape) < nan_fraction)] = np.nan
+    data[~on] = np.nan
+    return dict(data=data, alpha=alpha, beta=beta, lam=lam, detector2world=detector2world, scene=scene,
+                wavelengths=wl, n_slit=n_slit, ra=ra, dec=dec)
