@@ -150,6 +150,39 @@ def check(rc: int, exc=RuntimeError):
         raise exc(load().surfh_last_error().decode("utf-8", "replace"))
 
 
+def solve(model, fn, data, mu, mu_reg, x0, max_iter, tol, refresh, callback, planes=1, squeeze=True):
+    """Run one of the host-buffer solvers of the C ABI (``surfh_cg_cb``, ``surfh_mmmg``, ``surfh_cg_planes_cb``,
+    ``surfh_mmmg_planes_cb``) on ``model``'s plan.  ``grad_norm`` has one column per plane, or is ``[nit+1]`` when
+    ``squeeze`` (a single image).  Returns ``(x, grad_norm, nit)``."""
+    y = np.ascontiguousarray(np.asarray(data, dtype=np.float32).reshape(-1))
+    if y.size != model.osize:
+        raise ValueError("data size mismatch")
+    x0a = None if x0 is None else np.ascontiguousarray(np.asarray(x0, dtype=np.float32).reshape(-1))
+    if x0a is not None and x0a.size != model.isize:
+        raise ValueError("x0 size mismatch")
+    x = np.empty(model.isize, dtype=np.float32)
+    gn = np.zeros((max_iter + 1, planes), dtype=np.float64)
+    nit = C.c_int32()
+    err = []
+
+    def tramp(_user, it, gptr, xptr):
+        try:
+            g = np.ctypeslib.as_array(gptr, shape=(it + 1, planes)).copy()
+            xi = np.ctypeslib.as_array(xptr, shape=(model.isize,)).astype(np.float64).reshape(model.ishape)
+            return 1 if callback(it, g[:, 0] if squeeze else g, xi) else 0
+        except BaseException as e:          # never unwind through the C frame
+            err.append(e)
+            return 1
+
+    cb = CG_CALLBACK(tramp) if callback is not None else CG_CALLBACK()
+    check(fn(model._plan, fptr(y), float(mu), float(mu_reg), fptr(x0a) if x0a is not None else None, int(max_iter),
+             float(tol), int(refresh), fptr(x), dptr(gn), C.byref(nit), cb, None))
+    if err:
+        raise err[0]
+    gn = gn[: nit.value + 1]
+    return x.astype(np.float64).reshape(model.ishape), (gn[:, 0] if squeeze else gn).copy(), nit.value
+
+
 def fptr(a: np.ndarray):
     return a.ctypes.data_as(c_float_p)
 

@@ -207,7 +207,8 @@ class Blurred2D(LinOp):
         `qmm.lcg` restated).  Batched model: every plane is its own problem with its own step sizes; returns
         ``(x, grad_norm, nit)`` with ``grad_norm`` of shape ``[nit+1]`` (single image) or ``[nit+1, n_planes]``.
         ``callback(it, grad_norm, x)`` as for ``spectroSigRLSCT.cg``."""
-        return self._solve(self._L.surfh_cg_planes_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
+        return _lib.solve(self, self._L.surfh_cg_planes_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback,
+                          planes=self.n_planes, squeeze=not self.batched)
 
     # ---- instrumentation (HIP events on the plan's stream, as spectroSigRLSCT) -----------------------------
     def profile_enable(self, on=True):
@@ -244,34 +245,5 @@ class Blurred2D(LinOp):
         """Device-resident 3MG on the same criterion (`qmm.mmmg` restated for quadratic objectives) -- what the 2-D
         deconvolution driver's ``method = "qmm"`` runs (scripts/deconvolution_mrs_noRotation.py:199-212).  Same returns as
         ``cg`` except that ``grad_norm`` holds |grad| (not squared)."""
-        return self._solve(self._L.surfh_mmmg_planes_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
-
-    def _solve(self, fn, data, mu, mu_reg, x0, max_iter, tol, refresh, callback=None):
-        y = np.ascontiguousarray(np.asarray(data, dtype=np.float32).reshape(-1))
-        if y.size != self.osize:
-            raise ValueError("data size mismatch")
-        x0a = None if x0 is None else np.ascontiguousarray(np.asarray(x0, dtype=np.float32).reshape(-1))
-        if x0a is not None and x0a.size != self.isize:
-            raise ValueError("x0 size mismatch")
-        x = np.empty(self.isize, dtype=np.float32)
-        gn = np.zeros((max_iter + 1, self.n_planes), dtype=np.float64)
-        nit = C.c_int32()
-        err = []
-
-        def tramp(_user, it, gptr, xptr):
-            try:
-                g = np.ctypeslib.as_array(gptr, shape=(it + 1, self.n_planes)).copy()
-                xi = np.ctypeslib.as_array(xptr, shape=(self.isize,)).astype(np.float64).reshape(self.ishape)
-                return 1 if callback(it, g if self.batched else g[:, 0], xi) else 0
-            except BaseException as e:          # never unwind through the C frame
-                err.append(e)
-                return 1
-
-        cb = _lib.CG_CALLBACK(tramp) if callback is not None else _lib.CG_CALLBACK()
-        _lib.check(fn(self._plan, _lib.fptr(y), float(mu), float(mu_reg),
-                      _lib.fptr(x0a) if x0a is not None else None, int(max_iter), float(tol), int(refresh),
-                      _lib.fptr(x), _lib.dptr(gn), C.byref(nit), cb, None))
-        if err:
-            raise err[0]
-        gn = gn[: nit.value + 1]
-        return x.astype(np.float64).reshape(self.ishape), (gn if self.batched else gn[:, 0]).copy(), nit.value
+        return _lib.solve(self, self._L.surfh_mmmg_planes_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback,
+                          planes=self.n_planes, squeeze=not self.batched)

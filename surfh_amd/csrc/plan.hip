@@ -206,7 +206,8 @@ struct surfh_plan {
     double *dscal = nullptr, *dscratch = nullptr;   // [8] device scalars, [1024] partial sums
     double *cg_hist = nullptr;                     // device-resident r.r trace of the no-host-sync CG blocks (CG_HIST_CAP entries)
     int cg_hist_n = 0;
-    // plane-wise CG with device-resident data (surfh_cg_planes_begin_dev / _step_dev): per-plane scalars [3][Lc], the caller's iterate
+    // plane-wise CG with device-resident data (surfh_cg_planes_begin_dev / _step_dev): per-plane scalars [3][Lc] (the host-buffer
+    // plane-wise solvers use them too), the caller's iterate
     double *pl_sc = nullptr;
     float *pl_x = nullptr;
     double pl_mu = 1.0, pl_mu_reg = 0.0;
@@ -2286,6 +2287,37 @@ int surfh_residual_dev(surfh_plan *p, float *r, const float *b, const float *q, 
 
 // ---- full CG on one GPU (qmm.lcg semantics, see oracle/surfh_oracle.py:lcg) -------------------
 namespace {
+// out = Q v = mu A^T A v (+ mu_reg prior(v)): the operator of the map- and plane-domain solvers
+int normal_prior(surfh_plan *p, const float *v, float *out, double mu, double mu_reg) {
+    if (normal_dev(p, v, out, mu)) return 1;
+    if (mu_reg != 0.0) {
+        Prof pr(p, "prior_add");
+        LAUNCH_OK(prior_add(p, p->stream, v, out, p->T > 0 ? p->T : p->Lc, (float)mu_reg));
+    }
+    return 0;
+}
+// cg_b = mu A^T y, cg_q = Q x, cg_r = cg_b - cg_q; y on the device, x already holding the start
+int solver_setup(surfh_plan *p, const float *y, const float *x, double mu, double mu_reg) {
+    if (adjoint_dev(p, y, p->cg_b, false)) return 1;
+    if (mu != 1.0) LAUNCH_OK(launch_scale(p->stream, p->cg_b, p->isize, (float)mu));
+    if (normal_prior(p, x, p->cg_q, mu, mu_reg)) return 1;
+    LAUNCH_OK(launch_residual(p->stream, p->cg_r, p->cg_b, p->cg_q, p->isize));
+    return 0;
+}
+// hands the iterate x (device) after iteration `it` to the callback, if any; the work buffers hold nothing live between
+// iterations, so the callback may run forward / adjoint on this plan
+enum { CB_GO_ON = 0, CB_ERROR = 1, CB_STOP = 2 };
+int callback_iterate(surfh_plan *p, surfh_cg_callback callback, void *user, int it, const double *grad_norm, const float *x,
+                     std::vector<float> &hx) {
+    if (!callback) return CB_GO_ON;
+    hx.resize((size_t)p->isize);
+    HIP_OK(hipMemcpyAsync(hx.data(), x, p->isize * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    if (callback(user, it, grad_norm, hx.data())) return CB_STOP;
+    HIP_OK(hipSetDevice(p->dev));
+    return CB_GO_ON;
+}
+
 // The loop bench.py times, behind the exported solver: vectors = the maps' Parseval-scaled half spectra (surfh_normal_spec_dev:
 // no transform of the maps, no padding, no prior kernel inside an iteration), every scalar on the device
 // (surfh_cg_iter_nosync_dev), and the host reads the r.r trace -- the stopping test of qmm.lcg -- only every CG_CHECK iterations:
@@ -2295,8 +2327,7 @@ namespace {
 constexpr int CG_CHECK = 8;
 int cg_spectral(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol, int32_t refresh,
                 float *x, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
-    std::vector<float> hx;
-    if (callback) hx.resize((size_t)p->isize);
+    std::vector<float> hx;             // host copy of the iterate handed to the callback
     hipStream_t s = p->stream;
     const long n = p->isize, nv = 2L * p->T * p->PL;
     HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
@@ -2324,12 +2355,10 @@ int cg_spectral(surfh_plan *p, const float *y, double mu, double mu_reg, const f
         *nit = it + 1;
         if (!callback && (it + 1) % CG_CHECK != 0 && it + 1 != max_iter) continue;
         if (surfh_cg_trace(p, grad_norm, it + 2) != it + 2) return fail("CG trace read failed");     // synchronises
-        if (callback) {
-            if (surfh_from_spec_dev(p, p->cg_x, p->io_x)) return 1;
-            HIP_OK(hipMemcpyAsync(hx.data(), p->io_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
-            HIP_OK(hipStreamSynchronize(s));
-            if (callback(user, it + 1, grad_norm, hx.data())) break;
-            HIP_OK(hipSetDevice(p->dev));
+        if (callback && surfh_from_spec_dev(p, p->cg_x, p->io_x)) return 1;
+        if (const int rc = callback_iterate(p, callback, user, it + 1, grad_norm, p->io_x, hx)) {
+            if (rc == CB_STOP) break;
+            return 1;
         }
         if (std::sqrt(grad_norm[it + 1]) < (double)n * tol) break;
     }
@@ -2353,39 +2382,26 @@ int surfh_cg_cb(surfh_plan *p, const float *y, double mu, double mu_reg, const f
             return cg_spectral(p, y, mu, mu_reg, x0, max_iter, tol, refresh, x, grad_norm, nit, callback, user);
     }
     std::vector<float> hx;             // host copy of the iterate handed to the callback
-    if (callback) hx.resize((size_t)p->isize);
     hipStream_t s = p->stream;
     const long n = p->isize;
     double *rr = p->dscal + 0, *dq = p->dscal + 1, *rrn = p->dscal + 2;
-    auto Q = [&](const float *v, float *out) -> int {
-        if (normal_dev(p, v, out, mu)) return 1;
-        if (mu_reg != 0.0) {
-            Prof pr(p, "prior_add");
-            LAUNCH_OK(prior_add(p, s, v, out, p->T, (float)mu_reg));
-        }
-        return 0;
-    };
-    // b = mu A^T y
     HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
-    if (adjoint_dev(p, p->io_y, p->cg_b, false)) return 1;
-    if (mu != 1.0) LAUNCH_OK(launch_scale(s, p->cg_b, n, (float)mu));
     if (x0)
         HIP_OK(hipMemcpyAsync(p->cg_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
     else
         LAUNCH_OK(launch_fill_zero(s, p->cg_x, n));
-    if (Q(p->cg_x, p->cg_q)) return 1;
-    LAUNCH_OK(launch_residual(s, p->cg_r, p->cg_b, p->cg_q, n));
+    if (solver_setup(p, p->io_y, p->cg_x, mu, mu_reg)) return 1;
     HIP_OK(hipMemcpyAsync(p->cg_d, p->cg_r, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     LAUNCH_OK(launch_dot(s, p->cg_r, p->cg_r, n, p->dscratch, rr));
     HIP_OK(hipMemcpyAsync(&grad_norm[0], rr, sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
     *nit = 0;
     for (int it = 0; it < max_iter; ++it) {
-        if (Q(p->cg_d, p->cg_q)) return 1;
+        if (normal_prior(p, p->cg_d, p->cg_q, mu, mu_reg)) return 1;
         LAUNCH_OK(launch_dot(s, p->cg_d, p->cg_q, n, p->dscratch, dq));
         if (refresh > 0 && it % refresh == 0) {
             LAUNCH_OK(launch_cg_xupdate(s, p->cg_x, p->cg_d, n, rr, dq));
-            if (Q(p->cg_x, p->cg_q)) return 1;
+            if (normal_prior(p, p->cg_x, p->cg_q, mu, mu_reg)) return 1;
             LAUNCH_OK(launch_residual(s, p->cg_r, p->cg_b, p->cg_q, n));
             LAUNCH_OK(launch_dot(s, p->cg_r, p->cg_r, n, p->dscratch, rrn));
         } else {
@@ -2397,12 +2413,9 @@ int surfh_cg_cb(surfh_plan *p, const float *y, double mu, double mu_reg, const f
         HIP_OK(hipMemcpyAsync(&grad_norm[it + 1], rrn, sizeof(double), hipMemcpyDeviceToHost, s));
         HIP_OK(hipStreamSynchronize(s));
         *nit = it + 1;
-        if (callback) {
-            // the work buffers hold nothing live between iterations, so the callback may run forward / adjoint on this plan
-            HIP_OK(hipMemcpyAsync(hx.data(), p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
-            HIP_OK(hipStreamSynchronize(s));
-            if (callback(user, it + 1, grad_norm, hx.data())) break;
-            HIP_OK(hipSetDevice(p->dev));
+        if (const int rc = callback_iterate(p, callback, user, it + 1, grad_norm, p->cg_x, hx)) {
+            if (rc == CB_STOP) break;
+            return 1;
         }
         if (std::sqrt(grad_norm[it + 1]) < (double)n * tol) break;
     }
@@ -2432,32 +2445,20 @@ int surfh_mmmg(surfh_plan *p, const float *y, double mu, double mu_reg, const fl
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
     if (p->T <= 0) return fail("surfh_mmmg needs templates (the priors act on abundance maps)");
     std::vector<float> hx;
-    if (callback) hx.resize((size_t)p->isize);
     HIP_OK(hipSetDevice(p->dev));
     if (ensure_cg(p)) return 1;
     if (!p->cg_qm && (dev_alloc(&p->cg_qm, (size_t)p->isize) || dev_alloc(&p->cg_dd, (size_t)p->isize))) return 1;
     hipStream_t s = p->stream;
     const long n = p->isize;
     float *r = p->cg_r, *m = p->cg_d, *d = p->cg_dd, *qd = p->cg_q, *qm = p->cg_qm;
-    auto Q = [&](const float *v, float *out) -> int {
-        if (normal_dev(p, v, out, mu)) return 1;
-        if (mu_reg != 0.0) {
-            Prof pr(p, "prior_add");
-            LAUNCH_OK(prior_add(p, s, v, out, p->T, (float)mu_reg));
-        }
-        return 0;
-    };
     HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
-    if (adjoint_dev(p, p->io_y, p->cg_b, false)) return 1;
-    if (mu != 1.0) LAUNCH_OK(launch_scale(s, p->cg_b, n, (float)mu));
     if (x0)
         HIP_OK(hipMemcpyAsync(p->cg_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
     else
         LAUNCH_OK(launch_fill_zero(s, p->cg_x, n));
     LAUNCH_OK(launch_fill_zero(s, m, n));
     LAUNCH_OK(launch_fill_zero(s, qm, n));
-    if (Q(p->cg_x, qd)) return 1;
-    LAUNCH_OK(launch_residual(s, r, p->cg_b, qd, n));
+    if (solver_setup(p, p->io_y, p->cg_x, mu, mu_reg)) return 1;
     double h[6];
     *nit = 0;
     for (int it = 0;; ++it) {
@@ -2468,16 +2469,14 @@ int surfh_mmmg(surfh_plan *p, const float *y, double mu, double mu_reg, const fl
         HIP_OK(hipMemcpyAsync(h, p->dscal, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
         HIP_OK(hipStreamSynchronize(s));
         grad_norm[it] = std::sqrt(h[0]);
-        if (it > 0 && callback) {
-            HIP_OK(hipMemcpyAsync(hx.data(), p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
-            HIP_OK(hipStreamSynchronize(s));
-            if (callback(user, it, grad_norm, hx.data())) break;
-            HIP_OK(hipSetDevice(p->dev));
+        if (const int rc = it > 0 ? callback_iterate(p, callback, user, it, grad_norm, p->cg_x, hx) : CB_GO_ON) {
+            if (rc == CB_STOP) break;
+            return 1;
         }
         if (it >= max_iter || grad_norm[it] < (double)n * tol) break;
         const double mQm = h[2], beta = mQm > 0.0 ? -h[1] / mQm : 0.0;
         LAUNCH_OK(launch_lincomb(s, d, r, m, n, beta));
-        if (Q(d, qd)) return 1;
+        if (normal_prior(p, d, qd, mu, mu_reg)) return 1;
         LAUNCH_OK(launch_dot(s, d, qd, n, p->dscratch, p->dscal + 3));
         LAUNCH_OK(launch_dot(s, d, qm, n, p->dscratch, p->dscal + 4));
         LAUNCH_OK(launch_dot(s, d, r, n, p->dscratch, p->dscal + 5));
@@ -2500,7 +2499,7 @@ int surfh_mmmg(surfh_plan *p, const float *y, double mu, double mu_reg, const fl
             LAUNCH_OK(launch_mmmg_update(s, p->cg_x, r, d, m, qm, qd, n, s0, s1, fresh ? 0 : 1));
         }
         if (fresh) {
-            if (Q(p->cg_x, qd)) return 1;
+            if (normal_prior(p, p->cg_x, qd, mu, mu_reg)) return 1;
             LAUNCH_OK(launch_residual(s, r, p->cg_b, qd, n));
         }
         *nit = it + 1;
@@ -2511,11 +2510,31 @@ int surfh_mmmg(surfh_plan *p, const float *y, double mu, double mu_reg, const fl
 }
 
 // ---- CG on independent planes: the 2-D deconvolution path (criterion_2D.py:60-250 per image, batched over wavelength)
+namespace {
+// one iteration of qmm.lcg on every plane at once, on the plan's cg_d / cg_q / cg_r / cg_b and the iterate x; rr, dq, rrn are
+// [L] device scalars, rr = r.r per plane on entry and on return.  The residual is recomputed from scratch when refresh divides it.
+int cg_planes_iter(surfh_plan *p, float *x, double mu, double mu_reg, int it, int refresh, double *rr, double *dq, double *rrn) {
+    hipStream_t s = p->stream;
+    const int L = p->Lc;
+    const long npix = (long)p->Na * p->Nb;
+    if (normal_prior(p, p->cg_d, p->cg_q, mu, mu_reg)) return 1;
+    LAUNCH_OK(launch_dot_planes(s, p->cg_d, p->cg_q, L, npix, dq));
+    if (refresh > 0 && it % refresh == 0) {
+        LAUNCH_OK(launch_cg_step_planes(s, x, p->cg_r, p->cg_d, p->cg_q, L, npix, rr, dq, rrn, 0));
+        if (normal_prior(p, x, p->cg_q, mu, mu_reg)) return 1;
+        LAUNCH_OK(launch_residual(s, p->cg_r, p->cg_b, p->cg_q, p->isize));
+        LAUNCH_OK(launch_dot_planes(s, p->cg_r, p->cg_r, L, npix, rrn));
+    } else {
+        LAUNCH_OK(launch_cg_step_planes(s, x, p->cg_r, p->cg_d, p->cg_q, L, npix, rr, dq, rrn, 1));
+    }
+    LAUNCH_OK(launch_cg_dir_planes(s, p->cg_d, p->cg_r, L, npix, rrn, rr));      // also rr = rr'
+    return 0;
+}
+}  // namespace
+
 int surfh_cg_planes_cb(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
                        int32_t refresh, float *x, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
-    std::vector<float> hx;             // host copy of the iterate handed to the callback
-    if (callback) hx.resize((size_t)p->isize);
     if (p->T != 0) return fail("surfh_cg_planes is the solver of the plane-wise (no template) model; use surfh_cg with templates");
     if (p->ch.empty()) return fail("plan has no channel");
     HIP_OK(hipSetDevice(p->dev));
@@ -2523,62 +2542,38 @@ int surfh_cg_planes_cb(surfh_plan *p, const float *y, double mu, double mu_reg, 
     hipStream_t s = p->stream;
     const int L = p->Lc;
     const long npix = (long)p->Na * p->Nb, n = p->isize;
-    double *sc = nullptr;              // [3][L]: rr, dq, rr'
-    HIP_OK(hipMalloc((void **)&sc, (size_t)3 * L * sizeof(double)));
-    double *rr = sc, *dq = sc + L, *rrn = sc + 2 * L;
-    auto done = [&](int rc) { hipFree(sc); return rc; };
-    auto Q = [&](const float *v, float *out) -> int {
-        if (normal_dev(p, v, out, mu)) return 1;
-        if (mu_reg != 0.0) LAUNCH_OK(prior_add(p, s, v, out, L, (float)mu_reg));
-        return 0;
-    };
-    if (hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess) return done(fail("copy failed"));
-    if (adjoint_dev(p, p->io_y, p->cg_b, false)) return done(1);
-    int rc = 0;
-    if (mu != 1.0) rc = launch_scale(s, p->cg_b, n, (float)mu);
-    if (!rc) rc = x0 ? (int)hipMemcpyAsync(p->cg_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s) : launch_fill_zero(s, p->cg_x, n);
-    if (rc) return done(fail("cg setup failed"));
-    if (Q(p->cg_x, p->cg_q)) return done(1);
-    rc = launch_residual(s, p->cg_r, p->cg_b, p->cg_q, n);
-    if (!rc) rc = (int)hipMemcpyAsync(p->cg_d, p->cg_r, n * sizeof(float), hipMemcpyDeviceToDevice, s);
-    if (!rc) rc = launch_dot_planes(s, p->cg_r, p->cg_r, L, npix, rr);
-    if (!rc) rc = (int)hipMemcpyAsync(grad_norm, rr, L * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (!rc) rc = (int)hipStreamSynchronize(s);
-    if (rc) return done(fail("cg setup failed: %s", hipGetErrorString((hipError_t)rc)));
+    if (!p->pl_sc && dev_alloc(&p->pl_sc, (size_t)3 * L)) return 1;
+    double *rr = p->pl_sc, *dq = p->pl_sc + L, *rrn = p->pl_sc + 2 * L;
+    std::vector<float> hx;             // host copy of the iterate handed to the callback
+    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
+    if (x0)
+        HIP_OK(hipMemcpyAsync(p->cg_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
+    else
+        LAUNCH_OK(launch_fill_zero(s, p->cg_x, n));
+    if (solver_setup(p, p->io_y, p->cg_x, mu, mu_reg)) return 1;
+    HIP_OK(hipMemcpyAsync(p->cg_d, p->cg_r, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    LAUNCH_OK(launch_dot_planes(s, p->cg_r, p->cg_r, L, npix, rr));
+    HIP_OK(hipMemcpyAsync(grad_norm, rr, L * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
     *nit = 0;
     for (int it = 0; it < max_iter; ++it) {
-        if (Q(p->cg_d, p->cg_q)) return done(1);
-        rc = launch_dot_planes(s, p->cg_d, p->cg_q, L, npix, dq);
-        if (!rc && refresh > 0 && it % refresh == 0) {     // residual recomputed from scratch (qmm.lcg restated, see surfh_cg)
-            rc = launch_cg_step_planes(s, p->cg_x, p->cg_r, p->cg_d, p->cg_q, L, npix, rr, dq, rrn, 0);
-            if (rc) return done(fail("launch failed"));
-            if (Q(p->cg_x, p->cg_q)) return done(1);
-            rc = launch_residual(s, p->cg_r, p->cg_b, p->cg_q, n);
-            if (!rc) rc = launch_dot_planes(s, p->cg_r, p->cg_r, L, npix, rrn);
-        } else if (!rc) {
-            rc = launch_cg_step_planes(s, p->cg_x, p->cg_r, p->cg_d, p->cg_q, L, npix, rr, dq, rrn, 1);
-        }
-        if (!rc) rc = launch_cg_dir_planes(s, p->cg_d, p->cg_r, L, npix, rrn, rr);
+        if (cg_planes_iter(p, p->cg_x, mu, mu_reg, it, refresh, rr, dq, rrn)) return 1;
         double *gn = grad_norm + (size_t)(it + 1) * L;
-        if (!rc) rc = (int)hipMemcpyAsync(gn, rr, L * sizeof(double), hipMemcpyDeviceToHost, s);
-        if (!rc) rc = (int)hipStreamSynchronize(s);
-        if (rc) return done(fail("cg iteration failed: %s", hipGetErrorString((hipError_t)rc)));
+        HIP_OK(hipMemcpyAsync(gn, rr, L * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
         *nit = it + 1;
-        if (callback) {      // qmm.lcg's per-iteration callback (criterion_2D.py:163-225): trace so far [it + 2][L], current iterate
-            if (hipMemcpyAsync(hx.data(), p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess)
-                return done(fail("copy failed"));
-            if (callback(user, it + 1, grad_norm, hx.data())) break;
-            if (hipSetDevice(p->dev) != hipSuccess) return done(fail("hipSetDevice failed"));
+        // qmm.lcg's per-iteration callback (criterion_2D.py:163-225): trace so far [it + 2][L], current iterate
+        if (const int rc = callback_iterate(p, callback, user, it + 1, grad_norm, p->cg_x, hx)) {
+            if (rc == CB_STOP) break;
+            return 1;
         }
         double worst = 0.0;
         for (int l = 0; l < L; ++l) worst = std::max(worst, gn[l]);
         if (std::sqrt(worst) < (double)npix * tol) break;
     }
-    rc = (int)hipMemcpyAsync(x, p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s);
-    if (!rc) rc = (int)hipStreamSynchronize(s);
-    if (rc) return done(fail("copy failed"));
-    return done(0);
+    HIP_OK(hipMemcpyAsync(x, p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return 0;
 }
 
 int surfh_cg_planes(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
@@ -2656,16 +2651,11 @@ int surfh_cg_planes_begin_dev(surfh_plan *p, const float *y_dev, double mu, doub
         return 0;
     }
     if (ensure_cg(p)) return 1;
-    const long npix = (long)p->Na * p->Nb, n = p->isize;
-    if (!p->pl_sc) HIP_OK(hipMalloc((void **)&p->pl_sc, (size_t)3 * L * sizeof(double)));
+    if (!p->pl_sc && dev_alloc(&p->pl_sc, (size_t)3 * L)) return 1;
     p->pl_x = x_dev; p->pl_mu = mu; p->pl_mu_reg = mu_reg; p->pl_it = 0;
-    if (adjoint_dev(p, y_dev, p->cg_b, false)) return 1;
-    if (mu != 1.0) LAUNCH_OK(launch_scale(s, p->cg_b, n, (float)mu));
-    if (normal_dev(p, x_dev, p->cg_q, mu)) return 1;
-    if (mu_reg != 0.0) LAUNCH_OK(prior_add(p, s, x_dev, p->cg_q, L, (float)mu_reg));
-    LAUNCH_OK(launch_residual(s, p->cg_r, p->cg_b, p->cg_q, n));
-    HIP_OK(hipMemcpyAsync(p->cg_d, p->cg_r, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    LAUNCH_OK(launch_dot_planes(s, p->cg_r, p->cg_r, L, npix, p->pl_sc));
+    if (solver_setup(p, y_dev, x_dev, mu, mu_reg)) return 1;
+    HIP_OK(hipMemcpyAsync(p->cg_d, p->cg_r, p->isize * sizeof(float), hipMemcpyDeviceToDevice, s));
+    LAUNCH_OK(launch_dot_planes(s, p->cg_r, p->cg_r, L, (long)p->Na * p->Nb, p->pl_sc));
     return 0;
 }
 int surfh_cg_planes_step_dev(surfh_plan *p, int32_t iters, int32_t refresh) {
@@ -2697,31 +2687,12 @@ int surfh_cg_planes_step_dev(surfh_plan *p, int32_t iters, int32_t refresh) {
         LAUNCH_OK(launch_cube_from_lam_inner(s, xn, p->pl_x, 0, L, p->Na, p->Nb, p->NAP, p->LP));      // the caller's iterate
         return 0;
     }
-    const long npix = (long)p->Na * p->Nb, n = p->isize;
-    double *rr = p->pl_sc, *dq = p->pl_sc + L, *rrn = p->pl_sc + 2 * L;
-    float *x = p->pl_x;
-    auto Q = [&](const float *v, float *out) -> int {
-        if (normal_dev(p, v, out, p->pl_mu)) return 1;
-        if (p->pl_mu_reg != 0.0) LAUNCH_OK(prior_add(p, s, v, out, L, (float)p->pl_mu_reg));
-        return 0;
-    };
-    for (int i = 0; i < iters; ++i, ++p->pl_it) {
-        if (Q(p->cg_d, p->cg_q)) return 1;
-        LAUNCH_OK(launch_dot_planes(s, p->cg_d, p->cg_q, L, npix, dq));
-        if (refresh > 0 && p->pl_it % refresh == 0) {
-            LAUNCH_OK(launch_cg_step_planes(s, x, p->cg_r, p->cg_d, p->cg_q, L, npix, rr, dq, rrn, 0));
-            if (Q(x, p->cg_q)) return 1;
-            LAUNCH_OK(launch_residual(s, p->cg_r, p->cg_b, p->cg_q, n));
-            LAUNCH_OK(launch_dot_planes(s, p->cg_r, p->cg_r, L, npix, rrn));
-        } else {
-            LAUNCH_OK(launch_cg_step_planes(s, x, p->cg_r, p->cg_d, p->cg_q, L, npix, rr, dq, rrn, 1));
-        }
-        LAUNCH_OK(launch_cg_dir_planes(s, p->cg_d, p->cg_r, L, npix, rrn, rr));      // also rr = rr'
-    }
+    for (int i = 0; i < iters; ++i, ++p->pl_it)
+        if (cg_planes_iter(p, p->pl_x, p->pl_mu, p->pl_mu_reg, p->pl_it, refresh, p->pl_sc, p->pl_sc + L, p->pl_sc + 2 * L)) return 1;
     return 0;
 }
 int surfh_cg_planes_rr(surfh_plan *p, double *rr_host) {
-    if (!p || !rr_host || !(p->pn_active ? p->pn_sc : p->pl_sc)) return fail("surfh_cg_planes_begin_dev has not been called");
+    if (!p || !rr_host || !p->pl_x || !(p->pn_active ? p->pn_sc : p->pl_sc)) return fail("surfh_cg_planes_begin_dev has not been called");
     HIP_OK(hipSetDevice(p->dev));
     HIP_OK(hipMemcpyAsync(rr_host, p->pn_active ? p->pn_sc : p->pl_sc, (size_t)p->Lc * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     HIP_OK(hipStreamSynchronize(p->stream));
@@ -2733,8 +2704,6 @@ int surfh_cg_planes_rr(surfh_plan *p, double *rr_host) {
 int surfh_mmmg_planes_cb(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
                          int32_t refresh, float *x, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
-    std::vector<float> hx;
-    if (callback) hx.resize((size_t)p->isize);
     if (p->T != 0) return fail("surfh_mmmg_planes is the solver of the plane-wise (no template) model; use surfh_mmmg with templates");
     if (p->ch.empty()) return fail("plan has no channel");
     HIP_OK(hipSetDevice(p->dev));
@@ -2744,61 +2713,45 @@ int surfh_mmmg_planes_cb(surfh_plan *p, const float *y, double mu, double mu_reg
     const int L = p->Lc;
     const long npix = (long)p->Na * p->Nb, n = p->isize;
     float *r = p->cg_r, *m = p->cg_d, *d = p->cg_dd, *qd = p->cg_q, *qm = p->cg_qm;
-    double *sc = nullptr;              // [2][L]: r.r, m.Qm
-    HIP_OK(hipMalloc((void **)&sc, (size_t)2 * L * sizeof(double)));
-    double *rr = sc, *mqm = sc + L;
-    auto done = [&](int rc) { hipFree(sc); return rc; };
-    auto Q = [&](const float *v, float *out) -> int {
-        if (normal_dev(p, v, out, mu)) return 1;
-        if (mu_reg != 0.0) LAUNCH_OK(prior_add(p, s, v, out, L, (float)mu_reg));
-        return 0;
-    };
-    if (hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess) return done(fail("copy failed"));
-    if (adjoint_dev(p, p->io_y, p->cg_b, false)) return done(1);
-    int rc = 0;
-    if (mu != 1.0) rc = launch_scale(s, p->cg_b, n, (float)mu);
-    if (!rc) rc = x0 ? (int)hipMemcpyAsync(p->cg_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s) : launch_fill_zero(s, p->cg_x, n);
-    if (!rc) rc = launch_fill_zero(s, m, n);
-    if (!rc) rc = launch_fill_zero(s, qm, n);
-    if (rc) return done(fail("3MG setup failed"));
-    if (Q(p->cg_x, qd)) return done(1);
-    rc = launch_residual(s, r, p->cg_b, qd, n);
-    if (rc) return done(fail("3MG setup failed"));
+    if (!p->pl_sc && dev_alloc(&p->pl_sc, (size_t)3 * L)) return 1;
+    double *rr = p->pl_sc, *mqm = p->pl_sc + L;
+    std::vector<float> hx;
+    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
+    if (x0)
+        HIP_OK(hipMemcpyAsync(p->cg_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
+    else
+        LAUNCH_OK(launch_fill_zero(s, p->cg_x, n));
+    LAUNCH_OK(launch_fill_zero(s, m, n));
+    LAUNCH_OK(launch_fill_zero(s, qm, n));
+    if (solver_setup(p, p->io_y, p->cg_x, mu, mu_reg)) return 1;
     *nit = 0;
     for (int it = 0;; ++it) {
-        rc = launch_mmmg_dir_planes(s, d, r, m, qm, L, npix, rr, mqm);
+        LAUNCH_OK(launch_mmmg_dir_planes(s, d, r, m, qm, L, npix, rr, mqm));
         double *gn = grad_norm + (size_t)it * L;
-        if (!rc) rc = (int)hipMemcpyAsync(gn, rr, L * sizeof(double), hipMemcpyDeviceToHost, s);
-        if (!rc) rc = (int)hipStreamSynchronize(s);
-        if (rc) return done(fail("3MG iteration failed: %s", hipGetErrorString((hipError_t)rc)));
+        HIP_OK(hipMemcpyAsync(gn, rr, L * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
         double worst = 0.0;
         for (int l = 0; l < L; ++l) {
             gn[l] = std::sqrt(gn[l]);
             worst = std::max(worst, gn[l]);
         }
-        if (it > 0 && callback) {
-            if (hipMemcpyAsync(hx.data(), p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess)
-                return done(fail("copy failed"));
-            if (callback(user, it, grad_norm, hx.data())) break;
-            if (hipSetDevice(p->dev) != hipSuccess) return done(fail("hipSetDevice failed"));
+        if (const int rc = it > 0 ? callback_iterate(p, callback, user, it, grad_norm, p->cg_x, hx) : CB_GO_ON) {
+            if (rc == CB_STOP) break;
+            return 1;
         }
         if (it >= max_iter || worst < (double)npix * tol) break;
-        if (Q(d, qd)) return done(1);
+        if (normal_prior(p, d, qd, mu, mu_reg)) return 1;
         const bool fresh = refresh > 0 && it % refresh == 0;
-        rc = launch_mmmg_step_planes(s, p->cg_x, r, d, m, qm, qd, L, npix, mqm, fresh ? 0 : 1);
-        if (rc) return done(fail("launch failed"));
+        LAUNCH_OK(launch_mmmg_step_planes(s, p->cg_x, r, d, m, qm, qd, L, npix, mqm, fresh ? 0 : 1));
         if (fresh) {
-            if (Q(p->cg_x, qd)) return done(1);
-            rc = launch_residual(s, r, p->cg_b, qd, n);
-            if (rc) return done(fail("launch failed"));
+            if (normal_prior(p, p->cg_x, qd, mu, mu_reg)) return 1;
+            LAUNCH_OK(launch_residual(s, r, p->cg_b, qd, n));
         }
         *nit = it + 1;
     }
-    rc = (int)hipMemcpyAsync(x, p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s);
-    if (!rc) rc = (int)hipStreamSynchronize(s);
-    if (rc) return done(fail("copy failed"));
-    return done(0);
+    HIP_OK(hipMemcpyAsync(x, p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return 0;
 }
 
 int surfh_mmmg_planes(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,

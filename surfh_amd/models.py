@@ -320,39 +320,12 @@ class spectroSigRLSCT(LinOp):
         """Device-resident linear CG (qmm.lcg restated).  ``callback(it, grad_norm, x)`` -- the per-iteration callback
         of ``qmm.lcg`` (fusion_CT.py:194-225) -- receives the 1-based iteration, the grad_norm trace so far and the
         current iterate ``[T,Na,Nb]``; it may call ``forward`` / ``adjoint`` on this model; a truthy return stops."""
-        return self._solve(self._L.surfh_cg_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
+        return _lib.solve(self, self._L.surfh_cg_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
 
     def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None):
         """Device-resident 3MG (qmm.mmmg restated for quadratic objectives; the reference's ``method='mmmg'``,
         fusion_CT.py:194-198).  Same arguments as ``cg``; ``grad_norm`` holds |grad| (not squared) of every iterate."""
-        return self._solve(self._L.surfh_mmmg, data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
-
-    def _solve(self, fn, data, mu, mu_reg, x0, max_iter, tol, refresh, callback):
-        y = np.ascontiguousarray(np.asarray(data, dtype=np.float32).reshape(-1))
-        if y.size != self.osize:
-            raise ValueError("data size mismatch")
-        x0a = None if x0 is None else np.ascontiguousarray(np.asarray(x0, dtype=np.float32).reshape(-1))
-        x = np.empty(self.isize, dtype=np.float32)
-        gn = np.zeros(max_iter + 1, dtype=np.float64)
-        nit = C.c_int32()
-        err = []
-
-        def tramp(_user, it, gptr, xptr):
-            try:
-                g = np.ctypeslib.as_array(gptr, shape=(it + 1,)).copy()
-                xi = np.ctypeslib.as_array(xptr, shape=(self.isize,)).astype(np.float64).reshape(self.ishape)
-                return 1 if callback(it, g, xi) else 0
-            except BaseException as e:          # never unwind through the C frame
-                err.append(e)
-                return 1
-
-        cb = _lib.CG_CALLBACK(tramp) if callback is not None else _lib.CG_CALLBACK()
-        _lib.check(fn(self._plan, _lib.fptr(y), float(mu), float(mu_reg),
-                                       _lib.fptr(x0a) if x0a is not None else None, int(max_iter), float(tol),
-                                       int(refresh), _lib.fptr(x), _lib.dptr(gn), C.byref(nit), cb, None))
-        if err:
-            raise err[0]
-        return x.astype(np.float64).reshape(self.ishape), gn[: nit.value + 1].copy(), nit.value
+        return _lib.solve(self, self._L.surfh_mmmg, data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
 
     # ---- helpers the reference's drivers call -----------------------------------------------
     def cubeTomaps(self, cube):

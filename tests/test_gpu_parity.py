@@ -458,6 +458,8 @@ def test_error_behaviour():
         m.forward(np.zeros((3, 64, 64)))
     with pytest.raises(ValueError, match="size"):
         m.cg(np.zeros(7), max_iter=1)
+    with pytest.raises(ValueError, match="size"):
+        m.cg(np.zeros(m.osize), x0=np.zeros(7), max_iter=1)
     m.close()
     far = copy.deepcopy(cfg)
     far["pointings"] = [[(a + 40 * problems.STEP_DEG, b) for a, b in far["pointings"][0]]]
