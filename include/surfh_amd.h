@@ -325,6 +325,25 @@ int surfh_shepard(int32_t n_seg, const int64_t *pt_off, const float *pt_alpha, c
                   int32_t device_ptrs, void *stream, float *kernel_ms);
 const char *surfh_shepard_last_error(void);
 
+/* ---- spectral templates (the reference's template notebooks: scipy.ndimage.median_filter(cube, size, axes=[0]) and
+ * sklearn.decomposition.NMF(solver="cd", beta_loss="frobenius", shuffle=False), sklearn 1.7) ----
+ * surfh_spectral_median: dst = the median along axis 0 of the C-order host array src [L][C], size 1..63, mode 0 reflect,
+ * 1 nearest, 2 mirror.  The window and rank are scipy's (origin 0, rank size / 2), for any size, also size > L.
+ * surfh_nmf_cd: n_models coordinate-descent NMF models of one host X [P][L], run together.  Model m has K[m] components;
+ * W holds the models' [P][K[m]] blocks one after the other, H their [K[m]][L] blocks; both are the initial values on
+ * entry and the results on return.  max_iter >= 1 iterations at most; model m stops after the iteration at which its
+ * violation / violation of iteration 1 <= tol (or that is 0), n_iter[m] being that iteration.  Optional outputs:
+ * violation_trace [n_models][max_iter] (0 past n_iter), recon_err[m] = ||X - W H||_F and mre[m] = the mean over all
+ * entries of (X - W H) / X, 0 where X == 0 (both float64), ms_per_iter = device time per queued iteration.
+ * Results are deterministic and do not depend on which other models share the call.
+ * Both return 0, or non-zero with the message in surfh_templates_last_error().                                       */
+int surfh_spectral_median(const float *src, float *dst, int64_t L, int64_t C, int32_t size, int32_t mode,
+                          int32_t device);
+int surfh_nmf_cd(const float *X, int64_t P, int64_t L, int32_t n_models, const int32_t *K, float *W, float *H,
+                 int32_t max_iter, double tol, int32_t *n_iter, double *violation_trace, double *recon_err, double *mre,
+                 int32_t device, float *ms_per_iter);
+const char *surfh_templates_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,7 +55,7 @@ EXPORTS = [
     "surfh_cg_begin_dev", "surfh_cg_iter_nosync_dev", "surfh_cg_xupdate_nosync_dev", "surfh_cg_refresh_nosync_dev", "surfh_cg_trace",
     "surfh_profile_enable", "surfh_profile_filter", "surfh_profile_count", "surfh_profile_get", "surfh_profile_reset", "surfh_debug_copy",
     "surfh_debug_dims", "surfh_gemm_selftest", "surfh_gemm_selftest_ksteps", "surfh_klist_classify",
-    "surfh_shepard", "surfh_shepard_last_error",
+    "surfh_shepard", "surfh_shepard_last_error", "surfh_spectral_median", "surfh_nmf_cd", "surfh_templates_last_error",
 ]
 
 _lib = None
@@ -141,6 +141,10 @@ def load():
                                 c_float_p, c_float_p, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, C.c_int32, vp,
                                 c_float_p]
     L.surfh_shepard_last_error.restype = C.c_char_p
+    L.surfh_spectral_median.argtypes = [c_float_p, c_float_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32]
+    L.surfh_nmf_cd.argtypes = [c_float_p, C.c_int64, C.c_int64, C.c_int32, c_int32_p, c_float_p, c_float_p, C.c_int32,
+                               C.c_double, c_int32_p, c_double_p, c_double_p, c_double_p, C.c_int32, c_float_p]
+    L.surfh_templates_last_error.restype = C.c_char_p
     _lib = L
     return L
 

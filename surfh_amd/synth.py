@@ -198,3 +198,42 @@ def synthetic_mrs_exposure(band: str = "1a", n_rows: int = 1024, n_slit: int = N
     data[~on] = np.nan
     return dict(data=data, alpha=alpha, beta=beta, lam=lam, detector2world=detector2world, scene=scene,
                 wavelengths=wl, n_slit=n_slit, ra=ra, dec=dec)
+
+
+def synthetic_template_cube(n_lambda: int = 256, ny: int = 23, nx: int = 30, n_templates: int = 4, noise: float = 0.0,
+                            nan_fraction: float = 0.0, seed: int = 0, wavel=None) -> dict:
+    """A non-negative cube ``sum_k abundance_k(y, x) template_k(lambda)`` for the template extraction
+    (surfh_amd.templates, scripts/make_templates.py).
+
+    The first four spectra are ``templates(n_lambda)`` (linear ramps), further ones Gaussian emission lines on a small
+    continuum; the abundances are smooth non-negative blobs.  ``noise``: standard deviation of additive Gaussian noise,
+    relative to the cube's mean (the result is clipped at 0); ``nan_fraction``: share of spatial pixels set to NaN at
+    every wavelength.  Returns a dict: cube [n_lambda, ny, nx] float32, wavel [n_lambda], templates [n_templates,
+    n_lambda], abundances [n_templates, ny, nx]."""
+    rng = np.random.default_rng(seed)
+    lam = np.arange(n_lambda, dtype=np.float64)
+    base = templates(n_lambda)
+    spectra = []
+    for k in range(n_templates):
+        if k < 4:
+            spectra.append(base[k])
+        else:
+            c = (0.15 + 0.7 * rng.random()) * n_lambda
+            spectra.append(2.0 + 40.0 * np.exp(-0.5 * ((lam - c) / (0.02 * n_lambda + 1.0)) ** 2))
+    tpl = np.stack(spectra)
+    yy, xx = np.mgrid[0:ny, 0:nx].astype(np.float64)
+    ab = np.empty((n_templates, ny, nx))
+    for k in range(n_templates):
+        cy, cx = rng.random() * ny, rng.random() * nx
+        s = (0.2 + 0.3 * rng.random()) * max(ny, nx)
+        ab[k] = 0.05 + np.exp(-0.5 * (((yy - cy) ** 2 + (xx - cx) ** 2) / s ** 2))
+    cube = np.einsum("kl,kyx->lyx", tpl, ab)
+    if noise > 0:
+        cube = np.maximum(cube + noise * cube.mean() * rng.standard_normal(cube.shape), 0.0)
+    cube = cube.astype(np.float32)
+    if nan_fraction > 0:
+        mask = rng.random((ny, nx)) < nan_fraction
+        cube[:, mask] = np.nan
+    if wavel is None:
+        wavel = np.linspace(4.90, 28.70, n_lambda)
+    return {"cube": cube, "wavel": np.asarray(wavel, dtype=np.float64), "templates": tpl, "abundances": ab}
