@@ -171,6 +171,26 @@ int surfh_cg_cb(surfh_plan *plan, const float *y, double mu, double mu_reg, cons
 int surfh_mmmg(surfh_plan *plan, const float *y, double mu, double mu_reg, const float *x0,
                int32_t max_iter, double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit,
                surfh_cg_callback callback, void *user);
+/* 3MG with edge-preserving Huber priors on the separated circular first differences (the reference's lmm_reconstruction,
+ * surfh/ToolsDir/algorithms.py:73-106: qmm.mmmg with qmm.Huber(delta) on the row and column differences).  Minimises
+ *   J(x) = mu |y - A x|^2 / 2 + mu_reg sum_{k in r,c} sum_pixels phi(D_k x),
+ *   phi(u) = u^2 / 2 for |u| <= delta, delta (|u| - delta / 2) beyond;
+ * each iteration minimises the half-quadratic (Geman-Reynolds) majorant of J at x, weights w(u) = phi'(u) / u, over
+ * span{-gradient, previous move}.  delta = +inf is the quadratic criterion of surfh_mmmg (whatever surfh_set_prior holds,
+ * the separated differences are used).  Contract of surfh_mmmg otherwise: grad_norm receives |gradient| of x0 and of every
+ * iterate, the loop stops below size*tol, the data gradient is carried and recomputed every `refresh` iterations; callback
+ * as surfh_cg_cb.  prior_value (may be NULL) receives sum_k sum phi(D_k x) of the returned iterate.  The kernels work in fp32:
+ * fails on delta below FLT_MIN (delta <= 0 included), a NaN delta or mu_reg, and on non-positive curvature.  Template plans
+ * only. */
+int surfh_mmmg_huber(surfh_plan *plan, const float *y, double mu, double mu_reg, double delta, const float *x0,
+                     int32_t max_iter, double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit,
+                     double *prior_value, surfh_cg_callback callback, void *user);
+/* the Huber prior alone, on device maps [T][Na][Nb]: g += mu_reg sum_k D_k^T phi'(D_k x); *value_host = sum_k sum phi(D_k x)
+ * (float64 sums in a fixed order: repeated calls give the same bits).  Same delta rules as surfh_mmmg_huber. */
+int surfh_huber_prior_dev(surfh_plan *plan, const float *x_dev, float *g_dev, double mu_reg, double delta, double *value_host);
+/* the prior block of the majorant: sums_host[0..2] = sum_k sum w(D_k x) (D_k p0)^2, (D_k p0)(D_k p1), (D_k p1)^2, the weights
+ * w(u) = phi'(u) / u recomputed from x (same summation rules) */
+int surfh_huber_curv_dev(surfh_plan *plan, const float *x_dev, const float *p0_dev, const float *p1_dev, double delta, double *sums_host);
 
 /* ---- linear mixing model on the device: the drivers' mapsToCube / cubeTomaps
  * (spectroModel.py:187-198, jax_utils.py:10-26).  templates [T][Lc] float64 as in surfh_config,

@@ -110,22 +110,26 @@ def create_model(sotf, templates, origin_alpha_axis, origin_beta_axis, wavel_axi
                            instrs=list(instruments.values()), step_degree=step_angle, pointings=pointings, device=device)
 
 
-def result_dir_name(method, n_channels, n_templates, niter, hyper_parameter, scale_data):
-    """main_fusion.py:182."""
-    return f'{method}_MC_{n_channels}_MO_4_Temp_{n_templates}_nit_{str(niter)}_mu_{str("{:.2e}".format(hyper_parameter))}_SD_{scale_data}/'
+def result_dir_name(method, n_channels, n_templates, niter, hyper_parameter, scale_data, delta=None):
+    """main_fusion.py:182; with a Huber threshold `delta` (not in the reference) `_huber_<delta>` is appended."""
+    name = f'{method}_MC_{n_channels}_MO_4_Temp_{n_templates}_nit_{str(niter)}_mu_{str("{:.2e}".format(hyper_parameter))}_SD_{scale_data}'
+    if delta is not None:
+        name += f'_huber_{delta:.2e}'
+    return name + '/'
 
 
 def reconstruction_method(spectro_model, ndata, templates, result_path, hyper_parameter, niter, method, scale_data,
-                          checkpoint_every=0, resume=None):
+                          checkpoint_every=0, resume=None, delta=None):
     """main_fusion.py:162-206: regularised least squares by CG, then the three result files.  Not in the reference:
     `checkpoint_every` > 0 writes the iterate to checkpoint.npz in the result directory every that many iterations,
-    `resume` (such a file) warm-starts from it and runs the iterations that are left."""
+    `resume` (such a file) warm-starts from it and runs the iterations that are left; `delta` replaces the quadratic
+    priors by Huber potentials of that threshold (3MG only)."""
     value_init = 0
     path = pathlib.Path(result_path) / result_dir_name(method, len(spectro_model.instrs), templates.shape[0], niter,
-                                                       hyper_parameter, scale_data)
+                                                       hyper_parameter, scale_data, delta)
     path.mkdir(parents=True, exist_ok=True)
     crit = QuadCriterion_MRS(mu_spectro=1, y_spectro=np.copy(ndata), model_spectro=spectro_model,
-                             mu_reg=hyper_parameter, printing=True, gradient="separated")
+                             mu_reg=hyper_parameter, printing=True, gradient="separated", delta=delta)
     if resume:
         from surfh_amd.fusion import load_checkpoint
         x_saved, it_done, _ = load_checkpoint(resume)
@@ -168,10 +172,17 @@ def synthetic_problem(name, npix):
 @click.option('--device', default=0, type=int, help='GPU index.')
 @click.option('--checkpoint_every', default=0, type=int, help='Write the iterate to checkpoint.npz every that many iterations (0: never).')
 @click.option('--resume', default=None, type=str, help='checkpoint.npz of an interrupted run to warm-start from.')
+@click.option('--delta', default=None, type=float,
+              help='Huber threshold of the spatial priors (edge-preserving; needs --method mmmg). Default: quadratic priors.')
 def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, method, verbose, synthetic, device, checkpoint_every=0,
-         resume=None):
+         resume=None, delta=None):
+    if delta is not None and method == 'lcg':
+        raise click.BadParameter('lcg minimises quadratic criteria only; use --method mmmg with --delta', param_hint='--delta')
+    if delta is not None and not delta > 0:
+        raise click.BadParameter(f'must be positive, not {delta}', param_hint='--delta')
     print('options:', dict(fusion_dir=fusion_dir, npix=npix, hyper_parameter=hyper_parameter, niter=niter,
-                           n_templates=n_templates, scale_data=scale_data, method=method, synthetic=synthetic, device=device))
+                           n_templates=n_templates, scale_data=scale_data, method=method, synthetic=synthetic, device=device,
+                           delta=delta))
     if verbose:
         log.basicConfig(format="%(levelname)s: %(message)s", level=log.INFO)
 
@@ -203,7 +214,7 @@ def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, meth
 
     log.info(f'Start {method} algorithm')
     reconstruction_method(model, ndata, templates, paths["result_path"], hyper_parameter, niter, method, scale_data,
-                          checkpoint_every=checkpoint_every, resume=resume)
+                          checkpoint_every=checkpoint_every, resume=resume, delta=delta)
     model.close()
 
 

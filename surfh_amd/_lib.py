@@ -49,7 +49,7 @@ EXPORTS = [
     "surfh_stream", "surfh_forward", "surfh_adjoint", "surfh_adjoint_ref", "surfh_fwadj", "surfh_forward_dev",
     "surfh_adjoint_dev", "surfh_adjoint_ref_dev", "surfh_fwadj_dev", "surfh_wct_forward", "surfh_wct_adjoint",
     "surfh_wct_fwadj", "surfh_wct_expsol", "surfh_tst_create", "surfh_tst_destroy", "surfh_tst_forward",
-    "surfh_tst_adjoint", "surfh_tst_fwadj", "surfh_tst_last_error", "surfh_cg", "surfh_cg_cb", "surfh_mmmg", "surfh_cg_planes", "surfh_mmmg_planes", "surfh_cg_planes_cb", "surfh_mmmg_planes_cb", "surfh_cg_planes_begin_dev", "surfh_cg_planes_step_dev", "surfh_cg_planes_rr", "surfh_maps_to_cube", "surfh_cube_to_maps", "surfh_normal_dev",
+    "surfh_tst_adjoint", "surfh_tst_fwadj", "surfh_tst_last_error", "surfh_cg", "surfh_cg_cb", "surfh_mmmg", "surfh_mmmg_huber", "surfh_huber_prior_dev", "surfh_huber_curv_dev", "surfh_cg_planes", "surfh_mmmg_planes", "surfh_cg_planes_cb", "surfh_mmmg_planes_cb", "surfh_cg_planes_begin_dev", "surfh_cg_planes_step_dev", "surfh_cg_planes_rr", "surfh_maps_to_cube", "surfh_cube_to_maps", "surfh_normal_dev",
     "surfh_prior_add_dev", "surfh_spec_supported", "surfh_spec_size", "surfh_to_spec_dev", "surfh_from_spec_dev", "surfh_forward_spec_dev",
     "surfh_adjoint_spec_dev", "surfh_normal_spec_dev", "surfh_prior_spec_add_dev", "surfh_set_prior", "surfh_dot_dev", "surfh_cg_step_dev", "surfh_cg_dir_dev", "surfh_cg_iter_dev", "surfh_residual_dev",
     "surfh_cg_begin_dev", "surfh_cg_iter_nosync_dev", "surfh_cg_xupdate_nosync_dev", "surfh_cg_refresh_nosync_dev", "surfh_cg_trace",
@@ -96,6 +96,10 @@ def load():
     L.surfh_cg_cb.argtypes = [vp, c_float_p, C.c_double, C.c_double, c_float_p, C.c_int32, C.c_double, C.c_int32,
                               c_float_p, c_double_p, c_int32_p, CG_CALLBACK, vp]
     L.surfh_mmmg.argtypes = L.surfh_cg_cb.argtypes
+    L.surfh_mmmg_huber.argtypes = [vp, c_float_p, C.c_double, C.c_double, C.c_double, c_float_p, C.c_int32, C.c_double, C.c_int32,
+                                   c_float_p, c_double_p, c_int32_p, c_double_p, CG_CALLBACK, vp]
+    L.surfh_huber_prior_dev.argtypes = [vp, vp, vp, C.c_double, C.c_double, c_double_p]
+    L.surfh_huber_curv_dev.argtypes = [vp, vp, vp, vp, C.c_double, c_double_p]
     L.surfh_mmmg_planes.argtypes = L.surfh_cg_planes.argtypes
     L.surfh_cg_planes_begin_dev.argtypes = [vp, vp, C.c_double, C.c_double, vp]
     L.surfh_cg_planes_step_dev.argtypes = [vp, C.c_int32, C.c_int32]
@@ -158,6 +162,24 @@ def solve(model, fn, data, mu, mu_reg, x0, max_iter, tol, refresh, callback, pla
     """Run one of the host-buffer solvers of the C ABI (``surfh_cg_cb``, ``surfh_mmmg``, ``surfh_cg_planes_cb``,
     ``surfh_mmmg_planes_cb``) on ``model``'s plan.  ``grad_norm`` has one column per plane, or is ``[nit+1]`` when
     ``squeeze`` (a single image).  Returns ``(x, grad_norm, nit)``."""
+    def invoke(y, x0p, x, gn, nit, cb):
+        return fn(model._plan, y, float(mu), float(mu_reg), x0p, int(max_iter), float(tol), int(refresh), x, gn, nit, cb, None)
+    return _solve(model, invoke, data, x0, max_iter, callback, planes, squeeze)
+
+
+def solve_huber(model, data, mu, mu_reg, delta, x0, max_iter, tol, refresh, callback):
+    """``surfh_mmmg_huber`` on ``model``'s plan, arguments as ``solve``.  Returns ``(x, grad_norm, nit, prior_value)``,
+    prior_value = sum_k sum phi(D_k x) of the returned iterate."""
+    pv = C.c_double()
+
+    def invoke(y, x0p, x, gn, nit, cb):
+        return load().surfh_mmmg_huber(model._plan, y, float(mu), float(mu_reg), float(delta), x0p, int(max_iter), float(tol),
+                                       int(refresh), x, gn, nit, C.byref(pv), cb, None)
+    x, gn, nit = _solve(model, invoke, data, x0, max_iter, callback, 1, True)
+    return x, gn, nit, pv.value
+
+
+def _solve(model, invoke, data, x0, max_iter, callback, planes, squeeze):
     y = np.ascontiguousarray(np.asarray(data, dtype=np.float32).reshape(-1))
     if y.size != model.osize:
         raise ValueError("data size mismatch")
@@ -179,8 +201,7 @@ def solve(model, fn, data, mu, mu_reg, x0, max_iter, tol, refresh, callback, pla
             return 1
 
     cb = CG_CALLBACK(tramp) if callback is not None else CG_CALLBACK()
-    check(fn(model._plan, fptr(y), float(mu), float(mu_reg), fptr(x0a) if x0a is not None else None, int(max_iter),
-             float(tol), int(refresh), fptr(x), dptr(gn), C.byref(nit), cb, None))
+    check(invoke(fptr(y), fptr(x0a) if x0a is not None else None, fptr(x), dptr(gn), C.byref(nit), cb))
     if err:
         raise err[0]
     gn = gn[: nit.value + 1]

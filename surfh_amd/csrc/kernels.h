@@ -140,6 +140,15 @@ int launch_lincomb(hipStream_t s, float *out, const float *a, const float *b, lo
 // 3MG move: mv = s0 d + s1 m ; x += mv ; m = mv ; qm = s0 qd + s1 qm ; r -= qm (when update_r)
 int launch_mmmg_update(hipStream_t s, float *x, float *r, const float *d, float *m, float *qm, const float *qd, long n, double s0,
                        double s1, int update_r);
+// Huber priors on the separated circular first differences of [T][na][nb] maps, u_r = x[i-1][j] - x[i][j], u_c = x[i][j-1] - x[i][j]
+// (NpDiff_r / NpDiff_c); phi(u) = u^2/2 (|u| <= delta), delta (|u| - delta/2) beyond; w(u) = phi'(u) / u.  Float64 per-block partials
+// in `scratch` (>= 768 doubles), summed in a fixed order: the same inputs give the same bits.
+// out = src + coef * sum_k D_k^T phi'(D_k x) (out may alias src); sums[0] = out.out, sums[1] = sum_k sum phi(D_k x)
+int launch_huber_grad(hipStream_t s, const float *x, const float *src, float *out, int T, int na, int nb, float coef, float delta,
+                      double *scratch, double *sums);
+// sums[0..2] = sum_k sum w(D_k x) (D_k p0)^2, (D_k p0)(D_k p1), (D_k p1)^2: the prior block of the half-quadratic majorant
+int launch_huber_curv(hipStream_t s, const float *x, const float *p0, const float *p1, int T, int na, int nb, float delta,
+                      double *scratch, double *sums);
 // CG on independent planes ([nplanes][npix] arrays, per-plane scalars in double arrays of nplanes)
 int launch_dot_planes(hipStream_t s, const float *a, const float *b, int nplanes, long npix, double *out);
 int launch_cg_step_planes(hipStream_t s, float *x, float *r, const float *d, const float *q, int nplanes, long npix, const double *rr,

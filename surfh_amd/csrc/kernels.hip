@@ -1207,6 +1207,100 @@ __global__ __launch_bounds__(TPB) void mmmg_step_planes_kernel(float *__restrict
     }
 }
 
+// ---- Huber priors on the separated circular first differences (surfh_mmmg_huber) ----------------
+// One thread per map pixel (grid-stride): the pixel owns u_r = x[i-1][j] - x[i][j] and u_c = x[i][j-1] - x[i][j] and, for the
+// gradient, reads the differences it shares with its successors.  Maps are a few MB: the neighbour reads hit L2.
+__device__ __forceinline__ float huber_dphi(float u, float delta) { return fabsf(u) <= delta ? u : copysignf(delta, u); }
+__device__ __forceinline__ float huber_w(float u, float delta) { return fabsf(u) <= delta ? 1.f : delta / fabsf(u); }
+__device__ __forceinline__ double huber_phi(float u, float delta) {
+    const float a = fabsf(u);
+    return a <= delta ? 0.5 * (double)a * (double)a : (double)delta * ((double)a - 0.5 * (double)delta);
+}
+
+// K block sums in a fixed order; part[k * gridDim.x + blockIdx.x] = sum over the block of v[k]
+template <int K>
+__device__ inline void block_sums_to(double (&v)[K], double *__restrict__ part) {
+    __shared__ double sm[K][TPB / 64];
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_down(v[k], o, 64);
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int k = 0; k < K; ++k) sm[k][threadIdx.x >> 6] = v[k];
+    __syncthreads();
+    if (threadIdx.x < K) {
+        double s = 0.0;
+        for (int w = 0; w < TPB / 64; ++w) s += sm[threadIdx.x][w];
+        part[(long)threadIdx.x * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+struct PixelNbrs {   // (t, i, j) of element e of [T][na][nb] and the circular neighbour offsets inside its plane
+    long base;
+    int c, im, ip, jm, jp;
+};
+__device__ __forceinline__ PixelNbrs pixel_nbrs(long e, int na, int nb) {
+    const long plane = (long)na * nb;
+    const long t = e / plane;
+    const int rem = (int)(e - t * plane), i = rem / nb, j = rem - i * nb;
+    PixelNbrs q;
+    q.base = t * plane;
+    q.c = rem;
+    q.im = (i == 0 ? na - 1 : i - 1) * nb + j;
+    q.ip = (i == na - 1 ? 0 : i + 1) * nb + j;
+    q.jm = i * nb + (j == 0 ? nb - 1 : j - 1);
+    q.jp = i * nb + (j == nb - 1 ? 0 : j + 1);
+    return q;
+}
+
+// out = src + coef (Dr^T phi'(Dr x) + Dc^T phi'(Dc x)),  (D^T v)[i] = v[i+1] - v[i];  part: [2][gridDim.x] (out.out, sum phi)
+// src and out may be the same array (each element is read and written by one thread)
+__global__ __launch_bounds__(TPB) void huber_grad_kernel(const float *__restrict__ x, const float *src, float *out, long n, int na,
+                                                         int nb, float coef, float delta, double *__restrict__ part) {
+    double acc[2] = {0.0, 0.0};
+    const long stride = (long)gridDim.x * TPB;
+    for (long e = (long)blockIdx.x * TPB + threadIdx.x; e < n; e += stride) {
+        const PixelNbrs q = pixel_nbrs(e, na, nb);
+        const float *p = x + q.base;
+        const float c = p[q.c];
+        const float ur = p[q.im] - c, uc = p[q.jm] - c;            // (Dr x)[i][j], (Dc x)[i][j]
+        const float urn = c - p[q.ip], ucn = c - p[q.jp];          // (Dr x)[i+1][j], (Dc x)[i][j+1]
+        const float pg = (huber_dphi(urn, delta) - huber_dphi(ur, delta)) + (huber_dphi(ucn, delta) - huber_dphi(uc, delta));
+        const float g = src[e] + coef * pg;
+        out[e] = g;
+        acc[0] += (double)g * (double)g;
+        acc[1] += huber_phi(ur, delta) + huber_phi(uc, delta);
+    }
+    block_sums_to<2>(acc, part);
+}
+
+// part: [3][gridDim.x] = sum_k w(D_k x) (D_k p0)^2, (D_k p0)(D_k p1), (D_k p1)^2 (weights recomputed, none stored)
+__global__ __launch_bounds__(TPB) void huber_curv_kernel(const float *__restrict__ x, const float *__restrict__ p0,
+                                                         const float *__restrict__ p1, long n, int na, int nb, float delta,
+                                                         double *__restrict__ part) {
+    double acc[3] = {0.0, 0.0, 0.0};
+    const long stride = (long)gridDim.x * TPB;
+    for (long e = (long)blockIdx.x * TPB + threadIdx.x; e < n; e += stride) {
+        const PixelNbrs q = pixel_nbrs(e, na, nb);
+        const float *p = x + q.base, *a = p0 + q.base, *b = p1 + q.base;
+        const float c = p[q.c], ac = a[q.c], bc = b[q.c];
+        const double wr = huber_w(p[q.im] - c, delta), wc = huber_w(p[q.jm] - c, delta);
+        const double ar = a[q.im] - ac, acl = a[q.jm] - ac, br = b[q.im] - bc, bcl = b[q.jm] - bc;
+        acc[0] += wr * ar * ar + wc * acl * acl;
+        acc[1] += wr * ar * br + wc * acl * bcl;
+        acc[2] += wr * br * br + wc * bcl * bcl;
+    }
+    block_sums_to<3>(acc, part);
+}
+
+// out[k] = sum_i part[k * nparts + i], one block per k, reduce_final_kernel's order
+__global__ __launch_bounds__(TPB) void parts_reduce_kernel(const double *__restrict__ part, int nparts, double *__restrict__ out) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += TPB) s += part[(long)blockIdx.x * nparts + i];
+    s = block_sum(s);
+    if (threadIdx.x == 0) out[blockIdx.x] = s;
+}
+
 inline int nblocks(long n, int cap = 2048) {
     long b = (n + TPB - 1) / TPB;
     if (b < 1) b = 1;
@@ -1573,5 +1667,26 @@ size_t pn_part_doubles(long LP) { return (size_t)PN_SPLIT * (size_t)LP; }
 
 int launch_cg_dir_planes(hipStream_t s, float *d, const float *r, int nplanes, long npix, const double *rrn, double *rr) {
     hipLaunchKernelGGL(cg_dir_planes_kernel, dim3(nplanes), dim3(TPB), 0, s, d, r, npix, rrn, rr);
+    return (int)hipGetLastError();
+}
+
+// 256 blocks at most: [3][256] partials fit the plan's 1024-double scratch
+constexpr int HUBER_BLOCKS = 256;
+int launch_huber_grad(hipStream_t s, const float *x, const float *src, float *out, int T, int na, int nb, float coef, float delta,
+                      double *scratch, double *sums) {
+    if (T < 1 || na < 1 || nb < 1) return (int)hipErrorInvalidValue;
+    const long n = (long)T * na * nb;
+    const int nbk = nblocks(n, HUBER_BLOCKS);
+    hipLaunchKernelGGL(huber_grad_kernel, dim3(nbk), dim3(TPB), 0, s, x, src, out, n, na, nb, coef, delta, scratch);
+    hipLaunchKernelGGL(parts_reduce_kernel, dim3(2), dim3(TPB), 0, s, scratch, nbk, sums);
+    return (int)hipGetLastError();
+}
+int launch_huber_curv(hipStream_t s, const float *x, const float *p0, const float *p1, int T, int na, int nb, float delta,
+                      double *scratch, double *sums) {
+    if (T < 1 || na < 1 || nb < 1) return (int)hipErrorInvalidValue;
+    const long n = (long)T * na * nb;
+    const int nbk = nblocks(n, HUBER_BLOCKS);
+    hipLaunchKernelGGL(huber_curv_kernel, dim3(nbk), dim3(TPB), 0, s, x, p0, p1, n, na, nb, delta, scratch);
+    hipLaunchKernelGGL(parts_reduce_kernel, dim3(3), dim3(TPB), 0, s, scratch, nbk, sums);
     return (int)hipGetLastError();
 }

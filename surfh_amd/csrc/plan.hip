@@ -22,6 +22,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cfloat>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -203,6 +204,7 @@ struct surfh_plan {
     long isize = 0, osize = 0;
     // CG
     float *cg_x = nullptr, *cg_r = nullptr, *cg_d = nullptr, *cg_q = nullptr, *cg_b = nullptr, *cg_y = nullptr, *cg_qm = nullptr, *cg_dd = nullptr;
+    float *cg_hg = nullptr;                        // surfh_mmmg_huber: -gradient of the non-quadratic criterion
     double *dscal = nullptr, *dscratch = nullptr;   // [8] device scalars, [1024] partial sums
     double *cg_hist = nullptr;                     // device-resident r.r trace of the no-host-sync CG blocks (CG_HIST_CAP entries)
     int cg_hist_n = 0;
@@ -1492,7 +1494,7 @@ int surfh_plan_destroy(surfh_plan *p) {
     hipSetDevice(p->dev);
     if (p->stream) hipStreamSynchronize(p->stream);
     for (float *v : {p->sotf, p->tpl, p->mhat, p->spec, p->ycol, p->cube, p->ycol_maps, p->maps_pad, p->Fi, p->Gi, p->Gf,
-                     p->Ff, p->GiT, p->GfT, p->Cma, p->Sma, p->Gc, p->Gs, p->Cf, p->Sf, p->io_cube, p->hth, p->mhat2, p->gcube, p->io_x, p->io_y, p->cg_x, p->cg_r, p->cg_d, p->cg_q, p->cg_b, p->cg_y, p->cg_qm, p->cg_dd})
+                     p->Ff, p->GiT, p->GfT, p->Cma, p->Sma, p->Gc, p->Gs, p->Cf, p->Sf, p->io_cube, p->hth, p->mhat2, p->gcube, p->io_x, p->io_y, p->cg_x, p->cg_r, p->cg_d, p->cg_q, p->cg_b, p->cg_y, p->cg_qm, p->cg_dd, p->cg_hg})
         hipFree(v);
     hipFree(p->h2img);
     if (p->ctB.img != p->ctA.img) dft_ct_plan_destroy(&p->ctB);
@@ -2504,6 +2506,143 @@ int surfh_mmmg(surfh_plan *p, const float *y, double mu, double mu_reg, const fl
         }
         *nit = it + 1;
     }
+    HIP_OK(hipMemcpyAsync(x, p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return 0;
+}
+
+// ---- 3MG with Huber priors (qmm.mmmg with qmm.Huber on the row and column differences: the reference's lmm_reconstruction,
+// surfh/ToolsDir/algorithms.py:73-106).  The majorant at x is half-quadratic (Geman-Reynolds):
+//   B(x) = mu A^T A + mu_reg sum_k D_k^T diag(w(D_k x)) D_k,   w(u) = phi'(u) / u,
+// minimised over span{-g, m} (m the previous move).  The basis is [d, m] with d = -g + beta m B(x)-orthogonal to m, as in
+// surfh_mmmg: beta from the carried data image Q_D m = mu A^T A m and the prior block huber_curv(x; -g, m).  The data part
+// r = b - mu A^T A x is carried by linearity (recomputed every `refresh` iterations).  Two stencil passes per iteration, each
+// followed by a one-block reduction: huber_grad gives -g = r - mu_reg sum_k D_k^T phi'(D_k x), |g|^2 and the prior value;
+// huber_curv gives the prior block c = [(-g).W(-g), (-g).W m, m.W m] (W = D^T diag(w) D at x).  The block of (d, m) follows
+// from c by linearity in float64 (d.Wd = c00 + 2 beta c01 + beta^2 c11, d.Wm = c01 + beta c11); d.Bd = g.Bg - (g.Bm)^2 / m.Bm
+// is the Schur complement of a positive semi-definite 2x2 matrix, which float64 forms from fp64-accumulated sums with no
+// cancellation that matters at fp32 data precision.  Two host synchronisations per iteration (beta, then the 2x2 system).
+namespace {
+// the kernels take delta in fp32: a positive delta below FLT_MIN would flush to 0 there (every weight off u = 0 would vanish)
+int huber_args(double mu_reg, double delta) {
+    if (std::isnan(mu_reg) || std::isnan(delta)) return fail("Huber prior: mu_reg and delta must not be NaN");
+    if (!(delta >= (double)FLT_MIN)) return fail("Huber prior: delta must be at least %g (fp32 kernels; got %g)", (double)FLT_MIN, delta);
+    return 0;
+}
+}  // namespace
+
+int surfh_huber_prior_dev(surfh_plan *p, const float *x_dev, float *g_dev, double mu_reg, double delta, double *value) {
+    if (!p || !x_dev || !g_dev) return fail("null argument");
+    if (p->T <= 0) return fail("prior is defined on abundance maps (needs templates)");
+    if (huber_args(mu_reg, delta)) return 1;
+    HIP_OK(hipSetDevice(p->dev));
+    {
+        Prof pr(p, "huber_grad");
+        LAUNCH_OK(launch_huber_grad(p->stream, x_dev, g_dev, g_dev, p->T, p->Na, p->Nb, (float)mu_reg, (float)delta, p->dscratch,
+                                    p->dscal + 0));
+    }
+    double h[2];
+    HIP_OK(hipMemcpyAsync(h, p->dscal, 2 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    if (value) *value = h[1];
+    return 0;
+}
+int surfh_huber_curv_dev(surfh_plan *p, const float *x_dev, const float *p0_dev, const float *p1_dev, double delta, double *sums) {
+    if (!p || !x_dev || !p0_dev || !p1_dev || !sums) return fail("null argument");
+    if (p->T <= 0) return fail("prior is defined on abundance maps (needs templates)");
+    if (huber_args(0.0, delta)) return 1;
+    HIP_OK(hipSetDevice(p->dev));
+    {
+        Prof pr(p, "huber_curv");
+        LAUNCH_OK(launch_huber_curv(p->stream, x_dev, p0_dev, p1_dev, p->T, p->Na, p->Nb, (float)delta, p->dscratch, p->dscal + 0));
+    }
+    HIP_OK(hipMemcpyAsync(sums, p->dscal, 3 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int surfh_mmmg_huber(surfh_plan *p, const float *y, double mu, double mu_reg, double delta, const float *x0, int32_t max_iter,
+                     double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit, double *prior_value,
+                     surfh_cg_callback callback, void *user) {
+    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (p->T <= 0) return fail("surfh_mmmg_huber needs templates (the priors act on abundance maps)");
+    if (huber_args(mu_reg, delta)) return 1;
+    std::vector<float> hx;
+    HIP_OK(hipSetDevice(p->dev));
+    if (ensure_cg(p)) return 1;
+    if (!p->cg_qm && (dev_alloc(&p->cg_qm, (size_t)p->isize) || dev_alloc(&p->cg_dd, (size_t)p->isize))) return 1;
+    if (!p->cg_hg && dev_alloc(&p->cg_hg, (size_t)p->isize)) return 1;
+    hipStream_t s = p->stream;
+    const long n = p->isize;
+    const int T = p->T, Na = p->Na, Nb = p->Nb;
+    const float dl = (float)delta;
+    float *r = p->cg_r, *m = p->cg_d, *d = p->cg_dd, *qd = p->cg_q, *qm = p->cg_qm, *ng = p->cg_hg;
+    double *sc = p->dscal;
+    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
+    if (x0)
+        HIP_OK(hipMemcpyAsync(p->cg_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
+    else
+        LAUNCH_OK(launch_fill_zero(s, p->cg_x, n));
+    LAUNCH_OK(launch_fill_zero(s, m, n));
+    LAUNCH_OK(launch_fill_zero(s, qm, n));
+    if (solver_setup(p, p->io_y, p->cg_x, mu, 0.0)) return 1;          // r = b - mu A^T A x: the data part of -g
+    double h[7], prior = 0.0;
+    *nit = 0;
+    for (int it = 0;; ++it) {
+        // -g, |g|^2 and the prior value; then h2 = -g.Q_D m, h3 = m.Q_D m, h4.. = prior block of (-g, m) under w(D x)
+        {
+            Prof pr(p, "huber_grad");
+            LAUNCH_OK(launch_huber_grad(s, p->cg_x, r, ng, T, Na, Nb, -(float)mu_reg, dl, p->dscratch, sc + 0));
+        }
+        LAUNCH_OK(launch_dot(s, ng, qm, n, p->dscratch, sc + 2));
+        LAUNCH_OK(launch_dot(s, m, qm, n, p->dscratch, sc + 3));
+        {
+            Prof pr(p, "huber_curv");
+            LAUNCH_OK(launch_huber_curv(s, p->cg_x, ng, m, T, Na, Nb, dl, p->dscratch, sc + 4));
+        }
+        HIP_OK(hipMemcpyAsync(h, sc, 7 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        grad_norm[it] = std::sqrt(h[0]);
+        prior = h[1];
+        if (const int rc = it > 0 ? callback_iterate(p, callback, user, it, grad_norm, p->cg_x, hx) : CB_GO_ON) {
+            if (rc == CB_STOP) break;
+            return 1;
+        }
+        if (it >= max_iter || grad_norm[it] < (double)n * tol) break;
+        const double c00 = h[4], c01 = h[5], c11 = h[6];
+        const double mBm = h[3] + mu_reg * c11, beta = mBm > 0.0 ? -(h[2] + mu_reg * c01) / mBm : 0.0;
+        LAUNCH_OK(launch_lincomb(s, d, ng, m, n, beta));
+        if (normal_dev(p, d, qd, mu)) return 1;
+        // h0 = d.Q_D d, h1 = d.Q_D m, h2 = d.(-g), h3 = m.(-g)
+        LAUNCH_OK(launch_dot(s, d, qd, n, p->dscratch, sc + 0));
+        LAUNCH_OK(launch_dot(s, d, qm, n, p->dscratch, sc + 1));
+        LAUNCH_OK(launch_dot(s, d, ng, n, p->dscratch, sc + 2));
+        LAUNCH_OK(launch_dot(s, m, ng, n, p->dscratch, sc + 3));
+        HIP_OK(hipMemcpyAsync(h, sc, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        const double dWd = c00 + beta * (2.0 * c01 + beta * c11), dWm = c01 + beta * c11;
+        const double dBd = h[0] + mu_reg * dWd, dBm = h[1] + mu_reg * dWm, dg = h[2], mg = h[3];
+        if (!(dBd > 0.0)) return fail("3MG (Huber): non-positive curvature d.Bd = %g at iteration %d", dBd, it);
+        double s0 = dg / dBd, s1 = 0.0;
+        if (mBm > 0.0) {
+            const double sq = std::sqrt(dBd * mBm), c = dBm / sq, det = 1.0 - c * c;      // scaled 2x2 system
+            if (det > 1e-12) {
+                s0 = (dg / dBd - c * mg / sq) / det;
+                s1 = (mg / mBm - c * dg / sq) / det;
+            }
+        }
+        const bool fresh = refresh > 0 && it % refresh == 0;
+        {
+            Prof pr(p, "mmmg_update");
+            LAUNCH_OK(launch_mmmg_update(s, p->cg_x, r, d, m, qm, qd, n, s0, s1, fresh ? 0 : 1));
+        }
+        if (fresh) {
+            if (normal_dev(p, p->cg_x, qd, mu)) return 1;
+            LAUNCH_OK(launch_residual(s, r, p->cg_b, qd, n));
+        }
+        *nit = it + 1;
+    }
+    if (prior_value) *prior_value = prior;
     HIP_OK(hipMemcpyAsync(x, p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
     return 0;

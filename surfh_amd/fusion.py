@@ -32,16 +32,27 @@ class OptimizeResult:
 
 
 class QuadCriterion_MRS:
-    def __init__(self, mu_spectro, y_spectro, model_spectro, mu_reg, printing=False, gradient="separated"):
+    def __init__(self, mu_spectro, y_spectro, model_spectro, mu_reg, printing=False, gradient="separated", delta=None):
         """``gradient="joint"`` regularises with the Laplacian of ``Difference_Operator_Joint`` (fusion_CT.py:45-62); udft's
         ``laplacian(2)`` is absent from the reference tree, the 3 x 3 kernel [[0,-1,0],[-1,4,-1],[0,-1,0]] is restated: parity
         unpinned for that option (the operator is checked against the oracle's Fourier-domain form of the same kernel).
         NOTE on the data term: ``model_spectro.adjoint`` is the exact transpose of ``forward`` (what CG needs); the reference
         hands qmm its interpolating ``gridding_t`` adjoint instead (spectroModel.py:173-185), so its right-hand side
-        mu A_ref^T y and hence its iterates differ from the ones computed here (tests/test_gpu_driver.py records by how much)."""
+        mu A_ref^T y and hence its iterates differ from the ones computed here (tests/test_gpu_driver.py records by how much).
+        ``delta`` (not in fusion_CT.py; the priors of the reference's lmm_reconstruction, algorithms.py:73-106): Huber
+        potentials of threshold ``delta`` on the separated differences, criterion mu |y - A x|^2 / 2 + mu_reg sum_k sum
+        phi(D_k x) (include/surfh_amd.h: surfh_mmmg_huber); only ``run_method("mmmg")`` minimises it, CG being a solver of
+        quadratic criteria.  ``None``: the quadratic criterion."""
         assert isinstance(mu_reg, (float, int, list, np.ndarray))
         if gradient not in ("separated", "joint"):
             raise ValueError(f"gradient must be 'separated' or 'joint', not {gradient!r}")
+        if delta is not None:
+            if gradient != "separated":
+                raise ValueError("the Huber prior (delta) acts on the separated differences: gradient must be 'separated'")
+            delta = float(delta)
+            if not delta > 0.0:
+                raise ValueError(f"delta must be positive, not {delta!r}")
+        self.delta = delta
         self.mu_spectro, self.y_spectro, self.model_spectro, self.mu_reg = mu_spectro, y_spectro, model_spectro, mu_reg
         self.n_spec = model_spectro.ishape[0]
         self.shape_of_output = tuple(model_spectro.ishape)
@@ -62,6 +73,8 @@ class QuadCriterion_MRS:
         rename, so an interrupted run restarts from ``load_checkpoint(path)`` as ``value_init`` (a warm start of the solver,
         fusion_CT.py:122-126: the search directions start afresh)."""
         assert isinstance(self.mu_reg, (int, float))       # fusion_CT.py:119
+        if self.delta is not None and method == "lcg":
+            raise ValueError("lcg minimises quadratic criteria only: a Huber prior (delta) needs method='mmmg'")
         solver = self.model_spectro.cg if method == "lcg" else self.model_spectro.mmmg     # fusion_CT.py:194-198
         # the regulariser is state of the plan: select this criterion's for the duration of the solve and put back what was
         # there, so that two criteria sharing one model (different `gradient`) do not change each other's operator
@@ -112,8 +125,9 @@ class QuadCriterion_MRS:
                 return user_cb(it, gn, x) if user_cb is not None else None
         t0 = time.time()
         try:
+            kw = {} if self.delta is None else {"delta": self.delta}
             x, gn, nit = solver(self.y_spectro, mu=self.mu_spectro, mu_reg=self.mu_reg, x0=init,
-                                max_iter=maximum_iterations, tol=tolerance, callback=callback)
+                                max_iter=maximum_iterations, tol=tolerance, callback=callback, **kw)
         finally:
             if prior_before is not None:
                 self.model_spectro.set_prior(prior_before)
@@ -125,15 +139,27 @@ class QuadCriterion_MRS:
         return res
 
     def get_crit_val(self, x_hat):
-        """(mu |y - A x|^2 + mu_reg (|Dr x|^2 + |Dc x|^2)) / 2   (fusion_CT.py:242-265)."""
+        """(mu |y - A x|^2 + mu_reg (|Dr x|^2 + |Dc x|^2)) / 2   (fusion_CT.py:242-265); with ``delta``
+        mu |y - A x|^2 / 2 + mu_reg sum phi(Dr x) + phi(Dc x), phi the Huber potential (that criterion's limit delta -> inf)."""
         x_hat = np.asarray(x_hat).reshape(self.shape_of_output)
         data = self.mu_spectro * np.sum((self.y_spectro - self.model_spectro.forward(x_hat)) ** 2)
+        if self.delta is not None:
+            return data / 2 + self.mu_reg * (huber_phi(np.roll(x_hat, 1, axis=1) - x_hat, self.delta).sum() +
+                                             huber_phi(np.roll(x_hat, 1, axis=2) - x_hat, self.delta).sum())
         if self.gradient == "joint":                 # |D x|^2, D = circular 3 x 3 Laplacian centred on the pixel (:254-255, :45-54)
             dx = 4 * x_hat - np.roll(x_hat, 1, 1) - np.roll(x_hat, -1, 1) - np.roll(x_hat, 1, 2) - np.roll(x_hat, -1, 2)
             return (data + self.mu_reg * np.sum(dx ** 2)) / 2
         dr = np.roll(x_hat, 1, axis=1) - x_hat
         dc = np.roll(x_hat, 1, axis=2) - x_hat
         return (data + self.mu_reg * np.sum(dr ** 2 + dc ** 2)) / 2
+
+
+def huber_phi(u, delta):
+    """qmm.Huber's potential: u^2 / 2 for |u| <= delta, delta (|u| - delta / 2) beyond (delta = inf: u^2 / 2)."""
+    a = np.abs(np.asarray(u, dtype=np.float64))
+    if np.isinf(delta):
+        return a * a / 2
+    return np.where(a <= delta, a * a / 2, delta * (a - delta / 2))
 
 
 # ------------------------------------------------------------------------------------------------

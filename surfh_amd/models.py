@@ -83,6 +83,8 @@ class Channel(ChannelGeometry):
 
 
 class spectroSigRLSCT(LinOp):
+    huber_prior_value = None            # prior value of the last mmmg(delta=...) result (set by mmmg)
+
     def __init__(self, sotf, templates, alpha_axis, beta_axis, wavelength_axis, instrs: List[instru.IFU],
                  step_degree: float, pointings: Sequence[instru.CoordList], *, device: int = 0,
                  channels: Optional[Sequence[int]] = None, with_ref: bool = True, stream: Optional[int] = None,
@@ -322,10 +324,32 @@ class spectroSigRLSCT(LinOp):
         current iterate ``[T,Na,Nb]``; it may call ``forward`` / ``adjoint`` on this model; a truthy return stops."""
         return _lib.solve(self, self._L.surfh_cg_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
 
-    def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None):
+    def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, delta=None):
         """Device-resident 3MG (qmm.mmmg restated for quadratic objectives; the reference's ``method='mmmg'``,
-        fusion_CT.py:194-198).  Same arguments as ``cg``; ``grad_norm`` holds |grad| (not squared) of every iterate."""
-        return _lib.solve(self, self._L.surfh_mmmg, data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
+        fusion_CT.py:194-198).  Same arguments as ``cg``; ``grad_norm`` holds |grad| (not squared) of every iterate.
+
+        ``delta`` (a number): the spatial priors are Huber potentials of threshold ``delta`` on the separated circular
+        differences instead (qmm.Huber, the reference's lmm_reconstruction, algorithms.py:73-106) and the criterion is
+        ``mu |y - A x|^2 / 2 + mu_reg sum_k sum phi(D_k x)`` (include/surfh_amd.h: surfh_mmmg_huber); the prior value of the
+        returned iterate is left in ``self.huber_prior_value`` (None after a quadratic run, and before any run).  qmm is not
+        available to pin this restatement against.  ``None`` runs the quadratic solver above."""
+        self.huber_prior_value = None
+        if delta is None:
+            return _lib.solve(self, self._L.surfh_mmmg, data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
+        x, gn, nit, self.huber_prior_value = _lib.solve_huber(self, data, mu, mu_reg, delta, x0, max_iter, tol, refresh, callback)
+        return x, gn, nit
+
+    def huber_curv_dev(self, x_t, p0_t, p1_t, delta: float) -> np.ndarray:
+        """sum_k sum w(D_k x) (D_k p0)^2, (D_k p0)(D_k p1), (D_k p1)^2 on device maps: the prior block of the Huber majorant."""
+        out = np.zeros(3, dtype=np.float64)
+        _lib.check(self._L.surfh_huber_curv_dev(self._plan, _ptr(x_t), _ptr(p0_t), _ptr(p1_t), float(delta), _lib.dptr(out)))
+        return out
+
+    def huber_prior_dev(self, x_t, g_t, mu_reg: float, delta: float) -> float:
+        """g += mu_reg sum_k D_k^T phi'(D_k x) on device maps [T, Na, Nb]; returns sum_k sum phi(D_k x) (synchronises)."""
+        out = C.c_double()
+        _lib.check(self._L.surfh_huber_prior_dev(self._plan, _ptr(x_t), _ptr(g_t), float(mu_reg), float(delta), C.byref(out)))
+        return out.value
 
     # ---- helpers the reference's drivers call -----------------------------------------------
     def cubeTomaps(self, cube):
