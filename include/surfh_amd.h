@@ -191,6 +191,34 @@ int surfh_huber_prior_dev(surfh_plan *plan, const float *x_dev, float *g_dev, do
 /* the prior block of the majorant: sums_host[0..2] = sum_k sum w(D_k x) (D_k p0)^2, (D_k p0)(D_k p1), (D_k p1)^2, the weights
  * w(u) = phi'(u) / u recomputed from x (same summation rules) */
 int surfh_huber_curv_dev(surfh_plan *plan, const float *x_dev, const float *p0_dev, const float *p1_dev, double delta, double *sums_host);
+/* The same solver on the hyperspectral cube itself (the reference's vox_reconstruction, surfh/ToolsDir/algorithms.py:27-71:
+ * qmm.mmmg with qmm.Huber on the row, column and spectral differences).  Plans without templates only (n_templates = 0):
+ * x is the cube [Lc][Na][Nb], A the cube-domain operator of the plan.  Minimises
+ *   J(x) = mu |y - A x|^2 / 2 + spat_reg sum_{k in r,c} sum phi_{spat_delta}(D_k x) + spec_reg sum phi_{spec_delta}(D_l x),
+ * phi and w = phi'/u as above.  D_r, D_c: the separated circular differences inside every plane (the planes take the place of
+ * the maps).  D_l: (D_l x)[l] = x[l+1] - x[l], l = 0 .. Lc-2, NOT circular (Lc - 1 difference planes; (D_l^T v)[l] = v[l-1] - v[l]
+ * with v[-1] = v[Lc-1] = 0): a wrap would tie the shortest to the longest wavelength of the cube, which means nothing
+ * physically.  Adjacent planes are differenced whatever their spacing, as the reference does; Lc = 1 leaves the spectral term
+ * empty.  Both border conventions are unpinned against aljabr.Diff, which is not available (the reference's legacy Spectro model
+ * is (alpha, beta, lambda), hence its Diff(0) / Diff(1) / Diff(2); the cube here is [lambda][alpha][beta]).
+ * Majorant at x:  B(x) = mu A^T A + spat_reg sum_k D_k^T diag(w(D_k x)) D_k + spec_reg D_l^T diag(w(D_l x)) D_l, minimised over
+ * span{-gradient, previous move} in the [d, m] basis of surfh_mmmg_huber, whose contract holds otherwise (trace, stopping test
+ * |gradient| < size * tol, refresh, callback, failure on non-positive curvature).  Either delta may be +inf (that term is then
+ * quadratic; both: the quadratic solve of the cube-domain operator); a delta below FLT_MIN or NaN, or a NaN weight, fails; a weight
+ * of 0 switches its family off.  prior_values (may be NULL) receives the spatial and the spectral sum of phi at the returned
+ * iterate.  Work vectors: 8 cubes. */
+int surfh_mmmg_huber_vox(surfh_plan *plan, const float *y, double mu, double spat_reg, double spat_delta, double spec_reg,
+                         double spec_delta, const float *x0, int32_t max_iter, double tol, int32_t refresh, float *x,
+                         double *grad_norm, int32_t *nit, double *prior_values, surfh_cg_callback callback, void *user);
+/* the two stencil passes alone, on device cubes [Lc][Na][Nb] (float64 sums in a fixed order: repeated calls give the same bits):
+ * g += spat_reg sum_k D_k^T phi'(D_k x) + spec_reg D_l^T phi'(D_l x) in one pass; values_host[0..1] (may be NULL) = the spatial and
+ * the spectral sum of phi */
+int surfh_huber_vox_prior_dev(surfh_plan *plan, const float *x_dev, float *g_dev, double spat_reg, double spat_delta,
+                              double spec_reg, double spec_delta, double *values_host);
+/* sums_host[0..2] = sum_k sum w(D_k x) (D_k p0)^2, (D_k p0)(D_k p1), (D_k p1)^2 under the spatial weights, [3..5] the same on D_l
+ * under the spectral weights: the host applies spat_reg and spec_reg in float64 */
+int surfh_huber_vox_curv_dev(surfh_plan *plan, const float *x_dev, const float *p0_dev, const float *p1_dev, double spat_delta,
+                             double spec_delta, double *sums_host);
 
 /* ---- linear mixing model on the device: the drivers' mapsToCube / cubeTomaps
  * (spectroModel.py:187-198, jax_utils.py:10-26).  templates [T][Lc] float64 as in surfh_config,

@@ -8,13 +8,25 @@ with phi the Huber potential of threshold ``spat_th`` (qmm.Huber): the reference
 and two Huber objectives on aljabr.Diff(0) / aljabr.Diff(1).  Here the same criterion runs through
 ``spectroSigRLSCT.mmmg(..., delta=spat_th)`` (include/surfh_amd.h: surfh_mmmg_huber).
 
+``vox_reconstruction`` (algorithms.py:27-71) minimises the same kind of criterion over the hyperspectral cube x itself, without
+templates, with a third Huber objective on the spectral differences:
+
+    J(x) = |y - A x|^2 / 2  +  spat_reg * sum_{k in rows, columns} sum phi_spat_th(D_k x)  +  spec_reg * sum phi_spec_th(D_l x)
+
+through ``spectroSigRLSCT.mmmg_vox`` (include/surfh_amd.h: surfh_mmmg_huber_vox).  The reference's legacy ``Spectro`` model is
+``(alpha, beta, lambda)``, hence its ``Diff(0) / Diff(1) / Diff(2)``; the cube here is ``[lambda][alpha][beta]``.  The spectral
+difference ``D_l x = x[l+1] - x[l]`` is open (``Lc - 1`` difference planes): a wrap would tie the shortest to the longest
+wavelength of the cube, which means nothing physically.
+
 Parity is unpinned on two counts: qmm is not available to check the 3MG restatement against, and neither is aljabr, so
 ``aljabr.Diff``'s border and axis conventions are not known here -- the circular spatial differences of fusion_CT.py:16-43
-(NpDiff_r / NpDiff_c) are used instead.
+(NpDiff_r / NpDiff_c) are used instead, and the open spectral difference above.
 """
 from __future__ import annotations
 
 import time
+
+import numpy as np
 
 from .fusion import OptimizeResult
 
@@ -34,3 +46,33 @@ def lmm_reconstruction(data, data_model, spat_reg: float = 1.0, spat_th: float =
     x, gn, nit = data_model.mmmg(data, mu=1.0, mu_reg=float(spat_reg), x0=init, max_iter=int(max_iter), tol=float(tol),
                                  callback=callback, delta=float(spat_th))
     return OptimizeResult(x=x.ravel(), grad_norm=list(gn), nit=nit, success=bool(gn[-1] < x.size * tol), time=time.time() - t0)
+
+
+def vox_reconstruction(data, data_model, spat_reg: float = 1.0, spat_th: float = 1.0, spec_reg: float = 1.0, spec_th: float = 1.0,
+                       init=None, max_iter: int = 500, tol: float = 1e-4, callback=None) -> OptimizeResult:
+    """Edge-preserving reconstruction of the hyperspectral cube (algorithms.py:27-71).
+
+    ``data_model`` is a model without templates (``spectroSigRLSCT(sotf, None, ...)``); ``init=None`` starts from
+    ``data_model.adjoint(data)`` (qmm's ``ht_data``).  ``max_iter``, ``tol``, ``callback`` and the result as
+    ``lmm_reconstruction``; x is the raveled cube ``[Lc, Na, Nb]``."""
+    if init is None:
+        init = data_model.adjoint(data)
+    t0 = time.time()
+    x, gn, nit = data_model.mmmg_vox(data, mu=1.0, spat_reg=float(spat_reg), spat_delta=float(spat_th), spec_reg=float(spec_reg),
+                                     spec_delta=float(spec_th), x0=init, max_iter=int(max_iter), tol=float(tol), callback=callback)
+    return OptimizeResult(x=x.ravel(), grad_norm=list(gn), nit=nit, success=bool(gn[-1] < x.size * tol), time=time.time() - t0)
+
+
+def vox_criterion(data, data_model, x, spat_reg: float = 1.0, spat_th: float = 1.0, spec_reg: float = 1.0, spec_th: float = 1.0,
+                  mu: float = 1.0) -> float:
+    """J(x) of ``vox_reconstruction`` at the cube ``x`` (``mu`` weighs the data term, 1 in the reference): the forward model and
+    the two prior sums run on the device (``huber_vox_prior_dev``), the data term is summed in float64 on the host."""
+    import torch
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(data_model.ishape))
+    dev = f"cuda:{data_model.device}"
+    x_t = torch.as_tensor(x, device=dev)
+    g_t = torch.zeros_like(x_t)
+    torch.cuda.synchronize(dev)
+    v_spat, v_spec = data_model.huber_vox_prior_dev(x_t, g_t, 0.0, spat_th, 0.0, spec_th)
+    res = np.asarray(data, dtype=np.float64).ravel() - data_model.forward(x).ravel()
+    return float(mu * np.sum(res * res) / 2 + spat_reg * v_spat + spec_reg * v_spec)

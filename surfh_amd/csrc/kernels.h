@@ -149,6 +149,16 @@ int launch_huber_grad(hipStream_t s, const float *x, const float *src, float *ou
 // sums[0..2] = sum_k sum w(D_k x) (D_k p0)^2, (D_k p0)(D_k p1), (D_k p1)^2: the prior block of the half-quadratic majorant
 int launch_huber_curv(hipStream_t s, const float *x, const float *p0, const float *p1, int T, int na, int nb, float delta,
                       double *scratch, double *sums);
+// The same potentials on the cube [Lc][na][nb] (huber_vox.hip): the in-plane circular differences under the threshold ds and the
+// open wavelength difference u_l = x[l+1] - x[l], l = 0 .. Lc-2, under dl.  `scratch` holds launch_huber_vox_scratch_doubles().
+// out = src + cs sum_{k in r,c} D_k^T phi'_ds(D_k x) + cl Dl^T phi'_dl(Dl x) in one pass (out may alias src);
+// sums[0] = out.out, sums[1] = sum_{k in r,c} sum phi_ds(D_k x), sums[2] = sum phi_dl(Dl x)
+int launch_huber_vox_grad(hipStream_t s, const float *x, const float *src, float *out, int Lc, int na, int nb, float cs, float ds,
+                          float cl, float dl, double *scratch, double *sums);
+// sums[0..2] = sum_{k in r,c} sum w_ds(D_k x) (D_k p0)^2, (D_k p0)(D_k p1), (D_k p1)^2;  sums[3..5] = the same under w_dl(Dl x) on Dl
+int launch_huber_vox_curv(hipStream_t s, const float *x, const float *p0, const float *p1, int Lc, int na, int nb, float ds, float dl,
+                          double *scratch, double *sums);
+size_t launch_huber_vox_scratch_doubles();
 // CG on independent planes ([nplanes][npix] arrays, per-plane scalars in double arrays of nplanes)
 int launch_dot_planes(hipStream_t s, const float *a, const float *b, int nplanes, long npix, double *out);
 int launch_cg_step_planes(hipStream_t s, float *x, float *r, const float *d, const float *q, int nplanes, long npix, const double *rr,

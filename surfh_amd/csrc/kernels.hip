@@ -1,10 +1,12 @@
 // HBM-bound kernels of the surfh hot path for gfx950 (see kernels.h for the contracts).
 #include "kernels.h"
+#include "huber_dev.h"
 #include <cstdlib>
 
 namespace {
 
 constexpr int TPB = 256;
+static_assert(TPB == RED_TPB, "the shared reductions of huber_dev.h assume this block size");
 
 // ---------------------------------------------------------------------------------------------
 // spectral mix x OTF   (wavelength innermost; spectra are planar [2][PL][LP], or with `ilv` interleaved
@@ -854,18 +856,7 @@ __global__ __launch_bounds__(TPB) void scale_kernel(float *x, long n, float a) {
     for (; i < n; i += stride) x[i] *= a;
 }
 
-__device__ inline double block_sum(double v) {
-    __shared__ double sm[TPB / 64];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) sm[w] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0)
-        for (int k = 0; k < TPB / 64; ++k) s += sm[k];
-    return s;   // valid in thread 0
-}
-
+// block_sum: huber_dev.h
 __global__ __launch_bounds__(TPB) void dot_partial_kernel(const float *__restrict__ a, const float *__restrict__ b,
                                                           long n, double *__restrict__ scratch) {
     double s = 0.0;
@@ -1209,32 +1200,10 @@ __global__ __launch_bounds__(TPB) void mmmg_step_planes_kernel(float *__restrict
 
 // ---- Huber priors on the separated circular first differences (surfh_mmmg_huber) ----------------
 // One thread per map pixel (grid-stride): the pixel owns u_r = x[i-1][j] - x[i][j] and u_c = x[i][j-1] - x[i][j] and, for the
-// gradient, reads the differences it shares with its successors.  Maps are a few MB: the neighbour reads hit L2.
-__device__ __forceinline__ float huber_dphi(float u, float delta) { return fabsf(u) <= delta ? u : copysignf(delta, u); }
-__device__ __forceinline__ float huber_w(float u, float delta) { return fabsf(u) <= delta ? 1.f : delta / fabsf(u); }
-__device__ __forceinline__ double huber_phi(float u, float delta) {
-    const float a = fabsf(u);
-    return a <= delta ? 0.5 * (double)a * (double)a : (double)delta * ((double)a - 0.5 * (double)delta);
-}
+// gradient, reads the differences it shares with its successors.  Maps are a few MB: the neighbour reads hit L2 (the cube's
+// kernels, where that no longer holds, are in huber_vox.hip).  huber_phi / huber_dphi / huber_w: huber_dev.h.
 
-// K block sums in a fixed order; part[k * gridDim.x + blockIdx.x] = sum over the block of v[k]
-template <int K>
-__device__ inline void block_sums_to(double (&v)[K], double *__restrict__ part) {
-    __shared__ double sm[K][TPB / 64];
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_down(v[k], o, 64);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) sm[k][threadIdx.x >> 6] = v[k];
-    __syncthreads();
-    if (threadIdx.x < K) {
-        double s = 0.0;
-        for (int w = 0; w < TPB / 64; ++w) s += sm[threadIdx.x][w];
-        part[(long)threadIdx.x * gridDim.x + blockIdx.x] = s;
-    }
-}
-
+// block_sums_to<K>, parts_reduce_kernel: huber_dev.h
 struct PixelNbrs {   // (t, i, j) of element e of [T][na][nb] and the circular neighbour offsets inside its plane
     long base;
     int c, im, ip, jm, jp;
@@ -1291,14 +1260,6 @@ __global__ __launch_bounds__(TPB) void huber_curv_kernel(const float *__restrict
         acc[2] += wr * br * br + wc * bcl * bcl;
     }
     block_sums_to<3>(acc, part);
-}
-
-// out[k] = sum_i part[k * nparts + i], one block per k, reduce_final_kernel's order
-__global__ __launch_bounds__(TPB) void parts_reduce_kernel(const double *__restrict__ part, int nparts, double *__restrict__ out) {
-    double s = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += TPB) s += part[(long)blockIdx.x * nparts + i];
-    s = block_sum(s);
-    if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
 
 inline int nblocks(long n, int cap = 2048) {

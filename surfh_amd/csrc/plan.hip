@@ -204,8 +204,8 @@ struct surfh_plan {
     long isize = 0, osize = 0;
     // CG
     float *cg_x = nullptr, *cg_r = nullptr, *cg_d = nullptr, *cg_q = nullptr, *cg_b = nullptr, *cg_y = nullptr, *cg_qm = nullptr, *cg_dd = nullptr;
-    float *cg_hg = nullptr;                        // surfh_mmmg_huber: -gradient of the non-quadratic criterion
-    double *dscal = nullptr, *dscratch = nullptr;   // [8] device scalars, [1024] partial sums
+    float *cg_hg = nullptr;                        // surfh_mmmg_huber(_vox): -gradient of the non-quadratic criterion
+    double *dscal = nullptr, *dscratch = nullptr;   // [16] device scalars, partial sums (>= 1024, and what huber_vox.hip asks for)
     double *cg_hist = nullptr;                     // device-resident r.r trace of the no-host-sync CG blocks (CG_HIST_CAP entries)
     int cg_hist_n = 0;
     // plane-wise CG with device-resident data (surfh_cg_planes_begin_dev / _step_dev): per-plane scalars [3][Lc] (the host-buffer
@@ -1921,7 +1921,7 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
         }
     }
     if (dev_alloc(&p->io_x, (size_t)p->isize) || dev_alloc(&p->io_y, (size_t)p->osize) || dev_alloc(&p->cg_y, (size_t)p->osize) ||
-        dev_alloc(&p->dscal, 8) || dev_alloc(&p->dscratch, 1024))
+        dev_alloc(&p->dscal, 16) || dev_alloc(&p->dscratch, std::max((size_t)1024, launch_huber_vox_scratch_doubles())))
         return bail(1);
     if (hipDeviceSynchronize() != hipSuccess) return bail(fail("device error during plan creation: %s", hipGetErrorString(hipGetLastError())));
     *out = p;
@@ -2561,12 +2561,23 @@ int surfh_huber_curv_dev(surfh_plan *p, const float *x_dev, const float *p0_dev,
     return 0;
 }
 
-int surfh_mmmg_huber(surfh_plan *p, const float *y, double mu, double mu_reg, double delta, const float *x0, int32_t max_iter,
-                     double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit, double *prior_value,
-                     surfh_cg_callback callback, void *user) {
-    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
-    if (p->T <= 0) return fail("surfh_mmmg_huber needs templates (the priors act on abundance maps)");
-    if (huber_args(mu_reg, delta)) return 1;
+namespace {
+// The prior of one 3MG/Huber run: `nfam` families of differences with their weights, and the two stencil passes on the solver's
+// vectors.  grad: out = src - sum_f reg[f] D_f^T phi'(D_f x), sums[0] = out.out, sums[1 + f] = sum phi of family f;
+// curv: sums[3 f ..] = the (p0, p0), (p0, p1), (p1, p1) block of family f under w(D_f x).  The weights enter on the host, in float64.
+struct HuberPrior {
+    int nfam;
+    double reg[2];
+    const char *what;                                                       // names the solver in its error message
+    int (*grad)(surfh_plan *p, const HuberPrior &h, const float *x, const float *src, float *out, double *sums);
+    int (*curv)(surfh_plan *p, const HuberPrior &h, const float *x, const float *p0, const float *p1, double *sums);
+    float delta[2];
+};
+
+// the loop both Huber solvers run; prior_values receives nfam doubles (may be NULL)
+int mmmg_huber_loop(surfh_plan *p, const HuberPrior &hp, const float *y, double mu, const float *x0, int32_t max_iter, double tol,
+                    int32_t refresh, float *x, double *grad_norm, int32_t *nit, double *prior_values, surfh_cg_callback callback,
+                    void *user) {
     std::vector<float> hx;
     HIP_OK(hipSetDevice(p->dev));
     if (ensure_cg(p)) return 1;
@@ -2574,10 +2585,9 @@ int surfh_mmmg_huber(surfh_plan *p, const float *y, double mu, double mu_reg, do
     if (!p->cg_hg && dev_alloc(&p->cg_hg, (size_t)p->isize)) return 1;
     hipStream_t s = p->stream;
     const long n = p->isize;
-    const int T = p->T, Na = p->Na, Nb = p->Nb;
-    const float dl = (float)delta;
+    const int F = hp.nfam;
     float *r = p->cg_r, *m = p->cg_d, *d = p->cg_dd, *qd = p->cg_q, *qm = p->cg_qm, *ng = p->cg_hg;
-    double *sc = p->dscal;
+    double *sc = p->dscal;               // [0 .. F] huber_grad (|g|^2, F prior values), [F+1, F+2] dots, [F+3 .. 4F+2] huber_curv
     HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
     if (x0)
         HIP_OK(hipMemcpyAsync(p->cg_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
@@ -2586,31 +2596,30 @@ int surfh_mmmg_huber(surfh_plan *p, const float *y, double mu, double mu_reg, do
     LAUNCH_OK(launch_fill_zero(s, m, n));
     LAUNCH_OK(launch_fill_zero(s, qm, n));
     if (solver_setup(p, p->io_y, p->cg_x, mu, 0.0)) return 1;          // r = b - mu A^T A x: the data part of -g
-    double h[7], prior = 0.0;
+    double h[11], prior[2] = {0.0, 0.0};
     *nit = 0;
     for (int it = 0;; ++it) {
-        // -g, |g|^2 and the prior value; then h2 = -g.Q_D m, h3 = m.Q_D m, h4.. = prior block of (-g, m) under w(D x)
-        {
-            Prof pr(p, "huber_grad");
-            LAUNCH_OK(launch_huber_grad(s, p->cg_x, r, ng, T, Na, Nb, -(float)mu_reg, dl, p->dscratch, sc + 0));
-        }
-        LAUNCH_OK(launch_dot(s, ng, qm, n, p->dscratch, sc + 2));
-        LAUNCH_OK(launch_dot(s, m, qm, n, p->dscratch, sc + 3));
-        {
-            Prof pr(p, "huber_curv");
-            LAUNCH_OK(launch_huber_curv(s, p->cg_x, ng, m, T, Na, Nb, dl, p->dscratch, sc + 4));
-        }
-        HIP_OK(hipMemcpyAsync(h, sc, 7 * sizeof(double), hipMemcpyDeviceToHost, s));
+        // -g, |g|^2 and the prior values; then -g.Q_D m, m.Q_D m and the prior blocks of (-g, m) under w(D x)
+        if (hp.grad(p, hp, p->cg_x, r, ng, sc + 0)) return 1;
+        LAUNCH_OK(launch_dot(s, ng, qm, n, p->dscratch, sc + F + 1));
+        LAUNCH_OK(launch_dot(s, m, qm, n, p->dscratch, sc + F + 2));
+        if (hp.curv(p, hp, p->cg_x, ng, m, sc + F + 3)) return 1;
+        HIP_OK(hipMemcpyAsync(h, sc, (3 + 4 * F) * sizeof(double), hipMemcpyDeviceToHost, s));
         HIP_OK(hipStreamSynchronize(s));
         grad_norm[it] = std::sqrt(h[0]);
-        prior = h[1];
+        for (int f = 0; f < F; ++f) prior[f] = h[1 + f];
         if (const int rc = it > 0 ? callback_iterate(p, callback, user, it, grad_norm, p->cg_x, hx) : CB_GO_ON) {
             if (rc == CB_STOP) break;
             return 1;
         }
         if (it >= max_iter || grad_norm[it] < (double)n * tol) break;
-        const double c00 = h[4], c01 = h[5], c11 = h[6];
-        const double mBm = h[3] + mu_reg * c11, beta = mBm > 0.0 ? -(h[2] + mu_reg * c01) / mBm : 0.0;
+        double c[2][3], gBm = h[F + 1], mBm = h[F + 2];
+        for (int f = 0; f < F; ++f) {
+            for (int k = 0; k < 3; ++k) c[f][k] = h[F + 3 + 3 * f + k];
+            gBm += hp.reg[f] * c[f][1];
+            mBm += hp.reg[f] * c[f][2];
+        }
+        const double beta = mBm > 0.0 ? -gBm / mBm : 0.0;
         LAUNCH_OK(launch_lincomb(s, d, ng, m, n, beta));
         if (normal_dev(p, d, qd, mu)) return 1;
         // h0 = d.Q_D d, h1 = d.Q_D m, h2 = d.(-g), h3 = m.(-g)
@@ -2620,15 +2629,20 @@ int surfh_mmmg_huber(surfh_plan *p, const float *y, double mu, double mu_reg, do
         LAUNCH_OK(launch_dot(s, m, ng, n, p->dscratch, sc + 3));
         HIP_OK(hipMemcpyAsync(h, sc, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
         HIP_OK(hipStreamSynchronize(s));
-        const double dWd = c00 + beta * (2.0 * c01 + beta * c11), dWm = c01 + beta * c11;
-        const double dBd = h[0] + mu_reg * dWd, dBm = h[1] + mu_reg * dWm, dg = h[2], mg = h[3];
-        if (!(dBd > 0.0)) return fail("3MG (Huber): non-positive curvature d.Bd = %g at iteration %d", dBd, it);
+        double dBd = h[0], dBm = h[1];
+        const double dg = h[2], mg = h[3];
+        for (int f = 0; f < F; ++f) {                                  // the block of (d, m) from that of (-g, m), by linearity
+            const double dWd = c[f][0] + beta * (2.0 * c[f][1] + beta * c[f][2]), dWm = c[f][1] + beta * c[f][2];
+            dBd += hp.reg[f] * dWd;
+            dBm += hp.reg[f] * dWm;
+        }
+        if (!(dBd > 0.0)) return fail("3MG (%s): non-positive curvature d.Bd = %g at iteration %d", hp.what, dBd, it);
         double s0 = dg / dBd, s1 = 0.0;
         if (mBm > 0.0) {
-            const double sq = std::sqrt(dBd * mBm), c = dBm / sq, det = 1.0 - c * c;      // scaled 2x2 system
+            const double sq = std::sqrt(dBd * mBm), cc = dBm / sq, det = 1.0 - cc * cc;      // scaled 2x2 system
             if (det > 1e-12) {
-                s0 = (dg / dBd - c * mg / sq) / det;
-                s1 = (mg / mBm - c * dg / sq) / det;
+                s0 = (dg / dBd - cc * mg / sq) / det;
+                s1 = (mg / mBm - cc * dg / sq) / det;
             }
         }
         const bool fresh = refresh > 0 && it % refresh == 0;
@@ -2642,10 +2656,95 @@ int surfh_mmmg_huber(surfh_plan *p, const float *y, double mu, double mu_reg, do
         }
         *nit = it + 1;
     }
-    if (prior_value) *prior_value = prior;
+    if (prior_values)
+        for (int f = 0; f < F; ++f) prior_values[f] = prior[f];
     HIP_OK(hipMemcpyAsync(x, p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
     return 0;
+}
+
+// the maps' prior: one family (rows and columns under one weight and one threshold)
+int maps_grad(surfh_plan *p, const HuberPrior &h, const float *x, const float *src, float *out, double *sums) {
+    Prof pr(p, "huber_grad");
+    LAUNCH_OK(launch_huber_grad(p->stream, x, src, out, p->T, p->Na, p->Nb, -(float)h.reg[0], h.delta[0], p->dscratch, sums));
+    return 0;
+}
+int maps_curv(surfh_plan *p, const HuberPrior &h, const float *x, const float *p0, const float *p1, double *sums) {
+    Prof pr(p, "huber_curv");
+    LAUNCH_OK(launch_huber_curv(p->stream, x, p0, p1, p->T, p->Na, p->Nb, h.delta[0], p->dscratch, sums));
+    return 0;
+}
+// the cube's prior: the in-plane family and the wavelength family
+int vox_grad(surfh_plan *p, const HuberPrior &h, const float *x, const float *src, float *out, double *sums) {
+    Prof pr(p, "huber_vox_grad");
+    LAUNCH_OK(launch_huber_vox_grad(p->stream, x, src, out, p->Lc, p->Na, p->Nb, -(float)h.reg[0], h.delta[0], -(float)h.reg[1],
+                                    h.delta[1], p->dscratch, sums));
+    return 0;
+}
+int vox_curv(surfh_plan *p, const HuberPrior &h, const float *x, const float *p0, const float *p1, double *sums) {
+    Prof pr(p, "huber_vox_curv");
+    LAUNCH_OK(launch_huber_vox_curv(p->stream, x, p0, p1, p->Lc, p->Na, p->Nb, h.delta[0], h.delta[1], p->dscratch, sums));
+    return 0;
+}
+}  // namespace
+
+int surfh_mmmg_huber(surfh_plan *p, const float *y, double mu, double mu_reg, double delta, const float *x0, int32_t max_iter,
+                     double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit, double *prior_value,
+                     surfh_cg_callback callback, void *user) {
+    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (p->T <= 0) return fail("surfh_mmmg_huber needs templates (the priors act on abundance maps)");
+    if (huber_args(mu_reg, delta)) return 1;
+    const HuberPrior hp = {1, {mu_reg, 0.0}, "Huber", maps_grad, maps_curv, {(float)delta, 0.f}};
+    return mmmg_huber_loop(p, hp, y, mu, x0, max_iter, tol, refresh, x, grad_norm, nit, prior_value, callback, user);
+}
+
+// ---- the same solver on the cube itself (the reference's vox_reconstruction, surfh/ToolsDir/algorithms.py:27-71): no templates,
+// Huber priors on the row, column and wavelength differences, the two spatial families under (spat_reg, spat_delta), the spectral
+// one under (spec_reg, spec_delta).  The majorant gains the block spec_reg Dl^T diag(w(Dl x)) Dl; everything else is the loop above.
+int surfh_huber_vox_prior_dev(surfh_plan *p, const float *x_dev, float *g_dev, double spat_reg, double spat_delta, double spec_reg,
+                              double spec_delta, double *values) {
+    if (!p || !x_dev || !g_dev) return fail("null argument");
+    if (p->T > 0) return fail("the voxel-wise prior is defined on the cube (needs a plan without templates)");
+    if (huber_args(spat_reg, spat_delta) || huber_args(spec_reg, spec_delta)) return 1;
+    HIP_OK(hipSetDevice(p->dev));
+    {
+        Prof pr(p, "huber_vox_grad");
+        LAUNCH_OK(launch_huber_vox_grad(p->stream, x_dev, g_dev, g_dev, p->Lc, p->Na, p->Nb, (float)spat_reg, (float)spat_delta,
+                                        (float)spec_reg, (float)spec_delta, p->dscratch, p->dscal + 0));
+    }
+    double h[3];
+    HIP_OK(hipMemcpyAsync(h, p->dscal, 3 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    if (values) {
+        values[0] = h[1];
+        values[1] = h[2];
+    }
+    return 0;
+}
+int surfh_huber_vox_curv_dev(surfh_plan *p, const float *x_dev, const float *p0_dev, const float *p1_dev, double spat_delta,
+                             double spec_delta, double *sums) {
+    if (!p || !x_dev || !p0_dev || !p1_dev || !sums) return fail("null argument");
+    if (p->T > 0) return fail("the voxel-wise prior is defined on the cube (needs a plan without templates)");
+    if (huber_args(0.0, spat_delta) || huber_args(0.0, spec_delta)) return 1;
+    HIP_OK(hipSetDevice(p->dev));
+    {
+        Prof pr(p, "huber_vox_curv");
+        LAUNCH_OK(launch_huber_vox_curv(p->stream, x_dev, p0_dev, p1_dev, p->Lc, p->Na, p->Nb, (float)spat_delta, (float)spec_delta,
+                                        p->dscratch, p->dscal + 0));
+    }
+    HIP_OK(hipMemcpyAsync(sums, p->dscal, 6 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int surfh_mmmg_huber_vox(surfh_plan *p, const float *y, double mu, double spat_reg, double spat_delta, double spec_reg,
+                         double spec_delta, const float *x0, int32_t max_iter, double tol, int32_t refresh, float *x,
+                         double *grad_norm, int32_t *nit, double *prior_values, surfh_cg_callback callback, void *user) {
+    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (p->T > 0) return fail("surfh_mmmg_huber_vox reconstructs the cube: it needs a plan without templates (n_templates = 0)");
+    if (huber_args(spat_reg, spat_delta) || huber_args(spec_reg, spec_delta)) return 1;
+    const HuberPrior hp = {2, {spat_reg, spec_reg}, "Huber, voxel-wise", vox_grad, vox_curv, {(float)spat_delta, (float)spec_delta}};
+    return mmmg_huber_loop(p, hp, y, mu, x0, max_iter, tol, refresh, x, grad_norm, nit, prior_values, callback, user);
 }
 
 // ---- CG on independent planes: the 2-D deconvolution path (criterion_2D.py:60-250 per image, batched over wavelength)

@@ -84,6 +84,7 @@ class Channel(ChannelGeometry):
 
 class spectroSigRLSCT(LinOp):
     huber_prior_value = None            # prior value of the last mmmg(delta=...) result (set by mmmg)
+    huber_prior_values = None           # (spatial, spectral) prior values of the last mmmg_vox result
 
     def __init__(self, sotf, templates, alpha_axis, beta_axis, wavelength_axis, instrs: List[instru.IFU],
                  step_degree: float, pointings: Sequence[instru.CoordList], *, device: int = 0,
@@ -350,6 +351,43 @@ class spectroSigRLSCT(LinOp):
         out = C.c_double()
         _lib.check(self._L.surfh_huber_prior_dev(self._plan, _ptr(x_t), _ptr(g_t), float(mu_reg), float(delta), C.byref(out)))
         return out.value
+
+    # ---- the cube itself under Huber priors (models without templates) -----------------------
+    def mmmg_vox(self, data, mu=1.0, spat_reg=1.0, spat_delta=1.0, spec_reg=1.0, spec_delta=1.0, x0=None, max_iter=10, tol=1e-12,
+                 refresh=50, callback=None):
+        """3MG on the cube ``[Lc, Na, Nb]`` with Huber priors on its row, column and wavelength differences (the reference's
+        vox_reconstruction, algorithms.py:27-71; include/surfh_amd.h: surfh_mmmg_huber_vox):
+
+            mu |y - A x|^2 / 2 + spat_reg sum_{k in r,c} sum phi_spat_delta(D_k x) + spec_reg sum phi_spec_delta(D_l x)
+
+        ``D_r`` / ``D_c`` circular inside every plane, ``D_l x = x[l+1] - x[l]`` open along wavelength (``Lc - 1`` planes).  The
+        reference's legacy ``Spectro`` model is ``(alpha, beta, lambda)``, hence its ``Diff(0) / Diff(1) / Diff(2)``; the cube
+        here is ``[lambda][alpha][beta]``.  Needs a model built with ``templates=None``.  Returns ``(x, grad_norm, nit)`` as
+        ``mmmg`` and leaves ``self.huber_prior_values = (spatial, spectral)``.  A delta of ``inf`` makes its term quadratic, a
+        weight of 0 switches it off.  qmm and aljabr are not available to pin the restatement or the border conventions."""
+        self.huber_prior_values = None
+        if self.lmm:
+            raise ValueError("mmmg_vox reconstructs the cube itself: build the model with templates=None "
+                             "(mmmg(delta=...) is the solver of a template model)")
+        x, gn, nit, self.huber_prior_values = _lib.solve_huber_vox(self, data, mu, spat_reg, spat_delta, spec_reg, spec_delta, x0,
+                                                                   max_iter, tol, refresh, callback)
+        return x, gn, nit
+
+    def huber_vox_prior_dev(self, x_t, g_t, spat_reg: float, spat_delta: float, spec_reg: float, spec_delta: float):
+        """g += spat_reg sum_k D_k^T phi'(D_k x) + spec_reg D_l^T phi'(D_l x) on device cubes [Lc, Na, Nb]; returns the spatial
+        and the spectral sum of phi (synchronises)."""
+        out = np.zeros(2, dtype=np.float64)
+        _lib.check(self._L.surfh_huber_vox_prior_dev(self._plan, _ptr(x_t), _ptr(g_t), float(spat_reg), float(spat_delta),
+                                                     float(spec_reg), float(spec_delta), _lib.dptr(out)))
+        return float(out[0]), float(out[1])
+
+    def huber_vox_curv_dev(self, x_t, p0_t, p1_t, spat_delta: float, spec_delta: float) -> np.ndarray:
+        """[2, 3]: sum w (D p0)^2, (D p0)(D p1), (D p1)^2 under the spatial weights (row 0: rows and columns together) and under
+        the spectral weights (row 1), on device cubes: the prior blocks of the majorant before spat_reg / spec_reg."""
+        out = np.zeros(6, dtype=np.float64)
+        _lib.check(self._L.surfh_huber_vox_curv_dev(self._plan, _ptr(x_t), _ptr(p0_t), _ptr(p1_t), float(spat_delta),
+                                                    float(spec_delta), _lib.dptr(out)))
+        return out.reshape(2, 3)
 
     # ---- helpers the reference's drivers call -----------------------------------------------
     def cubeTomaps(self, cube):
