@@ -283,6 +283,23 @@ int surfh_prior_spec_add_dev(surfh_plan *plan, const float *dt_dev, float *qt_de
  * 0 = "separated": Dr^T Dr + Dc^T Dc, circular first differences NpDiff_r / NpDiff_c (fusion_CT.py:16-43) -- the default;
  * 1 = "joint": D^T D with D the circular convolution by the 3 x 3 Laplacian (Difference_Operator_Joint, fusion_CT.py:45-62).  */
 int surfh_set_prior(surfh_plan *plan, int32_t kind);
+/* ---- data weights: plan state, like the prior ----
+ * With weights w [osize] (the layout of y; every w[i] finite and >= 0) the data term of every solver is
+ *   mu (y - A x)^T W (y - A x) / 2,  W = diag(w):
+ * a 0/1 mask of bad samples, an inverse variance 1/sigma^2, or their product.  They act
+ *   - in every normal operator: surfh_normal_dev, surfh_fwadj(_dev), surfh_normal_spec_dev and the operators inside the solvers
+ *     apply mu A^T W A;
+ *   - in the right-hand side of every solver (surfh_cg(_cb), surfh_mmmg, surfh_mmmg_huber(_vox), surfh_cg_planes(_cb),
+ *     surfh_mmmg_planes(_cb), surfh_cg_planes_begin_dev): b = mu A^T W y, with W y formed by a select -- a sample of weight 0
+ *     contributes nothing whatever its datum, NaN and Inf included.
+ * They do NOT act on surfh_forward*, surfh_adjoint*, surfh_adjoint_ref*, surfh_forward_spec_dev and surfh_adjoint_spec_dev,
+ * which stay A and A^T.  Priors, stopping rules and traces are untouched.
+ * Both calls copy the weights into the plan (the caller's buffer is free afterwards); NULL clears them and frees the copies.
+ * Both fail on a negative, NaN or infinite weight (the device form synchronises the plan's stream for its check) and on plans
+ * without detector channels (n_channels = 0, the Model_WCT plans); a failed call leaves the plan's weights as they were. */
+int surfh_set_data_weights(surfh_plan *plan, const float *w_host);
+int surfh_set_data_weights_dev(surfh_plan *plan, const float *w_dev);
+int surfh_has_data_weights(const surfh_plan *plan);                                            /* 1 / 0 */
 int surfh_dot_dev(surfh_plan *plan, const float *a_dev, const float *b_dev, int64_t n, double *out_host);
 /* x += s d ; r -= s q ; returns r.r  (s = rr / d.q computed on device from rr_in)    */
 int surfh_cg_step_dev(surfh_plan *plan, float *x_dev, float *r_dev, const float *d_dev,

@@ -4,6 +4,7 @@
     python scripts/main_fusion.py -fd <fusion_dir> -np 501 -hp 5e3 -ni 50 -nt 4 -m lcg
     python scripts/main_fusion.py --synthetic config2 -hp 5e3 -ni 50         # no input files needed
     python scripts/main_fusion.py --synthetic small --voxel -m mmmg -hp 40 --delta 0.005 --spec_reg 20 --spec_delta 0.01
+    python scripts/main_fusion.py -fd <fusion_dir> -hp 5e3 -ni 50 --mask_nan --weights inv_variance.npy
 
 Inputs under ``fusion_dir`` (reference layout, main_fusion.py:65-75): ``Templates/`` (wavelength axis + NMF templates,
 .npy), ``PSF/`` (PSF stack, .npy), ``Filtered_slices/`` (one FITS file per band and pointing) -> results in
@@ -11,6 +12,11 @@ Inputs under ``fusion_dir`` (reference layout, main_fusion.py:65-75): ``Template
 ``res_cube.npy`` (``mapsToCube`` of them), ``criterion.npy`` (criterion trace, fusion_CT.py:163-175,242-265).  ``--voxel`` reconstructs the cube itself instead (no
 templates, Huber priors on its row, column and wavelength differences: the reference's vox_reconstruction,
 surfh/ToolsDir/algorithms.py:27-71) and writes ``res_cube.npy`` and ``criterion.npy`` under ``..._vox/``.
+
+``--weights FILE.npy`` gives every detector sample a weight in the data term (``[osize]``, the layout of the data: an inverse
+variance, a 0/1 mask of bad pixels), ``--mask_nan`` gives the samples that are NaN or Inf weight 0 -- the reference's real-data
+scripts overwrite them with 0 and fit the model to those zeros (scripts/fusion/fusion_real_data.py:175-177).  Either flag adds
+``_wgt`` to the result directory's name and ``weights.npy`` to its files; without them nothing changes.
 
 The FITS reader needs astropy (FITS I/O is outside the hot path and not rebuilt here); when it is not importable the
 same arrays may be given as ``Filtered_slices/<band>_<k>.npz`` with fields ``data`` (raveled ``[Ldet, S, a_out]`` as in
@@ -27,7 +33,8 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from surfh_amd import instru, synth                                   # noqa: E402
-from surfh_amd.fusion import QuadCriterion_MRS                        # noqa: E402
+from surfh_amd.fusion import QuadCriterion_MRS, weights_from_data     # noqa: E402
+from surfh_amd.weights import check_data_weights                      # noqa: E402
 from surfh_amd.models import spectroSigRLSCT                          # noqa: E402
 
 LIST_CHAN = ['1a', '1b', '1c', '2a', '2b', '2c', '3a', '3b', '3c', '4a', '4b', '4c']
@@ -115,54 +122,73 @@ def create_model(sotf, templates, origin_alpha_axis, origin_beta_axis, wavel_axi
                            instrs=list(instruments.values()), step_degree=step_angle, pointings=pointings, device=device)
 
 
-def result_dir_name(method, n_channels, n_templates, niter, hyper_parameter, scale_data, delta=None, voxel=False):
-    """main_fusion.py:182; with a Huber threshold `delta` (not in the reference) `_huber_<delta>` is appended, and `_vox` for a
-    voxel-wise reconstruction."""
+def result_dir_name(method, n_channels, n_templates, niter, hyper_parameter, scale_data, delta=None, voxel=False, weighted=False):
+    """main_fusion.py:182; with a Huber threshold `delta` (not in the reference) `_huber_<delta>` is appended, `_vox` for a
+    voxel-wise reconstruction, and `_wgt` for a run under data weights."""
     name = f'{method}_MC_{n_channels}_MO_4_Temp_{n_templates}_nit_{str(niter)}_mu_{str("{:.2e}".format(hyper_parameter))}_SD_{scale_data}'
     if delta is not None:
         name += f'_huber_{delta:.2e}'
     if voxel:
         name += '_vox'
+    if weighted:
+        name += '_wgt'
     return name + '/'
 
 
-def voxel_reconstruction(spectro_model, ndata, result_path, spat_reg, spat_th, spec_reg, spec_th, niter, method, scale_data):
+def data_weights(ndata, weights_file=None, mask_nan=False):
+    """The data and their weights as the two flags ask: (ndata, None) without either; `--weights` loads `[osize]` weights
+    (ValueError unless finite and >= 0); `--mask_nan` gives the samples that are not finite weight 0 and the datum 0
+    (`weights_from_data`), on top of the loaded weights if both are given."""
+    if not weights_file and not mask_nan:
+        return ndata, None
+    w = np.ones(ndata.size) if not weights_file else check_data_weights(np.load(weights_file), ndata.size).astype(np.float64)
+    if mask_nan:
+        ndata, keep = weights_from_data(ndata)
+        w = w * keep.ravel()
+    return ndata, w
+
+
+def voxel_reconstruction(spectro_model, ndata, result_path, spat_reg, spat_th, spec_reg, spec_th, niter, method, scale_data,
+                         weights=None):
     """The cube itself by vox_reconstruction (surfh_amd/algorithms.py): res_cube.npy [Lc, N, N], and in criterion.npy the
     criterion at the start and after iterations 1, 6, 11, ... -- the trace `reconstruction_method` writes (perf_crit = 1)."""
     from surfh_amd.algorithms import vox_criterion, vox_reconstruction
     path = pathlib.Path(result_path) / result_dir_name(method, len(spectro_model.instrs), 0, niter, spat_reg, scale_data, spat_th,
-                                                       voxel=True)
+                                                       voxel=True, weighted=weights is not None)
     path.mkdir(parents=True, exist_ok=True)
-    init = spectro_model.adjoint(ndata)
-    crit = [vox_criterion(ndata, spectro_model, init, spat_reg, spat_th, spec_reg, spec_th)]
+    init = spectro_model.adjoint(ndata if weights is None else np.where(weights > 0, weights * np.where(weights > 0, ndata, 0.), 0.))
+    crit = [vox_criterion(ndata, spectro_model, init, spat_reg, spat_th, spec_reg, spec_th, weights=weights)]
 
     def trace(it, grad_norm, x):
         if it % 5 == 1:
-            crit.append(vox_criterion(ndata, spectro_model, x, spat_reg, spat_th, spec_reg, spec_th))
+            crit.append(vox_criterion(ndata, spectro_model, x, spat_reg, spat_th, spec_reg, spec_th, weights=weights))
             print(f"iteration {it}: criterion {crit[-1]:.6e}, |grad| {grad_norm[-1]:.3e}")
         return False
 
     res = vox_reconstruction(ndata, spectro_model, spat_reg=spat_reg, spat_th=spat_th, spec_reg=spec_reg, spec_th=spec_th, init=init,
-                             max_iter=niter, callback=trace)
+                             max_iter=niter, callback=trace, weights=weights)
     print(f"voxel-wise 3MG: {res.nit} iterations, criterion {crit[0]:.6e} -> {crit[-1]:.6e}")
     print(f"Results save in {path}")
     np.save(path / 'res_cube.npy', res.x.reshape(spectro_model.ishape))
     np.save(path / 'criterion.npy', np.array(crit))
+    if weights is not None:
+        np.save(path / 'weights.npy', weights)
     return res, path
 
 
 def reconstruction_method(spectro_model, ndata, templates, result_path, hyper_parameter, niter, method, scale_data,
-                          checkpoint_every=0, resume=None, delta=None):
+                          checkpoint_every=0, resume=None, delta=None, weights=None):
     """main_fusion.py:162-206: regularised least squares by CG, then the three result files.  Not in the reference:
     `checkpoint_every` > 0 writes the iterate to checkpoint.npz in the result directory every that many iterations,
     `resume` (such a file) warm-starts from it and runs the iterations that are left; `delta` replaces the quadratic
-    priors by Huber potentials of that threshold (3MG only)."""
+    priors by Huber potentials of that threshold (3MG only); `weights` `[osize]` weigh the samples of the data term and are
+    stored beside the results as weights.npy."""
     value_init = 0
     path = pathlib.Path(result_path) / result_dir_name(method, len(spectro_model.instrs), templates.shape[0], niter,
-                                                       hyper_parameter, scale_data, delta)
+                                                       hyper_parameter, scale_data, delta, weighted=weights is not None)
     path.mkdir(parents=True, exist_ok=True)
     crit = QuadCriterion_MRS(mu_spectro=1, y_spectro=np.copy(ndata), model_spectro=spectro_model,
-                             mu_reg=hyper_parameter, printing=True, gradient="separated", delta=delta)
+                             mu_reg=hyper_parameter, printing=True, gradient="separated", delta=delta, weights=weights)
     if resume:
         from surfh_amd.fusion import load_checkpoint
         x_saved, it_done, _ = load_checkpoint(resume)
@@ -176,6 +202,8 @@ def reconstruction_method(spectro_model, ndata, templates, result_path, hyper_pa
     np.save(path / 'res_x.npy', res.x)
     np.save(path / 'res_cube.npy', y_cube)
     np.save(path / 'criterion.npy', crit.L_crit_val)
+    if weights is not None:
+        np.save(path / 'weights.npy', weights)
     return res, path
 
 
@@ -212,8 +240,11 @@ def synthetic_problem(name, npix):
                    'spatial differences (--delta defaults to 1), --spec_reg and --spec_delta the spectral ones.')
 @click.option('--spec_reg', default=1., type=float, help='Weight of the spectral Huber prior (--voxel).')
 @click.option('--spec_delta', default=1., type=float, help='Huber threshold of the spectral differences (--voxel).')
+@click.option('--weights', 'weights_file', default=None, type=str,
+              help='.npy file of per-sample data weights [osize] (inverse variance, 0/1 mask), finite and >= 0.')
+@click.option('--mask_nan', is_flag=True, default=False, help='Give the data samples that are NaN or Inf weight 0.')
 def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, method, verbose, synthetic, device, checkpoint_every=0,
-         resume=None, delta=None, voxel=False, spec_reg=1., spec_delta=1.):
+         resume=None, delta=None, voxel=False, spec_reg=1., spec_delta=1., weights_file=None, mask_nan=False):
     if voxel and method == 'lcg':
         raise click.BadParameter('the voxel-wise criterion is not quadratic; use --method mmmg with --voxel', param_hint='--voxel')
     if voxel and not spec_delta > 0:
@@ -254,6 +285,13 @@ def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, meth
                              data_dict, device=device)
         ndata = np.concatenate([np.array(data_dict['data'][chan]).ravel() for chan in LIST_CHAN])
 
+    try:
+        ndata, weights = data_weights(ndata, weights_file, mask_nan)
+    except ValueError as e:
+        raise click.BadParameter(str(e), param_hint='--weights')
+    if weights is not None:
+        log.info(f'Data weights: {int(np.sum(weights == 0))} of {weights.size} samples masked')
+
     if scale_data:
         log.info('Data scaling enable')
         ndata = model.real_data_janskySR_to_jansky(ndata)
@@ -261,11 +299,11 @@ def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, meth
     log.info(f'Start {method} algorithm')
     if voxel:
         voxel_reconstruction(model, ndata, paths["result_path"], hyper_parameter, 1. if delta is None else delta, spec_reg, spec_delta,
-                             niter, method, scale_data)
+                             niter, method, scale_data, weights=weights)
         model.close()
         return
     reconstruction_method(model, ndata, templates, paths["result_path"], hyper_parameter, niter, method, scale_data,
-                          checkpoint_every=checkpoint_every, resume=resume, delta=delta)
+                          checkpoint_every=checkpoint_every, resume=resume, delta=delta, weights=weights)
     model.close()
 
 

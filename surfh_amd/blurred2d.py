@@ -21,9 +21,10 @@ import numpy as np
 
 from . import _lib, instru
 from .linop import LinOp
+from .weights import DataWeights
 
 
-class Blurred2D(LinOp):
+class Blurred2D(DataWeights, LinOp):
     def __init__(self, sotf, alpha_axis, beta_axis, instr: instru.IFU, step_degree: float, pointings: instru.CoordList):
         self.sotf = sotf
         self.alpha_axis = np.asarray(alpha_axis, dtype=np.float64)
@@ -202,13 +203,15 @@ class Blurred2D(LinOp):
         return self._call(self._L.surfh_adjoint, data, self.osize, self.ishape)
 
     # ---- solver: regularised least squares by CG, one independent 2-D problem per plane -------------------
-    def cg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None):
+    def cg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, weights=None):
         """Device-resident linear CG on  mu |y - A x|^2 + mu_reg (|Dr x|^2 + |Dc x|^2)  (criterion_2D.py:60-250 with
         `qmm.lcg` restated).  Batched model: every plane is its own problem with its own step sizes; returns
         ``(x, grad_norm, nit)`` with ``grad_norm`` of shape ``[nit+1]`` (single image) or ``[nit+1, n_planes]``.
-        ``callback(it, grad_norm, x)`` as for ``spectroSigRLSCT.cg``."""
-        return _lib.solve(self, self._L.surfh_cg_planes_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback,
-                          planes=self.n_planes, squeeze=not self.batched)
+        ``callback(it, grad_norm, x)`` as for ``spectroSigRLSCT.cg``.  ``weights``: data weights in the layout of ``data`` for this
+        solve only, data term mu (y - A x)^T diag(w) (y - A x) (``set_data_weights``); None: the model's own state."""
+        with self.installed_weights(weights):
+            return _lib.solve(self, self._L.surfh_cg_planes_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback,
+                              planes=self.n_planes, squeeze=not self.batched)
 
     # ---- instrumentation (HIP events on the plan's stream, as spectroSigRLSCT) -----------------------------
     def profile_enable(self, on=True):
@@ -229,8 +232,12 @@ class Blurred2D(LinOp):
     def forward_dev(self, x_t, y_t):
         _lib.check(self._L.surfh_forward_dev(self._plan, C.c_void_p(x_t.data_ptr()), C.c_void_p(y_t.data_ptr())))
 
-    def cg_begin_dev(self, y_t, x_t, mu=1.0, mu_reg=0.0):
-        """``x_t`` [n_planes, Na, Nb] float32 on the plan's device: the start, then the current iterate (updated in place)."""
+    def cg_begin_dev(self, y_t, x_t, mu=1.0, mu_reg=0.0, weights=None):
+        """``x_t`` [n_planes, Na, Nb] float32 on the plan's device: the start, then the current iterate (updated in place).
+        ``weights`` (a host array): installed with ``set_data_weights`` before the loop begins and left in the plan, since the
+        ``cg_step_dev`` calls that follow apply them; None: the model's own state."""
+        if weights is not None:
+            self.set_data_weights(weights)
         _lib.check(self._L.surfh_cg_planes_begin_dev(self._plan, C.c_void_p(y_t.data_ptr()), float(mu), float(mu_reg), C.c_void_p(x_t.data_ptr())))
 
     def cg_step_dev(self, iters=1, refresh=50):
@@ -241,9 +248,10 @@ class Blurred2D(LinOp):
         _lib.check(self._L.surfh_cg_planes_rr(self._plan, _lib.dptr(out)))
         return out
 
-    def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None):
+    def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, weights=None):
         """Device-resident 3MG on the same criterion (`qmm.mmmg` restated for quadratic objectives) -- what the 2-D
         deconvolution driver's ``method = "qmm"`` runs (scripts/deconvolution_mrs_noRotation.py:199-212).  Same returns as
-        ``cg`` except that ``grad_norm`` holds |grad| (not squared)."""
-        return _lib.solve(self, self._L.surfh_mmmg_planes_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback,
-                          planes=self.n_planes, squeeze=not self.batched)
+        ``cg`` except that ``grad_norm`` holds |grad| (not squared).  ``weights`` as in ``cg``."""
+        with self.installed_weights(weights):
+            return _lib.solve(self, self._L.surfh_mmmg_planes_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback,
+                              planes=self.n_planes, squeeze=not self.batched)

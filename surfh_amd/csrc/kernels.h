@@ -95,6 +95,15 @@ long ymat_from_y_waves(int PS, int Ldet, int aout);
 // bit patterns.  The same bits as y_from_cpart + ymat_from_y + launch_split_rows2h, without materialising y.
 int launch_ymat16_from_cpart(hipStream_t s, const float *cpart, long slab, int nsplit, unsigned short *dst16, long plane, unsigned *rowmax,
                              int NP, int nrows, int Ldet, int LdetP);
+// the same with the data weights of the row, wmat [NP][LdetP] in ymat's layout (zero in the padding), multiplied into the slab sum
+// before the row maximum is taken: the bits of y_from_cpart + launch_weight_mul + ymat_from_y + launch_split_rows2h
+int launch_ymat16w_from_cpart(hipStream_t s, const float *cpart, long slab, int nsplit, unsigned short *dst16, long plane, unsigned *rowmax,
+                              int NP, int nrows, int Ldet, int LdetP, const float *wmat);
+// data weights: y *= w;  out = (w > 0 ? w y : 0), a select so that a masked NaN stays out;  *count += weights that are negative or
+// not finite (count is cleared by the caller)
+int launch_weight_mul(hipStream_t s, float *y, const float *w, long n);
+int launch_weight_select(hipStream_t s, const float *y, const float *w, float *out, long n);
+int launch_weight_count_bad(hipStream_t s, const float *w, long n, unsigned *count);
 
 // [L][Na][Nb] (wavelength-major, the reference's cube layout) <-> [NBP][NAP][LP] (wavelength innermost)
 int launch_cube_to_lam_inner(hipStream_t s, const float *src, float *dst, int l0, int L, int na, int nb, int nap, int LP);

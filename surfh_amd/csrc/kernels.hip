@@ -1,6 +1,8 @@
 // HBM-bound kernels of the surfh hot path for gfx950 (see kernels.h for the contracts).
 #include "kernels.h"
 #include "huber_dev.h"
+#include <algorithm>
+#include <cfloat>
 #include <cstdlib>
 
 namespace {
@@ -743,9 +745,13 @@ __device__ __forceinline__ float f16x2_row_scale(float amax) {         // f16x2_
     sc = sc < -126 ? -126 : (sc > 127 ? 127 : sc);
     return __uint_as_float((unsigned)(sc + 127) << 23);
 }
-template <int NV>      // float4 per thread: LdetP <= NV * 1024
-__global__ __launch_bounds__(TPB) void ymat16_from_cpart_kernel(const float *__restrict__ cpart, long slab, int nsplit, unsigned short *__restrict__ dst16,
-                                                                long plane, unsigned *__restrict__ rowmax, int nrows, int Ldet, int LdetP) {
+// WGT: the data weights of the row (surfh_set_data_weights; wmat in ymat's layout, zero in the padding) multiply the slab sum once,
+// BEFORE the row maximum -- a masked outlier must not take the row's fp16 range.  The bits are those of the chain with the
+// element-wise weight kernel on y between y_from_cpart and ymat_from_y.
+template <int NV, bool WGT>      // float4 per thread: LdetP <= NV * 1024
+__device__ __forceinline__ void ymat16_from_cpart_row(const float *__restrict__ cpart, long slab, int nsplit, unsigned short *__restrict__ dst16,
+                                                      long plane, unsigned *__restrict__ rowmax, int nrows, int Ldet, int LdetP,
+                                                      const float *__restrict__ wmat) {
     typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
     const int n = blockIdx.x;
     float4 v[NV];
@@ -763,6 +769,10 @@ __global__ __launch_bounds__(TPB) void ymat16_from_cpart_kernel(const float *__r
             if (l + 1 >= Ldet) s.y = 0.f;        // columns beyond Ldet hold the products of the zero rows of W: not part of y
             if (l + 2 >= Ldet) s.z = 0.f;
             if (l + 3 >= Ldet) s.w = 0.f;
+            if (WGT) {
+                const float4 w = *reinterpret_cast<const float4 *>(wmat + src);
+                s.x *= w.x; s.y *= w.y; s.z *= w.z; s.w *= w.w;
+            }
         }
         v[j] = s;
         m = fmaxf(m, fmaxf(fmaxf(fabsf(s.x), fabsf(s.y)), fmaxf(fabsf(s.z), fabsf(s.w))));
@@ -785,6 +795,52 @@ __global__ __launch_bounds__(TPB) void ymat16_from_cpart_kernel(const float *__r
         const long o = (long)n * LdetP + l;
         *reinterpret_cast<f16x4 *>(dst16 + o) = h;
         *reinterpret_cast<f16x4 *>(dst16 + plane + o) = lo;
+    }
+}
+template <int NV>
+__global__ __launch_bounds__(TPB) void ymat16_from_cpart_kernel(const float *__restrict__ cpart, long slab, int nsplit, unsigned short *__restrict__ dst16,
+                                                                long plane, unsigned *__restrict__ rowmax, int nrows, int Ldet, int LdetP) {
+    ymat16_from_cpart_row<NV, false>(cpart, slab, nsplit, dst16, plane, rowmax, nrows, Ldet, LdetP, nullptr);
+}
+template <int NV>
+__global__ __launch_bounds__(TPB) void ymat16w_from_cpart_kernel(const float *__restrict__ cpart, long slab, int nsplit, unsigned short *__restrict__ dst16,
+                                                                 long plane, unsigned *__restrict__ rowmax, int nrows, int Ldet, int LdetP,
+                                                                 const float *__restrict__ wmat) {
+    ymat16_from_cpart_row<NV, true>(cpart, slab, nsplit, dst16, plane, rowmax, nrows, Ldet, LdetP, wmat);
+}
+
+// ---- data weights (surfh_set_data_weights): W = diag(w) in the criterion mu (y - A x)^T W (y - A x) / 2 ------------------------
+// y *= w: the hand-over of the normal operator wherever it goes through y
+__global__ __launch_bounds__(TPB) void weight_mul_kernel(float *__restrict__ y, const float *__restrict__ w, long n) {
+    long i = (long)blockIdx.x * TPB + threadIdx.x;
+    const long stride = (long)gridDim.x * TPB;
+    for (; i < n; i += stride) y[i] *= w[i];
+}
+// out = W y for the right-hand side, as a select: a sample of weight 0 gives 0 whatever its datum (0 * NaN is NaN)
+__global__ __launch_bounds__(TPB) void weight_select_kernel(const float *__restrict__ y, const float *__restrict__ w, float *__restrict__ out, long n) {
+    long i = (long)blockIdx.x * TPB + threadIdx.x;
+    const long stride = (long)gridDim.x * TPB;
+    for (; i < n; i += stride) {
+        const float wi = w[i];
+        out[i] = wi > 0.f ? wi * y[i] : 0.f;
+    }
+}
+// *count += number of weights that are negative, NaN or infinite
+__global__ __launch_bounds__(TPB) void weight_count_bad_kernel(const float *__restrict__ w, long n, unsigned *__restrict__ count) {
+    long i = (long)blockIdx.x * TPB + threadIdx.x;
+    const long stride = (long)gridDim.x * TPB;
+    unsigned bad = 0;
+    for (; i < n; i += stride) {
+        const float wi = w[i];
+        bad += !(wi >= 0.f && wi <= FLT_MAX);
+    }
+    for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
+    __shared__ unsigned sm[TPB / 64];
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = bad;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        bad = sm[0] + sm[1] + sm[2] + sm[3];
+        if (bad) atomicAdd(count, bad);
     }
 }
 
@@ -1466,6 +1522,36 @@ int launch_ymat16_from_cpart(hipStream_t s, const float *cpart, long slab, int n
     else if (nv == 3) SURFH_Y16(3);
     else SURFH_Y16(4);
 #undef SURFH_Y16
+    return (int)hipGetLastError();
+}
+
+int launch_ymat16w_from_cpart(hipStream_t s, const float *cpart, long slab, int nsplit, unsigned short *dst16, long plane, unsigned *rowmax,
+                              int NP, int nrows, int Ldet, int LdetP, const float *wmat) {
+    if (LdetP % 4 || slab % 4 || plane % 4 || LdetP > 4 * 4 * TPB || nrows > NP || !wmat) return (int)hipErrorInvalidValue;
+    const int nv = (LdetP + 4 * TPB - 1) / (4 * TPB);
+#define SURFH_Y16W(NV_) hipLaunchKernelGGL(ymat16w_from_cpart_kernel<NV_>, dim3(NP), dim3(TPB), 0, s, cpart, slab, nsplit, dst16, plane, rowmax, nrows, Ldet, LdetP, wmat)
+    if (nv <= 1) SURFH_Y16W(1);
+    else if (nv == 2) SURFH_Y16W(2);
+    else if (nv == 3) SURFH_Y16W(3);
+    else SURFH_Y16W(4);
+#undef SURFH_Y16W
+    return (int)hipGetLastError();
+}
+
+static unsigned weight_grid(long n) { return (unsigned)std::min<long>((n + TPB - 1) / TPB, 4096); }
+int launch_weight_mul(hipStream_t s, float *y, const float *w, long n) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(weight_mul_kernel, dim3(weight_grid(n)), dim3(TPB), 0, s, y, w, n);
+    return (int)hipGetLastError();
+}
+int launch_weight_select(hipStream_t s, const float *y, const float *w, float *out, long n) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(weight_select_kernel, dim3(weight_grid(n)), dim3(TPB), 0, s, y, w, out, n);
+    return (int)hipGetLastError();
+}
+int launch_weight_count_bad(hipStream_t s, const float *w, long n, unsigned *count) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(weight_count_bad_kernel, dim3(weight_grid(n)), dim3(TPB), 0, s, w, n, count);
     return (int)hipGetLastError();
 }
 

@@ -113,6 +113,7 @@ struct Channel {
     HostEll adjT_host;                  // kept until the grouped scatter table is built (plan creation)
     bool has_ref = false;
     bool bsum = false;   // no spectral blur: y[l][(p,s,a)] = sum over the slit's beta columns (MRSBlurred)
+    float *wmat = nullptr;              // data weights of the channel in ymat's layout [NP][LdetP], padding zero (channels with ymat16; surfh_set_data_weights)
 };
 
 struct ProfRec {
@@ -202,6 +203,9 @@ struct surfh_plan {
     float *gcube = nullptr;
     std::vector<Channel> ch;
     long isize = 0, osize = 0;
+    // data weights (surfh_set_data_weights): w [osize] in the layout of y, and room for W y, the data of the solvers' right-hand side;
+    // both null = every sample counts 1
+    float *dw = nullptr, *dwy = nullptr;
     // CG
     float *cg_x = nullptr, *cg_r = nullptr, *cg_d = nullptr, *cg_q = nullptr, *cg_b = nullptr, *cg_y = nullptr, *cg_qm = nullptr, *cg_dd = nullptr;
     float *cg_hg = nullptr;                        // surfh_mmmg_huber(_vox): -gradient of the non-quadratic criterion
@@ -1276,7 +1280,11 @@ int forward_dev(surfh_plan *p, const float *x, float *y, bool hand_over = false)
                 LAUNCH_OK(launch_gemm_nt_f16x2_cc(sB, g));
             }
         }
-        if (hand_over && c.ymat16) {
+        if (hand_over && c.ymat16 && c.wmat) {          // the normal operator under data weights: mu A^T W A
+            Prof pr(p, "ymat16w_from_cpart", sB);
+            LAUNCH_OK(launch_ymat16w_from_cpart(sB, c.Cpart, (long)c.NP * c.LdetP, c.splitK, c.ymat16, (long)c.NP * c.LdetP, c.amax, c.NP,
+                                                c.P * c.S * c.aout, c.Ldet, c.LdetP, c.wmat));
+        } else if (hand_over && c.ymat16) {
             Prof pr(p, "ymat16_from_cpart", sB);
             LAUNCH_OK(launch_ymat16_from_cpart(sB, c.Cpart, (long)c.NP * c.LdetP, c.splitK, c.ymat16, (long)c.NP * c.LdetP, c.amax, c.NP,
                                                c.P * c.S * c.aout, c.Ldet, c.LdetP));
@@ -1436,12 +1444,30 @@ bool normal_hand_over(const surfh_plan *p) {
     return fused && !p->verify && !p->wblur_fp32;
 }
 
-int normal_dev(surfh_plan *p, const float *d, float *q, double mu) {
-    // y is only the hand-over between the two halves: the channels' slab sums go straight into the adjoint's GEMM operands
-    // (SURFH_NORMAL_FUSED=0: through y, as forward() + adjoint() do)
+// A^T W A v, the two halves of every normal operator: y is only the hand-over between them, and the channels' slab sums go
+// straight into the adjoint's GEMM operands (SURFH_NORMAL_FUSED=0: through y, as forward() + adjoint() do).  Data weights
+// (surfh_set_data_weights) ride on the hand-over: inside launch_ymat16w_from_cpart where y is never written, as one element-wise
+// pass over the part of y that is (verify plans, SURFH_WBLUR_FP32, SURFH_NORMAL_FUSED=0, channels without a spectral blur).
+int normal_halves(surfh_plan *p, const float *v, float *q) {
     const bool ho = normal_hand_over(p);
-    if (forward_dev(p, d, p->cg_y, ho)) return 1;
-    if (adjoint_dev(p, p->cg_y, q, false, ho)) return 1;
+    if (forward_dev(p, v, p->cg_y, ho)) return 1;
+    if (p->dw) {
+        Prof pr(p, "weight_mul");
+        for (auto &c : p->ch)
+            if (!(ho && !c.bsum && c.ymat16)) LAUNCH_OK(launch_weight_mul(p->stream, p->cg_y + c.yoff, p->dw + c.yoff, c.ysize));
+    }
+    return adjoint_dev(p, p->cg_y, q, false, ho);
+}
+// the data of the solvers' right-hand side b = mu A^T W y: y itself without weights, else W y formed once per solve by a select
+const float *weighted_data(surfh_plan *p, const float *y) {
+    if (!p->dw) return y;
+    Prof pr(p, "weight_select");
+    if (launch_weight_select(p->stream, y, p->dw, p->dwy, p->osize) != 0) { fail("launch_weight_select failed"); return nullptr; }
+    return p->dwy;
+}
+
+int normal_dev(surfh_plan *p, const float *d, float *q, double mu) {
+    if (normal_halves(p, d, q)) return 1;
     if (mu != 1.0) {
         Prof pr(p, "scale");
         LAUNCH_OK(launch_scale(p->stream, q, p->pn_native ? (long)p->NBP * p->NAP * p->LP : p->isize, (float)mu));
@@ -1511,6 +1537,8 @@ int surfh_plan_destroy(surfh_plan *p) {
     hipFree(p->cg_hist);
     hipFree(p->pl_sc);
     for (float *v : p->pn_v) hipFree(v);
+    hipFree(p->dw);
+    hipFree(p->dwy);
     hipFree(p->pn_sc);
     hipFree(p->pn_part);
     for (auto &c : p->ch) {
@@ -1522,6 +1550,7 @@ int surfh_plan_destroy(surfh_plan *p) {
         hipFree(c.Xs16);
         hipFree(c.bscale);
         hipFree(c.ymat16);
+        hipFree(c.wmat);
         hipFree(c.amax);
         hipFree(c.pmax);
         free_ell(&c.fwd);
@@ -2157,9 +2186,7 @@ int surfh_normal_spec_dev(surfh_plan *p, const float *dt, float *qt, double mu, 
     SpecScope sc{p};
     p->spec_in = dt;
     p->spec_out = qt; p->spec_mu = (float)mu; p->spec_prior_src = mu_reg != 0.0 ? dt : nullptr; p->spec_prior_mu = (float)mu_reg;
-    const bool ho = normal_hand_over(p);
-    if (forward_dev(p, nullptr, p->cg_y, ho)) return 1;
-    return adjoint_dev(p, p->cg_y, nullptr, false, ho);
+    return normal_halves(p, nullptr, nullptr);
 }
 // qt += mu_reg * prior(dt) on scaled half spectra (after an all-reduce of qt over ranks)
 int surfh_prior_spec_add_dev(surfh_plan *p, const float *dt, float *qt, double mu_reg) {
@@ -2175,6 +2202,79 @@ int surfh_set_prior(surfh_plan *p, int32_t kind) {
     p->prior_kind = kind;
     return 0;
 }
+// ---- data weights: plan state, like the prior ------------------------------------------------------------------------------------
+namespace {
+// installs the validated device weights w_new [osize] (taken over) or, with nullptr, clears the state; on failure the plan keeps what it had
+int install_data_weights(surfh_plan *p, float *w_new) {
+    std::vector<float *> wm(p->ch.size(), nullptr);
+    float *wy = nullptr;
+    auto drop = [&](int rc) {
+        for (float *v : wm) hipFree(v);
+        hipFree(wy);
+        hipFree(w_new);
+        return rc;
+    };
+    if (w_new) {
+        hipStream_t s = p->stream;
+        if (dev_alloc(&wy, (size_t)p->osize)) return drop(1);
+        for (size_t i = 0; i < p->ch.size(); ++i) {
+            const Channel &c = p->ch[i];
+            if (c.bsum || !c.ymat16) continue;
+            const size_t n = (size_t)c.NP * c.LdetP;
+            if (dev_alloc(&wm[i], n)) return drop(1);
+            if (hipMemsetAsync(wm[i], 0, n * sizeof(float), s) != hipSuccess) return drop(fail("memset failed"));
+            if (launch_ymat_from_y(s, w_new + c.yoff, wm[i], c.P * c.S, c.Ldet, c.aout, c.LdetP) != 0) return drop(fail("launch_ymat_from_y failed"));
+        }
+    }
+    if (hipStreamSynchronize(p->stream) != hipSuccess) return drop(fail("stream synchronisation failed"));   // nothing in flight reads the old buffers
+    for (size_t i = 0; i < p->ch.size(); ++i) std::swap(p->ch[i].wmat, wm[i]);
+    std::swap(p->dwy, wy);
+    std::swap(p->dw, w_new);
+    return drop(0);
+}
+int data_weights_check(surfh_plan *p) {
+    if (!p) return fail("null plan");
+    if (p->ch.empty() || p->osize <= 0) return fail("data weights need a plan with detector channels");
+    HIP_OK(hipSetDevice(p->dev));
+    return 0;
+}
+}  // namespace
+
+int surfh_set_data_weights(surfh_plan *p, const float *w) {
+    if (data_weights_check(p)) return 1;
+    if (!w) return install_data_weights(p, nullptr);
+    for (long i = 0; i < p->osize; ++i)
+        if (!(w[i] >= 0.f && w[i] <= FLT_MAX)) return fail("data weight %ld is %g: weights are finite and >= 0", i, (double)w[i]);
+    float *wd = nullptr;
+    if (dev_alloc(&wd, (size_t)p->osize)) return 1;
+    if (hipMemcpyAsync(wd, w, p->osize * sizeof(float), hipMemcpyHostToDevice, p->stream) != hipSuccess) {
+        hipFree(wd);
+        return fail("copy failed");
+    }
+    return install_data_weights(p, wd);
+}
+int surfh_set_data_weights_dev(surfh_plan *p, const float *w_dev) {
+    if (data_weights_check(p)) return 1;
+    if (!w_dev) return install_data_weights(p, nullptr);
+    hipStream_t s = p->stream;
+    float *wd = nullptr;
+    unsigned *cnt = nullptr, bad = 0;
+    if (dev_alloc(&wd, (size_t)p->osize) || dev_alloc(&cnt, 1)) {
+        hipFree(wd);
+        return 1;
+    }
+    const bool ok = hipMemcpyAsync(wd, w_dev, p->osize * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess &&
+                    hipMemsetAsync(cnt, 0, sizeof(unsigned), s) == hipSuccess && launch_weight_count_bad(s, wd, p->osize, cnt) == 0 &&
+                    hipMemcpyAsync(&bad, cnt, sizeof(unsigned), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+    hipFree(cnt);
+    if (!ok || bad) {
+        hipFree(wd);
+        return ok ? fail("%u data weights are negative or not finite: weights are finite and >= 0", bad) : fail("data weight check failed");
+    }
+    return install_data_weights(p, wd);
+}
+int surfh_has_data_weights(const surfh_plan *p) { return p && p->dw ? 1 : 0; }
+
 int surfh_dot_dev(surfh_plan *p, const float *a, const float *b, int64_t n, double *out) {
     if (!p) return fail("null plan");
     HIP_OK(hipSetDevice(p->dev));
@@ -2298,8 +2398,9 @@ int normal_prior(surfh_plan *p, const float *v, float *out, double mu, double mu
     }
     return 0;
 }
-// cg_b = mu A^T y, cg_q = Q x, cg_r = cg_b - cg_q; y on the device, x already holding the start
+// cg_b = mu A^T W y, cg_q = Q x, cg_r = cg_b - cg_q; y on the device, x already holding the start
 int solver_setup(surfh_plan *p, const float *y, const float *x, double mu, double mu_reg) {
+    if (!(y = weighted_data(p, y))) return 1;
     if (adjoint_dev(p, y, p->cg_b, false)) return 1;
     if (mu != 1.0) LAUNCH_OK(launch_scale(p->stream, p->cg_b, p->isize, (float)mu));
     if (normal_prior(p, x, p->cg_q, mu, mu_reg)) return 1;
@@ -2333,7 +2434,8 @@ int cg_spectral(surfh_plan *p, const float *y, double mu, double mu_reg, const f
     hipStream_t s = p->stream;
     const long n = p->isize, nv = 2L * p->T * p->PL;
     HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
-    if (surfh_adjoint_spec_dev(p, p->io_y, p->cg_b, mu, nullptr, 0.0)) return 1;           // b = mu A^T y
+    const float *wy = weighted_data(p, p->io_y);
+    if (!wy || surfh_adjoint_spec_dev(p, wy, p->cg_b, mu, nullptr, 0.0)) return 1;          // b = mu A^T W y
     if (x0) {
         HIP_OK(hipMemcpyAsync(p->io_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
         if (surfh_to_spec_dev(p, p->io_x, p->cg_x) || surfh_normal_spec_dev(p, p->cg_x, p->cg_q, mu, mu_reg)) return 1;
@@ -2837,8 +2939,7 @@ int pn_normal(surfh_plan *p, const float *v, float *q, double *dq) {
     const bool fold = prod || (p->ilv && !p->dense_dft && p->pl_mu_reg != 0.0);
     if (fold) {
         p->pn_fold_prior = true;
-        const bool ho = normal_hand_over(p);
-        const int rc = forward_dev(p, v, p->cg_y, ho) || adjoint_dev(p, p->cg_y, q, false, ho);
+        const int rc = normal_halves(p, v, q);
         p->pn_fold_prior = false;
         if (rc) return 1;
     } else if (normal_dev(p, v, q, p->pl_mu)) {
@@ -2878,8 +2979,9 @@ int surfh_cg_planes_begin_dev(surfh_plan *p, const float *y_dev, double mu, doub
         p->pl_x = x_dev; p->pl_mu = mu; p->pl_mu_reg = mu_reg; p->pl_it = 0;
         LAUNCH_OK(launch_cube_to_lam_inner(s, x_dev, xn, 0, L, p->Na, p->Nb, p->NAP, p->LP));
         {
+            const float *wy = weighted_data(p, y_dev);
             PnScope sc(p);
-            if (adjoint_dev(p, y_dev, b, false)) return 1;
+            if (!wy || adjoint_dev(p, wy, b, false)) return 1;
         }
         if (mu != 1.0) LAUNCH_OK(launch_scale(s, b, (long)nc, (float)mu));
         if (pn_normal(p, xn, q, dq)) return 1;

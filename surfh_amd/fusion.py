@@ -20,6 +20,7 @@ import numpy as np
 
 from . import instru
 from .models import spectroSigRLSCT
+from .weights import check_data_weights, weighted_sq_residual, weights_from_data  # noqa: F401  (weights_from_data: public here)
 
 
 @dataclass
@@ -32,7 +33,7 @@ class OptimizeResult:
 
 
 class QuadCriterion_MRS:
-    def __init__(self, mu_spectro, y_spectro, model_spectro, mu_reg, printing=False, gradient="separated", delta=None):
+    def __init__(self, mu_spectro, y_spectro, model_spectro, mu_reg, printing=False, gradient="separated", delta=None, weights=None):
         """``gradient="joint"`` regularises with the Laplacian of ``Difference_Operator_Joint`` (fusion_CT.py:45-62); udft's
         ``laplacian(2)`` is absent from the reference tree, the 3 x 3 kernel [[0,-1,0],[-1,4,-1],[0,-1,0]] is restated: parity
         unpinned for that option (the operator is checked against the oracle's Fourier-domain form of the same kernel).
@@ -42,7 +43,10 @@ class QuadCriterion_MRS:
         ``delta`` (not in fusion_CT.py; the priors of the reference's lmm_reconstruction, algorithms.py:73-106): Huber
         potentials of threshold ``delta`` on the separated differences, criterion mu |y - A x|^2 / 2 + mu_reg sum_k sum
         phi(D_k x) (include/surfh_amd.h: surfh_mmmg_huber); only ``run_method("mmmg")`` minimises it, CG being a solver of
-        quadratic criteria.  ``None``: the quadratic criterion."""
+        quadratic criteria.  ``None``: the quadratic criterion.
+        ``weights`` (not in fusion_CT.py): per-sample data weights ``w`` ``[osize]``, data term mu (y - A x)^T diag(w) (y - A x) / 2
+        (``spectroSigRLSCT.set_data_weights``); data of weight 0 are ignored whatever they hold, NaN included.  ``None``: the
+        weights the model holds, if any, are used by the solve and by ``get_crit_val``."""
         assert isinstance(mu_reg, (float, int, list, np.ndarray))
         if gradient not in ("separated", "joint"):
             raise ValueError(f"gradient must be 'separated' or 'joint', not {gradient!r}")
@@ -53,6 +57,7 @@ class QuadCriterion_MRS:
             if not delta > 0.0:
                 raise ValueError(f"delta must be positive, not {delta!r}")
         self.delta = delta
+        self.weights = None if weights is None else check_data_weights(weights, int(np.prod(model_spectro.oshape)))
         self.mu_spectro, self.y_spectro, self.model_spectro, self.mu_reg = mu_spectro, y_spectro, model_spectro, mu_reg
         self.n_spec = model_spectro.ishape[0]
         self.shape_of_output = tuple(model_spectro.ishape)
@@ -126,6 +131,8 @@ class QuadCriterion_MRS:
         t0 = time.time()
         try:
             kw = {} if self.delta is None else {"delta": self.delta}
+            if self.weights is not None:
+                kw["weights"] = self.weights           # installed for the solve, the model's own state put back afterwards
             x, gn, nit = solver(self.y_spectro, mu=self.mu_spectro, mu_reg=self.mu_reg, x0=init,
                                 max_iter=maximum_iterations, tol=tolerance, callback=callback, **kw)
         finally:
@@ -140,9 +147,11 @@ class QuadCriterion_MRS:
 
     def get_crit_val(self, x_hat):
         """(mu |y - A x|^2 + mu_reg (|Dr x|^2 + |Dc x|^2)) / 2   (fusion_CT.py:242-265); with ``delta``
-        mu |y - A x|^2 / 2 + mu_reg sum phi(Dr x) + phi(Dc x), phi the Huber potential (that criterion's limit delta -> inf)."""
+        mu |y - A x|^2 / 2 + mu_reg sum phi(Dr x) + phi(Dc x), phi the Huber potential (that criterion's limit delta -> inf).
+        Under data weights (this criterion's, else the model's) |y - A x|^2 is sum w (y - A x)^2 over the samples with w > 0."""
         x_hat = np.asarray(x_hat).reshape(self.shape_of_output)
-        data = self.mu_spectro * np.sum((self.y_spectro - self.model_spectro.forward(x_hat)) ** 2)
+        w = self.weights if self.weights is not None else getattr(self.model_spectro, "data_weights", None)
+        data = self.mu_spectro * weighted_sq_residual(self.y_spectro, self.model_spectro.forward(x_hat), w)
         if self.delta is not None:
             return data / 2 + self.mu_reg * (huber_phi(np.roll(x_hat, 1, axis=1) - x_hat, self.delta).sum() +
                                              huber_phi(np.roll(x_hat, 1, axis=2) - x_hat, self.delta).sum())

@@ -21,6 +21,7 @@ import numpy as np
 from . import _lib, instru
 from .geometry import ChannelGeometry
 from .linop import LinOp
+from .weights import DataWeights
 
 
 def _ptr(t):
@@ -82,7 +83,7 @@ class Channel(ChannelGeometry):
         return op.adjoint_ref(np.ascontiguousarray(s.transpose(1, 0, 2)))
 
 
-class spectroSigRLSCT(LinOp):
+class spectroSigRLSCT(DataWeights, LinOp):
     huber_prior_value = None            # prior value of the last mmmg(delta=...) result (set by mmmg)
     huber_prior_values = None           # (spatial, spectral) prior values of the last mmmg_vox result
 
@@ -319,13 +320,16 @@ class spectroSigRLSCT(LinOp):
         return getattr(self, "_prior", "separated")
 
     # ---- solver on one GPU ------------------------------------------------------------------
-    def cg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None):
+    def cg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, weights=None):
         """Device-resident linear CG (qmm.lcg restated).  ``callback(it, grad_norm, x)`` -- the per-iteration callback
         of ``qmm.lcg`` (fusion_CT.py:194-225) -- receives the 1-based iteration, the grad_norm trace so far and the
-        current iterate ``[T,Na,Nb]``; it may call ``forward`` / ``adjoint`` on this model; a truthy return stops."""
-        return _lib.solve(self, self._L.surfh_cg_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
+        current iterate ``[T,Na,Nb]``; it may call ``forward`` / ``adjoint`` on this model; a truthy return stops.
+        ``weights``: data weights ``[osize]`` for this solve only, data term mu (y - A x)^T diag(w) (y - A x) (``set_data_weights``;
+        what the model held is put back afterwards); None: the model's own state."""
+        with self.installed_weights(weights):
+            return _lib.solve(self, self._L.surfh_cg_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
 
-    def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, delta=None):
+    def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, delta=None, weights=None):
         """Device-resident 3MG (qmm.mmmg restated for quadratic objectives; the reference's ``method='mmmg'``,
         fusion_CT.py:194-198).  Same arguments as ``cg``; ``grad_norm`` holds |grad| (not squared) of every iterate.
 
@@ -333,11 +337,12 @@ class spectroSigRLSCT(LinOp):
         differences instead (qmm.Huber, the reference's lmm_reconstruction, algorithms.py:73-106) and the criterion is
         ``mu |y - A x|^2 / 2 + mu_reg sum_k sum phi(D_k x)`` (include/surfh_amd.h: surfh_mmmg_huber); the prior value of the
         returned iterate is left in ``self.huber_prior_value`` (None after a quadratic run, and before any run).  qmm is not
-        available to pin this restatement against.  ``None`` runs the quadratic solver above."""
+        available to pin this restatement against.  ``None`` runs the quadratic solver above.  ``weights`` as in ``cg``."""
         self.huber_prior_value = None
-        if delta is None:
-            return _lib.solve(self, self._L.surfh_mmmg, data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
-        x, gn, nit, self.huber_prior_value = _lib.solve_huber(self, data, mu, mu_reg, delta, x0, max_iter, tol, refresh, callback)
+        with self.installed_weights(weights):
+            if delta is None:
+                return _lib.solve(self, self._L.surfh_mmmg, data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
+            x, gn, nit, self.huber_prior_value = _lib.solve_huber(self, data, mu, mu_reg, delta, x0, max_iter, tol, refresh, callback)
         return x, gn, nit
 
     def huber_curv_dev(self, x_t, p0_t, p1_t, delta: float) -> np.ndarray:
@@ -354,7 +359,7 @@ class spectroSigRLSCT(LinOp):
 
     # ---- the cube itself under Huber priors (models without templates) -----------------------
     def mmmg_vox(self, data, mu=1.0, spat_reg=1.0, spat_delta=1.0, spec_reg=1.0, spec_delta=1.0, x0=None, max_iter=10, tol=1e-12,
-                 refresh=50, callback=None):
+                 refresh=50, callback=None, weights=None):
         """3MG on the cube ``[Lc, Na, Nb]`` with Huber priors on its row, column and wavelength differences (the reference's
         vox_reconstruction, algorithms.py:27-71; include/surfh_amd.h: surfh_mmmg_huber_vox):
 
@@ -364,13 +369,15 @@ class spectroSigRLSCT(LinOp):
         reference's legacy ``Spectro`` model is ``(alpha, beta, lambda)``, hence its ``Diff(0) / Diff(1) / Diff(2)``; the cube
         here is ``[lambda][alpha][beta]``.  Needs a model built with ``templates=None``.  Returns ``(x, grad_norm, nit)`` as
         ``mmmg`` and leaves ``self.huber_prior_values = (spatial, spectral)``.  A delta of ``inf`` makes its term quadratic, a
-        weight of 0 switches it off.  qmm and aljabr are not available to pin the restatement or the border conventions."""
+        weight of 0 switches it off.  qmm and aljabr are not available to pin the restatement or the border conventions.
+        ``weights``: data weights for this solve, as in ``cg`` (the data term is then ``mu (y - A x)^T W (y - A x) / 2``)."""
         self.huber_prior_values = None
         if self.lmm:
             raise ValueError("mmmg_vox reconstructs the cube itself: build the model with templates=None "
                              "(mmmg(delta=...) is the solver of a template model)")
-        x, gn, nit, self.huber_prior_values = _lib.solve_huber_vox(self, data, mu, spat_reg, spat_delta, spec_reg, spec_delta, x0,
-                                                                   max_iter, tol, refresh, callback)
+        with self.installed_weights(weights):
+            x, gn, nit, self.huber_prior_values = _lib.solve_huber_vox(self, data, mu, spat_reg, spat_delta, spec_reg, spec_delta, x0,
+                                                                       max_iter, tol, refresh, callback)
         return x, gn, nit
 
     def huber_vox_prior_dev(self, x_t, g_t, spat_reg: float, spat_delta: float, spec_reg: float, spec_delta: float):

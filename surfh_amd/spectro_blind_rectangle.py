@@ -21,6 +21,7 @@ import numpy as np
 
 from . import instru
 from .blurred2d import Blurred2D
+from .weights import check_data_weights, weighted_sq_residual
 
 
 class MRSBlurred(Blurred2D):
@@ -74,7 +75,10 @@ class QuadCriterion_MRS_2D:
     """The reference's 2-D criterion (surfh/Simulation/criterion_2D.py:66-250): same constructor, ``run_method('lcg' | 'mmmg')``
     and ``get_crit_val``, on ``MRSBlurred`` (one image, or a stack of independent images solved together)."""
 
-    def __init__(self, mu_spectro, y_spectro, model_spectro, mu_reg, printing=False, gradient="separated"):
+    def __init__(self, mu_spectro, y_spectro, model_spectro, mu_reg, printing=False, gradient="separated", weights=None):
+        """``weights`` (not in criterion_2D.py): per-sample data weights in the layout of ``y_spectro``, data term
+        mu (y - A x)^T diag(w) (y - A x) / 2 (``MRSBlurred.set_data_weights``); data of weight 0 are ignored whatever they hold.
+        ``None``: the weights the model holds, if any."""
         assert isinstance(mu_reg, (float, int, list, np.ndarray))
         if gradient != "separated":
             raise NotImplementedError("only the separated first-difference priors (NpDiff_r / NpDiff_c) are built")
@@ -82,6 +86,7 @@ class QuadCriterion_MRS_2D:
         self.shape_of_output = tuple(model_spectro.ishape)
         self.printing, self.gradient, self.it = printing, gradient, 1
         self.L_crit_val = []
+        self.weights = None if weights is None else check_data_weights(weights, model_spectro.osize)
 
     def run_method(self, method="lcg", maximum_iterations=10, tolerance=1e-12, calc_crit=False, perf_crit=None, value_init=0.5):
         assert isinstance(self.mu_reg, (int, float))             # criterion_2D.py:115
@@ -121,7 +126,8 @@ class QuadCriterion_MRS_2D:
             callback = None
         t0 = time.time()
         x, gn, nit = solver(self.y_spectro, mu=self.mu_spectro, mu_reg=self.mu_reg, x0=init,
-                            max_iter=maximum_iterations, tol=tolerance, callback=callback)
+                            max_iter=maximum_iterations, tol=tolerance, callback=callback,
+                            **({} if self.weights is None else {"weights": self.weights}))
         last = np.max(np.atleast_1d(gn[-1]))
         last = np.sqrt(last) if method == "lcg" else last           # lcg traces r.r, mmmg |grad|
         res = OptimizeResult(x=x.ravel(), grad_norm=list(gn), nit=nit,
@@ -131,10 +137,11 @@ class QuadCriterion_MRS_2D:
         return res
 
     def get_crit_val(self, x_hat):
-        """(mu |y - A x|^2 + mu_reg (|Dr x|^2 + |Dc x|^2)) / 2   (criterion_2D.py:252-275), summed over the planes."""
+        """(mu |y - A x|^2 + mu_reg (|Dr x|^2 + |Dc x|^2)) / 2   (criterion_2D.py:252-275), summed over the planes; under data
+        weights (this criterion's, else the model's) |y - A x|^2 is sum w (y - A x)^2 over the samples with w > 0."""
         x_hat = np.asarray(x_hat).reshape(self.shape_of_output)
-        data = self.mu_spectro * np.sum((np.asarray(self.y_spectro).reshape(self.model_spectro.oshape)
-                                         - self.model_spectro.forward(x_hat)) ** 2)
+        w = self.weights if self.weights is not None else getattr(self.model_spectro, "data_weights", None)
+        data = self.mu_spectro * weighted_sq_residual(self.y_spectro, self.model_spectro.forward(x_hat), w)
         dr = np.roll(x_hat, 1, axis=-2) - x_hat
         dc = np.roll(x_hat, 1, axis=-1) - x_hat
         return (data + self.mu_reg * np.sum(dr ** 2 + dc ** 2)) / 2
