@@ -258,6 +258,26 @@ int surfh_mmmg_planes_cb(surfh_plan *plan, const float *y, double mu, double mu_
                          double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit,
                          surfh_cg_callback callback, void *user);
 
+/* 3MG with edge-preserving Huber priors on the plane-wise model (n_templates = 0 only): every plane l minimises its own
+ *   J_l(x_l) = mu |y_l - A_l x_l|^2 / 2 + mu_reg sum_{k in r,c} sum phi_delta(D_k x_l)
+ * (phi, D_r, D_c as for surfh_mmmg_huber; mu_reg and delta shared by the planes; data weights act in A_l^T W A_l as in the other
+ * solvers) by the majorant scheme of surfh_mmmg_huber with its own beta, 2x2 system and step, all formed on the device.  Loop,
+ * trace and callback as surfh_mmmg_planes_cb: grad_norm receives |gradient_l| as [max_iter+1][Lc], the loop stops when the worst
+ * plane is below Na Nb tol.  A plane without positive curvature (no data, or at its minimum) keeps still.  delta = +inf gives the
+ * quadratic criterion of surfh_mmmg_planes up to its factor 1/2 (same minimiser, same iterates).  prior_values (may be NULL)
+ * receives sum_k sum phi(D_k x_l) of the returned iterate, [Lc].  Same delta and mu_reg rules as surfh_mmmg_huber. */
+int surfh_mmmg_huber_planes(surfh_plan *plan, const float *y, double mu, double mu_reg, double delta, const float *x0,
+                            int32_t max_iter, double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit,
+                            double *prior_values, surfh_cg_callback callback, void *user);
+/* the two stencil passes of that solver alone, on device arrays [Lc][Na][Nb] (float64 sums in a fixed order: repeated calls give
+ * the same bits; a plane's results depend on that plane only):  g += mu_reg sum_k D_k^T phi'(D_k x) with sq_host[l] = |g_l|^2 of the
+ * result and values_host[l] = sum_k sum phi(D_k x_l) (either may be NULL);  sums_host[k][l], k = 0..2, = sum_k sum w(D_k x_l)
+ * (D_k p0_l)^2, (D_k p0_l)(D_k p1_l), (D_k p1_l)^2, as [3][Lc] */
+int surfh_huber_planes_prior_dev(surfh_plan *plan, const float *x_dev, float *g_dev, double mu_reg, double delta, double *sq_host,
+                                 double *values_host);
+int surfh_huber_planes_curv_dev(surfh_plan *plan, const float *x_dev, const float *p0_dev, const float *p1_dev, double delta,
+                                double *sums_host);
+
 /* CG building blocks on device vectors, for the multi-GPU driver (one plan per rank,
  * RCCL all-reduce of `q` between surfh_normal_dev and surfh_cg_step_dev).            */
 int surfh_normal_dev(surfh_plan *plan, const float *d_dev, float *q_dev, double mu);          /* q  = mu A^T A d   */
@@ -290,7 +310,7 @@ int surfh_set_prior(surfh_plan *plan, int32_t kind);
  *   - in every normal operator: surfh_normal_dev, surfh_fwadj(_dev), surfh_normal_spec_dev and the operators inside the solvers
  *     apply mu A^T W A;
  *   - in the right-hand side of every solver (surfh_cg(_cb), surfh_mmmg, surfh_mmmg_huber(_vox), surfh_cg_planes(_cb),
- *     surfh_mmmg_planes(_cb), surfh_cg_planes_begin_dev): b = mu A^T W y, with W y formed by a select -- a sample of weight 0
+ *     surfh_mmmg_planes(_cb), surfh_mmmg_huber_planes, surfh_cg_planes_begin_dev): b = mu A^T W y, with W y formed by a select -- a sample of weight 0
  *     contributes nothing whatever its datum, NaN and Inf included.
  * They do NOT act on surfh_forward*, surfh_adjoint*, surfh_adjoint_ref*, surfh_forward_spec_dev and surfh_adjoint_spec_dev,
  * which stay A and A^T.  Priors, stopping rules and traces are untouched.

@@ -20,6 +20,10 @@ of view at ``8.2 - rotation_ref`` degrees, bilinear gridding, so ``--input`` poi
 exact transpose of that operator.  ``--data_to_img`` also writes the quick-look back-projection ``data_to_img`` of the data
 (``adj_mean.npy``, ``adj.npy``, deconvolution_mrs_single_wavelength.py:159) and of the result's forward (``adj_mean_fit.npy``,
 ``adj_fit.npy``, :194), single image only.
+
+``--delta D`` (not in the reference, whose criterion_2D.py imports qmm's ``Huber`` without building it): edge-preserving Huber
+priors of threshold D on the row and column differences, minimised by 3MG (``-m`` anything but ``lcg``); the results then go to
+``<--out>_huber_<D>``.
 """
 from __future__ import annotations
 
@@ -86,7 +90,13 @@ def build_problem(npix: int, planes: int, seed: int, inp: str | None, angle: flo
 @click.option("--angle", default=0.0, type=float,
               help="field-of-view angle in degrees; nonzero: the rotated-field operator spectro_blind.MRSBlurred (reference: 8.2)")
 @click.option("--data_to_img", is_flag=True, help="also write data_to_img of the data and of the result's forward")
-def main(npix, hyper_parameter, niter, method, value_init, planes, inp, out, quiet, seed, device, angle, data_to_img):
+@click.option("--delta", default=None, type=float,
+              help="Huber threshold of the priors (needs -m other than lcg); results go to <out>_huber_<delta>")
+def main(npix, hyper_parameter, niter, method, value_init, planes, inp, out, quiet, seed, device, angle, data_to_img, delta):
+    if delta is not None:
+        if method == "lcg":
+            raise ValueError("lcg minimises quadratic criteria only: a Huber prior (delta) needs method='mmmg'")
+        out = f"{out}_huber_{delta:g}"
     if angle:
         from surfh_amd.spectro_blind import MRSBlurred, QuadCriterion_MRS_2D
     else:
@@ -98,7 +108,7 @@ def main(npix, hyper_parameter, niter, method, value_init, planes, inp, out, qui
                        device=device)
     simulated_data = model.forward(prob["truth"])
     crit = QuadCriterion_MRS_2D(mu_spectro=1, y_spectro=np.copy(simulated_data), model_spectro=model, mu_reg=hyper_parameter,
-                                printing=True, gradient="separated")
+                                printing=True, gradient="separated", delta=delta)
     t0 = time.time()
     if quiet:
         res = crit.run_method(method, niter, value_init=value_init)

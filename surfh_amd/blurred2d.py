@@ -248,10 +248,36 @@ class Blurred2D(DataWeights, LinOp):
         _lib.check(self._L.surfh_cg_planes_rr(self._plan, _lib.dptr(out)))
         return out
 
-    def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, weights=None):
+    last_prior_values = None            # per-plane prior values of the last mmmg(delta=...) result (None after a quadratic run)
+
+    def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, delta=None, weights=None):
         """Device-resident 3MG on the same criterion (`qmm.mmmg` restated for quadratic objectives) -- what the 2-D
         deconvolution driver's ``method = "qmm"`` runs (scripts/deconvolution_mrs_noRotation.py:199-212).  Same returns as
-        ``cg`` except that ``grad_norm`` holds |grad| (not squared).  ``weights`` as in ``cg``."""
+        ``cg`` except that ``grad_norm`` holds |grad| (not squared).  ``weights`` as in ``cg``.
+        ``delta`` (a number): the priors are Huber potentials of threshold ``delta`` on the separated circular differences
+        (criterion_2D.py imports qmm's ``Huber`` for this), every plane minimising its own
+        mu |y - A x|^2 / 2 + mu_reg sum_k sum phi(D_k x)  (include/surfh_amd.h: surfh_mmmg_huber_planes); same returns, and the
+        prior values sum_k sum phi(D_k x_l) of the returned iterate are left in ``self.last_prior_values`` ([n_planes])."""
+        self.last_prior_values = None
         with self.installed_weights(weights):
-            return _lib.solve(self, self._L.surfh_mmmg_planes_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback,
-                              planes=self.n_planes, squeeze=not self.batched)
+            if delta is None:
+                return _lib.solve(self, self._L.surfh_mmmg_planes_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback,
+                                  planes=self.n_planes, squeeze=not self.batched)
+            x, gn, nit, self.last_prior_values = _lib.solve_huber_planes(self, data, mu, mu_reg, delta, x0, max_iter, tol, refresh,
+                                                                         callback, self.n_planes, not self.batched)
+            return x, gn, nit
+
+    def huber_planes_prior_dev(self, x_t, g_t, mu_reg: float, delta: float):
+        """g_t += mu_reg sum_k D_k^T phi'(D_k x_t) on device tensors [n_planes, Na, Nb] (float32, contiguous); returns
+        (|g_l|^2 of the result, sum_k sum phi(D_k x_l)), each [n_planes]: the gradient pass of ``mmmg(delta=...)`` alone."""
+        sq, val = np.zeros(self.n_planes), np.zeros(self.n_planes)
+        _lib.check(self._L.surfh_huber_planes_prior_dev(self._plan, C.c_void_p(x_t.data_ptr()), C.c_void_p(g_t.data_ptr()),
+                                                        float(mu_reg), float(delta), _lib.dptr(sq), _lib.dptr(val)))
+        return sq, val
+
+    def huber_planes_curv_dev(self, x_t, p0_t, p1_t, delta: float) -> np.ndarray:
+        """[n_planes, 3]: sum_k sum w(D_k x_l) (D_k p0_l)^2, (D_k p0_l)(D_k p1_l), (D_k p1_l)^2, the prior block of the majorant."""
+        out = np.zeros((3, self.n_planes))
+        _lib.check(self._L.surfh_huber_planes_curv_dev(self._plan, C.c_void_p(x_t.data_ptr()), C.c_void_p(p0_t.data_ptr()),
+                                                       C.c_void_p(p1_t.data_ptr()), float(delta), _lib.dptr(out)))
+        return np.ascontiguousarray(out.T)

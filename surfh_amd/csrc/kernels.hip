@@ -1318,6 +1318,145 @@ __global__ __launch_bounds__(TPB) void huber_curv_kernel(const float *__restrict
     block_sums_to<3>(acc, part);
 }
 
+// ---- 3MG with Huber priors on a batch of independent planes (surfh_mmmg_huber_planes): the scheme of surfh_mmmg_huber with
+// every plane's beta, 2x2 system and step formed on the device, one workgroup per plane as in mmmg_dir_planes_kernel /
+// mmmg_step_planes_kernel.  Per-plane scalars sc[k * L + l] (L = gridDim.x), k = HP_*.  A thread walks its plane row-major
+// with stride TPB, (i, j) carried along (no division per pixel); the neighbour rows come from L1 / L2.  Float64 sums in a fixed
+// order (block_sum_bcast): the same inputs give the same bits; nothing outside the plane is read.
+enum { HP_GG = 0, HP_PHI, HP_BETA, HP_MBM, HP_C00, HP_C01, HP_C11 };
+static_assert(HP_C11 + 1 == HUBER_PLANES_SCALARS, "kernels.h sizes the callers' scratch");
+
+struct PlaneWalk {   // element e = i * nb + j of a [na][nb] plane, e = threadIdx.x, threadIdx.x + TPB, ...
+    int e, i, j, si, sj;
+    __device__ PlaneWalk(int nb) : e(threadIdx.x), i(threadIdx.x / nb), j(threadIdx.x - i * nb), si(TPB / nb), sj(TPB - si * nb) {}
+    __device__ void next(int nb) {
+        e += TPB;
+        i += si;
+        j += sj;
+        if (j >= nb) {
+            j -= nb;
+            ++i;
+        }
+    }
+};
+
+// PHASES & 1, the gradient pass: g = src + coef sum_k D_k^T phi'(D_k x) (huber_grad_kernel's arithmetic; src may be g),
+//   sc[HP_GG] = |g|^2, sc[HP_PHI] = sum_k sum phi(D_k x).
+// PHASES & 2, the curvature pass on (g, m): sc[HP_C00 .. HP_C11] = sum_k sum w(D_k x) (D_k g)^2, (D_k g)(D_k m), (D_k m)^2
+//   (huber_curv_kernel's arithmetic, weights recomputed).
+// PHASES == 3, the solver's launch (src = r, coef = -mu_reg, g = -gradient): also g.Q_D m and m.Q_D m from the carried image
+//   qm, beta = -(g.Bm) / (m.Bm) with B = Q_D + reg W, d = g + beta m; sc[HP_BETA] = the fp32 beta that formed d, sc[HP_MBM] = m.Bm.
+template <int PHASES>
+__global__ __launch_bounds__(TPB) void huber_dir_planes_kernel(const float *__restrict__ x, const float *src, float *g,
+                                                               const float *__restrict__ m, const float *__restrict__ qm,
+                                                               float *__restrict__ d, int na, int nb, float coef, float delta,
+                                                               double reg, double *__restrict__ sc) {
+    const int l = blockIdx.x, L = gridDim.x, npix = na * nb;
+    const long off = (long)l * npix;
+    const float *px = x + off;
+    if constexpr ((PHASES & 1) != 0) {
+        double v[2] = {0.0, 0.0};
+        for (PlaneWalk q(nb); q.e < npix; q.next(nb)) {
+            const int im = q.e - nb + (q.i == 0 ? npix : 0), ip = q.e + nb - (q.i == na - 1 ? npix : 0);
+            const int jm = q.e - 1 + (q.j == 0 ? nb : 0), jp = q.e + 1 - (q.j == nb - 1 ? nb : 0);
+            const float c = px[q.e];
+            const float ur = px[im] - c, uc = px[jm] - c;              // (Dr x)[i][j], (Dc x)[i][j]
+            const float urn = c - px[ip], ucn = c - px[jp];            // (Dr x)[i+1][j], (Dc x)[i][j+1]
+            const float pg = (huber_dphi(urn, delta) - huber_dphi(ur, delta)) + (huber_dphi(ucn, delta) - huber_dphi(uc, delta));
+            const float gv = src[off + q.e] + coef * pg;
+            g[off + q.e] = gv;
+            v[0] += (double)gv * (double)gv;
+            v[1] += huber_phi(ur, delta) + huber_phi(uc, delta);
+        }
+        block_sum_bcast<2>(v);
+        if (threadIdx.x == 0) {
+            sc[HP_GG * L + l] = v[0];
+            sc[HP_PHI * L + l] = v[1];
+        }
+    }
+    if constexpr ((PHASES & 2) != 0) {
+        // The pass below reads neighbours of g that other threads of this workgroup stored above.  A workgroup runs on one
+        // compute unit and its waves share that unit's vector L1, which stores write through; __syncthreads() makes every wave
+        // wait for its outstanding stores before the barrier and is a workgroup-scope release / acquire fence for the
+        // compiler, so the loads after it see the stores before it.  g is neither __restrict__ nor const: the compiler may not
+        // assume the plane unchanged across the barrier, nor move these loads over it.  No other workgroup touches this plane.
+        __syncthreads();
+        const float *a = g + off, *b = m + off;
+        constexpr int NV = PHASES == 3 ? 5 : 3;
+        double v[NV] = {};
+        for (PlaneWalk q(nb); q.e < npix; q.next(nb)) {
+            const int im = q.e - nb + (q.i == 0 ? npix : 0), jm = q.e - 1 + (q.j == 0 ? nb : 0);
+            const float c = px[q.e], ac = a[q.e], bc = b[q.e];
+            const double wr = huber_w(px[im] - c, delta), wc = huber_w(px[jm] - c, delta);
+            const double ar = a[im] - ac, acl = a[jm] - ac, br = b[im] - bc, bcl = b[jm] - bc;
+            v[0] += wr * ar * ar + wc * acl * acl;
+            v[1] += wr * ar * br + wc * acl * bcl;
+            v[2] += wr * br * br + wc * bcl * bcl;
+            if constexpr (PHASES == 3) {
+                const double qv = qm[off + q.e];
+                v[3] += (double)ac * qv;
+                v[4] += (double)bc * qv;
+            }
+        }
+        block_sum_bcast<NV>(v);
+        float beta = 0.f;
+        if constexpr (PHASES == 3) {
+            const double gBm = v[3] + reg * v[1], mBm = v[4] + reg * v[2];
+            beta = mBm > 0.0 ? (float)(-gBm / mBm) : 0.f;
+            for (int e = threadIdx.x; e < npix; e += TPB) d[off + e] = a[e] + beta * b[e];
+            if (threadIdx.x == 0) {
+                sc[HP_BETA * L + l] = (double)beta;
+                sc[HP_MBM * L + l] = mBm;
+            }
+        }
+        if (threadIdx.x == 0) {
+            sc[HP_C00 * L + l] = v[0];
+            sc[HP_C01 * L + l] = v[1];
+            sc[HP_C11 * L + l] = v[2];
+        }
+    }
+}
+
+// The 2x2 majorant step of every plane in the basis [d, m]: qd = Q_D d from the operator, the prior block of (d, m) from that of
+// (g, m) by linearity in float64 (d = g + beta m).  A plane without positive curvature (no data, or at its minimum) keeps still.
+__global__ __launch_bounds__(TPB) void huber_step_planes_kernel(float *__restrict__ x, float *__restrict__ r, const float *__restrict__ d,
+                                                                float *__restrict__ m, float *__restrict__ qm,
+                                                                const float *__restrict__ qd, const float *__restrict__ g, long npix,
+                                                                double reg, const double *__restrict__ sc, int update_r) {
+    const int l = blockIdx.x, L = gridDim.x;
+    const long off = (long)l * npix;
+    double v[4] = {0.0, 0.0, 0.0, 0.0};                    // d.Q_D d, d.Q_D m, d.g, m.g
+    for (long i = threadIdx.x; i < npix; i += TPB) {
+        const double di = d[off + i], gi = g[off + i];
+        v[0] += di * (double)qd[off + i];
+        v[1] += di * (double)qm[off + i];
+        v[2] += di * gi;
+        v[3] += (double)m[off + i] * gi;
+    }
+    block_sum_bcast<4>(v);
+    const double beta = sc[HP_BETA * L + l], mBm = sc[HP_MBM * L + l];
+    const double c00 = sc[HP_C00 * L + l], c01 = sc[HP_C01 * L + l], c11 = sc[HP_C11 * L + l];
+    const double dBd = v[0] + reg * (c00 + beta * (2.0 * c01 + beta * c11)), dBm = v[1] + reg * (c01 + beta * c11);
+    const double dg = v[2], mg = v[3];
+    double s0 = dBd > 0.0 ? dg / dBd : 0.0, s1 = 0.0;
+    if (dBd > 0.0 && mBm > 0.0) {
+        const double sq = sqrt(dBd * mBm), cc = dBm / sq, det = 1.0 - cc * cc;      // scaled 2x2 system
+        if (det > 1e-12) {
+            s0 = (dg / dBd - cc * mg / sq) / det;
+            s1 = (mg / mBm - cc * dg / sq) / det;
+        }
+    }
+    const float f0 = (float)s0, f1 = (float)s1;
+    for (long i = threadIdx.x; i < npix; i += TPB) {
+        const float mv = f0 * d[off + i] + f1 * m[off + i];
+        const float qv = f0 * qd[off + i] + f1 * qm[off + i];
+        x[off + i] += mv;
+        m[off + i] = mv;
+        qm[off + i] = qv;
+        if (update_r) r[off + i] -= qv;
+    }
+}
+
 inline int nblocks(long n, int cap = 2048) {
     long b = (n + TPB - 1) / TPB;
     if (b < 1) b = 1;
@@ -1711,6 +1850,40 @@ int launch_pn_dir(hipStream_t s, float *d, const float *r, int Na, int Nb, int N
     return (int)hipGetLastError();
 }
 size_t pn_part_doubles(long LP) { return (size_t)PN_SPLIT * (size_t)LP; }
+
+namespace {
+inline bool plane_fits(int nplanes, int na, int nb) { return nplanes > 0 && na > 0 && nb > 0 && (long)na * nb <= 0x7fffffffL - TPB; }
+}  // namespace
+
+int launch_huber_dir_planes(hipStream_t s, const float *x, const float *r, float *g, const float *m, const float *qm, float *d,
+                            int nplanes, int na, int nb, double mu_reg, float delta, double *sc) {
+    if (!plane_fits(nplanes, na, nb)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(huber_dir_planes_kernel<3>, dim3(nplanes), dim3(TPB), 0, s, x, r, g, m, qm, d, na, nb, -(float)mu_reg, delta,
+                       mu_reg, sc);
+    return (int)hipGetLastError();
+}
+
+int launch_huber_planes_grad(hipStream_t s, const float *x, const float *src, float *out, int nplanes, int na, int nb, float coef,
+                             float delta, double *sc) {
+    if (!plane_fits(nplanes, na, nb)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(huber_dir_planes_kernel<1>, dim3(nplanes), dim3(TPB), 0, s, x, src, out, (const float *)nullptr,
+                       (const float *)nullptr, (float *)nullptr, na, nb, coef, delta, 0.0, sc);
+    return (int)hipGetLastError();
+}
+
+int launch_huber_planes_curv(hipStream_t s, const float *x, const float *p0, const float *p1, int nplanes, int na, int nb, float delta,
+                             double *sc) {
+    if (!plane_fits(nplanes, na, nb)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(huber_dir_planes_kernel<2>, dim3(nplanes), dim3(TPB), 0, s, x, (const float *)nullptr, const_cast<float *>(p0),
+                       p1, (const float *)nullptr, (float *)nullptr, na, nb, 0.f, delta, 0.0, sc);
+    return (int)hipGetLastError();
+}
+
+int launch_huber_step_planes(hipStream_t s, float *x, float *r, const float *d, float *m, float *qm, const float *qd, const float *g,
+                             int nplanes, long npix, double mu_reg, const double *sc, int update_r) {
+    hipLaunchKernelGGL(huber_step_planes_kernel, dim3(nplanes), dim3(TPB), 0, s, x, r, d, m, qm, qd, g, npix, mu_reg, sc, update_r);
+    return (int)hipGetLastError();
+}
 
 int launch_cg_dir_planes(hipStream_t s, float *d, const float *r, int nplanes, long npix, const double *rrn, double *rr) {
     hipLaunchKernelGGL(cg_dir_planes_kernel, dim3(nplanes), dim3(TPB), 0, s, d, r, npix, rrn, rr);

@@ -215,6 +215,7 @@ struct surfh_plan {
     // plane-wise CG with device-resident data (surfh_cg_planes_begin_dev / _step_dev): per-plane scalars [3][Lc] (the host-buffer
     // plane-wise solvers use them too), the caller's iterate
     double *pl_sc = nullptr;
+    double *pl_hsc = nullptr;                      // surfh_mmmg_huber_planes: [HUBER_PLANES_SCALARS][Lc] per-plane scalars
     float *pl_x = nullptr;
     double pl_mu = 1.0, pl_mu_reg = 0.0;
     int pl_it = 0;
@@ -1536,6 +1537,7 @@ int surfh_plan_destroy(surfh_plan *p) {
     hipFree(p->dscratch);
     hipFree(p->cg_hist);
     hipFree(p->pl_sc);
+    hipFree(p->pl_hsc);
     for (float *v : p->pn_v) hipFree(v);
     hipFree(p->dw);
     hipFree(p->dwy);
@@ -3097,6 +3099,113 @@ int surfh_mmmg_planes_cb(surfh_plan *p, const float *y, double mu, double mu_reg
 int surfh_mmmg_planes(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
                       int32_t refresh, float *x, double *grad_norm, int32_t *nit) {
     return surfh_mmmg_planes_cb(p, y, mu, mu_reg, x0, max_iter, tol, refresh, x, grad_norm, nit, nullptr, nullptr);
+}
+
+// ---- 3MG with Huber priors on independent planes: the criterion of surfh_mmmg_huber per plane,
+//   J_l(x_l) = mu |y_l - A_l x_l|^2 / 2 + mu_reg sum_k sum phi(D_k x_l),
+// minimised by the scheme of mmmg_huber_loop with every plane's beta, 2x2 system and step on the device (that loop reads one
+// beta and one system back per iteration; here there are Lc of each): huber_dir_planes gives -g_l, |g_l|^2, the prior value, the
+// prior block of (-g_l, m_l), beta_l and d_l = -g_l + beta_l m_l; the data part Q_D = mu A^T A is applied to d for all planes
+// together; huber_step_planes forms the block of (d_l, m_l) by linearity in float64, solves and moves.  b - Q_D x is carried by
+// linearity and recomputed every `refresh` iterations.  One host read per iteration: the Lc gradient norms.
+namespace {
+int huber_planes_ready(surfh_plan *p, const char *who) {
+    if (p->T != 0) return fail("%s works on the plane-wise (no template) model; the maps of a template model take surfh_mmmg_huber", who);
+    if (p->ch.empty()) return fail("plan has no channel");
+    HIP_OK(hipSetDevice(p->dev));
+    if (!p->pl_hsc && dev_alloc(&p->pl_hsc, (size_t)HUBER_PLANES_SCALARS * p->Lc)) return 1;
+    return 0;
+}
+}  // namespace
+
+int surfh_huber_planes_prior_dev(surfh_plan *p, const float *x_dev, float *g_dev, double mu_reg, double delta, double *sq_host,
+                                 double *values_host) {
+    if (!p || !x_dev || !g_dev) return fail("null argument");
+    if (huber_args(mu_reg, delta) || huber_planes_ready(p, "surfh_huber_planes_prior_dev")) return 1;
+    const int L = p->Lc;
+    {
+        Prof pr(p, "huber_planes_grad");
+        LAUNCH_OK(launch_huber_planes_grad(p->stream, x_dev, g_dev, g_dev, L, p->Na, p->Nb, (float)mu_reg, (float)delta, p->pl_hsc));
+    }
+    if (sq_host) HIP_OK(hipMemcpyAsync(sq_host, p->pl_hsc, L * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    if (values_host) HIP_OK(hipMemcpyAsync(values_host, p->pl_hsc + L, L * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int surfh_huber_planes_curv_dev(surfh_plan *p, const float *x_dev, const float *p0_dev, const float *p1_dev, double delta,
+                                double *sums_host) {
+    if (!p || !x_dev || !p0_dev || !p1_dev || !sums_host) return fail("null argument");
+    if (huber_args(0.0, delta) || huber_planes_ready(p, "surfh_huber_planes_curv_dev")) return 1;
+    const int L = p->Lc;
+    {
+        Prof pr(p, "huber_planes_curv");
+        LAUNCH_OK(launch_huber_planes_curv(p->stream, x_dev, p0_dev, p1_dev, L, p->Na, p->Nb, (float)delta, p->pl_hsc));
+    }
+    HIP_OK(hipMemcpyAsync(sums_host, p->pl_hsc + (size_t)(HUBER_PLANES_SCALARS - 3) * L, 3 * L * sizeof(double), hipMemcpyDeviceToHost,
+                          p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int surfh_mmmg_huber_planes(surfh_plan *p, const float *y, double mu, double mu_reg, double delta, const float *x0, int32_t max_iter,
+                            double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit, double *prior_values,
+                            surfh_cg_callback callback, void *user) {
+    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (huber_args(mu_reg, delta) || huber_planes_ready(p, "surfh_mmmg_huber_planes")) return 1;
+    if (ensure_cg(p)) return 1;
+    if (!p->cg_qm && (dev_alloc(&p->cg_qm, (size_t)p->isize) || dev_alloc(&p->cg_dd, (size_t)p->isize))) return 1;
+    if (!p->cg_hg && dev_alloc(&p->cg_hg, (size_t)p->isize)) return 1;
+    hipStream_t s = p->stream;
+    const int L = p->Lc;
+    const long npix = (long)p->Na * p->Nb, n = p->isize;
+    float *r = p->cg_r, *m = p->cg_d, *d = p->cg_dd, *qd = p->cg_q, *qm = p->cg_qm, *ng = p->cg_hg;
+    double *sc = p->pl_hsc;
+    std::vector<float> hx;
+    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
+    if (x0)
+        HIP_OK(hipMemcpyAsync(p->cg_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
+    else
+        LAUNCH_OK(launch_fill_zero(s, p->cg_x, n));
+    LAUNCH_OK(launch_fill_zero(s, m, n));
+    LAUNCH_OK(launch_fill_zero(s, qm, n));
+    if (solver_setup(p, p->io_y, p->cg_x, mu, 0.0)) return 1;          // r = b - mu A^T A x: the data part of -g
+    *nit = 0;
+    for (int it = 0;; ++it) {
+        {
+            Prof pr(p, "huber_dir_planes");
+            LAUNCH_OK(launch_huber_dir_planes(s, p->cg_x, r, ng, m, qm, d, L, p->Na, p->Nb, mu_reg, (float)delta, sc));
+        }
+        double *gn = grad_norm + (size_t)it * L;
+        HIP_OK(hipMemcpyAsync(gn, sc, L * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        double worst = 0.0;
+        for (int l = 0; l < L; ++l) {
+            gn[l] = std::sqrt(gn[l]);
+            worst = std::max(worst, gn[l]);
+        }
+        if (const int rc = it > 0 ? callback_iterate(p, callback, user, it, grad_norm, p->cg_x, hx) : CB_GO_ON) {
+            if (rc == CB_STOP) break;
+            return 1;
+        }
+        if (it >= max_iter || worst < (double)npix * tol) break;
+        if (normal_dev(p, d, qd, mu)) return 1;
+        const bool fresh = refresh > 0 && it % refresh == 0;
+        {
+            Prof pr(p, "huber_step_planes");
+            LAUNCH_OK(launch_huber_step_planes(s, p->cg_x, r, d, m, qm, qd, ng, L, npix, mu_reg, sc, fresh ? 0 : 1));
+        }
+        if (fresh) {
+            if (normal_dev(p, p->cg_x, qd, mu)) return 1;
+            LAUNCH_OK(launch_residual(s, r, p->cg_b, qd, n));
+        }
+        *nit = it + 1;
+    }
+    // the last launch of the dir kernel ran on the returned iterate: its prior values are the result's
+    if (prior_values) HIP_OK(hipMemcpyAsync(prior_values, sc + L, L * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(x, p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return 0;
 }
 
 // ---- drivers' LMM helpers on the device (spectroModel.py:187-198) -----------------------------

@@ -107,9 +107,10 @@ class MRSBlurred(Blurred2D):
         not reproduced."""
         return super().cg(data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
 
-    def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None):
-        """Device-resident 3MG on the criterion of ``cg``, with the exact transpose likewise."""
-        return super().mmmg(data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
+    def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, delta=None, weights=None):
+        """Device-resident 3MG on the criterion of ``cg``, with the exact transpose likewise; ``delta``: Huber priors, and
+        ``weights``, as ``Blurred2D.mmmg``."""
+        return super().mmmg(data, mu, mu_reg, x0, max_iter, tol, refresh, callback, delta=delta, weights=weights)
 
     # ---- reference helpers on the host ------------------------------------------------------------------
     def data_to_img(self, data):

@@ -75,11 +75,22 @@ class QuadCriterion_MRS_2D:
     """The reference's 2-D criterion (surfh/Simulation/criterion_2D.py:66-250): same constructor, ``run_method('lcg' | 'mmmg')``
     and ``get_crit_val``, on ``MRSBlurred`` (one image, or a stack of independent images solved together)."""
 
-    def __init__(self, mu_spectro, y_spectro, model_spectro, mu_reg, printing=False, gradient="separated", weights=None):
+    def __init__(self, mu_spectro, y_spectro, model_spectro, mu_reg, printing=False, gradient="separated", weights=None, delta=None):
         """``weights`` (not in criterion_2D.py): per-sample data weights in the layout of ``y_spectro``, data term
         mu (y - A x)^T diag(w) (y - A x) / 2 (``MRSBlurred.set_data_weights``); data of weight 0 are ignored whatever they hold.
-        ``None``: the weights the model holds, if any."""
+        ``None``: the weights the model holds, if any.
+        ``delta`` (criterion_2D.py imports qmm's ``Huber`` beside ``mmmg`` and never builds it): Huber potentials of threshold
+        ``delta`` on the separated differences, criterion mu |y - A x|^2 / 2 + mu_reg sum_k sum phi(D_k x) per plane
+        (include/surfh_amd.h: surfh_mmmg_huber_planes), as ``fusion.QuadCriterion_MRS``; only a method other than ``"lcg"``
+        minimises it.  ``None``: the quadratic criterion."""
         assert isinstance(mu_reg, (float, int, list, np.ndarray))
+        if delta is not None:
+            if gradient != "separated":
+                raise ValueError("the Huber prior (delta) acts on the separated differences: gradient must be 'separated'")
+            delta = float(delta)
+            if not delta > 0.0:
+                raise ValueError(f"delta must be positive, not {delta!r}")
+        self.delta = delta
         if gradient != "separated":
             raise NotImplementedError("only the separated first-difference priors (NpDiff_r / NpDiff_c) are built")
         self.mu_spectro, self.y_spectro, self.model_spectro, self.mu_reg = mu_spectro, y_spectro, model_spectro, mu_reg
@@ -90,6 +101,8 @@ class QuadCriterion_MRS_2D:
 
     def run_method(self, method="lcg", maximum_iterations=10, tolerance=1e-12, calc_crit=False, perf_crit=None, value_init=0.5):
         assert isinstance(self.mu_reg, (int, float))             # criterion_2D.py:115
+        if self.delta is not None and method == "lcg":
+            raise ValueError("lcg minimises quadratic criteria only: a Huber prior (delta) needs method='mmmg'")
         solver = self.model_spectro.cg if method == "lcg" else self.model_spectro.mmmg       # criterion_2D.py:190-193
         init = np.ones(self.shape_of_output) * value_init if isinstance(value_init, (int, float)) else value_init
         assert tuple(np.shape(init)) == self.shape_of_output
@@ -125,9 +138,11 @@ class QuadCriterion_MRS_2D:
         else:
             callback = None
         t0 = time.time()
+        kw = {} if self.delta is None else {"delta": self.delta}
+        if self.weights is not None:
+            kw["weights"] = self.weights
         x, gn, nit = solver(self.y_spectro, mu=self.mu_spectro, mu_reg=self.mu_reg, x0=init,
-                            max_iter=maximum_iterations, tol=tolerance, callback=callback,
-                            **({} if self.weights is None else {"weights": self.weights}))
+                            max_iter=maximum_iterations, tol=tolerance, callback=callback, **kw)
         last = np.max(np.atleast_1d(gn[-1]))
         last = np.sqrt(last) if method == "lcg" else last           # lcg traces r.r, mmmg |grad|
         res = OptimizeResult(x=x.ravel(), grad_norm=list(gn), nit=nit,
@@ -137,11 +152,15 @@ class QuadCriterion_MRS_2D:
         return res
 
     def get_crit_val(self, x_hat):
-        """(mu |y - A x|^2 + mu_reg (|Dr x|^2 + |Dc x|^2)) / 2   (criterion_2D.py:252-275), summed over the planes; under data
-        weights (this criterion's, else the model's) |y - A x|^2 is sum w (y - A x)^2 over the samples with w > 0."""
+        """(mu |y - A x|^2 + mu_reg (|Dr x|^2 + |Dc x|^2)) / 2   (criterion_2D.py:252-275), summed over the planes; with ``delta``
+        mu |y - A x|^2 / 2 + mu_reg sum phi(Dr x) + phi(Dc x), phi the Huber potential.  Under data weights (this criterion's,
+        else the model's) |y - A x|^2 is sum w (y - A x)^2 over the samples with w > 0."""
         x_hat = np.asarray(x_hat).reshape(self.shape_of_output)
         w = self.weights if self.weights is not None else getattr(self.model_spectro, "data_weights", None)
         data = self.mu_spectro * weighted_sq_residual(self.y_spectro, self.model_spectro.forward(x_hat), w)
         dr = np.roll(x_hat, 1, axis=-2) - x_hat
         dc = np.roll(x_hat, 1, axis=-1) - x_hat
+        if self.delta is not None:
+            from .fusion import huber_phi
+            return data / 2 + self.mu_reg * (huber_phi(dr, self.delta).sum() + huber_phi(dc, self.delta).sum())
         return (data + self.mu_reg * np.sum(dr ** 2 + dc ** 2)) / 2
