@@ -219,6 +219,36 @@ int surfh_huber_vox_prior_dev(surfh_plan *plan, const float *x_dev, float *g_dev
  * under the spectral weights: the host applies spat_reg and spec_reg in float64 */
 int surfh_huber_vox_curv_dev(surfh_plan *plan, const float *x_dev, const float *p0_dev, const float *p1_dev, double spat_delta,
                              double spec_delta, double *sums_host);
+/* ---- robust (Huber) data term: outlier-tolerant fusion (qmm.Objective(forward, adjoint, Huber(data_delta), data=y)) ----
+ * 3MG on
+ *   J(x) = mu sum_i phi_{data_delta}(t_i) + mu_reg sum_{k in r,c} sum phi_{delta}(D_k x),   t_i = sqrt(w_i) (y_i - (A x)_i),
+ * w the plan's data weights (surfh_set_data_weights; 1 without): with w = 1 / sigma^2 data_delta is in units of sigma.  A sample
+ * of weight 0 contributes nothing whatever it holds, NaN and Inf included.  data_delta = +inf is the weighted quadratic data
+ * term of surfh_mmmg_huber, delta = +inf the quadratic prior of surfh_mmmg (separated differences).  The majorant's data block is
+ * mu A^T diag(w omega(t)) A, omega(t) = phi'(t) / t recomputed at every iterate, so the loop keeps A x and A m as detector vectors
+ * and applies one forward and one adjoint per iteration (no normal operator); A x is recomputed every `refresh` iterations.
+ * Trace, stopping test, callback and failure on non-positive curvature as surfh_mmmg_huber; data_delta follows delta's rules
+ * (at least FLT_MIN, not NaN).  values (may be NULL) receives sum_i phi(t_i), the number of |t_i| > data_delta, then the prior
+ * value, all at the returned iterate; omega_out (may be NULL) receives its robustness weights omega(t_i) [osize], in (0, 1], 0
+ * where w_i = 0.  Template plans with detector channels only.  Work vectors: 4 maps (x, the data part of -g, -g, m) and 5 detector
+ * vectors (y, A x, v, A (-g), A m). */
+int surfh_mmmg_robust(surfh_plan *plan, const float *y, double mu, double data_delta, double mu_reg, double delta, const float *x0,
+                      int32_t max_iter, double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit, double *values,
+                      float *omega_out, surfh_cg_callback callback, void *user);
+/* the same data term with the two prior families of surfh_mmmg_huber_vox, on the cube (plans without templates); values receives
+ * sum phi(t), the number beyond data_delta, the spatial and the spectral prior value */
+int surfh_mmmg_robust_vox(surfh_plan *plan, const float *y, double mu, double data_delta, double spat_reg, double spat_delta,
+                          double spec_reg, double spec_delta, const float *x0, int32_t max_iter, double tol, int32_t refresh,
+                          float *x, double *grad_norm, int32_t *nit, double *values, float *omega_out, surfh_cg_callback callback,
+                          void *user);
+/* the detector-space passes alone, on device vectors of n floats (w_dev may be NULL: every weight 1; float64 sums in a fixed
+ * order: repeated calls give the same bits): v = sqrt(w) phi'(t), t = sqrt(w) (y - u); sums_host[0] = sum phi(t), [1] = the number
+ * of |t| > data_delta */
+int surfh_robust_data_dev(surfh_plan *plan, const float *y_dev, const float *u_dev, const float *w_dev, int64_t n, double data_delta,
+                          float *v_dev, double *sums_host);
+/* sums_host[0..2] = sum w omega(t) p0^2, sum w omega(t) p0 p1, sum w omega(t) p1^2: the data block of the majorant before mu */
+int surfh_robust_curv_dev(surfh_plan *plan, const float *y_dev, const float *u_dev, const float *w_dev, const float *p0_dev,
+                          const float *p1_dev, int64_t n, double data_delta, double *sums_host);
 
 /* ---- linear mixing model on the device: the drivers' mapsToCube / cubeTomaps
  * (spectroModel.py:187-198, jax_utils.py:10-26).  templates [T][Lc] float64 as in surfh_config,

@@ -5,6 +5,7 @@
     python scripts/main_fusion.py --synthetic config2 -hp 5e3 -ni 50         # no input files needed
     python scripts/main_fusion.py --synthetic small --voxel -m mmmg -hp 40 --delta 0.005 --spec_reg 20 --spec_delta 0.01
     python scripts/main_fusion.py -fd <fusion_dir> -hp 5e3 -ni 50 --mask_nan --weights inv_variance.npy
+    python scripts/main_fusion.py -fd <fusion_dir> -hp 5e3 -ni 50 -m mmmg --weights inv_variance.npy --data_delta 3
 
 Inputs under ``fusion_dir`` (reference layout, main_fusion.py:65-75): ``Templates/`` (wavelength axis + NMF templates,
 .npy), ``PSF/`` (PSF stack, .npy), ``Filtered_slices/`` (one FITS file per band and pointing) -> results in
@@ -17,6 +18,11 @@ surfh/ToolsDir/algorithms.py:27-71) and writes ``res_cube.npy`` and ``criterion.
 variance, a 0/1 mask of bad pixels), ``--mask_nan`` gives the samples that are NaN or Inf weight 0 -- the reference's real-data
 scripts overwrite them with 0 and fit the model to those zeros (scripts/fusion/fusion_real_data.py:175-177).  Either flag adds
 ``_wgt`` to the result directory's name and ``weights.npy`` to its files; without them nothing changes.
+
+``--data_delta D`` (``--method mmmg`` only) makes the data term robust: Huber's potential of threshold ``D`` on the residuals
+scaled by the square root of their weights, so that with inverse-variance weights ``D`` counts sigmas.  Outliers no flag marks
+(cosmic-ray hits, warm pixels) then pull linearly instead of quadratically.  The result directory's name gains ``_rob_<D>`` and its
+files ``robust_weights.npy``, the weights ``[osize]`` in (0, 1] the last iterate gave every sample (0 where masked).
 
 The FITS reader needs astropy (FITS I/O is outside the hot path and not rebuilt here); when it is not importable the
 same arrays may be given as ``Filtered_slices/<band>_<k>.npz`` with fields ``data`` (raveled ``[Ldet, S, a_out]`` as in
@@ -122,9 +128,10 @@ def create_model(sotf, templates, origin_alpha_axis, origin_beta_axis, wavel_axi
                            instrs=list(instruments.values()), step_degree=step_angle, pointings=pointings, device=device)
 
 
-def result_dir_name(method, n_channels, n_templates, niter, hyper_parameter, scale_data, delta=None, voxel=False, weighted=False):
+def result_dir_name(method, n_channels, n_templates, niter, hyper_parameter, scale_data, delta=None, voxel=False, weighted=False,
+                    data_delta=None):
     """main_fusion.py:182; with a Huber threshold `delta` (not in the reference) `_huber_<delta>` is appended, `_vox` for a
-    voxel-wise reconstruction, and `_wgt` for a run under data weights."""
+    voxel-wise reconstruction, `_wgt` for a run under data weights, and `_rob_<data_delta>` for a robust data term."""
     name = f'{method}_MC_{n_channels}_MO_4_Temp_{n_templates}_nit_{str(niter)}_mu_{str("{:.2e}".format(hyper_parameter))}_SD_{scale_data}'
     if delta is not None:
         name += f'_huber_{delta:.2e}'
@@ -132,6 +139,8 @@ def result_dir_name(method, n_channels, n_templates, niter, hyper_parameter, sca
         name += '_vox'
     if weighted:
         name += '_wgt'
+    if data_delta is not None:
+        name += f'_rob_{data_delta:g}'
     return name + '/'
 
 
@@ -149,46 +158,52 @@ def data_weights(ndata, weights_file=None, mask_nan=False):
 
 
 def voxel_reconstruction(spectro_model, ndata, result_path, spat_reg, spat_th, spec_reg, spec_th, niter, method, scale_data,
-                         weights=None):
+                         weights=None, data_delta=None):
     """The cube itself by vox_reconstruction (surfh_amd/algorithms.py): res_cube.npy [Lc, N, N], and in criterion.npy the
     criterion at the start and after iterations 1, 6, 11, ... -- the trace `reconstruction_method` writes (perf_crit = 1)."""
     from surfh_amd.algorithms import vox_criterion, vox_reconstruction
     path = pathlib.Path(result_path) / result_dir_name(method, len(spectro_model.instrs), 0, niter, spat_reg, scale_data, spat_th,
-                                                       voxel=True, weighted=weights is not None)
+                                                       voxel=True, weighted=weights is not None, data_delta=data_delta)
     path.mkdir(parents=True, exist_ok=True)
     init = spectro_model.adjoint(ndata if weights is None else np.where(weights > 0, weights * np.where(weights > 0, ndata, 0.), 0.))
-    crit = [vox_criterion(ndata, spectro_model, init, spat_reg, spat_th, spec_reg, spec_th, weights=weights)]
+    crit = [vox_criterion(ndata, spectro_model, init, spat_reg, spat_th, spec_reg, spec_th, weights=weights, data_th=data_delta)]
 
     def trace(it, grad_norm, x):
         if it % 5 == 1:
-            crit.append(vox_criterion(ndata, spectro_model, x, spat_reg, spat_th, spec_reg, spec_th, weights=weights))
+            crit.append(vox_criterion(ndata, spectro_model, x, spat_reg, spat_th, spec_reg, spec_th, weights=weights,
+                                      data_th=data_delta))
             print(f"iteration {it}: criterion {crit[-1]:.6e}, |grad| {grad_norm[-1]:.3e}")
         return False
 
     res = vox_reconstruction(ndata, spectro_model, spat_reg=spat_reg, spat_th=spat_th, spec_reg=spec_reg, spec_th=spec_th, init=init,
-                             max_iter=niter, callback=trace, weights=weights)
+                             max_iter=niter, callback=trace, weights=weights, data_th=data_delta)
     print(f"voxel-wise 3MG: {res.nit} iterations, criterion {crit[0]:.6e} -> {crit[-1]:.6e}")
     print(f"Results save in {path}")
     np.save(path / 'res_cube.npy', res.x.reshape(spectro_model.ishape))
     np.save(path / 'criterion.npy', np.array(crit))
     if weights is not None:
         np.save(path / 'weights.npy', weights)
+    if data_delta is not None:
+        np.save(path / 'robust_weights.npy', spectro_model.robust_weights)
     return res, path
 
 
 def reconstruction_method(spectro_model, ndata, templates, result_path, hyper_parameter, niter, method, scale_data,
-                          checkpoint_every=0, resume=None, delta=None, weights=None):
+                          checkpoint_every=0, resume=None, delta=None, weights=None, data_delta=None):
     """main_fusion.py:162-206: regularised least squares by CG, then the three result files.  Not in the reference:
     `checkpoint_every` > 0 writes the iterate to checkpoint.npz in the result directory every that many iterations,
     `resume` (such a file) warm-starts from it and runs the iterations that are left; `delta` replaces the quadratic
     priors by Huber potentials of that threshold (3MG only); `weights` `[osize]` weigh the samples of the data term and are
-    stored beside the results as weights.npy."""
+    stored beside the results as weights.npy; `data_delta` makes the data term robust (3MG only) and stores the last iterate's
+    robustness weights as robust_weights.npy."""
     value_init = 0
     path = pathlib.Path(result_path) / result_dir_name(method, len(spectro_model.instrs), templates.shape[0], niter,
-                                                       hyper_parameter, scale_data, delta, weighted=weights is not None)
+                                                       hyper_parameter, scale_data, delta, weighted=weights is not None,
+                                                       data_delta=data_delta)
     path.mkdir(parents=True, exist_ok=True)
     crit = QuadCriterion_MRS(mu_spectro=1, y_spectro=np.copy(ndata), model_spectro=spectro_model,
-                             mu_reg=hyper_parameter, printing=True, gradient="separated", delta=delta, weights=weights)
+                             mu_reg=hyper_parameter, printing=True, gradient="separated", delta=delta, weights=weights,
+                             data_delta=data_delta)
     if resume:
         from surfh_amd.fusion import load_checkpoint
         x_saved, it_done, _ = load_checkpoint(resume)
@@ -204,6 +219,8 @@ def reconstruction_method(spectro_model, ndata, templates, result_path, hyper_pa
     np.save(path / 'criterion.npy', crit.L_crit_val)
     if weights is not None:
         np.save(path / 'weights.npy', weights)
+    if data_delta is not None:
+        np.save(path / 'robust_weights.npy', spectro_model.robust_weights)
     return res, path
 
 
@@ -243,8 +260,15 @@ def synthetic_problem(name, npix):
 @click.option('--weights', 'weights_file', default=None, type=str,
               help='.npy file of per-sample data weights [osize] (inverse variance, 0/1 mask), finite and >= 0.')
 @click.option('--mask_nan', is_flag=True, default=False, help='Give the data samples that are NaN or Inf weight 0.')
+@click.option('--data_delta', default=None, type=float,
+              help='Huber threshold of a robust data term, in units of the weighted residual (sigmas under inverse-variance '
+                   'weights); needs --method mmmg. Default: quadratic data term.')
 def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, method, verbose, synthetic, device, checkpoint_every=0,
-         resume=None, delta=None, voxel=False, spec_reg=1., spec_delta=1., weights_file=None, mask_nan=False):
+         resume=None, delta=None, voxel=False, spec_reg=1., spec_delta=1., weights_file=None, mask_nan=False, data_delta=None):
+    if data_delta is not None and method != 'mmmg':
+        raise click.UsageError('--data_delta (robust data term) is not quadratic; use it with --method mmmg')
+    if data_delta is not None and not data_delta > 0:
+        raise click.BadParameter(f'must be positive, not {data_delta}', param_hint='--data_delta')
     if voxel and method == 'lcg':
         raise click.BadParameter('the voxel-wise criterion is not quadratic; use --method mmmg with --voxel', param_hint='--voxel')
     if voxel and not spec_delta > 0:
@@ -299,11 +323,11 @@ def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, meth
     log.info(f'Start {method} algorithm')
     if voxel:
         voxel_reconstruction(model, ndata, paths["result_path"], hyper_parameter, 1. if delta is None else delta, spec_reg, spec_delta,
-                             niter, method, scale_data, weights=weights)
+                             niter, method, scale_data, weights=weights, data_delta=data_delta)
         model.close()
         return
     reconstruction_method(model, ndata, templates, paths["result_path"], hyper_parameter, niter, method, scale_data,
-                          checkpoint_every=checkpoint_every, resume=resume, delta=delta, weights=weights)
+                          checkpoint_every=checkpoint_every, resume=resume, delta=delta, weights=weights, data_delta=data_delta)
     model.close()
 
 

@@ -49,7 +49,7 @@ EXPORTS = [
     "surfh_stream", "surfh_forward", "surfh_adjoint", "surfh_adjoint_ref", "surfh_fwadj", "surfh_forward_dev",
     "surfh_adjoint_dev", "surfh_adjoint_ref_dev", "surfh_fwadj_dev", "surfh_wct_forward", "surfh_wct_adjoint",
     "surfh_wct_fwadj", "surfh_wct_expsol", "surfh_tst_create", "surfh_tst_destroy", "surfh_tst_forward",
-    "surfh_tst_adjoint", "surfh_tst_fwadj", "surfh_tst_last_error", "surfh_cg", "surfh_cg_cb", "surfh_mmmg", "surfh_mmmg_huber", "surfh_huber_prior_dev", "surfh_huber_curv_dev", "surfh_mmmg_huber_vox", "surfh_huber_vox_prior_dev", "surfh_huber_vox_curv_dev", "surfh_mmmg_huber_planes", "surfh_huber_planes_prior_dev", "surfh_huber_planes_curv_dev", "surfh_cg_planes", "surfh_mmmg_planes", "surfh_cg_planes_cb", "surfh_mmmg_planes_cb", "surfh_cg_planes_begin_dev", "surfh_cg_planes_step_dev", "surfh_cg_planes_rr", "surfh_maps_to_cube", "surfh_cube_to_maps", "surfh_normal_dev",
+    "surfh_tst_adjoint", "surfh_tst_fwadj", "surfh_tst_last_error", "surfh_cg", "surfh_cg_cb", "surfh_mmmg", "surfh_mmmg_huber", "surfh_huber_prior_dev", "surfh_huber_curv_dev", "surfh_mmmg_huber_vox", "surfh_huber_vox_prior_dev", "surfh_huber_vox_curv_dev", "surfh_mmmg_robust", "surfh_mmmg_robust_vox", "surfh_robust_data_dev", "surfh_robust_curv_dev", "surfh_mmmg_huber_planes", "surfh_huber_planes_prior_dev", "surfh_huber_planes_curv_dev", "surfh_cg_planes", "surfh_mmmg_planes", "surfh_cg_planes_cb", "surfh_mmmg_planes_cb", "surfh_cg_planes_begin_dev", "surfh_cg_planes_step_dev", "surfh_cg_planes_rr", "surfh_maps_to_cube", "surfh_cube_to_maps", "surfh_normal_dev",
     "surfh_prior_add_dev", "surfh_spec_supported", "surfh_spec_size", "surfh_to_spec_dev", "surfh_from_spec_dev", "surfh_forward_spec_dev",
     "surfh_adjoint_spec_dev", "surfh_normal_spec_dev", "surfh_prior_spec_add_dev", "surfh_set_prior", "surfh_set_data_weights", "surfh_set_data_weights_dev", "surfh_has_data_weights", "surfh_dot_dev", "surfh_cg_step_dev", "surfh_cg_dir_dev", "surfh_cg_iter_dev", "surfh_residual_dev",
     "surfh_cg_begin_dev", "surfh_cg_iter_nosync_dev", "surfh_cg_xupdate_nosync_dev", "surfh_cg_refresh_nosync_dev", "surfh_cg_trace",
@@ -104,6 +104,12 @@ def load():
                                                                             c_float_p, c_double_p, c_int32_p, c_double_p, CG_CALLBACK, vp]
     L.surfh_huber_vox_prior_dev.argtypes = [vp, vp, vp] + [C.c_double] * 4 + [c_double_p]
     L.surfh_huber_vox_curv_dev.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, c_double_p]
+    L.surfh_mmmg_robust.argtypes = [vp, c_float_p] + [C.c_double] * 4 + [c_float_p, C.c_int32, C.c_double, C.c_int32,
+                                                                         c_float_p, c_double_p, c_int32_p, c_double_p, c_float_p, CG_CALLBACK, vp]
+    L.surfh_mmmg_robust_vox.argtypes = [vp, c_float_p] + [C.c_double] * 6 + [c_float_p, C.c_int32, C.c_double, C.c_int32,
+                                                                             c_float_p, c_double_p, c_int32_p, c_double_p, c_float_p, CG_CALLBACK, vp]
+    L.surfh_robust_data_dev.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_double, vp, c_double_p]
+    L.surfh_robust_curv_dev.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, C.c_double, c_double_p]
     L.surfh_mmmg_huber_planes.argtypes = L.surfh_mmmg_huber.argtypes
     L.surfh_huber_planes_prior_dev.argtypes = [vp, vp, vp, C.c_double, C.c_double, c_double_p, c_double_p]
     L.surfh_huber_planes_curv_dev.argtypes = [vp, vp, vp, vp, C.c_double, c_double_p]
@@ -211,6 +217,33 @@ def solve_huber_vox(model, data, mu, spat_reg, spat_delta, spec_reg, spec_delta,
                                            float(spec_delta), x0p, int(max_iter), float(tol), int(refresh), x, gn, nit, pv, cb, None)
     x, gn, nit = _solve(model, invoke, data, x0, max_iter, callback, 1, True)
     return x, gn, nit, (pv[0], pv[1])
+
+
+def solve_robust(model, data, mu, data_delta, mu_reg, delta, x0, max_iter, tol, refresh, callback):
+    """``surfh_mmmg_robust`` on ``model``'s plan, arguments as ``solve``.  Returns ``(x, grad_norm, nit, values, omega)``: values =
+    (sum phi(t), number of |t| > data_delta, prior value) and omega ``[osize]`` the robustness weights, at the returned iterate."""
+    vals = (C.c_double * 3)()
+    omega = np.zeros(model.osize, dtype=np.float32)
+
+    def invoke(y, x0p, x, gn, nit, cb):
+        return load().surfh_mmmg_robust(model._plan, y, float(mu), float(data_delta), float(mu_reg), float(delta), x0p, int(max_iter),
+                                        float(tol), int(refresh), x, gn, nit, vals, fptr(omega), cb, None)
+    x, gn, nit = _solve(model, invoke, data, x0, max_iter, callback, 1, True)
+    return x, gn, nit, tuple(vals), omega
+
+
+def solve_robust_vox(model, data, mu, data_delta, spat_reg, spat_delta, spec_reg, spec_delta, x0, max_iter, tol, refresh, callback):
+    """``surfh_mmmg_robust_vox`` on ``model``'s plan (no templates).  Returns ``(x, grad_norm, nit, values, omega)``, values =
+    (sum phi(t), number of |t| > data_delta, spatial prior value, spectral prior value)."""
+    vals = (C.c_double * 4)()
+    omega = np.zeros(model.osize, dtype=np.float32)
+
+    def invoke(y, x0p, x, gn, nit, cb):
+        return load().surfh_mmmg_robust_vox(model._plan, y, float(mu), float(data_delta), float(spat_reg), float(spat_delta),
+                                            float(spec_reg), float(spec_delta), x0p, int(max_iter), float(tol), int(refresh), x, gn,
+                                            nit, vals, fptr(omega), cb, None)
+    x, gn, nit = _solve(model, invoke, data, x0, max_iter, callback, 1, True)
+    return x, gn, nit, tuple(vals), omega
 
 
 def _solve(model, invoke, data, x0, max_iter, callback, planes, squeeze):

@@ -28,12 +28,12 @@ import time
 
 import numpy as np
 
-from .fusion import OptimizeResult
+from .fusion import OptimizeResult, robust_data_value
 from .weights import weighted_sq_residual
 
 
 def lmm_reconstruction(data, data_model, spat_reg: float = 1.0, spat_th: float = 1.0, init=None, max_iter: int = 500,
-                       tol: float = 1e-4, callback=None, weights=None) -> OptimizeResult:
+                       tol: float = 1e-4, callback=None, weights=None, data_th=None) -> OptimizeResult:
     """Edge-preserving reconstruction of the abundance maps (algorithms.py:73-106).
 
     ``data_model`` is a template model (``spectroSigRLSCT``); ``init=None`` starts from ``data_model.adjoint(data)``, the exact
@@ -42,36 +42,38 @@ def lmm_reconstruction(data, data_model, spat_reg: float = 1.0, spat_th: float =
     |grad| < size * tol.  ``callback(it, grad_norm, x)`` as ``spectroSigRLSCT.mmmg``; a truthy return stops.
     ``weights`` (not in the reference): per-sample data weights ``[osize]``, data term (y - A x)^T diag(w) (y - A x) / 2
     (``spectroSigRLSCT.set_data_weights``); the default start is then ``A^T (w y)``, masked data left out.
+    ``data_th`` (not in the reference): Huber threshold of a robust data term, sum_i phi(sqrt(w_i) (y_i - (A x)_i)) instead of the
+    quadratic one (``spectroSigRLSCT.mmmg(data_delta=...)``); ``None``: quadratic.
     Returns the ``OptimizeResult`` of ``fusion.py`` (x raveled, |grad| of every iterate)."""
     if init is None:
         init = _weighted_start(data, data_model, weights)
     t0 = time.time()
     x, gn, nit = data_model.mmmg(data, mu=1.0, mu_reg=float(spat_reg), x0=init, max_iter=int(max_iter), tol=float(tol),
-                                 callback=callback, delta=float(spat_th), weights=weights)
+                                 callback=callback, delta=float(spat_th), weights=weights, **_robust_kw(data_th))
     return OptimizeResult(x=x.ravel(), grad_norm=list(gn), nit=nit, success=bool(gn[-1] < x.size * tol), time=time.time() - t0)
 
 
 def vox_reconstruction(data, data_model, spat_reg: float = 1.0, spat_th: float = 1.0, spec_reg: float = 1.0, spec_th: float = 1.0,
-                       init=None, max_iter: int = 500, tol: float = 1e-4, callback=None, weights=None) -> OptimizeResult:
+                       init=None, max_iter: int = 500, tol: float = 1e-4, callback=None, weights=None, data_th=None) -> OptimizeResult:
     """Edge-preserving reconstruction of the hyperspectral cube (algorithms.py:27-71).
 
     ``data_model`` is a model without templates (``spectroSigRLSCT(sotf, None, ...)``); ``init=None`` starts from
-    ``data_model.adjoint(data)`` (qmm's ``ht_data``).  ``max_iter``, ``tol``, ``callback``, ``weights`` and the result as
+    ``data_model.adjoint(data)`` (qmm's ``ht_data``).  ``max_iter``, ``tol``, ``callback``, ``weights``, ``data_th`` and the result as
     ``lmm_reconstruction``; x is the raveled cube ``[Lc, Na, Nb]``."""
     if init is None:
         init = _weighted_start(data, data_model, weights)
     t0 = time.time()
     x, gn, nit = data_model.mmmg_vox(data, mu=1.0, spat_reg=float(spat_reg), spat_delta=float(spat_th), spec_reg=float(spec_reg),
                                      spec_delta=float(spec_th), x0=init, max_iter=int(max_iter), tol=float(tol), callback=callback,
-                                     weights=weights)
+                                     weights=weights, **_robust_kw(data_th))
     return OptimizeResult(x=x.ravel(), grad_norm=list(gn), nit=nit, success=bool(gn[-1] < x.size * tol), time=time.time() - t0)
 
 
 def vox_criterion(data, data_model, x, spat_reg: float = 1.0, spat_th: float = 1.0, spec_reg: float = 1.0, spec_th: float = 1.0,
-                  mu: float = 1.0, weights=None) -> float:
+                  mu: float = 1.0, weights=None, data_th=None) -> float:
     """J(x) of ``vox_reconstruction`` at the cube ``x`` (``mu`` weighs the data term, 1 in the reference): the forward model and
     the two prior sums run on the device (``huber_vox_prior_dev``), the data term is summed in float64 on the host -- under
-    ``weights`` as sum w (y - A x)^2 over the samples with w > 0."""
+    ``weights`` as sum w (y - A x)^2 over the samples with w > 0, with ``data_th`` as the robust term mu sum phi(sqrt(w) (y - A x))."""
     import torch
     x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(data_model.ishape))
     dev = f"cuda:{data_model.device}"
@@ -79,7 +81,16 @@ def vox_criterion(data, data_model, x, spat_reg: float = 1.0, spat_th: float = 1
     g_t = torch.zeros_like(x_t)
     torch.cuda.synchronize(dev)
     v_spat, v_spec = data_model.huber_vox_prior_dev(x_t, g_t, 0.0, spat_th, 0.0, spec_th)
-    return float(mu * weighted_sq_residual(data, data_model.forward(x), weights) / 2 + spat_reg * v_spat + spec_reg * v_spec)
+    if data_th is not None:
+        data_term = mu * robust_data_value(data, data_model.forward(x), weights, float(data_th))
+    else:
+        data_term = mu * weighted_sq_residual(data, data_model.forward(x), weights) / 2
+    return float(data_term + spat_reg * v_spat + spec_reg * v_spec)
+
+
+def _robust_kw(data_th):
+    """``data_delta`` for the solvers, only when a robust data term is asked for."""
+    return {} if data_th is None else {"data_delta": float(data_th)}
 
 
 def _weighted_start(data, data_model, weights):

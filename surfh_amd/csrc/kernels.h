@@ -168,6 +168,17 @@ int launch_huber_vox_grad(hipStream_t s, const float *x, const float *src, float
 int launch_huber_vox_curv(hipStream_t s, const float *x, const float *p0, const float *p1, int Lc, int na, int nb, float ds, float dl,
                           double *scratch, double *sums);
 size_t launch_huber_vox_scratch_doubles();
+// Robust (Huber) data term (robust_data.hip), on flat detector vectors [n]: t = sqrt(w) (y - u), a sample with w <= 0 taken out by
+// a select (NaN there stays out); w == nullptr: every weight 1.  `scratch` holds launch_robust_scratch_doubles(); float64 sums in a fixed order.
+// v = sqrt(w) phi'(t), omega (may be null) = phi'(t) / t in (0, 1], 0 where masked; sums[0] = sum phi(t), sums[1] = number of |t| > delta
+int launch_robust_data(hipStream_t s, const float *y, const float *u, const float *w, float *v, float *omega, long n, float delta,
+                       double *scratch, double *sums);
+// sums[0..2] = sum w omega(t) p0^2, p0 p1, p1^2: the data block of the half-quadratic majorant
+int launch_robust_curv(hipStream_t s, const float *y, const float *u, const float *w, const float *p0, const float *p1, long n,
+                       float delta, double *scratch, double *sums);
+// mv = c0 g + c1 m ; u += mv ; m = mv   (the 3MG move in the basis [g, m]; detector vectors and maps alike)
+int launch_robust_move(hipStream_t s, float *u, const float *g, float *m, long n, double c0, double c1);
+size_t launch_robust_scratch_doubles();
 // CG on independent planes ([nplanes][npix] arrays, per-plane scalars in double arrays of nplanes)
 int launch_dot_planes(hipStream_t s, const float *a, const float *b, int nplanes, long npix, double *out);
 int launch_cg_step_planes(hipStream_t s, float *x, float *r, const float *d, const float *q, int nplanes, long npix, const double *rr,

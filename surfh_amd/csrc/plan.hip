@@ -209,7 +209,8 @@ struct surfh_plan {
     // CG
     float *cg_x = nullptr, *cg_r = nullptr, *cg_d = nullptr, *cg_q = nullptr, *cg_b = nullptr, *cg_y = nullptr, *cg_qm = nullptr, *cg_dd = nullptr;
     float *cg_hg = nullptr;                        // surfh_mmmg_huber(_vox): -gradient of the non-quadratic criterion
-    double *dscal = nullptr, *dscratch = nullptr;   // [16] device scalars, partial sums (>= 1024, and what huber_vox.hip asks for)
+    float *rb_y = nullptr, *rb_u = nullptr, *rb_ag = nullptr, *rb_am = nullptr;   // surfh_mmmg_robust(_vox): y, A x, A (-g), A m [osize]
+    double *dscal = nullptr, *dscratch = nullptr;   // [16] device scalars, partial sums (>= 1024, and what huber_vox.hip and robust_data.hip ask for)
     double *cg_hist = nullptr;                     // device-resident r.r trace of the no-host-sync CG blocks (CG_HIST_CAP entries)
     int cg_hist_n = 0;
     // plane-wise CG with device-resident data (surfh_cg_planes_begin_dev / _step_dev): per-plane scalars [3][Lc] (the host-buffer
@@ -1521,7 +1522,8 @@ int surfh_plan_destroy(surfh_plan *p) {
     hipSetDevice(p->dev);
     if (p->stream) hipStreamSynchronize(p->stream);
     for (float *v : {p->sotf, p->tpl, p->mhat, p->spec, p->ycol, p->cube, p->ycol_maps, p->maps_pad, p->Fi, p->Gi, p->Gf,
-                     p->Ff, p->GiT, p->GfT, p->Cma, p->Sma, p->Gc, p->Gs, p->Cf, p->Sf, p->io_cube, p->hth, p->mhat2, p->gcube, p->io_x, p->io_y, p->cg_x, p->cg_r, p->cg_d, p->cg_q, p->cg_b, p->cg_y, p->cg_qm, p->cg_dd, p->cg_hg})
+                     p->Ff, p->GiT, p->GfT, p->Cma, p->Sma, p->Gc, p->Gs, p->Cf, p->Sf, p->io_cube, p->hth, p->mhat2, p->gcube, p->io_x, p->io_y, p->cg_x, p->cg_r, p->cg_d, p->cg_q, p->cg_b, p->cg_y, p->cg_qm, p->cg_dd, p->cg_hg,
+                     p->rb_y, p->rb_u, p->rb_ag, p->rb_am})
         hipFree(v);
     hipFree(p->h2img);
     if (p->ctB.img != p->ctA.img) dft_ct_plan_destroy(&p->ctB);
@@ -1952,7 +1954,7 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
         }
     }
     if (dev_alloc(&p->io_x, (size_t)p->isize) || dev_alloc(&p->io_y, (size_t)p->osize) || dev_alloc(&p->cg_y, (size_t)p->osize) ||
-        dev_alloc(&p->dscal, 16) || dev_alloc(&p->dscratch, std::max((size_t)1024, launch_huber_vox_scratch_doubles())))
+        dev_alloc(&p->dscal, 16) || dev_alloc(&p->dscratch, std::max({(size_t)1024, launch_huber_vox_scratch_doubles(), launch_robust_scratch_doubles()})))
         return bail(1);
     if (hipDeviceSynchronize() != hipSuccess) return bail(fail("device error during plan creation: %s", hipGetErrorString(hipGetLastError())));
     *out = p;
@@ -2849,6 +2851,177 @@ int surfh_mmmg_huber_vox(surfh_plan *p, const float *y, double mu, double spat_r
     if (huber_args(spat_reg, spat_delta) || huber_args(spec_reg, spec_delta)) return 1;
     const HuberPrior hp = {2, {spat_reg, spec_reg}, "Huber, voxel-wise", vox_grad, vox_curv, {(float)spat_delta, (float)spec_delta}};
     return mmmg_huber_loop(p, hp, y, mu, x0, max_iter, tol, refresh, x, grad_norm, nit, prior_values, callback, user);
+}
+
+// ---- 3MG with a robust (Huber) data term (qmm.Objective(forward, adjoint, Huber(delta_d), data=y)):
+//   J(x) = mu sum_i phi_dd(t_i) + priors(x),   t_i = sqrt(w_i) (y_i - (A x)_i),   w the plan's data weights (1 without)
+// The half-quadratic majorant's data block is mu A^T diag(w omega(t)) A with omega recomputed from the residual at every iterate
+// (IRLS), so neither the carried Q_D m nor the fused normal operator of mmmg_huber_loop applies: the loop keeps u = A x and
+// a_m = A m as detector vectors beside the maps and applies one forward and one adjoint per iteration, through y.  Per iteration:
+// robust_data (v = sqrt(w) phi'(t), sum phi, count beyond) -> adjoint (the data part of -g) -> the prior's grad pass (-g, |g|^2,
+// prior values) -> forward (a_g = A (-g)) -> robust_curv (the data block of (a_g, a_m)) -> the prior's curv pass -> one read-back.
+// The host forms, in float64, the blocks of B = mu A^T diag(w omega) A + sum_f reg_f D_f^T diag(w_f) D_f on (-g, m), beta that
+// makes d = -g + beta m B-orthogonal to m, the block of (d, m) by linearity, and the scaled 2x2 system with the guards of
+// mmmg_huber_loop; the move s0 d + s1 m = s0 (-g) + (s0 beta + s1) m is then one pass over the maps and one over the detector
+// vectors.  u is recomputed from x every `refresh` iterations.  One host synchronisation per iteration.
+namespace {
+int robust_args(double data_delta) {
+    if (std::isnan(data_delta)) return fail("robust data term: data_delta must not be NaN");
+    if (!(data_delta >= (double)FLT_MIN))
+        return fail("robust data term: data_delta must be at least %g (fp32 kernels; got %g)", (double)FLT_MIN, data_delta);
+    return 0;
+}
+float robust_delta_f32(double data_delta) { return data_delta > (double)FLT_MAX ? INFINITY : (float)data_delta; }
+
+// values receives sum phi(t), the number of |t| > data_delta, then the nfam prior values (may be NULL); omega_out [osize] (may be NULL)
+int mmmg_robust_loop(surfh_plan *p, const HuberPrior &hp, const float *y, double mu, double data_delta, const float *x0,
+                     int32_t max_iter, double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit, double *values,
+                     float *omega_out, surfh_cg_callback callback, void *user) {
+    std::vector<float> hx;
+    HIP_OK(hipSetDevice(p->dev));
+    if (p->ch.empty() || p->osize <= 0) return fail("3MG (%s, robust data term) needs a plan with detector channels", hp.what);
+    if (ensure_cg(p)) return 1;
+    if (!p->cg_hg && dev_alloc(&p->cg_hg, (size_t)p->isize)) return 1;
+    for (float **v : {&p->rb_y, &p->rb_u, &p->rb_ag, &p->rb_am})
+        if (!*v && dev_alloc(v, (size_t)p->osize)) return 1;
+    hipStream_t s = p->stream;
+    const long n = p->isize, no = p->osize;
+    const int F = hp.nfam;
+    const float dd = robust_delta_f32(data_delta);
+    float *r = p->cg_r, *m = p->cg_d, *ng = p->cg_hg, *v = p->cg_y, *yd = p->rb_y, *u = p->rb_u, *ag = p->rb_ag, *am = p->rb_am;
+    const float *w = p->dw;
+    // device scalars: [0, 1] robust_data, [2 .. 2+F] the prior's grad pass, [3+F .. 5+F] robust_curv, [6+F .. 5+4F] the prior's
+    // curv pass, [6+4F] m.(-g)
+    double *sc = p->dscal;
+    const int G = 2, CD = 3 + F, CP = 6 + F, MG = 6 + 4 * F;
+    HIP_OK(hipMemcpyAsync(yd, y, no * sizeof(float), hipMemcpyHostToDevice, s));
+    if (x0)
+        HIP_OK(hipMemcpyAsync(p->cg_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
+    else
+        LAUNCH_OK(launch_fill_zero(s, p->cg_x, n));
+    LAUNCH_OK(launch_fill_zero(s, m, n));
+    LAUNCH_OK(launch_fill_zero(s, am, no));
+    if (forward_dev(p, p->cg_x, u)) return 1;
+    double h[16], val[4] = {0.0, 0.0, 0.0, 0.0};
+    *nit = 0;
+    for (int it = 0;; ++it) {
+        const bool last = it >= max_iter;                  // only |g| and the values are wanted: no majorant
+        {
+            Prof pr(p, "robust_data");
+            LAUNCH_OK(launch_robust_data(s, yd, u, w, v, nullptr, no, dd, p->dscratch, sc + 0));
+        }
+        if (adjoint_dev(p, v, r, false)) return 1;
+        if (mu != 1.0) LAUNCH_OK(launch_scale(s, r, n, (float)mu));
+        if (hp.grad(p, hp, p->cg_x, r, ng, sc + G)) return 1;
+        if (!last) {
+            if (forward_dev(p, ng, ag)) return 1;
+            {
+                Prof pr(p, "robust_curv");
+                LAUNCH_OK(launch_robust_curv(s, yd, u, w, ag, am, no, dd, p->dscratch, sc + CD));
+            }
+            if (hp.curv(p, hp, p->cg_x, ng, m, sc + CP)) return 1;
+            LAUNCH_OK(launch_dot(s, m, ng, n, p->dscratch, sc + MG));
+        }
+        HIP_OK(hipMemcpyAsync(h, sc, (last ? 3 + F : 7 + 4 * F) * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        grad_norm[it] = std::sqrt(h[G]);
+        val[0] = h[0];
+        val[1] = h[1];
+        for (int f = 0; f < F; ++f) val[2 + f] = h[G + 1 + f];
+        if (const int rc = it > 0 ? callback_iterate(p, callback, user, it, grad_norm, p->cg_x, hx) : CB_GO_ON) {
+            if (rc == CB_STOP) break;
+            return 1;
+        }
+        if (last || grad_norm[it] < (double)n * tol) break;
+        // the block of (-g, m) under B: the data family in detector space, the prior families on the maps
+        double gBg = mu * h[CD], gBm = mu * h[CD + 1], mBm = mu * h[CD + 2];
+        for (int f = 0; f < F; ++f) {
+            gBg += hp.reg[f] * h[CP + 3 * f];
+            gBm += hp.reg[f] * h[CP + 3 * f + 1];
+            mBm += hp.reg[f] * h[CP + 3 * f + 2];
+        }
+        const double beta = mBm > 0.0 ? -gBm / mBm : 0.0;
+        const double dBd = gBg + beta * (2.0 * gBm + beta * mBm), dBm = gBm + beta * mBm;      // d = -g + beta m, by linearity
+        const double mg = h[MG], dg = h[G] + beta * mg;
+        if (!(dBd > 0.0)) return fail("3MG (%s, robust data term): non-positive curvature d.Bd = %g at iteration %d", hp.what, dBd, it);
+        double s0 = dg / dBd, s1 = 0.0;
+        if (mBm > 0.0) {
+            const double sq = std::sqrt(dBd * mBm), cc = dBm / sq, det = 1.0 - cc * cc;      // scaled 2x2 system
+            if (det > 1e-12) {
+                s0 = (dg / dBd - cc * mg / sq) / det;
+                s1 = (mg / mBm - cc * dg / sq) / det;
+            }
+        }
+        {
+            Prof pr(p, "robust_move");
+            LAUNCH_OK(launch_robust_move(s, p->cg_x, ng, m, n, s0, s0 * beta + s1));
+            LAUNCH_OK(launch_robust_move(s, u, ag, am, no, s0, s0 * beta + s1));
+        }
+        if (refresh > 0 && it % refresh == 0 && forward_dev(p, p->cg_x, u)) return 1;
+        *nit = it + 1;
+    }
+    if (values)
+        for (int k = 0; k < 2 + F; ++k) values[k] = val[k];
+    if (omega_out) {                                       // omega at the returned iterate (u = A x of it)
+        LAUNCH_OK(launch_robust_data(s, yd, u, w, v, ag, no, dd, p->dscratch, sc + 0));
+        HIP_OK(hipMemcpyAsync(omega_out, ag, no * sizeof(float), hipMemcpyDeviceToHost, s));
+    }
+    HIP_OK(hipMemcpyAsync(x, p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return 0;
+}
+}  // namespace
+
+int surfh_mmmg_robust(surfh_plan *p, const float *y, double mu, double data_delta, double mu_reg, double delta, const float *x0,
+                      int32_t max_iter, double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit, double *values,
+                      float *omega_out, surfh_cg_callback callback, void *user) {
+    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (p->T <= 0) return fail("surfh_mmmg_robust needs templates (the priors act on abundance maps)");
+    if (robust_args(data_delta) || huber_args(mu_reg, delta)) return 1;
+    const HuberPrior hp = {1, {mu_reg, 0.0}, "Huber", maps_grad, maps_curv, {(float)delta, 0.f}};
+    return mmmg_robust_loop(p, hp, y, mu, data_delta, x0, max_iter, tol, refresh, x, grad_norm, nit, values, omega_out, callback, user);
+}
+
+int surfh_mmmg_robust_vox(surfh_plan *p, const float *y, double mu, double data_delta, double spat_reg, double spat_delta,
+                          double spec_reg, double spec_delta, const float *x0, int32_t max_iter, double tol, int32_t refresh,
+                          float *x, double *grad_norm, int32_t *nit, double *values, float *omega_out, surfh_cg_callback callback,
+                          void *user) {
+    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (p->T > 0) return fail("surfh_mmmg_robust_vox reconstructs the cube: it needs a plan without templates (n_templates = 0)");
+    if (robust_args(data_delta) || huber_args(spat_reg, spat_delta) || huber_args(spec_reg, spec_delta)) return 1;
+    const HuberPrior hp = {2, {spat_reg, spec_reg}, "Huber, voxel-wise", vox_grad, vox_curv, {(float)spat_delta, (float)spec_delta}};
+    return mmmg_robust_loop(p, hp, y, mu, data_delta, x0, max_iter, tol, refresh, x, grad_norm, nit, values, omega_out, callback, user);
+}
+
+int surfh_robust_data_dev(surfh_plan *p, const float *y_dev, const float *u_dev, const float *w_dev, int64_t n, double data_delta,
+                          float *v_dev, double *sums_host) {
+    if (!p || !y_dev || !u_dev || !v_dev || !sums_host) return fail("null argument");
+    if (n < 1) return fail("surfh_robust_data_dev: n = %ld", (long)n);
+    if (robust_args(data_delta)) return 1;
+    HIP_OK(hipSetDevice(p->dev));
+    {
+        Prof pr(p, "robust_data");
+        LAUNCH_OK(launch_robust_data(p->stream, y_dev, u_dev, w_dev, v_dev, nullptr, n, robust_delta_f32(data_delta), p->dscratch,
+                                     p->dscal + 0));
+    }
+    HIP_OK(hipMemcpyAsync(sums_host, p->dscal, 2 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+int surfh_robust_curv_dev(surfh_plan *p, const float *y_dev, const float *u_dev, const float *w_dev, const float *p0_dev,
+                          const float *p1_dev, int64_t n, double data_delta, double *sums_host) {
+    if (!p || !y_dev || !u_dev || !p0_dev || !p1_dev || !sums_host) return fail("null argument");
+    if (n < 1) return fail("surfh_robust_curv_dev: n = %ld", (long)n);
+    if (robust_args(data_delta)) return 1;
+    HIP_OK(hipSetDevice(p->dev));
+    {
+        Prof pr(p, "robust_curv");
+        LAUNCH_OK(launch_robust_curv(p->stream, y_dev, u_dev, w_dev, p0_dev, p1_dev, n, robust_delta_f32(data_delta), p->dscratch,
+                                     p->dscal + 0));
+    }
+    HIP_OK(hipMemcpyAsync(sums_host, p->dscal, 3 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
 }
 
 // ---- CG on independent planes: the 2-D deconvolution path (criterion_2D.py:60-250 per image, batched over wavelength)

@@ -33,7 +33,8 @@ class OptimizeResult:
 
 
 class QuadCriterion_MRS:
-    def __init__(self, mu_spectro, y_spectro, model_spectro, mu_reg, printing=False, gradient="separated", delta=None, weights=None):
+    def __init__(self, mu_spectro, y_spectro, model_spectro, mu_reg, printing=False, gradient="separated", delta=None, weights=None,
+                 data_delta=None):
         """``gradient="joint"`` regularises with the Laplacian of ``Difference_Operator_Joint`` (fusion_CT.py:45-62); udft's
         ``laplacian(2)`` is absent from the reference tree, the 3 x 3 kernel [[0,-1,0],[-1,4,-1],[0,-1,0]] is restated: parity
         unpinned for that option (the operator is checked against the oracle's Fourier-domain form of the same kernel).
@@ -46,7 +47,10 @@ class QuadCriterion_MRS:
         quadratic criteria.  ``None``: the quadratic criterion.
         ``weights`` (not in fusion_CT.py): per-sample data weights ``w`` ``[osize]``, data term mu (y - A x)^T diag(w) (y - A x) / 2
         (``spectroSigRLSCT.set_data_weights``); data of weight 0 are ignored whatever they hold, NaN included.  ``None``: the
-        weights the model holds, if any, are used by the solve and by ``get_crit_val``."""
+        weights the model holds, if any, are used by the solve and by ``get_crit_val``.
+        ``data_delta`` (not in fusion_CT.py; qmm.Objective with a Huber loss): the robust data term mu sum_i phi(t_i),
+        t_i = sqrt(w_i) (y_i - (A x)_i), phi the Huber potential of threshold ``data_delta`` (include/surfh_amd.h:
+        surfh_mmmg_robust); like ``delta`` it needs ``run_method("mmmg")`` and the separated differences.  ``None``: quadratic."""
         assert isinstance(mu_reg, (float, int, list, np.ndarray))
         if gradient not in ("separated", "joint"):
             raise ValueError(f"gradient must be 'separated' or 'joint', not {gradient!r}")
@@ -57,6 +61,14 @@ class QuadCriterion_MRS:
             if not delta > 0.0:
                 raise ValueError(f"delta must be positive, not {delta!r}")
         self.delta = delta
+        if data_delta is not None:
+            if gradient != "separated":
+                raise ValueError("the robust data term (data_delta) comes with priors on the separated differences: "
+                                 "gradient must be 'separated'")
+            data_delta = float(data_delta)
+            if not data_delta > 0.0:
+                raise ValueError(f"data_delta must be positive, not {data_delta!r}")
+        self.data_delta = data_delta
         self.weights = None if weights is None else check_data_weights(weights, int(np.prod(model_spectro.oshape)))
         self.mu_spectro, self.y_spectro, self.model_spectro, self.mu_reg = mu_spectro, y_spectro, model_spectro, mu_reg
         self.n_spec = model_spectro.ishape[0]
@@ -80,6 +92,8 @@ class QuadCriterion_MRS:
         assert isinstance(self.mu_reg, (int, float))       # fusion_CT.py:119
         if self.delta is not None and method == "lcg":
             raise ValueError("lcg minimises quadratic criteria only: a Huber prior (delta) needs method='mmmg'")
+        if self.data_delta is not None and method == "lcg":
+            raise ValueError("lcg minimises quadratic criteria only: a robust data term (data_delta) needs method='mmmg'")
         solver = self.model_spectro.cg if method == "lcg" else self.model_spectro.mmmg     # fusion_CT.py:194-198
         # the regulariser is state of the plan: select this criterion's for the duration of the solve and put back what was
         # there, so that two criteria sharing one model (different `gradient`) do not change each other's operator
@@ -133,6 +147,8 @@ class QuadCriterion_MRS:
             kw = {} if self.delta is None else {"delta": self.delta}
             if self.weights is not None:
                 kw["weights"] = self.weights           # installed for the solve, the model's own state put back afterwards
+            if self.data_delta is not None:
+                kw["data_delta"] = self.data_delta
             x, gn, nit = solver(self.y_spectro, mu=self.mu_spectro, mu_reg=self.mu_reg, x0=init,
                                 max_iter=maximum_iterations, tol=tolerance, callback=callback, **kw)
         finally:
@@ -148,10 +164,14 @@ class QuadCriterion_MRS:
     def get_crit_val(self, x_hat):
         """(mu |y - A x|^2 + mu_reg (|Dr x|^2 + |Dc x|^2)) / 2   (fusion_CT.py:242-265); with ``delta``
         mu |y - A x|^2 / 2 + mu_reg sum phi(Dr x) + phi(Dc x), phi the Huber potential (that criterion's limit delta -> inf).
-        Under data weights (this criterion's, else the model's) |y - A x|^2 is sum w (y - A x)^2 over the samples with w > 0."""
+        Under data weights (this criterion's, else the model's) |y - A x|^2 is sum w (y - A x)^2 over the samples with w > 0.
+        With ``data_delta`` the data term is mu sum phi(sqrt(w) (y - A x)) over those samples instead of mu |y - A x|^2 / 2."""
         x_hat = np.asarray(x_hat).reshape(self.shape_of_output)
         w = self.weights if self.weights is not None else getattr(self.model_spectro, "data_weights", None)
-        data = self.mu_spectro * weighted_sq_residual(self.y_spectro, self.model_spectro.forward(x_hat), w)
+        if self.data_delta is not None:
+            data = 2 * self.mu_spectro * robust_data_value(self.y_spectro, self.model_spectro.forward(x_hat), w, self.data_delta)
+        else:
+            data = self.mu_spectro * weighted_sq_residual(self.y_spectro, self.model_spectro.forward(x_hat), w)
         if self.delta is not None:
             return data / 2 + self.mu_reg * (huber_phi(np.roll(x_hat, 1, axis=1) - x_hat, self.delta).sum() +
                                              huber_phi(np.roll(x_hat, 1, axis=2) - x_hat, self.delta).sum())
@@ -161,6 +181,16 @@ class QuadCriterion_MRS:
         dr = np.roll(x_hat, 1, axis=1) - x_hat
         dc = np.roll(x_hat, 1, axis=2) - x_hat
         return (data + self.mu_reg * np.sum(dr ** 2 + dc ** 2)) / 2
+
+
+def robust_data_value(y, ax, weights, data_delta):
+    """``sum phi(sqrt(w) (y - A x))`` in float64 over the samples with w > 0 (``weights=None``: all, w = 1)."""
+    y, ax = np.asarray(y, dtype=np.float64).ravel(), np.asarray(ax, dtype=np.float64).ravel()
+    if weights is None:
+        return float(huber_phi(y - ax, data_delta).sum())
+    w = np.asarray(weights, dtype=np.float64).ravel()
+    keep = w > 0
+    return float(huber_phi(np.sqrt(w[keep]) * (y[keep] - ax[keep]), data_delta).sum())
 
 
 def huber_phi(u, delta):

@@ -86,6 +86,9 @@ class Channel(ChannelGeometry):
 class spectroSigRLSCT(DataWeights, LinOp):
     huber_prior_value = None            # prior value of the last mmmg(delta=...) result (set by mmmg)
     huber_prior_values = None           # (spatial, spectral) prior values of the last mmmg_vox result
+    robust_weights = None               # omega(t) [osize] of the last mmmg / mmmg_vox result under data_delta (else None)
+    robust_data_value = None            # sum phi(t) of that result
+    robust_n_beyond = None              # number of its samples with |t| > data_delta
 
     def __init__(self, sotf, templates, alpha_axis, beta_axis, wavelength_axis, instrs: List[instru.IFU],
                  step_degree: float, pointings: Sequence[instru.CoordList], *, device: int = 0,
@@ -320,16 +323,21 @@ class spectroSigRLSCT(DataWeights, LinOp):
         return getattr(self, "_prior", "separated")
 
     # ---- solver on one GPU ------------------------------------------------------------------
-    def cg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, weights=None):
+    def cg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, weights=None,
+           data_delta=None):
         """Device-resident linear CG (qmm.lcg restated).  ``callback(it, grad_norm, x)`` -- the per-iteration callback
         of ``qmm.lcg`` (fusion_CT.py:194-225) -- receives the 1-based iteration, the grad_norm trace so far and the
         current iterate ``[T,Na,Nb]``; it may call ``forward`` / ``adjoint`` on this model; a truthy return stops.
         ``weights``: data weights ``[osize]`` for this solve only, data term mu (y - A x)^T diag(w) (y - A x) (``set_data_weights``;
-        what the model held is put back afterwards); None: the model's own state."""
+        what the model held is put back afterwards); None: the model's own state.  ``data_delta`` must stay None: the robust
+        data term of ``mmmg`` is not quadratic."""
+        if data_delta is not None:
+            raise ValueError("cg minimises quadratic criteria only: a robust data term (data_delta) needs mmmg")
         with self.installed_weights(weights):
             return _lib.solve(self, self._L.surfh_cg_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
 
-    def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, delta=None, weights=None):
+    def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, delta=None, weights=None,
+             data_delta=None):
         """Device-resident 3MG (qmm.mmmg restated for quadratic objectives; the reference's ``method='mmmg'``,
         fusion_CT.py:194-198).  Same arguments as ``cg``; ``grad_norm`` holds |grad| (not squared) of every iterate.
 
@@ -337,9 +345,27 @@ class spectroSigRLSCT(DataWeights, LinOp):
         differences instead (qmm.Huber, the reference's lmm_reconstruction, algorithms.py:73-106) and the criterion is
         ``mu |y - A x|^2 / 2 + mu_reg sum_k sum phi(D_k x)`` (include/surfh_amd.h: surfh_mmmg_huber); the prior value of the
         returned iterate is left in ``self.huber_prior_value`` (None after a quadratic run, and before any run).  qmm is not
-        available to pin this restatement against.  ``None`` runs the quadratic solver above.  ``weights`` as in ``cg``."""
+        available to pin this restatement against.  ``None`` runs the quadratic solver above.  ``weights`` as in ``cg``.
+
+        ``data_delta`` (a number): the data term is robust, ``mu sum_i phi_data_delta(t_i)`` with ``t_i = sqrt(w_i) (y_i - (A x)_i)``
+        (qmm.Objective with a Huber loss; include/surfh_amd.h: surfh_mmmg_robust) -- with ``weights = 1 / sigma^2`` the threshold is
+        in units of sigma, 3 say, and samples further off (cosmic-ray hits, warm pixels no flag marks) pull linearly instead of
+        quadratically.  The priors stay what ``delta`` says (``None``: quadratic, on the separated differences).  Afterwards
+        ``self.robust_weights`` holds ``omega(t) = phi'(t) / t`` ``[osize]`` of the returned iterate (1 inside the threshold, below 1
+        beyond, 0 where the weight is 0), ``self.robust_data_value`` ``sum phi(t)`` and ``self.robust_n_beyond`` the number of
+        samples beyond; all three are None after any other run.  ``None`` runs exactly the solvers above."""
         self.huber_prior_value = None
+        self.robust_weights = self.robust_data_value = self.robust_n_beyond = None
+        if data_delta is not None and self.get_prior() != "separated":
+            raise ValueError("the robust data term (data_delta) comes with priors on the separated differences: set_prior('separated')")
         with self.installed_weights(weights):
+            if data_delta is not None:
+                x, gn, nit, vals, omega = _lib.solve_robust(self, data, mu, data_delta, mu_reg, float("inf") if delta is None else delta,
+                                                            x0, max_iter, tol, refresh, callback)
+                self.robust_data_value, self.robust_n_beyond, self.robust_weights = vals[0], int(round(vals[1])), omega
+                if delta is not None:
+                    self.huber_prior_value = vals[2]
+                return x, gn, nit
             if delta is None:
                 return _lib.solve(self, self._L.surfh_mmmg, data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
             x, gn, nit, self.huber_prior_value = _lib.solve_huber(self, data, mu, mu_reg, delta, x0, max_iter, tol, refresh, callback)
@@ -351,6 +377,21 @@ class spectroSigRLSCT(DataWeights, LinOp):
         _lib.check(self._L.surfh_huber_curv_dev(self._plan, _ptr(x_t), _ptr(p0_t), _ptr(p1_t), float(delta), _lib.dptr(out)))
         return out
 
+    def robust_data_dev(self, y_t, u_t, w_t, v_t, n: int, data_delta: float):
+        """v = sqrt(w) phi'(t), t = sqrt(w) (y - u), on device vectors of ``n`` floats (``w_t=None``: every weight 1; a weight of 0
+        takes its sample out whatever y holds); returns (sum phi(t), number of |t| > data_delta) (synchronises)."""
+        out = np.zeros(2, dtype=np.float64)
+        _lib.check(self._L.surfh_robust_data_dev(self._plan, _ptr(y_t), _ptr(u_t), None if w_t is None else _ptr(w_t), int(n),
+                                                 float(data_delta), _ptr(v_t), _lib.dptr(out)))
+        return float(out[0]), int(round(out[1]))
+
+    def robust_curv_dev(self, y_t, u_t, w_t, p0_t, p1_t, n: int, data_delta: float) -> np.ndarray:
+        """sum w omega(t) p0^2, p0 p1, p1^2 on device vectors of ``n`` floats: the data block of the robust majorant."""
+        out = np.zeros(3, dtype=np.float64)
+        _lib.check(self._L.surfh_robust_curv_dev(self._plan, _ptr(y_t), _ptr(u_t), None if w_t is None else _ptr(w_t), _ptr(p0_t),
+                                                 _ptr(p1_t), int(n), float(data_delta), _lib.dptr(out)))
+        return out
+
     def huber_prior_dev(self, x_t, g_t, mu_reg: float, delta: float) -> float:
         """g += mu_reg sum_k D_k^T phi'(D_k x) on device maps [T, Na, Nb]; returns sum_k sum phi(D_k x) (synchronises)."""
         out = C.c_double()
@@ -359,7 +400,7 @@ class spectroSigRLSCT(DataWeights, LinOp):
 
     # ---- the cube itself under Huber priors (models without templates) -----------------------
     def mmmg_vox(self, data, mu=1.0, spat_reg=1.0, spat_delta=1.0, spec_reg=1.0, spec_delta=1.0, x0=None, max_iter=10, tol=1e-12,
-                 refresh=50, callback=None, weights=None):
+                 refresh=50, callback=None, weights=None, data_delta=None):
         """3MG on the cube ``[Lc, Na, Nb]`` with Huber priors on its row, column and wavelength differences (the reference's
         vox_reconstruction, algorithms.py:27-71; include/surfh_amd.h: surfh_mmmg_huber_vox):
 
@@ -370,12 +411,21 @@ class spectroSigRLSCT(DataWeights, LinOp):
         here is ``[lambda][alpha][beta]``.  Needs a model built with ``templates=None``.  Returns ``(x, grad_norm, nit)`` as
         ``mmmg`` and leaves ``self.huber_prior_values = (spatial, spectral)``.  A delta of ``inf`` makes its term quadratic, a
         weight of 0 switches it off.  qmm and aljabr are not available to pin the restatement or the border conventions.
-        ``weights``: data weights for this solve, as in ``cg`` (the data term is then ``mu (y - A x)^T W (y - A x) / 2``)."""
+        ``weights``: data weights for this solve, as in ``cg`` (the data term is then ``mu (y - A x)^T W (y - A x) / 2``).
+        ``data_delta``: the robust data term of ``mmmg`` (include/surfh_amd.h: surfh_mmmg_robust_vox), with the same diagnostics
+        left in ``self.robust_weights``, ``self.robust_data_value`` and ``self.robust_n_beyond``; ``None``: the solver above."""
         self.huber_prior_values = None
+        self.robust_weights = self.robust_data_value = self.robust_n_beyond = None
         if self.lmm:
             raise ValueError("mmmg_vox reconstructs the cube itself: build the model with templates=None "
                              "(mmmg(delta=...) is the solver of a template model)")
         with self.installed_weights(weights):
+            if data_delta is not None:
+                x, gn, nit, vals, omega = _lib.solve_robust_vox(self, data, mu, data_delta, spat_reg, spat_delta, spec_reg, spec_delta,
+                                                                x0, max_iter, tol, refresh, callback)
+                self.robust_data_value, self.robust_n_beyond, self.robust_weights = vals[0], int(round(vals[1])), omega
+                self.huber_prior_values = (vals[2], vals[3])
+                return x, gn, nit
             x, gn, nit, self.huber_prior_values = _lib.solve_huber_vox(self, data, mu, spat_reg, spat_delta, spec_reg, spec_delta, x0,
                                                                        max_iter, tol, refresh, callback)
         return x, gn, nit
