@@ -406,6 +406,10 @@ int surfh_gemm_selftest_ksteps(int64_t near_far[2]);
  * Returns the number of tiles, or a negative error.                                                                     */
 int32_t surfh_klist_classify(const float *B, int32_t n, int32_t k, int64_t ldb, int32_t perm_p, int32_t perm_lin,
                              int32_t *records, int64_t capacity);
+/* host only (no GPU): the 2x2 step solve every 3MG solver shares, step = (s0, s1) with [[dBd, dBm], [dBm, mBm]] step = [dg, mg];
+ * (0, 0) without curvature along d (dBd <= 0 or NaN), (dg / dBd, 0) without a memory direction (mBm <= 0) or when the scaled
+ * system is singular (1 - dBm^2 / (dBd mBm) <= 1e-12) */
+int surfh_mm_step2(double dBd, double dBm, double mBm, double dg, double mg, double step[2]);
 
 /* ---- masked linear mixing model (MixingST, surfh/Models/mixing.py:276-337; kernels c_fast_forward_TST,
  * c_fast_adjoint_TST, c_precompute_TST of surfh/ToolsDir/cythons_files.pyx:370-463) ----

@@ -54,7 +54,7 @@ EXPORTS = [
     "surfh_adjoint_spec_dev", "surfh_normal_spec_dev", "surfh_prior_spec_add_dev", "surfh_set_prior", "surfh_set_data_weights", "surfh_set_data_weights_dev", "surfh_has_data_weights", "surfh_dot_dev", "surfh_cg_step_dev", "surfh_cg_dir_dev", "surfh_cg_iter_dev", "surfh_residual_dev",
     "surfh_cg_begin_dev", "surfh_cg_iter_nosync_dev", "surfh_cg_xupdate_nosync_dev", "surfh_cg_refresh_nosync_dev", "surfh_cg_trace",
     "surfh_profile_enable", "surfh_profile_filter", "surfh_profile_count", "surfh_profile_get", "surfh_profile_reset", "surfh_debug_copy",
-    "surfh_debug_dims", "surfh_gemm_selftest", "surfh_gemm_selftest_ksteps", "surfh_klist_classify",
+    "surfh_debug_dims", "surfh_gemm_selftest", "surfh_gemm_selftest_ksteps", "surfh_klist_classify", "surfh_mm_step2",
     "surfh_shepard", "surfh_shepard_last_error", "surfh_spectral_median", "surfh_nmf_cd", "surfh_templates_last_error",
 ]
 
@@ -157,6 +157,7 @@ def load():
     L.surfh_gemm_selftest_ksteps.argtypes = [C.POINTER(C.c_int64)]
     L.surfh_klist_classify.argtypes = [c_float_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64]
     L.surfh_klist_classify.restype = C.c_int32
+    L.surfh_mm_step2.argtypes = [C.c_double] * 5 + [c_double_p]
     L.surfh_shepard.argtypes = [C.c_int32, C.POINTER(C.c_int64), vp, vp, vp, c_int32_p, c_int32_p, C.c_int32, vp, vp,
                                 c_float_p, c_float_p, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, C.c_int32, vp,
                                 c_float_p]
@@ -174,79 +175,11 @@ def check(rc: int, exc=RuntimeError):
         raise exc(load().surfh_last_error().decode("utf-8", "replace"))
 
 
-def solve(model, fn, data, mu, mu_reg, x0, max_iter, tol, refresh, callback, planes=1, squeeze=True):
-    """Run one of the host-buffer solvers of the C ABI (``surfh_cg_cb``, ``surfh_mmmg``, ``surfh_cg_planes_cb``,
-    ``surfh_mmmg_planes_cb``) on ``model``'s plan.  ``grad_norm`` has one column per plane, or is ``[nit+1]`` when
+def _solve(model, fn, data, lead, x0, max_iter, tol, refresh, outs, callback, planes=1, squeeze=True):
+    """Run one host-buffer solver of the C ABI on ``model``'s plan:
+    ``fn(plan, y, *lead, x0, max_iter, tol, refresh, x, grad_norm, nit, *outs, callback, NULL)``, ``lead`` the solver's doubles
+    (weights, thresholds) and ``outs`` its further out-buffers.  ``grad_norm`` has one column per plane, or is ``[nit+1]`` when
     ``squeeze`` (a single image).  Returns ``(x, grad_norm, nit)``."""
-    def invoke(y, x0p, x, gn, nit, cb):
-        return fn(model._plan, y, float(mu), float(mu_reg), x0p, int(max_iter), float(tol), int(refresh), x, gn, nit, cb, None)
-    return _solve(model, invoke, data, x0, max_iter, callback, planes, squeeze)
-
-
-def solve_huber(model, data, mu, mu_reg, delta, x0, max_iter, tol, refresh, callback):
-    """``surfh_mmmg_huber`` on ``model``'s plan, arguments as ``solve``.  Returns ``(x, grad_norm, nit, prior_value)``,
-    prior_value = sum_k sum phi(D_k x) of the returned iterate."""
-    pv = C.c_double()
-
-    def invoke(y, x0p, x, gn, nit, cb):
-        return load().surfh_mmmg_huber(model._plan, y, float(mu), float(mu_reg), float(delta), x0p, int(max_iter), float(tol),
-                                       int(refresh), x, gn, nit, C.byref(pv), cb, None)
-    x, gn, nit = _solve(model, invoke, data, x0, max_iter, callback, 1, True)
-    return x, gn, nit, pv.value
-
-
-def solve_huber_planes(model, data, mu, mu_reg, delta, x0, max_iter, tol, refresh, callback, planes, squeeze):
-    """``surfh_mmmg_huber_planes`` on ``model``'s plan, arguments as ``solve``.  Returns ``(x, grad_norm, nit, prior_values)``,
-    prior_values[l] = sum_k sum phi(D_k x_l) of the returned iterate."""
-    pv = np.zeros(planes, dtype=np.float64)
-
-    def invoke(y, x0p, x, gn, nit, cb):
-        return load().surfh_mmmg_huber_planes(model._plan, y, float(mu), float(mu_reg), float(delta), x0p, int(max_iter), float(tol),
-                                              int(refresh), x, gn, nit, dptr(pv), cb, None)
-    x, gn, nit = _solve(model, invoke, data, x0, max_iter, callback, planes, squeeze)
-    return x, gn, nit, pv
-
-
-def solve_huber_vox(model, data, mu, spat_reg, spat_delta, spec_reg, spec_delta, x0, max_iter, tol, refresh, callback):
-    """``surfh_mmmg_huber_vox`` on ``model``'s plan (no templates), arguments as ``solve``.  Returns ``(x, grad_norm, nit,
-    (spatial, spectral))``, the two sums of phi at the returned iterate."""
-    pv = (C.c_double * 2)()
-
-    def invoke(y, x0p, x, gn, nit, cb):
-        return load().surfh_mmmg_huber_vox(model._plan, y, float(mu), float(spat_reg), float(spat_delta), float(spec_reg),
-                                           float(spec_delta), x0p, int(max_iter), float(tol), int(refresh), x, gn, nit, pv, cb, None)
-    x, gn, nit = _solve(model, invoke, data, x0, max_iter, callback, 1, True)
-    return x, gn, nit, (pv[0], pv[1])
-
-
-def solve_robust(model, data, mu, data_delta, mu_reg, delta, x0, max_iter, tol, refresh, callback):
-    """``surfh_mmmg_robust`` on ``model``'s plan, arguments as ``solve``.  Returns ``(x, grad_norm, nit, values, omega)``: values =
-    (sum phi(t), number of |t| > data_delta, prior value) and omega ``[osize]`` the robustness weights, at the returned iterate."""
-    vals = (C.c_double * 3)()
-    omega = np.zeros(model.osize, dtype=np.float32)
-
-    def invoke(y, x0p, x, gn, nit, cb):
-        return load().surfh_mmmg_robust(model._plan, y, float(mu), float(data_delta), float(mu_reg), float(delta), x0p, int(max_iter),
-                                        float(tol), int(refresh), x, gn, nit, vals, fptr(omega), cb, None)
-    x, gn, nit = _solve(model, invoke, data, x0, max_iter, callback, 1, True)
-    return x, gn, nit, tuple(vals), omega
-
-
-def solve_robust_vox(model, data, mu, data_delta, spat_reg, spat_delta, spec_reg, spec_delta, x0, max_iter, tol, refresh, callback):
-    """``surfh_mmmg_robust_vox`` on ``model``'s plan (no templates).  Returns ``(x, grad_norm, nit, values, omega)``, values =
-    (sum phi(t), number of |t| > data_delta, spatial prior value, spectral prior value)."""
-    vals = (C.c_double * 4)()
-    omega = np.zeros(model.osize, dtype=np.float32)
-
-    def invoke(y, x0p, x, gn, nit, cb):
-        return load().surfh_mmmg_robust_vox(model._plan, y, float(mu), float(data_delta), float(spat_reg), float(spat_delta),
-                                            float(spec_reg), float(spec_delta), x0p, int(max_iter), float(tol), int(refresh), x, gn,
-                                            nit, vals, fptr(omega), cb, None)
-    x, gn, nit = _solve(model, invoke, data, x0, max_iter, callback, 1, True)
-    return x, gn, nit, tuple(vals), omega
-
-
-def _solve(model, invoke, data, x0, max_iter, callback, planes, squeeze):
     y = np.ascontiguousarray(np.asarray(data, dtype=np.float32).reshape(-1))
     if y.size != model.osize:
         raise ValueError("data size mismatch")
@@ -268,11 +201,56 @@ def _solve(model, invoke, data, x0, max_iter, callback, planes, squeeze):
             return 1
 
     cb = CG_CALLBACK(tramp) if callback is not None else CG_CALLBACK()
-    check(invoke(fptr(y), fptr(x0a) if x0a is not None else None, fptr(x), dptr(gn), C.byref(nit), cb))
+    check(fn(model._plan, fptr(y), *map(float, lead), fptr(x0a) if x0a is not None else None, int(max_iter), float(tol),
+             int(refresh), fptr(x), dptr(gn), C.byref(nit), *outs, cb, None))
     if err:
         raise err[0]
     gn = gn[: nit.value + 1]
     return x.astype(np.float64).reshape(model.ishape), (gn[:, 0] if squeeze else gn).copy(), nit.value
+
+
+def solve(model, fn, data, mu, mu_reg, x0, max_iter, tol, refresh, callback, planes=1, squeeze=True):
+    """``surfh_cg_cb``, ``surfh_mmmg``, ``surfh_cg_planes_cb`` or ``surfh_mmmg_planes_cb`` (``fn``).  Returns ``(x, grad_norm, nit)``."""
+    return _solve(model, fn, data, (mu, mu_reg), x0, max_iter, tol, refresh, (), callback, planes, squeeze)
+
+
+def solve_huber(model, data, mu, mu_reg, delta, x0, max_iter, tol, refresh, callback):
+    """``surfh_mmmg_huber``.  Returns ``(x, grad_norm, nit, prior_value)``, prior_value = sum_k sum phi(D_k x) of the returned
+    iterate."""
+    pv = (C.c_double * 1)()
+    return _solve(model, load().surfh_mmmg_huber, data, (mu, mu_reg, delta), x0, max_iter, tol, refresh, (pv,), callback) + (pv[0],)
+
+
+def solve_huber_planes(model, data, mu, mu_reg, delta, x0, max_iter, tol, refresh, callback, planes, squeeze):
+    """``surfh_mmmg_huber_planes``.  Returns ``(x, grad_norm, nit, prior_values)``, prior_values[l] = sum_k sum phi(D_k x_l) of
+    the returned iterate."""
+    pv = np.zeros(planes, dtype=np.float64)
+    return _solve(model, load().surfh_mmmg_huber_planes, data, (mu, mu_reg, delta), x0, max_iter, tol, refresh, (dptr(pv),), callback,
+                  planes, squeeze) + (pv,)
+
+
+def solve_huber_vox(model, data, mu, spat_reg, spat_delta, spec_reg, spec_delta, x0, max_iter, tol, refresh, callback):
+    """``surfh_mmmg_huber_vox`` (a plan without templates).  Returns ``(x, grad_norm, nit, (spatial, spectral))``, the two sums
+    of phi at the returned iterate."""
+    pv = (C.c_double * 2)()
+    return _solve(model, load().surfh_mmmg_huber_vox, data, (mu, spat_reg, spat_delta, spec_reg, spec_delta), x0, max_iter, tol,
+                  refresh, (pv,), callback) + (tuple(pv),)
+
+
+def solve_robust(model, data, mu, data_delta, mu_reg, delta, x0, max_iter, tol, refresh, callback):
+    """``surfh_mmmg_robust``.  Returns ``(x, grad_norm, nit, values, omega)``: values = (sum phi(t), number of |t| > data_delta,
+    prior value) and omega ``[osize]`` the robustness weights, at the returned iterate."""
+    vals, omega = (C.c_double * 3)(), np.zeros(model.osize, dtype=np.float32)
+    return _solve(model, load().surfh_mmmg_robust, data, (mu, data_delta, mu_reg, delta), x0, max_iter, tol, refresh,
+                  (vals, fptr(omega)), callback) + (tuple(vals), omega)
+
+
+def solve_robust_vox(model, data, mu, data_delta, spat_reg, spat_delta, spec_reg, spec_delta, x0, max_iter, tol, refresh, callback):
+    """``surfh_mmmg_robust_vox`` (a plan without templates).  Returns ``(x, grad_norm, nit, values, omega)``, values =
+    (sum phi(t), number of |t| > data_delta, spatial prior value, spectral prior value)."""
+    vals, omega = (C.c_double * 4)(), np.zeros(model.osize, dtype=np.float32)
+    return _solve(model, load().surfh_mmmg_robust_vox, data, (mu, data_delta, spat_reg, spat_delta, spec_reg, spec_delta), x0, max_iter,
+                  tol, refresh, (vals, fptr(omega)), callback) + (tuple(vals), omega)
 
 
 def fptr(a: np.ndarray):

@@ -1,6 +1,7 @@
 // HBM-bound kernels of the surfh hot path for gfx950 (see kernels.h for the contracts).
 #include "kernels.h"
 #include "huber_dev.h"
+#include "mm_step.h"
 #include <algorithm>
 #include <cfloat>
 #include <cstdlib>
@@ -1234,15 +1235,8 @@ __global__ __launch_bounds__(TPB) void mmmg_step_planes_kernel(float *__restrict
         v[3] += (double)m[off + i] * ri;
     }
     block_sum_bcast<4>(v);
-    const double dQd = v[0], dQm = v[1], dr = v[2], mr = v[3], mQm = mqm[blockIdx.x];
-    double s0 = dQd > 0.0 ? dr / dQd : 0.0, s1 = 0.0;
-    if (dQd > 0.0 && mQm > 0.0) {
-        const double sc = sqrt(dQd * mQm), c = dQm / sc, det = 1.0 - c * c;
-        if (det > 1e-12) {
-            s0 = (dr / dQd - c * mr / sc) / det;
-            s1 = (mr / mQm - c * dr / sc) / det;
-        }
-    }
+    double s0, s1;
+    mm_step2(v[0], v[1], mqm[blockIdx.x], v[2], v[3], &s0, &s1);
     const float f0 = (float)s0, f1 = (float)s1;
     for (long i = threadIdx.x; i < npix; i += TPB) {
         const float mv = f0 * d[off + i] + f1 * m[off + i];
@@ -1436,16 +1430,9 @@ __global__ __launch_bounds__(TPB) void huber_step_planes_kernel(float *__restric
     block_sum_bcast<4>(v);
     const double beta = sc[HP_BETA * L + l], mBm = sc[HP_MBM * L + l];
     const double c00 = sc[HP_C00 * L + l], c01 = sc[HP_C01 * L + l], c11 = sc[HP_C11 * L + l];
-    const double dBd = v[0] + reg * (c00 + beta * (2.0 * c01 + beta * c11)), dBm = v[1] + reg * (c01 + beta * c11);
-    const double dg = v[2], mg = v[3];
-    double s0 = dBd > 0.0 ? dg / dBd : 0.0, s1 = 0.0;
-    if (dBd > 0.0 && mBm > 0.0) {
-        const double sq = sqrt(dBd * mBm), cc = dBm / sq, det = 1.0 - cc * cc;      // scaled 2x2 system
-        if (det > 1e-12) {
-            s0 = (dg / dBd - cc * mg / sq) / det;
-            s1 = (mg / mBm - cc * dg / sq) / det;
-        }
-    }
+    double dWd, dWm, s0, s1;
+    mm_block_of_d(c00, c01, c11, beta, &dWd, &dWm);
+    mm_step2(v[0] + reg * dWd, v[1] + reg * dWm, mBm, v[2], v[3], &s0, &s1);
     const float f0 = (float)s0, f1 = (float)s1;
     for (long i = threadIdx.x; i < npix; i += TPB) {
         const float mv = f0 * d[off + i] + f1 * m[off + i];

@@ -27,6 +27,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -36,6 +37,7 @@
 #include "dft_ct.h"
 #include "gemm_f32.h"
 #include "kernels.h"
+#include "mm_step.h"
 
 namespace {
 
@@ -2425,6 +2427,53 @@ int callback_iterate(surfh_plan *p, surfh_cg_callback callback, void *user, int 
     return CB_GO_ON;
 }
 
+// ---- the frame of every 3MG loop (the variants and what each plugs in: the 3MG sections below) ----
+// Start: the work buffers (cg_hg where the variant keeps -g apart from r), y [osize] to yd, x0 or zeros to cg_x, zeros to the
+// memory direction cg_d and to its image: cg_qm (with cg_dd beside it), or the caller's detector vector `am` [osize].
+int mmmg_begin(surfh_plan *p, bool want_hg, const float *y, float *yd, const float *x0, float *am = nullptr) {
+    hipStream_t s = p->stream;
+    if (ensure_cg(p)) return 1;
+    if (!am && !p->cg_qm && (dev_alloc(&p->cg_qm, (size_t)p->isize) || dev_alloc(&p->cg_dd, (size_t)p->isize))) return 1;
+    if (want_hg && !p->cg_hg && dev_alloc(&p->cg_hg, (size_t)p->isize)) return 1;
+    HIP_OK(hipMemcpyAsync(yd, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
+    if (x0)
+        HIP_OK(hipMemcpyAsync(p->cg_x, x0, p->isize * sizeof(float), hipMemcpyHostToDevice, s));
+    else
+        LAUNCH_OK(launch_fill_zero(s, p->cg_x, p->isize));
+    LAUNCH_OK(launch_fill_zero(s, p->cg_d, p->isize));
+    if (am)
+        LAUNCH_OK(launch_fill_zero(s, am, p->osize));
+    else
+        LAUNCH_OK(launch_fill_zero(s, p->cg_qm, p->isize));
+    return 0;
+}
+// Top of iteration `it`, once its trace entry is stored: the callback sees the iterate (it > 0), then the stopping rule on
+// `norm` (the gradient norm; the largest over the planes) against scale * tol.  CB_STOP: leave the loop, the result stands.
+int mmmg_check(surfh_plan *p, surfh_cg_callback callback, void *user, int it, int max_iter, const double *grad_norm, double norm,
+               double scale, double tol, std::vector<float> &hx) {
+    if (it > 0)
+        if (const int rc = callback_iterate(p, callback, user, it, grad_norm, p->cg_x, hx)) return rc;
+    return it >= max_iter || norm < scale * tol ? CB_STOP : CB_GO_ON;
+}
+// the carried vector (r, or u = A x) is recomputed from x in the iterations `refresh` divides
+bool refresh_due(int refresh, int it) { return refresh > 0 && it % refresh == 0; }
+int mmmg_finish(surfh_plan *p, float *x) {
+    HIP_OK(hipMemcpyAsync(x, p->cg_x, p->isize * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+// A device diagnostic of one pass: the launch under its Prof name, then k doubles from `src` (device) to `dst` (host).
+int diag_pass(surfh_plan *p, const char *name, const std::function<int()> &launch, const double *src, double *dst, size_t k) {
+    HIP_OK(hipSetDevice(p->dev));
+    {
+        Prof pr(p, name);
+        LAUNCH_OK(launch());
+    }
+    HIP_OK(hipMemcpyAsync(dst, src, k * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
 // The loop bench.py times, behind the exported solver: vectors = the maps' Parseval-scaled half spectra (surfh_normal_spec_dev:
 // no transform of the maps, no padding, no prior kernel inside an iteration), every scalar on the device
 // (surfh_cg_iter_nosync_dev), and the host reads the r.r trace -- the stopping test of qmm.lcg -- only every CG_CHECK iterations:
@@ -2538,96 +2587,31 @@ int surfh_cg(surfh_plan *p, const float *y, double mu, double mu_reg, const floa
 }
 
 // ---- 3MG (majorize-minimize memory gradient, qmm.mmmg; selected by method != 'lcg' at fusion_CT.py:194-198) ----
-// For the quadratic objectives of this path the quadratic majorant is the criterion itself, so the MM step is the exact
-// minimiser of the criterion over span{-grad, previous move}.  qmm solves the 2x2 system in the basis [-grad, move] with the
-// operator applied to the gradient; in fp32 that form loses the conjugacy (the determinant r.Qr m.Qm - (r.Qm)^2 cancels) and
-// was measured to converge visibly slower than CG.  The same subspace is therefore spanned by [d, m], d = r + beta m made
-// Q-orthogonal to the previous move m with the carried image Qm, and the operator is applied to d: the 2x2 system
-//   [[d.Qd, d.Qm], [d.Qm, m.Qm]] step = [d.r, m.r]
-// is then nearly diagonal.  Same iterates in exact arithmetic, one normal-operator application per iteration; r is carried as
-// r -= Q move and recomputed from scratch every `refresh` iterations.  numpy's pinv cut (1e-15 of the unscaled matrix),
-// which in qmm drops the memory direction once |move|^2 / |grad|^2 < 1e-15, is not reproduced: the direction is dropped
-// only when the scaled system is singular.
-int surfh_mmmg(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
-               int32_t refresh, float *x, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
-    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
-    if (p->T <= 0) return fail("surfh_mmmg needs templates (the priors act on abundance maps)");
-    std::vector<float> hx;
-    HIP_OK(hipSetDevice(p->dev));
-    if (ensure_cg(p)) return 1;
-    if (!p->cg_qm && (dev_alloc(&p->cg_qm, (size_t)p->isize) || dev_alloc(&p->cg_dd, (size_t)p->isize))) return 1;
-    hipStream_t s = p->stream;
-    const long n = p->isize;
-    float *r = p->cg_r, *m = p->cg_d, *d = p->cg_dd, *qd = p->cg_q, *qm = p->cg_qm;
-    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
-    if (x0)
-        HIP_OK(hipMemcpyAsync(p->cg_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
-    else
-        LAUNCH_OK(launch_fill_zero(s, p->cg_x, n));
-    LAUNCH_OK(launch_fill_zero(s, m, n));
-    LAUNCH_OK(launch_fill_zero(s, qm, n));
-    if (solver_setup(p, p->io_y, p->cg_x, mu, mu_reg)) return 1;
-    double h[6];
-    *nit = 0;
-    for (int it = 0;; ++it) {
-        // h0 = r.r (stopping quantity and trace entry), h1 = r.Qm, h2 = m.Qm
-        LAUNCH_OK(launch_dot(s, r, r, n, p->dscratch, p->dscal + 0));
-        LAUNCH_OK(launch_dot(s, r, qm, n, p->dscratch, p->dscal + 1));
-        LAUNCH_OK(launch_dot(s, m, qm, n, p->dscratch, p->dscal + 2));
-        HIP_OK(hipMemcpyAsync(h, p->dscal, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_OK(hipStreamSynchronize(s));
-        grad_norm[it] = std::sqrt(h[0]);
-        if (const int rc = it > 0 ? callback_iterate(p, callback, user, it, grad_norm, p->cg_x, hx) : CB_GO_ON) {
-            if (rc == CB_STOP) break;
-            return 1;
-        }
-        if (it >= max_iter || grad_norm[it] < (double)n * tol) break;
-        const double mQm = h[2], beta = mQm > 0.0 ? -h[1] / mQm : 0.0;
-        LAUNCH_OK(launch_lincomb(s, d, r, m, n, beta));
-        if (normal_prior(p, d, qd, mu, mu_reg)) return 1;
-        LAUNCH_OK(launch_dot(s, d, qd, n, p->dscratch, p->dscal + 3));
-        LAUNCH_OK(launch_dot(s, d, qm, n, p->dscratch, p->dscal + 4));
-        LAUNCH_OK(launch_dot(s, d, r, n, p->dscratch, p->dscal + 5));
-        LAUNCH_OK(launch_dot(s, m, r, n, p->dscratch, p->dscal + 6));
-        HIP_OK(hipMemcpyAsync(h, p->dscal + 3, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_OK(hipStreamSynchronize(s));
-        const double dQd = h[0], dQm = h[1], dr = h[2], mr = h[3];
-        if (!(dQd > 0.0)) return fail("3MG: non-positive curvature d.Qd = %g at iteration %d", dQd, it);
-        double s0 = dr / dQd, s1 = 0.0;
-        if (mQm > 0.0) {
-            const double c = dQm / std::sqrt(dQd * mQm), det = 1.0 - c * c;      // scaled 2x2 system
-            if (det > 1e-12) {
-                s0 = (dr / dQd - c * mr / std::sqrt(dQd * mQm)) / det;
-                s1 = (mr / mQm - c * dr / std::sqrt(dQd * mQm)) / det;
-            }
-        }
-        const bool fresh = refresh > 0 && it % refresh == 0;
-        {
-            Prof pr(p, "mmmg_update");
-            LAUNCH_OK(launch_mmmg_update(s, p->cg_x, r, d, m, qm, qd, n, s0, s1, fresh ? 0 : 1));
-        }
-        if (fresh) {
-            if (normal_prior(p, p->cg_x, qd, mu, mu_reg)) return 1;
-            LAUNCH_OK(launch_residual(s, r, p->cg_b, qd, n));
-        }
-        *nit = it + 1;
-    }
-    HIP_OK(hipMemcpyAsync(x, p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    return 0;
-}
-
-// ---- 3MG with Huber priors (qmm.mmmg with qmm.Huber on the row and column differences: the reference's lmm_reconstruction,
+// Every variant minimises a quadratic majorant with matrix B(x) at the iterate over span{-g, m}, m the previous move.  qmm
+// solves the 2x2 system in the basis [-g, m] with the operator applied to the gradient; in fp32 that form loses the conjugacy
+// (the determinant cancels) and was measured to converge visibly slower than CG.  The same subspace is therefore spanned by
+// [d, m], d = -g + beta m made B-orthogonal to m with the carried image of m, and the operator is applied to d: the system
+//   [[d.Bd, d.Bm], [d.Bm, m.Bm]] step = [d.(-g), m.(-g)]                                   (mm_step.h: mm_step2)
+// is then nearly diagonal.  Same iterates in exact arithmetic, one operator application per iteration; the carried residual
+// follows by linearity and is recomputed from x every `refresh` iterations.  numpy's pinv cut (1e-15 of the unscaled matrix),
+// which in qmm drops the memory direction once |move|^2 / |grad|^2 < 1e-15, is not reproduced: the direction is dropped only
+// when the scaled system is singular.  All loops stand on one frame (mmmg_begin, mmmg_check, refresh_due, mmmg_finish):
+//   mmmg_huber_loop    surfh_mmmg, surfh_mmmg_huber, surfh_mmmg_huber_vox       beta and the system on the host, 2 syncs / iteration
+//   mmmg_robust_loop   surfh_mmmg_robust, surfh_mmmg_robust_vox                 one read-back, 1 sync / iteration
+//   mmmg_planes_loop   surfh_mmmg_planes_cb, surfh_mmmg_huber_planes            beta and the system per plane on the device, 1 sync
+//
+// Huber priors (qmm.Huber on the row and column differences: the reference's lmm_reconstruction,
 // surfh/ToolsDir/algorithms.py:73-106).  The majorant at x is half-quadratic (Geman-Reynolds):
-//   B(x) = mu A^T A + mu_reg sum_k D_k^T diag(w(D_k x)) D_k,   w(u) = phi'(u) / u,
-// minimised over span{-g, m} (m the previous move).  The basis is [d, m] with d = -g + beta m B(x)-orthogonal to m, as in
-// surfh_mmmg: beta from the carried data image Q_D m = mu A^T A m and the prior block huber_curv(x; -g, m).  The data part
-// r = b - mu A^T A x is carried by linearity (recomputed every `refresh` iterations).  Two stencil passes per iteration, each
-// followed by a one-block reduction: huber_grad gives -g = r - mu_reg sum_k D_k^T phi'(D_k x), |g|^2 and the prior value;
-// huber_curv gives the prior block c = [(-g).W(-g), (-g).W m, m.W m] (W = D^T diag(w) D at x).  The block of (d, m) follows
-// from c by linearity in float64 (d.Wd = c00 + 2 beta c01 + beta^2 c11, d.Wm = c01 + beta c11); d.Bd = g.Bg - (g.Bm)^2 / m.Bm
-// is the Schur complement of a positive semi-definite 2x2 matrix, which float64 forms from fp64-accumulated sums with no
-// cancellation that matters at fp32 data precision.  Two host synchronisations per iteration (beta, then the 2x2 system).
+//   B(x) = mu A^T A + mu_reg sum_k D_k^T diag(w(D_k x)) D_k,   w(u) = phi'(u) / u.
+// beta comes from the carried data image Q_D m = mu A^T A m and the prior block huber_curv(x; -g, m); the data part
+// r = b - mu A^T A x of -g is the carried residual.  Two stencil passes per iteration, each followed by a one-block reduction:
+// huber_grad gives -g = r - mu_reg sum_k D_k^T phi'(D_k x), |g|^2 and the prior value; huber_curv gives the prior block
+// c = [(-g).W(-g), (-g).W m, m.W m] (W = D^T diag(w) D at x).  The block of (d, m) follows from c by linearity in float64
+// (mm_block_of_d); d.Bd = g.Bg - (g.Bm)^2 / m.Bm is the Schur complement of a positive semi-definite 2x2 matrix, which float64
+// forms from fp64-accumulated sums with no cancellation that matters at fp32 data precision.
+// The quadratic solver surfh_mmmg is the same loop with no Huber family: its prior rides in the operator Q = mu A^T A + mu_reg
+// prior, so -g is the carried residual r itself, the grad pass is the dot r.r and there is no curv pass; the majorant is the
+// criterion, the step its exact minimiser over the subspace.
 namespace {
 // the kernels take delta in fp32: a positive delta below FLT_MIN would flush to 0 there (every weight off u = 0 would vanish)
 int huber_args(double mu_reg, double delta) {
@@ -2641,15 +2625,11 @@ int surfh_huber_prior_dev(surfh_plan *p, const float *x_dev, float *g_dev, doubl
     if (!p || !x_dev || !g_dev) return fail("null argument");
     if (p->T <= 0) return fail("prior is defined on abundance maps (needs templates)");
     if (huber_args(mu_reg, delta)) return 1;
-    HIP_OK(hipSetDevice(p->dev));
-    {
-        Prof pr(p, "huber_grad");
-        LAUNCH_OK(launch_huber_grad(p->stream, x_dev, g_dev, g_dev, p->T, p->Na, p->Nb, (float)mu_reg, (float)delta, p->dscratch,
-                                    p->dscal + 0));
-    }
     double h[2];
-    HIP_OK(hipMemcpyAsync(h, p->dscal, 2 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-    HIP_OK(hipStreamSynchronize(p->stream));
+    const auto pass = [&] {
+        return launch_huber_grad(p->stream, x_dev, g_dev, g_dev, p->T, p->Na, p->Nb, (float)mu_reg, (float)delta, p->dscratch, p->dscal);
+    };
+    if (diag_pass(p, "huber_grad", pass, p->dscal, h, 2)) return 1;
     if (value) *value = h[1];
     return 0;
 }
@@ -2657,20 +2637,17 @@ int surfh_huber_curv_dev(surfh_plan *p, const float *x_dev, const float *p0_dev,
     if (!p || !x_dev || !p0_dev || !p1_dev || !sums) return fail("null argument");
     if (p->T <= 0) return fail("prior is defined on abundance maps (needs templates)");
     if (huber_args(0.0, delta)) return 1;
-    HIP_OK(hipSetDevice(p->dev));
-    {
-        Prof pr(p, "huber_curv");
-        LAUNCH_OK(launch_huber_curv(p->stream, x_dev, p0_dev, p1_dev, p->T, p->Na, p->Nb, (float)delta, p->dscratch, p->dscal + 0));
-    }
-    HIP_OK(hipMemcpyAsync(sums, p->dscal, 3 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-    HIP_OK(hipStreamSynchronize(p->stream));
-    return 0;
+    const auto pass = [&] {
+        return launch_huber_curv(p->stream, x_dev, p0_dev, p1_dev, p->T, p->Na, p->Nb, (float)delta, p->dscratch, p->dscal);
+    };
+    return diag_pass(p, "huber_curv", pass, p->dscal, sums, 3);
 }
 
 namespace {
-// The prior of one 3MG/Huber run: `nfam` families of differences with their weights, and the two stencil passes on the solver's
+// The prior of one 3MG run: `nfam` families of differences with their weights, and the two stencil passes on the solver's
 // vectors.  grad: out = src - sum_f reg[f] D_f^T phi'(D_f x), sums[0] = out.out, sums[1 + f] = sum phi of family f;
 // curv: sums[3 f ..] = the (p0, p0), (p0, p1), (p1, p1) block of family f under w(D_f x).  The weights enter on the host, in float64.
+// nfam = 0 is the quadratic solver: out is src itself (grad leaves sums[0] = src.src), the prior is quad_reg's, in the operator.
 struct HuberPrior {
     int nfam;
     double reg[2];
@@ -2678,34 +2655,28 @@ struct HuberPrior {
     int (*grad)(surfh_plan *p, const HuberPrior &h, const float *x, const float *src, float *out, double *sums);
     int (*curv)(surfh_plan *p, const HuberPrior &h, const float *x, const float *p0, const float *p1, double *sums);
     float delta[2];
+    double quad_reg;                                                        // weight of the quadratic prior the operator carries
 };
 
-// the loop both Huber solvers run; prior_values receives nfam doubles (may be NULL)
+// the loop of the map and cube solvers; prior_values receives nfam doubles (may be NULL)
 int mmmg_huber_loop(surfh_plan *p, const HuberPrior &hp, const float *y, double mu, const float *x0, int32_t max_iter, double tol,
                     int32_t refresh, float *x, double *grad_norm, int32_t *nit, double *prior_values, surfh_cg_callback callback,
                     void *user) {
     std::vector<float> hx;
     HIP_OK(hipSetDevice(p->dev));
-    if (ensure_cg(p)) return 1;
-    if (!p->cg_qm && (dev_alloc(&p->cg_qm, (size_t)p->isize) || dev_alloc(&p->cg_dd, (size_t)p->isize))) return 1;
-    if (!p->cg_hg && dev_alloc(&p->cg_hg, (size_t)p->isize)) return 1;
+    if (mmmg_begin(p, hp.nfam > 0, y, p->io_y, x0)) return 1;
     hipStream_t s = p->stream;
     const long n = p->isize;
     const int F = hp.nfam;
-    float *r = p->cg_r, *m = p->cg_d, *d = p->cg_dd, *qd = p->cg_q, *qm = p->cg_qm, *ng = p->cg_hg;
-    double *sc = p->dscal;               // [0 .. F] huber_grad (|g|^2, F prior values), [F+1, F+2] dots, [F+3 .. 4F+2] huber_curv
-    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
-    if (x0)
-        HIP_OK(hipMemcpyAsync(p->cg_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
-    else
-        LAUNCH_OK(launch_fill_zero(s, p->cg_x, n));
-    LAUNCH_OK(launch_fill_zero(s, m, n));
-    LAUNCH_OK(launch_fill_zero(s, qm, n));
-    if (solver_setup(p, p->io_y, p->cg_x, mu, 0.0)) return 1;          // r = b - mu A^T A x: the data part of -g
+    float *r = p->cg_r, *m = p->cg_d, *d = p->cg_dd, *qd = p->cg_q, *qm = p->cg_qm, *ng = F ? p->cg_hg : r;
+    // [0 .. F] the grad pass (|g|^2, F prior values), [F+1, F+2] dots, [F+3 .. 4F+2] the curv pass; then the step's four dots
+    // over the block just read (the quadratic solver's behind it)
+    double *sc = p->dscal, *sd = sc + (F ? 0 : 3);
+    if (solver_setup(p, p->io_y, p->cg_x, mu, hp.quad_reg)) return 1;  // r = b - Q x: the data part of -g (all of it when F = 0)
     double h[11], prior[2] = {0.0, 0.0};
     *nit = 0;
     for (int it = 0;; ++it) {
-        // -g, |g|^2 and the prior values; then -g.Q_D m, m.Q_D m and the prior blocks of (-g, m) under w(D x)
+        // -g, |g|^2 and the prior values; then -g.Qm, m.Qm and the prior blocks of (-g, m) under w(D x)
         if (hp.grad(p, hp, p->cg_x, r, ng, sc + 0)) return 1;
         LAUNCH_OK(launch_dot(s, ng, qm, n, p->dscratch, sc + F + 1));
         LAUNCH_OK(launch_dot(s, m, qm, n, p->dscratch, sc + F + 2));
@@ -2714,11 +2685,10 @@ int mmmg_huber_loop(surfh_plan *p, const HuberPrior &hp, const float *y, double 
         HIP_OK(hipStreamSynchronize(s));
         grad_norm[it] = std::sqrt(h[0]);
         for (int f = 0; f < F; ++f) prior[f] = h[1 + f];
-        if (const int rc = it > 0 ? callback_iterate(p, callback, user, it, grad_norm, p->cg_x, hx) : CB_GO_ON) {
+        if (const int rc = mmmg_check(p, callback, user, it, max_iter, grad_norm, grad_norm[it], (double)n, tol, hx)) {
             if (rc == CB_STOP) break;
             return 1;
         }
-        if (it >= max_iter || grad_norm[it] < (double)n * tol) break;
         double c[2][3], gBm = h[F + 1], mBm = h[F + 2];
         for (int f = 0; f < F; ++f) {
             for (int k = 0; k < 3; ++k) c[f][k] = h[F + 3 + 3 * f + k];
@@ -2727,48 +2697,47 @@ int mmmg_huber_loop(surfh_plan *p, const HuberPrior &hp, const float *y, double 
         }
         const double beta = mBm > 0.0 ? -gBm / mBm : 0.0;
         LAUNCH_OK(launch_lincomb(s, d, ng, m, n, beta));
-        if (normal_dev(p, d, qd, mu)) return 1;
-        // h0 = d.Q_D d, h1 = d.Q_D m, h2 = d.(-g), h3 = m.(-g)
-        LAUNCH_OK(launch_dot(s, d, qd, n, p->dscratch, sc + 0));
-        LAUNCH_OK(launch_dot(s, d, qm, n, p->dscratch, sc + 1));
-        LAUNCH_OK(launch_dot(s, d, ng, n, p->dscratch, sc + 2));
-        LAUNCH_OK(launch_dot(s, m, ng, n, p->dscratch, sc + 3));
-        HIP_OK(hipMemcpyAsync(h, sc, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (normal_prior(p, d, qd, mu, hp.quad_reg)) return 1;
+        // h0 = d.Qd, h1 = d.Qm, h2 = d.(-g), h3 = m.(-g)
+        LAUNCH_OK(launch_dot(s, d, qd, n, p->dscratch, sd + 0));
+        LAUNCH_OK(launch_dot(s, d, qm, n, p->dscratch, sd + 1));
+        LAUNCH_OK(launch_dot(s, d, ng, n, p->dscratch, sd + 2));
+        LAUNCH_OK(launch_dot(s, m, ng, n, p->dscratch, sd + 3));
+        HIP_OK(hipMemcpyAsync(h, sd, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
         HIP_OK(hipStreamSynchronize(s));
-        double dBd = h[0], dBm = h[1];
-        const double dg = h[2], mg = h[3];
-        for (int f = 0; f < F; ++f) {                                  // the block of (d, m) from that of (-g, m), by linearity
-            const double dWd = c[f][0] + beta * (2.0 * c[f][1] + beta * c[f][2]), dWm = c[f][1] + beta * c[f][2];
+        double dBd = h[0], dBm = h[1], s0, s1;
+        for (int f = 0; f < F; ++f) {
+            double dWd, dWm;
+            mm_block_of_d(c[f][0], c[f][1], c[f][2], beta, &dWd, &dWm);
             dBd += hp.reg[f] * dWd;
             dBm += hp.reg[f] * dWm;
         }
-        if (!(dBd > 0.0)) return fail("3MG (%s): non-positive curvature d.Bd = %g at iteration %d", hp.what, dBd, it);
-        double s0 = dg / dBd, s1 = 0.0;
-        if (mBm > 0.0) {
-            const double sq = std::sqrt(dBd * mBm), cc = dBm / sq, det = 1.0 - cc * cc;      // scaled 2x2 system
-            if (det > 1e-12) {
-                s0 = (dg / dBd - cc * mg / sq) / det;
-                s1 = (mg / mBm - cc * dg / sq) / det;
-            }
-        }
-        const bool fresh = refresh > 0 && it % refresh == 0;
+        if (!(dBd > 0.0))
+            return F ? fail("3MG (%s): non-positive curvature d.Bd = %g at iteration %d", hp.what, dBd, it)
+                     : fail("3MG: non-positive curvature d.Qd = %g at iteration %d", dBd, it);
+        mm_step2(dBd, dBm, mBm, h[2], h[3], &s0, &s1);
+        const bool fresh = refresh_due(refresh, it);
         {
             Prof pr(p, "mmmg_update");
             LAUNCH_OK(launch_mmmg_update(s, p->cg_x, r, d, m, qm, qd, n, s0, s1, fresh ? 0 : 1));
         }
         if (fresh) {
-            if (normal_dev(p, p->cg_x, qd, mu)) return 1;
+            if (normal_prior(p, p->cg_x, qd, mu, hp.quad_reg)) return 1;
             LAUNCH_OK(launch_residual(s, r, p->cg_b, qd, n));
         }
         *nit = it + 1;
     }
     if (prior_values)
         for (int f = 0; f < F; ++f) prior_values[f] = prior[f];
-    HIP_OK(hipMemcpyAsync(x, p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    return 0;
+    return mmmg_finish(p, x);
 }
 
+// no Huber family (surfh_mmmg): -g is the carried residual, in place
+int quad_grad(surfh_plan *p, const HuberPrior &, const float *, const float *src, float *, double *sums) {
+    LAUNCH_OK(launch_dot(p->stream, src, src, p->isize, p->dscratch, sums));
+    return 0;
+}
+int quad_curv(surfh_plan *, const HuberPrior &, const float *, const float *, const float *, double *) { return 0; }
 // the maps' prior: one family (rows and columns under one weight and one threshold)
 int maps_grad(surfh_plan *p, const HuberPrior &h, const float *x, const float *src, float *out, double *sums) {
     Prof pr(p, "huber_grad");
@@ -2804,6 +2773,14 @@ int surfh_mmmg_huber(surfh_plan *p, const float *y, double mu, double mu_reg, do
     return mmmg_huber_loop(p, hp, y, mu, x0, max_iter, tol, refresh, x, grad_norm, nit, prior_value, callback, user);
 }
 
+int surfh_mmmg(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
+               int32_t refresh, float *x, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
+    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (p->T <= 0) return fail("surfh_mmmg needs templates (the priors act on abundance maps)");
+    const HuberPrior hp = {0, {0.0, 0.0}, nullptr, quad_grad, quad_curv, {0.f, 0.f}, mu_reg};
+    return mmmg_huber_loop(p, hp, y, mu, x0, max_iter, tol, refresh, x, grad_norm, nit, nullptr, callback, user);
+}
+
 // ---- the same solver on the cube itself (the reference's vox_reconstruction, surfh/ToolsDir/algorithms.py:27-71): no templates,
 // Huber priors on the row, column and wavelength differences, the two spatial families under (spat_reg, spat_delta), the spectral
 // one under (spec_reg, spec_delta).  The majorant gains the block spec_reg Dl^T diag(w(Dl x)) Dl; everything else is the loop above.
@@ -2812,15 +2789,12 @@ int surfh_huber_vox_prior_dev(surfh_plan *p, const float *x_dev, float *g_dev, d
     if (!p || !x_dev || !g_dev) return fail("null argument");
     if (p->T > 0) return fail("the voxel-wise prior is defined on the cube (needs a plan without templates)");
     if (huber_args(spat_reg, spat_delta) || huber_args(spec_reg, spec_delta)) return 1;
-    HIP_OK(hipSetDevice(p->dev));
-    {
-        Prof pr(p, "huber_vox_grad");
-        LAUNCH_OK(launch_huber_vox_grad(p->stream, x_dev, g_dev, g_dev, p->Lc, p->Na, p->Nb, (float)spat_reg, (float)spat_delta,
-                                        (float)spec_reg, (float)spec_delta, p->dscratch, p->dscal + 0));
-    }
     double h[3];
-    HIP_OK(hipMemcpyAsync(h, p->dscal, 3 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-    HIP_OK(hipStreamSynchronize(p->stream));
+    const auto pass = [&] {
+        return launch_huber_vox_grad(p->stream, x_dev, g_dev, g_dev, p->Lc, p->Na, p->Nb, (float)spat_reg, (float)spat_delta,
+                                     (float)spec_reg, (float)spec_delta, p->dscratch, p->dscal);
+    };
+    if (diag_pass(p, "huber_vox_grad", pass, p->dscal, h, 3)) return 1;
     if (values) {
         values[0] = h[1];
         values[1] = h[2];
@@ -2832,15 +2806,11 @@ int surfh_huber_vox_curv_dev(surfh_plan *p, const float *x_dev, const float *p0_
     if (!p || !x_dev || !p0_dev || !p1_dev || !sums) return fail("null argument");
     if (p->T > 0) return fail("the voxel-wise prior is defined on the cube (needs a plan without templates)");
     if (huber_args(0.0, spat_delta) || huber_args(0.0, spec_delta)) return 1;
-    HIP_OK(hipSetDevice(p->dev));
-    {
-        Prof pr(p, "huber_vox_curv");
-        LAUNCH_OK(launch_huber_vox_curv(p->stream, x_dev, p0_dev, p1_dev, p->Lc, p->Na, p->Nb, (float)spat_delta, (float)spec_delta,
-                                        p->dscratch, p->dscal + 0));
-    }
-    HIP_OK(hipMemcpyAsync(sums, p->dscal, 6 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-    HIP_OK(hipStreamSynchronize(p->stream));
-    return 0;
+    const auto pass = [&] {
+        return launch_huber_vox_curv(p->stream, x_dev, p0_dev, p1_dev, p->Lc, p->Na, p->Nb, (float)spat_delta, (float)spec_delta,
+                                     p->dscratch, p->dscal);
+    };
+    return diag_pass(p, "huber_vox_curv", pass, p->dscal, sums, 6);
 }
 
 int surfh_mmmg_huber_vox(surfh_plan *p, const float *y, double mu, double spat_reg, double spat_delta, double spec_reg,
@@ -2861,8 +2831,7 @@ int surfh_mmmg_huber_vox(surfh_plan *p, const float *y, double mu, double spat_r
 // robust_data (v = sqrt(w) phi'(t), sum phi, count beyond) -> adjoint (the data part of -g) -> the prior's grad pass (-g, |g|^2,
 // prior values) -> forward (a_g = A (-g)) -> robust_curv (the data block of (a_g, a_m)) -> the prior's curv pass -> one read-back.
 // The host forms, in float64, the blocks of B = mu A^T diag(w omega) A + sum_f reg_f D_f^T diag(w_f) D_f on (-g, m), beta that
-// makes d = -g + beta m B-orthogonal to m, the block of (d, m) by linearity, and the scaled 2x2 system with the guards of
-// mmmg_huber_loop; the move s0 d + s1 m = s0 (-g) + (s0 beta + s1) m is then one pass over the maps and one over the detector
+// makes d = -g + beta m B-orthogonal to m, the block of (d, m) by linearity, and the step (mm_step2); the move s0 d + s1 m = s0 (-g) + (s0 beta + s1) m is then one pass over the maps and one over the detector
 // vectors.  u is recomputed from x every `refresh` iterations.  One host synchronisation per iteration.
 namespace {
 int robust_args(double data_delta) {
@@ -2880,10 +2849,9 @@ int mmmg_robust_loop(surfh_plan *p, const HuberPrior &hp, const float *y, double
     std::vector<float> hx;
     HIP_OK(hipSetDevice(p->dev));
     if (p->ch.empty() || p->osize <= 0) return fail("3MG (%s, robust data term) needs a plan with detector channels", hp.what);
-    if (ensure_cg(p)) return 1;
-    if (!p->cg_hg && dev_alloc(&p->cg_hg, (size_t)p->isize)) return 1;
     for (float **v : {&p->rb_y, &p->rb_u, &p->rb_ag, &p->rb_am})
         if (!*v && dev_alloc(v, (size_t)p->osize)) return 1;
+    if (mmmg_begin(p, true, y, p->rb_y, x0, p->rb_am)) return 1;
     hipStream_t s = p->stream;
     const long n = p->isize, no = p->osize;
     const int F = hp.nfam;
@@ -2894,13 +2862,6 @@ int mmmg_robust_loop(surfh_plan *p, const HuberPrior &hp, const float *y, double
     // curv pass, [6+4F] m.(-g)
     double *sc = p->dscal;
     const int G = 2, CD = 3 + F, CP = 6 + F, MG = 6 + 4 * F;
-    HIP_OK(hipMemcpyAsync(yd, y, no * sizeof(float), hipMemcpyHostToDevice, s));
-    if (x0)
-        HIP_OK(hipMemcpyAsync(p->cg_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
-    else
-        LAUNCH_OK(launch_fill_zero(s, p->cg_x, n));
-    LAUNCH_OK(launch_fill_zero(s, m, n));
-    LAUNCH_OK(launch_fill_zero(s, am, no));
     if (forward_dev(p, p->cg_x, u)) return 1;
     double h[16], val[4] = {0.0, 0.0, 0.0, 0.0};
     *nit = 0;
@@ -2928,11 +2889,10 @@ int mmmg_robust_loop(surfh_plan *p, const HuberPrior &hp, const float *y, double
         val[0] = h[0];
         val[1] = h[1];
         for (int f = 0; f < F; ++f) val[2 + f] = h[G + 1 + f];
-        if (const int rc = it > 0 ? callback_iterate(p, callback, user, it, grad_norm, p->cg_x, hx) : CB_GO_ON) {
+        if (const int rc = mmmg_check(p, callback, user, it, max_iter, grad_norm, grad_norm[it], (double)n, tol, hx)) {
             if (rc == CB_STOP) break;
             return 1;
         }
-        if (last || grad_norm[it] < (double)n * tol) break;
         // the block of (-g, m) under B: the data family in detector space, the prior families on the maps
         double gBg = mu * h[CD], gBm = mu * h[CD + 1], mBm = mu * h[CD + 2];
         for (int f = 0; f < F; ++f) {
@@ -2941,23 +2901,17 @@ int mmmg_robust_loop(surfh_plan *p, const HuberPrior &hp, const float *y, double
             mBm += hp.reg[f] * h[CP + 3 * f + 2];
         }
         const double beta = mBm > 0.0 ? -gBm / mBm : 0.0;
-        const double dBd = gBg + beta * (2.0 * gBm + beta * mBm), dBm = gBm + beta * mBm;      // d = -g + beta m, by linearity
+        double dBd, dBm, s0, s1;
+        mm_block_of_d(gBg, gBm, mBm, beta, &dBd, &dBm);
         const double mg = h[MG], dg = h[G] + beta * mg;
         if (!(dBd > 0.0)) return fail("3MG (%s, robust data term): non-positive curvature d.Bd = %g at iteration %d", hp.what, dBd, it);
-        double s0 = dg / dBd, s1 = 0.0;
-        if (mBm > 0.0) {
-            const double sq = std::sqrt(dBd * mBm), cc = dBm / sq, det = 1.0 - cc * cc;      // scaled 2x2 system
-            if (det > 1e-12) {
-                s0 = (dg / dBd - cc * mg / sq) / det;
-                s1 = (mg / mBm - cc * dg / sq) / det;
-            }
-        }
+        mm_step2(dBd, dBm, mBm, dg, mg, &s0, &s1);
         {
             Prof pr(p, "robust_move");
             LAUNCH_OK(launch_robust_move(s, p->cg_x, ng, m, n, s0, s0 * beta + s1));
             LAUNCH_OK(launch_robust_move(s, u, ag, am, no, s0, s0 * beta + s1));
         }
-        if (refresh > 0 && it % refresh == 0 && forward_dev(p, p->cg_x, u)) return 1;
+        if (refresh_due(refresh, it) && forward_dev(p, p->cg_x, u)) return 1;
         *nit = it + 1;
     }
     if (values)
@@ -2966,9 +2920,7 @@ int mmmg_robust_loop(surfh_plan *p, const HuberPrior &hp, const float *y, double
         LAUNCH_OK(launch_robust_data(s, yd, u, w, v, ag, no, dd, p->dscratch, sc + 0));
         HIP_OK(hipMemcpyAsync(omega_out, ag, no * sizeof(float), hipMemcpyDeviceToHost, s));
     }
-    HIP_OK(hipMemcpyAsync(x, p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    return 0;
+    return mmmg_finish(p, x);
 }
 }  // namespace
 
@@ -2998,30 +2950,20 @@ int surfh_robust_data_dev(surfh_plan *p, const float *y_dev, const float *u_dev,
     if (!p || !y_dev || !u_dev || !v_dev || !sums_host) return fail("null argument");
     if (n < 1) return fail("surfh_robust_data_dev: n = %ld", (long)n);
     if (robust_args(data_delta)) return 1;
-    HIP_OK(hipSetDevice(p->dev));
-    {
-        Prof pr(p, "robust_data");
-        LAUNCH_OK(launch_robust_data(p->stream, y_dev, u_dev, w_dev, v_dev, nullptr, n, robust_delta_f32(data_delta), p->dscratch,
-                                     p->dscal + 0));
-    }
-    HIP_OK(hipMemcpyAsync(sums_host, p->dscal, 2 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-    HIP_OK(hipStreamSynchronize(p->stream));
-    return 0;
+    const auto pass = [&] {
+        return launch_robust_data(p->stream, y_dev, u_dev, w_dev, v_dev, nullptr, n, robust_delta_f32(data_delta), p->dscratch, p->dscal);
+    };
+    return diag_pass(p, "robust_data", pass, p->dscal, sums_host, 2);
 }
 int surfh_robust_curv_dev(surfh_plan *p, const float *y_dev, const float *u_dev, const float *w_dev, const float *p0_dev,
                           const float *p1_dev, int64_t n, double data_delta, double *sums_host) {
     if (!p || !y_dev || !u_dev || !p0_dev || !p1_dev || !sums_host) return fail("null argument");
     if (n < 1) return fail("surfh_robust_curv_dev: n = %ld", (long)n);
     if (robust_args(data_delta)) return 1;
-    HIP_OK(hipSetDevice(p->dev));
-    {
-        Prof pr(p, "robust_curv");
-        LAUNCH_OK(launch_robust_curv(p->stream, y_dev, u_dev, w_dev, p0_dev, p1_dev, n, robust_delta_f32(data_delta), p->dscratch,
-                                     p->dscal + 0));
-    }
-    HIP_OK(hipMemcpyAsync(sums_host, p->dscal, 3 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-    HIP_OK(hipStreamSynchronize(p->stream));
-    return 0;
+    const auto pass = [&] {
+        return launch_robust_curv(p->stream, y_dev, u_dev, w_dev, p0_dev, p1_dev, n, robust_delta_f32(data_delta), p->dscratch, p->dscal);
+    };
+    return diag_pass(p, "robust_curv", pass, p->dscal, sums_host, 3);
 }
 
 // ---- CG on independent planes: the 2-D deconvolution path (criterion_2D.py:60-250 per image, batched over wavelength)
@@ -3214,59 +3156,70 @@ int surfh_cg_planes_rr(surfh_plan *p, double *rr_host) {
     return 0;
 }
 
-// ---- 3MG on independent planes: what `method = "qmm"` of the 2-D deconvolution driver runs
-// (scripts/deconvolution_mrs_noRotation.py:199-212 -> criterion_2D.py:190-193 -> qmm.mmmg); see surfh_mmmg for the scheme.
-int surfh_mmmg_planes_cb(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
-                         int32_t refresh, float *x, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
-    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
-    if (p->T != 0) return fail("surfh_mmmg_planes is the solver of the plane-wise (no template) model; use surfh_mmmg with templates");
-    if (p->ch.empty()) return fail("plan has no channel");
-    HIP_OK(hipSetDevice(p->dev));
-    if (ensure_cg(p)) return 1;
-    if (!p->cg_qm && (dev_alloc(&p->cg_qm, (size_t)p->isize) || dev_alloc(&p->cg_dd, (size_t)p->isize))) return 1;
+// ---- 3MG on independent planes: every plane's beta, 2x2 system and step on the device, so the host reads one thing per
+// iteration, the Lc squared gradient norms `sq` that `dir` leaves.  dir() forms d = -g + beta m per plane from the carried
+// residual; the operator (mu A^T A, + op_reg prior) is applied to d for all planes together; step(update_r) solves and moves.
+// The iterate is left in cg_x: the caller ends with mmmg_finish.
+namespace {
+int mmmg_planes_loop(surfh_plan *p, bool want_hg, const float *y, double mu, double op_reg, const float *x0, int32_t max_iter, double tol,
+                     int32_t refresh, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user, const double *sq,
+                     const std::function<int()> &dir, const std::function<int(int)> &step) {
+    std::vector<float> hx;
+    if (mmmg_begin(p, want_hg, y, p->io_y, x0)) return 1;
     hipStream_t s = p->stream;
     const int L = p->Lc;
-    const long npix = (long)p->Na * p->Nb, n = p->isize;
-    float *r = p->cg_r, *m = p->cg_d, *d = p->cg_dd, *qd = p->cg_q, *qm = p->cg_qm;
-    if (!p->pl_sc && dev_alloc(&p->pl_sc, (size_t)3 * L)) return 1;
-    double *rr = p->pl_sc, *mqm = p->pl_sc + L;
-    std::vector<float> hx;
-    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
-    if (x0)
-        HIP_OK(hipMemcpyAsync(p->cg_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
-    else
-        LAUNCH_OK(launch_fill_zero(s, p->cg_x, n));
-    LAUNCH_OK(launch_fill_zero(s, m, n));
-    LAUNCH_OK(launch_fill_zero(s, qm, n));
-    if (solver_setup(p, p->io_y, p->cg_x, mu, mu_reg)) return 1;
+    const long npix = (long)p->Na * p->Nb;
+    if (solver_setup(p, p->io_y, p->cg_x, mu, op_reg)) return 1;
     *nit = 0;
     for (int it = 0;; ++it) {
-        LAUNCH_OK(launch_mmmg_dir_planes(s, d, r, m, qm, L, npix, rr, mqm));
+        if (dir()) return 1;
         double *gn = grad_norm + (size_t)it * L;
-        HIP_OK(hipMemcpyAsync(gn, rr, L * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(gn, sq, L * sizeof(double), hipMemcpyDeviceToHost, s));
         HIP_OK(hipStreamSynchronize(s));
         double worst = 0.0;
         for (int l = 0; l < L; ++l) {
             gn[l] = std::sqrt(gn[l]);
             worst = std::max(worst, gn[l]);
         }
-        if (const int rc = it > 0 ? callback_iterate(p, callback, user, it, grad_norm, p->cg_x, hx) : CB_GO_ON) {
+        if (const int rc = mmmg_check(p, callback, user, it, max_iter, grad_norm, worst, (double)npix, tol, hx)) {
             if (rc == CB_STOP) break;
             return 1;
         }
-        if (it >= max_iter || worst < (double)npix * tol) break;
-        if (normal_prior(p, d, qd, mu, mu_reg)) return 1;
-        const bool fresh = refresh > 0 && it % refresh == 0;
-        LAUNCH_OK(launch_mmmg_step_planes(s, p->cg_x, r, d, m, qm, qd, L, npix, mqm, fresh ? 0 : 1));
+        if (normal_prior(p, p->cg_dd, p->cg_q, mu, op_reg)) return 1;
+        const bool fresh = refresh_due(refresh, it);
+        if (step(fresh ? 0 : 1)) return 1;
         if (fresh) {
-            if (normal_prior(p, p->cg_x, qd, mu, mu_reg)) return 1;
-            LAUNCH_OK(launch_residual(s, r, p->cg_b, qd, n));
+            if (normal_prior(p, p->cg_x, p->cg_q, mu, op_reg)) return 1;
+            LAUNCH_OK(launch_residual(s, p->cg_r, p->cg_b, p->cg_q, p->isize));
         }
         *nit = it + 1;
     }
-    HIP_OK(hipMemcpyAsync(x, p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
     return 0;
+}
+}  // namespace
+
+// what `method = "qmm"` of the 2-D deconvolution driver runs (scripts/deconvolution_mrs_noRotation.py:199-212 ->
+// criterion_2D.py:190-193 -> qmm.mmmg): the quadratic prior rides in the operator, -g is the carried residual
+int surfh_mmmg_planes_cb(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
+                         int32_t refresh, float *x, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
+    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (p->T != 0) return fail("surfh_mmmg_planes is the solver of the plane-wise (no template) model; use surfh_mmmg with templates");
+    if (p->ch.empty()) return fail("plan has no channel");
+    HIP_OK(hipSetDevice(p->dev));
+    const int L = p->Lc;
+    const long npix = (long)p->Na * p->Nb;
+    if (!p->pl_sc && dev_alloc(&p->pl_sc, (size_t)3 * L)) return 1;
+    double *rr = p->pl_sc, *mqm = p->pl_sc + L;
+    const auto dir = [&] {
+        LAUNCH_OK(launch_mmmg_dir_planes(p->stream, p->cg_dd, p->cg_r, p->cg_d, p->cg_qm, L, npix, rr, mqm));
+        return 0;
+    };
+    const auto step = [&](int update_r) {
+        LAUNCH_OK(launch_mmmg_step_planes(p->stream, p->cg_x, p->cg_r, p->cg_dd, p->cg_d, p->cg_qm, p->cg_q, L, npix, mqm, update_r));
+        return 0;
+    };
+    if (mmmg_planes_loop(p, false, y, mu, mu_reg, x0, max_iter, tol, refresh, grad_norm, nit, callback, user, rr, dir, step)) return 1;
+    return mmmg_finish(p, x);
 }
 
 int surfh_mmmg_planes(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
@@ -3276,11 +3229,9 @@ int surfh_mmmg_planes(surfh_plan *p, const float *y, double mu, double mu_reg, c
 
 // ---- 3MG with Huber priors on independent planes: the criterion of surfh_mmmg_huber per plane,
 //   J_l(x_l) = mu |y_l - A_l x_l|^2 / 2 + mu_reg sum_k sum phi(D_k x_l),
-// minimised by the scheme of mmmg_huber_loop with every plane's beta, 2x2 system and step on the device (that loop reads one
-// beta and one system back per iteration; here there are Lc of each): huber_dir_planes gives -g_l, |g_l|^2, the prior value, the
-// prior block of (-g_l, m_l), beta_l and d_l = -g_l + beta_l m_l; the data part Q_D = mu A^T A is applied to d for all planes
-// together; huber_step_planes forms the block of (d_l, m_l) by linearity in float64, solves and moves.  b - Q_D x is carried by
-// linearity and recomputed every `refresh` iterations.  One host read per iteration: the Lc gradient norms.
+// minimised by mmmg_planes_loop: huber_dir_planes gives -g_l, |g_l|^2, the prior value, the prior block of (-g_l, m_l), beta_l
+// and d_l = -g_l + beta_l m_l; the operator is the data part Q_D = mu A^T A alone; huber_step_planes forms the block of
+// (d_l, m_l) by linearity in float64, solves and moves.
 namespace {
 int huber_planes_ready(surfh_plan *p, const char *who) {
     if (p->T != 0) return fail("%s works on the plane-wise (no template) model; the maps of a template model take surfh_mmmg_huber", who);
@@ -3311,14 +3262,8 @@ int surfh_huber_planes_curv_dev(surfh_plan *p, const float *x_dev, const float *
     if (!p || !x_dev || !p0_dev || !p1_dev || !sums_host) return fail("null argument");
     if (huber_args(0.0, delta) || huber_planes_ready(p, "surfh_huber_planes_curv_dev")) return 1;
     const int L = p->Lc;
-    {
-        Prof pr(p, "huber_planes_curv");
-        LAUNCH_OK(launch_huber_planes_curv(p->stream, x_dev, p0_dev, p1_dev, L, p->Na, p->Nb, (float)delta, p->pl_hsc));
-    }
-    HIP_OK(hipMemcpyAsync(sums_host, p->pl_hsc + (size_t)(HUBER_PLANES_SCALARS - 3) * L, 3 * L * sizeof(double), hipMemcpyDeviceToHost,
-                          p->stream));
-    HIP_OK(hipStreamSynchronize(p->stream));
-    return 0;
+    const auto pass = [&] { return launch_huber_planes_curv(p->stream, x_dev, p0_dev, p1_dev, L, p->Na, p->Nb, (float)delta, p->pl_hsc); };
+    return diag_pass(p, "huber_planes_curv", pass, p->pl_hsc + (size_t)(HUBER_PLANES_SCALARS - 3) * L, sums_host, (size_t)3 * L);
 }
 
 int surfh_mmmg_huber_planes(surfh_plan *p, const float *y, double mu, double mu_reg, double delta, const float *x0, int32_t max_iter,
@@ -3326,59 +3271,25 @@ int surfh_mmmg_huber_planes(surfh_plan *p, const float *y, double mu, double mu_
                             surfh_cg_callback callback, void *user) {
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
     if (huber_args(mu_reg, delta) || huber_planes_ready(p, "surfh_mmmg_huber_planes")) return 1;
-    if (ensure_cg(p)) return 1;
-    if (!p->cg_qm && (dev_alloc(&p->cg_qm, (size_t)p->isize) || dev_alloc(&p->cg_dd, (size_t)p->isize))) return 1;
-    if (!p->cg_hg && dev_alloc(&p->cg_hg, (size_t)p->isize)) return 1;
-    hipStream_t s = p->stream;
     const int L = p->Lc;
-    const long npix = (long)p->Na * p->Nb, n = p->isize;
-    float *r = p->cg_r, *m = p->cg_d, *d = p->cg_dd, *qd = p->cg_q, *qm = p->cg_qm, *ng = p->cg_hg;
+    const long npix = (long)p->Na * p->Nb;
     double *sc = p->pl_hsc;
-    std::vector<float> hx;
-    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
-    if (x0)
-        HIP_OK(hipMemcpyAsync(p->cg_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
-    else
-        LAUNCH_OK(launch_fill_zero(s, p->cg_x, n));
-    LAUNCH_OK(launch_fill_zero(s, m, n));
-    LAUNCH_OK(launch_fill_zero(s, qm, n));
-    if (solver_setup(p, p->io_y, p->cg_x, mu, 0.0)) return 1;          // r = b - mu A^T A x: the data part of -g
-    *nit = 0;
-    for (int it = 0;; ++it) {
-        {
-            Prof pr(p, "huber_dir_planes");
-            LAUNCH_OK(launch_huber_dir_planes(s, p->cg_x, r, ng, m, qm, d, L, p->Na, p->Nb, mu_reg, (float)delta, sc));
-        }
-        double *gn = grad_norm + (size_t)it * L;
-        HIP_OK(hipMemcpyAsync(gn, sc, L * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_OK(hipStreamSynchronize(s));
-        double worst = 0.0;
-        for (int l = 0; l < L; ++l) {
-            gn[l] = std::sqrt(gn[l]);
-            worst = std::max(worst, gn[l]);
-        }
-        if (const int rc = it > 0 ? callback_iterate(p, callback, user, it, grad_norm, p->cg_x, hx) : CB_GO_ON) {
-            if (rc == CB_STOP) break;
-            return 1;
-        }
-        if (it >= max_iter || worst < (double)npix * tol) break;
-        if (normal_dev(p, d, qd, mu)) return 1;
-        const bool fresh = refresh > 0 && it % refresh == 0;
-        {
-            Prof pr(p, "huber_step_planes");
-            LAUNCH_OK(launch_huber_step_planes(s, p->cg_x, r, d, m, qm, qd, ng, L, npix, mu_reg, sc, fresh ? 0 : 1));
-        }
-        if (fresh) {
-            if (normal_dev(p, p->cg_x, qd, mu)) return 1;
-            LAUNCH_OK(launch_residual(s, r, p->cg_b, qd, n));
-        }
-        *nit = it + 1;
-    }
+    const auto dir = [&] {
+        Prof pr(p, "huber_dir_planes");
+        LAUNCH_OK(launch_huber_dir_planes(p->stream, p->cg_x, p->cg_r, p->cg_hg, p->cg_d, p->cg_qm, p->cg_dd, L, p->Na, p->Nb, mu_reg,
+                                          (float)delta, sc));
+        return 0;
+    };
+    const auto step = [&](int update_r) {
+        Prof pr(p, "huber_step_planes");
+        LAUNCH_OK(launch_huber_step_planes(p->stream, p->cg_x, p->cg_r, p->cg_dd, p->cg_d, p->cg_qm, p->cg_q, p->cg_hg, L, npix, mu_reg,
+                                           sc, update_r));
+        return 0;
+    };
+    if (mmmg_planes_loop(p, true, y, mu, 0.0, x0, max_iter, tol, refresh, grad_norm, nit, callback, user, sc, dir, step)) return 1;
     // the last launch of the dir kernel ran on the returned iterate: its prior values are the result's
-    if (prior_values) HIP_OK(hipMemcpyAsync(prior_values, sc + L, L * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(x, p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    return 0;
+    if (prior_values) HIP_OK(hipMemcpyAsync(prior_values, sc + L, L * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    return mmmg_finish(p, x);
 }
 
 // ---- drivers' LMM helpers on the device (spectroModel.py:187-198) -----------------------------
@@ -3526,6 +3437,12 @@ int32_t surfh_klist_classify(const float *B, int32_t n, int32_t k, int64_t ldb, 
     if ((int64_t)kl.size() > capacity) return -fail("surfh_klist_classify: capacity too small");
     std::memcpy(records, kl.data(), kl.size() * sizeof(int));
     return (int32_t)(kl.size() / (size_t)stride);
+}
+
+int surfh_mm_step2(double dBd, double dBm, double mBm, double dg, double mg, double step[2]) {
+    if (!step) return fail("null argument");
+    mm_step2(dBd, dBm, mBm, dg, mg, &step[0], &step[1]);
+    return 0;
 }
 
 static long g_selftest_ksteps[2] = {0, 0};
