@@ -333,6 +333,26 @@ int surfh_prior_spec_add_dev(surfh_plan *plan, const float *dt_dev, float *qt_de
  * 0 = "separated": Dr^T Dr + Dc^T Dc, circular first differences NpDiff_r / NpDiff_c (fusion_CT.py:16-43) -- the default;
  * 1 = "joint": D^T D with D the circular convolution by the 3 x 3 Laplacian (Difference_Operator_Joint, fusion_CT.py:45-62).  */
 int surfh_set_prior(surfh_plan *plan, int32_t kind);
+/* ---- potentials: plan state, like the prior and the data weights ----
+ * Which potential phi the non-quadratic terms of the 3MG solvers use.  Everything said of "Huber" at surfh_mmmg_huber(_vox,
+ * _planes), surfh_mmmg_robust(_vox) and their *_dev passes holds for the other kinds with their phi, phi' and w = phi' / u; all
+ * are normalised alike (phi(u) ~ u^2 / 2 near 0, w(0) = 1, delta = +inf exactly the quadratic term).  With t = u / delta:
+ *   kind 0  huber         phi = u^2 / 2 (|u| <= delta), delta (|u| - delta / 2) beyond    w = 1 or delta / |u|       (the default)
+ *   kind 1  hyperbolic    phi = delta^2 (sqrt(1 + t^2) - 1)                                w = 1 / sqrt(1 + t^2)
+ *   kind 2  hebert_leahy  phi = delta^2 log(1 + t^2) / 2                                   w = 1 / (1 + t^2)
+ * hyperbolic (Charbonnier, pseudo-Huber) is convex with a smooth w; Hebert-Leahy is non-convex, phi' redescends (as a data term
+ * the Cauchy / Student-t likelihood): the majorant still holds and every iteration descends, but the limit is a local minimum
+ * that depends on the start.  phi' is formed as u w; no NaN or Inf for any finite u and any delta >= FLT_MIN (|t| >= 2^24: the
+ * hyperbolic w is delta / |u|; the Hebert-Leahy w flushes to 0 once t^2 overflows fp32).
+ *   slot 0  the spatial prior: the maps (surfh_mmmg_huber, surfh_mmmg_robust, surfh_huber_prior_dev / _curv_dev), the planes
+ *           (surfh_mmmg_huber_planes, surfh_huber_planes_prior_dev / _curv_dev) and the cube's row / column families
+ *   slot 1  the cube's spectral prior (surfh_mmmg_huber_vox, surfh_mmmg_robust_vox, surfh_huber_vox_prior_dev / _curv_dev)
+ *   slot 2  the data term (surfh_mmmg_robust(_vox), surfh_robust_data_dev / _curv_dev); the count "number of |t| > data_delta"
+ *           keeps its meaning for every kind: the samples past the knee
+ * A new plan holds huber in all three.  The quadratic surfh_mmmg and the CG solvers ignore the slots.  set fails on an unknown
+ * slot or kind (message in surfh_last_error) and leaves the plan as it was; get returns the kind, or -1 on an unknown slot. */
+int surfh_set_potential(surfh_plan *plan, int32_t slot, int32_t kind);
+int surfh_get_potential(const surfh_plan *plan, int32_t slot);
 /* ---- data weights: plan state, like the prior ----
  * With weights w [osize] (the layout of y; every w[i] finite and >= 0) the data term of every solver is
  *   mu (y - A x)^T W (y - A x) / 2,  W = diag(w):

@@ -23,7 +23,8 @@ exact transpose of that operator.  ``--data_to_img`` also writes the quick-look 
 
 ``--delta D`` (not in the reference, whose criterion_2D.py imports qmm's ``Huber`` without building it): edge-preserving Huber
 priors of threshold D on the row and column differences, minimised by 3MG (``-m`` anything but ``lcg``); the results then go to
-``<--out>_huber_<D>``.
+``<--out>_huber_<D>``.  ``--potential`` (with ``--delta``) replaces Huber's potential by ``hyperbolic`` or ``hebert_leahy``
+(surfh_amd/potentials.py); the results then go to ``<--out>_<kind>_<D>``.
 """
 from __future__ import annotations
 
@@ -75,6 +76,11 @@ def build_problem(npix: int, planes: int, seed: int, inp: str | None, angle: flo
                 pointings=instru.CoordList([instru.Coord(a, b) for a, b in pts]), truth=truth)
 
 
+def result_dir(out, delta, potential="huber"):
+    """<out>_huber_<delta> as before; another potential puts its name in Huber's place"""
+    return f"{out}_{potential}_{delta:g}"
+
+
 @click.command()
 @click.option("-np", "--npix", default=251, type=int, help="image size (the reference's maps are 251 x 251)")
 @click.option("-hp", "--hyper_parameter", default=5.0, type=float, help="mu_reg (reference: 5)")
@@ -92,11 +98,16 @@ def build_problem(npix: int, planes: int, seed: int, inp: str | None, angle: flo
 @click.option("--data_to_img", is_flag=True, help="also write data_to_img of the data and of the result's forward")
 @click.option("--delta", default=None, type=float,
               help="Huber threshold of the priors (needs -m other than lcg); results go to <out>_huber_<delta>")
-def main(npix, hyper_parameter, niter, method, value_init, planes, inp, out, quiet, seed, device, angle, data_to_img, delta):
+@click.option("--potential", default="huber", type=click.Choice(["huber", "hyperbolic", "hebert_leahy"]),
+              help="potential of the priors under --delta; other than huber: results go to <out>_<potential>_<delta>")
+def main(npix, hyper_parameter, niter, method, value_init, planes, inp, out, quiet, seed, device, angle, data_to_img, delta,
+         potential="huber"):
+    if potential != "huber" and delta is None:
+        raise click.UsageError("--potential needs --delta: a potential of the quadratic prior means nothing")
     if delta is not None:
         if method == "lcg":
             raise ValueError("lcg minimises quadratic criteria only: a Huber prior (delta) needs method='mmmg'")
-        out = f"{out}_huber_{delta:g}"
+        out = result_dir(out, delta, potential)
     if angle:
         from surfh_amd.spectro_blind import MRSBlurred, QuadCriterion_MRS_2D
     else:
@@ -108,7 +119,7 @@ def main(npix, hyper_parameter, niter, method, value_init, planes, inp, out, qui
                        device=device)
     simulated_data = model.forward(prob["truth"])
     crit = QuadCriterion_MRS_2D(mu_spectro=1, y_spectro=np.copy(simulated_data), model_spectro=model, mu_reg=hyper_parameter,
-                                printing=True, gradient="separated", delta=delta)
+                                printing=True, gradient="separated", delta=delta, potential=potential)
     t0 = time.time()
     if quiet:
         res = crit.run_method(method, niter, value_init=value_init)

@@ -6,6 +6,7 @@
     python scripts/main_fusion.py --synthetic small --voxel -m mmmg -hp 40 --delta 0.005 --spec_reg 20 --spec_delta 0.01
     python scripts/main_fusion.py -fd <fusion_dir> -hp 5e3 -ni 50 --mask_nan --weights inv_variance.npy
     python scripts/main_fusion.py -fd <fusion_dir> -hp 5e3 -ni 50 -m mmmg --weights inv_variance.npy --data_delta 3
+    python scripts/main_fusion.py --synthetic small -m mmmg -hp 5e3 --delta 0.1 --potential hebert_leahy
 
 Inputs under ``fusion_dir`` (reference layout, main_fusion.py:65-75): ``Templates/`` (wavelength axis + NMF templates,
 .npy), ``PSF/`` (PSF stack, .npy), ``Filtered_slices/`` (one FITS file per band and pointing) -> results in
@@ -24,6 +25,11 @@ scaled by the square root of their weights, so that with inverse-variance weight
 (cosmic-ray hits, warm pixels) then pull linearly instead of quadratically.  The result directory's name gains ``_rob_<D>`` and its
 files ``robust_weights.npy``, the weights ``[osize]`` in (0, 1] the last iterate gave every sample (0 where masked).
 
+``--potential`` / ``--data_potential`` (``--method mmmg`` only) and ``--spec_potential`` (``--voxel``) choose the potential under
+``--delta``, ``--data_delta`` and ``--spec_delta``: ``huber`` (the default), ``hyperbolic`` or ``hebert_leahy``
+(surfh_amd/potentials.py).  With another potential than Huber the directory's ``_huber_<D>`` becomes ``_<kind>_<D>``, its
+``_rob_<D>`` ``_rob_<kind>_<D>``, and a voxel-wise run under another spectral potential gains ``_spec_<kind>``.
+
 The FITS reader needs astropy (FITS I/O is outside the hot path and not rebuilt here); when it is not importable the
 same arrays may be given as ``Filtered_slices/<band>_<k>.npz`` with fields ``data`` (raveled ``[Ldet, S, a_out]`` as in
 the FITS primary HDU), ``PA_V3``, ``TARG_RA``, ``TARG_DEC``.  ``--synthetic`` builds one of the benchmark problems
@@ -41,6 +47,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from surfh_amd import instru, synth                                   # noqa: E402
 from surfh_amd.fusion import QuadCriterion_MRS, weights_from_data     # noqa: E402
 from surfh_amd.weights import check_data_weights                      # noqa: E402
+from surfh_amd.potentials import NAMES as POTENTIALS                  # noqa: E402
 from surfh_amd.models import spectroSigRLSCT                          # noqa: E402
 
 LIST_CHAN = ['1a', '1b', '1c', '2a', '2b', '2c', '3a', '3b', '3c', '4a', '4b', '4c']
@@ -129,18 +136,22 @@ def create_model(sotf, templates, origin_alpha_axis, origin_beta_axis, wavel_axi
 
 
 def result_dir_name(method, n_channels, n_templates, niter, hyper_parameter, scale_data, delta=None, voxel=False, weighted=False,
-                    data_delta=None):
+                    data_delta=None, potential='huber', data_potential='huber', spec_potential='huber'):
     """main_fusion.py:182; with a Huber threshold `delta` (not in the reference) `_huber_<delta>` is appended, `_vox` for a
-    voxel-wise reconstruction, `_wgt` for a run under data weights, and `_rob_<data_delta>` for a robust data term."""
+    voxel-wise reconstruction, `_wgt` for a run under data weights, and `_rob_<data_delta>` for a robust data term.  Another
+    potential than Huber puts its name in Huber's place (`_<kind>_<delta>`, `_rob_<kind>_<data_delta>`; `_spec_<kind>` for the
+    spectral prior of a voxel-wise run); with Huber the names are unchanged."""
     name = f'{method}_MC_{n_channels}_MO_4_Temp_{n_templates}_nit_{str(niter)}_mu_{str("{:.2e}".format(hyper_parameter))}_SD_{scale_data}'
     if delta is not None:
-        name += f'_huber_{delta:.2e}'
+        name += f'_{potential}_{delta:.2e}'
     if voxel:
         name += '_vox'
+        if spec_potential != 'huber':
+            name += f'_spec_{spec_potential}'
     if weighted:
         name += '_wgt'
     if data_delta is not None:
-        name += f'_rob_{data_delta:g}'
+        name += f'_rob_{data_delta:g}' if data_potential == 'huber' else f'_rob_{data_potential}_{data_delta:g}'
     return name + '/'
 
 
@@ -158,25 +169,29 @@ def data_weights(ndata, weights_file=None, mask_nan=False):
 
 
 def voxel_reconstruction(spectro_model, ndata, result_path, spat_reg, spat_th, spec_reg, spec_th, niter, method, scale_data,
-                         weights=None, data_delta=None):
+                         weights=None, data_delta=None, potential='huber', data_potential='huber', spec_potential='huber'):
     """The cube itself by vox_reconstruction (surfh_amd/algorithms.py): res_cube.npy [Lc, N, N], and in criterion.npy the
     criterion at the start and after iterations 1, 6, 11, ... -- the trace `reconstruction_method` writes (perf_crit = 1)."""
     from surfh_amd.algorithms import vox_criterion, vox_reconstruction
     path = pathlib.Path(result_path) / result_dir_name(method, len(spectro_model.instrs), 0, niter, spat_reg, scale_data, spat_th,
-                                                       voxel=True, weighted=weights is not None, data_delta=data_delta)
+                                                       voxel=True, weighted=weights is not None, data_delta=data_delta,
+                                                       potential=potential, data_potential=data_potential,
+                                                       spec_potential=spec_potential)
+    pots = dict(spat_potential=potential, spec_potential=spec_potential, data_potential=data_potential)
     path.mkdir(parents=True, exist_ok=True)
     init = spectro_model.adjoint(ndata if weights is None else np.where(weights > 0, weights * np.where(weights > 0, ndata, 0.), 0.))
-    crit = [vox_criterion(ndata, spectro_model, init, spat_reg, spat_th, spec_reg, spec_th, weights=weights, data_th=data_delta)]
+    crit = [vox_criterion(ndata, spectro_model, init, spat_reg, spat_th, spec_reg, spec_th, weights=weights, data_th=data_delta,
+                          **pots)]
 
     def trace(it, grad_norm, x):
         if it % 5 == 1:
             crit.append(vox_criterion(ndata, spectro_model, x, spat_reg, spat_th, spec_reg, spec_th, weights=weights,
-                                      data_th=data_delta))
+                                      data_th=data_delta, **pots))
             print(f"iteration {it}: criterion {crit[-1]:.6e}, |grad| {grad_norm[-1]:.3e}")
         return False
 
     res = vox_reconstruction(ndata, spectro_model, spat_reg=spat_reg, spat_th=spat_th, spec_reg=spec_reg, spec_th=spec_th, init=init,
-                             max_iter=niter, callback=trace, weights=weights, data_th=data_delta)
+                             max_iter=niter, callback=trace, weights=weights, data_th=data_delta, **pots)
     print(f"voxel-wise 3MG: {res.nit} iterations, criterion {crit[0]:.6e} -> {crit[-1]:.6e}")
     print(f"Results save in {path}")
     np.save(path / 'res_cube.npy', res.x.reshape(spectro_model.ishape))
@@ -189,21 +204,22 @@ def voxel_reconstruction(spectro_model, ndata, result_path, spat_reg, spat_th, s
 
 
 def reconstruction_method(spectro_model, ndata, templates, result_path, hyper_parameter, niter, method, scale_data,
-                          checkpoint_every=0, resume=None, delta=None, weights=None, data_delta=None):
+                          checkpoint_every=0, resume=None, delta=None, weights=None, data_delta=None, potential='huber',
+                          data_potential='huber'):
     """main_fusion.py:162-206: regularised least squares by CG, then the three result files.  Not in the reference:
     `checkpoint_every` > 0 writes the iterate to checkpoint.npz in the result directory every that many iterations,
     `resume` (such a file) warm-starts from it and runs the iterations that are left; `delta` replaces the quadratic
     priors by Huber potentials of that threshold (3MG only); `weights` `[osize]` weigh the samples of the data term and are
     stored beside the results as weights.npy; `data_delta` makes the data term robust (3MG only) and stores the last iterate's
-    robustness weights as robust_weights.npy."""
+    robustness weights as robust_weights.npy; `potential` / `data_potential` name the potential under `delta` / `data_delta`."""
     value_init = 0
     path = pathlib.Path(result_path) / result_dir_name(method, len(spectro_model.instrs), templates.shape[0], niter,
                                                        hyper_parameter, scale_data, delta, weighted=weights is not None,
-                                                       data_delta=data_delta)
+                                                       data_delta=data_delta, potential=potential, data_potential=data_potential)
     path.mkdir(parents=True, exist_ok=True)
     crit = QuadCriterion_MRS(mu_spectro=1, y_spectro=np.copy(ndata), model_spectro=spectro_model,
                              mu_reg=hyper_parameter, printing=True, gradient="separated", delta=delta, weights=weights,
-                             data_delta=data_delta)
+                             data_delta=data_delta, potential=potential, data_potential=data_potential)
     if resume:
         from surfh_amd.fusion import load_checkpoint
         x_saved, it_done, _ = load_checkpoint(resume)
@@ -263,8 +279,23 @@ def synthetic_problem(name, npix):
 @click.option('--data_delta', default=None, type=float,
               help='Huber threshold of a robust data term, in units of the weighted residual (sigmas under inverse-variance '
                    'weights); needs --method mmmg. Default: quadratic data term.')
+@click.option('--potential', default='huber', type=click.Choice(POTENTIALS),
+              help='Potential of the spatial priors under --delta (needs --method mmmg and --delta).')
+@click.option('--data_potential', default='huber', type=click.Choice(POTENTIALS),
+              help='Potential of the robust data term under --data_delta (needs --method mmmg and --data_delta).')
+@click.option('--spec_potential', default='huber', type=click.Choice(POTENTIALS),
+              help='Potential of the spectral prior under --spec_delta (--voxel).')
 def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, method, verbose, synthetic, device, checkpoint_every=0,
-         resume=None, delta=None, voxel=False, spec_reg=1., spec_delta=1., weights_file=None, mask_nan=False, data_delta=None):
+         resume=None, delta=None, voxel=False, spec_reg=1., spec_delta=1., weights_file=None, mask_nan=False, data_delta=None,
+         potential='huber', data_potential='huber', spec_potential='huber'):
+    if (potential != 'huber' or data_potential != 'huber') and method != 'mmmg':
+        raise click.UsageError('--potential and --data_potential choose a non-quadratic term; use them with --method mmmg')
+    if potential != 'huber' and delta is None and not voxel:
+        raise click.UsageError('--potential needs --delta: a potential of the quadratic prior means nothing')
+    if data_potential != 'huber' and data_delta is None:
+        raise click.UsageError('--data_potential needs --data_delta: a potential of the quadratic data term means nothing')
+    if spec_potential != 'huber' and not voxel:
+        raise click.UsageError('--spec_potential is the potential of the spectral prior of a voxel-wise run; use it with --voxel')
     if data_delta is not None and method != 'mmmg':
         raise click.UsageError('--data_delta (robust data term) is not quadratic; use it with --method mmmg')
     if data_delta is not None and not data_delta > 0:
@@ -323,11 +354,13 @@ def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, meth
     log.info(f'Start {method} algorithm')
     if voxel:
         voxel_reconstruction(model, ndata, paths["result_path"], hyper_parameter, 1. if delta is None else delta, spec_reg, spec_delta,
-                             niter, method, scale_data, weights=weights, data_delta=data_delta)
+                             niter, method, scale_data, weights=weights, data_delta=data_delta, potential=potential,
+                             data_potential=data_potential, spec_potential=spec_potential)
         model.close()
         return
     reconstruction_method(model, ndata, templates, paths["result_path"], hyper_parameter, niter, method, scale_data,
-                          checkpoint_every=checkpoint_every, resume=resume, delta=delta, weights=weights, data_delta=data_delta)
+                          checkpoint_every=checkpoint_every, resume=resume, delta=delta, weights=weights, data_delta=data_delta,
+                          potential=potential, data_potential=data_potential)
     model.close()
 
 

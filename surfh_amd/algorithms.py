@@ -28,12 +28,14 @@ import time
 
 import numpy as np
 
+from . import potentials as _pot
 from .fusion import OptimizeResult, robust_data_value
 from .weights import weighted_sq_residual
 
 
 def lmm_reconstruction(data, data_model, spat_reg: float = 1.0, spat_th: float = 1.0, init=None, max_iter: int = 500,
-                       tol: float = 1e-4, callback=None, weights=None, data_th=None) -> OptimizeResult:
+                       tol: float = 1e-4, callback=None, weights=None, data_th=None, spat_potential="huber",
+                       data_potential="huber") -> OptimizeResult:
     """Edge-preserving reconstruction of the abundance maps (algorithms.py:73-106).
 
     ``data_model`` is a template model (``spectroSigRLSCT``); ``init=None`` starts from ``data_model.adjoint(data)``, the exact
@@ -44,45 +46,55 @@ def lmm_reconstruction(data, data_model, spat_reg: float = 1.0, spat_th: float =
     (``spectroSigRLSCT.set_data_weights``); the default start is then ``A^T (w y)``, masked data left out.
     ``data_th`` (not in the reference): Huber threshold of a robust data term, sum_i phi(sqrt(w_i) (y_i - (A x)_i)) instead of the
     quadratic one (``spectroSigRLSCT.mmmg(data_delta=...)``); ``None``: quadratic.
+    ``spat_potential`` / ``data_potential`` (the reference builds qmm.Huber; qmm takes any potential): "huber", "hyperbolic" or
+    "hebert_leahy" (``surfh_amd.potentials``) under ``spat_th`` and ``data_th``; a data potential other than Huber needs ``data_th``.
     Returns the ``OptimizeResult`` of ``fusion.py`` (x raveled, |grad| of every iterate)."""
     if init is None:
         init = _weighted_start(data, data_model, weights)
     t0 = time.time()
     x, gn, nit = data_model.mmmg(data, mu=1.0, mu_reg=float(spat_reg), x0=init, max_iter=int(max_iter), tol=float(tol),
-                                 callback=callback, delta=float(spat_th), weights=weights, **_robust_kw(data_th))
+                                 callback=callback, delta=float(spat_th), weights=weights, potential=spat_potential,
+                                 data_potential=data_potential, **_robust_kw(data_th))
     return OptimizeResult(x=x.ravel(), grad_norm=list(gn), nit=nit, success=bool(gn[-1] < x.size * tol), time=time.time() - t0)
 
 
 def vox_reconstruction(data, data_model, spat_reg: float = 1.0, spat_th: float = 1.0, spec_reg: float = 1.0, spec_th: float = 1.0,
-                       init=None, max_iter: int = 500, tol: float = 1e-4, callback=None, weights=None, data_th=None) -> OptimizeResult:
+                       init=None, max_iter: int = 500, tol: float = 1e-4, callback=None, weights=None, data_th=None,
+                       spat_potential="huber", spec_potential="huber", data_potential="huber") -> OptimizeResult:
     """Edge-preserving reconstruction of the hyperspectral cube (algorithms.py:27-71).
 
     ``data_model`` is a model without templates (``spectroSigRLSCT(sotf, None, ...)``); ``init=None`` starts from
     ``data_model.adjoint(data)`` (qmm's ``ht_data``).  ``max_iter``, ``tol``, ``callback``, ``weights``, ``data_th`` and the result as
-    ``lmm_reconstruction``; x is the raveled cube ``[Lc, Na, Nb]``."""
+    ``lmm_reconstruction``; x is the raveled cube ``[Lc, Na, Nb]``.  ``spat_potential`` / ``spec_potential`` / ``data_potential``:
+    the potentials under ``spat_th``, ``spec_th`` and ``data_th``, as ``lmm_reconstruction``'s."""
     if init is None:
         init = _weighted_start(data, data_model, weights)
     t0 = time.time()
     x, gn, nit = data_model.mmmg_vox(data, mu=1.0, spat_reg=float(spat_reg), spat_delta=float(spat_th), spec_reg=float(spec_reg),
                                      spec_delta=float(spec_th), x0=init, max_iter=int(max_iter), tol=float(tol), callback=callback,
-                                     weights=weights, **_robust_kw(data_th))
+                                     weights=weights, spat_potential=spat_potential, spec_potential=spec_potential,
+                                     data_potential=data_potential, **_robust_kw(data_th))
     return OptimizeResult(x=x.ravel(), grad_norm=list(gn), nit=nit, success=bool(gn[-1] < x.size * tol), time=time.time() - t0)
 
 
 def vox_criterion(data, data_model, x, spat_reg: float = 1.0, spat_th: float = 1.0, spec_reg: float = 1.0, spec_th: float = 1.0,
-                  mu: float = 1.0, weights=None, data_th=None) -> float:
+                  mu: float = 1.0, weights=None, data_th=None, spat_potential="huber", spec_potential="huber",
+                  data_potential="huber") -> float:
     """J(x) of ``vox_reconstruction`` at the cube ``x`` (``mu`` weighs the data term, 1 in the reference): the forward model and
     the two prior sums run on the device (``huber_vox_prior_dev``), the data term is summed in float64 on the host -- under
-    ``weights`` as sum w (y - A x)^2 over the samples with w > 0, with ``data_th`` as the robust term mu sum phi(sqrt(w) (y - A x))."""
+    ``weights`` as sum w (y - A x)^2 over the samples with w > 0, with ``data_th`` as the robust term mu sum phi(sqrt(w) (y - A x)).
+    The potentials as ``vox_reconstruction``'s."""
+    _pot.need_delta(data_potential, data_th, "data_th")
     import torch
     x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(data_model.ishape))
     dev = f"cuda:{data_model.device}"
     x_t = torch.as_tensor(x, device=dev)
     g_t = torch.zeros_like(x_t)
     torch.cuda.synchronize(dev)
-    v_spat, v_spec = data_model.huber_vox_prior_dev(x_t, g_t, 0.0, spat_th, 0.0, spec_th)
+    with _pot.installed(data_model, spatial=spat_potential, spectral=spec_potential):
+        v_spat, v_spec = data_model.huber_vox_prior_dev(x_t, g_t, 0.0, spat_th, 0.0, spec_th)
     if data_th is not None:
-        data_term = mu * robust_data_value(data, data_model.forward(x), weights, float(data_th))
+        data_term = mu * robust_data_value(data, data_model.forward(x), weights, float(data_th), data_potential)
     else:
         data_term = mu * weighted_sq_residual(data, data_model.forward(x), weights) / 2
     return float(data_term + spat_reg * v_spat + spec_reg * v_spec)

@@ -21,10 +21,11 @@ import numpy as np
 
 from . import _lib, instru
 from .linop import LinOp
+from . import potentials as _pot
 from .weights import DataWeights
 
 
-class Blurred2D(DataWeights, LinOp):
+class Blurred2D(DataWeights, _pot.Potentials, LinOp):
     def __init__(self, sotf, alpha_axis, beta_axis, instr: instru.IFU, step_degree: float, pointings: instru.CoordList):
         self.sotf = sotf
         self.alpha_axis = np.asarray(alpha_axis, dtype=np.float64)
@@ -250,16 +251,20 @@ class Blurred2D(DataWeights, LinOp):
 
     last_prior_values = None            # per-plane prior values of the last mmmg(delta=...) result (None after a quadratic run)
 
-    def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, delta=None, weights=None):
+    def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, delta=None, weights=None,
+             potential="huber"):
         """Device-resident 3MG on the same criterion (`qmm.mmmg` restated for quadratic objectives) -- what the 2-D
         deconvolution driver's ``method = "qmm"`` runs (scripts/deconvolution_mrs_noRotation.py:199-212).  Same returns as
         ``cg`` except that ``grad_norm`` holds |grad| (not squared).  ``weights`` as in ``cg``.
         ``delta`` (a number): the priors are Huber potentials of threshold ``delta`` on the separated circular differences
         (criterion_2D.py imports qmm's ``Huber`` for this), every plane minimising its own
         mu |y - A x|^2 / 2 + mu_reg sum_k sum phi(D_k x)  (include/surfh_amd.h: surfh_mmmg_huber_planes); same returns, and the
-        prior values sum_k sum phi(D_k x_l) of the returned iterate are left in ``self.last_prior_values`` ([n_planes])."""
+        prior values sum_k sum phi(D_k x_l) of the returned iterate are left in ``self.last_prior_values`` ([n_planes]).
+        ``potential``: the potential under ``delta`` for this call, "huber" (the default), "hyperbolic" or "hebert_leahy"
+        (``surfh_amd.potentials``); ``ValueError`` for another one than Huber without ``delta``."""
         self.last_prior_values = None
-        with self.installed_weights(weights):
+        _pot.need_delta(potential, delta, "delta")
+        with _pot.installed(self, spatial=potential), self.installed_weights(weights):
             if delta is None:
                 return _lib.solve(self, self._L.surfh_mmmg_planes_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback,
                                   planes=self.n_planes, squeeze=not self.batched)

@@ -25,6 +25,7 @@ constexpr int VOX_BLOCKS = 2048;      // 8 blocks per CU; [6][2048] partials fit
 // curv: part [6][blocks]: sum w (D p0)^2, (D p0)(D p1), (D p1)^2 over the two in-plane families with w = w_ds(D_k x), then the
 // same three over the wavelength differences with w = w_dl(Dl x) (weights recomputed, none stored).
 // Grid (pixel tiles, wavelength chunks); chunk c owns planes [Lc c / C, Lc (c + 1) / C)
+// KS, KL: the potential of the in-plane families and of the wavelength family (huber_dev.h), all 3 x 3 pairs instantiated
 struct PixNbrs {
     int up, dn, lf, rt;                // offsets inside a plane of the four circular neighbours
     __device__ PixNbrs(int p, int na, int nb) {
@@ -36,6 +37,7 @@ struct PixNbrs {
     }
 };
 
+template <int KS, int KL>
 __global__ __launch_bounds__(TPB) void huber_vox_grad_kernel(const float *__restrict__ x, const float *src, float *out, int Lc,
                                                                    int na, int nb, float cs, float ds, float cl, float dl,
                                                                    double *__restrict__ part) {
@@ -46,22 +48,22 @@ __global__ __launch_bounds__(TPB) void huber_vox_grad_kernel(const float *__rest
         const PixNbrs q(p, na, nb);
         const float *pl = x + (long)l0 * npix;
         float c = pl[p];
-        float vprev = l0 > 0 ? huber_dphi(c - pl[p - (long)npix], dl) : 0.f;      // phi'(Dl x) at l0 - 1: the halo plane
+        float vprev = l0 > 0 ? pot_dphi<KL>(c - pl[p - (long)npix], dl) : 0.f;      // phi'(Dl x) at l0 - 1: the halo plane
         for (int l = l0; l < l1; ++l, pl += npix) {
             float nxt = 0.f, vown = 0.f;
             if (l < Lc - 1) {
                 nxt = pl[p + (long)npix];
                 const float ul = nxt - c;
-                vown = huber_dphi(ul, dl);
-                acc[2] += huber_phi(ul, dl);
+                vown = pot_dphi<KL>(ul, dl);
+                acc[2] += pot_phi<KL>(ul, dl);
             }
             const float ur = pl[q.up] - c, uc = pl[q.lf] - c, urn = c - pl[q.dn], ucn = c - pl[q.rt];
-            const float pgs = (huber_dphi(urn, ds) - huber_dphi(ur, ds)) + (huber_dphi(ucn, ds) - huber_dphi(uc, ds));
+            const float pgs = (pot_dphi<KS>(urn, ds) - pot_dphi<KS>(ur, ds)) + (pot_dphi<KS>(ucn, ds) - pot_dphi<KS>(uc, ds));
             const long e = (long)l * npix + p;
             const float g = src[e] + cs * pgs + cl * (vprev - vown);
             out[e] = g;
             acc[0] += (double)g * (double)g;
-            acc[1] += huber_phi(ur, ds) + huber_phi(uc, ds);
+            acc[1] += pot_phi<KS>(ur, ds) + pot_phi<KS>(uc, ds);
             vprev = vown;
             c = nxt;
         }
@@ -69,6 +71,7 @@ __global__ __launch_bounds__(TPB) void huber_vox_grad_kernel(const float *__rest
     block_sums_to<3>(acc, part, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
 }
 
+template <int KS, int KL>
 __global__ __launch_bounds__(TPB) void huber_vox_curv_kernel(const float *__restrict__ x, const float *__restrict__ p0,
                                                                    const float *__restrict__ p1, int Lc, int na, int nb, float ds,
                                                                    float dl, double *__restrict__ part) {
@@ -81,7 +84,7 @@ __global__ __launch_bounds__(TPB) void huber_vox_curv_kernel(const float *__rest
         const float *px = x + off, *pa = p0 + off, *pb = p1 + off;
         float c = px[p], ac = pa[p], bc = pb[p];
         for (int l = l0; l < l1; ++l, px += npix, pa += npix, pb += npix) {
-            const double wr = huber_w(px[q.up] - c, ds), wc = huber_w(px[q.lf] - c, ds);
+            const double wr = pot_w<KS>(px[q.up] - c, ds), wc = pot_w<KS>(px[q.lf] - c, ds);
             const double ar = pa[q.up] - ac, acl = pa[q.lf] - ac, br = pb[q.up] - bc, bcl = pb[q.lf] - bc;
             acc[0] += wr * ar * ar + wc * acl * acl;
             acc[1] += wr * ar * br + wc * acl * bcl;
@@ -91,7 +94,7 @@ __global__ __launch_bounds__(TPB) void huber_vox_curv_kernel(const float *__rest
                 cn = px[p + (long)npix];
                 an = pa[p + (long)npix];
                 bn = pb[p + (long)npix];
-                const double wl = huber_w(cn - c, dl), al = an - ac, bl = bn - bc;
+                const double wl = pot_w<KL>(cn - c, dl), al = an - ac, bl = bn - bc;
                 acc[3] += wl * al * al;
                 acc[4] += wl * al * bl;
                 acc[5] += wl * bl * bl;
@@ -113,24 +116,43 @@ inline dim3 march_grid(int Lc, int na, int nb) {
     return dim3(gx, gy < 1 ? 1 : gy);
 }
 
+// pot_dispatch on the spatial kind around one on the spectral kind: f(KS) returns what the inner dispatch returned
+template <class F>
+inline bool vox_dispatch(int ks, F &&f) {
+    bool ok = false;
+    return pot_dispatch(ks, [&](auto KS) { ok = f(KS); }) && ok;
+}
+
 }  // namespace
 
 size_t launch_huber_vox_scratch_doubles() { return (size_t)6 * VOX_BLOCKS; }
 
 int launch_huber_vox_grad(hipStream_t s, const float *x, const float *src, float *out, int Lc, int na, int nb, float cs, float ds,
-                          float cl, float dl, double *scratch, double *sums) {
+                          float cl, float dl, int ks, int kl, double *scratch, double *sums) {
     if (Lc < 1 || na < 1 || nb < 1 || (long)na * nb > 0x7fffffffL - 2 * TPB * (long)VOX_BLOCKS) return (int)hipErrorInvalidValue;
     const dim3 g = march_grid(Lc, na, nb);
-    hipLaunchKernelGGL(huber_vox_grad_kernel, g, dim3(TPB), 0, s, x, src, out, Lc, na, nb, cs, ds, cl, dl, scratch);
+    const auto go = [&](auto KS) {
+        return pot_dispatch(kl, [&](auto KL) {
+            hipLaunchKernelGGL((huber_vox_grad_kernel<decltype(KS)::value, decltype(KL)::value>), g, dim3(TPB), 0, s, x, src, out, Lc, na,
+                               nb, cs, ds, cl, dl, scratch);
+        });
+    };
+    if (!vox_dispatch(ks, go)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(parts_reduce_kernel, dim3(3), dim3(TPB), 0, s, scratch, (int)(g.x * g.y), sums);
     return (int)hipGetLastError();
 }
 
 int launch_huber_vox_curv(hipStream_t s, const float *x, const float *p0, const float *p1, int Lc, int na, int nb, float ds, float dl,
-                          double *scratch, double *sums) {
+                          int ks, int kl, double *scratch, double *sums) {
     if (Lc < 1 || na < 1 || nb < 1 || (long)na * nb > 0x7fffffffL - 2 * TPB * (long)VOX_BLOCKS) return (int)hipErrorInvalidValue;
     const dim3 g = march_grid(Lc, na, nb);
-    hipLaunchKernelGGL(huber_vox_curv_kernel, g, dim3(TPB), 0, s, x, p0, p1, Lc, na, nb, ds, dl, scratch);
+    const auto go = [&](auto KS) {
+        return pot_dispatch(kl, [&](auto KL) {
+            hipLaunchKernelGGL((huber_vox_curv_kernel<decltype(KS)::value, decltype(KL)::value>), g, dim3(TPB), 0, s, x, p0, p1, Lc, na,
+                               nb, ds, dl, scratch);
+        });
+    };
+    if (!vox_dispatch(ks, go)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(parts_reduce_kernel, dim3(6), dim3(TPB), 0, s, scratch, (int)(g.x * g.y), sums);
     return (int)hipGetLastError();
 }

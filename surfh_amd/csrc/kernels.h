@@ -152,30 +152,32 @@ int launch_mmmg_update(hipStream_t s, float *x, float *r, const float *d, float 
 // Huber priors on the separated circular first differences of [T][na][nb] maps, u_r = x[i-1][j] - x[i][j], u_c = x[i][j-1] - x[i][j]
 // (NpDiff_r / NpDiff_c); phi(u) = u^2/2 (|u| <= delta), delta (|u| - delta/2) beyond; w(u) = phi'(u) / u.  Float64 per-block partials
 // in `scratch` (>= 768 doubles), summed in a fixed order: the same inputs give the same bits.
+// `kind` (here and below; `ks`, `kl` for the cube's in-plane and wavelength families): the potential, 0 Huber as described,
+// 1 hyperbolic, 2 Hebert-Leahy (huber_dev.h); the kernels are instantiated per kind, an unknown kind is hipErrorInvalidValue.
 // out = src + coef * sum_k D_k^T phi'(D_k x) (out may alias src); sums[0] = out.out, sums[1] = sum_k sum phi(D_k x)
 int launch_huber_grad(hipStream_t s, const float *x, const float *src, float *out, int T, int na, int nb, float coef, float delta,
-                      double *scratch, double *sums);
+                      int kind, double *scratch, double *sums);
 // sums[0..2] = sum_k sum w(D_k x) (D_k p0)^2, (D_k p0)(D_k p1), (D_k p1)^2: the prior block of the half-quadratic majorant
 int launch_huber_curv(hipStream_t s, const float *x, const float *p0, const float *p1, int T, int na, int nb, float delta,
-                      double *scratch, double *sums);
+                      int kind, double *scratch, double *sums);
 // The same potentials on the cube [Lc][na][nb] (huber_vox.hip): the in-plane circular differences under the threshold ds and the
 // open wavelength difference u_l = x[l+1] - x[l], l = 0 .. Lc-2, under dl.  `scratch` holds launch_huber_vox_scratch_doubles().
 // out = src + cs sum_{k in r,c} D_k^T phi'_ds(D_k x) + cl Dl^T phi'_dl(Dl x) in one pass (out may alias src);
 // sums[0] = out.out, sums[1] = sum_{k in r,c} sum phi_ds(D_k x), sums[2] = sum phi_dl(Dl x)
 int launch_huber_vox_grad(hipStream_t s, const float *x, const float *src, float *out, int Lc, int na, int nb, float cs, float ds,
-                          float cl, float dl, double *scratch, double *sums);
+                          float cl, float dl, int ks, int kl, double *scratch, double *sums);
 // sums[0..2] = sum_{k in r,c} sum w_ds(D_k x) (D_k p0)^2, (D_k p0)(D_k p1), (D_k p1)^2;  sums[3..5] = the same under w_dl(Dl x) on Dl
 int launch_huber_vox_curv(hipStream_t s, const float *x, const float *p0, const float *p1, int Lc, int na, int nb, float ds, float dl,
-                          double *scratch, double *sums);
+                          int ks, int kl, double *scratch, double *sums);
 size_t launch_huber_vox_scratch_doubles();
 // Robust (Huber) data term (robust_data.hip), on flat detector vectors [n]: t = sqrt(w) (y - u), a sample with w <= 0 taken out by
 // a select (NaN there stays out); w == nullptr: every weight 1.  `scratch` holds launch_robust_scratch_doubles(); float64 sums in a fixed order.
 // v = sqrt(w) phi'(t), omega (may be null) = phi'(t) / t in (0, 1], 0 where masked; sums[0] = sum phi(t), sums[1] = number of |t| > delta
 int launch_robust_data(hipStream_t s, const float *y, const float *u, const float *w, float *v, float *omega, long n, float delta,
-                       double *scratch, double *sums);
+                       int kind, double *scratch, double *sums);
 // sums[0..2] = sum w omega(t) p0^2, p0 p1, p1^2: the data block of the half-quadratic majorant
 int launch_robust_curv(hipStream_t s, const float *y, const float *u, const float *w, const float *p0, const float *p1, long n,
-                       float delta, double *scratch, double *sums);
+                       float delta, int kind, double *scratch, double *sums);
 // mv = c0 g + c1 m ; u += mv ; m = mv   (the 3MG move in the basis [g, m]; detector vectors and maps alike)
 int launch_robust_move(hipStream_t s, float *u, const float *g, float *m, long n, double c0, double c1);
 size_t launch_robust_scratch_doubles();
@@ -203,15 +205,15 @@ int launch_mmmg_step_planes(hipStream_t s, float *x, float *r, const float *d, f
 // step: the 2x2 majorant step in [d, m] with qd = Q_D d; a plane without positive curvature keeps still
 constexpr int HUBER_PLANES_SCALARS = 7;
 int launch_huber_dir_planes(hipStream_t s, const float *x, const float *r, float *g, const float *m, const float *qm, float *d,
-                            int nplanes, int na, int nb, double mu_reg, float delta, double *sc);
+                            int nplanes, int na, int nb, double mu_reg, float delta, int kind, double *sc);
 int launch_huber_step_planes(hipStream_t s, float *x, float *r, const float *d, float *m, float *qm, const float *qd, const float *g,
                              int nplanes, long npix, double mu_reg, const double *sc, int update_r);
 // the two passes of the dir kernel alone: out = src + coef sum_k D_k^T phi'(D_k x) (out may alias src) with sc[0], sc[1] = |out|^2 and
 // sum phi per plane; sc[4..6] = the prior block of (p0, p1) per plane
 int launch_huber_planes_grad(hipStream_t s, const float *x, const float *src, float *out, int nplanes, int na, int nb, float coef,
-                             float delta, double *sc);
+                             float delta, int kind, double *sc);
 int launch_huber_planes_curv(hipStream_t s, const float *x, const float *p0, const float *p1, int nplanes, int na, int nb, float delta,
-                             double *sc);
+                             int kind, double *sc);
 // (hth + diag(mu reg)) z = in per frequency bin (reg < 0 marks padding bins); *flag |= 1 on a non-positive pivot
 int launch_wct_solve(hipStream_t s, const float *hth, const float *reg, const double *mu, const float *in, float *out, int T,
                      long PL, int *flag);

@@ -1251,7 +1251,7 @@ __global__ __launch_bounds__(TPB) void mmmg_step_planes_kernel(float *__restrict
 // ---- Huber priors on the separated circular first differences (surfh_mmmg_huber) ----------------
 // One thread per map pixel (grid-stride): the pixel owns u_r = x[i-1][j] - x[i][j] and u_c = x[i][j-1] - x[i][j] and, for the
 // gradient, reads the differences it shares with its successors.  Maps are a few MB: the neighbour reads hit L2 (the cube's
-// kernels, where that no longer holds, are in huber_vox.hip).  huber_phi / huber_dphi / huber_w: huber_dev.h.
+// kernels, where that no longer holds, are in huber_vox.hip).  pot_phi / pot_dphi / pot_w<KIND>: huber_dev.h.
 
 // block_sums_to<K>, parts_reduce_kernel: huber_dev.h
 struct PixelNbrs {   // (t, i, j) of element e of [T][na][nb] and the circular neighbour offsets inside its plane
@@ -1273,7 +1273,8 @@ __device__ __forceinline__ PixelNbrs pixel_nbrs(long e, int na, int nb) {
 }
 
 // out = src + coef (Dr^T phi'(Dr x) + Dc^T phi'(Dc x)),  (D^T v)[i] = v[i+1] - v[i];  part: [2][gridDim.x] (out.out, sum phi)
-// src and out may be the same array (each element is read and written by one thread)
+// src and out may be the same array (each element is read and written by one thread).  KIND: the potential (huber_dev.h)
+template <int KIND>
 __global__ __launch_bounds__(TPB) void huber_grad_kernel(const float *__restrict__ x, const float *src, float *out, long n, int na,
                                                          int nb, float coef, float delta, double *__restrict__ part) {
     double acc[2] = {0.0, 0.0};
@@ -1284,16 +1285,17 @@ __global__ __launch_bounds__(TPB) void huber_grad_kernel(const float *__restrict
         const float c = p[q.c];
         const float ur = p[q.im] - c, uc = p[q.jm] - c;            // (Dr x)[i][j], (Dc x)[i][j]
         const float urn = c - p[q.ip], ucn = c - p[q.jp];          // (Dr x)[i+1][j], (Dc x)[i][j+1]
-        const float pg = (huber_dphi(urn, delta) - huber_dphi(ur, delta)) + (huber_dphi(ucn, delta) - huber_dphi(uc, delta));
+        const float pg = (pot_dphi<KIND>(urn, delta) - pot_dphi<KIND>(ur, delta)) + (pot_dphi<KIND>(ucn, delta) - pot_dphi<KIND>(uc, delta));
         const float g = src[e] + coef * pg;
         out[e] = g;
         acc[0] += (double)g * (double)g;
-        acc[1] += huber_phi(ur, delta) + huber_phi(uc, delta);
+        acc[1] += pot_phi<KIND>(ur, delta) + pot_phi<KIND>(uc, delta);
     }
     block_sums_to<2>(acc, part);
 }
 
 // part: [3][gridDim.x] = sum_k w(D_k x) (D_k p0)^2, (D_k p0)(D_k p1), (D_k p1)^2 (weights recomputed, none stored)
+template <int KIND>
 __global__ __launch_bounds__(TPB) void huber_curv_kernel(const float *__restrict__ x, const float *__restrict__ p0,
                                                          const float *__restrict__ p1, long n, int na, int nb, float delta,
                                                          double *__restrict__ part) {
@@ -1303,7 +1305,7 @@ __global__ __launch_bounds__(TPB) void huber_curv_kernel(const float *__restrict
         const PixelNbrs q = pixel_nbrs(e, na, nb);
         const float *p = x + q.base, *a = p0 + q.base, *b = p1 + q.base;
         const float c = p[q.c], ac = a[q.c], bc = b[q.c];
-        const double wr = huber_w(p[q.im] - c, delta), wc = huber_w(p[q.jm] - c, delta);
+        const double wr = pot_w<KIND>(p[q.im] - c, delta), wc = pot_w<KIND>(p[q.jm] - c, delta);
         const double ar = a[q.im] - ac, acl = a[q.jm] - ac, br = b[q.im] - bc, bcl = b[q.jm] - bc;
         acc[0] += wr * ar * ar + wc * acl * acl;
         acc[1] += wr * ar * br + wc * acl * bcl;
@@ -1340,7 +1342,7 @@ struct PlaneWalk {   // element e = i * nb + j of a [na][nb] plane, e = threadId
 //   (huber_curv_kernel's arithmetic, weights recomputed).
 // PHASES == 3, the solver's launch (src = r, coef = -mu_reg, g = -gradient): also g.Q_D m and m.Q_D m from the carried image
 //   qm, beta = -(g.Bm) / (m.Bm) with B = Q_D + reg W, d = g + beta m; sc[HP_BETA] = the fp32 beta that formed d, sc[HP_MBM] = m.Bm.
-template <int PHASES>
+template <int PHASES, int KIND>
 __global__ __launch_bounds__(TPB) void huber_dir_planes_kernel(const float *__restrict__ x, const float *src, float *g,
                                                                const float *__restrict__ m, const float *__restrict__ qm,
                                                                float *__restrict__ d, int na, int nb, float coef, float delta,
@@ -1356,11 +1358,11 @@ __global__ __launch_bounds__(TPB) void huber_dir_planes_kernel(const float *__re
             const float c = px[q.e];
             const float ur = px[im] - c, uc = px[jm] - c;              // (Dr x)[i][j], (Dc x)[i][j]
             const float urn = c - px[ip], ucn = c - px[jp];            // (Dr x)[i+1][j], (Dc x)[i][j+1]
-            const float pg = (huber_dphi(urn, delta) - huber_dphi(ur, delta)) + (huber_dphi(ucn, delta) - huber_dphi(uc, delta));
+            const float pg = (pot_dphi<KIND>(urn, delta) - pot_dphi<KIND>(ur, delta)) + (pot_dphi<KIND>(ucn, delta) - pot_dphi<KIND>(uc, delta));
             const float gv = src[off + q.e] + coef * pg;
             g[off + q.e] = gv;
             v[0] += (double)gv * (double)gv;
-            v[1] += huber_phi(ur, delta) + huber_phi(uc, delta);
+            v[1] += pot_phi<KIND>(ur, delta) + pot_phi<KIND>(uc, delta);
         }
         block_sum_bcast<2>(v);
         if (threadIdx.x == 0) {
@@ -1381,7 +1383,7 @@ __global__ __launch_bounds__(TPB) void huber_dir_planes_kernel(const float *__re
         for (PlaneWalk q(nb); q.e < npix; q.next(nb)) {
             const int im = q.e - nb + (q.i == 0 ? npix : 0), jm = q.e - 1 + (q.j == 0 ? nb : 0);
             const float c = px[q.e], ac = a[q.e], bc = b[q.e];
-            const double wr = huber_w(px[im] - c, delta), wc = huber_w(px[jm] - c, delta);
+            const double wr = pot_w<KIND>(px[im] - c, delta), wc = pot_w<KIND>(px[jm] - c, delta);
             const double ar = a[im] - ac, acl = a[jm] - ac, br = b[im] - bc, bcl = b[jm] - bc;
             v[0] += wr * ar * ar + wc * acl * acl;
             v[1] += wr * ar * br + wc * acl * bcl;
@@ -1843,26 +1845,35 @@ inline bool plane_fits(int nplanes, int na, int nb) { return nplanes > 0 && na >
 }  // namespace
 
 int launch_huber_dir_planes(hipStream_t s, const float *x, const float *r, float *g, const float *m, const float *qm, float *d,
-                            int nplanes, int na, int nb, double mu_reg, float delta, double *sc) {
+                            int nplanes, int na, int nb, double mu_reg, float delta, int kind, double *sc) {
     if (!plane_fits(nplanes, na, nb)) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(huber_dir_planes_kernel<3>, dim3(nplanes), dim3(TPB), 0, s, x, r, g, m, qm, d, na, nb, -(float)mu_reg, delta,
-                       mu_reg, sc);
+    const auto go = [&](auto K) {
+        hipLaunchKernelGGL((huber_dir_planes_kernel<3, decltype(K)::value>), dim3(nplanes), dim3(TPB), 0, s, x, r, g, m, qm, d, na, nb,
+                           -(float)mu_reg, delta, mu_reg, sc);
+    };
+    if (!pot_dispatch(kind, go)) return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
 }
 
 int launch_huber_planes_grad(hipStream_t s, const float *x, const float *src, float *out, int nplanes, int na, int nb, float coef,
-                             float delta, double *sc) {
+                             float delta, int kind, double *sc) {
     if (!plane_fits(nplanes, na, nb)) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(huber_dir_planes_kernel<1>, dim3(nplanes), dim3(TPB), 0, s, x, src, out, (const float *)nullptr,
-                       (const float *)nullptr, (float *)nullptr, na, nb, coef, delta, 0.0, sc);
+    const auto go = [&](auto K) {
+        hipLaunchKernelGGL((huber_dir_planes_kernel<1, decltype(K)::value>), dim3(nplanes), dim3(TPB), 0, s, x, src, out,
+                           (const float *)nullptr, (const float *)nullptr, (float *)nullptr, na, nb, coef, delta, 0.0, sc);
+    };
+    if (!pot_dispatch(kind, go)) return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
 }
 
 int launch_huber_planes_curv(hipStream_t s, const float *x, const float *p0, const float *p1, int nplanes, int na, int nb, float delta,
-                             double *sc) {
+                             int kind, double *sc) {
     if (!plane_fits(nplanes, na, nb)) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(huber_dir_planes_kernel<2>, dim3(nplanes), dim3(TPB), 0, s, x, (const float *)nullptr, const_cast<float *>(p0),
-                       p1, (const float *)nullptr, (float *)nullptr, na, nb, 0.f, delta, 0.0, sc);
+    const auto go = [&](auto K) {
+        hipLaunchKernelGGL((huber_dir_planes_kernel<2, decltype(K)::value>), dim3(nplanes), dim3(TPB), 0, s, x, (const float *)nullptr,
+                           const_cast<float *>(p0), p1, (const float *)nullptr, (float *)nullptr, na, nb, 0.f, delta, 0.0, sc);
+    };
+    if (!pot_dispatch(kind, go)) return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
 }
 
@@ -1880,20 +1891,26 @@ int launch_cg_dir_planes(hipStream_t s, float *d, const float *r, int nplanes, l
 // 256 blocks at most: [3][256] partials fit the plan's 1024-double scratch
 constexpr int HUBER_BLOCKS = 256;
 int launch_huber_grad(hipStream_t s, const float *x, const float *src, float *out, int T, int na, int nb, float coef, float delta,
-                      double *scratch, double *sums) {
+                      int kind, double *scratch, double *sums) {
     if (T < 1 || na < 1 || nb < 1) return (int)hipErrorInvalidValue;
     const long n = (long)T * na * nb;
     const int nbk = nblocks(n, HUBER_BLOCKS);
-    hipLaunchKernelGGL(huber_grad_kernel, dim3(nbk), dim3(TPB), 0, s, x, src, out, n, na, nb, coef, delta, scratch);
+    const auto go = [&](auto K) {
+        hipLaunchKernelGGL(huber_grad_kernel<decltype(K)::value>, dim3(nbk), dim3(TPB), 0, s, x, src, out, n, na, nb, coef, delta, scratch);
+    };
+    if (!pot_dispatch(kind, go)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(parts_reduce_kernel, dim3(2), dim3(TPB), 0, s, scratch, nbk, sums);
     return (int)hipGetLastError();
 }
 int launch_huber_curv(hipStream_t s, const float *x, const float *p0, const float *p1, int T, int na, int nb, float delta,
-                      double *scratch, double *sums) {
+                      int kind, double *scratch, double *sums) {
     if (T < 1 || na < 1 || nb < 1) return (int)hipErrorInvalidValue;
     const long n = (long)T * na * nb;
     const int nbk = nblocks(n, HUBER_BLOCKS);
-    hipLaunchKernelGGL(huber_curv_kernel, dim3(nbk), dim3(TPB), 0, s, x, p0, p1, n, na, nb, delta, scratch);
+    const auto go = [&](auto K) {
+        hipLaunchKernelGGL(huber_curv_kernel<decltype(K)::value>, dim3(nbk), dim3(TPB), 0, s, x, p0, p1, n, na, nb, delta, scratch);
+    };
+    if (!pot_dispatch(kind, go)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(parts_reduce_kernel, dim3(3), dim3(TPB), 0, s, scratch, nbk, sums);
     return (int)hipGetLastError();
 }

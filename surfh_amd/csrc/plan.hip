@@ -163,6 +163,9 @@ struct surfh_plan {
     // gather / scatter rows) -- the strict dot test; storage stays fp32
     bool verify = false;
     int prior_kind = 0;                          // 0: separated first differences (NpDiff_r / NpDiff_c); 1: joint Laplacian (surfh_set_prior)
+    // surfh_set_potential: the potential of the spatial prior (maps, planes, the cube's rows / columns), of the cube's spectral
+    // prior and of the robust data term; 0 Huber, 1 hyperbolic, 2 Hebert-Leahy (huber_dev.h)
+    int pot[3] = {0, 0, 0};
     // two-piece fp16 passes with LDS-resident matrices (dft_h2.h): the plan's complex arrays (sotf, spec, ycol, and
     // mhat when T == 0) are then INTERLEAVED [..][LP][2] instead of planar [2][..][LP]
     bool h2 = false;
@@ -2208,6 +2211,24 @@ int surfh_set_prior(surfh_plan *p, int32_t kind) {
     p->prior_kind = kind;
     return 0;
 }
+int surfh_set_potential(surfh_plan *p, int32_t slot, int32_t kind) {
+    if (slot < 0 || slot > 2) return fail("potential slot %d: 0 = spatial prior, 1 = spectral prior, 2 = data term", (int)slot);
+    if (kind < 0 || kind > 2) return fail("potential kind %d: 0 = huber, 1 = hyperbolic, 2 = hebert_leahy", (int)kind);
+    if (!p) return fail("null plan");
+    p->pot[slot] = kind;
+    return 0;
+}
+int surfh_get_potential(const surfh_plan *p, int32_t slot) {
+    if (slot < 0 || slot > 2) {
+        fail("potential slot %d: 0 = spatial prior, 1 = spectral prior, 2 = data term", (int)slot);
+        return -1;
+    }
+    if (!p) {
+        fail("null plan");
+        return -1;
+    }
+    return p->pot[slot];
+}
 // ---- data weights: plan state, like the prior ------------------------------------------------------------------------------------
 namespace {
 // installs the validated device weights w_new [osize] (taken over) or, with nullptr, clears the state; on failure the plan keeps what it had
@@ -2627,7 +2648,8 @@ int surfh_huber_prior_dev(surfh_plan *p, const float *x_dev, float *g_dev, doubl
     if (huber_args(mu_reg, delta)) return 1;
     double h[2];
     const auto pass = [&] {
-        return launch_huber_grad(p->stream, x_dev, g_dev, g_dev, p->T, p->Na, p->Nb, (float)mu_reg, (float)delta, p->dscratch, p->dscal);
+        return launch_huber_grad(p->stream, x_dev, g_dev, g_dev, p->T, p->Na, p->Nb, (float)mu_reg, (float)delta, p->pot[0], p->dscratch,
+                                 p->dscal);
     };
     if (diag_pass(p, "huber_grad", pass, p->dscal, h, 2)) return 1;
     if (value) *value = h[1];
@@ -2638,7 +2660,7 @@ int surfh_huber_curv_dev(surfh_plan *p, const float *x_dev, const float *p0_dev,
     if (p->T <= 0) return fail("prior is defined on abundance maps (needs templates)");
     if (huber_args(0.0, delta)) return 1;
     const auto pass = [&] {
-        return launch_huber_curv(p->stream, x_dev, p0_dev, p1_dev, p->T, p->Na, p->Nb, (float)delta, p->dscratch, p->dscal);
+        return launch_huber_curv(p->stream, x_dev, p0_dev, p1_dev, p->T, p->Na, p->Nb, (float)delta, p->pot[0], p->dscratch, p->dscal);
     };
     return diag_pass(p, "huber_curv", pass, p->dscal, sums, 3);
 }
@@ -2655,6 +2677,7 @@ struct HuberPrior {
     int (*grad)(surfh_plan *p, const HuberPrior &h, const float *x, const float *src, float *out, double *sums);
     int (*curv)(surfh_plan *p, const HuberPrior &h, const float *x, const float *p0, const float *p1, double *sums);
     float delta[2];
+    int kind[2];                                                            // the potential of each family (surfh_set_potential)
     double quad_reg;                                                        // weight of the quadratic prior the operator carries
 };
 
@@ -2741,24 +2764,25 @@ int quad_curv(surfh_plan *, const HuberPrior &, const float *, const float *, co
 // the maps' prior: one family (rows and columns under one weight and one threshold)
 int maps_grad(surfh_plan *p, const HuberPrior &h, const float *x, const float *src, float *out, double *sums) {
     Prof pr(p, "huber_grad");
-    LAUNCH_OK(launch_huber_grad(p->stream, x, src, out, p->T, p->Na, p->Nb, -(float)h.reg[0], h.delta[0], p->dscratch, sums));
+    LAUNCH_OK(launch_huber_grad(p->stream, x, src, out, p->T, p->Na, p->Nb, -(float)h.reg[0], h.delta[0], h.kind[0], p->dscratch, sums));
     return 0;
 }
 int maps_curv(surfh_plan *p, const HuberPrior &h, const float *x, const float *p0, const float *p1, double *sums) {
     Prof pr(p, "huber_curv");
-    LAUNCH_OK(launch_huber_curv(p->stream, x, p0, p1, p->T, p->Na, p->Nb, h.delta[0], p->dscratch, sums));
+    LAUNCH_OK(launch_huber_curv(p->stream, x, p0, p1, p->T, p->Na, p->Nb, h.delta[0], h.kind[0], p->dscratch, sums));
     return 0;
 }
 // the cube's prior: the in-plane family and the wavelength family
 int vox_grad(surfh_plan *p, const HuberPrior &h, const float *x, const float *src, float *out, double *sums) {
     Prof pr(p, "huber_vox_grad");
     LAUNCH_OK(launch_huber_vox_grad(p->stream, x, src, out, p->Lc, p->Na, p->Nb, -(float)h.reg[0], h.delta[0], -(float)h.reg[1],
-                                    h.delta[1], p->dscratch, sums));
+                                    h.delta[1], h.kind[0], h.kind[1], p->dscratch, sums));
     return 0;
 }
 int vox_curv(surfh_plan *p, const HuberPrior &h, const float *x, const float *p0, const float *p1, double *sums) {
     Prof pr(p, "huber_vox_curv");
-    LAUNCH_OK(launch_huber_vox_curv(p->stream, x, p0, p1, p->Lc, p->Na, p->Nb, h.delta[0], h.delta[1], p->dscratch, sums));
+    LAUNCH_OK(launch_huber_vox_curv(p->stream, x, p0, p1, p->Lc, p->Na, p->Nb, h.delta[0], h.delta[1], h.kind[0], h.kind[1], p->dscratch,
+                                    sums));
     return 0;
 }
 }  // namespace
@@ -2769,7 +2793,7 @@ int surfh_mmmg_huber(surfh_plan *p, const float *y, double mu, double mu_reg, do
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
     if (p->T <= 0) return fail("surfh_mmmg_huber needs templates (the priors act on abundance maps)");
     if (huber_args(mu_reg, delta)) return 1;
-    const HuberPrior hp = {1, {mu_reg, 0.0}, "Huber", maps_grad, maps_curv, {(float)delta, 0.f}};
+    const HuberPrior hp = {1, {mu_reg, 0.0}, "Huber", maps_grad, maps_curv, {(float)delta, 0.f}, {p->pot[0], 0}};
     return mmmg_huber_loop(p, hp, y, mu, x0, max_iter, tol, refresh, x, grad_norm, nit, prior_value, callback, user);
 }
 
@@ -2777,7 +2801,7 @@ int surfh_mmmg(surfh_plan *p, const float *y, double mu, double mu_reg, const fl
                int32_t refresh, float *x, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
     if (p->T <= 0) return fail("surfh_mmmg needs templates (the priors act on abundance maps)");
-    const HuberPrior hp = {0, {0.0, 0.0}, nullptr, quad_grad, quad_curv, {0.f, 0.f}, mu_reg};
+    const HuberPrior hp = {0, {0.0, 0.0}, nullptr, quad_grad, quad_curv, {0.f, 0.f}, {0, 0}, mu_reg};
     return mmmg_huber_loop(p, hp, y, mu, x0, max_iter, tol, refresh, x, grad_norm, nit, nullptr, callback, user);
 }
 
@@ -2792,7 +2816,7 @@ int surfh_huber_vox_prior_dev(surfh_plan *p, const float *x_dev, float *g_dev, d
     double h[3];
     const auto pass = [&] {
         return launch_huber_vox_grad(p->stream, x_dev, g_dev, g_dev, p->Lc, p->Na, p->Nb, (float)spat_reg, (float)spat_delta,
-                                     (float)spec_reg, (float)spec_delta, p->dscratch, p->dscal);
+                                     (float)spec_reg, (float)spec_delta, p->pot[0], p->pot[1], p->dscratch, p->dscal);
     };
     if (diag_pass(p, "huber_vox_grad", pass, p->dscal, h, 3)) return 1;
     if (values) {
@@ -2808,7 +2832,7 @@ int surfh_huber_vox_curv_dev(surfh_plan *p, const float *x_dev, const float *p0_
     if (huber_args(0.0, spat_delta) || huber_args(0.0, spec_delta)) return 1;
     const auto pass = [&] {
         return launch_huber_vox_curv(p->stream, x_dev, p0_dev, p1_dev, p->Lc, p->Na, p->Nb, (float)spat_delta, (float)spec_delta,
-                                     p->dscratch, p->dscal);
+                                     p->pot[0], p->pot[1], p->dscratch, p->dscal);
     };
     return diag_pass(p, "huber_vox_curv", pass, p->dscal, sums, 6);
 }
@@ -2819,7 +2843,8 @@ int surfh_mmmg_huber_vox(surfh_plan *p, const float *y, double mu, double spat_r
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
     if (p->T > 0) return fail("surfh_mmmg_huber_vox reconstructs the cube: it needs a plan without templates (n_templates = 0)");
     if (huber_args(spat_reg, spat_delta) || huber_args(spec_reg, spec_delta)) return 1;
-    const HuberPrior hp = {2, {spat_reg, spec_reg}, "Huber, voxel-wise", vox_grad, vox_curv, {(float)spat_delta, (float)spec_delta}};
+    const HuberPrior hp = {2, {spat_reg, spec_reg}, "Huber, voxel-wise", vox_grad, vox_curv, {(float)spat_delta, (float)spec_delta},
+                           {p->pot[0], p->pot[1]}};
     return mmmg_huber_loop(p, hp, y, mu, x0, max_iter, tol, refresh, x, grad_norm, nit, prior_values, callback, user);
 }
 
@@ -2856,6 +2881,7 @@ int mmmg_robust_loop(surfh_plan *p, const HuberPrior &hp, const float *y, double
     const long n = p->isize, no = p->osize;
     const int F = hp.nfam;
     const float dd = robust_delta_f32(data_delta);
+    const int dk = p->pot[2];                              // the potential of the data term
     float *r = p->cg_r, *m = p->cg_d, *ng = p->cg_hg, *v = p->cg_y, *yd = p->rb_y, *u = p->rb_u, *ag = p->rb_ag, *am = p->rb_am;
     const float *w = p->dw;
     // device scalars: [0, 1] robust_data, [2 .. 2+F] the prior's grad pass, [3+F .. 5+F] robust_curv, [6+F .. 5+4F] the prior's
@@ -2869,7 +2895,7 @@ int mmmg_robust_loop(surfh_plan *p, const HuberPrior &hp, const float *y, double
         const bool last = it >= max_iter;                  // only |g| and the values are wanted: no majorant
         {
             Prof pr(p, "robust_data");
-            LAUNCH_OK(launch_robust_data(s, yd, u, w, v, nullptr, no, dd, p->dscratch, sc + 0));
+            LAUNCH_OK(launch_robust_data(s, yd, u, w, v, nullptr, no, dd, dk, p->dscratch, sc + 0));
         }
         if (adjoint_dev(p, v, r, false)) return 1;
         if (mu != 1.0) LAUNCH_OK(launch_scale(s, r, n, (float)mu));
@@ -2878,7 +2904,7 @@ int mmmg_robust_loop(surfh_plan *p, const HuberPrior &hp, const float *y, double
             if (forward_dev(p, ng, ag)) return 1;
             {
                 Prof pr(p, "robust_curv");
-                LAUNCH_OK(launch_robust_curv(s, yd, u, w, ag, am, no, dd, p->dscratch, sc + CD));
+                LAUNCH_OK(launch_robust_curv(s, yd, u, w, ag, am, no, dd, dk, p->dscratch, sc + CD));
             }
             if (hp.curv(p, hp, p->cg_x, ng, m, sc + CP)) return 1;
             LAUNCH_OK(launch_dot(s, m, ng, n, p->dscratch, sc + MG));
@@ -2917,7 +2943,7 @@ int mmmg_robust_loop(surfh_plan *p, const HuberPrior &hp, const float *y, double
     if (values)
         for (int k = 0; k < 2 + F; ++k) values[k] = val[k];
     if (omega_out) {                                       // omega at the returned iterate (u = A x of it)
-        LAUNCH_OK(launch_robust_data(s, yd, u, w, v, ag, no, dd, p->dscratch, sc + 0));
+        LAUNCH_OK(launch_robust_data(s, yd, u, w, v, ag, no, dd, dk, p->dscratch, sc + 0));
         HIP_OK(hipMemcpyAsync(omega_out, ag, no * sizeof(float), hipMemcpyDeviceToHost, s));
     }
     return mmmg_finish(p, x);
@@ -2930,7 +2956,7 @@ int surfh_mmmg_robust(surfh_plan *p, const float *y, double mu, double data_delt
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
     if (p->T <= 0) return fail("surfh_mmmg_robust needs templates (the priors act on abundance maps)");
     if (robust_args(data_delta) || huber_args(mu_reg, delta)) return 1;
-    const HuberPrior hp = {1, {mu_reg, 0.0}, "Huber", maps_grad, maps_curv, {(float)delta, 0.f}};
+    const HuberPrior hp = {1, {mu_reg, 0.0}, "Huber", maps_grad, maps_curv, {(float)delta, 0.f}, {p->pot[0], 0}};
     return mmmg_robust_loop(p, hp, y, mu, data_delta, x0, max_iter, tol, refresh, x, grad_norm, nit, values, omega_out, callback, user);
 }
 
@@ -2941,7 +2967,8 @@ int surfh_mmmg_robust_vox(surfh_plan *p, const float *y, double mu, double data_
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
     if (p->T > 0) return fail("surfh_mmmg_robust_vox reconstructs the cube: it needs a plan without templates (n_templates = 0)");
     if (robust_args(data_delta) || huber_args(spat_reg, spat_delta) || huber_args(spec_reg, spec_delta)) return 1;
-    const HuberPrior hp = {2, {spat_reg, spec_reg}, "Huber, voxel-wise", vox_grad, vox_curv, {(float)spat_delta, (float)spec_delta}};
+    const HuberPrior hp = {2, {spat_reg, spec_reg}, "Huber, voxel-wise", vox_grad, vox_curv, {(float)spat_delta, (float)spec_delta},
+                           {p->pot[0], p->pot[1]}};
     return mmmg_robust_loop(p, hp, y, mu, data_delta, x0, max_iter, tol, refresh, x, grad_norm, nit, values, omega_out, callback, user);
 }
 
@@ -2951,7 +2978,8 @@ int surfh_robust_data_dev(surfh_plan *p, const float *y_dev, const float *u_dev,
     if (n < 1) return fail("surfh_robust_data_dev: n = %ld", (long)n);
     if (robust_args(data_delta)) return 1;
     const auto pass = [&] {
-        return launch_robust_data(p->stream, y_dev, u_dev, w_dev, v_dev, nullptr, n, robust_delta_f32(data_delta), p->dscratch, p->dscal);
+        return launch_robust_data(p->stream, y_dev, u_dev, w_dev, v_dev, nullptr, n, robust_delta_f32(data_delta), p->pot[2], p->dscratch,
+                                  p->dscal);
     };
     return diag_pass(p, "robust_data", pass, p->dscal, sums_host, 2);
 }
@@ -2961,7 +2989,8 @@ int surfh_robust_curv_dev(surfh_plan *p, const float *y_dev, const float *u_dev,
     if (n < 1) return fail("surfh_robust_curv_dev: n = %ld", (long)n);
     if (robust_args(data_delta)) return 1;
     const auto pass = [&] {
-        return launch_robust_curv(p->stream, y_dev, u_dev, w_dev, p0_dev, p1_dev, n, robust_delta_f32(data_delta), p->dscratch, p->dscal);
+        return launch_robust_curv(p->stream, y_dev, u_dev, w_dev, p0_dev, p1_dev, n, robust_delta_f32(data_delta), p->pot[2], p->dscratch,
+                                  p->dscal);
     };
     return diag_pass(p, "robust_curv", pass, p->dscal, sums_host, 3);
 }
@@ -3249,7 +3278,7 @@ int surfh_huber_planes_prior_dev(surfh_plan *p, const float *x_dev, float *g_dev
     const int L = p->Lc;
     {
         Prof pr(p, "huber_planes_grad");
-        LAUNCH_OK(launch_huber_planes_grad(p->stream, x_dev, g_dev, g_dev, L, p->Na, p->Nb, (float)mu_reg, (float)delta, p->pl_hsc));
+        LAUNCH_OK(launch_huber_planes_grad(p->stream, x_dev, g_dev, g_dev, L, p->Na, p->Nb, (float)mu_reg, (float)delta, p->pot[0], p->pl_hsc));
     }
     if (sq_host) HIP_OK(hipMemcpyAsync(sq_host, p->pl_hsc, L * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     if (values_host) HIP_OK(hipMemcpyAsync(values_host, p->pl_hsc + L, L * sizeof(double), hipMemcpyDeviceToHost, p->stream));
@@ -3262,7 +3291,7 @@ int surfh_huber_planes_curv_dev(surfh_plan *p, const float *x_dev, const float *
     if (!p || !x_dev || !p0_dev || !p1_dev || !sums_host) return fail("null argument");
     if (huber_args(0.0, delta) || huber_planes_ready(p, "surfh_huber_planes_curv_dev")) return 1;
     const int L = p->Lc;
-    const auto pass = [&] { return launch_huber_planes_curv(p->stream, x_dev, p0_dev, p1_dev, L, p->Na, p->Nb, (float)delta, p->pl_hsc); };
+    const auto pass = [&] { return launch_huber_planes_curv(p->stream, x_dev, p0_dev, p1_dev, L, p->Na, p->Nb, (float)delta, p->pot[0], p->pl_hsc); };
     return diag_pass(p, "huber_planes_curv", pass, p->pl_hsc + (size_t)(HUBER_PLANES_SCALARS - 3) * L, sums_host, (size_t)3 * L);
 }
 
@@ -3277,7 +3306,7 @@ int surfh_mmmg_huber_planes(surfh_plan *p, const float *y, double mu, double mu_
     const auto dir = [&] {
         Prof pr(p, "huber_dir_planes");
         LAUNCH_OK(launch_huber_dir_planes(p->stream, p->cg_x, p->cg_r, p->cg_hg, p->cg_d, p->cg_qm, p->cg_dd, L, p->Na, p->Nb, mu_reg,
-                                          (float)delta, sc));
+                                          (float)delta, p->pot[0], sc));
         return 0;
     };
     const auto step = [&](int update_r) {

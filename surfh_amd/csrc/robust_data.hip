@@ -64,28 +64,31 @@ __device__ __forceinline__ float scaled_residual(float y, float u, float w, floa
     return keep ? sw * (y - u) : 0.f;
 }
 
+template <int KIND>
 __device__ __forceinline__ void data_one(float y, float u, float w, float delta, float &v, float &om, double (&acc)[2]) {
     float sw;
     bool keep;
     const float t = scaled_residual(y, u, w, sw, keep);
-    v = sw * huber_dphi(t, delta);
-    om = keep ? huber_w(t, delta) : 0.f;
-    acc[0] += huber_phi(t, delta);
+    v = sw * pot_dphi<KIND>(t, delta);
+    om = keep ? pot_w<KIND>(t, delta) : 0.f;
+    acc[0] += pot_phi<KIND>(t, delta);
     acc[1] += fabsf(t) > delta ? 1.0 : 0.0;
 }
 
+template <int KIND>
 __device__ __forceinline__ void curv_one(float y, float u, float w, float a, float b, float delta, double (&acc)[3]) {
     float sw;
     bool keep;
     const float t = scaled_residual(y, u, w, sw, keep);
-    const double ww = keep ? (double)w * (double)huber_w(t, delta) : 0.0, da = a, db = b;
+    const double ww = keep ? (double)w * (double)pot_w<KIND>(t, delta) : 0.0, da = a, db = b;
     acc[0] += ww * da * da;
     acc[1] += ww * da * db;
     acc[2] += ww * db * db;
 }
 
-// part [2][blocks]: sum phi(t), number of |t| > delta.  om may be null.
-template <int V>
+// part [2][blocks]: sum phi(t), number of |t| > delta (the samples past the knee, whatever the potential).  om may be null.
+// KIND: the potential of the data term (huber_dev.h).
+template <int V, int KIND>
 __global__ __launch_bounds__(TPB) void robust_data_kernel(const float *__restrict__ y, const float *__restrict__ u,
                                                           const float *__restrict__ w, float *__restrict__ v, float *__restrict__ om,
                                                           long n, float delta, double *__restrict__ part) {
@@ -98,14 +101,14 @@ __global__ __launch_bounds__(TPB) void robust_data_kernel(const float *__restric
         if (w) load<V>(rw, w, i);
         else fill<V>(rw, 1.f);
 #pragma unroll
-        for (int k = 0; k < V; ++k) data_one(ry[k], ru[k], rw[k], delta, rv[k], ro[k], acc);
+        for (int k = 0; k < V; ++k) data_one<KIND>(ry[k], ru[k], rw[k], delta, rv[k], ro[k], acc);
         store<V>(rv, v, i);
         if (om) store<V>(ro, om, i);
     }
     const long e = nv * V + gid;                         // the tail: fewer than V elements
     if (V > 1 && e < n) {
         float tv, to;
-        data_one(y[e], u[e], w ? w[e] : 1.f, delta, tv, to, acc);
+        data_one<KIND>(y[e], u[e], w ? w[e] : 1.f, delta, tv, to, acc);
         v[e] = tv;
         if (om) om[e] = to;
     }
@@ -113,7 +116,7 @@ __global__ __launch_bounds__(TPB) void robust_data_kernel(const float *__restric
 }
 
 // part [3][blocks]: sum w omega p0^2, sum w omega p0 p1, sum w omega p1^2
-template <int V>
+template <int V, int KIND>
 __global__ __launch_bounds__(TPB) void robust_curv_kernel(const float *__restrict__ y, const float *__restrict__ u,
                                                           const float *__restrict__ w, const float *__restrict__ p0,
                                                           const float *__restrict__ p1, long n, float delta,
@@ -129,10 +132,10 @@ __global__ __launch_bounds__(TPB) void robust_curv_kernel(const float *__restric
         load<V>(ra, p0, i);
         load<V>(rb, p1, i);
 #pragma unroll
-        for (int k = 0; k < V; ++k) curv_one(ry[k], ru[k], rw[k], ra[k], rb[k], delta, acc);
+        for (int k = 0; k < V; ++k) curv_one<KIND>(ry[k], ru[k], rw[k], ra[k], rb[k], delta, acc);
     }
     const long e = nv * V + gid;
-    if (V > 1 && e < n) curv_one(y[e], u[e], w ? w[e] : 1.f, p0[e], p1[e], delta, acc);
+    if (V > 1 && e < n) curv_one<KIND>(y[e], u[e], w ? w[e] : 1.f, p0[e], p1[e], delta, acc);
     block_sums_to<3>(acc, part);
 }
 
@@ -182,24 +185,35 @@ inline unsigned rob_grid(long n, int V) {
     default: hipLaunchKernelGGL(kernel<1>, dim3(grid), dim3(TPB), 0, s, __VA_ARGS__); break;                 \
     }
 
+// the same for a kernel<V, KIND>; evaluates to false on an unknown kind
+#define ROB_POT_DISPATCH(V, kind, kernel, grid, ...)                                                         \
+    pot_dispatch(kind, [&](auto K) {                                                                         \
+        constexpr int KIND = decltype(K)::value;                                                             \
+        switch (V) {                                                                                         \
+        case 4: hipLaunchKernelGGL((kernel<4, KIND>), dim3(grid), dim3(TPB), 0, s, __VA_ARGS__); break;      \
+        case 2: hipLaunchKernelGGL((kernel<2, KIND>), dim3(grid), dim3(TPB), 0, s, __VA_ARGS__); break;      \
+        default: hipLaunchKernelGGL((kernel<1, KIND>), dim3(grid), dim3(TPB), 0, s, __VA_ARGS__); break;     \
+        }                                                                                                    \
+    })
+
 size_t launch_robust_scratch_doubles() { return (size_t)3 * ROB_BLOCKS; }
 
 int launch_robust_data(hipStream_t s, const float *y, const float *u, const float *w, float *v, float *omega, long n, float delta,
-                       double *scratch, double *sums) {
+                       int kind, double *scratch, double *sums) {
     if (n < 1 || !(delta > 0.f)) return (int)hipErrorInvalidValue;
     const int V = vec_width({y, u, w, v, omega});
     const unsigned g = rob_grid(n, V);
-    ROB_DISPATCH(V, robust_data_kernel, g, y, u, w, v, omega, n, delta, scratch);
+    if (!ROB_POT_DISPATCH(V, kind, robust_data_kernel, g, y, u, w, v, omega, n, delta, scratch)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(parts_reduce_kernel, dim3(2), dim3(TPB), 0, s, scratch, (int)g, sums);
     return (int)hipGetLastError();
 }
 
 int launch_robust_curv(hipStream_t s, const float *y, const float *u, const float *w, const float *p0, const float *p1, long n,
-                       float delta, double *scratch, double *sums) {
+                       float delta, int kind, double *scratch, double *sums) {
     if (n < 1 || !(delta > 0.f)) return (int)hipErrorInvalidValue;
     const int V = vec_width({y, u, w, p0, p1});
     const unsigned g = rob_grid(n, V);
-    ROB_DISPATCH(V, robust_curv_kernel, g, y, u, w, p0, p1, n, delta, scratch);
+    if (!ROB_POT_DISPATCH(V, kind, robust_curv_kernel, g, y, u, w, p0, p1, n, delta, scratch)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(parts_reduce_kernel, dim3(3), dim3(TPB), 0, s, scratch, (int)g, sums);
     return (int)hipGetLastError();
 }

@@ -20,6 +20,7 @@ import numpy as np
 
 from . import instru
 from .models import spectroSigRLSCT
+from .potentials import kind_name, need_delta
 from .weights import check_data_weights, weighted_sq_residual, weights_from_data  # noqa: F401  (weights_from_data: public here)
 
 
@@ -34,7 +35,7 @@ class OptimizeResult:
 
 class QuadCriterion_MRS:
     def __init__(self, mu_spectro, y_spectro, model_spectro, mu_reg, printing=False, gradient="separated", delta=None, weights=None,
-                 data_delta=None):
+                 data_delta=None, potential="huber", data_potential="huber"):
         """``gradient="joint"`` regularises with the Laplacian of ``Difference_Operator_Joint`` (fusion_CT.py:45-62); udft's
         ``laplacian(2)`` is absent from the reference tree, the 3 x 3 kernel [[0,-1,0],[-1,4,-1],[0,-1,0]] is restated: parity
         unpinned for that option (the operator is checked against the oracle's Fourier-domain form of the same kernel).
@@ -50,7 +51,13 @@ class QuadCriterion_MRS:
         weights the model holds, if any, are used by the solve and by ``get_crit_val``.
         ``data_delta`` (not in fusion_CT.py; qmm.Objective with a Huber loss): the robust data term mu sum_i phi(t_i),
         t_i = sqrt(w_i) (y_i - (A x)_i), phi the Huber potential of threshold ``data_delta`` (include/surfh_amd.h:
-        surfh_mmmg_robust); like ``delta`` it needs ``run_method("mmmg")`` and the separated differences.  ``None``: quadratic."""
+        surfh_mmmg_robust); like ``delta`` it needs ``run_method("mmmg")`` and the separated differences.  ``None``: quadratic.
+        ``potential`` / ``data_potential`` (Hebert-Leahy is what fusion_CT.py imports beside Huber): the potential under ``delta``
+        and under ``data_delta``, "huber" (the default), "hyperbolic" or "hebert_leahy" (``surfh_amd.potentials``); another one
+        than Huber needs its threshold."""
+        self.potential, self.data_potential = kind_name(potential), kind_name(data_potential)
+        need_delta(potential, delta, "delta")
+        need_delta(data_potential, data_delta, "data_delta")
         assert isinstance(mu_reg, (float, int, list, np.ndarray))
         if gradient not in ("separated", "joint"):
             raise ValueError(f"gradient must be 'separated' or 'joint', not {gradient!r}")
@@ -149,6 +156,10 @@ class QuadCriterion_MRS:
                 kw["weights"] = self.weights           # installed for the solve, the model's own state put back afterwards
             if self.data_delta is not None:
                 kw["data_delta"] = self.data_delta
+            if self.potential != "huber":
+                kw["potential"] = self.potential
+            if self.data_potential != "huber":
+                kw["data_potential"] = self.data_potential
             x, gn, nit = solver(self.y_spectro, mu=self.mu_spectro, mu_reg=self.mu_reg, x0=init,
                                 max_iter=maximum_iterations, tol=tolerance, callback=callback, **kw)
         finally:
@@ -169,12 +180,13 @@ class QuadCriterion_MRS:
         x_hat = np.asarray(x_hat).reshape(self.shape_of_output)
         w = self.weights if self.weights is not None else getattr(self.model_spectro, "data_weights", None)
         if self.data_delta is not None:
-            data = 2 * self.mu_spectro * robust_data_value(self.y_spectro, self.model_spectro.forward(x_hat), w, self.data_delta)
+            data = 2 * self.mu_spectro * robust_data_value(self.y_spectro, self.model_spectro.forward(x_hat), w, self.data_delta,
+                                                              self.data_potential)
         else:
             data = self.mu_spectro * weighted_sq_residual(self.y_spectro, self.model_spectro.forward(x_hat), w)
         if self.delta is not None:
-            return data / 2 + self.mu_reg * (huber_phi(np.roll(x_hat, 1, axis=1) - x_hat, self.delta).sum() +
-                                             huber_phi(np.roll(x_hat, 1, axis=2) - x_hat, self.delta).sum())
+            return data / 2 + self.mu_reg * (_phi(np.roll(x_hat, 1, axis=1) - x_hat, self.delta, self.potential).sum() +
+                                             _phi(np.roll(x_hat, 1, axis=2) - x_hat, self.delta, self.potential).sum())
         if self.gradient == "joint":                 # |D x|^2, D = circular 3 x 3 Laplacian centred on the pixel (:254-255, :45-54)
             dx = 4 * x_hat - np.roll(x_hat, 1, 1) - np.roll(x_hat, -1, 1) - np.roll(x_hat, 1, 2) - np.roll(x_hat, -1, 2)
             return (data + self.mu_reg * np.sum(dx ** 2)) / 2
@@ -183,14 +195,23 @@ class QuadCriterion_MRS:
         return (data + self.mu_reg * np.sum(dr ** 2 + dc ** 2)) / 2
 
 
-def robust_data_value(y, ax, weights, data_delta):
-    """``sum phi(sqrt(w) (y - A x))`` in float64 over the samples with w > 0 (``weights=None``: all, w = 1)."""
+def robust_data_value(y, ax, weights, data_delta, potential="huber"):
+    """``sum phi(sqrt(w) (y - A x))`` in float64 over the samples with w > 0 (``weights=None``: all, w = 1); ``potential``: phi,
+    "huber" by default (``surfh_amd.potentials``)."""
     y, ax = np.asarray(y, dtype=np.float64).ravel(), np.asarray(ax, dtype=np.float64).ravel()
     if weights is None:
-        return float(huber_phi(y - ax, data_delta).sum())
+        return float(_phi(y - ax, data_delta, potential).sum())
     w = np.asarray(weights, dtype=np.float64).ravel()
     keep = w > 0
-    return float(huber_phi(np.sqrt(w[keep]) * (y[keep] - ax[keep]), data_delta).sum())
+    return float(_phi(np.sqrt(w[keep]) * (y[keep] - ax[keep]), data_delta, potential).sum())
+
+
+def _phi(u, delta, potential):
+    """phi of the named potential; Huber through ``huber_phi`` below."""
+    if kind_name(potential) == "huber":
+        return huber_phi(u, delta)
+    from .potentials import phi
+    return phi(u, delta, potential)
 
 
 def huber_phi(u, delta):

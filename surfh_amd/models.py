@@ -21,6 +21,7 @@ import numpy as np
 from . import _lib, instru
 from .geometry import ChannelGeometry
 from .linop import LinOp
+from . import potentials as _pot
 from .weights import DataWeights
 
 
@@ -83,7 +84,7 @@ class Channel(ChannelGeometry):
         return op.adjoint_ref(np.ascontiguousarray(s.transpose(1, 0, 2)))
 
 
-class spectroSigRLSCT(DataWeights, LinOp):
+class spectroSigRLSCT(DataWeights, _pot.Potentials, LinOp):
     huber_prior_value = None            # prior value of the last mmmg(delta=...) result (set by mmmg)
     huber_prior_values = None           # (spatial, spectral) prior values of the last mmmg_vox result
     robust_weights = None               # omega(t) [osize] of the last mmmg / mmmg_vox result under data_delta (else None)
@@ -337,7 +338,7 @@ class spectroSigRLSCT(DataWeights, LinOp):
             return _lib.solve(self, self._L.surfh_cg_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
 
     def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, delta=None, weights=None,
-             data_delta=None):
+             data_delta=None, potential="huber", data_potential="huber"):
         """Device-resident 3MG (qmm.mmmg restated for quadratic objectives; the reference's ``method='mmmg'``,
         fusion_CT.py:194-198).  Same arguments as ``cg``; ``grad_norm`` holds |grad| (not squared) of every iterate.
 
@@ -353,7 +354,18 @@ class spectroSigRLSCT(DataWeights, LinOp):
         quadratically.  The priors stay what ``delta`` says (``None``: quadratic, on the separated differences).  Afterwards
         ``self.robust_weights`` holds ``omega(t) = phi'(t) / t`` ``[osize]`` of the returned iterate (1 inside the threshold, below 1
         beyond, 0 where the weight is 0), ``self.robust_data_value`` ``sum phi(t)`` and ``self.robust_n_beyond`` the number of
-        samples beyond; all three are None after any other run.  ``None`` runs exactly the solvers above."""
+        samples beyond; all three are None after any other run.  ``None`` runs exactly the solvers above.
+
+        ``potential`` / ``data_potential``: the potential of the priors under ``delta`` and of the data term under ``data_delta``
+        for this call -- "huber" (the default), "hyperbolic" or "hebert_leahy" (``surfh_amd.potentials``); the plan's slots are put
+        back afterwards.  ``ValueError`` for another potential than Huber without its threshold.  ``robust_n_beyond`` counts the
+        samples past the knee, |t| > data_delta, whatever the potential."""
+        _pot.need_delta(potential, delta, "delta")
+        _pot.need_delta(data_potential, data_delta, "data_delta")
+        with _pot.installed(self, spatial=potential, data=data_potential):
+            return self._mmmg(data, mu, mu_reg, x0, max_iter, tol, refresh, callback, delta, weights, data_delta)
+
+    def _mmmg(self, data, mu, mu_reg, x0, max_iter, tol, refresh, callback, delta, weights, data_delta):
         self.huber_prior_value = None
         self.robust_weights = self.robust_data_value = self.robust_n_beyond = None
         if data_delta is not None and self.get_prior() != "separated":
@@ -400,7 +412,8 @@ class spectroSigRLSCT(DataWeights, LinOp):
 
     # ---- the cube itself under Huber priors (models without templates) -----------------------
     def mmmg_vox(self, data, mu=1.0, spat_reg=1.0, spat_delta=1.0, spec_reg=1.0, spec_delta=1.0, x0=None, max_iter=10, tol=1e-12,
-                 refresh=50, callback=None, weights=None, data_delta=None):
+                 refresh=50, callback=None, weights=None, data_delta=None, spat_potential="huber", spec_potential="huber",
+                 data_potential="huber"):
         """3MG on the cube ``[Lc, Na, Nb]`` with Huber priors on its row, column and wavelength differences (the reference's
         vox_reconstruction, algorithms.py:27-71; include/surfh_amd.h: surfh_mmmg_huber_vox):
 
@@ -413,7 +426,16 @@ class spectroSigRLSCT(DataWeights, LinOp):
         weight of 0 switches it off.  qmm and aljabr are not available to pin the restatement or the border conventions.
         ``weights``: data weights for this solve, as in ``cg`` (the data term is then ``mu (y - A x)^T W (y - A x) / 2``).
         ``data_delta``: the robust data term of ``mmmg`` (include/surfh_amd.h: surfh_mmmg_robust_vox), with the same diagnostics
-        left in ``self.robust_weights``, ``self.robust_data_value`` and ``self.robust_n_beyond``; ``None``: the solver above."""
+        left in ``self.robust_weights``, ``self.robust_data_value`` and ``self.robust_n_beyond``; ``None``: the solver above.
+        ``spat_potential`` / ``spec_potential`` / ``data_potential``: the potential of the in-plane families, of the wavelength
+        family and of the data term for this call, as ``mmmg``'s (a data potential other than Huber needs ``data_delta``)."""
+        _pot.need_delta(data_potential, data_delta, "data_delta")
+        with _pot.installed(self, spatial=spat_potential, spectral=spec_potential, data=data_potential):
+            return self._mmmg_vox(data, mu, spat_reg, spat_delta, spec_reg, spec_delta, x0, max_iter, tol, refresh, callback, weights,
+                                  data_delta)
+
+    def _mmmg_vox(self, data, mu, spat_reg, spat_delta, spec_reg, spec_delta, x0, max_iter, tol, refresh, callback, weights,
+                  data_delta):
         self.huber_prior_values = None
         self.robust_weights = self.robust_data_value = self.robust_n_beyond = None
         if self.lmm:

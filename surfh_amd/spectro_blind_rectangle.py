@@ -21,6 +21,7 @@ import numpy as np
 
 from . import instru
 from .blurred2d import Blurred2D
+from .potentials import kind_name, need_delta, phi as potential_phi
 from .weights import check_data_weights, weighted_sq_residual
 
 
@@ -75,15 +76,20 @@ class QuadCriterion_MRS_2D:
     """The reference's 2-D criterion (surfh/Simulation/criterion_2D.py:66-250): same constructor, ``run_method('lcg' | 'mmmg')``
     and ``get_crit_val``, on ``MRSBlurred`` (one image, or a stack of independent images solved together)."""
 
-    def __init__(self, mu_spectro, y_spectro, model_spectro, mu_reg, printing=False, gradient="separated", weights=None, delta=None):
+    def __init__(self, mu_spectro, y_spectro, model_spectro, mu_reg, printing=False, gradient="separated", weights=None, delta=None,
+                 potential="huber"):
         """``weights`` (not in criterion_2D.py): per-sample data weights in the layout of ``y_spectro``, data term
         mu (y - A x)^T diag(w) (y - A x) / 2 (``MRSBlurred.set_data_weights``); data of weight 0 are ignored whatever they hold.
         ``None``: the weights the model holds, if any.
         ``delta`` (criterion_2D.py imports qmm's ``Huber`` beside ``mmmg`` and never builds it): Huber potentials of threshold
         ``delta`` on the separated differences, criterion mu |y - A x|^2 / 2 + mu_reg sum_k sum phi(D_k x) per plane
         (include/surfh_amd.h: surfh_mmmg_huber_planes), as ``fusion.QuadCriterion_MRS``; only a method other than ``"lcg"``
-        minimises it.  ``None``: the quadratic criterion."""
+        minimises it.  ``None``: the quadratic criterion.
+        ``potential``: the potential under ``delta``, "huber" (the default), "hyperbolic" or "hebert_leahy"
+        (``surfh_amd.potentials``); another one than Huber needs ``delta``."""
         assert isinstance(mu_reg, (float, int, list, np.ndarray))
+        self.potential = kind_name(potential)
+        need_delta(potential, delta, "delta")
         if delta is not None:
             if gradient != "separated":
                 raise ValueError("the Huber prior (delta) acts on the separated differences: gradient must be 'separated'")
@@ -139,6 +145,8 @@ class QuadCriterion_MRS_2D:
             callback = None
         t0 = time.time()
         kw = {} if self.delta is None else {"delta": self.delta}
+        if self.potential != "huber":
+            kw["potential"] = self.potential
         if self.weights is not None:
             kw["weights"] = self.weights
         x, gn, nit = solver(self.y_spectro, mu=self.mu_spectro, mu_reg=self.mu_reg, x0=init,
@@ -153,7 +161,7 @@ class QuadCriterion_MRS_2D:
 
     def get_crit_val(self, x_hat):
         """(mu |y - A x|^2 + mu_reg (|Dr x|^2 + |Dc x|^2)) / 2   (criterion_2D.py:252-275), summed over the planes; with ``delta``
-        mu |y - A x|^2 / 2 + mu_reg sum phi(Dr x) + phi(Dc x), phi the Huber potential.  Under data weights (this criterion's,
+        mu |y - A x|^2 / 2 + mu_reg sum phi(Dr x) + phi(Dc x), phi the criterion's potential (Huber by default).  Under data weights (this criterion's,
         else the model's) |y - A x|^2 is sum w (y - A x)^2 over the samples with w > 0."""
         x_hat = np.asarray(x_hat).reshape(self.shape_of_output)
         w = self.weights if self.weights is not None else getattr(self.model_spectro, "data_weights", None)
@@ -161,6 +169,6 @@ class QuadCriterion_MRS_2D:
         dr = np.roll(x_hat, 1, axis=-2) - x_hat
         dc = np.roll(x_hat, 1, axis=-1) - x_hat
         if self.delta is not None:
-            from .fusion import huber_phi
-            return data / 2 + self.mu_reg * (huber_phi(dr, self.delta).sum() + huber_phi(dc, self.delta).sum())
+            return data / 2 + self.mu_reg * (potential_phi(dr, self.delta, self.potential).sum() +
+                                             potential_phi(dc, self.delta, self.potential).sum())
         return (data + self.mu_reg * np.sum(dr ** 2 + dc ** 2)) / 2
