@@ -164,7 +164,7 @@ int surfh_cg_cb(surfh_plan *plan, const float *y, double mu, double mu_reg, cons
  * for the same quadratic criterion: every iteration minimises it exactly over span{-gradient, previous move}
  * (the quadratic majorant of a quadratic objective is the objective).  The 2x2 subspace system is solved in a basis
  * [d, move] with d Q-orthogonal to the previous move and the operator applied to d -- the same iterates as qmm's
- * [-gradient, move] form in exact arithmetic, but as accurate as CG in fp32 (see plan.hip).  One normal-operator
+ * [-gradient, move] form in exact arithmetic, but as accurate as CG in fp32 (see plan_solvers.hip).  One normal-operator
  * application per iteration; the gradient is carried by linearity and recomputed every `refresh` iterations.
  * grad_norm receives |gradient| of x0 and of every iterate (nit+1 doubles, capacity max_iter+1); stops when it falls
  * below size*tol.  callback as surfh_cg_cb. */

@@ -1,0 +1,210 @@
+// Host side of the C ABI (include/surfh_amd.h), diagnostics: the profiler's read-out, the debug accessors, and the self-tests of
+// the K-step classifier, the 2x2 step solve and the GEMMs.  Depends on the other three files; nothing depends on it.
+// Plan struct and data layout: plan_internal.h.
+#include "plan_internal.h"
+#include "mm_step.h"
+
+extern "C" {
+
+// ---- instrumentation ------------------------------------------------------------------------
+int surfh_profile_enable(surfh_plan *p, int32_t on) {
+    if (!p) return fail("null plan");
+    p->prof = on != 0;
+    return 0;
+}
+int surfh_profile_filter(surfh_plan *p, const char *prefix) {
+    if (!p) return fail("null plan");
+    p->prof_filter = prefix ? prefix : "";
+    return 0;
+}
+int32_t surfh_profile_count(surfh_plan *p) {
+    if (!p) return -1;
+    hipSetDevice(p->dev);
+    prof_collect(p);
+    return (int32_t)p->acc_names.size();
+}
+int surfh_profile_get(surfh_plan *p, int32_t i, const char **name, int64_t *launches, double *ms) {
+    if (!p || i < 0 || i >= (int32_t)p->acc_names.size()) return fail("bad profile index");
+    auto &e = p->acc[p->acc_names[i]];
+    *name = p->acc_names[i].c_str();
+    *launches = e.first;
+    *ms = e.second;
+    return 0;
+}
+int surfh_profile_reset(surfh_plan *p) {
+    if (!p) return fail("null plan");
+    hipSetDevice(p->dev);
+    prof_collect(p);
+    p->acc.clear();
+    p->acc_names.clear();
+    return 0;
+}
+
+static int resolve(surfh_plan *p, const char *which, const float **ptr, int64_t dims[4]) {
+    std::string w(which ? which : "");
+    dims[0] = dims[1] = dims[2] = dims[3] = 1;
+    *ptr = nullptr;
+    if (w == "blurred" || w == "gcube") {          // [beta][alpha][lambda]; the exact adjoint's accumulator may be its own buffer
+        *ptr = (w == "gcube" && p->gcube) ? p->gcube : p->cube; dims[0] = p->NBP; dims[1] = p->NAP; dims[2] = p->LP;
+    } else if (w == "spec") {                       // [2][k_alpha][k_beta][lambda]; h2 plans: [k_alpha][k_beta][lambda][2]
+        *ptr = p->spec;
+        if (p->ilv) { dims[0] = p->KAP; dims[1] = p->KBP; dims[2] = p->LP; dims[3] = 2; }
+        else { dims[0] = 2; dims[1] = p->KAP; dims[2] = p->KBP; dims[3] = p->LP; }
+    } else if (w == "mhat" && p->T > 0) {
+        *ptr = p->mhat; dims[0] = p->T; dims[1] = 2; dims[2] = p->KAP; dims[3] = p->KBP;
+    } else if (w.rfind("xs:", 0) == 0 || w.rfind("xsinfo:", 0) == 0) {
+        const bool info = w[2] == 'i';
+        const int c = atoi(w.c_str() + (info ? 7 : 3));
+        if (c < 0 || c >= (int)p->ch.size()) return fail("bad channel index");
+        if (info) {                                 // (LinP, first valid lambda column, n_beta_slit, Lin)
+            dims[0] = p->ch[c].LinP; dims[1] = p->ch[c].shift; dims[2] = p->ch[c].nbs; dims[3] = p->ch[c].Lin;
+        } else {                                    // [(p,s,a)][b'][LinP]
+            Channel &ch = p->ch[c];
+            if (ch.Xs16) {     // the forward operand lives as block-scaled fp16 pieces: rebuilt in fp32 for inspection
+                if (launch_dequant_f16x2(p->stream, ch.Xs16, (long)ch.NP * ch.K, ch.bscale, ch.Xs, ch.NP, ch.K, ch.LinP,
+                                         (ch.LinP + 1023) / 1024))
+                    return fail("dequant launch failed");
+                if (hipStreamSynchronize(p->stream) != hipSuccess) return fail("dequant failed");
+            }
+            *ptr = p->ch[c].Xs; dims[0] = p->ch[c].NP; dims[1] = p->ch[c].bsum ? 1 : p->ch[c].nbs; dims[2] = p->ch[c].LinP;
+        }
+    } else if (w == "range") {         // cube columns / rows the channels' tables touch: [a_lo, a_hi) x [b_lo, b_hi)
+        dims[0] = p->a_lo; dims[1] = p->a_hi; dims[2] = p->b_lo; dims[3] = p->b_hi;
+    } else if (w == "otf") {           // super-tiles (k_beta, 128 wavelengths) inside the OTF's support / all of them
+        dims[0] = p->otf_vlist ? p->otf_nvalid : (long)(p->Nb / 2 + 1) * (p->LP / 128); dims[1] = (long)(p->Nb / 2 + 1) * (p->LP / 128);
+    } else if (w == "ksteps") {        // (tile, K step) pairs of the spectral-blur GEMMs: near / far of the forward, near / far of the adjoint
+        for (auto &c : p->ch)
+            for (int i = 0; i < 4; ++i) dims[i] += c.ksteps[i];
+        for (int i = 0; i < 4; ++i) dims[i] -= 1;
+    } else if (w == "info") {
+        dims[0] = p->lo; dims[1] = p->hi; dims[2] = p->Lown; dims[3] = (int64_t)p->segs.size();
+    } else {
+        return fail("unknown debug buffer '%s'", w.c_str());
+    }
+    return 0;
+}
+
+int surfh_debug_dims(surfh_plan *p, const char *which, int64_t dims[4]) {
+    if (!p) return fail("null plan");
+    const float *ptr;
+    return resolve(p, which, &ptr, dims);
+}
+
+int64_t surfh_debug_copy(surfh_plan *p, const char *which, float *out, int64_t cap) {
+    if (!p || !out) return -1;
+    const float *ptr = nullptr;
+    int64_t d[4];
+    if (resolve(p, which, &ptr, d) || !ptr) return -1;
+    const int64_t n = d[0] * d[1] * d[2] * d[3];
+    if (n > cap) {
+        fail("capacity %lld < %lld", (long long)cap, (long long)n);
+        return -1;
+    }
+    hipSetDevice(p->dev);
+    hipStreamSynchronize(p->stream);
+    if (hipMemcpy(out, ptr, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return n;
+}
+
+int32_t surfh_klist_classify(const float *B, int32_t n, int32_t k, int64_t ldb, int32_t perm_p, int32_t perm_lin, int32_t *records,
+                             int64_t capacity) {
+    if (!B || !records || n < 1 || k < 32 || k % 32 || ldb < k) return -fail("surfh_klist_classify: bad arguments");
+    if (perm_p && ((perm_p != 1 && perm_p != 2 && perm_p != 4 && perm_p != 8) || perm_lin < 1 || perm_lin % (256 / perm_p) || n % perm_lin))
+        return -fail("surfh_klist_classify: bad tile shape");
+    std::vector<int> kl;
+    int stride = 0;
+    long nn = 0, nf = 0;
+    build_klist(B, n, k, ldb, 0, 0, 1.0 / 256, 1.0 / 1024, &kl, &stride, &nn, &nf, perm_p, perm_lin);
+    if ((int64_t)kl.size() > capacity) return -fail("surfh_klist_classify: capacity too small");
+    std::memcpy(records, kl.data(), kl.size() * sizeof(int));
+    return (int32_t)(kl.size() / (size_t)stride);
+}
+
+int surfh_mm_step2(double dBd, double dBm, double mBm, double dg, double mg, double step[2]) {
+    if (!step) return fail("null argument");
+    mm_step2(dBd, dBm, mBm, dg, mg, &step[0], &step[1]);
+    return 0;
+}
+
+static long g_selftest_ksteps[2] = {0, 0};
+int surfh_gemm_selftest_ksteps(int64_t near_far[2]) {
+    near_far[0] = g_selftest_ksteps[0]; near_far[1] = g_selftest_ksteps[1];
+    return 0;
+}
+
+int surfh_gemm_selftest(int32_t device, int32_t M, int32_t N, int32_t K, int32_t split_k, const float *A,
+                        const float *B, float *C) {
+    HIP_OK(hipSetDevice(device));
+    float *dA = nullptr, *dB = nullptr, *dC = nullptr;
+    const int sk = std::max(1, (int)split_k);
+    HIP_OK(hipMalloc((void **)&dA, (size_t)M * K * 4));
+    HIP_OK(hipMalloc((void **)&dB, (size_t)K * N * 4));
+    HIP_OK(hipMalloc((void **)&dC, (size_t)sk * M * N * 4));
+    HIP_OK(hipMemcpy(dA, A, (size_t)M * K * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(dB, B, (size_t)K * N * 4, hipMemcpyHostToDevice));
+    GemmArgs g;
+    g.A0 = dA; g.lda = K; g.B0 = dB; g.ldb = N; g.C = dC; g.ldc = N;
+    g.M = M; g.N = N; g.K = K; g.splitK = sk; g.sCsplit = (long)M * N;
+    int rc;
+    const char *mode = getenv("SURFH_SELFTEST_F16X2");
+    if (mode && (mode[0] == '1' || mode[0] == '2')) {
+        // two-piece fp16 kernel, NT form: B is handed over as [K][N]; transpose it on the host into [N][K]
+        std::vector<float> bt((size_t)N * K);
+        for (int k = 0; k < K; ++k)
+            for (int n = 0; n < N; ++n) bt[(size_t)n * K + k] = B[(size_t)k * N + n];
+        HIP_OK(hipMemcpy(dB, bt.data(), bt.size() * 4, hipMemcpyHostToDevice));
+        g.ldb = K;
+        unsigned short *dB16 = nullptr, *dA16 = nullptr;
+        unsigned *dmax = nullptr;
+        float amB = 0.f;
+        for (float v : bt) amB = std::max(amB, std::fabs(v));
+        std::vector<unsigned> rows((size_t)M, 0u);           // max |A[m][:]| as bit patterns
+        for (int m = 0; m < M; ++m) {
+            float am = 0.f;
+            for (int k = 0; k < K; ++k) am = std::max(am, std::fabs(A[(size_t)m * K + k]));
+            memcpy(&rows[m], &am, 4);
+        }
+        HIP_OK(hipMalloc((void **)&dB16, bt.size() * 4));
+        HIP_OK(hipMalloc((void **)&dmax, rows.size() * sizeof(unsigned)));
+        HIP_OK(hipMalloc((void **)&dA16, (size_t)M * K * 4));
+        HIP_OK(hipMemcpy(dmax, rows.data(), rows.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+        g.sB16 = gemm_f16x2_scale(amB); g.B16 = dB16; g.pB16 = (long)bt.size(); g.amax = dmax;
+        rc = launch_split2h(nullptr, dB, dB16, (long)bt.size(), (long)bt.size(), g.sB16);
+        if (rc == 0) rc = launch_split_rows2h(nullptr, dA, dmax, dA16, M, K, (long)M * K);
+        g.A3 = dA16; g.pA3 = (long)M * K;
+        int *dkl = nullptr;
+        g_selftest_ksteps[0] = g_selftest_ksteps[1] = 0;
+        if (mode[0] == '2') {      // with K-step lists, classes and tolerances as at plan creation
+            std::vector<int> kl;
+            // SURFH_SELFTEST_PERM=<rows per column of B>: tiles of 64 rows of four neighbouring columns, as the adjoint spectral-blur GEMM
+            const char *ep = getenv("SURFH_SELFTEST_PERM");
+            const int lin = ep ? atoi(ep) : 0;
+            if (lin > 0) { g.permP = 4; g.permLin = lin; }
+            build_klist(bt.data(), N, K, K, 0, 0, 1.0 / 256, 1.0 / 1024, &kl, &g.klistStride, &g_selftest_ksteps[0], &g_selftest_ksteps[1], g.permP,
+                        g.permLin);
+            if (dev_upload(&dkl, kl)) return 1;
+            g.klist = dkl;
+        }
+        if (rc == 0) rc = launch_gemm_nt_f16x2_cc(nullptr, g);
+        if (rc == 0) rc = (int)hipDeviceSynchronize();
+        hipFree(dkl);
+        hipFree(dB16);
+        hipFree(dmax);
+        hipFree(dA16);
+    } else {
+        rc = launch_gemm_f32(nullptr, g);
+    }
+    if (rc == 0) rc = (int)hipDeviceSynchronize();
+    std::vector<float> h((size_t)sk * M * N);
+    if (rc == 0) rc = (int)hipMemcpy(h.data(), dC, h.size() * 4, hipMemcpyDeviceToHost);
+    hipFree(dA); hipFree(dB); hipFree(dC);
+    if (rc) return fail("gemm selftest failed: %s", hipGetErrorString((hipError_t)rc));
+    for (size_t i = 0; i < (size_t)M * N; ++i) {
+        float s = 0.f;
+        for (int k = 0; k < sk; ++k) s += h[(size_t)k * M * N + i];
+        C[i] = s;
+    }
+    return 0;
+}
+
+}  // extern "C"

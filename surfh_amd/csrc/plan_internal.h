@@ -1,0 +1,303 @@
+// Internal header of the host side of the C ABI (include/surfh_amd.h), shared by plan.hip (plan build and plan state),
+// plan_ops.hip (operators), plan_solvers.hip (solvers) and plan_diag.hip (diagnostics).  The rule of the split: solvers call the
+// operators, operators read the plan, plan build knows neither operators nor solvers, diagnostics depend on everything and
+// nothing depends on them -- so this header declares only the helpers that cross a file boundary in that direction.
+// Everything shared lives in namespace surfh_impl, which has hidden visibility: the shared object exports the C ABI and nothing else.
+//
+// Data layout: WAVELENGTH IS THE INNERMOST AXIS of every large device array (lambda is the batch
+// dimension of every stage of the reference, so making it contiguous turns every kernel into
+// coalesced streaming and every dense stage into one large GEMM):
+//   spectra  sotf, spec      [2 (re,im)][KAP][KBP][LP]
+//   cube     blurred / g     [NBP (beta)][NAP (alpha)][LP]
+//   operand  Xs (per channel)[NP = (p,s,a)][n_beta_slit][LinP]      K index = (b', lambda)
+// LP = owned planes padded to 128, all other dims padded to 64, padding is zero.
+//
+// Pipeline (per plan = per GPU), reference citations relative to the reference's source tree:
+//   forward  (spectroModel.py:158-170, spectroModelChannel.py:215-231)
+//     maps --pad--> rfft2 (2 small GEMMs) --> mhat[T][2][KAP][KBP]
+//     spec[k][l] = sotf[k][l] * sum_t tpl[t,l] mhat[t][k]             (T and C fused, Fourier domain)
+//     blurred    = irfft2(spec): two GEMMs with the DFT matrices as the A operand
+//     per channel:  Xs[(p,s,a)][b'][l] = G * blurred                  (S + box-sum + L + decimation, row gather)
+//                   y^T[(p,s,a)][l'] = Xs * W^T                       (R + beta-sum, one GEMM, split-K)
+//   adjoint  (spectroModel.py:173-185, spectroModelChannel.py:234-264): the transposes, in reverse.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <array>
+#include <cfloat>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <functional>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/surfh_amd.h"
+#include "dft_h2.h"
+#include "dft_ct.h"
+#include "gemm_f32.h"
+#include "kernels.h"
+
+namespace surfh_impl __attribute__((visibility("hidden"))) {
+
+// records the message surfh_last_error() returns and returns 1; defined once, in plan.hip, beside the thread's error string
+int fail(const char *fmt, ...);
+
+// a boolean SURFH_* switch: `dflt` when the variable is unset or empty; a default-on switch goes off only with a leading '0',
+// a default-off switch goes on only with a leading '1'
+inline bool env_on(const char *name, bool dflt) {
+    const char *e = getenv(name);
+    return dflt ? !(e && e[0] == '0') : (e && e[0] == '1');
+}
+
+#define HIP_OK(expr)                                                                              \
+    do {                                                                                          \
+        hipError_t e_ = (expr);                                                                   \
+        if (e_ != hipSuccess) return fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+#define LAUNCH_OK(expr)                                                                           \
+    do {                                                                                          \
+        int e_ = (expr);                                                                          \
+        if (e_ != 0) return fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString((hipError_t)e_), __FILE__, __LINE__); \
+    } while (0)
+
+inline int pad64(int n) { return (n + 63) / 64 * 64; }
+
+// host-side sparse rows: (source index, weight) lists + one destination per row
+struct HostEll {
+    std::vector<std::vector<std::pair<int64_t, float>>> rows;
+    std::vector<int64_t> dst;
+};
+
+struct DevEll {
+    EllTable t;
+    int32_t *cnt = nullptr;
+    int64_t *col = nullptr, *dst = nullptr;
+    float *val = nullptr;
+    uint32_t *rmw = nullptr;            // scatter tables: chunks of a row that need read-modify-write (EllTable::rmw)
+    int2 *rng = nullptr, *g_rng = nullptr;   // ... or the exact wavelength ranges (EllTable::rng, GroupTable::rng)
+    std::vector<int64_t> host_dst;      // kept for the scatter tables until the plan is complete
+    // the same table with its rows grouped SCATTER_G at a time (GroupTable)
+    GroupTable g;
+    int32_t *g_cnt = nullptr;
+    int64_t *g_col = nullptr, *g_dst = nullptr;
+    float *g_val = nullptr;
+    uint32_t *g_rmw = nullptr;
+};
+
+struct Channel {
+    int ws0 = 0, ws1 = 0, Lin = 0, P = 0, S = 0, Ldet = 0, aout = 0, srf = 0, na = 0, nb = 0, alpha0 = 0, nas = 0,
+        nbs = 0;
+    int ws0a = 0;      // window start relative to the plan's first plane, rounded down to a multiple of 4
+    int LinA = 0;      // planes from ws0a to the window end
+    int LinP = 0;      // LinA padded to 64
+    int shift = 0;     // (ws0 - lo) - ws0a
+    int nlam = 0;      // LinA rounded up to 4: wavelengths the gather kernels process
+    int K = 0, NP = 0, LdetP = 0, splitK = 1;
+    long yoff = 0, ysize = 0;
+    float *W = nullptr, *Wt = nullptr, *Xs = nullptr, *Cpart = nullptr, *ymat = nullptr;
+    unsigned short *W16 = nullptr, *Wt16 = nullptr; // ... or into their two fp16 pieces [2][rows][cols] of W / sW (gemm_cc16.hip)
+    unsigned short *Xs16 = nullptr, *ymat16 = nullptr;   // the data operands as fp16 pieces (all-consumer kernel, gemm_cc16.hip)
+    float *bscale = nullptr;                        // Xs16's scales, one per (row, K segment): [nbs * ceil(LinP/1024)][NP]
+    float sW = 1.f;
+    // K-step classes of the two GEMMs (gemm_cc16.hip, build_klist below): per 256-row tile of W16 / Wt16 the steps that keep
+    // all three products and the steps kept as h*h only; ksteps = (near, far) of the forward, (near, far) of the adjoint
+    int *klF = nullptr, *klA = nullptr;
+    int klFs = 0, klAs = 0;
+    int permA = 0;                      // adjoint GEMM: a tile takes 256 / permA wavelengths of each of permA neighbouring beta columns (0: 256 consecutive rows)
+    long ksteps[4] = {0, 0, 0, 0};
+    unsigned *amax = nullptr;                       // [2][NP] max |row| of the data operands: Xs (forward), ymat (adjoint)
+    unsigned *pmax = nullptr;                       // per-wave maxima of the kernel that wrote the operand (reduced into amax)
+    DevEll fwd, adjT, adjRef;
+    HostEll adjT_host;                  // kept until the grouped scatter table is built (plan creation)
+    bool has_ref = false;
+    bool bsum = false;   // no spectral blur: y[l][(p,s,a)] = sum over the slit's beta columns (MRSBlurred)
+    float *wmat = nullptr;              // data weights of the channel in ymat's layout [NP][LdetP], padding zero (channels with ymat16; surfh_set_data_weights)
+};
+
+struct ProfRec {
+    const char *name;
+    hipEvent_t a, b;
+};
+
+}  // namespace surfh_impl
+
+using namespace surfh_impl;      // struct surfh_plan is the C ABI's opaque type and stays at global scope
+
+struct surfh_plan {
+    int dev = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    // second stream: the spectral-blur GEMMs run here while the gather / scatter of the neighbouring channel runs on
+    // `stream` (different units: matrix cores vs L2 bandwidth, and the GEMM leaves registers for them on every SIMD)
+    hipStream_t stream2 = nullptr;
+    bool overlap = false;
+    std::vector<hipEvent_t> sync_ev;             // dependency events between the two streams (no timing)
+    size_t sync_next = 0;
+    int Na = 0, Nb = 0, Lc = 0, T = 0, NAP = 0, NBP = 0, KAP = 0, KBP = 0;
+    long PL = 0, PLc = 0;
+    int lo = 0, hi = 0, Lown = 0, LP = 0;
+    // owned cube planes = union of the channels' windows, stored compactly: segment = (first plane, length, compact offset)
+    struct Seg { int start, len, coff; };
+    std::vector<Seg> segs;
+    std::vector<int> planes;   // compact index -> cube plane
+    int compact(int l) const {
+        for (auto &g : segs) if (l >= g.start && l <= g.start + g.len) return g.coff + (l - g.start);
+        return -1;
+    }
+    float *sotf = nullptr, *tpl = nullptr, *mhat = nullptr, *spec = nullptr, *ycol = nullptr, *cube = nullptr,
+          *maps_pad = nullptr, *ycol_maps = nullptr;
+    float *Fi = nullptr, *Gi = nullptr, *Gf = nullptr, *Ff = nullptr, *GiT = nullptr, *GfT = nullptr;
+    // folded-DFT matrices [MPx][KPx]: cos/sin along alpha; weighted cos/sin for c2r; plain cos/sin for r2c
+    float *Cma = nullptr, *Sma = nullptr, *Gc = nullptr, *Gs = nullptr, *Cf = nullptr, *Sf = nullptr;
+    int MPa = 0, KPa = 0, MPb = 0, KPb = 0;
+    int n_cu = 256;
+    bool gather_sorted = true;                   // gather rows ordered by cube location (L2 reuse across pointings)
+    bool gemm_grouped = true;                    // the adjoint's spectral-blur GEMMs of up to four channels as one launch (SURFH_GEMM_GROUPED=0: one each)
+    bool scatter_grouped = true;                 // adjoint scatter with SCATTER_G neighbouring pixels per workgroup (GroupTable)
+    bool otf_prod = true;                        // plane-wise model: OTF products inside the loader of the inverse transform (SURFH_OTF_PROD=0: own kernels)
+    bool gather_grouped = true;                  // forward gather (fp16 output) likewise
+    bool dense_dft = false, fuse_mix = true, wblur_fp32 = false;
+    // surfh_config.verify: every long sum accumulated in float64 (dense DFT products, spectral blur, adjoint spectral mix,
+    // gather / scatter rows) -- the strict dot test; storage stays fp32
+    bool verify = false;
+    int prior_kind = 0;                          // 0: separated first differences (NpDiff_r / NpDiff_c); 1: joint Laplacian (surfh_set_prior)
+    // surfh_set_potential: the potential of the spatial prior (maps, planes, the cube's rows / columns), of the cube's spectral
+    // prior and of the robust data term; 0 Huber, 1 hyperbolic, 2 Hebert-Leahy (huber_dev.h)
+    int pot[3] = {0, 0, 0};
+    // two-piece fp16 passes with LDS-resident matrices (dft_h2.h): the plan's complex arrays (sotf, spec, ycol, and
+    // mhat when T == 0) are then INTERLEAVED [..][LP][2] instead of planar [2][..][LP]
+    bool h2 = false;
+    unsigned short *h2img = nullptr;             // three images: (Cma, Sma), (Gc, Gs), (Cf, Sf)
+    // Cooley-Tukey passes (dft_ct.h) for lengths whose folded matrix does not fit LDS (N = R * M: 501, 512, ...); same
+    // interleaved layout.  ilv = h2 || ct is the layout flag of the complex arrays.
+    bool ct = false, ilv = false;
+    DftCtPlan ctA, ctB;                          // transform lengths Na / Nb (ctB aliases ctA when they are equal)
+    // which kernel transforms an axis: the choice is per axis (a 300 x 64 image runs dft_ct along alpha and dft_h2 along beta);
+    // h2 = both axes on dft_h2 (fused adjoint tail, OTF-support lists), ct = at least one axis on dft_ct.  An axis neither covers
+    // (a prime factor above 190, fewer than 32 points) puts the plan on the dense fp32 products with planar arrays.
+    int ax_a = 0, ax_b = 0;                      // 0: none, 1: dft_h2, 2: dft_ct
+    // cube columns alpha in [a_lo, a_hi) hold every pixel any channel's tables touch: the transform passes that are batched
+    // over alpha skip the rest (forward: the cube outside is never read; adjoint: it is zero).  ycol_adj: the adjoint's
+    // intermediate in its own buffer, whose columns outside the range stay zero from plan creation on.
+    int a_lo = 0, a_hi = 0, b_lo = 0, b_hi = 0;  // (b: the same for the cube rows beta)
+    float *ycol_adj = nullptr;
+    // spectral-domain solver calls (surfh_normal_spec_dev ...): the maps' half spectra in Parseval-scaled form go in and out of the
+    // transform passes directly.  Set for the duration of one call.
+    const float *spec_in = nullptr;              // forward: the mix loader reads this instead of mhat
+    float *spec_out = nullptr;                   // adjoint: the fused tail writes this instead of mhat
+    const float *spec_prior_src = nullptr;       // adjoint: + spec_prior_mu * |D|^2 * this (the quadratic prior, world = 1)
+    float spec_mu = 1.f, spec_prior_mu = 0.f;
+    float *adjmix_part = nullptr;                // fused adjoint tail (dft_h2_adjmix_kernel): partial sums per (k_beta, slot); null: off
+    // Support of the OTF (otf_support below): the (k_beta, chunk of 128 wavelengths) pairs -- super-tiles of the two passes that
+    // touch the OTF, index k_beta * (LP / 128) + chunk -- in which some |sotf| exceeds 2^-24 of its plane's largest magnitude.
+    // The forward's complex pass and the fused adjoint tail visit only these; otf_kbstart[kb] = first list position of kb.
+    // ycol_mix: the forward's intermediate in its own buffer, whose other tiles stay zero from plan creation on.
+    int *otf_vlist = nullptr, *otf_kbstart = nullptr;
+    int otf_nvalid = 0;
+    // per chunk of 128 wavelengths: k-steps of the forward's complex pass (k_alpha inside the support), k-steps of its pass along
+    // beta (k_beta inside: the rest of ycol_mix is zero), rows k_beta the adjoint's first pass has to store: [3][LP / 128]
+    int *otf_tabs = nullptr;
+    float *ycol_mix = nullptr;
+    int h2kA[3] = {0, 0, 0};
+    float *io_x = nullptr, *io_y = nullptr, *io_cube = nullptr, *hth = nullptr, *mhat2 = nullptr;
+    // accumulator of the exact adjoint: cleared ONCE at plan creation.  Every scatter row knows which of its wavelengths an
+    // earlier channel has already written in the same pass (read-modify-write) and stores the others, so nothing stale
+    // survives a pass and no per-call clear is needed (nullptr: the tables could not express that -- clear `cube` every call)
+    float *gcube = nullptr;
+    std::vector<Channel> ch;
+    long isize = 0, osize = 0;
+    // data weights (surfh_set_data_weights): w [osize] in the layout of y, and room for W y, the data of the solvers' right-hand side;
+    // both null = every sample counts 1
+    float *dw = nullptr, *dwy = nullptr;
+    // CG
+    float *cg_x = nullptr, *cg_r = nullptr, *cg_d = nullptr, *cg_q = nullptr, *cg_b = nullptr, *cg_y = nullptr, *cg_qm = nullptr, *cg_dd = nullptr;
+    float *cg_hg = nullptr;                        // surfh_mmmg_huber(_vox): -gradient of the non-quadratic criterion
+    float *rb_y = nullptr, *rb_u = nullptr, *rb_ag = nullptr, *rb_am = nullptr;   // surfh_mmmg_robust(_vox): y, A x, A (-g), A m [osize]
+    double *dscal = nullptr, *dscratch = nullptr;   // [16] device scalars, partial sums (>= 1024, and what huber_vox.hip and robust_data.hip ask for)
+    double *cg_hist = nullptr;                     // device-resident r.r trace of the no-host-sync CG blocks (CG_HIST_CAP entries)
+    int cg_hist_n = 0;
+    // plane-wise CG with device-resident data (surfh_cg_planes_begin_dev / _step_dev): per-plane scalars [3][Lc] (the host-buffer
+    // plane-wise solvers use them too), the caller's iterate
+    double *pl_sc = nullptr;
+    double *pl_hsc = nullptr;                      // surfh_mmmg_huber_planes: [HUBER_PLANES_SCALARS][Lc] per-plane scalars
+    float *pl_x = nullptr;
+    double pl_mu = 1.0, pl_mu_reg = 0.0;
+    int pl_it = 0;
+    // ... with its vectors in the cube's wavelength-innermost layout [NBP][NAP][LP] (no layout transpose inside an iteration):
+    // x, r, d, q, b; per-wavelength scalars [3][LP] + partial sums; set while forward_dev / adjoint_dev are called on such vectors
+    float *pn_v[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    double *pn_sc = nullptr, *pn_part = nullptr;
+    bool pn_native = false, pn_active = false, pn_fold_prior = false;
+    // profiling
+    bool prof = false;
+    std::string prof_filter;                     // non-empty: only stages whose name starts with it are bracketed by events
+    std::vector<ProfRec> pending;
+    std::vector<hipEvent_t> pool;
+    std::map<std::string, std::pair<long, double>> acc;
+    std::vector<std::string> acc_names;
+};
+
+namespace surfh_impl __attribute__((visibility("hidden"))) {
+
+struct Prof {
+    surfh_plan *p;
+    ProfRec r;
+    bool on;
+    hipStream_t st;
+    Prof(surfh_plan *pl, const char *name, hipStream_t stream = nullptr) : p(pl), on(pl->prof), st(stream ? stream : pl->stream) {
+        if (on && !pl->prof_filter.empty() && strncmp(name, pl->prof_filter.c_str(), pl->prof_filter.size()) != 0) on = false;
+        if (!on) return;
+        r.name = name;
+        for (hipEvent_t *e : {&r.a, &r.b}) {
+            if (!p->pool.empty()) {
+                *e = p->pool.back();
+                p->pool.pop_back();
+            } else {
+                hipEventCreate(e);
+            }
+        }
+        hipEventRecord(r.a, st);
+    }
+    ~Prof() {
+        if (!on) return;
+        hipEventRecord(r.b, st);
+        p->pending.push_back(r);
+    }
+};
+
+template <typename Tp>
+int dev_alloc(Tp **p, size_t n) {
+    HIP_OK(hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(Tp)));
+    return 0;
+}
+
+template <typename Tp>
+int dev_upload(Tp **p, const std::vector<Tp> &h) {
+    if (dev_alloc(p, h.size())) return 1;
+    if (!h.empty()) HIP_OK(hipMemcpy(*p, h.data(), h.size() * sizeof(Tp), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// ---- helpers that cross a file boundary (default arguments live here) --------------------------------------------------------
+// plan.hip
+int chain(surfh_plan *p, hipStream_t from, hipStream_t to);
+void prof_collect(surfh_plan *p);
+int build_klist(const float *B, int N, int K, long ldb, int segLinP, int segChunks, double tol1, double tol2, std::vector<int> *out,
+                int *stride, long *n_near, long *n_far, int permP = 0, int permLin = 0);
+// plan_ops.hip
+int prior_add(surfh_plan *p, hipStream_t st, const float *d, float *q, int n_img, float mu_reg);
+bool prod_capable(const surfh_plan *p);
+int forward_dev(surfh_plan *p, const float *x, float *y, bool hand_over = false);
+int adjoint_dev(surfh_plan *p, const float *y, float *x, bool ref, bool handed_over = false);
+int normal_halves(surfh_plan *p, const float *v, float *q);
+const float *weighted_data(surfh_plan *p, const float *y);
+int normal_dev(surfh_plan *p, const float *d, float *q, double mu);
+int ensure_cg(surfh_plan *p);
+
+}  // namespace surfh_impl

@@ -1,0 +1,949 @@
+// Host side of the C ABI (include/surfh_amd.h), the operators: the transform passes, the forward, adjoint and normal pipelines
+// on device buffers, and the entry points that only wrap them (surfh_forward* / surfh_adjoint* / surfh_fwadj*, Model_WCT,
+// surfh_normal_dev, surfh_prior_add_dev, the spectral-domain operator, the LMM helpers).  They read the plan that plan.hip builds;
+// the solvers in plan_solvers.hip call them.  Plan struct and data layout: plan_internal.h.  All device work goes through
+// gemm_f32.hip, dft_h2.hip, dft_ct.hip and kernels.hip on the plan's stream.
+#include "plan_internal.h"
+
+namespace surfh_impl {
+
+// q += mu_reg * (the plan's regulariser) d, per image of n_img
+int prior_add(surfh_plan *p, hipStream_t st, const float *d, float *q, int n_img, float mu_reg) {
+    return p->prior_kind == 1 ? launch_prior_joint_add(st, d, q, n_img, p->Na, p->Nb, mu_reg) : launch_prior_add(st, d, q, n_img, p->Na, p->Nb, mu_reg);
+}
+
+namespace {
+
+// fp32-MFMA GEMM, or its float64-accumulating twin in verification mode
+int gemm32(surfh_plan *p, hipStream_t st, const GemmArgs &g) { return p->verify ? launch_gemm_f64acc(st, g) : launch_gemm_f32(st, g); }
+
+// ---- plane-major 2-D transforms (only for the T abundance maps) ---------------------------------
+// real [B][NAP][NBP] -> spec [B][2][KAP][KBP]   (tmp = ycol_maps viewed as [B][NAP][2*KBP])
+int rfft2_planes(surfh_plan *p, const float *src, float *dst, int B) {
+    GemmArgs g;
+    g.A0 = src; g.lda = p->NBP; g.sA = p->PLc;
+    g.B0 = p->Gf; g.ldb = 2 * p->KBP; g.sB = 0;
+    g.C = p->ycol_maps; g.ldc = 2 * p->KBP; g.sC = (long)p->NAP * 2 * p->KBP;
+    g.M = p->NAP; g.N = 2 * p->KBP; g.K = p->NBP; g.batch = B;
+    {
+        Prof pr(p, "gemm_dft_rows_fwd_maps");
+        LAUNCH_OK(gemm32(p, p->stream, g));
+    }
+    GemmArgs h;
+    h.A0 = p->Ff; h.lda = 2 * p->NAP; h.sA = 0;
+    h.B0 = p->ycol_maps; h.B1 = p->ycol_maps + p->KBP; h.ksplitB = p->NAP; h.ldb = 2 * p->KBP;
+    h.sB = (long)p->NAP * 2 * p->KBP;
+    h.C = dst; h.ldc = p->KBP; h.sC = 2 * p->PL;
+    h.M = 2 * p->KAP; h.N = p->KBP; h.K = 2 * p->NAP; h.batch = B;
+    {
+        Prof pr(p, "gemm_dft_cols_fwd_maps");
+        LAUNCH_OK(gemm32(p, p->stream, h));
+    }
+    return 0;
+}
+
+// spec [B][2][KAP][KBP] -> real [B][NAP][NBP]   (tmp = ycol_maps viewed as [B][2][NAP][KBP])
+int irfft2_planes(surfh_plan *p, const float *src, float *dst, int B) {
+    GemmArgs g;
+    g.A0 = p->Fi; g.lda = 2 * p->KAP; g.sA = 0;
+    g.B0 = src; g.ldb = p->KBP; g.sB = 2 * p->PL;
+    g.C = p->ycol_maps; g.ldc = p->KBP; g.sC = (long)2 * p->NAP * p->KBP;
+    g.M = 2 * p->NAP; g.N = p->KBP; g.K = 2 * p->KAP; g.batch = B;
+    {
+        Prof pr(p, "gemm_dft_cols_inv_maps");
+        LAUNCH_OK(gemm32(p, p->stream, g));
+    }
+    GemmArgs h;
+    h.A0 = p->ycol_maps; h.A1 = p->ycol_maps + (long)p->NAP * p->KBP; h.ksplitA = p->KBP; h.lda = p->KBP;
+    h.sA = (long)2 * p->NAP * p->KBP;
+    h.B0 = p->Gi; h.ldb = p->NBP; h.sB = 0;
+    h.C = dst; h.ldc = p->NBP; h.sC = p->PLc;
+    h.M = p->NAP; h.N = p->NBP; h.K = 2 * p->KBP; h.batch = B;
+    {
+        Prof pr(p, "gemm_dft_rows_inv_maps");
+        LAUNCH_OK(gemm32(p, p->stream, h));
+    }
+    return 0;
+}
+
+// ---- wavelength-innermost 2-D transforms of the whole owned cube -------------------------------
+// cube [NBP][NAP][LP] -> spec [2][KAP][KBP][LP]        (tmp ycol viewed as Z[2][KBP][NAP][LP])
+int rfft2_lam(surfh_plan *p, const float *src, float *dst) {
+    const long LP = p->LP;
+    GemmArgs g;   // Z[(c,kb)][(a,l)] = GfT[(c,kb)][b] * cube[b][(a,l)]
+    g.A0 = p->GfT; g.lda = p->NBP;
+    g.B0 = src; g.ldb = p->NAP * LP;
+    g.C = p->ycol; g.ldc = p->NAP * LP;
+    g.M = 2 * p->KBP; g.N = (int)(p->NAP * LP); g.K = p->NBP;
+    {
+        Prof pr(p, "gemm_dft_rows_fwd");
+        LAUNCH_OK(gemm32(p, p->stream, g));
+    }
+    GemmArgs h;   // per kb: S[(c,ka)][l] = Ff[(c,ka)][(c',a)] * Z[c'][kb][a][l]
+    h.A0 = p->Ff; h.lda = 2 * p->NAP;
+    h.B0 = p->ycol; h.B1 = p->ycol + (long)p->KBP * p->NAP * LP; h.ksplitB = p->NAP; h.ldb = LP; h.sB = p->NAP * LP;
+    h.C = dst; h.ldc = p->KBP * LP; h.sC = LP;
+    h.M = 2 * p->KAP; h.N = (int)LP; h.K = 2 * p->NAP; h.batch = p->KBP;
+    {
+        Prof pr(p, "gemm_dft_cols_fwd");
+        LAUNCH_OK(gemm32(p, p->stream, h));
+    }
+    return 0;
+}
+
+// spec [2][KAP][KBP][LP] -> cube [NBP][NAP][LP]        (tmp ycol viewed as Y[2][NAP][KBP][LP])
+int irfft2_lam(surfh_plan *p, const float *src, float *dst) {
+    const long LP = p->LP;
+    GemmArgs g;   // Y[(c,a)][(kb,l)] = Fi[(c,a)][(c',ka)] * S[(c',ka)][(kb,l)]
+    g.A0 = p->Fi; g.lda = 2 * p->KAP;
+    g.B0 = src; g.ldb = p->KBP * LP;
+    g.C = p->ycol; g.ldc = p->KBP * LP;
+    g.M = 2 * p->NAP; g.N = (int)(p->KBP * LP); g.K = 2 * p->KAP;
+    {
+        Prof pr(p, "gemm_dft_cols_inv");
+        LAUNCH_OK(gemm32(p, p->stream, g));
+    }
+    GemmArgs h;   // per a: cube[b][a][l] = GiT[b][(c,kb)] * Y[c][a][kb][l]
+    h.A0 = p->GiT; h.lda = 2 * p->KBP;
+    h.B0 = p->ycol; h.B1 = p->ycol + (long)p->NAP * p->KBP * LP; h.ksplitB = p->KBP; h.ldb = LP; h.sB = p->KBP * LP;
+    h.C = dst; h.ldc = p->NAP * LP; h.sC = LP;
+    h.M = p->NBP; h.N = (int)LP; h.K = 2 * p->KBP; h.batch = p->NAP;
+    {
+        Prof pr(p, "gemm_dft_rows_inv");
+        LAUNCH_OK(gemm32(p, p->stream, h));
+    }
+    return 0;
+}
+
+// ---- two-piece fp16 passes, matrices resident in LDS, interleaved complex arrays (dft_h2.h) --------
+// cube [NBP][NAP][LP] -> spec [KAP][KBP][LP][2]        (tmp ycol viewed as Z[KBP][NAP][LP][2])
+// `madj` != nullptr: the second pass does not store the spectrum but multiplies it by conj(sotf) and reduces it over the
+// wavelengths with the template weights straight into madj [T][2][KAP][KBP] (the adjoint's tail, spectroModel.py:175-181)
+// `acols`: the source cube is zero outside the alpha range [a_lo, a_hi) (the adjoint's accumulator): the first pass
+// transforms only those columns, into ycol_adj whose other columns are zero for good
+// `which`: bit 0 = the pass along beta, bit 1 = the pass along alpha (plans whose axes run on different kernels call one of each)
+int rfft2_lam_h2(surfh_plan *p, const float *src, float *dst, float *madj = nullptr, bool acols = false, int which = 3) {
+    const long LP = p->LP;
+    const int ha = p->Na / 2 + 1, hb = p->Nb / 2 + 1;
+    const bool sub = acols && p->ycol_adj && p->a_hi > p->a_lo;
+    float *const yc = sub ? p->ycol_adj : p->ycol;
+    const int a0 = sub ? p->a_lo : 0, na = sub ? p->a_hi - p->a_lo : p->Na;
+    DftH2Args g;   // r2c along beta
+    g.kind = 1; g.src = src + (long)a0 * LP; g.ldb = p->NAP * LP; g.Kn = p->Nb;
+    g.dst = yc + 2 * (long)a0 * LP; g.ldc = 2 * p->NAP * LP; g.e[0] = 1.f; g.e[3] = -1.f; g.rvalid = hb;
+    g.KP = p->KPb; g.N = (int)(na * LP);
+    // fused tail with the OTF's support: it reads no k_beta beyond the support of a wavelength chunk, so those rows are not stored
+    if (madj && p->otf_vlist && p->ycol_mix && p->otf_tabs) { g.rtab = p->otf_tabs + 2 * (LP / 128); g.tabLP = (int)LP; }
+    if (which & 1) {
+        Prof pr(p, "dft_h2_rows_fwd");
+        LAUNCH_OK(launch_dft_h2(p->stream, g, p->h2img + 2 * DFT_H2_IMAGE_HALFS, p->h2kA[2]));
+    }
+    if (!(which & 2)) return 0;
+    DftH2Args h;   // c2c along alpha, batched over k_beta
+    h.kind = 0; h.src = yc; h.ldb = 2 * LP; h.sB = 2 * p->NAP * LP; h.Kn = p->Na;
+    h.dst = dst; h.ldc = 2 * p->KBP * LP; h.sC = 2 * LP; h.Rn = p->Na; h.rvalid = ha;
+    h.KP = p->KPa; h.N = (int)LP; h.batch = hb;
+    h.e[0] = 1.f; h.e[1] = 1.f; h.e[2] = 1.f; h.e[3] = -1.f;                 // Re Z[r] = C ae + S bo, Re Z[N-r] = C ae - S bo
+    h.e_alt[0] = 1.f; h.e_alt[1] = -1.f; h.e_alt[2] = 1.f; h.e_alt[3] = 1.f;  // Im Z[r] = C be - S ao, Im Z[N-r] = C be + S ao
+    if (madj) {
+        DftH2AdjMix am;
+        am.hsrc = p->sotf; am.ldh = 2 * p->KBP * LP; am.sH = 2 * LP; am.tpl = p->tpl; am.T = p->T; am.LPt = (int)LP; am.mpart = p->adjmix_part;
+        if (p->otf_vlist && p->ycol_mix) { am.vlist = p->otf_vlist; am.kbstart = p->otf_kbstart; am.nvalid = p->otf_nvalid; }
+        if (sub) {       // rows alpha < a_lo and alpha >= a_hi of the intermediate are zero: leading k-steps (rows k, Na - k) without a non-zero row
+            int kt0 = 0;
+            while (16 * kt0 + 15 < p->a_lo && p->Na - (16 * kt0 + 15) >= p->a_hi && h.KP / 16 - (kt0 + 1) >= 5) ++kt0;
+            am.kt0 = kt0;
+        }
+        if (p->spec_out && madj == p->spec_out) {      // the solver's scaled half spectrum, mu and the quadratic prior folded in
+            am.out_self = p->spec_mu; am.out_pair = p->spec_mu * 1.41421356237309505f; am.Nb = p->Nb;
+            am.prior_src = p->spec_prior_src; am.prior_mu = p->spec_prior_mu;
+        }
+        Prof pr(p, "dft_h2_cols_fwd_adjmix");
+        LAUNCH_OK(launch_dft_h2_adjmix(p->stream, h, am, madj, p->PL, p->KBP, p->h2img, p->h2kA[0]));
+        return 0;
+    }
+    {
+        Prof pr(p, "dft_h2_cols_fwd");
+        LAUNCH_OK(launch_dft_h2(p->stream, h, p->h2img, p->h2kA[0]));
+    }
+    return 0;
+}
+
+// spec [KAP][KBP][LP][2] -> cube [NBP][NAP][LP]        (tmp ycol viewed as Y[NAP][KBP][LP][2])
+// `acols`: only the cube columns alpha in [a_lo, a_hi) are wanted (the gathers read nothing else)
+int irfft2_lam_h2(surfh_plan *p, const float *src, float *dst, bool mix, bool acols = false, int which = 3) {
+    const long LP = p->LP;
+    const int ha = p->Na / 2 + 1, hb = p->Nb / 2 + 1;
+    DftH2Args g;   // c2c along alpha (optionally with the spectral mix formed in the loader)
+    g.kind = 0; g.src = src; g.ldb = 2 * p->KBP * LP; g.Kn = p->Na;
+    g.dst = p->ycol; g.ldc = 2 * p->KBP * LP; g.Rn = p->Na; g.rvalid = ha;
+    g.KP = p->KPa; g.N = (int)(hb * LP);
+    g.e[0] = 1.f; g.e[1] = -1.f; g.e[2] = 1.f; g.e[3] = 1.f;
+    g.e_alt[0] = 1.f; g.e_alt[1] = 1.f; g.e_alt[2] = 1.f; g.e_alt[3] = -1.f;
+    if (mix) { g.mhat = p->mhat; g.tpl = p->tpl; g.T = p->T; g.LP = (int)p->LP; g.PL = p->PL; g.KBP = p->KBP; }
+    if (mix && p->spec_in) { g.mhat = p->spec_in; g.mhat_self = 1.f; g.mhat_pair = 0.70710678118654752f; g.mix_Nb = p->Nb; }
+    // the OTF's support: tiles outside it are neither computed nor stored -- their place in ycol_mix is zero for good
+    const bool supp = mix && p->otf_vlist && p->ycol_mix && p->adjmix_part;
+    float *const yc = supp ? p->ycol_mix : p->ycol;
+    if (supp) { g.vlist = p->otf_vlist; g.nvalid = p->otf_nvalid; g.dst = yc; }
+    if (supp && p->otf_tabs) { g.ktab = p->otf_tabs; g.tabLP = (int)LP; }          // k_alpha beyond the support: not read
+    if (which & 2) {
+        Prof pr(p, mix ? "dft_h2_cols_inv_mix" : "dft_h2_cols_inv");
+        LAUNCH_OK(launch_dft_h2(p->stream, g, p->h2img, p->h2kA[0]));
+    }
+    if (!(which & 1)) return 0;
+    const bool sub = acols && p->a_hi > p->a_lo;
+    const int a0 = sub ? p->a_lo : 0, na = sub ? p->a_hi - p->a_lo : p->Na;
+    DftH2Args h;   // c2r along beta, batched over alpha: cube[b] = Gc Yr - Gs Yi, cube[N-b] = Gc Yr + Gs Yi
+    h.kind = 2; h.src = yc + (long)a0 * 2 * p->KBP * LP; h.ldb = 2 * LP; h.sB = 2 * p->KBP * LP;
+    h.dst = dst + (long)a0 * LP; h.ldc = p->NAP * LP; h.sC = LP;
+    h.e[0] = 1.f; h.e[1] = -1.f; h.e[2] = 1.f; h.e[3] = 1.f; h.Rn = p->Nb; h.rvalid = hb;
+    h.KP = p->KPb; h.N = (int)LP; h.batch = na;
+    if (supp && p->otf_tabs) { h.ktab = p->otf_tabs + LP / 128; h.tabLP = (int)LP; }   // k_beta beyond the support: zero in ycol_mix
+    {
+        Prof pr(p, "dft_h2_rows_inv");
+        LAUNCH_OK(launch_dft_h2(p->stream, h, p->h2img + DFT_H2_IMAGE_HALFS, p->h2kA[1]));
+    }
+    return 0;
+}
+
+// ---- Cooley-Tukey passes (dft_ct.h): the same four passes for N = R * M, interleaved complex arrays ---------------
+// cube [NBP][NAP][LP] -> spec [KAP][KBP][LP][2]        (tmp ycol viewed as Z[KBP][NAP][LP][2])
+// `lists`: the caller is the adjoint's tail, whose reduction reads the spectrum only inside the OTF's support
+int rfft2_lam_ct(surfh_plan *p, const float *src, float *dst, bool acols = false, bool lists = false, int which = 3) {
+    const long LP = p->LP;
+    const int hb = p->Nb / 2 + 1;
+    const bool sub = acols && p->ycol_adj && p->a_hi > p->a_lo;
+    float *const yc = sub ? p->ycol_adj : p->ycol;
+    const int a0 = sub ? p->a_lo : 0, na = sub ? p->a_hi - p->a_lo : p->Na;
+    DftCtArgs g;   // r2c along beta: neighbouring wavelengths as packed pairs a + i b, separated in the epilogue
+    g.R = p->ctB.R; g.M = p->ctB.M; g.loader = DFT_CT_PLAIN; g.epi = DFT_CT_HSEP; g.sgn = -1.f;
+    g.scale = (float)(0.5 / std::sqrt((double)p->Nb));
+    g.src = src + (long)a0 * LP; g.ldb = p->NAP * LP;
+    g.dst = yc + 2 * (long)a0 * LP; g.ldc = 2 * p->NAP * LP;
+    g.ncols = (int)(na * LP / 2); g.batch = 1;
+    // the reduction reads no k_beta beyond the support of a wavelength chunk: those rows are not stored (chunks of 64 packed pairs)
+    const bool supp = lists && p->otf_vlist && p->ycol_mix && p->otf_tabs && p->T > 0;
+    if (supp) { g.rtab = p->otf_tabs + 2 * (LP / 128); g.tabLP = (int)(LP / 2); g.tabShift = 6; }
+    if (which & 1) {
+        Prof pr(p, "dft_ct_rows_fwd");
+        LAUNCH_OK(launch_dft_ct(p->stream, g, p->ctB));
+    }
+    if (!(which & 2)) return 0;
+    DftCtArgs h;   // c2c along alpha, batched over k_beta
+    h.R = p->ctA.R; h.M = p->ctA.M; h.loader = DFT_CT_PLAIN; h.epi = DFT_CT_STORE; h.sgn = -1.f;
+    h.scale = (float)(1.0 / std::sqrt((double)p->Na));
+    h.src = yc; h.ldb = 2 * LP; h.sB = 2 * p->NAP * LP;
+    h.dst = dst; h.ldc = 2 * p->KBP * LP; h.sC = 2 * LP;
+    h.ncols = (int)LP; h.batch = hb;
+    if (supp) {       // only the (k_beta, wavelength chunk) super-tiles and the rows k_alpha inside the OTF's support
+        h.vlist = p->otf_vlist; h.nvalid = p->otf_nvalid;
+        h.rtab = p->otf_tabs + 3 * (LP / 128); h.tabLP = (int)LP;
+    }
+    {
+        Prof pr(p, "dft_ct_cols_fwd");
+        LAUNCH_OK(launch_dft_ct(p->stream, h, p->ctA));
+    }
+    return 0;
+}
+
+// element-wise product formed in the loader of the first inverse pass (dft_ct.h, loader PROD): src * prod (sign +1) or
+// src * conj(prod) (-1), times `scale` -- the plane-wise path's OTF product without its own kernel and array
+struct ProdOperand {
+    const float *prod = nullptr;
+    float sign = 1.f, scale = 1.f;
+    // + add_w |D|^2 add (loader PRODADD): the quadratic prior's term of the plane-wise normal operator, `add` = the spectrum of
+    // the vector the operator is applied to, |D|^2 = the circular first differences' transfer function (fusion_CT.py:16-43)
+    const float *add = nullptr;
+    float add_w = 0.f;
+};
+}  // namespace
+
+// the complex pass along alpha runs on the kernel that has the PROD loader (SURFH_OTF_PROD=0: the separate product kernels)
+bool prod_capable(const surfh_plan *p) { return p->otf_prod && p->T == 0 && p->ilv && !p->dense_dft && p->ax_a == 2; }
+
+namespace {
+
+// spec [KAP][KBP][LP][2] -> cube [NBP][NAP][LP]        (tmp ycol viewed as Y[NAP][KBP][LP][2])
+int irfft2_lam_ct(surfh_plan *p, const float *src, float *dst, bool mix, bool acols = false, int which = 3, const ProdOperand *po = nullptr) {
+    const long LP = p->LP;
+    const int hb = p->Nb / 2 + 1;
+    DftCtArgs g;   // c2c along alpha (optionally with the spectral mix formed in the loader)
+    g.R = p->ctA.R; g.M = p->ctA.M; g.loader = mix ? DFT_CT_MIX : DFT_CT_PLAIN; g.epi = DFT_CT_STORE; g.sgn = 1.f;
+    g.scale = (float)(1.0 / std::sqrt((double)p->Na));
+    g.src = src; g.ldb = 2 * p->KBP * LP;
+    g.dst = p->ycol; g.ldc = 2 * p->KBP * LP;
+    g.ncols = (int)(hb * LP); g.batch = 1;
+    if (mix) { g.mhat = p->mhat; g.tpl = p->tpl; g.T = p->T; g.LP = (int)p->LP; g.PL = p->PL; g.KBP = p->KBP; }
+    if (mix && p->spec_in) { g.mhat = p->spec_in; g.mhat_self = 1.f; g.mhat_pair = 0.70710678118654752f; g.mix_Nb = p->Nb; }
+    if (po && po->prod && !mix) {
+        g.loader = DFT_CT_PROD; g.prod = po->prod; g.ldp = g.ldb; g.sP = 0; g.prod_sign = po->sign; g.scale *= po->scale;
+        if (po->add && po->add_w != 0.f) {
+            g.loader = DFT_CT_PRODADD; g.add = po->add; g.add_w = po->add_w; g.add_Nb = p->Nb; g.LP = (int)p->LP;
+        }
+    }
+    // the OTF's support: tiles outside it are neither computed nor stored -- their place in ycol_mix is zero for good
+    const bool supp = mix && p->otf_vlist && p->ycol_mix && p->otf_tabs;
+    float *const yc = supp ? p->ycol_mix : p->ycol;
+    if (supp) { g.vlist = p->otf_vlist; g.nvalid = p->otf_nvalid; g.dst = yc; g.ktab = p->otf_tabs; g.tabLP = (int)LP; }
+    if (which & 2) {
+        Prof pr(p, mix ? "dft_ct_cols_inv_mix" : (g.loader == DFT_CT_PROD ? "dft_ct_cols_inv_prod" : g.loader == DFT_CT_PRODADD ? "dft_ct_cols_inv_prodadd" : "dft_ct_cols_inv"));
+        LAUNCH_OK(launch_dft_ct(p->stream, g, p->ctA));
+    }
+    if (!(which & 1)) return 0;
+    const bool sub = acols && p->a_hi > p->a_lo;
+    const int a0 = sub ? p->a_lo : 0, na = sub ? p->a_hi - p->a_lo : p->Na;
+    DftCtArgs h;   // c2r along beta, batched over alpha: two neighbouring half spectra as one Hermitian-extended complex sequence
+    h.R = p->ctB.R; h.M = p->ctB.M; h.loader = DFT_CT_HPACK; h.epi = DFT_CT_STORE; h.sgn = 1.f;
+    h.scale = (float)(1.0 / std::sqrt((double)p->Nb));
+    h.src = yc + (long)a0 * 2 * p->KBP * LP; h.ldb = 2 * LP; h.sB = 2 * p->KBP * LP;
+    h.dst = dst + (long)a0 * LP; h.ldc = p->NAP * LP; h.sC = LP;
+    h.ncols = (int)(LP / 2); h.batch = na;
+    if (supp) { h.ktab = p->otf_tabs + LP / 128; h.tabLP = (int)(LP / 2); h.tabShift = 6; }      // k_beta beyond the support: zero in ycol_mix
+    {
+        Prof pr(p, "dft_ct_rows_inv");
+        LAUNCH_OK(launch_dft_ct(p->stream, h, p->ctB));
+    }
+    return 0;
+}
+
+// the two transforms on interleaved arrays, each pass on the kernel of its axis (surfh_plan::ax_a / ax_b)
+int rfft2_lam_ilv(surfh_plan *p, const float *src, float *dst, float *madj = nullptr, bool acols = false, bool lists = false) {
+    if (p->h2) return rfft2_lam_h2(p, src, dst, madj, acols);
+    if (p->ax_b == 1 ? rfft2_lam_h2(p, src, dst, nullptr, acols, 1) : rfft2_lam_ct(p, src, dst, acols, lists, 1)) return 1;
+    return p->ax_a == 1 ? rfft2_lam_h2(p, src, dst, nullptr, acols, 2) : rfft2_lam_ct(p, src, dst, acols, lists, 2);
+}
+int irfft2_lam_ilv(surfh_plan *p, const float *src, float *dst, bool mix = false, bool acols = false, const ProdOperand *po = nullptr) {
+    if (po && p->ax_a != 2) return fail("irfft2: the product loader needs the Cooley-Tukey pass along alpha");
+    if (p->h2) return irfft2_lam_h2(p, src, dst, mix, acols);
+    if (p->ax_a == 1 ? irfft2_lam_h2(p, src, dst, mix, acols, 2) : irfft2_lam_ct(p, src, dst, mix, acols, 2, po)) return 1;
+    return p->ax_b == 1 ? irfft2_lam_h2(p, src, dst, mix, acols, 1) : irfft2_lam_ct(p, src, dst, mix, acols, 1);
+}
+
+// ---------------------------------------------------------------------------------------------
+// pipelines on device buffers
+// ---------------------------------------------------------------------------------------------
+int rfft2_cube(surfh_plan *p, const float *src, float *dst) { return p->dense_dft ? rfft2_lam(p, src, dst) : rfft2_lam_ilv(p, src, dst); }
+int irfft2_cube(surfh_plan *p, const float *src, float *dst, bool mix = false, bool acols = false, const ProdOperand *po = nullptr) {
+    if (po && p->dense_dft) return fail("irfft2: the product loader is not part of the dense plan");
+    return p->dense_dft ? irfft2_lam(p, src, dst) : irfft2_lam_ilv(p, src, dst, mix, acols, po);
+}
+
+// mhat[t] = sum_l tpl[t][l] conj(sotf[l]) rfft2(cube[l])  (T > 0), or the per-plane product (T == 0)
+// `acols`: the cube is zero outside the alpha range of the channels' tables (the adjoint's accumulator)
+int adjoint_tail(surfh_plan *p, const float *cube, bool acols = false) {
+    if (p->adjmix_part && p->h2 && p->T > 0) return rfft2_lam_h2(p, cube, p->spec, p->spec_out ? p->spec_out : p->mhat, acols);
+    if (p->ct && !p->dense_dft) {
+        if (rfft2_lam_ilv(p, cube, p->spec, nullptr, acols, true)) return 1;
+        if (prod_capable(p)) return 0;      // plane-wise: conj(OTF) x spec is formed by the loader of the inverse transform that follows
+        SpecmixAdjOpt o;
+        o.Na = p->Na; o.KBP = p->KBP;
+        if (p->T > 0 && p->otf_vlist && p->ycol_mix && p->otf_tabs) o.lim = p->otf_tabs + 2 * (p->LP / 128);
+        if (p->spec_out) {      // the solver's scaled half spectrum, mu and the quadratic prior folded in
+            o.Nb = p->Nb; o.out_self = p->spec_mu; o.out_pair = p->spec_mu * 1.41421356237309505f;
+            o.prior_src = p->spec_prior_src; o.prior_mu = p->spec_prior_mu;
+        }
+        Prof pr(p, "specmix_adj");
+        if (p->T == 0 && p->pn_fold_prior) {      // plane-wise normal operator: mu and the quadratic prior in the OTF product (see below)
+            SpecmixAdjOpt o2;
+            o2.Na = p->Na; o2.Nb = p->Nb; o2.KBP = p->KBP; o2.out_self = (float)p->pl_mu; o2.prior_src = p->mhat; o2.prior_mu = (float)p->pl_mu_reg;
+            LAUNCH_OK(launch_specmix_adj(p->stream, p->spec, p->sotf, p->tpl, p->mhat, 0, p->PL, p->LP, false, 1, &o2));
+            return 0;
+        }
+        LAUNCH_OK(launch_specmix_adj(p->stream, p->spec, p->sotf, p->tpl, p->spec_out ? p->spec_out : p->mhat, p->T, p->PL, p->LP, false, 1,
+                                     p->T > 0 ? &o : nullptr));
+        return 0;
+    }
+    if (rfft2_cube(p, cube, p->spec)) return 1;
+    Prof pr(p, "specmix_adj");
+    if (p->T == 0 && p->ilv && p->pn_fold_prior) {
+        // plane-wise normal operator: `mhat` still holds the spectrum of the vector the forward half was applied to -- mu and the
+        // quadratic prior go into the OTF product, no prior kernel and no scaling pass afterwards
+        SpecmixAdjOpt o;
+        o.Na = p->Na; o.Nb = p->Nb; o.KBP = p->KBP; o.out_self = (float)p->pl_mu; o.prior_src = p->mhat; o.prior_mu = (float)p->pl_mu_reg;
+        LAUNCH_OK(launch_specmix_adj(p->stream, p->spec, p->sotf, p->tpl, p->mhat, 0, p->PL, p->LP, false, 1, &o));
+        return 0;
+    }
+    LAUNCH_OK(launch_specmix_adj(p->stream, p->spec, p->sotf, p->tpl, p->mhat, p->T, p->PL, p->LP, p->verify, p->ilv));
+    return 0;
+}
+
+}  // namespace
+
+// `hand_over`: the caller is the normal operator -- channels with a spectral-blur GEMM do not write y but leave the adjoint's
+// GEMM operand (fp16 pieces of ymat + row maxima) behind
+int forward_dev(surfh_plan *p, const float *x, float *y, bool hand_over) {
+    hipStream_t s = p->stream;
+    if (p->spec_in) {
+        // the maps' spectra are the caller's vector: nothing to transform
+    } else if (p->T > 0) {
+        {
+            Prof pr(p, "pad_planes");
+            LAUNCH_OK(launch_pad_planes(s, x, p->maps_pad, p->T, p->Na, p->Nb, p->NAP, p->NBP));
+        }
+        if (rfft2_planes(p, p->maps_pad, p->mhat, p->T)) return 1;
+    } else if (p->pn_native) {
+        // plane-wise solver on wavelength-innermost vectors: x is already in the cube's layout [NBP][NAP][LP]
+        if (rfft2_cube(p, x, p->mhat)) return 1;
+    } else {
+        {
+            Prof pr(p, "cube_transpose");
+            for (auto &g : p->segs)
+                LAUNCH_OK(launch_cube_to_lam_inner(s, x, p->cube + g.coff, g.start, g.len, p->Na, p->Nb, p->NAP, p->LP));
+        }
+        if (rfft2_cube(p, p->cube, p->mhat)) return 1;
+    }
+    if (p->T > 0 && p->T <= 4 && p->fuse_mix && !p->dense_dft) {
+        // spectral mix x OTF fused into the loader of the first inverse pass: `spec` is never written
+        // (the normal operator needs the blurred cube only where a gather reads it)
+        if (irfft2_cube(p, p->sotf, p->cube, true, hand_over)) return 1;
+    } else if (prod_capable(p)) {
+        // plane-wise model on the Cooley-Tukey passes: OTF x spectrum in the loader of the first inverse pass, `spec` is never written
+        ProdOperand po;
+        po.prod = p->sotf;
+        if (irfft2_cube(p, p->mhat, p->cube, false, false, &po)) return 1;
+    } else {
+        {
+            Prof pr(p, "specmix_fwd");
+            LAUNCH_OK(launch_specmix_fwd(s, p->mhat, p->sotf, p->tpl, p->spec, p->T, p->PL, p->LP, p->ilv));
+        }
+        if (irfft2_cube(p, p->spec, p->cube)) return 1;
+    }
+    // gather on the main stream, spectral-blur GEMM + slab sum on the second one: GEMM(c) overlaps gather(c+1)
+    hipStream_t sB = (p->overlap && p->stream2) ? p->stream2 : s;
+    for (auto &c : p->ch) {
+        const bool f16 = c.W16 != nullptr;
+        {
+            Prof pr(p, "spmm_gather_fwd");
+            if (c.Xs16 && c.fwd.g.NG)     // straight to the block-scaled fp16 pieces of the all-consumer GEMM
+                LAUNCH_OK(launch_spmm_group_gather_f16(s, c.fwd.g, p->cube, c.Xs16, (long)c.NP * c.K, c.nlam, c.bscale, c.NP, c.K, c.LinP));
+            else if (c.Xs16)
+                LAUNCH_OK(launch_spmm_rows_f16(s, c.fwd.t, p->cube, c.Xs16, (long)c.NP * c.K, c.nlam, c.bscale, c.NP, c.K, c.LinP));
+            else if (p->verify)
+                LAUNCH_OK(launch_spmm_rows_f64acc(s, c.fwd.t, p->cube, c.Xs, c.nlam, 0));
+            else
+                LAUNCH_OK(launch_spmm_rows(s, c.fwd.t, p->cube, c.Xs, c.nlam, 0));
+        }
+        if (c.bsum) {   // y[l][(p,s,a)] = Xs[(p,s,a)][l]
+            Prof pr(p, "y_transpose");
+            LAUNCH_OK(launch_cube_from_lam_inner(s, c.Xs + c.shift, y + c.yoff, 0, c.Lin, 1, c.P * c.S * c.aout, 1, c.LinP));
+            continue;
+        }
+        if (chain(p, s, sB)) return 1;
+        GemmArgs g;   // y^T[n][l'] = sum_k Xs[n][k] W[l'][k]
+        g.A0 = c.Xs; g.lda = c.K;
+        g.C = c.Cpart; g.ldc = c.LdetP;
+        g.M = c.NP; g.N = c.LdetP; g.K = c.K; g.splitK = c.splitK; g.sCsplit = (long)c.NP * c.LdetP;
+        {
+            Prof pr(p, "gemm_wblur_fwd", sB);
+            if (p->wblur_fp32) {
+                g.B0 = c.Wt; g.ldb = c.LdetP;        // B as [K][N]
+                LAUNCH_OK(gemm32(p, sB, g));
+            } else {
+                // both operands as fp16 pieces (the gather wrote the block-scaled pieces of Xs): 256 x 256 all-consumer kernel
+                g.ldb = c.K;                         // B as [N][K]
+                g.B16 = c.W16; g.pB16 = (long)c.LdetP * c.K; g.sB16 = c.sW;
+                g.A3 = c.Xs16; g.pA3 = (long)c.NP * c.K;
+                g.bscale = c.bscale; g.segLinP = c.LinP; g.segChunks = (c.LinP + 1023) / 1024;
+                g.klist = c.klF; g.klistStride = c.klFs;
+                LAUNCH_OK(launch_gemm_nt_f16x2_cc(sB, g));
+            }
+        }
+        if (hand_over && c.ymat16 && c.wmat) {          // the normal operator under data weights: mu A^T W A
+            Prof pr(p, "ymat16w_from_cpart", sB);
+            LAUNCH_OK(launch_ymat16w_from_cpart(sB, c.Cpart, (long)c.NP * c.LdetP, c.splitK, c.ymat16, (long)c.NP * c.LdetP, c.amax, c.NP,
+                                                c.P * c.S * c.aout, c.Ldet, c.LdetP, c.wmat));
+        } else if (hand_over && c.ymat16) {
+            Prof pr(p, "ymat16_from_cpart", sB);
+            LAUNCH_OK(launch_ymat16_from_cpart(sB, c.Cpart, (long)c.NP * c.LdetP, c.splitK, c.ymat16, (long)c.NP * c.LdetP, c.amax, c.NP,
+                                               c.P * c.S * c.aout, c.Ldet, c.LdetP));
+        } else {
+            Prof pr(p, "y_from_cpart", sB);
+            LAUNCH_OK(launch_y_from_cpart(sB, c.Cpart, (long)c.NP * c.LdetP, c.splitK, y + c.yoff, c.P * c.S, c.Ldet,
+                                          c.aout, c.LdetP));
+        }
+    }
+    if (chain(p, sB, s)) return 1;     // everything after this call sees y complete
+    return 0;
+}
+
+// `handed_over`: forward_dev(hand_over) has just left the GEMM operands of the channels with a spectral blur behind
+int adjoint_dev(surfh_plan *p, const float *y, float *x, bool ref, bool handed_over) {
+    hipStream_t s = p->stream;
+    // detector-side work (y -> ymat, R^T GEMM) on the second stream, cube-side scatter on the main one: GEMM(c+1)
+    // overlaps scatter(c); the scatters stay in channel order on one stream because their windows overlap
+    hipStream_t sB = (p->overlap && p->stream2) ? p->stream2 : s;
+    if (chain(p, s, sB)) return 1;     // y (and the previous users of Xs / ymat) are ordered before the second stream's work
+    // the exact adjoint accumulates in its own buffer without clearing it (surfh_plan::gcube); the reference adjoint and the
+    // verification plan read-modify-write every row of the cleared work cube
+    float *const acc = (!ref && p->gcube) ? p->gcube : p->cube;
+    if (acc == p->cube) {
+        Prof pr(p, "fill_zero");
+        LAUNCH_OK(launch_fill_zero(s, p->cube, (long)p->NBP * p->NAP * p->LP));
+    }
+    // detector side of one channel: y -> ymat (-> its fp16 pieces, unless the forward half has just left them behind)
+    auto prepare = [&](Channel &c) -> int {
+        const bool f16 = c.W16 != nullptr;
+        if (handed_over && f16 && c.ymat16) return 0;
+        {
+            Prof pr(p, "ymat_from_y", sB);
+            LAUNCH_OK(launch_ymat_from_y(sB, y + c.yoff, c.ymat, c.P * c.S, c.Ldet, c.aout, c.LdetP, f16 ? c.pmax : nullptr,
+                                         f16 ? c.amax : nullptr, c.NP));
+        }
+        if (f16 && !p->wblur_fp32)
+            LAUNCH_OK(launch_split_rows2h(sB, c.ymat, c.amax, c.ymat16, c.NP, c.LdetP, (long)c.NP * c.LdetP));   // one scale per row
+        return 0;
+    };
+    auto gemm_args = [&](Channel &c) {   // Xs_t[n][k] = sum_l' y^T[n][l'] W[l'][k]
+        GemmArgs g;
+        g.A0 = c.ymat; g.lda = c.LdetP;
+        g.C = c.Xs; g.ldc = c.K;
+        g.M = c.NP; g.N = c.K; g.K = c.LdetP;
+        if (p->wblur_fp32) {
+            g.B0 = c.W; g.ldb = c.K;             // B as [K'=l'][N'=k]
+        } else if (c.W16) {
+            g.K = (c.Ldet + 31) / 32 * 32;       // the columns of ymat beyond Ldet are zero: whole K steps of them are skipped
+            g.ldb = c.LdetP;                     // B as [N'=k][K'=l']
+            g.B16 = c.Wt16; g.pB16 = (long)c.LdetP * c.K; g.sB16 = c.sW; g.amax = c.amax;
+            g.A3 = c.ymat16; g.pA3 = (long)c.NP * c.LdetP;
+            g.klist = c.klA; g.klistStride = c.klAs;
+            if (c.klA && c.permA) { g.permP = c.permA; g.permLin = c.LinP; }
+        }
+        return g;
+    };
+    // The two-piece fp16 GEMMs of up to four channels go out as ONE launch (each is 1.5-1.8 rounds of workgroups on its own;
+    // their operands and outputs are per channel, so nothing orders them among themselves): detector-side preparation of all
+    // of them first, the grouped GEMM, then the scatters in channel order.  SURFH_GEMM_GROUPED=0: one launch per channel.
+    std::vector<char> gemm_done(p->ch.size(), 0);
+    if (p->gemm_grouped && !p->wblur_fp32 && !p->verify) {
+        std::vector<GemmArgs> ga;
+        std::vector<size_t> gc;
+        for (size_t ci = 0; ci <= p->ch.size(); ++ci) {
+            const bool last = ci == p->ch.size();
+            if (!last) {
+                Channel &c = p->ch[ci];
+                if (c.bsum || !c.W16 || (ref && !c.has_ref)) continue;
+                if (prepare(c)) return 1;
+                ga.push_back(gemm_args(c)); gc.push_back(ci);
+            }
+            if (!ga.empty() && (last || (int)ga.size() == GEMM_GROUP_MAX)) {
+                {
+                    Prof pr(p, "gemm_wblur_adj", sB);
+                    LAUNCH_OK(launch_gemm_nt_f16x2_cc_group(sB, ga.data(), (int)ga.size()));
+                }
+                for (size_t i : gc) gemm_done[i] = 1;
+                ga.clear(); gc.clear();
+            }
+        }
+    }
+    for (size_t ci = 0; ci < p->ch.size(); ++ci) {
+        Channel &c = p->ch[ci];
+        if (ref && !c.has_ref) return fail("adjoint_ref needs the gridding_t tables (gt_*) in the channel descriptor");
+        if (c.bsum) {
+            {
+                Prof pr(p, "y_transpose");
+                LAUNCH_OK(launch_cube_to_lam_inner(s, y + c.yoff, c.Xs + c.shift, 0, c.Lin, 1, c.P * c.S * c.aout, 1, c.LinP));
+            }
+            Prof pr(p, ref ? "spmm_degrid_ref" : "spmm_scatter_adj");
+            if (p->verify)
+                LAUNCH_OK(launch_spmm_rows_f64acc(s, ref ? c.adjRef.t : c.adjT.t, c.Xs, acc, c.nlam, 1));
+            else if (!ref && c.adjT.g.NG)
+                LAUNCH_OK(launch_spmm_group_scatter(s, c.adjT.g, c.Xs, acc, c.nlam));
+            else
+                LAUNCH_OK(launch_spmm_rows(s, ref ? c.adjRef.t : c.adjT.t, c.Xs, acc, c.nlam, 1));
+            continue;
+        }
+        if (!gemm_done[ci]) {
+            if (prepare(c)) return 1;
+            const GemmArgs g = gemm_args(c);
+            Prof pr(p, "gemm_wblur_adj", sB);
+            if (p->wblur_fp32 || !c.W16) LAUNCH_OK(gemm32(p, sB, g));
+            else LAUNCH_OK(launch_gemm_nt_f16x2_cc(sB, g));
+        }
+        if (chain(p, sB, s)) return 1;
+        {
+            Prof pr(p, ref ? "spmm_degrid_ref" : "spmm_scatter_adj");
+            if (p->verify)
+                LAUNCH_OK(launch_spmm_rows_f64acc(s, ref ? c.adjRef.t : c.adjT.t, c.Xs, acc, c.nlam, 1));
+            else if (!ref && c.adjT.g.NG)
+                LAUNCH_OK(launch_spmm_group_scatter(s, c.adjT.g, c.Xs, acc, c.nlam));
+            else
+                LAUNCH_OK(launch_spmm_rows(s, ref ? c.adjRef.t : c.adjT.t, c.Xs, acc, c.nlam, 1));
+        }
+    }
+    if (adjoint_tail(p, acc, true)) return 1;
+    if (p->spec_out) return 0;         // the caller's vector is the spectrum
+    if (p->T > 0) {
+        if (irfft2_planes(p, p->mhat, p->maps_pad, p->T)) return 1;
+        Prof pr(p, "unpad_planes");
+        LAUNCH_OK(launch_unpad_planes(s, p->maps_pad, x, p->T, p->Na, p->Nb, p->NAP, p->NBP));
+    } else if (prod_capable(p)) {
+        // conj(OTF) x spectrum of the accumulated cube in the loader; inside the plane-wise normal operator mu rides on the pass and
+        // the quadratic prior comes in as a third operand: `mhat` still holds the spectrum of the vector the forward half was applied to
+        ProdOperand po;
+        po.prod = p->sotf; po.sign = -1.f; po.scale = p->pn_fold_prior ? (float)p->pl_mu : 1.f;
+        if (p->pn_fold_prior && p->pl_mu_reg != 0.0 && p->pl_mu != 0.0) {      // q = mu (A^T A d + (mu_r / mu) D^T D d)
+            po.add = p->mhat; po.add_w = (float)(p->pl_mu_reg / p->pl_mu);
+        }
+        float *const out = p->pn_native ? x : p->cube;
+        if (irfft2_cube(p, p->spec, out, false, false, &po)) return 1;
+        if (!p->pn_native) {
+            const long pl = (long)p->Na * p->Nb;
+            if (p->Lown < p->Lc) LAUNCH_OK(launch_fill_zero(s, x, (long)p->Lc * pl));   // planes no channel observes
+            Prof pr(p, "cube_transpose");
+            for (auto &g : p->segs)
+                LAUNCH_OK(launch_cube_from_lam_inner(s, p->cube + g.coff, x, g.start, g.len, p->Na, p->Nb, p->NAP, p->LP));
+        }
+    } else if (p->pn_native) {
+        if (irfft2_cube(p, p->mhat, x)) return 1;           // straight into the caller's wavelength-innermost vector
+    } else {
+        if (irfft2_cube(p, p->mhat, p->cube)) return 1;
+        const long pl = (long)p->Na * p->Nb;
+        if (p->Lown < p->Lc) LAUNCH_OK(launch_fill_zero(s, x, (long)p->Lc * pl));   // planes no channel observes
+        Prof pr(p, "cube_transpose");
+        for (auto &g : p->segs)
+            LAUNCH_OK(launch_cube_from_lam_inner(s, p->cube + g.coff, x, g.start, g.len, p->Na, p->Nb, p->NAP, p->LP));
+    }
+    return 0;
+}
+
+// the normal operator's two halves exchange the GEMM operands directly (SURFH_NORMAL_FUSED=0: through y)
+static bool normal_hand_over(const surfh_plan *p) {
+    static const bool fused = env_on("SURFH_NORMAL_FUSED", true);
+    return fused && !p->verify && !p->wblur_fp32;
+}
+
+// A^T W A v, the two halves of every normal operator: y is only the hand-over between them, and the channels' slab sums go
+// straight into the adjoint's GEMM operands (SURFH_NORMAL_FUSED=0: through y, as forward() + adjoint() do).  Data weights
+// (surfh_set_data_weights) ride on the hand-over: inside launch_ymat16w_from_cpart where y is never written, as one element-wise
+// pass over the part of y that is (verify plans, SURFH_WBLUR_FP32, SURFH_NORMAL_FUSED=0, channels without a spectral blur).
+int normal_halves(surfh_plan *p, const float *v, float *q) {
+    const bool ho = normal_hand_over(p);
+    if (forward_dev(p, v, p->cg_y, ho)) return 1;
+    if (p->dw) {
+        Prof pr(p, "weight_mul");
+        for (auto &c : p->ch)
+            if (!(ho && !c.bsum && c.ymat16)) LAUNCH_OK(launch_weight_mul(p->stream, p->cg_y + c.yoff, p->dw + c.yoff, c.ysize));
+    }
+    return adjoint_dev(p, p->cg_y, q, false, ho);
+}
+// the data of the solvers' right-hand side b = mu A^T W y: y itself without weights, else W y formed once per solve by a select
+const float *weighted_data(surfh_plan *p, const float *y) {
+    if (!p->dw) return y;
+    Prof pr(p, "weight_select");
+    if (launch_weight_select(p->stream, y, p->dw, p->dwy, p->osize) != 0) { fail("launch_weight_select failed"); return nullptr; }
+    return p->dwy;
+}
+
+int normal_dev(surfh_plan *p, const float *d, float *q, double mu) {
+    if (normal_halves(p, d, q)) return 1;
+    if (mu != 1.0) {
+        Prof pr(p, "scale");
+        LAUNCH_OK(launch_scale(p->stream, q, p->pn_native ? (long)p->NBP * p->NAP * p->LP : p->isize, (float)mu));
+    }
+    return 0;
+}
+
+// explicit per-frequency Hessian of Model_WCT and its work buffer: published only once both allocations and the launch
+// that fills `hth` have succeeded (a half-built pair would make the next call skip the launch)
+static int ensure_hessian(surfh_plan *p) {
+    if (p->hth && p->mhat2) return 0;
+    float *h = nullptr, *m2 = nullptr;
+    if (dev_alloc(&h, (size_t)p->T * p->T * p->PL) || dev_alloc(&m2, (size_t)p->T * 2 * p->PL)) {
+        hipFree(h);
+        hipFree(m2);
+        return 1;
+    }
+    const int rc = launch_wct_hessian(p->stream, p->sotf, p->tpl, h, p->T, p->PL, p->LP, p->ilv);
+    if (rc != 0) {
+        hipFree(h);
+        hipFree(m2);
+        return fail("launch_wct_hessian failed: %s", hipGetErrorString((hipError_t)rc));
+    }
+    p->hth = h;
+    p->mhat2 = m2;
+    return 0;
+}
+
+int ensure_cg(surfh_plan *p) {
+    if (p->cg_x) return 0;
+    // room for the vectors in either basis: the maps [T][Na][Nb] or their scaled half spectra [T][2][KAP][KBP]
+    const size_t n = std::max((size_t)p->isize, (size_t)2 * std::max(p->T, 0) * (size_t)p->PL);
+    for (float **v : {&p->cg_x, &p->cg_r, &p->cg_d, &p->cg_q, &p->cg_b})
+        if (dev_alloc(v, n)) return 1;
+    return 0;
+}
+
+}  // namespace surfh_impl
+
+extern "C" {
+
+int surfh_forward_dev(surfh_plan *p, const float *x, float *y) {
+    if (!p) return fail("null plan");
+    HIP_OK(hipSetDevice(p->dev));
+    return forward_dev(p, x, y);
+}
+int surfh_adjoint_dev(surfh_plan *p, const float *y, float *x) {
+    if (!p) return fail("null plan");
+    HIP_OK(hipSetDevice(p->dev));
+    return adjoint_dev(p, y, x, false);
+}
+int surfh_adjoint_ref_dev(surfh_plan *p, const float *y, float *x) {
+    if (!p) return fail("null plan");
+    HIP_OK(hipSetDevice(p->dev));
+    return adjoint_dev(p, y, x, true);
+}
+int surfh_fwadj_dev(surfh_plan *p, const float *x, float *out) {
+    if (!p) return fail("null plan");
+    HIP_OK(hipSetDevice(p->dev));
+    return normal_dev(p, x, out, 1.0);
+}
+
+static int host_call(surfh_plan *p, const float *in, long nin, float *outp, long nout, int which) {
+    if (!p || !in || !outp) return fail("null argument");
+    HIP_OK(hipSetDevice(p->dev));
+    float *din = (which == 0 || which == 3) ? p->io_x : p->io_y;
+    float *dout = (which == 0) ? p->io_y : p->io_x;
+    if (which == 3) {
+        if (ensure_cg(p)) return 1;
+        dout = p->cg_q;
+    }
+    HIP_OK(hipMemcpyAsync(din, in, nin * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    int rc = 0;
+    if (which == 0) rc = forward_dev(p, din, dout);
+    else if (which == 1) rc = adjoint_dev(p, din, dout, false);
+    else if (which == 2) rc = adjoint_dev(p, din, dout, true);
+    else rc = normal_dev(p, din, dout, 1.0);
+    if (rc) return rc;
+    HIP_OK(hipMemcpyAsync(outp, dout, nout * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int surfh_forward(surfh_plan *p, const float *maps, float *y) { return host_call(p, maps, p ? p->isize : 0, y, p ? p->osize : 0, 0); }
+int surfh_adjoint(surfh_plan *p, const float *y, float *maps) { return host_call(p, y, p ? p->osize : 0, maps, p ? p->isize : 0, 1); }
+int surfh_adjoint_ref(surfh_plan *p, const float *y, float *maps) { return host_call(p, y, p ? p->osize : 0, maps, p ? p->isize : 0, 2); }
+int surfh_fwadj(surfh_plan *p, const float *x, float *o) { return host_call(p, x, p ? p->isize : 0, o, p ? p->isize : 0, 3); }
+
+// ---- Model_WCT: the T.C stage alone, cube in the reference's [Lc][Na][Nb] layout ------------------
+static int wct_check(surfh_plan *p) {
+    if (!p) return fail("null plan");
+    if (p->T < 1) return fail("Model_WCT needs templates");
+    if (p->segs.size() != 1 || p->segs[0].start != 0 || p->segs[0].len != p->Lc) return fail("Model_WCT needs a plan that owns every cube plane");
+    if (hipSetDevice(p->dev) != hipSuccess) return fail("hipSetDevice failed");
+    const size_t n = (size_t)p->Lc * p->Na * p->Nb;
+    if (!p->io_cube && dev_alloc(&p->io_cube, n)) return 1;
+    return 0;
+}
+
+int surfh_wct_forward(surfh_plan *p, const float *maps, float *cube) {
+    if (wct_check(p)) return 1;
+    if (!maps || !cube) return fail("null argument");
+    hipStream_t s = p->stream;
+    HIP_OK(hipMemcpyAsync(p->io_x, maps, p->isize * sizeof(float), hipMemcpyHostToDevice, s));
+    LAUNCH_OK(launch_pad_planes(s, p->io_x, p->maps_pad, p->T, p->Na, p->Nb, p->NAP, p->NBP));
+    if (rfft2_planes(p, p->maps_pad, p->mhat, p->T)) return 1;
+    LAUNCH_OK(launch_specmix_fwd(s, p->mhat, p->sotf, p->tpl, p->spec, p->T, p->PL, p->LP, p->ilv));
+    if (irfft2_cube(p, p->spec, p->cube)) return 1;
+    LAUNCH_OK(launch_cube_from_lam_inner(s, p->cube, p->io_cube, 0, p->Lc, p->Na, p->Nb, p->NAP, p->LP));
+    HIP_OK(hipMemcpyAsync(cube, p->io_cube, (size_t)p->Lc * p->Na * p->Nb * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return 0;
+}
+
+int surfh_wct_adjoint(surfh_plan *p, const float *cube, float *maps) {
+    if (wct_check(p)) return 1;
+    if (!maps || !cube) return fail("null argument");
+    hipStream_t s = p->stream;
+    HIP_OK(hipMemcpyAsync(p->io_cube, cube, (size_t)p->Lc * p->Na * p->Nb * sizeof(float), hipMemcpyHostToDevice, s));
+    LAUNCH_OK(launch_fill_zero(s, p->cube, (long)p->NBP * p->NAP * p->LP));
+    LAUNCH_OK(launch_cube_to_lam_inner(s, p->io_cube, p->cube, 0, p->Lc, p->Na, p->Nb, p->NAP, p->LP));
+    if (adjoint_tail(p, p->cube)) return 1;
+    if (irfft2_planes(p, p->mhat, p->maps_pad, p->T)) return 1;
+    LAUNCH_OK(launch_unpad_planes(s, p->maps_pad, p->io_x, p->T, p->Na, p->Nb, p->NAP, p->NBP));
+    HIP_OK(hipMemcpyAsync(maps, p->io_x, p->isize * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return 0;
+}
+
+int surfh_wct_fwadj(surfh_plan *p, const float *x, float *out) {
+    if (wct_check(p)) return 1;
+    if (!x || !out) return fail("null argument");
+    hipStream_t s = p->stream;
+    if (ensure_hessian(p)) return 1;
+    HIP_OK(hipMemcpyAsync(p->io_x, x, p->isize * sizeof(float), hipMemcpyHostToDevice, s));
+    LAUNCH_OK(launch_pad_planes(s, p->io_x, p->maps_pad, p->T, p->Na, p->Nb, p->NAP, p->NBP));
+    if (rfft2_planes(p, p->maps_pad, p->mhat, p->T)) return 1;
+    LAUNCH_OK(launch_wct_hess_apply(s, p->hth, p->mhat, p->mhat2, p->T, p->PL));
+    if (irfft2_planes(p, p->mhat2, p->maps_pad, p->T)) return 1;
+    LAUNCH_OK(launch_unpad_planes(s, p->maps_pad, p->io_x, p->T, p->Na, p->Nb, p->NAP, p->NBP));
+    HIP_OK(hipMemcpyAsync(out, p->io_x, p->isize * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return 0;
+}
+
+// explicit inverse of the regularised normal operator (QuadCriterion3.run_expsol, fusion_mixing.py:309-438)
+int surfh_wct_expsol(surfh_plan *p, const float *cube, const double *mu_reg, const double *reg_freq, float *maps) {
+    if (wct_check(p)) return 1;
+    if (!maps || !cube || !mu_reg || !reg_freq) return fail("null argument");
+    for (int t = 0; t < p->T; ++t)
+        if (!(mu_reg[t] >= 0.0)) return fail("mu_reg[%d] must be >= 0", t);
+    hipStream_t s = p->stream;
+    if (ensure_hessian(p)) return 1;
+    // |D(f)|^2 into the padded spectral layout [KAP][KBP]; -1 marks the padding bins
+    const int hb = p->Nb / 2 + 1;
+    std::vector<float> reg((size_t)p->PL, -1.f);
+    for (int a = 0; a < p->Na; ++a)
+        for (int b = 0; b < hb; ++b) {
+            const double v = reg_freq[(size_t)a * hb + b];
+            if (!(v >= 0.0)) return fail("reg_freq must be >= 0");
+            reg[(size_t)a * p->KBP + b] = (float)v;
+        }
+    float *dreg = nullptr;
+    double *dmu = nullptr;
+    int *dflag = nullptr;
+    auto done = [&](int r) { hipFree(dreg); hipFree(dmu); hipFree(dflag); return r; };
+    if (dev_upload(&dreg, reg) || dev_alloc(&dmu, (size_t)p->T) || dev_alloc(&dflag, 1)) return done(1);
+    if (hipMemcpy(dmu, mu_reg, p->T * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(dflag, 0, sizeof(int)) != hipSuccess) return done(fail("copy failed"));
+    // b = H^T y in the Fourier domain (surfh_wct_adjoint up to the inverse transform)
+    if (hipMemcpyAsync(p->io_cube, cube, (size_t)p->Lc * p->Na * p->Nb * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess)
+        return done(fail("copy failed"));
+    int rc = launch_fill_zero(s, p->cube, (long)p->NBP * p->NAP * p->LP);
+    if (!rc) rc = launch_cube_to_lam_inner(s, p->io_cube, p->cube, 0, p->Lc, p->Na, p->Nb, p->NAP, p->LP);
+    if (rc) return done(fail("launch failed: %s", hipGetErrorString((hipError_t)rc)));
+    if (adjoint_tail(p, p->cube)) return done(1);
+    rc = launch_wct_solve(s, p->hth, dreg, dmu, p->mhat, p->mhat2, p->T, p->PL, dflag);
+    if (rc) return done(fail("launch failed: %s", hipGetErrorString((hipError_t)rc)));
+    if (irfft2_planes(p, p->mhat2, p->maps_pad, p->T)) return done(1);
+    rc = launch_unpad_planes(s, p->maps_pad, p->io_x, p->T, p->Na, p->Nb, p->NAP, p->NBP);
+    int flag = 0;
+    if (!rc) rc = (int)hipMemcpyAsync(maps, p->io_x, p->isize * sizeof(float), hipMemcpyDeviceToHost, s);
+    if (!rc) rc = (int)hipMemcpyAsync(&flag, dflag, sizeof(int), hipMemcpyDeviceToHost, s);
+    if (!rc) rc = (int)hipStreamSynchronize(s);
+    if (rc) return done(fail("expsol failed: %s", hipGetErrorString((hipError_t)rc)));
+    if (flag) return done(fail("the regularised normal matrix is singular at some frequency (numpy.linalg.inv would raise LinAlgError)"));
+    return done(0);
+}
+
+// ---- CG building blocks ---------------------------------------------------------------------
+int surfh_normal_dev(surfh_plan *p, const float *d, float *q, double mu) {
+    if (!p) return fail("null plan");
+    HIP_OK(hipSetDevice(p->dev));
+    return normal_dev(p, d, q, mu);
+}
+int surfh_prior_add_dev(surfh_plan *p, const float *d, float *q, double mu_reg) {
+    if (!p) return fail("null plan");
+    if (p->T <= 0) return fail("prior is defined on abundance maps (needs templates)");
+    HIP_OK(hipSetDevice(p->dev));
+    Prof pr(p, "prior_add");
+    LAUNCH_OK(prior_add(p, p->stream, d, q, p->T, (float)mu_reg));
+    return 0;
+}
+// ---- the normal operator on the maps' half spectra (the solver's vectors live in the Fourier domain) -------------------------
+// A vector is [T][2 (re, im)][KAP][KBP] floats (padding zero), bin (ka, kb) multiplied by sqrt(2) unless it is its own conjugate
+// (kb = 0, or 2 kb = Nb): the transforms are unitary, so plain dot products of such vectors are the dot products of the maps.
+namespace {
+int spec_check(surfh_plan *p) {
+    if (!p) return fail("null plan");
+    if (!(((p->adjmix_part && p->h2) || p->ct) && p->T > 0 && p->T <= 4 && p->fuse_mix && !p->dense_dft && !p->verify))
+        return fail("spectral-domain calls need the fused transform passes (dft_h2 with the fused adjoint tail, or dft_ct)");
+    HIP_OK(hipSetDevice(p->dev));
+    return 0;
+}
+struct SpecScope {      // the transient pointers never outlive a call
+    surfh_plan *p;
+    ~SpecScope() { p->spec_in = nullptr; p->spec_out = nullptr; p->spec_prior_src = nullptr; p->spec_mu = 1.f; p->spec_prior_mu = 0.f; }
+};
+}  // namespace
+
+int surfh_spec_supported(surfh_plan *p) {
+    return p && ((p->adjmix_part && p->h2) || p->ct) && p->T > 0 && p->T <= 4 && p->fuse_mix && !p->dense_dft && !p->verify && p->prior_kind == 0;
+}
+int64_t surfh_spec_size(surfh_plan *p) { return p ? (int64_t)2 * p->T * p->PL : 0; }
+
+// xt = scaled half spectra of the maps x [T][Na][Nb]
+int surfh_to_spec_dev(surfh_plan *p, const float *x, float *xt) {
+    if (spec_check(p)) return 1;
+    hipStream_t s = p->stream;
+    LAUNCH_OK(launch_pad_planes(s, x, p->maps_pad, p->T, p->Na, p->Nb, p->NAP, p->NBP));
+    if (rfft2_planes(p, p->maps_pad, p->mhat, p->T)) return 1;
+    LAUNCH_OK(launch_spec_scale(s, p->mhat, xt, 2 * p->T, p->PL, p->KBP, p->Nb, 1.f, 1.41421356237309505f));
+    return 0;
+}
+// x = maps of the scaled half spectra xt
+int surfh_from_spec_dev(surfh_plan *p, const float *xt, float *x) {
+    if (spec_check(p)) return 1;
+    hipStream_t s = p->stream;
+    LAUNCH_OK(launch_spec_scale(s, xt, p->mhat, 2 * p->T, p->PL, p->KBP, p->Nb, 1.f, 0.70710678118654752f));
+    if (irfft2_planes(p, p->mhat, p->maps_pad, p->T)) return 1;
+    LAUNCH_OK(launch_unpad_planes(s, p->maps_pad, x, p->T, p->Na, p->Nb, p->NAP, p->NBP));
+    return 0;
+}
+// y = A maps(dt)
+int surfh_forward_spec_dev(surfh_plan *p, const float *dt, float *y) {
+    if (spec_check(p)) return 1;
+    SpecScope sc{p};
+    p->spec_in = dt;
+    return forward_dev(p, nullptr, y);
+}
+// qt = mu * spectra(A^T y)  (+ mu_reg * prior(dt) when dt != NULL: only where q is not summed over ranks afterwards)
+int surfh_adjoint_spec_dev(surfh_plan *p, const float *y, float *qt, double mu, const float *dt, double mu_reg) {
+    if (spec_check(p)) return 1;
+    if (dt && p->prior_kind != 0) return fail("the fused spectral prior is the separated first differences");
+    SpecScope sc{p};
+    p->spec_out = qt; p->spec_mu = (float)mu; p->spec_prior_src = dt; p->spec_prior_mu = dt ? (float)mu_reg : 0.f;
+    return adjoint_dev(p, y, nullptr, false);
+}
+// qt = mu * spectra(A^T A maps(dt)) (+ mu_reg * prior(dt) if mu_reg != 0): the CG's normal operator without a single transform
+// of the maps -- no padding, no small DFTs, no prior kernel
+int surfh_normal_spec_dev(surfh_plan *p, const float *dt, float *qt, double mu, double mu_reg) {
+    if (spec_check(p)) return 1;
+    if (mu_reg != 0.0 && p->prior_kind != 0) return fail("the fused spectral prior is the separated first differences");
+    SpecScope sc{p};
+    p->spec_in = dt;
+    p->spec_out = qt; p->spec_mu = (float)mu; p->spec_prior_src = mu_reg != 0.0 ? dt : nullptr; p->spec_prior_mu = (float)mu_reg;
+    return normal_halves(p, nullptr, nullptr);
+}
+// qt += mu_reg * prior(dt) on scaled half spectra (after an all-reduce of qt over ranks)
+int surfh_prior_spec_add_dev(surfh_plan *p, const float *dt, float *qt, double mu_reg) {
+    if (spec_check(p)) return 1;
+    if (p->prior_kind != 0) return fail("the spectral prior is the separated first differences");
+    LAUNCH_OK(launch_spec_prior_add(p->stream, dt, qt, 2 * p->T, p->Na, p->Nb, p->PL, p->KBP, (float)mu_reg));
+    return 0;
+}
+
+// ---- drivers' LMM helpers on the device (spectroModel.py:187-198) -----------------------------
+static int lmm_host(surfh_plan *p, const double *templates, int32_t T, int32_t L, const float *in, float *out, bool to_cube) {
+    if (!p || !templates || !in || !out) return fail("null argument");
+    if (T < 1 || L < 1) return fail("bad template shape");
+    HIP_OK(hipSetDevice(p->dev));
+    const long npix = (long)p->Na * p->Nb;
+    std::vector<float> t((size_t)T * L);
+    for (size_t i = 0; i < t.size(); ++i) t[i] = (float)templates[i];
+    float *dt = nullptr, *dm = nullptr, *dc = nullptr;
+    int rc = 0;
+    auto done = [&](int r) { hipFree(dt); hipFree(dm); hipFree(dc); return r; };
+    if (dev_upload(&dt, t) || dev_alloc(&dm, (size_t)T * npix) || dev_alloc(&dc, (size_t)L * npix)) return done(1);
+    hipStream_t s = p->stream;
+    if (to_cube) {
+        if (hipMemcpyAsync(dm, in, (size_t)T * npix * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess) return done(fail("copy failed"));
+        rc = launch_lmm_maps2cube(s, dm, dt, dc, T, L, npix);
+        if (!rc) rc = (int)hipMemcpyAsync(out, dc, (size_t)L * npix * sizeof(float), hipMemcpyDeviceToHost, s);
+    } else {
+        if (hipMemcpyAsync(dc, in, (size_t)L * npix * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess) return done(fail("copy failed"));
+        rc = launch_lmm_cube2maps(s, dc, dt, dm, T, L, npix);
+        if (!rc) rc = (int)hipMemcpyAsync(out, dm, (size_t)T * npix * sizeof(float), hipMemcpyDeviceToHost, s);
+    }
+    if (!rc) rc = (int)hipStreamSynchronize(s);
+    if (rc) return done(fail("lmm: %s", hipGetErrorString((hipError_t)rc)));
+    return done(0);
+}
+int surfh_maps_to_cube(surfh_plan *p, const double *templates, int32_t T, int32_t L, const float *maps, float *cube) {
+    return lmm_host(p, templates, T, L, maps, cube, true);
+}
+int surfh_cube_to_maps(surfh_plan *p, const double *templates, int32_t T, int32_t L, const float *cube, float *maps) {
+    return lmm_host(p, templates, T, L, cube, maps, false);
+}
+
+}  // extern "C"

@@ -1,0 +1,1027 @@
+// Host side of the C ABI (include/surfh_amd.h), the solvers: the CG building blocks, surfh_cg, the 3MG loops (quadratic, Huber,
+// voxel-wise, robust data term) with their prior / curvature diagnostics, and the plane-wise solvers.  They call the operators of
+// plan_ops.hip and nothing calls them.  Plan struct and data layout: plan_internal.h.
+#include "plan_internal.h"
+#include "mm_step.h"
+
+extern "C" {
+
+int surfh_dot_dev(surfh_plan *p, const float *a, const float *b, int64_t n, double *out) {
+    if (!p) return fail("null plan");
+    HIP_OK(hipSetDevice(p->dev));
+    LAUNCH_OK(launch_dot(p->stream, a, b, n, p->dscratch, p->dscal + 7));
+    HIP_OK(hipMemcpyAsync(out, p->dscal + 7, sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+int surfh_cg_step_dev(surfh_plan *p, float *x, float *r, const float *d, const float *q, int64_t n, double rr_in,
+                      double *rr_out) {
+    if (!p) return fail("null plan");
+    HIP_OK(hipSetDevice(p->dev));
+    HIP_OK(hipMemcpyAsync(p->dscal + 0, &rr_in, sizeof(double), hipMemcpyHostToDevice, p->stream));
+    LAUNCH_OK(launch_dot(p->stream, d, q, n, p->dscratch, p->dscal + 1));
+    LAUNCH_OK(launch_cg_step(p->stream, x, r, d, q, n, p->dscal + 0, p->dscal + 1, p->dscratch, p->dscal + 2));
+    HIP_OK(hipMemcpyAsync(rr_out, p->dscal + 2, sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+int surfh_cg_dir_dev(surfh_plan *p, float *d, const float *r, int64_t n, double beta) {
+    if (!p) return fail("null plan");
+    HIP_OK(hipSetDevice(p->dev));
+    const double one = 1.0;
+    HIP_OK(hipMemcpyAsync(p->dscal + 3, &beta, sizeof(double), hipMemcpyHostToDevice, p->stream));
+    HIP_OK(hipMemcpyAsync(p->dscal + 4, &one, sizeof(double), hipMemcpyHostToDevice, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));   // host scalars are stack variables
+    LAUNCH_OK(launch_cg_dir(p->stream, d, r, n, p->dscal + 3, p->dscal + 4));
+    return 0;
+}
+// cg_step + cg_dir in one call with one host synchronisation: x += s d, r -= s q, rr' = r.r, d = r + (rr'/rr) d
+int surfh_cg_iter_dev(surfh_plan *p, float *x, float *r, float *d, const float *q, int64_t n, double rr_in, double *rr_out) {
+    if (!p) return fail("null plan");
+    HIP_OK(hipSetDevice(p->dev));
+    HIP_OK(hipMemcpyAsync(p->dscal + 0, &rr_in, sizeof(double), hipMemcpyHostToDevice, p->stream));
+    LAUNCH_OK(launch_dot(p->stream, d, q, n, p->dscratch, p->dscal + 1));
+    LAUNCH_OK(launch_cg_step(p->stream, x, r, d, q, n, p->dscal + 0, p->dscal + 1, p->dscratch, p->dscal + 2));
+    LAUNCH_OK(launch_cg_dir(p->stream, d, r, n, p->dscal + 2, p->dscal + 0));
+    HIP_OK(hipMemcpyAsync(rr_out, p->dscal + 2, sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));   // also covers the pageable rr_in copy
+    return 0;
+}
+// ---- the same blocks with every scalar kept on the device: nothing here synchronises with the host.  The trace cg_hist IS the
+// scalar store: r.r of the current iterate is its last entry, an iteration reads it there and writes the next entry (read back
+// with surfh_cg_trace).  An iteration is three launches -- partial sums of d.q; step (sums them, leaves partial sums of the new
+// r.r); direction (sums those) -- and no copies (round 2: five launches and two 8-byte device-to-device copies, 42 us of an
+// iteration's 2.87 ms on config 3).  For the multi-GPU loop: the only other work of an iteration is the normal operator and
+// the all-reduce, both asynchronous on the plan's stream.
+static constexpr int CG_HIST_CAP = 1 << 16;
+static int cg_hist_room(surfh_plan *p) {
+    if (!p->cg_hist && dev_alloc(&p->cg_hist, (size_t)CG_HIST_CAP)) return 1;
+    if (p->cg_hist_n >= CG_HIST_CAP) return fail("CG trace full (%d iterations): read it with surfh_cg_trace", CG_HIST_CAP);
+    return 0;
+}
+int surfh_cg_begin_dev(surfh_plan *p, const float *r, int64_t n) {         /* rr = r.r; trace restarts with it */
+    if (!p) return fail("null plan");
+    HIP_OK(hipSetDevice(p->dev));
+    p->cg_hist_n = 0;
+    if (cg_hist_room(p)) return 1;
+    LAUNCH_OK(launch_dot(p->stream, r, r, n, p->dscratch, p->cg_hist + 0));
+    p->cg_hist_n = 1;
+    return 0;
+}
+int surfh_cg_iter_nosync_dev(surfh_plan *p, float *x, float *r, float *d, const float *q, int64_t n) {
+    if (!p) return fail("null plan");
+    HIP_OK(hipSetDevice(p->dev));
+    if (p->cg_hist_n < 1) return fail("surfh_cg_iter_nosync_dev before surfh_cg_begin_dev");
+    if (cg_hist_room(p)) return 1;
+    double *const rr = p->cg_hist + p->cg_hist_n - 1, *const pa = p->dscratch, *const pb = p->dscratch + dot_parts_stride();
+    LAUNCH_OK(launch_dot_parts(p->stream, d, q, n, pa));
+    LAUNCH_OK(launch_cg_step_parts(p->stream, x, r, d, q, n, rr, pa, p->dscal + 1, pb));
+    LAUNCH_OK(launch_cg_dir_parts(p->stream, d, r, n, pb, rr, rr + 1));
+    ++p->cg_hist_n;
+    return 0;
+}
+/* the residual-refresh iteration of qmm.lcg in two halves around the caller's normal operator on x:
+ * x += (rr / d.q) d   ...   r = b - q; rr' = r.r; d = r + (rr' / rr) d; rr = rr'                                   */
+int surfh_cg_xupdate_nosync_dev(surfh_plan *p, float *x, const float *d, const float *q, int64_t n) {
+    if (!p) return fail("null plan");
+    HIP_OK(hipSetDevice(p->dev));
+    if (p->cg_hist_n < 1) return fail("surfh_cg_xupdate_nosync_dev before surfh_cg_begin_dev");
+    LAUNCH_OK(launch_dot(p->stream, d, q, n, p->dscratch, p->dscal + 1));
+    LAUNCH_OK(launch_cg_xupdate(p->stream, x, d, n, p->cg_hist + p->cg_hist_n - 1, p->dscal + 1));
+    return 0;
+}
+int surfh_cg_refresh_nosync_dev(surfh_plan *p, float *r, const float *b, const float *q, float *d, int64_t n) {
+    if (!p) return fail("null plan");
+    HIP_OK(hipSetDevice(p->dev));
+    if (p->cg_hist_n < 1) return fail("surfh_cg_refresh_nosync_dev before surfh_cg_begin_dev");
+    if (cg_hist_room(p)) return 1;
+    double *const rr = p->cg_hist + p->cg_hist_n - 1, *const pb = p->dscratch + dot_parts_stride();
+    LAUNCH_OK(launch_residual(p->stream, r, b, q, n));
+    LAUNCH_OK(launch_dot_parts(p->stream, r, r, n, pb));
+    LAUNCH_OK(launch_cg_dir_parts(p->stream, d, r, n, pb, rr, rr + 1));
+    ++p->cg_hist_n;
+    return 0;
+}
+/* synchronises the plan's stream and copies the r.r trace (entry 0 = surfh_cg_begin_dev); returns the number of entries */
+int32_t surfh_cg_trace(surfh_plan *p, double *out, int32_t cap) {
+    if (!p || !out) return -1;
+    if (hipSetDevice(p->dev) != hipSuccess) return -1;
+    const int n = p->cg_hist_n < cap ? p->cg_hist_n : cap;
+    if (hipStreamSynchronize(p->stream) != hipSuccess) return -1;
+    if (n > 0 && hipMemcpy(out, p->cg_hist, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return n;
+}
+int surfh_residual_dev(surfh_plan *p, float *r, const float *b, const float *q, int64_t n) {
+    if (!p) return fail("null plan");
+    HIP_OK(hipSetDevice(p->dev));
+    LAUNCH_OK(launch_residual(p->stream, r, b, q, n));
+    return 0;
+}
+
+// ---- full CG on one GPU (qmm.lcg semantics, see oracle/surfh_oracle.py:lcg) -------------------
+namespace {
+// out = Q v = mu A^T A v (+ mu_reg prior(v)): the operator of the map- and plane-domain solvers
+int normal_prior(surfh_plan *p, const float *v, float *out, double mu, double mu_reg) {
+    if (normal_dev(p, v, out, mu)) return 1;
+    if (mu_reg != 0.0) {
+        Prof pr(p, "prior_add");
+        LAUNCH_OK(prior_add(p, p->stream, v, out, p->T > 0 ? p->T : p->Lc, (float)mu_reg));
+    }
+    return 0;
+}
+// cg_b = mu A^T W y, cg_q = Q x, cg_r = cg_b - cg_q; y on the device, x already holding the start
+int solver_setup(surfh_plan *p, const float *y, const float *x, double mu, double mu_reg) {
+    if (!(y = weighted_data(p, y))) return 1;
+    if (adjoint_dev(p, y, p->cg_b, false)) return 1;
+    if (mu != 1.0) LAUNCH_OK(launch_scale(p->stream, p->cg_b, p->isize, (float)mu));
+    if (normal_prior(p, x, p->cg_q, mu, mu_reg)) return 1;
+    LAUNCH_OK(launch_residual(p->stream, p->cg_r, p->cg_b, p->cg_q, p->isize));
+    return 0;
+}
+// hands the iterate x (device) after iteration `it` to the callback, if any; the work buffers hold nothing live between
+// iterations, so the callback may run forward / adjoint on this plan
+enum { CB_GO_ON = 0, CB_ERROR = 1, CB_STOP = 2 };
+int callback_iterate(surfh_plan *p, surfh_cg_callback callback, void *user, int it, const double *grad_norm, const float *x,
+                     std::vector<float> &hx) {
+    if (!callback) return CB_GO_ON;
+    hx.resize((size_t)p->isize);
+    HIP_OK(hipMemcpyAsync(hx.data(), x, p->isize * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    if (callback(user, it, grad_norm, hx.data())) return CB_STOP;
+    HIP_OK(hipSetDevice(p->dev));
+    return CB_GO_ON;
+}
+
+// ---- the frame of every 3MG loop (the variants and what each plugs in: the 3MG sections below) ----
+// Start: the work buffers (cg_hg where the variant keeps -g apart from r), y [osize] to yd, x0 or zeros to cg_x, zeros to the
+// memory direction cg_d and to its image: cg_qm (with cg_dd beside it), or the caller's detector vector `am` [osize].
+int mmmg_begin(surfh_plan *p, bool want_hg, const float *y, float *yd, const float *x0, float *am = nullptr) {
+    hipStream_t s = p->stream;
+    if (ensure_cg(p)) return 1;
+    if (!am && !p->cg_qm && (dev_alloc(&p->cg_qm, (size_t)p->isize) || dev_alloc(&p->cg_dd, (size_t)p->isize))) return 1;
+    if (want_hg && !p->cg_hg && dev_alloc(&p->cg_hg, (size_t)p->isize)) return 1;
+    HIP_OK(hipMemcpyAsync(yd, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
+    if (x0)
+        HIP_OK(hipMemcpyAsync(p->cg_x, x0, p->isize * sizeof(float), hipMemcpyHostToDevice, s));
+    else
+        LAUNCH_OK(launch_fill_zero(s, p->cg_x, p->isize));
+    LAUNCH_OK(launch_fill_zero(s, p->cg_d, p->isize));
+    if (am)
+        LAUNCH_OK(launch_fill_zero(s, am, p->osize));
+    else
+        LAUNCH_OK(launch_fill_zero(s, p->cg_qm, p->isize));
+    return 0;
+}
+// Top of iteration `it`, once its trace entry is stored: the callback sees the iterate (it > 0), then the stopping rule on
+// `norm` (the gradient norm; the largest over the planes) against scale * tol.  CB_STOP: leave the loop, the result stands.
+int mmmg_check(surfh_plan *p, surfh_cg_callback callback, void *user, int it, int max_iter, const double *grad_norm, double norm,
+               double scale, double tol, std::vector<float> &hx) {
+    if (it > 0)
+        if (const int rc = callback_iterate(p, callback, user, it, grad_norm, p->cg_x, hx)) return rc;
+    return it >= max_iter || norm < scale * tol ? CB_STOP : CB_GO_ON;
+}
+// the carried vector (r, or u = A x) is recomputed from x in the iterations `refresh` divides
+bool refresh_due(int refresh, int it) { return refresh > 0 && it % refresh == 0; }
+int mmmg_finish(surfh_plan *p, float *x) {
+    HIP_OK(hipMemcpyAsync(x, p->cg_x, p->isize * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+// A device diagnostic of one pass: the launch under its Prof name, then k doubles from `src` (device) to `dst` (host).
+int diag_pass(surfh_plan *p, const char *name, const std::function<int()> &launch, const double *src, double *dst, size_t k) {
+    HIP_OK(hipSetDevice(p->dev));
+    {
+        Prof pr(p, name);
+        LAUNCH_OK(launch());
+    }
+    HIP_OK(hipMemcpyAsync(dst, src, k * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+// The loop bench.py times, behind the exported solver: vectors = the maps' Parseval-scaled half spectra (surfh_normal_spec_dev:
+// no transform of the maps, no padding, no prior kernel inside an iteration), every scalar on the device
+// (surfh_cg_iter_nosync_dev), and the host reads the r.r trace -- the stopping test of qmm.lcg -- only every CG_CHECK iterations:
+// the loop may run up to CG_CHECK - 1 iterations past the one that met the tolerance (nit and x are those of the last iteration
+// run, grad_norm holds every r.r).  With a callback installed the trace and the iterate go to the host after every iteration,
+// as the callback's contract says.
+constexpr int CG_CHECK = 8;
+int cg_spectral(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol, int32_t refresh,
+                float *x, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
+    std::vector<float> hx;             // host copy of the iterate handed to the callback
+    hipStream_t s = p->stream;
+    const long n = p->isize, nv = 2L * p->T * p->PL;
+    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
+    const float *wy = weighted_data(p, p->io_y);
+    if (!wy || surfh_adjoint_spec_dev(p, wy, p->cg_b, mu, nullptr, 0.0)) return 1;          // b = mu A^T W y
+    if (x0) {
+        HIP_OK(hipMemcpyAsync(p->io_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
+        if (surfh_to_spec_dev(p, p->io_x, p->cg_x) || surfh_normal_spec_dev(p, p->cg_x, p->cg_q, mu, mu_reg)) return 1;
+        LAUNCH_OK(launch_residual(s, p->cg_r, p->cg_b, p->cg_q, nv));
+    } else {                                                                                // r = b - Q 0
+        LAUNCH_OK(launch_fill_zero(s, p->cg_x, nv));
+        HIP_OK(hipMemcpyAsync(p->cg_r, p->cg_b, nv * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    HIP_OK(hipMemcpyAsync(p->cg_d, p->cg_r, nv * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (surfh_cg_begin_dev(p, p->cg_r, nv)) return 1;
+    *nit = 0;
+    for (int it = 0; it < max_iter; ++it) {
+        if (surfh_normal_spec_dev(p, p->cg_d, p->cg_q, mu, mu_reg)) return 1;
+        if (refresh > 0 && it % refresh == 0) {             // residual recomputed from scratch
+            if (surfh_cg_xupdate_nosync_dev(p, p->cg_x, p->cg_d, p->cg_q, nv) || surfh_normal_spec_dev(p, p->cg_x, p->cg_q, mu, mu_reg) ||
+                surfh_cg_refresh_nosync_dev(p, p->cg_r, p->cg_b, p->cg_q, p->cg_d, nv))
+                return 1;
+        } else if (surfh_cg_iter_nosync_dev(p, p->cg_x, p->cg_r, p->cg_d, p->cg_q, nv)) {
+            return 1;
+        }
+        *nit = it + 1;
+        if (!callback && (it + 1) % CG_CHECK != 0 && it + 1 != max_iter) continue;
+        if (surfh_cg_trace(p, grad_norm, it + 2) != it + 2) return fail("CG trace read failed");     // synchronises
+        if (callback && surfh_from_spec_dev(p, p->cg_x, p->io_x)) return 1;
+        if (const int rc = callback_iterate(p, callback, user, it + 1, grad_norm, p->io_x, hx)) {
+            if (rc == CB_STOP) break;
+            return 1;
+        }
+        if (std::sqrt(grad_norm[it + 1]) < (double)n * tol) break;
+    }
+    if (surfh_cg_trace(p, grad_norm, *nit + 1) != *nit + 1) return fail("CG trace read failed");
+    if (surfh_from_spec_dev(p, p->cg_x, p->io_x)) return 1;
+    HIP_OK(hipMemcpyAsync(x, p->io_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return 0;
+}
+}  // namespace
+
+int surfh_cg_cb(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
+                int32_t refresh, float *x, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
+    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (p->T <= 0) return fail("surfh_cg needs templates (the priors act on abundance maps)");
+    HIP_OK(hipSetDevice(p->dev));
+    if (ensure_cg(p)) return 1;
+    {   // SURFH_SPECTRAL_CG=0: vectors are the maps (the loop below)
+        if (env_on("SURFH_SPECTRAL_CG", true) && surfh_spec_supported(p) && max_iter < (1 << 16) - 1)
+            return cg_spectral(p, y, mu, mu_reg, x0, max_iter, tol, refresh, x, grad_norm, nit, callback, user);
+    }
+    std::vector<float> hx;             // host copy of the iterate handed to the callback
+    hipStream_t s = p->stream;
+    const long n = p->isize;
+    double *rr = p->dscal + 0, *dq = p->dscal + 1, *rrn = p->dscal + 2;
+    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
+    if (x0)
+        HIP_OK(hipMemcpyAsync(p->cg_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
+    else
+        LAUNCH_OK(launch_fill_zero(s, p->cg_x, n));
+    if (solver_setup(p, p->io_y, p->cg_x, mu, mu_reg)) return 1;
+    HIP_OK(hipMemcpyAsync(p->cg_d, p->cg_r, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    LAUNCH_OK(launch_dot(s, p->cg_r, p->cg_r, n, p->dscratch, rr));
+    HIP_OK(hipMemcpyAsync(&grad_norm[0], rr, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    *nit = 0;
+    for (int it = 0; it < max_iter; ++it) {
+        if (normal_prior(p, p->cg_d, p->cg_q, mu, mu_reg)) return 1;
+        LAUNCH_OK(launch_dot(s, p->cg_d, p->cg_q, n, p->dscratch, dq));
+        if (refresh > 0 && it % refresh == 0) {
+            LAUNCH_OK(launch_cg_xupdate(s, p->cg_x, p->cg_d, n, rr, dq));
+            if (normal_prior(p, p->cg_x, p->cg_q, mu, mu_reg)) return 1;
+            LAUNCH_OK(launch_residual(s, p->cg_r, p->cg_b, p->cg_q, n));
+            LAUNCH_OK(launch_dot(s, p->cg_r, p->cg_r, n, p->dscratch, rrn));
+        } else {
+            Prof pr(p, "cg_step");
+            LAUNCH_OK(launch_cg_step(s, p->cg_x, p->cg_r, p->cg_d, p->cg_q, n, rr, dq, p->dscratch, rrn));
+        }
+        LAUNCH_OK(launch_cg_dir(s, p->cg_d, p->cg_r, n, rrn, rr));
+        HIP_OK(hipMemcpyAsync(rr, rrn, sizeof(double), hipMemcpyDeviceToDevice, s));
+        HIP_OK(hipMemcpyAsync(&grad_norm[it + 1], rrn, sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        *nit = it + 1;
+        if (const int rc = callback_iterate(p, callback, user, it + 1, grad_norm, p->cg_x, hx)) {
+            if (rc == CB_STOP) break;
+            return 1;
+        }
+        if (std::sqrt(grad_norm[it + 1]) < (double)n * tol) break;
+    }
+    HIP_OK(hipMemcpyAsync(x, p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return 0;
+}
+
+int surfh_cg(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
+             int32_t refresh, float *x, double *grad_norm, int32_t *nit) {
+    return surfh_cg_cb(p, y, mu, mu_reg, x0, max_iter, tol, refresh, x, grad_norm, nit, nullptr, nullptr);
+}
+
+// ---- 3MG (majorize-minimize memory gradient, qmm.mmmg; selected by method != 'lcg' at fusion_CT.py:194-198) ----
+// Every variant minimises a quadratic majorant with matrix B(x) at the iterate over span{-g, m}, m the previous move.  qmm
+// solves the 2x2 system in the basis [-g, m] with the operator applied to the gradient; in fp32 that form loses the conjugacy
+// (the determinant cancels) and was measured to converge visibly slower than CG.  The same subspace is therefore spanned by
+// [d, m], d = -g + beta m made B-orthogonal to m with the carried image of m, and the operator is applied to d: the system
+//   [[d.Bd, d.Bm], [d.Bm, m.Bm]] step = [d.(-g), m.(-g)]                                   (mm_step.h: mm_step2)
+// is then nearly diagonal.  Same iterates in exact arithmetic, one operator application per iteration; the carried residual
+// follows by linearity and is recomputed from x every `refresh` iterations.  numpy's pinv cut (1e-15 of the unscaled matrix),
+// which in qmm drops the memory direction once |move|^2 / |grad|^2 < 1e-15, is not reproduced: the direction is dropped only
+// when the scaled system is singular.  All loops stand on one frame (mmmg_begin, mmmg_check, refresh_due, mmmg_finish):
+//   mmmg_huber_loop    surfh_mmmg, surfh_mmmg_huber, surfh_mmmg_huber_vox       beta and the system on the host, 2 syncs / iteration
+//   mmmg_robust_loop   surfh_mmmg_robust, surfh_mmmg_robust_vox                 one read-back, 1 sync / iteration
+//   mmmg_planes_loop   surfh_mmmg_planes_cb, surfh_mmmg_huber_planes            beta and the system per plane on the device, 1 sync
+//
+// Huber priors (qmm.Huber on the row and column differences: the reference's lmm_reconstruction,
+// surfh/ToolsDir/algorithms.py:73-106).  The majorant at x is half-quadratic (Geman-Reynolds):
+//   B(x) = mu A^T A + mu_reg sum_k D_k^T diag(w(D_k x)) D_k,   w(u) = phi'(u) / u.
+// beta comes from the carried data image Q_D m = mu A^T A m and the prior block huber_curv(x; -g, m); the data part
+// r = b - mu A^T A x of -g is the carried residual.  Two stencil passes per iteration, each followed by a one-block reduction:
+// huber_grad gives -g = r - mu_reg sum_k D_k^T phi'(D_k x), |g|^2 and the prior value; huber_curv gives the prior block
+// c = [(-g).W(-g), (-g).W m, m.W m] (W = D^T diag(w) D at x).  The block of (d, m) follows from c by linearity in float64
+// (mm_block_of_d); d.Bd = g.Bg - (g.Bm)^2 / m.Bm is the Schur complement of a positive semi-definite 2x2 matrix, which float64
+// forms from fp64-accumulated sums with no cancellation that matters at fp32 data precision.
+// The quadratic solver surfh_mmmg is the same loop with no Huber family: its prior rides in the operator Q = mu A^T A + mu_reg
+// prior, so -g is the carried residual r itself, the grad pass is the dot r.r and there is no curv pass; the majorant is the
+// criterion, the step its exact minimiser over the subspace.
+namespace {
+// the kernels take delta in fp32: a positive delta below FLT_MIN would flush to 0 there (every weight off u = 0 would vanish)
+int huber_args(double mu_reg, double delta) {
+    if (std::isnan(mu_reg) || std::isnan(delta)) return fail("Huber prior: mu_reg and delta must not be NaN");
+    if (!(delta >= (double)FLT_MIN)) return fail("Huber prior: delta must be at least %g (fp32 kernels; got %g)", (double)FLT_MIN, delta);
+    return 0;
+}
+}  // namespace
+
+int surfh_huber_prior_dev(surfh_plan *p, const float *x_dev, float *g_dev, double mu_reg, double delta, double *value) {
+    if (!p || !x_dev || !g_dev) return fail("null argument");
+    if (p->T <= 0) return fail("prior is defined on abundance maps (needs templates)");
+    if (huber_args(mu_reg, delta)) return 1;
+    double h[2];
+    const auto pass = [&] {
+        return launch_huber_grad(p->stream, x_dev, g_dev, g_dev, p->T, p->Na, p->Nb, (float)mu_reg, (float)delta, p->pot[0], p->dscratch,
+                                 p->dscal);
+    };
+    if (diag_pass(p, "huber_grad", pass, p->dscal, h, 2)) return 1;
+    if (value) *value = h[1];
+    return 0;
+}
+int surfh_huber_curv_dev(surfh_plan *p, const float *x_dev, const float *p0_dev, const float *p1_dev, double delta, double *sums) {
+    if (!p || !x_dev || !p0_dev || !p1_dev || !sums) return fail("null argument");
+    if (p->T <= 0) return fail("prior is defined on abundance maps (needs templates)");
+    if (huber_args(0.0, delta)) return 1;
+    const auto pass = [&] {
+        return launch_huber_curv(p->stream, x_dev, p0_dev, p1_dev, p->T, p->Na, p->Nb, (float)delta, p->pot[0], p->dscratch, p->dscal);
+    };
+    return diag_pass(p, "huber_curv", pass, p->dscal, sums, 3);
+}
+
+namespace {
+// The prior of one 3MG run: `nfam` families of differences with their weights, and the two stencil passes on the solver's
+// vectors.  grad: out = src - sum_f reg[f] D_f^T phi'(D_f x), sums[0] = out.out, sums[1 + f] = sum phi of family f;
+// curv: sums[3 f ..] = the (p0, p0), (p0, p1), (p1, p1) block of family f under w(D_f x).  The weights enter on the host, in float64.
+// nfam = 0 is the quadratic solver: out is src itself (grad leaves sums[0] = src.src), the prior is quad_reg's, in the operator.
+struct HuberPrior {
+    int nfam;
+    double reg[2];
+    const char *what;                                                       // names the solver in its error message
+    int (*grad)(surfh_plan *p, const HuberPrior &h, const float *x, const float *src, float *out, double *sums);
+    int (*curv)(surfh_plan *p, const HuberPrior &h, const float *x, const float *p0, const float *p1, double *sums);
+    float delta[2];
+    int kind[2];                                                            // the potential of each family (surfh_set_potential)
+    double quad_reg;                                                        // weight of the quadratic prior the operator carries
+};
+
+// the loop of the map and cube solvers; prior_values receives nfam doubles (may be NULL)
+int mmmg_huber_loop(surfh_plan *p, const HuberPrior &hp, const float *y, double mu, const float *x0, int32_t max_iter, double tol,
+                    int32_t refresh, float *x, double *grad_norm, int32_t *nit, double *prior_values, surfh_cg_callback callback,
+                    void *user) {
+    std::vector<float> hx;
+    HIP_OK(hipSetDevice(p->dev));
+    if (mmmg_begin(p, hp.nfam > 0, y, p->io_y, x0)) return 1;
+    hipStream_t s = p->stream;
+    const long n = p->isize;
+    const int F = hp.nfam;
+    float *r = p->cg_r, *m = p->cg_d, *d = p->cg_dd, *qd = p->cg_q, *qm = p->cg_qm, *ng = F ? p->cg_hg : r;
+    // [0 .. F] the grad pass (|g|^2, F prior values), [F+1, F+2] dots, [F+3 .. 4F+2] the curv pass; then the step's four dots
+    // over the block just read (the quadratic solver's behind it)
+    double *sc = p->dscal, *sd = sc + (F ? 0 : 3);
+    if (solver_setup(p, p->io_y, p->cg_x, mu, hp.quad_reg)) return 1;  // r = b - Q x: the data part of -g (all of it when F = 0)
+    double h[11], prior[2] = {0.0, 0.0};
+    *nit = 0;
+    for (int it = 0;; ++it) {
+        // -g, |g|^2 and the prior values; then -g.Qm, m.Qm and the prior blocks of (-g, m) under w(D x)
+        if (hp.grad(p, hp, p->cg_x, r, ng, sc + 0)) return 1;
+        LAUNCH_OK(launch_dot(s, ng, qm, n, p->dscratch, sc + F + 1));
+        LAUNCH_OK(launch_dot(s, m, qm, n, p->dscratch, sc + F + 2));
+        if (hp.curv(p, hp, p->cg_x, ng, m, sc + F + 3)) return 1;
+        HIP_OK(hipMemcpyAsync(h, sc, (3 + 4 * F) * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        grad_norm[it] = std::sqrt(h[0]);
+        for (int f = 0; f < F; ++f) prior[f] = h[1 + f];
+        if (const int rc = mmmg_check(p, callback, user, it, max_iter, grad_norm, grad_norm[it], (double)n, tol, hx)) {
+            if (rc == CB_STOP) break;
+            return 1;
+        }
+        double c[2][3], gBm = h[F + 1], mBm = h[F + 2];
+        for (int f = 0; f < F; ++f) {
+            for (int k = 0; k < 3; ++k) c[f][k] = h[F + 3 + 3 * f + k];
+            gBm += hp.reg[f] * c[f][1];
+            mBm += hp.reg[f] * c[f][2];
+        }
+        const double beta = mBm > 0.0 ? -gBm / mBm : 0.0;
+        LAUNCH_OK(launch_lincomb(s, d, ng, m, n, beta));
+        if (normal_prior(p, d, qd, mu, hp.quad_reg)) return 1;
+        // h0 = d.Qd, h1 = d.Qm, h2 = d.(-g), h3 = m.(-g)
+        LAUNCH_OK(launch_dot(s, d, qd, n, p->dscratch, sd + 0));
+        LAUNCH_OK(launch_dot(s, d, qm, n, p->dscratch, sd + 1));
+        LAUNCH_OK(launch_dot(s, d, ng, n, p->dscratch, sd + 2));
+        LAUNCH_OK(launch_dot(s, m, ng, n, p->dscratch, sd + 3));
+        HIP_OK(hipMemcpyAsync(h, sd, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        double dBd = h[0], dBm = h[1], s0, s1;
+        for (int f = 0; f < F; ++f) {
+            double dWd, dWm;
+            mm_block_of_d(c[f][0], c[f][1], c[f][2], beta, &dWd, &dWm);
+            dBd += hp.reg[f] * dWd;
+            dBm += hp.reg[f] * dWm;
+        }
+        if (!(dBd > 0.0))
+            return F ? fail("3MG (%s): non-positive curvature d.Bd = %g at iteration %d", hp.what, dBd, it)
+                     : fail("3MG: non-positive curvature d.Qd = %g at iteration %d", dBd, it);
+        mm_step2(dBd, dBm, mBm, h[2], h[3], &s0, &s1);
+        const bool fresh = refresh_due(refresh, it);
+        {
+            Prof pr(p, "mmmg_update");
+            LAUNCH_OK(launch_mmmg_update(s, p->cg_x, r, d, m, qm, qd, n, s0, s1, fresh ? 0 : 1));
+        }
+        if (fresh) {
+            if (normal_prior(p, p->cg_x, qd, mu, hp.quad_reg)) return 1;
+            LAUNCH_OK(launch_residual(s, r, p->cg_b, qd, n));
+        }
+        *nit = it + 1;
+    }
+    if (prior_values)
+        for (int f = 0; f < F; ++f) prior_values[f] = prior[f];
+    return mmmg_finish(p, x);
+}
+
+// no Huber family (surfh_mmmg): -g is the carried residual, in place
+int quad_grad(surfh_plan *p, const HuberPrior &, const float *, const float *src, float *, double *sums) {
+    LAUNCH_OK(launch_dot(p->stream, src, src, p->isize, p->dscratch, sums));
+    return 0;
+}
+int quad_curv(surfh_plan *, const HuberPrior &, const float *, const float *, const float *, double *) { return 0; }
+// the maps' prior: one family (rows and columns under one weight and one threshold)
+int maps_grad(surfh_plan *p, const HuberPrior &h, const float *x, const float *src, float *out, double *sums) {
+    Prof pr(p, "huber_grad");
+    LAUNCH_OK(launch_huber_grad(p->stream, x, src, out, p->T, p->Na, p->Nb, -(float)h.reg[0], h.delta[0], h.kind[0], p->dscratch, sums));
+    return 0;
+}
+int maps_curv(surfh_plan *p, const HuberPrior &h, const float *x, const float *p0, const float *p1, double *sums) {
+    Prof pr(p, "huber_curv");
+    LAUNCH_OK(launch_huber_curv(p->stream, x, p0, p1, p->T, p->Na, p->Nb, h.delta[0], h.kind[0], p->dscratch, sums));
+    return 0;
+}
+// the cube's prior: the in-plane family and the wavelength family
+int vox_grad(surfh_plan *p, const HuberPrior &h, const float *x, const float *src, float *out, double *sums) {
+    Prof pr(p, "huber_vox_grad");
+    LAUNCH_OK(launch_huber_vox_grad(p->stream, x, src, out, p->Lc, p->Na, p->Nb, -(float)h.reg[0], h.delta[0], -(float)h.reg[1],
+                                    h.delta[1], h.kind[0], h.kind[1], p->dscratch, sums));
+    return 0;
+}
+int vox_curv(surfh_plan *p, const HuberPrior &h, const float *x, const float *p0, const float *p1, double *sums) {
+    Prof pr(p, "huber_vox_curv");
+    LAUNCH_OK(launch_huber_vox_curv(p->stream, x, p0, p1, p->Lc, p->Na, p->Nb, h.delta[0], h.delta[1], h.kind[0], h.kind[1], p->dscratch,
+                                    sums));
+    return 0;
+}
+}  // namespace
+
+int surfh_mmmg_huber(surfh_plan *p, const float *y, double mu, double mu_reg, double delta, const float *x0, int32_t max_iter,
+                     double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit, double *prior_value,
+                     surfh_cg_callback callback, void *user) {
+    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (p->T <= 0) return fail("surfh_mmmg_huber needs templates (the priors act on abundance maps)");
+    if (huber_args(mu_reg, delta)) return 1;
+    const HuberPrior hp = {1, {mu_reg, 0.0}, "Huber", maps_grad, maps_curv, {(float)delta, 0.f}, {p->pot[0], 0}};
+    return mmmg_huber_loop(p, hp, y, mu, x0, max_iter, tol, refresh, x, grad_norm, nit, prior_value, callback, user);
+}
+
+int surfh_mmmg(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
+               int32_t refresh, float *x, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
+    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (p->T <= 0) return fail("surfh_mmmg needs templates (the priors act on abundance maps)");
+    const HuberPrior hp = {0, {0.0, 0.0}, nullptr, quad_grad, quad_curv, {0.f, 0.f}, {0, 0}, mu_reg};
+    return mmmg_huber_loop(p, hp, y, mu, x0, max_iter, tol, refresh, x, grad_norm, nit, nullptr, callback, user);
+}
+
+// ---- the same solver on the cube itself (the reference's vox_reconstruction, surfh/ToolsDir/algorithms.py:27-71): no templates,
+// Huber priors on the row, column and wavelength differences, the two spatial families under (spat_reg, spat_delta), the spectral
+// one under (spec_reg, spec_delta).  The majorant gains the block spec_reg Dl^T diag(w(Dl x)) Dl; everything else is the loop above.
+int surfh_huber_vox_prior_dev(surfh_plan *p, const float *x_dev, float *g_dev, double spat_reg, double spat_delta, double spec_reg,
+                              double spec_delta, double *values) {
+    if (!p || !x_dev || !g_dev) return fail("null argument");
+    if (p->T > 0) return fail("the voxel-wise prior is defined on the cube (needs a plan without templates)");
+    if (huber_args(spat_reg, spat_delta) || huber_args(spec_reg, spec_delta)) return 1;
+    double h[3];
+    const auto pass = [&] {
+        return launch_huber_vox_grad(p->stream, x_dev, g_dev, g_dev, p->Lc, p->Na, p->Nb, (float)spat_reg, (float)spat_delta,
+                                     (float)spec_reg, (float)spec_delta, p->pot[0], p->pot[1], p->dscratch, p->dscal);
+    };
+    if (diag_pass(p, "huber_vox_grad", pass, p->dscal, h, 3)) return 1;
+    if (values) {
+        values[0] = h[1];
+        values[1] = h[2];
+    }
+    return 0;
+}
+int surfh_huber_vox_curv_dev(surfh_plan *p, const float *x_dev, const float *p0_dev, const float *p1_dev, double spat_delta,
+                             double spec_delta, double *sums) {
+    if (!p || !x_dev || !p0_dev || !p1_dev || !sums) return fail("null argument");
+    if (p->T > 0) return fail("the voxel-wise prior is defined on the cube (needs a plan without templates)");
+    if (huber_args(0.0, spat_delta) || huber_args(0.0, spec_delta)) return 1;
+    const auto pass = [&] {
+        return launch_huber_vox_curv(p->stream, x_dev, p0_dev, p1_dev, p->Lc, p->Na, p->Nb, (float)spat_delta, (float)spec_delta,
+                                     p->pot[0], p->pot[1], p->dscratch, p->dscal);
+    };
+    return diag_pass(p, "huber_vox_curv", pass, p->dscal, sums, 6);
+}
+
+int surfh_mmmg_huber_vox(surfh_plan *p, const float *y, double mu, double spat_reg, double spat_delta, double spec_reg,
+                         double spec_delta, const float *x0, int32_t max_iter, double tol, int32_t refresh, float *x,
+                         double *grad_norm, int32_t *nit, double *prior_values, surfh_cg_callback callback, void *user) {
+    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (p->T > 0) return fail("surfh_mmmg_huber_vox reconstructs the cube: it needs a plan without templates (n_templates = 0)");
+    if (huber_args(spat_reg, spat_delta) || huber_args(spec_reg, spec_delta)) return 1;
+    const HuberPrior hp = {2, {spat_reg, spec_reg}, "Huber, voxel-wise", vox_grad, vox_curv, {(float)spat_delta, (float)spec_delta},
+                           {p->pot[0], p->pot[1]}};
+    return mmmg_huber_loop(p, hp, y, mu, x0, max_iter, tol, refresh, x, grad_norm, nit, prior_values, callback, user);
+}
+
+// ---- 3MG with a robust (Huber) data term (qmm.Objective(forward, adjoint, Huber(delta_d), data=y)):
+//   J(x) = mu sum_i phi_dd(t_i) + priors(x),   t_i = sqrt(w_i) (y_i - (A x)_i),   w the plan's data weights (1 without)
+// The half-quadratic majorant's data block is mu A^T diag(w omega(t)) A with omega recomputed from the residual at every iterate
+// (IRLS), so neither the carried Q_D m nor the fused normal operator of mmmg_huber_loop applies: the loop keeps u = A x and
+// a_m = A m as detector vectors beside the maps and applies one forward and one adjoint per iteration, through y.  Per iteration:
+// robust_data (v = sqrt(w) phi'(t), sum phi, count beyond) -> adjoint (the data part of -g) -> the prior's grad pass (-g, |g|^2,
+// prior values) -> forward (a_g = A (-g)) -> robust_curv (the data block of (a_g, a_m)) -> the prior's curv pass -> one read-back.
+// The host forms, in float64, the blocks of B = mu A^T diag(w omega) A + sum_f reg_f D_f^T diag(w_f) D_f on (-g, m), beta that
+// makes d = -g + beta m B-orthogonal to m, the block of (d, m) by linearity, and the step (mm_step2); the move s0 d + s1 m = s0 (-g) + (s0 beta + s1) m is then one pass over the maps and one over the detector
+// vectors.  u is recomputed from x every `refresh` iterations.  One host synchronisation per iteration.
+namespace {
+int robust_args(double data_delta) {
+    if (std::isnan(data_delta)) return fail("robust data term: data_delta must not be NaN");
+    if (!(data_delta >= (double)FLT_MIN))
+        return fail("robust data term: data_delta must be at least %g (fp32 kernels; got %g)", (double)FLT_MIN, data_delta);
+    return 0;
+}
+float robust_delta_f32(double data_delta) { return data_delta > (double)FLT_MAX ? INFINITY : (float)data_delta; }
+
+// values receives sum phi(t), the number of |t| > data_delta, then the nfam prior values (may be NULL); omega_out [osize] (may be NULL)
+int mmmg_robust_loop(surfh_plan *p, const HuberPrior &hp, const float *y, double mu, double data_delta, const float *x0,
+                     int32_t max_iter, double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit, double *values,
+                     float *omega_out, surfh_cg_callback callback, void *user) {
+    std::vector<float> hx;
+    HIP_OK(hipSetDevice(p->dev));
+    if (p->ch.empty() || p->osize <= 0) return fail("3MG (%s, robust data term) needs a plan with detector channels", hp.what);
+    for (float **v : {&p->rb_y, &p->rb_u, &p->rb_ag, &p->rb_am})
+        if (!*v && dev_alloc(v, (size_t)p->osize)) return 1;
+    if (mmmg_begin(p, true, y, p->rb_y, x0, p->rb_am)) return 1;
+    hipStream_t s = p->stream;
+    const long n = p->isize, no = p->osize;
+    const int F = hp.nfam;
+    const float dd = robust_delta_f32(data_delta);
+    const int dk = p->pot[2];                              // the potential of the data term
+    float *r = p->cg_r, *m = p->cg_d, *ng = p->cg_hg, *v = p->cg_y, *yd = p->rb_y, *u = p->rb_u, *ag = p->rb_ag, *am = p->rb_am;
+    const float *w = p->dw;
+    // device scalars: [0, 1] robust_data, [2 .. 2+F] the prior's grad pass, [3+F .. 5+F] robust_curv, [6+F .. 5+4F] the prior's
+    // curv pass, [6+4F] m.(-g)
+    double *sc = p->dscal;
+    const int G = 2, CD = 3 + F, CP = 6 + F, MG = 6 + 4 * F;
+    if (forward_dev(p, p->cg_x, u)) return 1;
+    double h[16], val[4] = {0.0, 0.0, 0.0, 0.0};
+    *nit = 0;
+    for (int it = 0;; ++it) {
+        const bool last = it >= max_iter;                  // only |g| and the values are wanted: no majorant
+        {
+            Prof pr(p, "robust_data");
+            LAUNCH_OK(launch_robust_data(s, yd, u, w, v, nullptr, no, dd, dk, p->dscratch, sc + 0));
+        }
+        if (adjoint_dev(p, v, r, false)) return 1;
+        if (mu != 1.0) LAUNCH_OK(launch_scale(s, r, n, (float)mu));
+        if (hp.grad(p, hp, p->cg_x, r, ng, sc + G)) return 1;
+        if (!last) {
+            if (forward_dev(p, ng, ag)) return 1;
+            {
+                Prof pr(p, "robust_curv");
+                LAUNCH_OK(launch_robust_curv(s, yd, u, w, ag, am, no, dd, dk, p->dscratch, sc + CD));
+            }
+            if (hp.curv(p, hp, p->cg_x, ng, m, sc + CP)) return 1;
+            LAUNCH_OK(launch_dot(s, m, ng, n, p->dscratch, sc + MG));
+        }
+        HIP_OK(hipMemcpyAsync(h, sc, (last ? 3 + F : 7 + 4 * F) * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        grad_norm[it] = std::sqrt(h[G]);
+        val[0] = h[0];
+        val[1] = h[1];
+        for (int f = 0; f < F; ++f) val[2 + f] = h[G + 1 + f];
+        if (const int rc = mmmg_check(p, callback, user, it, max_iter, grad_norm, grad_norm[it], (double)n, tol, hx)) {
+            if (rc == CB_STOP) break;
+            return 1;
+        }
+        // the block of (-g, m) under B: the data family in detector space, the prior families on the maps
+        double gBg = mu * h[CD], gBm = mu * h[CD + 1], mBm = mu * h[CD + 2];
+        for (int f = 0; f < F; ++f) {
+            gBg += hp.reg[f] * h[CP + 3 * f];
+            gBm += hp.reg[f] * h[CP + 3 * f + 1];
+            mBm += hp.reg[f] * h[CP + 3 * f + 2];
+        }
+        const double beta = mBm > 0.0 ? -gBm / mBm : 0.0;
+        double dBd, dBm, s0, s1;
+        mm_block_of_d(gBg, gBm, mBm, beta, &dBd, &dBm);
+        const double mg = h[MG], dg = h[G] + beta * mg;
+        if (!(dBd > 0.0)) return fail("3MG (%s, robust data term): non-positive curvature d.Bd = %g at iteration %d", hp.what, dBd, it);
+        mm_step2(dBd, dBm, mBm, dg, mg, &s0, &s1);
+        {
+            Prof pr(p, "robust_move");
+            LAUNCH_OK(launch_robust_move(s, p->cg_x, ng, m, n, s0, s0 * beta + s1));
+            LAUNCH_OK(launch_robust_move(s, u, ag, am, no, s0, s0 * beta + s1));
+        }
+        if (refresh_due(refresh, it) && forward_dev(p, p->cg_x, u)) return 1;
+        *nit = it + 1;
+    }
+    if (values)
+        for (int k = 0; k < 2 + F; ++k) values[k] = val[k];
+    if (omega_out) {                                       // omega at the returned iterate (u = A x of it)
+        LAUNCH_OK(launch_robust_data(s, yd, u, w, v, ag, no, dd, dk, p->dscratch, sc + 0));
+        HIP_OK(hipMemcpyAsync(omega_out, ag, no * sizeof(float), hipMemcpyDeviceToHost, s));
+    }
+    return mmmg_finish(p, x);
+}
+}  // namespace
+
+int surfh_mmmg_robust(surfh_plan *p, const float *y, double mu, double data_delta, double mu_reg, double delta, const float *x0,
+                      int32_t max_iter, double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit, double *values,
+                      float *omega_out, surfh_cg_callback callback, void *user) {
+    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (p->T <= 0) return fail("surfh_mmmg_robust needs templates (the priors act on abundance maps)");
+    if (robust_args(data_delta) || huber_args(mu_reg, delta)) return 1;
+    const HuberPrior hp = {1, {mu_reg, 0.0}, "Huber", maps_grad, maps_curv, {(float)delta, 0.f}, {p->pot[0], 0}};
+    return mmmg_robust_loop(p, hp, y, mu, data_delta, x0, max_iter, tol, refresh, x, grad_norm, nit, values, omega_out, callback, user);
+}
+
+int surfh_mmmg_robust_vox(surfh_plan *p, const float *y, double mu, double data_delta, double spat_reg, double spat_delta,
+                          double spec_reg, double spec_delta, const float *x0, int32_t max_iter, double tol, int32_t refresh,
+                          float *x, double *grad_norm, int32_t *nit, double *values, float *omega_out, surfh_cg_callback callback,
+                          void *user) {
+    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (p->T > 0) return fail("surfh_mmmg_robust_vox reconstructs the cube: it needs a plan without templates (n_templates = 0)");
+    if (robust_args(data_delta) || huber_args(spat_reg, spat_delta) || huber_args(spec_reg, spec_delta)) return 1;
+    const HuberPrior hp = {2, {spat_reg, spec_reg}, "Huber, voxel-wise", vox_grad, vox_curv, {(float)spat_delta, (float)spec_delta},
+                           {p->pot[0], p->pot[1]}};
+    return mmmg_robust_loop(p, hp, y, mu, data_delta, x0, max_iter, tol, refresh, x, grad_norm, nit, values, omega_out, callback, user);
+}
+
+int surfh_robust_data_dev(surfh_plan *p, const float *y_dev, const float *u_dev, const float *w_dev, int64_t n, double data_delta,
+                          float *v_dev, double *sums_host) {
+    if (!p || !y_dev || !u_dev || !v_dev || !sums_host) return fail("null argument");
+    if (n < 1) return fail("surfh_robust_data_dev: n = %ld", (long)n);
+    if (robust_args(data_delta)) return 1;
+    const auto pass = [&] {
+        return launch_robust_data(p->stream, y_dev, u_dev, w_dev, v_dev, nullptr, n, robust_delta_f32(data_delta), p->pot[2], p->dscratch,
+                                  p->dscal);
+    };
+    return diag_pass(p, "robust_data", pass, p->dscal, sums_host, 2);
+}
+int surfh_robust_curv_dev(surfh_plan *p, const float *y_dev, const float *u_dev, const float *w_dev, const float *p0_dev,
+                          const float *p1_dev, int64_t n, double data_delta, double *sums_host) {
+    if (!p || !y_dev || !u_dev || !p0_dev || !p1_dev || !sums_host) return fail("null argument");
+    if (n < 1) return fail("surfh_robust_curv_dev: n = %ld", (long)n);
+    if (robust_args(data_delta)) return 1;
+    const auto pass = [&] {
+        return launch_robust_curv(p->stream, y_dev, u_dev, w_dev, p0_dev, p1_dev, n, robust_delta_f32(data_delta), p->pot[2], p->dscratch,
+                                  p->dscal);
+    };
+    return diag_pass(p, "robust_curv", pass, p->dscal, sums_host, 3);
+}
+
+// ---- CG on independent planes: the 2-D deconvolution path (criterion_2D.py:60-250 per image, batched over wavelength)
+namespace {
+// one iteration of qmm.lcg on every plane at once, on the plan's cg_d / cg_q / cg_r / cg_b and the iterate x; rr, dq, rrn are
+// [L] device scalars, rr = r.r per plane on entry and on return.  The residual is recomputed from scratch when refresh divides it.
+int cg_planes_iter(surfh_plan *p, float *x, double mu, double mu_reg, int it, int refresh, double *rr, double *dq, double *rrn) {
+    hipStream_t s = p->stream;
+    const int L = p->Lc;
+    const long npix = (long)p->Na * p->Nb;
+    if (normal_prior(p, p->cg_d, p->cg_q, mu, mu_reg)) return 1;
+    LAUNCH_OK(launch_dot_planes(s, p->cg_d, p->cg_q, L, npix, dq));
+    if (refresh > 0 && it % refresh == 0) {
+        LAUNCH_OK(launch_cg_step_planes(s, x, p->cg_r, p->cg_d, p->cg_q, L, npix, rr, dq, rrn, 0));
+        if (normal_prior(p, x, p->cg_q, mu, mu_reg)) return 1;
+        LAUNCH_OK(launch_residual(s, p->cg_r, p->cg_b, p->cg_q, p->isize));
+        LAUNCH_OK(launch_dot_planes(s, p->cg_r, p->cg_r, L, npix, rrn));
+    } else {
+        LAUNCH_OK(launch_cg_step_planes(s, x, p->cg_r, p->cg_d, p->cg_q, L, npix, rr, dq, rrn, 1));
+    }
+    LAUNCH_OK(launch_cg_dir_planes(s, p->cg_d, p->cg_r, L, npix, rrn, rr));      // also rr = rr'
+    return 0;
+}
+}  // namespace
+
+int surfh_cg_planes_cb(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
+                       int32_t refresh, float *x, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
+    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (p->T != 0) return fail("surfh_cg_planes is the solver of the plane-wise (no template) model; use surfh_cg with templates");
+    if (p->ch.empty()) return fail("plan has no channel");
+    HIP_OK(hipSetDevice(p->dev));
+    if (ensure_cg(p)) return 1;
+    hipStream_t s = p->stream;
+    const int L = p->Lc;
+    const long npix = (long)p->Na * p->Nb, n = p->isize;
+    if (!p->pl_sc && dev_alloc(&p->pl_sc, (size_t)3 * L)) return 1;
+    double *rr = p->pl_sc, *dq = p->pl_sc + L, *rrn = p->pl_sc + 2 * L;
+    std::vector<float> hx;             // host copy of the iterate handed to the callback
+    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
+    if (x0)
+        HIP_OK(hipMemcpyAsync(p->cg_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
+    else
+        LAUNCH_OK(launch_fill_zero(s, p->cg_x, n));
+    if (solver_setup(p, p->io_y, p->cg_x, mu, mu_reg)) return 1;
+    HIP_OK(hipMemcpyAsync(p->cg_d, p->cg_r, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    LAUNCH_OK(launch_dot_planes(s, p->cg_r, p->cg_r, L, npix, rr));
+    HIP_OK(hipMemcpyAsync(grad_norm, rr, L * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    *nit = 0;
+    for (int it = 0; it < max_iter; ++it) {
+        if (cg_planes_iter(p, p->cg_x, mu, mu_reg, it, refresh, rr, dq, rrn)) return 1;
+        double *gn = grad_norm + (size_t)(it + 1) * L;
+        HIP_OK(hipMemcpyAsync(gn, rr, L * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        *nit = it + 1;
+        // qmm.lcg's per-iteration callback (criterion_2D.py:163-225): trace so far [it + 2][L], current iterate
+        if (const int rc = callback_iterate(p, callback, user, it + 1, grad_norm, p->cg_x, hx)) {
+            if (rc == CB_STOP) break;
+            return 1;
+        }
+        double worst = 0.0;
+        for (int l = 0; l < L; ++l) worst = std::max(worst, gn[l]);
+        if (std::sqrt(worst) < (double)npix * tol) break;
+    }
+    HIP_OK(hipMemcpyAsync(x, p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return 0;
+}
+
+int surfh_cg_planes(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
+                    int32_t refresh, float *x, double *grad_norm, int32_t *nit) {
+    return surfh_cg_planes_cb(p, y, mu, mu_reg, x0, max_iter, tol, refresh, x, grad_norm, nit, nullptr, nullptr);
+}
+
+// ---- the same loop with the data and the iterate resident on the device and no host synchronisation inside: begin (b = mu A^T y,
+// r = b - Q x, d = r), any number of step calls, r.r per plane on request.  x_dev stays the caller's buffer and holds the iterate.
+namespace {
+struct PnScope {                       // forward_dev / adjoint_dev read and write wavelength-innermost vectors for the duration of a call
+    surfh_plan *p;
+    explicit PnScope(surfh_plan *pl) : p(pl) { p->pn_native = true; }
+    ~PnScope() { p->pn_native = false; }
+};
+// q = mu A^T A v (+ mu_reg prior, fused with the dot product v . q -> dq) on wavelength-innermost vectors
+int pn_normal(surfh_plan *p, const float *v, float *q, double *dq) {
+    PnScope sc(p);
+    // with interleaved spectra and a prior weight the OTF product of the adjoint applies mu and adds the prior (adjoint_tail): the
+    // two halves are called directly so that no scaling pass follows
+    // (plans whose inverse transform forms the OTF product in its loader -- prod_capable -- take mu and the prior on that pass)
+    const bool prod = prod_capable(p) && p->pl_mu != 0.0;
+    const bool fold = prod || (p->ilv && !p->dense_dft && p->pl_mu_reg != 0.0);
+    if (fold) {
+        p->pn_fold_prior = true;
+        const int rc = normal_halves(p, v, q);
+        p->pn_fold_prior = false;
+        if (rc) return 1;
+    } else if (normal_dev(p, v, q, p->pl_mu)) {
+        return 1;
+    }
+    Prof pr(p, "pn_prior_dot");
+    if (fold) LAUNCH_OK(launch_pn_dot(p->stream, v, q, p->Na, p->Nb, p->NAP, p->LP, p->pn_part, dq));
+    else LAUNCH_OK(launch_pn_prior_dot(p->stream, v, q, p->Na, p->Nb, p->NAP, p->LP, (float)p->pl_mu_reg, p->pn_part, dq));
+    return 0;
+}
+bool pn_capable(const surfh_plan *p) {
+    const bool on = env_on("SURFH_PLANES_NATIVE", true);       // 0: vectors in the caller's [Lc][Na][Nb] layout (two transposes per operator application)
+    return on && p->T == 0 && p->segs.size() == 1 && p->segs[0].coff == 0 && p->segs[0].start == 0 && p->Lown == p->Lc && p->prior_kind == 0 &&
+           p->LP % 64 == 0;
+}
+}  // namespace
+
+int surfh_cg_planes_begin_dev(surfh_plan *p, const float *y_dev, double mu, double mu_reg, float *x_dev) {
+    if (!p || !y_dev || !x_dev) return fail("null argument");
+    if (p->T != 0) return fail("surfh_cg_planes is the solver of the plane-wise (no template) model; use surfh_cg with templates");
+    if (p->ch.empty()) return fail("plan has no channel");
+    HIP_OK(hipSetDevice(p->dev));
+    hipStream_t s = p->stream;
+    const int L = p->Lc;
+    p->pn_active = pn_capable(p);
+    if (p->pn_active) {
+        // vectors in the cube's layout: the caller's x is transposed in here and out again at the end of every step call
+        const size_t nc = (size_t)p->NBP * p->NAP * p->LP;
+        for (float *&v : p->pn_v)
+            if (!v) {
+                if (dev_alloc(&v, nc)) return 1;
+                HIP_OK(hipMemsetAsync(v, 0, nc * sizeof(float), s));       // the padding (rows >= Nb, columns >= Na, planes >= Lc) stays zero
+            }
+        if (!p->pn_sc && (dev_alloc(&p->pn_sc, (size_t)3 * p->LP) || dev_alloc(&p->pn_part, pn_part_doubles(p->LP)))) return 1;
+        float *xn = p->pn_v[0], *r = p->pn_v[1], *d = p->pn_v[2], *q = p->pn_v[3], *b = p->pn_v[4];
+        double *rr = p->pn_sc, *dq = p->pn_sc + p->LP;
+        p->pl_x = x_dev; p->pl_mu = mu; p->pl_mu_reg = mu_reg; p->pl_it = 0;
+        LAUNCH_OK(launch_cube_to_lam_inner(s, x_dev, xn, 0, L, p->Na, p->Nb, p->NAP, p->LP));
+        {
+            const float *wy = weighted_data(p, y_dev);
+            PnScope sc(p);
+            if (!wy || adjoint_dev(p, wy, b, false)) return 1;
+        }
+        if (mu != 1.0) LAUNCH_OK(launch_scale(s, b, (long)nc, (float)mu));
+        if (pn_normal(p, xn, q, dq)) return 1;
+        LAUNCH_OK(launch_residual(s, r, b, q, (long)nc));
+        HIP_OK(hipMemcpyAsync(d, r, nc * sizeof(float), hipMemcpyDeviceToDevice, s));
+        LAUNCH_OK(launch_pn_dot(s, r, r, p->Na, p->Nb, p->NAP, p->LP, p->pn_part, rr));
+        return 0;
+    }
+    if (ensure_cg(p)) return 1;
+    if (!p->pl_sc && dev_alloc(&p->pl_sc, (size_t)3 * L)) return 1;
+    p->pl_x = x_dev; p->pl_mu = mu; p->pl_mu_reg = mu_reg; p->pl_it = 0;
+    if (solver_setup(p, y_dev, x_dev, mu, mu_reg)) return 1;
+    HIP_OK(hipMemcpyAsync(p->cg_d, p->cg_r, p->isize * sizeof(float), hipMemcpyDeviceToDevice, s));
+    LAUNCH_OK(launch_dot_planes(s, p->cg_r, p->cg_r, L, (long)p->Na * p->Nb, p->pl_sc));
+    return 0;
+}
+int surfh_cg_planes_step_dev(surfh_plan *p, int32_t iters, int32_t refresh) {
+    if (!p || !p->pl_x || !(p->pn_active ? (void *)p->pn_sc : (void *)p->pl_sc)) return fail("surfh_cg_planes_begin_dev has not been called");
+    HIP_OK(hipSetDevice(p->dev));
+    hipStream_t s = p->stream;
+    const int L = p->Lc;
+    if (p->pn_active) {
+        float *xn = p->pn_v[0], *r = p->pn_v[1], *d = p->pn_v[2], *q = p->pn_v[3], *b = p->pn_v[4];
+        double *rr = p->pn_sc, *dq = p->pn_sc + p->LP, *rrn = p->pn_sc + 2 * p->LP;
+        const long nc = (long)p->NBP * p->NAP * p->LP;
+        for (int i = 0; i < iters; ++i, ++p->pl_it) {
+            if (pn_normal(p, d, q, dq)) return 1;
+            if (refresh > 0 && p->pl_it % refresh == 0) {
+                LAUNCH_OK(launch_pn_step(s, xn, r, d, q, p->Na, p->Nb, p->NAP, p->LP, rr, dq, p->pn_part, rrn, 0));
+                if (pn_normal(p, xn, q, dq)) return 1;
+                LAUNCH_OK(launch_residual(s, r, b, q, nc));
+                LAUNCH_OK(launch_pn_dot(s, r, r, p->Na, p->Nb, p->NAP, p->LP, p->pn_part, rrn));
+            } else {
+                Prof pr(p, "pn_step");
+                LAUNCH_OK(launch_pn_step(s, xn, r, d, q, p->Na, p->Nb, p->NAP, p->LP, rr, dq, p->pn_part, rrn, 1));
+            }
+            {
+                Prof pr(p, "pn_dir");
+                LAUNCH_OK(launch_pn_dir(s, d, r, p->Na, p->Nb, p->NAP, p->LP, rrn, rr));
+            }
+            HIP_OK(hipMemcpyAsync(rr, rrn, (size_t)p->LP * sizeof(double), hipMemcpyDeviceToDevice, s));
+        }
+        LAUNCH_OK(launch_cube_from_lam_inner(s, xn, p->pl_x, 0, L, p->Na, p->Nb, p->NAP, p->LP));      // the caller's iterate
+        return 0;
+    }
+    for (int i = 0; i < iters; ++i, ++p->pl_it)
+        if (cg_planes_iter(p, p->pl_x, p->pl_mu, p->pl_mu_reg, p->pl_it, refresh, p->pl_sc, p->pl_sc + L, p->pl_sc + 2 * L)) return 1;
+    return 0;
+}
+int surfh_cg_planes_rr(surfh_plan *p, double *rr_host) {
+    if (!p || !rr_host || !p->pl_x || !(p->pn_active ? p->pn_sc : p->pl_sc)) return fail("surfh_cg_planes_begin_dev has not been called");
+    HIP_OK(hipSetDevice(p->dev));
+    HIP_OK(hipMemcpyAsync(rr_host, p->pn_active ? p->pn_sc : p->pl_sc, (size_t)p->Lc * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+// ---- 3MG on independent planes: every plane's beta, 2x2 system and step on the device, so the host reads one thing per
+// iteration, the Lc squared gradient norms `sq` that `dir` leaves.  dir() forms d = -g + beta m per plane from the carried
+// residual; the operator (mu A^T A, + op_reg prior) is applied to d for all planes together; step(update_r) solves and moves.
+// The iterate is left in cg_x: the caller ends with mmmg_finish.
+namespace {
+int mmmg_planes_loop(surfh_plan *p, bool want_hg, const float *y, double mu, double op_reg, const float *x0, int32_t max_iter, double tol,
+                     int32_t refresh, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user, const double *sq,
+                     const std::function<int()> &dir, const std::function<int(int)> &step) {
+    std::vector<float> hx;
+    if (mmmg_begin(p, want_hg, y, p->io_y, x0)) return 1;
+    hipStream_t s = p->stream;
+    const int L = p->Lc;
+    const long npix = (long)p->Na * p->Nb;
+    if (solver_setup(p, p->io_y, p->cg_x, mu, op_reg)) return 1;
+    *nit = 0;
+    for (int it = 0;; ++it) {
+        if (dir()) return 1;
+        double *gn = grad_norm + (size_t)it * L;
+        HIP_OK(hipMemcpyAsync(gn, sq, L * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        double worst = 0.0;
+        for (int l = 0; l < L; ++l) {
+            gn[l] = std::sqrt(gn[l]);
+            worst = std::max(worst, gn[l]);
+        }
+        if (const int rc = mmmg_check(p, callback, user, it, max_iter, grad_norm, worst, (double)npix, tol, hx)) {
+            if (rc == CB_STOP) break;
+            return 1;
+        }
+        if (normal_prior(p, p->cg_dd, p->cg_q, mu, op_reg)) return 1;
+        const bool fresh = refresh_due(refresh, it);
+        if (step(fresh ? 0 : 1)) return 1;
+        if (fresh) {
+            if (normal_prior(p, p->cg_x, p->cg_q, mu, op_reg)) return 1;
+            LAUNCH_OK(launch_residual(s, p->cg_r, p->cg_b, p->cg_q, p->isize));
+        }
+        *nit = it + 1;
+    }
+    return 0;
+}
+}  // namespace
+
+// what `method = "qmm"` of the 2-D deconvolution driver runs (scripts/deconvolution_mrs_noRotation.py:199-212 ->
+// criterion_2D.py:190-193 -> qmm.mmmg): the quadratic prior rides in the operator, -g is the carried residual
+int surfh_mmmg_planes_cb(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
+                         int32_t refresh, float *x, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
+    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (p->T != 0) return fail("surfh_mmmg_planes is the solver of the plane-wise (no template) model; use surfh_mmmg with templates");
+    if (p->ch.empty()) return fail("plan has no channel");
+    HIP_OK(hipSetDevice(p->dev));
+    const int L = p->Lc;
+    const long npix = (long)p->Na * p->Nb;
+    if (!p->pl_sc && dev_alloc(&p->pl_sc, (size_t)3 * L)) return 1;
+    double *rr = p->pl_sc, *mqm = p->pl_sc + L;
+    const auto dir = [&] {
+        LAUNCH_OK(launch_mmmg_dir_planes(p->stream, p->cg_dd, p->cg_r, p->cg_d, p->cg_qm, L, npix, rr, mqm));
+        return 0;
+    };
+    const auto step = [&](int update_r) {
+        LAUNCH_OK(launch_mmmg_step_planes(p->stream, p->cg_x, p->cg_r, p->cg_dd, p->cg_d, p->cg_qm, p->cg_q, L, npix, mqm, update_r));
+        return 0;
+    };
+    if (mmmg_planes_loop(p, false, y, mu, mu_reg, x0, max_iter, tol, refresh, grad_norm, nit, callback, user, rr, dir, step)) return 1;
+    return mmmg_finish(p, x);
+}
+
+int surfh_mmmg_planes(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
+                      int32_t refresh, float *x, double *grad_norm, int32_t *nit) {
+    return surfh_mmmg_planes_cb(p, y, mu, mu_reg, x0, max_iter, tol, refresh, x, grad_norm, nit, nullptr, nullptr);
+}
+
+// ---- 3MG with Huber priors on independent planes: the criterion of surfh_mmmg_huber per plane,
+//   J_l(x_l) = mu |y_l - A_l x_l|^2 / 2 + mu_reg sum_k sum phi(D_k x_l),
+// minimised by mmmg_planes_loop: huber_dir_planes gives -g_l, |g_l|^2, the prior value, the prior block of (-g_l, m_l), beta_l
+// and d_l = -g_l + beta_l m_l; the operator is the data part Q_D = mu A^T A alone; huber_step_planes forms the block of
+// (d_l, m_l) by linearity in float64, solves and moves.
+namespace {
+int huber_planes_ready(surfh_plan *p, const char *who) {
+    if (p->T != 0) return fail("%s works on the plane-wise (no template) model; the maps of a template model take surfh_mmmg_huber", who);
+    if (p->ch.empty()) return fail("plan has no channel");
+    HIP_OK(hipSetDevice(p->dev));
+    if (!p->pl_hsc && dev_alloc(&p->pl_hsc, (size_t)HUBER_PLANES_SCALARS * p->Lc)) return 1;
+    return 0;
+}
+}  // namespace
+
+int surfh_huber_planes_prior_dev(surfh_plan *p, const float *x_dev, float *g_dev, double mu_reg, double delta, double *sq_host,
+                                 double *values_host) {
+    if (!p || !x_dev || !g_dev) return fail("null argument");
+    if (huber_args(mu_reg, delta) || huber_planes_ready(p, "surfh_huber_planes_prior_dev")) return 1;
+    const int L = p->Lc;
+    {
+        Prof pr(p, "huber_planes_grad");
+        LAUNCH_OK(launch_huber_planes_grad(p->stream, x_dev, g_dev, g_dev, L, p->Na, p->Nb, (float)mu_reg, (float)delta, p->pot[0], p->pl_hsc));
+    }
+    if (sq_host) HIP_OK(hipMemcpyAsync(sq_host, p->pl_hsc, L * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    if (values_host) HIP_OK(hipMemcpyAsync(values_host, p->pl_hsc + L, L * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int surfh_huber_planes_curv_dev(surfh_plan *p, const float *x_dev, const float *p0_dev, const float *p1_dev, double delta,
+                                double *sums_host) {
+    if (!p || !x_dev || !p0_dev || !p1_dev || !sums_host) return fail("null argument");
+    if (huber_args(0.0, delta) || huber_planes_ready(p, "surfh_huber_planes_curv_dev")) return 1;
+    const int L = p->Lc;
+    const auto pass = [&] { return launch_huber_planes_curv(p->stream, x_dev, p0_dev, p1_dev, L, p->Na, p->Nb, (float)delta, p->pot[0], p->pl_hsc); };
+    return diag_pass(p, "huber_planes_curv", pass, p->pl_hsc + (size_t)(HUBER_PLANES_SCALARS - 3) * L, sums_host, (size_t)3 * L);
+}
+
+int surfh_mmmg_huber_planes(surfh_plan *p, const float *y, double mu, double mu_reg, double delta, const float *x0, int32_t max_iter,
+                            double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit, double *prior_values,
+                            surfh_cg_callback callback, void *user) {
+    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (huber_args(mu_reg, delta) || huber_planes_ready(p, "surfh_mmmg_huber_planes")) return 1;
+    const int L = p->Lc;
+    const long npix = (long)p->Na * p->Nb;
+    double *sc = p->pl_hsc;
+    const auto dir = [&] {
+        Prof pr(p, "huber_dir_planes");
+        LAUNCH_OK(launch_huber_dir_planes(p->stream, p->cg_x, p->cg_r, p->cg_hg, p->cg_d, p->cg_qm, p->cg_dd, L, p->Na, p->Nb, mu_reg,
+                                          (float)delta, p->pot[0], sc));
+        return 0;
+    };
+    const auto step = [&](int update_r) {
+        Prof pr(p, "huber_step_planes");
+        LAUNCH_OK(launch_huber_step_planes(p->stream, p->cg_x, p->cg_r, p->cg_dd, p->cg_d, p->cg_qm, p->cg_q, p->cg_hg, L, npix, mu_reg,
+                                           sc, update_r));
+        return 0;
+    };
+    if (mmmg_planes_loop(p, true, y, mu, 0.0, x0, max_iter, tol, refresh, grad_norm, nit, callback, user, sc, dir, step)) return 1;
+    // the last launch of the dir kernel ran on the returned iterate: its prior values are the result's
+    if (prior_values) HIP_OK(hipMemcpyAsync(prior_values, sc + L, L * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    return mmmg_finish(p, x);
+}
+
+}  // extern "C"

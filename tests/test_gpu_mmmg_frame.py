@@ -1,4 +1,4 @@
-"""The contract of the frame all seven 3MG entry points of the library stand on (plan.hip: mmmg_begin, mmmg_check, mmmg_finish),
+"""The contract of the frame all seven 3MG entry points of the library stand on (plan_solvers.hip: mmmg_begin, mmmg_check, mmmg_finish),
 on the smallest problem the suite has for each: what max_iter = 0 returns, what the callback sees, where a callback's stop and
 the tolerance stop leave the iterate.  What the solvers compute is pinned by their own test files (needs an MI355X).
 
