@@ -370,6 +370,50 @@ int surfh_get_potential(const surfh_plan *plan, int32_t slot);
 int surfh_set_data_weights(surfh_plan *plan, const float *w_host);
 int surfh_set_data_weights_dev(surfh_plan *plan, const float *w_dev);
 int surfh_has_data_weights(const surfh_plan *plan);                                            /* 1 / 0 */
+/* ---- imager data term: a second instrument on the same maps (the reference's instru.MSImager; the slot y_imager / mu_imager /
+ * model_imager its criterion classes reserve, fusion_CT.py:68, :243-261) ----
+ * A multi-filter broadband imager sees the cube the maps span, blurred plane by plane, integrated over wavelength under F
+ * filters, and summed over the decim x decim cube pixels one of its detector pixels spans:
+ *   cube[l] = sum_t tpl[t,l] x[t];   blur[l] = irfft2(rfft2(cube[l]) sotf[l])  (ortho);   z[f] = sum_l filters[f,l] blur[l];
+ *   y_im[f,a,b] = sum_{i,j < decim} z[f, a decim + i, b decim + j],   a < Na / decim, b < Nb / decim
+ * -- whole detector pixels only: no wrap, rows and columns beyond (N / decim) decim are not observed.  filters [F][n_lambda] are
+ * finite and >= 0 (WavelFilter.transmittance(wavelength axis, normalized=True) per row), 1 <= F <= 16, 1 <= decim <= min(Na, Nb).
+ * sotf = NULL: the plan's own OTF, read on the device -- the plan must then own every cube plane (one channel window over the
+ * whole axis, or n_channels = 0: the Model_WCT kind of plan may hold an imager).  Otherwise the imager's own OTF
+ * [n_lambda][Na][Nb/2+1] complex128 (re, im pairs), streamed to the device in chunks of at most 128 planes; any plan with
+ * templates takes it.  Either way the set-up reduces G[f,t,k] = sum_l filters[f,l] tpl[t,l] sotf[l,k] once, in float64, and an
+ * application costs transforms of T + F planes.  surfh_set_imager(NULL desc) detaches: G and the data are freed.
+ * surfh_imager_forward / _adjoint are A_im and its exact transpose, host buffers maps [T][Na][Nb] and y_im [surfh_imager_osize];
+ * the _dev forms take device buffers and are asynchronous on the plan's stream.  surfh_imager_fwadj is A_im^T W_im A_im x.
+ * surfh_set_imager_data(y_im, w_im, mu_imager) adds mu_imager (y_im - A_im x)^T W_im (y_im - A_im x) / 2 to the criterion of
+ * surfh_cg(_cb), surfh_mmmg and surfh_mmmg_huber (every potential) -- the factor convention of their spectrometer term:
+ * the operator of their loops gains mu_imager A_im^T W_im A_im, their right-hand side mu_imager A_im^T W_im y_im.  w_im
+ * [surfh_imager_osize] follows the rules of the data weights (finite, >= 0, weight 0 takes the sample out whatever it holds, NaN
+ * included; NULL: 1); mu_imager is finite and >= 0.  y_im = NULL clears the data.  While a term with mu_imager > 0 is set,
+ * surfh_cg(_cb) runs its map-domain loop (folding G^H W G into surfh_normal_spec_dev is a follow-up: the term is not diagonal there
+ * for decim > 1), and surfh_mmmg_robust(_vox), surfh_mmmg_huber_vox, the plane-wise solvers and surfh_cg_planes_begin_dev fail with
+ * a message naming the imager.  With no imager, no data or mu_imager = 0 no kernel of the term is launched and every result has the
+ * bits it had without.
+ * surfh_forward*, surfh_adjoint*, surfh_fwadj*, surfh_normal_dev and the *_spec_dev calls stay the spectrometer's alone.
+ * Failures (the plan is left as it was, the previous imager and data included): F outside 1..16, decim < 1 or larger than Na or
+ * Nb, a negative or non-finite filter or weight, a plan without templates, sotf = NULL on a plan that does not own every plane.
+ * SURFH_IMAGER_CHUNK (read by surfh_set_imager): planes per chunk of the streamed OTF, a multiple of 32 up to 128 (default 128);
+ * the result has the same bits for every value. */
+typedef struct {
+    int32_t n_filters;
+    const double *filters;         /* [n_filters][n_lambda] */
+    int32_t decim;
+    const double *sotf;            /* NULL: the plan's */
+} surfh_imager_desc;
+int surfh_set_imager(surfh_plan *plan, const surfh_imager_desc *desc);
+int surfh_imager_osize(const surfh_plan *plan);                                                /* F (Na/d) (Nb/d), 0 without */
+int surfh_imager_forward(surfh_plan *plan, const float *maps, float *y_im);
+int surfh_imager_adjoint(surfh_plan *plan, const float *y_im, float *maps);
+int surfh_imager_forward_dev(surfh_plan *plan, const float *maps_dev, float *y_im_dev);
+int surfh_imager_adjoint_dev(surfh_plan *plan, const float *y_im_dev, float *maps_dev);
+int surfh_imager_fwadj(surfh_plan *plan, const float *x, float *out);
+int surfh_set_imager_data(surfh_plan *plan, const float *y_im, const float *w_im, double mu_imager);
+int surfh_has_imager_term(const surfh_plan *plan);                                             /* 1: data with mu_imager > 0 is set */
 int surfh_dot_dev(surfh_plan *plan, const float *a_dev, const float *b_dev, int64_t n, double *out_host);
 /* x += s d ; r -= s q ; returns r.r  (s = rr / d.q computed on device from rr_in)    */
 int surfh_cg_step_dev(surfh_plan *plan, float *x_dev, float *r_dev, const float *d_dev,

@@ -136,11 +136,12 @@ def create_model(sotf, templates, origin_alpha_axis, origin_beta_axis, wavel_axi
 
 
 def result_dir_name(method, n_channels, n_templates, niter, hyper_parameter, scale_data, delta=None, voxel=False, weighted=False,
-                    data_delta=None, potential='huber', data_potential='huber', spec_potential='huber'):
+                    data_delta=None, potential='huber', data_potential='huber', spec_potential='huber', imager=0):
     """main_fusion.py:182; with a Huber threshold `delta` (not in the reference) `_huber_<delta>` is appended, `_vox` for a
     voxel-wise reconstruction, `_wgt` for a run under data weights, and `_rob_<data_delta>` for a robust data term.  Another
     potential than Huber puts its name in Huber's place (`_<kind>_<delta>`, `_rob_<kind>_<data_delta>`; `_spec_<kind>` for the
-    spectral prior of a voxel-wise run); with Huber the names are unchanged."""
+    spectral prior of a voxel-wise run); with Huber the names are unchanged.  `_img_<F>` comes last, for a run with an imager
+    data term of F filters."""
     name = f'{method}_MC_{n_channels}_MO_4_Temp_{n_templates}_nit_{str(niter)}_mu_{str("{:.2e}".format(hyper_parameter))}_SD_{scale_data}'
     if delta is not None:
         name += f'_{potential}_{delta:.2e}'
@@ -152,6 +153,8 @@ def result_dir_name(method, n_channels, n_templates, niter, hyper_parameter, sca
         name += '_wgt'
     if data_delta is not None:
         name += f'_rob_{data_delta:g}' if data_potential == 'huber' else f'_rob_{data_potential}_{data_delta:g}'
+    if imager:
+        name += f'_img_{imager}'
     return name + '/'
 
 
@@ -205,21 +208,24 @@ def voxel_reconstruction(spectro_model, ndata, result_path, spat_reg, spat_th, s
 
 def reconstruction_method(spectro_model, ndata, templates, result_path, hyper_parameter, niter, method, scale_data,
                           checkpoint_every=0, resume=None, delta=None, weights=None, data_delta=None, potential='huber',
-                          data_potential='huber'):
+                          data_potential='huber', imager=None):
     """main_fusion.py:162-206: regularised least squares by CG, then the three result files.  Not in the reference:
     `checkpoint_every` > 0 writes the iterate to checkpoint.npz in the result directory every that many iterations,
     `resume` (such a file) warm-starts from it and runs the iterations that are left; `delta` replaces the quadratic
     priors by Huber potentials of that threshold (3MG only); `weights` `[osize]` weigh the samples of the data term and are
     stored beside the results as weights.npy; `data_delta` makes the data term robust (3MG only) and stores the last iterate's
-    robustness weights as robust_weights.npy; `potential` / `data_potential` name the potential under `delta` / `data_delta`."""
+    robustness weights as robust_weights.npy; `potential` / `data_potential` name the potential under `delta` / `data_delta`;
+    `imager` = (ImagerModel, y_im, mu_imager) adds the imager data term and stores y_im as y_imager.npy."""
     value_init = 0
     path = pathlib.Path(result_path) / result_dir_name(method, len(spectro_model.instrs), templates.shape[0], niter,
                                                        hyper_parameter, scale_data, delta, weighted=weights is not None,
-                                                       data_delta=data_delta, potential=potential, data_potential=data_potential)
+                                                       data_delta=data_delta, potential=potential, data_potential=data_potential,
+                                                       imager=imager[0].oshape[0] if imager else 0)
     path.mkdir(parents=True, exist_ok=True)
+    im_kw = dict(model_imager=imager[0], y_imager=imager[1], mu_imager=imager[2]) if imager else {}
     crit = QuadCriterion_MRS(mu_spectro=1, y_spectro=np.copy(ndata), model_spectro=spectro_model,
                              mu_reg=hyper_parameter, printing=True, gradient="separated", delta=delta, weights=weights,
-                             data_delta=data_delta, potential=potential, data_potential=data_potential)
+                             data_delta=data_delta, potential=potential, data_potential=data_potential, **im_kw)
     if resume:
         from surfh_amd.fusion import load_checkpoint
         x_saved, it_done, _ = load_checkpoint(resume)
@@ -237,6 +243,8 @@ def reconstruction_method(spectro_model, ndata, templates, result_path, hyper_pa
         np.save(path / 'weights.npy', weights)
     if data_delta is not None:
         np.save(path / 'robust_weights.npy', spectro_model.robust_weights)
+    if imager:
+        np.save(path / 'y_imager.npy', imager[1])
     return res, path
 
 
@@ -285,9 +293,29 @@ def synthetic_problem(name, npix):
               help='Potential of the robust data term under --data_delta (needs --method mmmg and --data_delta).')
 @click.option('--spec_potential', default='huber', type=click.Choice(POTENTIALS),
               help='Potential of the spectral prior under --spec_delta (--voxel).')
+@click.option('--imager', 'imager_filters', default=0, type=int,
+              help='Add the data term of a synthetic imager with that many Gaussian filters tiling the wavelength axis (1..16; '
+                   'needs --synthetic). Default: none.')
+@click.option('--mu_imager', default=1., type=float, help='Weight of the imager data term (--imager).')
+@click.option('--imager_decim', default=1, type=int, help='Cube pixels per imager pixel along each axis (--imager).')
 def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, method, verbose, synthetic, device, checkpoint_every=0,
          resume=None, delta=None, voxel=False, spec_reg=1., spec_delta=1., weights_file=None, mask_nan=False, data_delta=None,
-         potential='huber', data_potential='huber', spec_potential='huber'):
+         potential='huber', data_potential='huber', spec_potential='huber', imager_filters=0, mu_imager=1., imager_decim=1):
+    if imager_filters:
+        if not 1 <= imager_filters <= 16:
+            raise click.BadParameter(f'1 to 16 filters, not {imager_filters}', param_hint='--imager')
+        if data_delta is not None:
+            raise click.UsageError('--imager: the robust data term (--data_delta) does not carry the imager data term')
+        if voxel:
+            raise click.UsageError('--imager: the voxel-wise solver (--voxel) does not carry the imager data term')
+        if not synthetic:
+            raise click.UsageError('--imager simulates the imager data: use it with --synthetic')
+        if not (mu_imager >= 0 and np.isfinite(mu_imager)):
+            raise click.BadParameter(f'must be finite and >= 0, not {mu_imager}', param_hint='--mu_imager')
+        if not 1 <= imager_decim <= npix:
+            raise click.BadParameter(f'must be in 1..{npix}, not {imager_decim}', param_hint='--imager_decim')
+    elif mu_imager != 1. or imager_decim != 1:
+        raise click.UsageError('--mu_imager and --imager_decim belong to --imager')
     if (potential != 'huber' or data_potential != 'huber') and method != 'mmmg':
         raise click.UsageError('--potential and --data_potential choose a non-quadratic term; use them with --method mmmg')
     if potential != 'huber' and delta is None and not voxel:
@@ -327,7 +355,15 @@ def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, meth
         model = spectroSigRLSCT(prob['sotf'], templates, prob['alpha_axis'], prob['beta_axis'], prob['wavel'],
                                 prob['ifus'], prob['step_deg'], prob['pointings'], device=device)
         y = model.forward(truth)
-        ndata = y + np.random.default_rng(1).standard_normal(y.shape) * 1e-2 * np.sqrt(np.mean(y ** 2))
+        rng = np.random.default_rng(1)               # the run's noise seed: the spectrometer's draw first, then the imager's
+        ndata = y + rng.standard_normal(y.shape) * 1e-2 * np.sqrt(np.mean(y ** 2))
+        imager = None
+        if imager_filters:
+            from surfh_amd.imager import ImagerModel, synthetic_filters
+            im_model = ImagerModel(model, synthetic_filters(prob['wavel'], imager_filters), decim=imager_decim)
+            model.set_imager(im_model)
+            y_im = im_model.forward(truth)
+            imager = (im_model, y_im + rng.standard_normal(y_im.shape) * 1e-2 * np.sqrt(np.mean(y_im ** 2)), mu_imager)
     else:
         log.info('Load simulation data')
         origin_alpha_axis, origin_beta_axis, wavel_axis, templates, sotf = load_simulation_data(paths, step, step_angle, npix, n_templates,
@@ -360,7 +396,7 @@ def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, meth
         return
     reconstruction_method(model, ndata, templates, paths["result_path"], hyper_parameter, niter, method, scale_data,
                           checkpoint_every=checkpoint_every, resume=resume, delta=delta, weights=weights, data_delta=data_delta,
-                          potential=potential, data_potential=data_potential)
+                          potential=potential, data_potential=data_potential, imager=imager if synthetic else None)
     model.close()
 
 

@@ -44,6 +44,10 @@ class Config(C.Structure):
     ]
 
 
+class ImagerDesc(C.Structure):
+    _fields_ = [("n_filters", C.c_int32), ("filters", c_double_p), ("decim", C.c_int32), ("sotf", c_double_p)]
+
+
 EXPORTS = [
     "surfh_last_error", "surfh_version", "surfh_plan_create", "surfh_plan_destroy", "surfh_isize", "surfh_osize",
     "surfh_stream", "surfh_forward", "surfh_adjoint", "surfh_adjoint_ref", "surfh_fwadj", "surfh_forward_dev",
@@ -51,7 +55,7 @@ EXPORTS = [
     "surfh_wct_fwadj", "surfh_wct_expsol", "surfh_tst_create", "surfh_tst_destroy", "surfh_tst_forward",
     "surfh_tst_adjoint", "surfh_tst_fwadj", "surfh_tst_last_error", "surfh_cg", "surfh_cg_cb", "surfh_mmmg", "surfh_mmmg_huber", "surfh_huber_prior_dev", "surfh_huber_curv_dev", "surfh_mmmg_huber_vox", "surfh_huber_vox_prior_dev", "surfh_huber_vox_curv_dev", "surfh_mmmg_robust", "surfh_mmmg_robust_vox", "surfh_robust_data_dev", "surfh_robust_curv_dev", "surfh_mmmg_huber_planes", "surfh_huber_planes_prior_dev", "surfh_huber_planes_curv_dev", "surfh_cg_planes", "surfh_mmmg_planes", "surfh_cg_planes_cb", "surfh_mmmg_planes_cb", "surfh_cg_planes_begin_dev", "surfh_cg_planes_step_dev", "surfh_cg_planes_rr", "surfh_maps_to_cube", "surfh_cube_to_maps", "surfh_normal_dev",
     "surfh_prior_add_dev", "surfh_spec_supported", "surfh_spec_size", "surfh_to_spec_dev", "surfh_from_spec_dev", "surfh_forward_spec_dev",
-    "surfh_adjoint_spec_dev", "surfh_normal_spec_dev", "surfh_prior_spec_add_dev", "surfh_set_prior", "surfh_set_potential", "surfh_get_potential", "surfh_set_data_weights", "surfh_set_data_weights_dev", "surfh_has_data_weights", "surfh_dot_dev", "surfh_cg_step_dev", "surfh_cg_dir_dev", "surfh_cg_iter_dev", "surfh_residual_dev",
+    "surfh_adjoint_spec_dev", "surfh_normal_spec_dev", "surfh_prior_spec_add_dev", "surfh_set_prior", "surfh_set_potential", "surfh_get_potential", "surfh_set_data_weights", "surfh_set_data_weights_dev", "surfh_has_data_weights", "surfh_set_imager", "surfh_imager_osize", "surfh_imager_forward", "surfh_imager_adjoint", "surfh_imager_forward_dev", "surfh_imager_adjoint_dev", "surfh_imager_fwadj", "surfh_set_imager_data", "surfh_has_imager_term", "surfh_dot_dev", "surfh_cg_step_dev", "surfh_cg_dir_dev", "surfh_cg_iter_dev", "surfh_residual_dev",
     "surfh_cg_begin_dev", "surfh_cg_iter_nosync_dev", "surfh_cg_xupdate_nosync_dev", "surfh_cg_refresh_nosync_dev", "surfh_cg_trace",
     "surfh_profile_enable", "surfh_profile_filter", "surfh_profile_count", "surfh_profile_get", "surfh_profile_reset", "surfh_debug_copy",
     "surfh_debug_dims", "surfh_gemm_selftest", "surfh_gemm_selftest_ksteps", "surfh_klist_classify", "surfh_mm_step2",
@@ -138,6 +142,14 @@ def load():
     L.surfh_set_data_weights.argtypes = [vp, c_float_p]
     L.surfh_set_data_weights_dev.argtypes = [vp, vp]
     L.surfh_has_data_weights.argtypes = [vp]
+    L.surfh_set_imager.argtypes = [vp, C.POINTER(ImagerDesc)]
+    L.surfh_imager_osize.argtypes = [vp]
+    L.surfh_has_imager_term.argtypes = [vp]
+    for n in ("surfh_imager_forward", "surfh_imager_adjoint", "surfh_imager_fwadj"):
+        getattr(L, n).argtypes = [vp, c_float_p, c_float_p]
+    for n in ("surfh_imager_forward_dev", "surfh_imager_adjoint_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp]
+    L.surfh_set_imager_data.argtypes = [vp, c_float_p, c_float_p, C.c_double]
     L.surfh_dot_dev.argtypes = [vp, vp, vp, C.c_int64, c_double_p]
     L.surfh_cg_step_dev.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_double, c_double_p]
     L.surfh_cg_dir_dev.argtypes = [vp, vp, vp, C.c_int64, C.c_double]

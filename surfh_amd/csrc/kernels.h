@@ -220,3 +220,23 @@ int launch_wct_solve(hipStream_t s, const float *hth, const float *reg, const do
 // linear mixing model, plane-major arrays: cube[l][i] = sum_t tpl[t][l] maps[t][i];  maps[t][i] = sum_l tpl[t][l] cube[l][i]
 int launch_lmm_maps2cube(hipStream_t s, const float *maps, const float *tpl, float *cube, int T, int L, long npix);
 int launch_lmm_cube2maps(hipStream_t s, const float *cube, const float *tpl, float *maps, int T, int L, long npix);
+// ---- Imager data term (imager.hip; include/surfh_amd.h: surfh_set_imager) ---------------------------------------------------------
+// G[f][t][2][PL] = sum_l wf[f,l] tpl[t,l] sotf[l,k], accumulated in float64 into acc (same layout; read and written back, cleared
+// by the caller before the first launch) over the L planes handed in -- L a multiple of 64, tpl [T][ldt] and wf [F][ldw] zero
+// beyond the last plane; sotf: re at sotf[k sk + l sl], im at + im_off.  The sum has one order however the planes are split
+// over launches, provided every launch but the last takes a multiple of 32 planes.  g_store: the fp32 copy the mixes read.
+int launch_imager_build_g(hipStream_t s, const float *sotf, long sk, long sl, long im_off, const float *tpl, long ldt, const double *wf,
+                          long ldw, int L, double *acc, int F, int T, int Na, int nkb, long KBP, long PL);
+int launch_imager_g_store(hipStream_t s, const double *acc, float *g, long n);
+// src [n][Na][nkb] complex fp32 -> dst [2][KAP][KBP][CH] (wavelength innermost, dst cleared by the caller)
+int launch_imager_otf_chunk(hipStream_t s, const float *src, float *dst, int n, int CH, int Na, int nkb, long KBP, long PL);
+// zhat[f][k] = sum_t G[f,t,k] xhat[t][k];  ghat[t][k] (+)= scale sum_f conj(G[f,t,k]) yhat[f][k]   (half spectra [B][2][PL])
+int launch_imager_mix_fwd(hipStream_t s, const float *g, const float *xhat, float *zhat, int F, int T, long PL);
+int launch_imager_mix_adj(hipStream_t s, const float *g, const float *yhat, float *ghat, int F, int T, long PL, float scale, int accumulate);
+// padded images z [F][NAP][NBP] (plane pitch PLc) <-> detector y [F][Na / d][Nb / d]: d x d sums, their transpose, and both around
+// the weights w (null: 1; w <= 0 takes the sample out) in place
+int launch_imager_sample(hipStream_t s, const float *z, float *y, int F, int d, int Na, int Nb, long NBP, long PLc);
+int launch_imager_spread(hipStream_t s, const float *y, float *z, int F, int d, int Na, int Nb, long NBP, long PLc);
+int launch_imager_window(hipStream_t s, float *z, const float *w, int F, int d, int Na, int Nb, long NBP, long PLc);
+// out [T][Na][Nb] (+)= pad [T][NAP][NBP]
+int launch_imager_unpad(hipStream_t s, const float *pad, float *out, int T, int Na, int Nb, long NBP, long PLc, int accumulate);

@@ -637,6 +637,7 @@ int surfh_plan_destroy(surfh_plan *p) {
     for (float *v : p->pn_v) hipFree(v);
     hipFree(p->dw);
     hipFree(p->dwy);
+    for (float *v : {p->im_g, p->im_xpad, p->im_xhat, p->im_zpad, p->im_zhat, p->im_io, p->im_y, p->im_w, p->im_wy}) hipFree(v);
     hipFree(p->pn_sc);
     hipFree(p->pn_part);
     for (auto &c : p->ch) {
@@ -799,6 +800,7 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
             for (int l = 0; l < p->Lown; ++l)
                 if (p->planes[l] >= 0) t[(size_t)k * LP + l] = (float)cfg->templates[(size_t)k * p->Lc + p->planes[l]];
         if (dev_upload(&p->tpl, t)) return bail(1);
+        p->tpl_host.assign(cfg->templates, cfg->templates + (size_t)p->T * p->Lc);
     }
     {
         std::vector<float> Fi, Gi, Gf, Ff, GiT, GfT;
@@ -896,6 +898,7 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
     hipMemset(p->mhat, 0, nmhat * sizeof(float));
     hipMemset(p->maps_pad, 0, nmaps * sizeof(float));
     hipMemset(p->ycol_maps, 0, nycm * sizeof(float));
+    p->ycm_planes = std::max(p->T, 1);
     // ---- channels -------------------------------------------------------------------------
     p->a_lo = p->b_lo = 1 << 30; p->a_hi = p->b_hi = 0;      // alpha / beta range of the pixels the channels' tables touch (build_channel)
     p->ch.resize(cfg->n_channels);

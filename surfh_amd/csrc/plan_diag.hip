@@ -52,6 +52,8 @@ static int resolve(surfh_plan *p, const char *which, const float **ptr, int64_t 
         else { dims[0] = 2; dims[1] = p->KAP; dims[2] = p->KBP; dims[3] = p->LP; }
     } else if (w == "mhat" && p->T > 0) {
         *ptr = p->mhat; dims[0] = p->T; dims[1] = 2; dims[2] = p->KAP; dims[3] = p->KBP;
+    } else if (w == "imager_g" && p->im_g) {        // [(f,t)][2][k_alpha][k_beta]
+        *ptr = p->im_g; dims[0] = (int64_t)p->im_F * p->T; dims[1] = 2; dims[2] = p->KAP; dims[3] = p->KBP;
     } else if (w.rfind("xs:", 0) == 0 || w.rfind("xsinfo:", 0) == 0) {
         const bool info = w[2] == 'i';
         const int c = atoi(w.c_str() + (info ? 7 : 3));

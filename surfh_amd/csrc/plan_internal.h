@@ -215,6 +215,15 @@ struct surfh_plan {
     // data weights (surfh_set_data_weights): w [osize] in the layout of y, and room for W y, the data of the solvers' right-hand side;
     // both null = every sample counts 1
     float *dw = nullptr, *dwy = nullptr;
+    // imager data term (surfh_set_imager, surfh_set_imager_data): G [F][T][2][KAP][KBP] and the work buffers of an application --
+    // padded maps / images and their half spectra -- then the data y_im, w_im (null: 1) and W y_im [im_osize]; im_g null = no imager
+    int im_F = 0, im_d = 0;
+    long im_osize = 0;
+    float *im_g = nullptr, *im_xpad = nullptr, *im_xhat = nullptr, *im_zpad = nullptr, *im_zhat = nullptr, *im_io = nullptr;
+    float *im_y = nullptr, *im_w = nullptr, *im_wy = nullptr;
+    double im_mu = 0.0;
+    int ycm_planes = 0;                            // planes ycol_maps holds (max(T, 1); max(T, F) once an imager has been attached)
+    std::vector<double> tpl_host;                  // the templates [T][Lc] as given (the imager's streamed set-up reads them)
     // CG
     float *cg_x = nullptr, *cg_r = nullptr, *cg_d = nullptr, *cg_q = nullptr, *cg_b = nullptr, *cg_y = nullptr, *cg_qm = nullptr, *cg_dd = nullptr;
     float *cg_hg = nullptr;                        // surfh_mmmg_huber(_vox): -gradient of the non-quadratic criterion
@@ -299,5 +308,8 @@ int normal_halves(surfh_plan *p, const float *v, float *q);
 const float *weighted_data(surfh_plan *p, const float *y);
 int normal_dev(surfh_plan *p, const float *d, float *q, double mu);
 int ensure_cg(surfh_plan *p);
+inline bool imager_active(const surfh_plan *p) { return p->im_g && p->im_y && p->im_mu > 0.0; }
+int imager_normal_add(surfh_plan *p, const float *v, float *q);      // q += mu_imager A_im^T W_im A_im v
+int imager_rhs_add(surfh_plan *p, float *b);                         // b += mu_imager A_im^T W_im y_im
 
 }  // namespace surfh_impl

@@ -947,3 +947,244 @@ int surfh_cube_to_maps(surfh_plan *p, const double *templates, int32_t T, int32_
 }
 
 }  // extern "C"
+
+// ---- imager data term (include/surfh_amd.h: surfh_set_imager; kernels: imager.hip) ---------------------------------------------
+// A_im = sample . irfft2 . G . rfft2 on T maps -> F images, its transpose the same chain backwards with conj(G); the transforms
+// are the plane transforms of the maps (rfft2_planes / irfft2_planes) on the imager's own padded buffers, so an application
+// leaves every buffer of the spectrometer's operator alone except their temporary ycol_maps.
+namespace surfh_impl {
+namespace {
+int imager_to_spectra(surfh_plan *p, const float *x) {            // x [T][Na][Nb] -> im_xhat
+    {
+        Prof pr(p, "imager_pad");
+        LAUNCH_OK(launch_pad_planes(p->stream, x, p->im_xpad, p->T, p->Na, p->Nb, p->NAP, p->NBP));
+    }
+    return rfft2_planes(p, p->im_xpad, p->im_xhat, p->T);
+}
+int imager_to_images(surfh_plan *p) {                             // im_xhat -> im_zpad (full resolution, before the detector)
+    {
+        Prof pr(p, "imager_mix_fwd");
+        LAUNCH_OK(launch_imager_mix_fwd(p->stream, p->im_g, p->im_xhat, p->im_zhat, p->im_F, p->T, p->PL));
+    }
+    return irfft2_planes(p, p->im_zhat, p->im_zpad, p->im_F);
+}
+int imager_from_images(surfh_plan *p, float *out, float scale, bool accumulate) {      // out (+)= scale * (maps of im_zpad)
+    if (rfft2_planes(p, p->im_zpad, p->im_zhat, p->im_F)) return 1;
+    {
+        Prof pr(p, "imager_mix_adj");
+        LAUNCH_OK(launch_imager_mix_adj(p->stream, p->im_g, p->im_zhat, p->im_xhat, p->im_F, p->T, p->PL, scale, 0));
+    }
+    if (irfft2_planes(p, p->im_xhat, p->im_xpad, p->T)) return 1;
+    Prof pr(p, "imager_unpad");
+    LAUNCH_OK(launch_imager_unpad(p->stream, p->im_xpad, out, p->T, p->Na, p->Nb, p->NBP, p->PLc, accumulate ? 1 : 0));
+    return 0;
+}
+int imager_forward_dev(surfh_plan *p, const float *x, float *y) {
+    if (imager_to_spectra(p, x) || imager_to_images(p)) return 1;
+    Prof pr(p, "imager_sample");
+    LAUNCH_OK(launch_imager_sample(p->stream, p->im_zpad, y, p->im_F, p->im_d, p->Na, p->Nb, p->NBP, p->PLc));
+    return 0;
+}
+int imager_adjoint_dev(surfh_plan *p, const float *y, float *x, float scale, bool accumulate) {
+    {
+        Prof pr(p, "imager_spread");
+        LAUNCH_OK(launch_imager_spread(p->stream, y, p->im_zpad, p->im_F, p->im_d, p->Na, p->Nb, p->NBP, p->PLc));
+    }
+    return imager_from_images(p, x, scale, accumulate);
+}
+// q (+)= scale A_im^T diag(w) A_im v
+int imager_normal_dev(surfh_plan *p, const float *v, float *q, const float *w, float scale, bool accumulate) {
+    if (imager_to_spectra(p, v) || imager_to_images(p)) return 1;
+    {
+        Prof pr(p, "imager_window");
+        LAUNCH_OK(launch_imager_window(p->stream, p->im_zpad, w, p->im_F, p->im_d, p->Na, p->Nb, p->NBP, p->PLc));
+    }
+    return imager_from_images(p, q, scale, accumulate);
+}
+void imager_free(std::initializer_list<void *> l) {
+    for (void *v : l) hipFree(v);
+}
+}  // namespace
+
+int imager_normal_add(surfh_plan *p, const float *v, float *q) { return imager_normal_dev(p, v, q, p->im_w, (float)p->im_mu, true); }
+int imager_rhs_add(surfh_plan *p, float *b) {
+    const float *y = p->im_y;
+    if (p->im_w) {          // W y by a select: a masked NaN stays out
+        Prof pr(p, "imager_weight_select");
+        LAUNCH_OK(launch_weight_select(p->stream, p->im_y, p->im_w, p->im_wy, p->im_osize));
+        y = p->im_wy;
+    }
+    return imager_adjoint_dev(p, y, b, (float)p->im_mu, true);
+}
+}  // namespace surfh_impl
+
+extern "C" {
+
+int surfh_set_imager(surfh_plan *p, const surfh_imager_desc *desc) {
+    if (!p) return fail("null plan");
+    HIP_OK(hipSetDevice(p->dev));
+    hipStream_t s = p->stream;
+    if (!desc) {
+        HIP_OK(hipStreamSynchronize(s));
+        imager_free({p->im_g, p->im_xpad, p->im_xhat, p->im_zpad, p->im_zhat, p->im_io, p->im_y, p->im_w, p->im_wy});
+        p->im_g = p->im_xpad = p->im_xhat = p->im_zpad = p->im_zhat = p->im_io = p->im_y = p->im_w = p->im_wy = nullptr;
+        p->im_F = p->im_d = 0; p->im_osize = 0; p->im_mu = 0.0;
+        return 0;
+    }
+    const int F = desc->n_filters, d = desc->decim, T = p->T, Lc = p->Lc, nkb = p->Nb / 2 + 1;
+    if (T < 1) return fail("imager: the plan has no templates (the imager observes the cube the maps span)");
+    if (T > SURFH_MAX_TEMPLATES) return fail("imager: at most %d templates (the plan has %d)", SURFH_MAX_TEMPLATES, T);
+    if (F < 1 || F > 16) return fail("imager: n_filters = %d is outside 1..16", F);
+    if (d < 1 || d > p->Na || d > p->Nb) return fail("imager: decim = %d is outside 1..min(n_alpha, n_beta) = %d", d, std::min(p->Na, p->Nb));
+    if (!desc->filters) return fail("imager: null filters");
+    for (long i = 0; i < (long)F * Lc; ++i)
+        if (!(desc->filters[i] >= 0.0 && desc->filters[i] <= DBL_MAX))
+            return fail("imager: filter %ld has %g at plane %ld: transmittances are finite and >= 0", i / Lc, desc->filters[i], i % Lc);
+    const bool owns_all = p->segs.size() == 1 && p->segs[0].start == 0 && p->segs[0].len == Lc;
+    if (!desc->sotf && !owns_all)
+        return fail("imager: the plan does not own every cube plane (its channels' windows cover %d of %d): its own OTF cannot serve the "
+                    "imager, hand the imager's OTF in", p->Lown, Lc);
+    int chunk = 128;
+    if (const char *e = getenv("SURFH_IMAGER_CHUNK")) {
+        chunk = atoi(e);
+        if (chunk < 32 || chunk > 128 || chunk % 32) return fail("imager: SURFH_IMAGER_CHUNK = %s is not a multiple of 32 in 32..128", e);
+    }
+    const size_t ng = (size_t)F * T * 2 * p->PL, osz = (size_t)F * (p->Na / d) * (p->Nb / d);
+    float *g = nullptr, *xpad = nullptr, *xhat = nullptr, *zpad = nullptr, *zhat = nullptr, *io = nullptr, *ycm = nullptr;
+    float *otf_in = nullptr, *otf_pl = nullptr, *tplc = nullptr;
+    double *acc = nullptr, *wf = nullptr;
+    auto done = [&](int rc) {
+        imager_free({g, xpad, xhat, zpad, zhat, io, ycm, otf_in, otf_pl, tplc, acc, wf});
+        return rc;
+    };
+    const size_t nycm = (size_t)F * 2 * p->NAP * p->KBP;
+    if (dev_alloc(&g, ng) || dev_alloc(&acc, ng) || dev_alloc(&xpad, (size_t)T * p->PLc) || dev_alloc(&xhat, (size_t)T * 2 * p->PL) ||
+        dev_alloc(&zpad, (size_t)F * p->PLc) || dev_alloc(&zhat, (size_t)F * 2 * p->PL) || dev_alloc(&io, osz) ||
+        (F > p->ycm_planes && dev_alloc(&ycm, nycm)))
+        return done(1);
+    if (hipMemsetAsync(acc, 0, ng * sizeof(double), s) != hipSuccess || hipMemsetAsync(xpad, 0, (size_t)T * p->PLc * sizeof(float), s) != hipSuccess ||
+        hipMemsetAsync(zpad, 0, (size_t)F * p->PLc * sizeof(float), s) != hipSuccess ||
+        (ycm && hipMemsetAsync(ycm, 0, nycm * sizeof(float), s) != hipSuccess))
+        return done(fail("memset failed"));
+    if (!desc->sotf) {       // the plan's device OTF and templates: compact plane index = cube plane
+        const long LP = p->LP;
+        std::vector<double> h((size_t)F * LP, 0.0);
+        for (int f = 0; f < F; ++f) std::copy(desc->filters + (size_t)f * Lc, desc->filters + (size_t)(f + 1) * Lc, h.begin() + (size_t)f * LP);
+        if (dev_upload(&wf, h)) return done(1);
+        const int rc = p->ilv ? launch_imager_build_g(s, p->sotf, 2 * LP, 2, 1, p->tpl, LP, wf, LP, (int)LP, acc, F, T, p->Na, nkb, p->KBP, p->PL)
+                              : launch_imager_build_g(s, p->sotf, LP, 1, p->PL * LP, p->tpl, LP, wf, LP, (int)LP, acc, F, T, p->Na, nkb, p->KBP, p->PL);
+        if (rc) return done(fail("launch_imager_build_g failed: %s", hipGetErrorString((hipError_t)rc)));
+    } else {                 // the imager's own OTF, streamed: chunk -> the plan's padded layout (wavelength innermost) -> the same kernel
+        const int CHP = (chunk + 63) / 64 * 64;
+        const size_t nbin = (size_t)p->Na * nkb;
+        if (dev_alloc(&otf_in, (size_t)chunk * nbin * 2) || dev_alloc(&otf_pl, (size_t)2 * p->PL * CHP) || dev_alloc(&tplc, (size_t)T * CHP) ||
+            dev_alloc(&wf, (size_t)F * CHP))
+            return done(1);
+        std::vector<float> ho((size_t)chunk * nbin * 2), ht((size_t)T * CHP);
+        std::vector<double> hw((size_t)F * CHP);
+        if (hipMemsetAsync(otf_pl, 0, (size_t)2 * p->PL * CHP * sizeof(float), s) != hipSuccess) return done(fail("memset failed"));
+        for (int l0 = 0; l0 < Lc; l0 += chunk) {
+            const int n = std::min(chunk, Lc - l0);
+            const double *src = desc->sotf + (size_t)l0 * nbin * 2;
+            for (size_t i = 0; i < (size_t)n * nbin * 2; ++i) ho[i] = (float)src[i];
+            std::fill(ht.begin(), ht.end(), 0.f);
+            std::fill(hw.begin(), hw.end(), 0.0);
+            for (int l = 0; l < n; ++l) {
+                for (int t = 0; t < T; ++t) ht[(size_t)t * CHP + l] = (float)p->tpl_host[(size_t)t * Lc + l0 + l];
+                for (int f = 0; f < F; ++f) hw[(size_t)f * CHP + l] = desc->filters[(size_t)f * Lc + l0 + l];
+            }
+            if (hipMemcpyAsync(otf_in, ho.data(), (size_t)n * nbin * 2 * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
+                hipMemcpyAsync(tplc, ht.data(), ht.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
+                hipMemcpyAsync(wf, hw.data(), hw.size() * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess)
+                return done(fail("imager: OTF upload failed"));
+            int rc = launch_imager_otf_chunk(s, otf_in, otf_pl, n, CHP, p->Na, nkb, p->KBP, p->PL);
+            if (!rc) rc = launch_imager_build_g(s, otf_pl, CHP, 1, p->PL * CHP, tplc, CHP, wf, CHP, CHP, acc, F, T, p->Na, nkb, p->KBP, p->PL);
+            if (rc) return done(fail("launch_imager_build_g failed: %s", hipGetErrorString((hipError_t)rc)));
+            if (hipStreamSynchronize(s) != hipSuccess) return done(fail("imager: set-up failed on the device"));   // the host buffers are reused
+        }
+    }
+    if (const int rc = launch_imager_g_store(s, acc, g, (long)ng)) return done(fail("launch_imager_g_store failed: %s", hipGetErrorString((hipError_t)rc)));
+    if (hipStreamSynchronize(s) != hipSuccess) return done(fail("imager: set-up failed on the device"));
+    // publish: nothing in flight reads the old buffers; the data of a previous imager go with it (their size is that imager's)
+    std::swap(p->im_g, g); std::swap(p->im_xpad, xpad); std::swap(p->im_xhat, xhat); std::swap(p->im_zpad, zpad);
+    std::swap(p->im_zhat, zhat); std::swap(p->im_io, io);
+    if (ycm) { std::swap(p->ycol_maps, ycm); p->ycm_planes = F; }
+    imager_free({p->im_y, p->im_w, p->im_wy});
+    p->im_y = p->im_w = p->im_wy = nullptr;
+    p->im_mu = 0.0;
+    p->im_F = F; p->im_d = d; p->im_osize = (long)osz;
+    return done(0);
+}
+
+int surfh_imager_osize(const surfh_plan *p) { return p && p->im_g ? (int)p->im_osize : 0; }
+int surfh_has_imager_term(const surfh_plan *p) { return p && imager_active(p) ? 1 : 0; }
+
+static int imager_check(surfh_plan *p, const void *a, const void *b) {
+    if (!p || !a || !b) return fail("null argument");
+    if (!p->im_g) return fail("no imager is attached to this plan (surfh_set_imager)");
+    HIP_OK(hipSetDevice(p->dev));
+    return 0;
+}
+int surfh_imager_forward_dev(surfh_plan *p, const float *maps, float *y_im) {
+    if (imager_check(p, maps, y_im)) return 1;
+    return imager_forward_dev(p, maps, y_im);
+}
+int surfh_imager_adjoint_dev(surfh_plan *p, const float *y_im, float *maps) {
+    if (imager_check(p, y_im, maps)) return 1;
+    return imager_adjoint_dev(p, y_im, maps, 1.f, false);
+}
+int surfh_imager_forward(surfh_plan *p, const float *maps, float *y_im) {
+    if (imager_check(p, maps, y_im)) return 1;
+    HIP_OK(hipMemcpyAsync(p->io_x, maps, p->isize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    if (imager_forward_dev(p, p->io_x, p->im_io)) return 1;
+    HIP_OK(hipMemcpyAsync(y_im, p->im_io, p->im_osize * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+int surfh_imager_adjoint(surfh_plan *p, const float *y_im, float *maps) {
+    if (imager_check(p, y_im, maps)) return 1;
+    HIP_OK(hipMemcpyAsync(p->im_io, y_im, p->im_osize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    if (imager_adjoint_dev(p, p->im_io, p->io_x, 1.f, false)) return 1;
+    HIP_OK(hipMemcpyAsync(maps, p->io_x, p->isize * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+int surfh_imager_fwadj(surfh_plan *p, const float *x, float *out) {
+    if (imager_check(p, x, out)) return 1;
+    if (ensure_cg(p)) return 1;
+    HIP_OK(hipMemcpyAsync(p->io_x, x, p->isize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    if (imager_normal_dev(p, p->io_x, p->cg_q, p->im_y ? p->im_w : nullptr, 1.f, false)) return 1;
+    HIP_OK(hipMemcpyAsync(out, p->cg_q, p->isize * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int surfh_set_imager_data(surfh_plan *p, const float *y_im, const float *w_im, double mu_imager) {
+    if (!p) return fail("null plan");
+    if (!p->im_g) return fail("no imager is attached to this plan (surfh_set_imager)");
+    HIP_OK(hipSetDevice(p->dev));
+    float *y = nullptr, *w = nullptr, *wy = nullptr;
+    auto done = [&](int rc) {
+        imager_free({y, w, wy});
+        return rc;
+    };
+    double mu = 0.0;
+    if (y_im) {
+        if (!(mu_imager >= 0.0 && mu_imager <= DBL_MAX)) return fail("imager: mu_imager = %g must be finite and >= 0", mu_imager);
+        const size_t n = (size_t)p->im_osize;
+        if (w_im)
+            for (size_t i = 0; i < n; ++i)
+                if (!(w_im[i] >= 0.f && w_im[i] <= FLT_MAX)) return fail("imager: weight %ld is %g: weights are finite and >= 0", (long)i, (double)w_im[i]);
+        if (dev_alloc(&y, n) || (w_im && (dev_alloc(&w, n) || dev_alloc(&wy, n)))) return done(1);
+        if (hipMemcpyAsync(y, y_im, n * sizeof(float), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
+            (w_im && hipMemcpyAsync(w, w_im, n * sizeof(float), hipMemcpyHostToDevice, p->stream) != hipSuccess))
+            return done(fail("copy failed"));
+        mu = mu_imager;
+    }
+    if (hipStreamSynchronize(p->stream) != hipSuccess) return done(fail("stream synchronisation failed"));
+    std::swap(p->im_y, y); std::swap(p->im_w, w); std::swap(p->im_wy, wy);
+    p->im_mu = mu;
+    return done(0);
+}
+
+}  // extern "C"

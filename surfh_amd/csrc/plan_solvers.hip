@@ -127,6 +127,14 @@ int normal_prior(surfh_plan *p, const float *v, float *out, double mu, double mu
         Prof pr(p, "prior_add");
         LAUNCH_OK(prior_add(p, p->stream, v, out, p->T > 0 ? p->T : p->Lc, (float)mu_reg));
     }
+    if (imager_active(p) && imager_normal_add(p, v, out)) return 1;       // + mu_imager A_im^T W_im A_im v
+    return 0;
+}
+// the solvers that do not carry the imager term say so instead of ignoring it
+int imager_refuse(const surfh_plan *p, const char *who) {
+    if (p && imager_active(p))
+        return fail("%s does not carry the imager data term set on this plan (surfh_set_imager_data): clear it, or use surfh_cg, "
+                    "surfh_mmmg or surfh_mmmg_huber", who);
     return 0;
 }
 // cg_b = mu A^T W y, cg_q = Q x, cg_r = cg_b - cg_q; y on the device, x already holding the start
@@ -134,6 +142,7 @@ int solver_setup(surfh_plan *p, const float *y, const float *x, double mu, doubl
     if (!(y = weighted_data(p, y))) return 1;
     if (adjoint_dev(p, y, p->cg_b, false)) return 1;
     if (mu != 1.0) LAUNCH_OK(launch_scale(p->stream, p->cg_b, p->isize, (float)mu));
+    if (imager_active(p) && imager_rhs_add(p, p->cg_b)) return 1;           // + mu_imager A_im^T W_im y_im
     if (normal_prior(p, x, p->cg_q, mu, mu_reg)) return 1;
     LAUNCH_OK(launch_residual(p->stream, p->cg_r, p->cg_b, p->cg_q, p->isize));
     return 0;
@@ -258,8 +267,8 @@ int surfh_cg_cb(surfh_plan *p, const float *y, double mu, double mu_reg, const f
     if (p->T <= 0) return fail("surfh_cg needs templates (the priors act on abundance maps)");
     HIP_OK(hipSetDevice(p->dev));
     if (ensure_cg(p)) return 1;
-    {   // SURFH_SPECTRAL_CG=0: vectors are the maps (the loop below)
-        if (env_on("SURFH_SPECTRAL_CG", true) && surfh_spec_supported(p) && max_iter < (1 << 16) - 1)
+    {   // SURFH_SPECTRAL_CG=0, or an imager term (not diagonal in that basis): vectors are the maps (the loop below)
+        if (env_on("SURFH_SPECTRAL_CG", true) && !imager_active(p) && surfh_spec_supported(p) && max_iter < (1 << 16) - 1)
             return cg_spectral(p, y, mu, mu_reg, x0, max_iter, tol, refresh, x, grad_norm, nit, callback, user);
     }
     std::vector<float> hx;             // host copy of the iterate handed to the callback
@@ -544,6 +553,7 @@ int surfh_mmmg_huber_vox(surfh_plan *p, const float *y, double mu, double spat_r
                          double spec_delta, const float *x0, int32_t max_iter, double tol, int32_t refresh, float *x,
                          double *grad_norm, int32_t *nit, double *prior_values, surfh_cg_callback callback, void *user) {
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (imager_refuse(p, "surfh_mmmg_huber_vox")) return 1;
     if (p->T > 0) return fail("surfh_mmmg_huber_vox reconstructs the cube: it needs a plan without templates (n_templates = 0)");
     if (huber_args(spat_reg, spat_delta) || huber_args(spec_reg, spec_delta)) return 1;
     const HuberPrior hp = {2, {spat_reg, spec_reg}, "Huber, voxel-wise", vox_grad, vox_curv, {(float)spat_delta, (float)spec_delta},
@@ -657,6 +667,7 @@ int surfh_mmmg_robust(surfh_plan *p, const float *y, double mu, double data_delt
                       int32_t max_iter, double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit, double *values,
                       float *omega_out, surfh_cg_callback callback, void *user) {
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (imager_refuse(p, "surfh_mmmg_robust")) return 1;
     if (p->T <= 0) return fail("surfh_mmmg_robust needs templates (the priors act on abundance maps)");
     if (robust_args(data_delta) || huber_args(mu_reg, delta)) return 1;
     const HuberPrior hp = {1, {mu_reg, 0.0}, "Huber", maps_grad, maps_curv, {(float)delta, 0.f}, {p->pot[0], 0}};
@@ -668,6 +679,7 @@ int surfh_mmmg_robust_vox(surfh_plan *p, const float *y, double mu, double data_
                           float *x, double *grad_norm, int32_t *nit, double *values, float *omega_out, surfh_cg_callback callback,
                           void *user) {
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (imager_refuse(p, "surfh_mmmg_robust_vox")) return 1;
     if (p->T > 0) return fail("surfh_mmmg_robust_vox reconstructs the cube: it needs a plan without templates (n_templates = 0)");
     if (robust_args(data_delta) || huber_args(spat_reg, spat_delta) || huber_args(spec_reg, spec_delta)) return 1;
     const HuberPrior hp = {2, {spat_reg, spec_reg}, "Huber, voxel-wise", vox_grad, vox_curv, {(float)spat_delta, (float)spec_delta},
@@ -724,6 +736,7 @@ int cg_planes_iter(surfh_plan *p, float *x, double mu, double mu_reg, int it, in
 int surfh_cg_planes_cb(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
                        int32_t refresh, float *x, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (imager_refuse(p, "surfh_cg_planes")) return 1;
     if (p->T != 0) return fail("surfh_cg_planes is the solver of the plane-wise (no template) model; use surfh_cg with templates");
     if (p->ch.empty()) return fail("plan has no channel");
     HIP_OK(hipSetDevice(p->dev));
@@ -808,6 +821,7 @@ bool pn_capable(const surfh_plan *p) {
 
 int surfh_cg_planes_begin_dev(surfh_plan *p, const float *y_dev, double mu, double mu_reg, float *x_dev) {
     if (!p || !y_dev || !x_dev) return fail("null argument");
+    if (imager_refuse(p, "surfh_cg_planes_begin_dev")) return 1;
     if (p->T != 0) return fail("surfh_cg_planes is the solver of the plane-wise (no template) model; use surfh_cg with templates");
     if (p->ch.empty()) return fail("plan has no channel");
     HIP_OK(hipSetDevice(p->dev));
@@ -935,6 +949,7 @@ int mmmg_planes_loop(surfh_plan *p, bool want_hg, const float *y, double mu, dou
 int surfh_mmmg_planes_cb(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
                          int32_t refresh, float *x, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (imager_refuse(p, "surfh_mmmg_planes")) return 1;
     if (p->T != 0) return fail("surfh_mmmg_planes is the solver of the plane-wise (no template) model; use surfh_mmmg with templates");
     if (p->ch.empty()) return fail("plan has no channel");
     HIP_OK(hipSetDevice(p->dev));
@@ -966,6 +981,7 @@ int surfh_mmmg_planes(surfh_plan *p, const float *y, double mu, double mu_reg, c
 // (d_l, m_l) by linearity in float64, solves and moves.
 namespace {
 int huber_planes_ready(surfh_plan *p, const char *who) {
+    if (imager_refuse(p, who)) return 1;
     if (p->T != 0) return fail("%s works on the plane-wise (no template) model; the maps of a template model take surfh_mmmg_huber", who);
     if (p->ch.empty()) return fail("plan has no channel");
     HIP_OK(hipSetDevice(p->dev));

@@ -35,7 +35,8 @@ class OptimizeResult:
 
 class QuadCriterion_MRS:
     def __init__(self, mu_spectro, y_spectro, model_spectro, mu_reg, printing=False, gradient="separated", delta=None, weights=None,
-                 data_delta=None, potential="huber", data_potential="huber"):
+                 data_delta=None, potential="huber", data_potential="huber", mu_imager=None, y_imager=None, model_imager=None,
+                 weights_imager=None):
         """``gradient="joint"`` regularises with the Laplacian of ``Difference_Operator_Joint`` (fusion_CT.py:45-62); udft's
         ``laplacian(2)`` is absent from the reference tree, the 3 x 3 kernel [[0,-1,0],[-1,4,-1],[0,-1,0]] is restated: parity
         unpinned for that option (the operator is checked against the oracle's Fourier-domain form of the same kernel).
@@ -54,7 +55,25 @@ class QuadCriterion_MRS:
         surfh_mmmg_robust); like ``delta`` it needs ``run_method("mmmg")`` and the separated differences.  ``None``: quadratic.
         ``potential`` / ``data_potential`` (Hebert-Leahy is what fusion_CT.py imports beside Huber): the potential under ``delta``
         and under ``data_delta``, "huber" (the default), "hyperbolic" or "hebert_leahy" (``surfh_amd.potentials``); another one
-        than Huber needs its threshold."""
+        than Huber needs its threshold.
+        ``mu_imager`` / ``y_imager`` / ``model_imager`` (the names fusion_CT.py reserves, :68, :243-261): the second instrument,
+        an ``ImagerModel`` built on ``model_spectro``, its data ``[F, Na//d, Nb//d]`` and weight: the criterion gains
+        mu_imager (y_im - A_im x)^T W_im (y_im - A_im x) / 2 (``weights_imager``, not in fusion_CT.py: ``W_im``, 1 by default;
+        include/surfh_amd.h: surfh_set_imager_data), minimised by ``lcg`` and ``mmmg`` (any prior), not with ``data_delta``."""
+        given = [v is not None for v in (mu_imager, y_imager, model_imager)]
+        if any(given) and not all(given):
+            raise ValueError("the imager term needs mu_imager, y_imager and model_imager together")
+        if weights_imager is not None and not all(given):
+            raise ValueError("weights_imager come with mu_imager, y_imager and model_imager")
+        self.imager = None
+        if all(given):
+            from .imager import check_imager_data
+            if data_delta is not None:
+                raise ValueError("the robust data term (data_delta) does not carry the imager data term")
+            if getattr(model_imager, "model", None) is not model_spectro:
+                raise ValueError("y_imager must be compatible with fusion model: model_imager is not built on model_spectro")
+            self.imager = check_imager_data(y_imager, mu_imager, weights_imager, model_imager.osize)      # (y, w, mu)
+        self.mu_imager, self.y_imager, self.model_imager = mu_imager, y_imager, model_imager
         self.potential, self.data_potential = kind_name(potential), kind_name(data_potential)
         need_delta(potential, delta, "delta")
         need_delta(data_potential, data_delta, "data_delta")
@@ -160,6 +179,10 @@ class QuadCriterion_MRS:
                 kw["potential"] = self.potential
             if self.data_potential != "huber":
                 kw["data_potential"] = self.data_potential
+            if self.imager is not None:
+                if self.model_spectro.imager is not self.model_imager:
+                    self.model_spectro.set_imager(self.model_imager)
+                kw["imager"] = (self.imager[0], self.imager[2], self.imager[1])      # set for the solve, cleared afterwards
             x, gn, nit = solver(self.y_spectro, mu=self.mu_spectro, mu_reg=self.mu_reg, x0=init,
                                 max_iter=maximum_iterations, tol=tolerance, callback=callback, **kw)
         finally:
@@ -184,6 +207,11 @@ class QuadCriterion_MRS:
                                                               self.data_potential)
         else:
             data = self.mu_spectro * weighted_sq_residual(self.y_spectro, self.model_spectro.forward(x_hat), w)
+        if self.imager is not None:                  # + mu_imager (y_im - A_im x)^T W_im (y_im - A_im x), halved with the rest below
+            if self.model_spectro.imager is not self.model_imager:
+                self.model_spectro.set_imager(self.model_imager)
+            y_im, w_im, mu_im = self.imager
+            data = data + mu_im * weighted_sq_residual(y_im, self.model_imager.forward(x_hat), w_im)
         if self.delta is not None:
             return data / 2 + self.mu_reg * (_phi(np.roll(x_hat, 1, axis=1) - x_hat, self.delta, self.potential).sum() +
                                              _phi(np.roll(x_hat, 1, axis=2) - x_hat, self.delta, self.potential).sum())
@@ -415,12 +443,14 @@ class DistributedFusion:
     """One rank of the channel-sharded CG.  ``prob`` is a dict as produced by ``surfh_amd.synth.problem``."""
 
     def __init__(self, prob: dict, rank: int = 0, world: int = 1, device: int = 0, with_ref: bool = False,
-                 model_factory=None, split: str = "lambda"):
+                 model_factory=None, split: str = "lambda", mu_imager=None, y_imager=None, model_imager=None):
         """``model_factory(ifus, pointings, lam_slices)`` replaces the HIP operator (used by the gloo tests on
         CPU, where a checker-backed stand-in exposes the same ``*_dev`` methods on CPU tensors).
         ``split``: how a band is shared when there are more ranks than bands -- "lambda" (its wavelength
         window, partial y all-reduced inside the band's group) or "pointing" (its pointings, no extra
         collective but the band's FFT-conv work is repeated on every rank of the group)."""
+        if mu_imager is not None or y_imager is not None or model_imager is not None:
+            raise NotImplementedError("the imager data term is not part of the multi-GPU solver (one-GPU QuadCriterion_MRS carries it)")
         import contextlib
         import torch
         self.torch = torch

@@ -267,3 +267,38 @@ class IFU:
     def pix(self, step):
         return IFU(FOV(self.fov.alpha_width, self.fov.beta_width, self.fov.origin.pix(step), self.fov.angle),
                    self.det_pix_size, self.n_slit, self.w_blur, self.pce, self.wavel_axis, self.name + "_pix")
+
+
+class WavelFilter:
+    """A wavelength filter of the imager (instru.py:700-737): measured transmittance, interpolated on any axis."""
+
+    def __init__(self, measured_wavelength, measured_values, name: str = ""):
+        self.measured_wavelength = measured_wavelength
+        self.measured_values = measured_values
+        self.name = name
+
+    def transmittance(self, wavelengths, normalized: bool = False):
+        """Linear interpolation of the measured values, 0 outside their range; ``normalized``: divided by its sum."""
+        spectrum = np.interp(wavelengths, self.measured_wavelength, self.measured_values, left=0, right=0)
+        if normalized:
+            return spectrum / np.sum(spectrum)
+        else:
+            return spectrum
+
+    def integrate_hsi(self, cube, wavelength):
+        """cube is [lambda, alpha, beta]; returns im[alpha, beta] = sum_lambda cube[lambda, alpha, beta] filter[lambda]."""
+        return sum(image * weight for image, weight in zip(cube, self.transmittance(wavelength, True)))
+
+    def integrate_spectrum(self, spectrum, wavelength) -> float:
+        """i = sum_lambda spectrum[lambda] filter[lambda]."""
+        return np.sum(spectrum * self.transmittance(wavelength, True))
+
+
+@dataclass
+class MSImager:
+    """Multi-spectral imager (instru.py:740-747)."""
+
+    sotf: np.ndarray
+    fov: FOV
+    wfilters: List[WavelFilter]
+    det_pix_size: float

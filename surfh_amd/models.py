@@ -84,6 +84,33 @@ class Channel(ChannelGeometry):
         return op.adjoint_ref(np.ascontiguousarray(s.transpose(1, 0, 2)))
 
 
+class _InstalledImager:
+    def __init__(self, model, imager):
+        self.model, self.args = model, None
+        if imager is not None:
+            from .imager import check_imager_data
+            if model._imager is None:
+                raise ValueError("imager=(y_im, mu_imager[, w_im]) needs an attached imager: set_imager(...) first")
+            if not 2 <= len(imager) <= 3:
+                raise ValueError("imager must be (y_im, mu_imager) or (y_im, mu_imager, w_im)")
+            check_imager_data(imager[0], imager[1], imager[2] if len(imager) == 3 else None, model._imager.osize)
+            self.args = (imager[0], imager[1], imager[2] if len(imager) == 3 else None)
+
+    def __enter__(self):
+        if self.args is not None:
+            self.held = self.model._imager_data
+            self.model.set_imager_data(*self.args)
+
+    def __exit__(self, *exc):
+        if self.args is not None:                    # back to what the model held, as installed_weights does: cleared if nothing
+            if self.held is None:
+                self.model.set_imager_data(None)
+            else:
+                y, mu, w = self.held
+                self.model.set_imager_data(y, mu, w)
+        return False
+
+
 class spectroSigRLSCT(DataWeights, _pot.Potentials, LinOp):
     huber_prior_value = None            # prior value of the last mmmg(delta=...) result (set by mmmg)
     huber_prior_values = None           # (spatial, spectral) prior values of the last mmmg_vox result
@@ -323,22 +350,78 @@ class spectroSigRLSCT(DataWeights, _pot.Potentials, LinOp):
         """The regulariser ``set_prior`` selected last ("separated" on a new model)."""
         return getattr(self, "_prior", "separated")
 
+    # ---- the imager data term (surfh_amd.imager; include/surfh_amd.h: surfh_set_imager) ----------------------------------------
+    _imager = None
+    _imager_data = None
+
+    def set_imager(self, imager_model=None):
+        """Attach ``imager_model`` (an ``ImagerModel`` built on this model) to the plan, or detach with ``None``.  Attaching or
+        detaching clears the imager data."""
+        if imager_model is None:
+            _lib.check(self._L.surfh_set_imager(self._plan, None))
+            self._imager = None
+        else:
+            if imager_model.model is not self:
+                raise ValueError("the ImagerModel was built on another model")
+            imager_model.attach()
+        self._imager_data = None
+
+    @property
+    def imager(self):
+        return self._imager
+
+    def set_imager_data(self, y_im=None, mu_imager=0.0, weights=None):
+        """The imager's data term ``mu_imager (y_im - A_im x)^T W_im (y_im - A_im x) / 2`` of ``cg``, ``mmmg`` and
+        ``mmmg(delta=...)``: plan state until cleared with ``y_im=None``.  ``weights`` ``[F, Na//d, Nb//d]`` follow the rules of
+        the data weights (weight 0 takes the sample out, NaN included).  ``mu_imager = 0`` switches the term off."""
+        from .imager import check_imager_data
+        if self._imager is None:
+            raise ValueError("no imager is attached: set_imager(ImagerModel(model, filters, ...)) first")
+        if y_im is None:
+            _lib.check(self._L.surfh_set_imager_data(self._plan, None, None, 0.0))
+            self._imager_data = None
+            return
+        y, w, mu = check_imager_data(y_im, mu_imager, weights, self._imager.osize)
+        _lib.check(self._L.surfh_set_imager_data(self._plan, _lib.fptr(y), None if w is None else _lib.fptr(w), mu), ValueError)
+        self._imager_data = (y, mu, w)
+
+    @property
+    def imager_data(self):
+        """``(y_im, mu_imager, w_im)`` as set last (float32 vectors, w_im None without weights), or None."""
+        return self._imager_data
+
+    def has_imager_term(self) -> bool:
+        return bool(self._L.surfh_has_imager_term(self._plan))
+
+    def installed_imager(self, imager):
+        """``with model.installed_imager((y_im, mu_imager[, w_im])):`` -- the data are set for the solves inside and cleared
+        afterwards (data set earlier with ``set_imager_data`` are put back instead, the way ``installed_weights`` puts the model's
+        weights back); ``None`` leaves the plan's state alone.  The arguments are checked before any library call."""
+        return _InstalledImager(self, imager)
+
+    def _refuse_imager(self, what, imager=None):
+        if imager is not None or self._imager_data is not None and self._imager_data[1] > 0:
+            raise ValueError(f"{what} does not carry the imager data term: clear it (set_imager_data(None)), or use cg / mmmg")
+
     # ---- solver on one GPU ------------------------------------------------------------------
     def cg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, weights=None,
-           data_delta=None):
+           data_delta=None, imager=None):
         """Device-resident linear CG (qmm.lcg restated).  ``callback(it, grad_norm, x)`` -- the per-iteration callback
         of ``qmm.lcg`` (fusion_CT.py:194-225) -- receives the 1-based iteration, the grad_norm trace so far and the
         current iterate ``[T,Na,Nb]``; it may call ``forward`` / ``adjoint`` on this model; a truthy return stops.
         ``weights``: data weights ``[osize]`` for this solve only, data term mu (y - A x)^T diag(w) (y - A x) (``set_data_weights``;
         what the model held is put back afterwards); None: the model's own state.  ``data_delta`` must stay None: the robust
-        data term of ``mmmg`` is not quadratic."""
+        data term of ``mmmg`` is not quadratic.  ``imager=(y_im, mu_imager[, w_im])``: the imager's data term for this solve
+        (``set_imager_data``; cleared afterwards, or, where ``set_imager_data`` had set a term before, that one put back) -- the
+        loop then runs on the maps, not on their spectra."""
         if data_delta is not None:
             raise ValueError("cg minimises quadratic criteria only: a robust data term (data_delta) needs mmmg")
-        with self.installed_weights(weights):
+        with_imager = self.installed_imager(imager)             # checked here, before any library call
+        with self.installed_weights(weights), with_imager:
             return _lib.solve(self, self._L.surfh_cg_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
 
     def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, delta=None, weights=None,
-             data_delta=None, potential="huber", data_potential="huber"):
+             data_delta=None, potential="huber", data_potential="huber", imager=None):
         """Device-resident 3MG (qmm.mmmg restated for quadratic objectives; the reference's ``method='mmmg'``,
         fusion_CT.py:194-198).  Same arguments as ``cg``; ``grad_norm`` holds |grad| (not squared) of every iterate.
 
@@ -359,10 +442,16 @@ class spectroSigRLSCT(DataWeights, _pot.Potentials, LinOp):
         ``potential`` / ``data_potential``: the potential of the priors under ``delta`` and of the data term under ``data_delta``
         for this call -- "huber" (the default), "hyperbolic" or "hebert_leahy" (``surfh_amd.potentials``); the plan's slots are put
         back afterwards.  ``ValueError`` for another potential than Huber without its threshold.  ``robust_n_beyond`` counts the
-        samples past the knee, |t| > data_delta, whatever the potential."""
+        samples past the knee, |t| > data_delta, whatever the potential.
+
+        ``imager=(y_im, mu_imager[, w_im])``: the imager's data term for this solve, as in ``cg``; not with ``data_delta``
+        (``ValueError`` before the library is reached)."""
         _pot.need_delta(potential, delta, "delta")
         _pot.need_delta(data_potential, data_delta, "data_delta")
-        with _pot.installed(self, spatial=potential, data=data_potential):
+        if data_delta is not None:
+            self._refuse_imager("the robust data term (data_delta)", imager)
+        with_imager = self.installed_imager(imager)             # checked here, before any library call
+        with _pot.installed(self, spatial=potential, data=data_potential), with_imager:
             return self._mmmg(data, mu, mu_reg, x0, max_iter, tol, refresh, callback, delta, weights, data_delta)
 
     def _mmmg(self, data, mu, mu_reg, x0, max_iter, tol, refresh, callback, delta, weights, data_delta):
@@ -430,6 +519,7 @@ class spectroSigRLSCT(DataWeights, _pot.Potentials, LinOp):
         ``spat_potential`` / ``spec_potential`` / ``data_potential``: the potential of the in-plane families, of the wavelength
         family and of the data term for this call, as ``mmmg``'s (a data potential other than Huber needs ``data_delta``)."""
         _pot.need_delta(data_potential, data_delta, "data_delta")
+        self._refuse_imager("mmmg_vox")
         with _pot.installed(self, spatial=spat_potential, spectral=spec_potential, data=data_potential):
             return self._mmmg_vox(data, mu, spat_reg, spat_delta, spec_reg, spec_delta, x0, max_iter, tol, refresh, callback, weights,
                                   data_delta)
