@@ -931,11 +931,14 @@ __global__ __launch_bounds__(TPB) void reduce_final_kernel(const double *__restr
     if (threadIdx.x == 0) out[0] = s;
 }
 
+// ---- the CG vector updates of the map-domain and spectral loops, scalars read from the device.  A residual that is already
+// zero (no data, every weight zero, or converged exactly) gives rr = d.q = 0: step and beta are then 0, not 0/0, and the iterate
+// keeps still, as in the plane-wise kernels below.
 __global__ __launch_bounds__(TPB) void cg_step_kernel(float *__restrict__ x, float *__restrict__ r,
                                                       const float *__restrict__ d, const float *__restrict__ q,
                                                       long n, const double *__restrict__ rr,
                                                       const double *__restrict__ dq, double *__restrict__ scratch) {
-    const float step = (float)(rr[0] / dq[0]);
+    const float step = dq[0] != 0.0 ? (float)(rr[0] / dq[0]) : 0.f;
     double s = 0.0;
     const long stride = (long)gridDim.x * TPB;
     for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < n; i += stride) {
@@ -951,7 +954,7 @@ __global__ __launch_bounds__(TPB) void cg_step_kernel(float *__restrict__ x, flo
 __global__ __launch_bounds__(TPB) void cg_xupdate_kernel(float *__restrict__ x, const float *__restrict__ d, long n,
                                                          const double *__restrict__ rr,
                                                          const double *__restrict__ dq) {
-    const float step = (float)(rr[0] / dq[0]);
+    const float step = dq[0] != 0.0 ? (float)(rr[0] / dq[0]) : 0.f;
     const long stride = (long)gridDim.x * TPB;
     for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < n; i += stride) x[i] += step * d[i];
 }
@@ -959,7 +962,7 @@ __global__ __launch_bounds__(TPB) void cg_xupdate_kernel(float *__restrict__ x, 
 __global__ __launch_bounds__(TPB) void cg_dir_kernel(float *__restrict__ d, const float *__restrict__ r, long n,
                                                      const double *__restrict__ rr_new,
                                                      const double *__restrict__ rr_old) {
-    const float beta = (float)(rr_new[0] / rr_old[0]);
+    const float beta = rr_old[0] != 0.0 ? (float)(rr_new[0] / rr_old[0]) : 0.f;
     const long stride = (long)gridDim.x * TPB;
     for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < n; i += stride) d[i] = r[i] + beta * d[i];
 }
@@ -991,7 +994,7 @@ __global__ __launch_bounds__(TPB) void cg_step_parts_kernel(float *__restrict__ 
                                                             double *__restrict__ scratch) {
     const double dq = parts_sum(dq_parts, nparts);
     if (blockIdx.x == 0 && threadIdx.x == 0) dq_out[0] = dq;
-    const float step = (float)(rr[0] / dq);
+    const float step = dq != 0.0 ? (float)(rr[0] / dq) : 0.f;
     double s = 0.0;
     const long stride = (long)gridDim.x * TPB;
     for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < n; i += stride) {
@@ -1010,7 +1013,7 @@ __global__ __launch_bounds__(TPB) void cg_dir_parts_kernel(float *__restrict__ d
                                                            const double *__restrict__ rr_old, double *__restrict__ rr_out) {
     const double rrn = parts_sum(rr_parts, nparts);
     if (blockIdx.x == 0 && threadIdx.x == 0) rr_out[0] = rrn;
-    const float beta = (float)(rrn / rr_old[0]);
+    const float beta = rr_old[0] != 0.0 ? (float)(rrn / rr_old[0]) : 0.f;
     const long stride = (long)gridDim.x * TPB;
     for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < n; i += stride) d[i] = r[i] + beta * d[i];
 }
