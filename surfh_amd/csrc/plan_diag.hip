@@ -78,6 +78,9 @@ static int resolve(surfh_plan *p, const char *which, const float **ptr, int64_t 
         for (auto &c : p->ch)
             for (int i = 0; i < 4; ++i) dims[i] += c.ksteps[i];
         for (int i = 0; i < 4; ++i) dims[i] -= 1;
+    } else if (w == "groups") {        // workgroups of the grouped gather / grouped scatter tables, all channels (0: row by row)
+        dims[0] = dims[1] = 0;
+        for (auto &c : p->ch) { dims[0] += c.fwd.g.NG; dims[1] += c.adjT.g.NG; }
     } else if (w == "info") {
         dims[0] = p->lo; dims[1] = p->hi; dims[2] = p->Lown; dims[3] = (int64_t)p->segs.size();
     } else {

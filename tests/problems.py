@@ -124,6 +124,60 @@ def two_channel_mid():
                 templates=tpl, sotf=sotf, pointings=[p1, p2], maps=maps, step_deg=STEP_DEG)
 
 
+def mk(N, Lc, wav_lo, wav_hi, chans, seed):
+    """A problem of NxN pixels and ``Lc`` planes from a list of channels
+    (fov_a ["], fov_b ["], angle, n_slit, grating resolution, detector axis, number of dither points, name)."""
+    ax = orc.synthetic_axes(N, STEP_DEG)
+    wav = np.linspace(wav_lo, wav_hi, Lc)
+    specs = [orc.ChannelSpec(fa / 3600, fb / 3600, (0.0, 0.0), ang, 0.196, ns, float(R), det, name)
+             for fa, fb, ang, ns, R, det, _, name in chans]
+    pts = [orc.dither4(s.det_pix_size, s.beta_width / s.n_slit)[:c[6]] for s, c in zip(specs, chans)]
+    tpl = orc.synthetic_templates(Lc)
+    sotf = orc.ir2fr(orc.gaussian_psf(wav, STEP), (N, N))
+    maps = np.random.default_rng(seed).random((4, N, N))
+    return dict(N=N, Lc=Lc, alpha_axis=ax, beta_axis=ax.copy(), wavel=wav, specs=specs, templates=tpl, sotf=sotf,
+                pointings=pts, maps=maps, step_deg=STEP_DEG)
+
+
+# The edge problems below reach, at 48 x 48 pixels, the code paths that otherwise only the full-size configs take
+# (tests/test_gpu_local_parity.py).  The oracle's windows are asserted in tests/test_local_metrics_host.py.
+LONG_WINDOWS = [(0, 1315), (813, 2303)]
+THREE_WINDOWS = {"A": (0, 62), "B": (4, 127), "C": (68, 127)}
+FIVE_WINDOWS = [(0, 69), (7, 93), (31, 117), (55, 141), (79, 159)]
+
+
+def long_windows():
+    """48x48x2304, two channels whose wavelength windows (0, 1315) and (813, 2303) and detector axes (1100 and 1060 samples) are
+    all longer than 1024: a second 1024-plane chunk in the gather and scatter grids, two block-scale segments per beta column of
+    the forward GEMM operand, more than 32 K steps in the adjoint GEMM.  The overlap 813..1315 lies in chunk 0 of the second
+    channel only, so its two read-modify-write mask bits differ; the plan reads the masks only on the cleared-cube path
+    (SURFH_ADJ_CLEAR=1), by default it keeps the exact-range accumulator."""
+    return mk(48, 2304, 7.0, 8.84,
+              [(0.6, 0.7, 8.2, 3, 3050, np.linspace(7.05, 7.95, 1100), 2, "A"),
+               (0.7, 0.6, -5.0, 2, 2900, np.linspace(7.75, 8.80, 1060), 2, "B")], seed=31)
+
+
+def three_channels(order="ABC"):
+    """48x48x128, three channels with windows A (0, 62), B (4, 127), C (68, 127), listed in ``order``.  "ABC": the third channel's
+    exact read-modify-write range is a union over its earlier neighbours.  "ACB": the middle band comes last, its overlap with the
+    earlier channels at a shared pixel is two pieces with a gap (4..62 and 68..127), which no single range describes: the plan
+    must fall back to the cleared cube and the chunk masks."""
+    ch = {"A": (0.6, 0.7, 8.2, 3, 3050, np.linspace(7.45, 7.55, 40), 2, "A"),
+          "B": (0.7, 0.6, -5.0, 2, 2900, np.linspace(7.52, 7.82, 36), 2, "B"),
+          "C": (0.5, 0.75, 3.0, 3, 3000, np.linspace(7.78, 7.88, 44), 1, "C")}
+    return mk(48, 128, 7.40, 7.92, [ch[k] for k in order], seed=32)
+
+
+def five_channels():
+    """48x48x160, five channels in ascending bands, every interior plane covered by two or three of them: one more channel than
+    a grouped adjoint GEMM launch takes (GEMM_GROUP_MAX = 4, so 4 + 1), exact ranges that are unions over up to two earlier
+    channels."""
+    ang = (8.2, -5.0, 3.0, -8.0, 6.0)
+    return mk(48, 160, 7.40, 8.00,
+              [(0.55 + 0.03 * (i % 3), 0.65 - 0.03 * (i % 2), ang[i], 2 + i % 2, 3000,
+                np.linspace(7.44 + 0.09 * i, 7.56 + 0.09 * i, 30 + 3 * i), 1 + i % 2, "C%d" % i) for i in range(5)], seed=33)
+
+
 def oracle_model(cfg, box="fft", gridding="bilinear"):
     return orc.OracleModel(cfg["sotf"], cfg["templates"], cfg["alpha_axis"], cfg["beta_axis"],
                            cfg["wavel"], cfg["specs"], cfg["step_deg"], cfg["pointings"], box=box, gridding=gridding)

@@ -12,13 +12,12 @@ import numpy as np
 import pytest
 
 import problems
-from helpers import build_model, rel
+from helpers import TOL, build_model, rel
 from oracle import surfh_oracle as orc
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(__file__), "golden")
 OUT = os.path.join(os.path.dirname(os.path.dirname(__file__)), "gpurun_out")
-TOL = 1e-5
 
 
 def note(name, **kw):
