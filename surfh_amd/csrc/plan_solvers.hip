@@ -1,8 +1,10 @@
-// Host side of the C ABI (include/surfh_amd.h), the solvers: the CG building blocks, surfh_cg, the 3MG loops (quadratic, Huber,
-// voxel-wise, robust data term) with their prior / curvature diagnostics, and the plane-wise solvers.  They call the operators of
-// plan_ops.hip and nothing calls them.  Plan struct and data layout: plan_internal.h.
+// Host side of the C ABI (include/surfh_amd.h), the solvers: the CG building blocks, the CG frame (cg_start / cg_iteration / cg_loop
+// on the maps, their spectra and the planes: surfh_cg, surfh_cg_planes and the device-resident plane loop), the 3MG loops (quadratic,
+// Huber, voxel-wise, robust data term) with their prior / curvature diagnostics.  They call the operators of plan_ops.hip and
+// nothing calls them.  Plan struct and data layout: plan_internal.h.
 #include "plan_internal.h"
 #include "mm_step.h"
+#include <optional>
 
 extern "C" {
 
@@ -118,7 +120,7 @@ int surfh_residual_dev(surfh_plan *p, float *r, const float *b, const float *q, 
     return 0;
 }
 
-// ---- full CG on one GPU (qmm.lcg semantics, see oracle/surfh_oracle.py:lcg) -------------------
+// ---- what the CG and the 3MG loops share, and their frames ----
 namespace {
 // out = Q v = mu A^T A v (+ mu_reg prior(v)): the operator of the map- and plane-domain solvers
 int normal_prior(surfh_plan *p, const float *v, float *out, double mu, double mu_reg) {
@@ -161,6 +163,12 @@ int callback_iterate(surfh_plan *p, surfh_cg_callback callback, void *user, int 
     return CB_GO_ON;
 }
 
+// the start of a solver called with host buffers: x0 [isize], or zeros, to cg_x
+int start_iterate(surfh_plan *p, const float *x0) {
+    if (x0) HIP_OK(hipMemcpyAsync(p->cg_x, x0, p->isize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    else LAUNCH_OK(launch_fill_zero(p->stream, p->cg_x, p->isize));
+    return 0;
+}
 // ---- the frame of every 3MG loop (the variants and what each plugs in: the 3MG sections below) ----
 // Start: the work buffers (cg_hg where the variant keeps -g apart from r), y [osize] to yd, x0 or zeros to cg_x, zeros to the
 // memory direction cg_d and to its image: cg_qm (with cg_dd beside it), or the caller's detector vector `am` [osize].
@@ -170,10 +178,7 @@ int mmmg_begin(surfh_plan *p, bool want_hg, const float *y, float *yd, const flo
     if (!am && !p->cg_qm && (dev_alloc(&p->cg_qm, (size_t)p->isize) || dev_alloc(&p->cg_dd, (size_t)p->isize))) return 1;
     if (want_hg && !p->cg_hg && dev_alloc(&p->cg_hg, (size_t)p->isize)) return 1;
     HIP_OK(hipMemcpyAsync(yd, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
-    if (x0)
-        HIP_OK(hipMemcpyAsync(p->cg_x, x0, p->isize * sizeof(float), hipMemcpyHostToDevice, s));
-    else
-        LAUNCH_OK(launch_fill_zero(s, p->cg_x, p->isize));
+    if (start_iterate(p, x0)) return 1;
     LAUNCH_OK(launch_fill_zero(s, p->cg_d, p->isize));
     if (am)
         LAUNCH_OK(launch_fill_zero(s, am, p->osize));
@@ -208,55 +213,237 @@ int diag_pass(surfh_plan *p, const char *name, const std::function<int()> &launc
     return 0;
 }
 
-// The loop bench.py times, behind the exported solver: vectors = the maps' Parseval-scaled half spectra (surfh_normal_spec_dev:
-// no transform of the maps, no padding, no prior kernel inside an iteration), every scalar on the device
-// (surfh_cg_iter_nosync_dev), and the host reads the r.r trace -- the stopping test of qmm.lcg -- only every CG_CHECK iterations:
-// the loop may run up to CG_CHECK - 1 iterations past the one that met the tolerance (nit and x are those of the last iteration
-// run, grad_norm holds every r.r).  With a callback installed the trace and the iterate go to the host after every iteration,
-// as the callback's contract says.
-constexpr int CG_CHECK = 8;
-int cg_spectral(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol, int32_t refresh,
-                float *x, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
-    std::vector<float> hx;             // host copy of the iterate handed to the callback
-    hipStream_t s = p->stream;
-    const long n = p->isize, nv = 2L * p->T * p->PL;
-    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
-    const float *wy = weighted_data(p, p->io_y);
-    if (!wy || surfh_adjoint_spec_dev(p, wy, p->cg_b, mu, nullptr, 0.0)) return 1;          // b = mu A^T W y
+// ---- the frame of every CG loop (qmm.lcg, see oracle/surfh_oracle.py:lcg): cg_start, cg_iteration, cg_loop on a CgSpace ----
+// A CgSpace is the vector space of one run: its buffers, the device scalars of an iteration and the kernels that differ.
+//   maps      surfh_cg with SURFH_SPECTRAL_CG=0 or an imager term: normal_prior, one scalar per slot in dscal
+//   spectra   surfh_cg, the loop bench.py times: the maps' Parseval-scaled half spectra (surfh_normal_spec_dev: no transform of the
+//             maps, no padding, no prior kernel inside an iteration) under the surfh_cg_*_nosync_dev blocks, every scalar in the trace
+//   planes    surfh_cg_planes, and _begin_dev / _step_dev under SURFH_PLANES_NATIVE=0: the caller's [Lc][Na][Nb] layout, normal_prior,
+//             Lc scalars per slot in pl_sc
+//   native    surfh_cg_planes_begin_dev / _step_dev: the cube's wavelength-innermost layout (no layout transpose inside an
+//             iteration), pn_normal with d.q fused into its last kernel, LP scalars per slot in pn_sc
+struct CgSpace {
+    float *x, *r, *d, *q, *b;      // iterate, residual, direction, Q d, right-hand side: `len` floats each
+    float *xc;                     // the iterate in the caller's layout, on the device [isize]: x itself where the layouts agree
+    long len, n;                   // ... and a row of the trace meets the tolerance when sqrt(its largest r.r) < n tol
+    int rows;                      // independent problems: the row length of the r.r trace
+    double mu, mu_reg;
+    double *rr, *dq, *rrn;         // device scalars, one per problem: r.r, d.q, the new r.r (spectra: they live in the trace)
+    int (*setup)(surfh_plan *p, const CgSpace &s, const float *y, const float *x0);   // b = mu A^T W y, x = x0, r = b - Q x
+    int (*rr0)(surfh_plan *p, const CgSpace &s);                                      // rr = r.r: entry 0 of the trace
+    int (*apply)(surfh_plan *p, const CgSpace &s, const float *v);                    // q = Q v (native: and dq = v.q)
+    int (*step)(surfh_plan *p, const CgSpace &s, int update_r);    // dq = d.q, x += (rr / dq) d; update_r: r -= (rr / dq) q, rrn = r.r
+    int (*refresh)(surfh_plan *p, const CgSpace &s);               // r = b - q, rrn = r.r
+    int (*dir)(surfh_plan *p, const CgSpace &s);                   // d = r + (rrn / rr) d, rr = rrn
+    int (*trace)(surfh_plan *p, const CgSpace &s, double *grad_norm, int it);         // rows 0 .. it of the trace on the host
+    int (*to_caller)(surfh_plan *p, const CgSpace &s);                                // xc = x in the caller's layout
+};
+int cg_nop(surfh_plan *, const CgSpace &) { return 0; }     // to_caller: the layouts agree; dir: the step's block went on to the direction
+// the maps and the planes keep the current row only: it goes to the host after every iteration
+int row_trace(surfh_plan *p, const CgSpace &s, double *grad_norm, int it) {
+    HIP_OK(hipMemcpyAsync(grad_norm + (size_t)it * s.rows, s.rr, s.rows * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+int img_setup(surfh_plan *p, const CgSpace &s, const float *y, const float *) { return solver_setup(p, y, s.x, s.mu, s.mu_reg); }
+int img_apply(surfh_plan *p, const CgSpace &s, const float *v) { return normal_prior(p, v, s.q, s.mu, s.mu_reg); }
+int maps_rr0(surfh_plan *p, const CgSpace &s) { LAUNCH_OK(launch_dot(p->stream, s.r, s.r, s.len, p->dscratch, s.rr)); return 0; }
+int maps_step(surfh_plan *p, const CgSpace &s, int update_r) {
+    LAUNCH_OK(launch_dot(p->stream, s.d, s.q, s.len, p->dscratch, s.dq));
+    if (update_r) {
+        Prof pr(p, "cg_step");
+        LAUNCH_OK(launch_cg_step(p->stream, s.x, s.r, s.d, s.q, s.len, s.rr, s.dq, p->dscratch, s.rrn));
+    } else LAUNCH_OK(launch_cg_xupdate(p->stream, s.x, s.d, s.len, s.rr, s.dq));
+    return 0;
+}
+int maps_refresh(surfh_plan *p, const CgSpace &s) {
+    LAUNCH_OK(launch_residual(p->stream, s.r, s.b, s.q, s.len));
+    LAUNCH_OK(launch_dot(p->stream, s.r, s.r, s.len, p->dscratch, s.rrn));
+    return 0;
+}
+int maps_dir(surfh_plan *p, const CgSpace &s) {
+    LAUNCH_OK(launch_cg_dir(p->stream, s.d, s.r, s.len, s.rrn, s.rr));
+    HIP_OK(hipMemcpyAsync(s.rr, s.rrn, sizeof(double), hipMemcpyDeviceToDevice, p->stream));
+    return 0;
+}
+CgSpace maps_space(surfh_plan *p, double mu, double mu_reg) {
+    return {p->cg_x, p->cg_r, p->cg_d, p->cg_q, p->cg_b, p->cg_x, p->isize, p->isize, 1, mu, mu_reg, p->dscal + 0, p->dscal + 1, p->dscal + 2,
+            img_setup, maps_rr0, img_apply, maps_step, maps_refresh, maps_dir, row_trace, cg_nop};
+}
+int spec_setup(surfh_plan *p, const CgSpace &s, const float *y, const float *x0) {
+    const float *wy = weighted_data(p, y);
+    if (!wy || surfh_adjoint_spec_dev(p, wy, s.b, s.mu, nullptr, 0.0)) return 1;
     if (x0) {
-        HIP_OK(hipMemcpyAsync(p->io_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
-        if (surfh_to_spec_dev(p, p->io_x, p->cg_x) || surfh_normal_spec_dev(p, p->cg_x, p->cg_q, mu, mu_reg)) return 1;
-        LAUNCH_OK(launch_residual(s, p->cg_r, p->cg_b, p->cg_q, nv));
+        if (surfh_to_spec_dev(p, x0, s.x) || surfh_normal_spec_dev(p, s.x, s.q, s.mu, s.mu_reg)) return 1;
+        LAUNCH_OK(launch_residual(p->stream, s.r, s.b, s.q, s.len));
     } else {                                                                                // r = b - Q 0
-        LAUNCH_OK(launch_fill_zero(s, p->cg_x, nv));
-        HIP_OK(hipMemcpyAsync(p->cg_r, p->cg_b, nv * sizeof(float), hipMemcpyDeviceToDevice, s));
+        LAUNCH_OK(launch_fill_zero(p->stream, s.x, s.len));
+        HIP_OK(hipMemcpyAsync(s.r, s.b, s.len * sizeof(float), hipMemcpyDeviceToDevice, p->stream));
     }
-    HIP_OK(hipMemcpyAsync(p->cg_d, p->cg_r, nv * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (surfh_cg_begin_dev(p, p->cg_r, nv)) return 1;
+    return 0;
+}
+int spec_rr0(surfh_plan *p, const CgSpace &s) { return surfh_cg_begin_dev(p, s.r, s.len); }
+int spec_apply(surfh_plan *p, const CgSpace &s, const float *v) { return surfh_normal_spec_dev(p, v, s.q, s.mu, s.mu_reg); }
+int spec_step(surfh_plan *p, const CgSpace &s, int update_r) {
+    return update_r ? surfh_cg_iter_nosync_dev(p, s.x, s.r, s.d, s.q, s.len) : surfh_cg_xupdate_nosync_dev(p, s.x, s.d, s.q, s.len);
+}
+int spec_refresh(surfh_plan *p, const CgSpace &s) { return surfh_cg_refresh_nosync_dev(p, s.r, s.b, s.q, s.d, s.len); }
+int spec_trace(surfh_plan *p, const CgSpace &, double *grad_norm, int it) {                // synchronises
+    return surfh_cg_trace(p, grad_norm, it + 1) != it + 1 ? fail("CG trace read failed") : 0;
+}
+int spec_to_caller(surfh_plan *p, const CgSpace &s) { return surfh_from_spec_dev(p, s.x, s.xc); }
+CgSpace spectral_space(surfh_plan *p, double mu, double mu_reg) {
+    return {p->cg_x, p->cg_r, p->cg_d, p->cg_q, p->cg_b, p->io_x, 2L * p->T * p->PL, p->isize, 1, mu, mu_reg, nullptr, nullptr, nullptr,
+            spec_setup, spec_rr0, spec_apply, spec_step, spec_refresh, cg_nop, spec_trace, spec_to_caller};
+}
+int planes_rr0(surfh_plan *p, const CgSpace &s) { LAUNCH_OK(launch_dot_planes(p->stream, s.r, s.r, s.rows, s.n, s.rr)); return 0; }
+int planes_step(surfh_plan *p, const CgSpace &s, int update_r) {
+    LAUNCH_OK(launch_dot_planes(p->stream, s.d, s.q, s.rows, s.n, s.dq));
+    LAUNCH_OK(launch_cg_step_planes(p->stream, s.x, s.r, s.d, s.q, s.rows, s.n, s.rr, s.dq, s.rrn, update_r));
+    return 0;
+}
+int planes_refresh(surfh_plan *p, const CgSpace &s) {
+    LAUNCH_OK(launch_residual(p->stream, s.r, s.b, s.q, s.len));
+    LAUNCH_OK(launch_dot_planes(p->stream, s.r, s.r, s.rows, s.n, s.rrn));
+    return 0;
+}
+int planes_dir(surfh_plan *p, const CgSpace &s) { LAUNCH_OK(launch_cg_dir_planes(p->stream, s.d, s.r, s.rows, s.n, s.rrn, s.rr)); return 0; }
+CgSpace planes_space(surfh_plan *p, float *x, double mu, double mu_reg) {
+    const int L = p->Lc;
+    return {x, p->cg_r, p->cg_d, p->cg_q, p->cg_b, x, p->isize, (long)p->Na * p->Nb, L, mu, mu_reg, p->pl_sc, p->pl_sc + L, p->pl_sc + 2 * L,
+            img_setup, planes_rr0, img_apply, planes_step, planes_refresh, planes_dir, row_trace, cg_nop};
+}
+struct PnScope {                       // forward_dev / adjoint_dev read and write wavelength-innermost vectors for the duration of a call
+    surfh_plan *p;
+    explicit PnScope(surfh_plan *pl) : p(pl) { p->pn_native = true; }
+    ~PnScope() { p->pn_native = false; }
+};
+// q = mu A^T A v (+ mu_reg prior, fused with the dot product v . q -> dq) on wavelength-innermost vectors
+int pn_normal(surfh_plan *p, const float *v, float *q, double *dq) {
+    PnScope sc(p);
+    // with interleaved spectra and a prior weight the OTF product of the adjoint applies mu and adds the prior (adjoint_tail): the
+    // two halves are called directly so that no scaling pass follows
+    // (plans whose inverse transform forms the OTF product in its loader -- prod_capable -- take mu and the prior on that pass)
+    const bool prod = prod_capable(p) && p->pl_mu != 0.0;
+    const bool fold = prod || (p->ilv && !p->dense_dft && p->pl_mu_reg != 0.0);
+    if (fold) {
+        p->pn_fold_prior = true;
+        const int rc = normal_halves(p, v, q);
+        p->pn_fold_prior = false;
+        if (rc) return 1;
+    } else if (normal_dev(p, v, q, p->pl_mu)) {
+        return 1;
+    }
+    Prof pr(p, "pn_prior_dot");
+    if (fold) LAUNCH_OK(launch_pn_dot(p->stream, v, q, p->Na, p->Nb, p->NAP, p->LP, p->pn_part, dq));
+    else LAUNCH_OK(launch_pn_prior_dot(p->stream, v, q, p->Na, p->Nb, p->NAP, p->LP, (float)p->pl_mu_reg, p->pn_part, dq));
+    return 0;
+}
+bool pn_capable(const surfh_plan *p) {
+    const bool on = env_on("SURFH_PLANES_NATIVE", true);       // 0: vectors in the caller's [Lc][Na][Nb] layout (two transposes per operator application)
+    return on && p->T == 0 && p->segs.size() == 1 && p->segs[0].coff == 0 && p->segs[0].start == 0 && p->Lown == p->Lc && p->prior_kind == 0 &&
+           p->LP % 64 == 0;
+}
+int pn_setup(surfh_plan *p, const CgSpace &s, const float *y, const float *x0) {     // mu and mu_reg: the plan's pl_mu, pl_mu_reg
+    LAUNCH_OK(launch_cube_to_lam_inner(p->stream, x0, s.x, 0, p->Lc, p->Na, p->Nb, p->NAP, p->LP));
+    {
+        const float *wy = weighted_data(p, y);
+        PnScope sc(p);
+        if (!wy || adjoint_dev(p, wy, s.b, false)) return 1;
+    }
+    if (s.mu != 1.0) LAUNCH_OK(launch_scale(p->stream, s.b, s.len, (float)s.mu));
+    if (pn_normal(p, s.x, s.q, s.dq)) return 1;
+    LAUNCH_OK(launch_residual(p->stream, s.r, s.b, s.q, s.len));
+    return 0;
+}
+int pn_rr0(surfh_plan *p, const CgSpace &s) { LAUNCH_OK(launch_pn_dot(p->stream, s.r, s.r, p->Na, p->Nb, p->NAP, p->LP, p->pn_part, s.rr)); return 0; }
+int pn_apply(surfh_plan *p, const CgSpace &s, const float *v) { return pn_normal(p, v, s.q, s.dq); }
+int pn_step(surfh_plan *p, const CgSpace &s, int update_r) {
+    std::optional<Prof> pr;
+    if (update_r) pr.emplace(p, "pn_step");
+    LAUNCH_OK(launch_pn_step(p->stream, s.x, s.r, s.d, s.q, p->Na, p->Nb, p->NAP, p->LP, s.rr, s.dq, p->pn_part, s.rrn, update_r));
+    return 0;
+}
+int pn_refresh(surfh_plan *p, const CgSpace &s) {
+    LAUNCH_OK(launch_residual(p->stream, s.r, s.b, s.q, s.len));
+    LAUNCH_OK(launch_pn_dot(p->stream, s.r, s.r, p->Na, p->Nb, p->NAP, p->LP, p->pn_part, s.rrn));
+    return 0;
+}
+int pn_dir(surfh_plan *p, const CgSpace &s) {
+    {
+        Prof pr(p, "pn_dir");
+        LAUNCH_OK(launch_pn_dir(p->stream, s.d, s.r, p->Na, p->Nb, p->NAP, p->LP, s.rrn, s.rr));
+    }
+    HIP_OK(hipMemcpyAsync(s.rr, s.rrn, (size_t)p->LP * sizeof(double), hipMemcpyDeviceToDevice, p->stream));
+    return 0;
+}
+int pn_to_caller(surfh_plan *p, const CgSpace &s) {
+    LAUNCH_OK(launch_cube_from_lam_inner(p->stream, s.x, s.xc, 0, p->Lc, p->Na, p->Nb, p->NAP, p->LP));
+    return 0;
+}
+// what an entry point of the plane-wise CG checks and allocates before it builds its space
+int cg_planes_ready(surfh_plan *p, const char *who, bool native) {
+    if (imager_refuse(p, who)) return 1;
+    if (p->T != 0) return fail("surfh_cg_planes is the solver of the plane-wise (no template) model; use surfh_cg with templates");
+    if (p->ch.empty()) return fail("plan has no channel");
+    HIP_OK(hipSetDevice(p->dev));
+    if (!native) return ensure_cg(p) || (!p->pl_sc && dev_alloc(&p->pl_sc, (size_t)3 * p->Lc));
+    // vectors in the cube's layout: the caller's x is transposed in here and out again at the end of every step call
+    const size_t nc = (size_t)p->NBP * p->NAP * p->LP;
+    for (float *&v : p->pn_v)
+        if (!v) {
+            if (dev_alloc(&v, nc)) return 1;
+            HIP_OK(hipMemsetAsync(v, 0, nc * sizeof(float), p->stream));       // the padding (rows >= Nb, columns >= Na, planes >= Lc) stays zero
+        }
+    return !p->pn_sc && (dev_alloc(&p->pn_sc, (size_t)3 * p->LP) || dev_alloc(&p->pn_part, pn_part_doubles(p->LP)));
+}
+// the plane space surfh_cg_planes_begin_dev chose, from what it left in the plan (pn_active, pl_x, pl_mu, pl_mu_reg)
+CgSpace stored_space(surfh_plan *p) {
+    if (!p->pn_active) return planes_space(p, p->pl_x, p->pl_mu, p->pl_mu_reg);
+    float *const *v = p->pn_v;
+    return {v[0], v[1], v[2], v[3], v[4], p->pl_x, (long)p->NBP * p->NAP * p->LP, (long)p->Na * p->Nb, p->Lc, p->pl_mu, p->pl_mu_reg,
+            p->pn_sc, p->pn_sc + p->LP, p->pn_sc + 2 * p->LP, pn_setup, pn_rr0, pn_apply, pn_step, pn_refresh, pn_dir, row_trace, pn_to_caller};
+}
+
+// y and x0 on the device, x0 in the caller's layout (s.xc; the spectra take NULL for zeros): b, r = b - Q x, d = r, trace entry 0
+int cg_start(surfh_plan *p, const CgSpace &s, const float *y, const float *x0) {
+    if (s.setup(p, s, y, x0)) return 1;
+    HIP_OK(hipMemcpyAsync(s.d, s.r, s.len * sizeof(float), hipMemcpyDeviceToDevice, p->stream));
+    return s.rr0(p, s);
+}
+// iteration `it` of qmm.lcg, nothing read by the host; the residual is recomputed from x in the iterations `refresh` divides
+int cg_iteration(surfh_plan *p, const CgSpace &s, int it, int refresh) {
+    const bool fresh = refresh_due(refresh, it);
+    if (s.apply(p, s, s.d) || s.step(p, s, fresh ? 0 : 1)) return 1;
+    if (fresh && (s.apply(p, s, s.x) || s.refresh(p, s))) return 1;
+    return s.dir(p, s);
+}
+// The iterations after cg_start and the copy-out to x [isize].  The host reads the trace -- the stopping test of qmm.lcg, on the
+// worst problem of a row -- every `check` iterations (1 where the space keeps one row: row_trace) and at max_iter: the loop may run
+// up to check - 1 iterations past the one that met the tolerance (nit and x are those of the last iteration run, grad_norm holds
+// every r.r).  With a callback the trace so far [it + 1][rows] and the iterate go to the host after every iteration, as its contract says.
+constexpr int CG_CHECK = 8;
+int cg_loop(surfh_plan *p, const CgSpace &s, int32_t max_iter, double tol, int32_t refresh, int check, float *x, double *grad_norm,
+            int32_t *nit, surfh_cg_callback callback, void *user) {
+    std::vector<float> hx;             // host copy of the iterate handed to the callback
+    if (callback) check = 1;
+    if (s.trace(p, s, grad_norm, 0)) return 1;
     *nit = 0;
     for (int it = 0; it < max_iter; ++it) {
-        if (surfh_normal_spec_dev(p, p->cg_d, p->cg_q, mu, mu_reg)) return 1;
-        if (refresh > 0 && it % refresh == 0) {             // residual recomputed from scratch
-            if (surfh_cg_xupdate_nosync_dev(p, p->cg_x, p->cg_d, p->cg_q, nv) || surfh_normal_spec_dev(p, p->cg_x, p->cg_q, mu, mu_reg) ||
-                surfh_cg_refresh_nosync_dev(p, p->cg_r, p->cg_b, p->cg_q, p->cg_d, nv))
-                return 1;
-        } else if (surfh_cg_iter_nosync_dev(p, p->cg_x, p->cg_r, p->cg_d, p->cg_q, nv)) {
-            return 1;
-        }
+        if (cg_iteration(p, s, it, refresh)) return 1;
         *nit = it + 1;
-        if (!callback && (it + 1) % CG_CHECK != 0 && it + 1 != max_iter) continue;
-        if (surfh_cg_trace(p, grad_norm, it + 2) != it + 2) return fail("CG trace read failed");     // synchronises
-        if (callback && surfh_from_spec_dev(p, p->cg_x, p->io_x)) return 1;
-        if (const int rc = callback_iterate(p, callback, user, it + 1, grad_norm, p->io_x, hx)) {
+        if ((it + 1) % check != 0 && it + 1 != max_iter) continue;
+        if (s.trace(p, s, grad_norm, it + 1) || (callback && s.to_caller(p, s))) return 1;
+        if (const int rc = callback_iterate(p, callback, user, it + 1, grad_norm, s.xc, hx)) {
             if (rc == CB_STOP) break;
             return 1;
         }
-        if (std::sqrt(grad_norm[it + 1]) < (double)n * tol) break;
+        const double *gn = grad_norm + (size_t)(it + 1) * s.rows;
+        if (std::sqrt(*std::max_element(gn, gn + s.rows)) < (double)s.n * tol) break;
     }
-    if (surfh_cg_trace(p, grad_norm, *nit + 1) != *nit + 1) return fail("CG trace read failed");
-    if (surfh_from_spec_dev(p, p->cg_x, p->io_x)) return 1;
-    HIP_OK(hipMemcpyAsync(x, p->io_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
+    if (s.to_caller(p, s)) return 1;
+    HIP_OK(hipMemcpyAsync(x, s.xc, p->isize * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
     return 0;
 }
 }  // namespace
@@ -267,51 +454,13 @@ int surfh_cg_cb(surfh_plan *p, const float *y, double mu, double mu_reg, const f
     if (p->T <= 0) return fail("surfh_cg needs templates (the priors act on abundance maps)");
     HIP_OK(hipSetDevice(p->dev));
     if (ensure_cg(p)) return 1;
-    {   // SURFH_SPECTRAL_CG=0, or an imager term (not diagonal in that basis): vectors are the maps (the loop below)
-        if (env_on("SURFH_SPECTRAL_CG", true) && !imager_active(p) && surfh_spec_supported(p) && max_iter < (1 << 16) - 1)
-            return cg_spectral(p, y, mu, mu_reg, x0, max_iter, tol, refresh, x, grad_norm, nit, callback, user);
-    }
-    std::vector<float> hx;             // host copy of the iterate handed to the callback
-    hipStream_t s = p->stream;
-    const long n = p->isize;
-    double *rr = p->dscal + 0, *dq = p->dscal + 1, *rrn = p->dscal + 2;
-    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
-    if (x0)
-        HIP_OK(hipMemcpyAsync(p->cg_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
-    else
-        LAUNCH_OK(launch_fill_zero(s, p->cg_x, n));
-    if (solver_setup(p, p->io_y, p->cg_x, mu, mu_reg)) return 1;
-    HIP_OK(hipMemcpyAsync(p->cg_d, p->cg_r, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    LAUNCH_OK(launch_dot(s, p->cg_r, p->cg_r, n, p->dscratch, rr));
-    HIP_OK(hipMemcpyAsync(&grad_norm[0], rr, sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    *nit = 0;
-    for (int it = 0; it < max_iter; ++it) {
-        if (normal_prior(p, p->cg_d, p->cg_q, mu, mu_reg)) return 1;
-        LAUNCH_OK(launch_dot(s, p->cg_d, p->cg_q, n, p->dscratch, dq));
-        if (refresh > 0 && it % refresh == 0) {
-            LAUNCH_OK(launch_cg_xupdate(s, p->cg_x, p->cg_d, n, rr, dq));
-            if (normal_prior(p, p->cg_x, p->cg_q, mu, mu_reg)) return 1;
-            LAUNCH_OK(launch_residual(s, p->cg_r, p->cg_b, p->cg_q, n));
-            LAUNCH_OK(launch_dot(s, p->cg_r, p->cg_r, n, p->dscratch, rrn));
-        } else {
-            Prof pr(p, "cg_step");
-            LAUNCH_OK(launch_cg_step(s, p->cg_x, p->cg_r, p->cg_d, p->cg_q, n, rr, dq, p->dscratch, rrn));
-        }
-        LAUNCH_OK(launch_cg_dir(s, p->cg_d, p->cg_r, n, rrn, rr));
-        HIP_OK(hipMemcpyAsync(rr, rrn, sizeof(double), hipMemcpyDeviceToDevice, s));
-        HIP_OK(hipMemcpyAsync(&grad_norm[it + 1], rrn, sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_OK(hipStreamSynchronize(s));
-        *nit = it + 1;
-        if (const int rc = callback_iterate(p, callback, user, it + 1, grad_norm, p->cg_x, hx)) {
-            if (rc == CB_STOP) break;
-            return 1;
-        }
-        if (std::sqrt(grad_norm[it + 1]) < (double)n * tol) break;
-    }
-    HIP_OK(hipMemcpyAsync(x, p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    return 0;
+    // SURFH_SPECTRAL_CG=0, or an imager term (not diagonal in that basis): the vectors are the maps
+    const bool spectral = env_on("SURFH_SPECTRAL_CG", true) && !imager_active(p) && surfh_spec_supported(p) && max_iter < (1 << 16) - 1;
+    const CgSpace s = spectral ? spectral_space(p, mu, mu_reg) : maps_space(p, mu, mu_reg);
+    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    if (spectral && x0) HIP_OK(hipMemcpyAsync(s.xc, x0, p->isize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    if ((!spectral && start_iterate(p, x0)) || cg_start(p, s, p->io_y, x0 ? s.xc : nullptr)) return 1;
+    return cg_loop(p, s, max_iter, tol, refresh, spectral ? CG_CHECK : 1, x, grad_norm, nit, callback, user);
 }
 
 int surfh_cg(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
@@ -711,71 +860,14 @@ int surfh_robust_curv_dev(surfh_plan *p, const float *y_dev, const float *u_dev,
 }
 
 // ---- CG on independent planes: the 2-D deconvolution path (criterion_2D.py:60-250 per image, batched over wavelength)
-namespace {
-// one iteration of qmm.lcg on every plane at once, on the plan's cg_d / cg_q / cg_r / cg_b and the iterate x; rr, dq, rrn are
-// [L] device scalars, rr = r.r per plane on entry and on return.  The residual is recomputed from scratch when refresh divides it.
-int cg_planes_iter(surfh_plan *p, float *x, double mu, double mu_reg, int it, int refresh, double *rr, double *dq, double *rrn) {
-    hipStream_t s = p->stream;
-    const int L = p->Lc;
-    const long npix = (long)p->Na * p->Nb;
-    if (normal_prior(p, p->cg_d, p->cg_q, mu, mu_reg)) return 1;
-    LAUNCH_OK(launch_dot_planes(s, p->cg_d, p->cg_q, L, npix, dq));
-    if (refresh > 0 && it % refresh == 0) {
-        LAUNCH_OK(launch_cg_step_planes(s, x, p->cg_r, p->cg_d, p->cg_q, L, npix, rr, dq, rrn, 0));
-        if (normal_prior(p, x, p->cg_q, mu, mu_reg)) return 1;
-        LAUNCH_OK(launch_residual(s, p->cg_r, p->cg_b, p->cg_q, p->isize));
-        LAUNCH_OK(launch_dot_planes(s, p->cg_r, p->cg_r, L, npix, rrn));
-    } else {
-        LAUNCH_OK(launch_cg_step_planes(s, x, p->cg_r, p->cg_d, p->cg_q, L, npix, rr, dq, rrn, 1));
-    }
-    LAUNCH_OK(launch_cg_dir_planes(s, p->cg_d, p->cg_r, L, npix, rrn, rr));      // also rr = rr'
-    return 0;
-}
-}  // namespace
-
 int surfh_cg_planes_cb(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
                        int32_t refresh, float *x, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
-    if (imager_refuse(p, "surfh_cg_planes")) return 1;
-    if (p->T != 0) return fail("surfh_cg_planes is the solver of the plane-wise (no template) model; use surfh_cg with templates");
-    if (p->ch.empty()) return fail("plan has no channel");
-    HIP_OK(hipSetDevice(p->dev));
-    if (ensure_cg(p)) return 1;
-    hipStream_t s = p->stream;
-    const int L = p->Lc;
-    const long npix = (long)p->Na * p->Nb, n = p->isize;
-    if (!p->pl_sc && dev_alloc(&p->pl_sc, (size_t)3 * L)) return 1;
-    double *rr = p->pl_sc, *dq = p->pl_sc + L, *rrn = p->pl_sc + 2 * L;
-    std::vector<float> hx;             // host copy of the iterate handed to the callback
-    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
-    if (x0)
-        HIP_OK(hipMemcpyAsync(p->cg_x, x0, n * sizeof(float), hipMemcpyHostToDevice, s));
-    else
-        LAUNCH_OK(launch_fill_zero(s, p->cg_x, n));
-    if (solver_setup(p, p->io_y, p->cg_x, mu, mu_reg)) return 1;
-    HIP_OK(hipMemcpyAsync(p->cg_d, p->cg_r, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    LAUNCH_OK(launch_dot_planes(s, p->cg_r, p->cg_r, L, npix, rr));
-    HIP_OK(hipMemcpyAsync(grad_norm, rr, L * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    *nit = 0;
-    for (int it = 0; it < max_iter; ++it) {
-        if (cg_planes_iter(p, p->cg_x, mu, mu_reg, it, refresh, rr, dq, rrn)) return 1;
-        double *gn = grad_norm + (size_t)(it + 1) * L;
-        HIP_OK(hipMemcpyAsync(gn, rr, L * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_OK(hipStreamSynchronize(s));
-        *nit = it + 1;
-        // qmm.lcg's per-iteration callback (criterion_2D.py:163-225): trace so far [it + 2][L], current iterate
-        if (const int rc = callback_iterate(p, callback, user, it + 1, grad_norm, p->cg_x, hx)) {
-            if (rc == CB_STOP) break;
-            return 1;
-        }
-        double worst = 0.0;
-        for (int l = 0; l < L; ++l) worst = std::max(worst, gn[l]);
-        if (std::sqrt(worst) < (double)npix * tol) break;
-    }
-    HIP_OK(hipMemcpyAsync(x, p->cg_x, n * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    return 0;
+    if (cg_planes_ready(p, "surfh_cg_planes", false)) return 1;
+    const CgSpace s = planes_space(p, p->cg_x, mu, mu_reg);
+    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    if (start_iterate(p, x0) || cg_start(p, s, p->io_y, s.xc)) return 1;
+    return cg_loop(p, s, max_iter, tol, refresh, 1, x, grad_norm, nit, callback, user);
 }
 
 int surfh_cg_planes(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
@@ -783,123 +875,29 @@ int surfh_cg_planes(surfh_plan *p, const float *y, double mu, double mu_reg, con
     return surfh_cg_planes_cb(p, y, mu, mu_reg, x0, max_iter, tol, refresh, x, grad_norm, nit, nullptr, nullptr);
 }
 
-// ---- the same loop with the data and the iterate resident on the device and no host synchronisation inside: begin (b = mu A^T y,
-// r = b - Q x, d = r), any number of step calls, r.r per plane on request.  x_dev stays the caller's buffer and holds the iterate.
-namespace {
-struct PnScope {                       // forward_dev / adjoint_dev read and write wavelength-innermost vectors for the duration of a call
-    surfh_plan *p;
-    explicit PnScope(surfh_plan *pl) : p(pl) { p->pn_native = true; }
-    ~PnScope() { p->pn_native = false; }
-};
-// q = mu A^T A v (+ mu_reg prior, fused with the dot product v . q -> dq) on wavelength-innermost vectors
-int pn_normal(surfh_plan *p, const float *v, float *q, double *dq) {
-    PnScope sc(p);
-    // with interleaved spectra and a prior weight the OTF product of the adjoint applies mu and adds the prior (adjoint_tail): the
-    // two halves are called directly so that no scaling pass follows
-    // (plans whose inverse transform forms the OTF product in its loader -- prod_capable -- take mu and the prior on that pass)
-    const bool prod = prod_capable(p) && p->pl_mu != 0.0;
-    const bool fold = prod || (p->ilv && !p->dense_dft && p->pl_mu_reg != 0.0);
-    if (fold) {
-        p->pn_fold_prior = true;
-        const int rc = normal_halves(p, v, q);
-        p->pn_fold_prior = false;
-        if (rc) return 1;
-    } else if (normal_dev(p, v, q, p->pl_mu)) {
-        return 1;
-    }
-    Prof pr(p, "pn_prior_dot");
-    if (fold) LAUNCH_OK(launch_pn_dot(p->stream, v, q, p->Na, p->Nb, p->NAP, p->LP, p->pn_part, dq));
-    else LAUNCH_OK(launch_pn_prior_dot(p->stream, v, q, p->Na, p->Nb, p->NAP, p->LP, (float)p->pl_mu_reg, p->pn_part, dq));
-    return 0;
-}
-bool pn_capable(const surfh_plan *p) {
-    const bool on = env_on("SURFH_PLANES_NATIVE", true);       // 0: vectors in the caller's [Lc][Na][Nb] layout (two transposes per operator application)
-    return on && p->T == 0 && p->segs.size() == 1 && p->segs[0].coff == 0 && p->segs[0].start == 0 && p->Lown == p->Lc && p->prior_kind == 0 &&
-           p->LP % 64 == 0;
-}
-}  // namespace
-
+// ---- the same iterations with the data and the iterate resident on the device and no host synchronisation inside: begin (cg_start),
+// any number of step calls, r.r per plane on request.  x_dev stays the caller's buffer and holds the iterate.
 int surfh_cg_planes_begin_dev(surfh_plan *p, const float *y_dev, double mu, double mu_reg, float *x_dev) {
     if (!p || !y_dev || !x_dev) return fail("null argument");
-    if (imager_refuse(p, "surfh_cg_planes_begin_dev")) return 1;
-    if (p->T != 0) return fail("surfh_cg_planes is the solver of the plane-wise (no template) model; use surfh_cg with templates");
-    if (p->ch.empty()) return fail("plan has no channel");
-    HIP_OK(hipSetDevice(p->dev));
-    hipStream_t s = p->stream;
-    const int L = p->Lc;
-    p->pn_active = pn_capable(p);
-    if (p->pn_active) {
-        // vectors in the cube's layout: the caller's x is transposed in here and out again at the end of every step call
-        const size_t nc = (size_t)p->NBP * p->NAP * p->LP;
-        for (float *&v : p->pn_v)
-            if (!v) {
-                if (dev_alloc(&v, nc)) return 1;
-                HIP_OK(hipMemsetAsync(v, 0, nc * sizeof(float), s));       // the padding (rows >= Nb, columns >= Na, planes >= Lc) stays zero
-            }
-        if (!p->pn_sc && (dev_alloc(&p->pn_sc, (size_t)3 * p->LP) || dev_alloc(&p->pn_part, pn_part_doubles(p->LP)))) return 1;
-        float *xn = p->pn_v[0], *r = p->pn_v[1], *d = p->pn_v[2], *q = p->pn_v[3], *b = p->pn_v[4];
-        double *rr = p->pn_sc, *dq = p->pn_sc + p->LP;
-        p->pl_x = x_dev; p->pl_mu = mu; p->pl_mu_reg = mu_reg; p->pl_it = 0;
-        LAUNCH_OK(launch_cube_to_lam_inner(s, x_dev, xn, 0, L, p->Na, p->Nb, p->NAP, p->LP));
-        {
-            const float *wy = weighted_data(p, y_dev);
-            PnScope sc(p);
-            if (!wy || adjoint_dev(p, wy, b, false)) return 1;
-        }
-        if (mu != 1.0) LAUNCH_OK(launch_scale(s, b, (long)nc, (float)mu));
-        if (pn_normal(p, xn, q, dq)) return 1;
-        LAUNCH_OK(launch_residual(s, r, b, q, (long)nc));
-        HIP_OK(hipMemcpyAsync(d, r, nc * sizeof(float), hipMemcpyDeviceToDevice, s));
-        LAUNCH_OK(launch_pn_dot(s, r, r, p->Na, p->Nb, p->NAP, p->LP, p->pn_part, rr));
-        return 0;
-    }
-    if (ensure_cg(p)) return 1;
-    if (!p->pl_sc && dev_alloc(&p->pl_sc, (size_t)3 * L)) return 1;
+    const bool native = pn_capable(p);
+    if (cg_planes_ready(p, "surfh_cg_planes_begin_dev", native)) return 1;
+    p->pn_active = native;
     p->pl_x = x_dev; p->pl_mu = mu; p->pl_mu_reg = mu_reg; p->pl_it = 0;
-    if (solver_setup(p, y_dev, x_dev, mu, mu_reg)) return 1;
-    HIP_OK(hipMemcpyAsync(p->cg_d, p->cg_r, p->isize * sizeof(float), hipMemcpyDeviceToDevice, s));
-    LAUNCH_OK(launch_dot_planes(s, p->cg_r, p->cg_r, L, (long)p->Na * p->Nb, p->pl_sc));
-    return 0;
+    return cg_start(p, stored_space(p), y_dev, x_dev);
 }
 int surfh_cg_planes_step_dev(surfh_plan *p, int32_t iters, int32_t refresh) {
     if (!p || !p->pl_x || !(p->pn_active ? (void *)p->pn_sc : (void *)p->pl_sc)) return fail("surfh_cg_planes_begin_dev has not been called");
     HIP_OK(hipSetDevice(p->dev));
-    hipStream_t s = p->stream;
-    const int L = p->Lc;
-    if (p->pn_active) {
-        float *xn = p->pn_v[0], *r = p->pn_v[1], *d = p->pn_v[2], *q = p->pn_v[3], *b = p->pn_v[4];
-        double *rr = p->pn_sc, *dq = p->pn_sc + p->LP, *rrn = p->pn_sc + 2 * p->LP;
-        const long nc = (long)p->NBP * p->NAP * p->LP;
-        for (int i = 0; i < iters; ++i, ++p->pl_it) {
-            if (pn_normal(p, d, q, dq)) return 1;
-            if (refresh > 0 && p->pl_it % refresh == 0) {
-                LAUNCH_OK(launch_pn_step(s, xn, r, d, q, p->Na, p->Nb, p->NAP, p->LP, rr, dq, p->pn_part, rrn, 0));
-                if (pn_normal(p, xn, q, dq)) return 1;
-                LAUNCH_OK(launch_residual(s, r, b, q, nc));
-                LAUNCH_OK(launch_pn_dot(s, r, r, p->Na, p->Nb, p->NAP, p->LP, p->pn_part, rrn));
-            } else {
-                Prof pr(p, "pn_step");
-                LAUNCH_OK(launch_pn_step(s, xn, r, d, q, p->Na, p->Nb, p->NAP, p->LP, rr, dq, p->pn_part, rrn, 1));
-            }
-            {
-                Prof pr(p, "pn_dir");
-                LAUNCH_OK(launch_pn_dir(s, d, r, p->Na, p->Nb, p->NAP, p->LP, rrn, rr));
-            }
-            HIP_OK(hipMemcpyAsync(rr, rrn, (size_t)p->LP * sizeof(double), hipMemcpyDeviceToDevice, s));
-        }
-        LAUNCH_OK(launch_cube_from_lam_inner(s, xn, p->pl_x, 0, L, p->Na, p->Nb, p->NAP, p->LP));      // the caller's iterate
-        return 0;
-    }
+    const CgSpace s = stored_space(p);
     for (int i = 0; i < iters; ++i, ++p->pl_it)
-        if (cg_planes_iter(p, p->pl_x, p->pl_mu, p->pl_mu_reg, p->pl_it, refresh, p->pl_sc, p->pl_sc + L, p->pl_sc + 2 * L)) return 1;
-    return 0;
+        if (cg_iteration(p, s, p->pl_it, refresh)) return 1;
+    return s.to_caller(p, s);                                              // the caller's iterate
 }
 int surfh_cg_planes_rr(surfh_plan *p, double *rr_host) {
     if (!p || !rr_host || !p->pl_x || !(p->pn_active ? p->pn_sc : p->pl_sc)) return fail("surfh_cg_planes_begin_dev has not been called");
     HIP_OK(hipSetDevice(p->dev));
-    HIP_OK(hipMemcpyAsync(rr_host, p->pn_active ? p->pn_sc : p->pl_sc, (size_t)p->Lc * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-    HIP_OK(hipStreamSynchronize(p->stream));
-    return 0;
+    const CgSpace s = stored_space(p);
+    return s.trace(p, s, rr_host, 0);
 }
 
 // ---- 3MG on independent planes: every plane's beta, 2x2 system and step on the device, so the host reads one thing per

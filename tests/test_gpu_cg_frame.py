@@ -1,5 +1,5 @@
-"""The contract of the CG loops of the library (plan_solvers.hip: surfh_cg_cb on the maps, cg_spectral on their scaled half spectra,
-surfh_cg_planes_cb plane by plane) and of ``DistributedFusion.lcg``, the spectral loop driven from Python, on the smallest problem the
+"""The contract of the CG loop of the library (plan_solvers.hip: cg_loop, which surfh_cg_cb runs on the maps or on their scaled half
+spectra and surfh_cg_planes_cb plane by plane) and of ``DistributedFusion.lcg``, the spectral loop driven from Python, on the smallest problem the
 suite has for each: what max_iter = 0 returns, what the callback sees, where a callback's stop and the tolerance stop leave the
 iterate, that a run is a prefix of every longer run on either side of a CG_CHECK boundary, and that a residual which is exactly
 zero keeps the iterate still.  Warm starts and residual refreshes are compared with the float64 oracle (needs an MI355X).
