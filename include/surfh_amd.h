@@ -27,7 +27,7 @@
  *   - environment switches read at plan creation (A/B paths, parity-tested where they engage): SURFH_DFT_H2=0 (axes
  *     <= 255 on the Cooley-Tukey kernel too), SURFH_DFT_CT=0, SURFH_DFT_DENSE=1, SURFH_NO_FUSED_MIX=1, SURFH_WBLUR_FP32=1,
  *     SURFH_WBLUR_FAR=0, SURFH_WBLUR_PERM=0, SURFH_GEMM_GROUPED=0, SURFH_ADJ_FUSED=0 (separate adjoint reduction kernel),
- *     SURFH_OTF_SUPPORT=0, SURFH_OTF_RANGES=0, SURFH_ALPHA_RANGE=0 (transform the whole cube), SURFH_GATHER_SORTED=0,
+ *     SURFH_OTF_SUPPORT=0, SURFH_OTF_RANGES=0, SURFH_ALPHA_RANGE=0 (transform the whole cube), SURFH_LAMBDA_TRIM=0 (... and every padded plane), SURFH_GATHER_SORTED=0,
  *     SURFH_GATHER_GROUPED=0, SURFH_SCATTER_GROUPED=0, SURFH_SCATTER_RMW_ALL=1, SURFH_ADJ_CLEAR=1, SURFH_OVERLAP=1,
  *     SURFH_PLANES_NATIVE=0, SURFH_OTF_PROD=0 (plane-wise model: the OTF products as kernels of their own); surfh_config.exact switches the far class / the support lists off per plan; read per call:
  *     SURFH_SPECTRAL_CG=0 (solver vectors = maps); read once per process: SURFH_NORMAL_FUSED=0 (the normal operator
@@ -464,6 +464,9 @@ int surfh_gemm_selftest(int32_t device, int32_t M, int32_t N, int32_t K, int32_t
 /* (tile, K step) pairs the last two-piece fp16 self-test (SURFH_SELFTEST_F16X2=2: with K-step lists, as the spectral-blur
  * GEMMs of a plan) ran with all three products / with the leading product only */
 int surfh_gemm_selftest_ksteps(int64_t near_far[2]);
+/* mean milliseconds per launch of the last two-piece fp16 self-test run with SURFH_SELFTEST_REPEAT=<n> (n timed launches behind
+ * three warm-up ones, device events); -1 when the last self-test did not repeat its launch */
+int surfh_gemm_selftest_ms(double *ms);
 /* host only (no GPU): the K-step classes the spectral-blur GEMMs of a plan would use for the constant operand B [n][ldb]
  * (k columns, k % 32 == 0): records[(tile) * (2 + k / 32)] = n_near, n_far, near steps ascending, far steps ascending
  * (entry = step | segment << 16).  perm_p / perm_lin: the adjoint's tile shape (0: tiles of 256 consecutive rows).

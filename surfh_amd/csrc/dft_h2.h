@@ -44,7 +44,11 @@ struct DftH2Args {
     float e_alt[4] = {1.f, 0.f, 0.f, 1.f};
     int Rn = 0, rvalid = 0;                    // output rows r < rvalid (and their mirrors Rn - r where they exist)
     int KP = 0;                                // K padded to 16 (columns of the image in use)
-    int N = 0, batch = 1;                      // columns per batch entry (complex columns for kind 0; % 128 == 0)
+    int N = 0, batch = 1;                      // columns per batch entry (complex columns for kind 0); % 32 (% 128 with mhat, vlist or Nv)
+    // optional (kind 0 with N % 128 == 0; not the fused tail): of every NvP consecutive columns (NvP % 128 == 0, N % NvP == 0)
+    // only the first Nv (% 16, > NvP - 128) hold data, the others are zero padding nobody reads: the wave tiles that lie wholly
+    // in the padding run two k-steps and store nothing; every other tile keeps its bits.
+    int Nv = 0, NvP = 0;
     const float *mhat = nullptr, *tpl = nullptr;   // optional fused spectral mix (kind 0)
     int T = 0, LP = 0;
     long PL = 0, KBP = 0;

@@ -264,9 +264,16 @@ __global__ __launch_bounds__(NTHREADS) void dft_h2_kernel(DftH2Args g, const uin
         const bool more = vt + NWAVES < vtend;
         const int next = more ? H2_RT(vt + NWAVES) : tile;
         // per-tile limits (wave-uniform): k-steps that can be non-zero, output rows that anybody reads
-        const int chunk_ = g.tabLP ? (int)(((long)(tile % tilesX) * TNW % g.tabLP) >> 7) : 0;
-        const int nkt = g.ktab ? g.ktab[chunk_] : nk;
-        const int mtn = g.rtab ? (g.rtab[chunk_] + 31) / 32 : 4;       // row tiles of 32 that anybody reads
+        // first column of the tile inside its block of tabLP (= NvP, launcher) columns: the tile's chunk of 128, and whether it
+        // lies wholly in the padding (DftH2Args::Nv)
+        const int per_ = g.tabLP ? g.tabLP : g.NvP;
+        const int colp_ = per_ ? (int)((long)(tile % tilesX) * TNW % per_) : 0;
+        const int chunk_ = colp_ >> 7;
+        // a tile of padding (zeros in, nobody reads what would come out) keeps its place in the wave's stream of k-steps -- every
+        // wave of the workgroup meets every change of k_beta -- but runs the two k-steps already requested and stores nothing
+        const bool pad_ = KIND == 0 && g.Nv && colp_ >= g.Nv;
+        const int nkt = pad_ ? 2 : (g.ktab ? g.ktab[chunk_] : nk);
+        const int mtn = pad_ ? 0 : (g.rtab ? (g.rtab[chunk_] + 31) / 32 : 4);       // row tiles of 32 that anybody reads
         for (int kt = 0; kt + 1 < nkt; ++kt) {
             H2_MFMA(0, kt, acc1, c0h, c0l);
             H2_FOLD(kt + 1);           // raw holds k-step kt + 1 of this tile
@@ -742,7 +749,12 @@ int dft_h2_build_image(const float *A0, const float *A1, int MP, int KP, int lda
 }
 
 int launch_dft_h2(hipStream_t stream, const DftH2Args &g, const unsigned short *img, int kA) {
-    if (g.kind < 0 || g.kind > 2 || g.KP % BK || g.KP < 2 * BK || g.KP > KT * BK || g.N % 128 || g.batch < 1 || !img || !g.src || !g.dst)
+    if (g.kind < 0 || g.kind > 2 || g.KP % BK || g.KP < 2 * BK || g.KP > KT * BK || g.N < 32 || g.N % 32 || g.batch < 1 || !img || !g.src || !g.dst)
+        return (int)hipErrorInvalidValue;
+    // whole super-tiles of 128 columns: the fused mix (one k_beta per super-tile), a list of super-tiles, padding inside the axis
+    if ((g.mhat || g.vlist || g.Nv) && g.N % 128) return (int)hipErrorInvalidValue;
+    if (g.Nv && g.tabLP && g.tabLP != g.NvP) return (int)hipErrorInvalidValue;
+    if (g.Nv && (g.kind != 0 || g.NvP < 128 || g.NvP % 128 || g.N % g.NvP || g.Nv % 16 || g.Nv <= g.NvP - 128 || g.Nv >= g.NvP))
         return (int)hipErrorInvalidValue;
     if (g.kind != 2 && g.KP > g.Kn) return (int)hipErrorInvalidValue;
     if (g.rvalid < 1 || g.rvalid > 128) return (int)hipErrorInvalidValue;
@@ -822,6 +834,7 @@ int launch_dft_h2_adjmix(hipStream_t stream, const DftH2Args &g, const DftH2AdjM
         return (int)hipErrorInvalidValue;
     adjmix_geometry(cus, g.N / 16, g.batch, am0.vlist ? am0.nvalid : 0, NS, G, nslot);
     if (NS >= 2147483647L / 8 || g.N % 128) return (int)hipErrorInvalidValue;
+    if (g.Nv) return (int)hipErrorInvalidValue;                // the fused tail knows no padding inside the axis
     DftH2AdjMix am = am0;
     am.nslot = nslot;
     static unsigned long long d4 = 0;

@@ -740,6 +740,8 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
             for (int l = 0; l < g.len; ++l) p->planes[g.coff + l] = g.start + l;
     }
     p->LP = (p->Lown + 127) / 128 * 128;
+    // the passes of the fused forward / adjoint run over the planes that exist, in whole wave tiles (read at plan creation; 0: over LP)
+    p->Leff = env_on("SURFH_LAMBDA_TRIM", true) ? std::min(p->LP, (p->Lown + 31) / 32 * 32) : p->LP;
     p->isize = (long)(p->T > 0 ? p->T : p->Lc) * p->Na * p->Nb;
     const size_t LP = (size_t)p->LP;
 

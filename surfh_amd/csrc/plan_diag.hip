@@ -81,6 +81,8 @@ static int resolve(surfh_plan *p, const char *which, const float **ptr, int64_t 
     } else if (w == "groups") {        // workgroups of the grouped gather / grouped scatter tables, all channels (0: row by row)
         dims[0] = dims[1] = 0;
         for (auto &c : p->ch) { dims[0] += c.fwd.g.NG; dims[1] += c.adjT.g.NG; }
+    } else if (w == "trim") {          // planes the fused transform passes run over, the plane pitch, owned planes
+        dims[0] = p->Leff; dims[1] = p->LP; dims[2] = p->Lown;
     } else if (w == "info") {
         dims[0] = p->lo; dims[1] = p->hi; dims[2] = p->Lown; dims[3] = (int64_t)p->segs.size();
     } else {
@@ -134,6 +136,15 @@ int surfh_mm_step2(double dBd, double dBm, double mBm, double dg, double mg, dou
 static long g_selftest_ksteps[2] = {0, 0};
 int surfh_gemm_selftest_ksteps(int64_t near_far[2]) {
     near_far[0] = g_selftest_ksteps[0]; near_far[1] = g_selftest_ksteps[1];
+    return 0;
+}
+
+// SURFH_SELFTEST_REPEAT=<n>: the two-piece fp16 launch of the self-test is repeated n times behind three warm-up launches,
+// bracketed by device events; mean milliseconds per launch of the last such call (-1: none)
+static double g_selftest_ms = -1.0;
+int surfh_gemm_selftest_ms(double *ms) {
+    if (!ms) return fail("null argument");
+    *ms = g_selftest_ms;
     return 0;
 }
 
@@ -192,6 +203,24 @@ int surfh_gemm_selftest(int32_t device, int32_t M, int32_t N, int32_t K, int32_t
         }
         if (rc == 0) rc = launch_gemm_nt_f16x2_cc(nullptr, g);
         if (rc == 0) rc = (int)hipDeviceSynchronize();
+        g_selftest_ms = -1.0;
+        const char *er = getenv("SURFH_SELFTEST_REPEAT");
+        const int nrep = er ? atoi(er) : 0;
+        if (rc == 0 && nrep > 0) {
+            hipEvent_t ea, eb;
+            HIP_OK(hipEventCreate(&ea));
+            HIP_OK(hipEventCreate(&eb));
+            for (int i = 0; i < 3 && rc == 0; ++i) rc = launch_gemm_nt_f16x2_cc(nullptr, g);
+            hipEventRecord(ea, nullptr);
+            for (int i = 0; i < nrep && rc == 0; ++i) rc = launch_gemm_nt_f16x2_cc(nullptr, g);
+            hipEventRecord(eb, nullptr);
+            if (rc == 0) rc = (int)hipEventSynchronize(eb);
+            float ms = 0.f;
+            if (rc == 0) rc = (int)hipEventElapsedTime(&ms, ea, eb);
+            if (rc == 0) g_selftest_ms = (double)ms / nrep;
+            hipEventDestroy(ea);
+            hipEventDestroy(eb);
+        }
         hipFree(dkl);
         hipFree(dB16);
         hipFree(dmax);

@@ -11,6 +11,11 @@
 //   cube     blurred / g     [NBP (beta)][NAP (alpha)][LP]
 //   operand  Xs (per channel)[NP = (p,s,a)][n_beta_slit][LinP]      K index = (b', lambda)
 // LP = owned planes padded to 128, all other dims padded to 64, padding is zero.
+// Leff = owned planes rounded up to 32 (the widest wave tile of the transform passes), the extent the passes of the
+// fused-mix forward and the adjoint's pass in front of the fused tail are launched over; every stride and allocation stays LP.  The planes [Leff, LP) of ycol, ycol_mix, ycol_adj,
+// cube and gcube are zeroed at plan creation and never written by those passes -- "zero for good", like the columns outside
+// [a_lo, a_hi) of ycol_adj and the tiles outside the OTF's support of ycol_mix.  (The planes [Lown, Leff) are transformed: their
+// sources -- sotf, tpl, what the scatters leave -- are zero, so they come out as zeros.)
 //
 // Pipeline (per plan = per GPU), reference citations relative to the reference's source tree:
 //   forward  (spectroModel.py:158-170, spectroModelChannel.py:215-231)
@@ -142,6 +147,7 @@ struct surfh_plan {
     int Na = 0, Nb = 0, Lc = 0, T = 0, NAP = 0, NBP = 0, KAP = 0, KBP = 0;
     long PL = 0, PLc = 0;
     int lo = 0, hi = 0, Lown = 0, LP = 0;
+    int Leff = 0;                                // planes the trimmed transform passes run over (SURFH_LAMBDA_TRIM=0: LP)
     // owned cube planes = union of the channels' windows, stored compactly: segment = (first plane, length, compact offset)
     struct Seg { int start, len, coff; };
     std::vector<Seg> segs;

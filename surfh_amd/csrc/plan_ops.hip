@@ -128,10 +128,15 @@ int rfft2_lam_h2(surfh_plan *p, const float *src, float *dst, float *madj = null
     const bool sub = acols && p->ycol_adj && p->a_hi > p->a_lo;
     float *const yc = sub ? p->ycol_adj : p->ycol;
     const int a0 = sub ? p->a_lo : 0, na = sub ? p->a_hi - p->a_lo : p->Na;
-    DftH2Args g;   // r2c along beta
-    g.kind = 1; g.src = src + (long)a0 * LP; g.ldb = p->NAP * LP; g.Kn = p->Nb;
-    g.dst = yc + 2 * (long)a0 * LP; g.ldc = 2 * p->NAP * LP; g.e[0] = 1.f; g.e[3] = -1.f; g.rvalid = hb;
-    g.KP = p->KPb; g.N = (int)(na * LP);
+    // in front of the fused tail the pass runs over the planes that exist (Leff, plan_internal.h): the source's planes beyond are
+    // zero and so is their place in the intermediate, for good; the other callers may hand in any vector and get every plane of LP.
+    // The tail itself keeps LP: its workgroups take equal counts of super-tiles and only some ranges hold a padded chunk, so
+    // passing those tiles over (measured) leaves the slowest workgroup, and the launch, where it was.
+    const int Lrun = madj ? p->Leff : (int)LP;
+    DftH2Args g;   // r2c along beta, batched over alpha
+    g.kind = 1; g.src = src + (long)a0 * LP; g.ldb = p->NAP * LP; g.sB = LP; g.Kn = p->Nb;
+    g.dst = yc + 2 * (long)a0 * LP; g.ldc = 2 * p->NAP * LP; g.sC = 2 * LP; g.e[0] = 1.f; g.e[3] = -1.f; g.rvalid = hb;
+    g.KP = p->KPb; g.N = Lrun; g.batch = na;
     // fused tail with the OTF's support: it reads no k_beta beyond the support of a wavelength chunk, so those rows are not stored
     if (madj && p->otf_vlist && p->ycol_mix && p->otf_tabs) { g.rtab = p->otf_tabs + 2 * (LP / 128); g.tabLP = (int)LP; }
     if (which & 1) {
@@ -187,6 +192,11 @@ int irfft2_lam_h2(surfh_plan *p, const float *src, float *dst, bool mix, bool ac
     float *const yc = supp ? p->ycol_mix : p->ycol;
     if (supp) { g.vlist = p->otf_vlist; g.nvalid = p->otf_nvalid; g.dst = yc; }
     if (supp && p->otf_tabs) { g.ktab = p->otf_tabs; g.tabLP = (int)LP; }          // k_alpha beyond the support: not read
+    // the fused forward runs over the planes that exist (Leff, plan_internal.h): sotf and tpl are zero beyond, the gathers read
+    // nothing there.  The complex pass keeps its super-tiles of 128 planes of one k_beta (one mix table per super-tile) and marks
+    // the tiles beyond Leff as padding; the pass along beta is launched over Leff planes.
+    const int Lrun = mix ? p->Leff : (int)LP;
+    if (Lrun < LP) { g.Nv = Lrun; g.NvP = (int)LP; }
     if (which & 2) {
         Prof pr(p, mix ? "dft_h2_cols_inv_mix" : "dft_h2_cols_inv");
         LAUNCH_OK(launch_dft_h2(p->stream, g, p->h2img, p->h2kA[0]));
@@ -198,7 +208,7 @@ int irfft2_lam_h2(surfh_plan *p, const float *src, float *dst, bool mix, bool ac
     h.kind = 2; h.src = yc + (long)a0 * 2 * p->KBP * LP; h.ldb = 2 * LP; h.sB = 2 * p->KBP * LP;
     h.dst = dst + (long)a0 * LP; h.ldc = p->NAP * LP; h.sC = LP;
     h.e[0] = 1.f; h.e[1] = -1.f; h.e[2] = 1.f; h.e[3] = 1.f; h.Rn = p->Nb; h.rvalid = hb;
-    h.KP = p->KPb; h.N = (int)LP; h.batch = na;
+    h.KP = p->KPb; h.N = Lrun; h.batch = na;
     if (supp && p->otf_tabs) { h.ktab = p->otf_tabs + LP / 128; h.tabLP = (int)LP; }   // k_beta beyond the support: zero in ycol_mix
     {
         Prof pr(p, "dft_h2_rows_inv");
