@@ -52,6 +52,8 @@ static int resolve(surfh_plan *p, const char *which, const float **ptr, int64_t 
         else { dims[0] = 2; dims[1] = p->KAP; dims[2] = p->KBP; dims[3] = p->LP; }
     } else if (w == "mhat" && p->T > 0) {
         *ptr = p->mhat; dims[0] = p->T; dims[1] = 2; dims[2] = p->KAP; dims[3] = p->KBP;
+    } else if (w == "hth" && p->T > 0) {            // Model_WCT's Hessian [t][t'][k_alpha][k_beta]; no pointer before its first use
+        *ptr = p->hth; dims[0] = p->T; dims[1] = p->T; dims[2] = p->KAP; dims[3] = p->KBP;
     } else if (w == "imager_g" && p->im_g) {        // [(f,t)][2][k_alpha][k_beta]
         *ptr = p->im_g; dims[0] = (int64_t)p->im_F * p->T; dims[1] = 2; dims[2] = p->KAP; dims[3] = p->KBP;
     } else if (w.rfind("xs:", 0) == 0 || w.rfind("xsinfo:", 0) == 0) {
@@ -81,7 +83,9 @@ static int resolve(surfh_plan *p, const char *which, const float **ptr, int64_t 
     } else if (w == "groups") {        // workgroups of the grouped gather / grouped scatter tables, all channels (0: row by row)
         dims[0] = dims[1] = 0;
         for (auto &c : p->ch) { dims[0] += c.fwd.g.NG; dims[1] += c.adjT.g.NG; }
-    } else if (w == "trim") {          // planes the fused transform passes run over, the plane pitch, owned planes
+    } else if (w == "dft") {           // kernel of each transform axis (0: dense, 1: dft_h2, 2: dft_ct), interleaved arrays, fused adjoint tail
+        dims[0] = p->ax_a; dims[1] = p->ax_b; dims[2] = p->ilv ? 1 : 0; dims[3] = p->adjmix_part ? 1 : 0;
+    } else if (w == "trim") {         // planes the fused transform passes run over, the plane pitch, owned planes
         dims[0] = p->Leff; dims[1] = p->LP; dims[2] = p->Lown;
     } else if (w == "info") {
         dims[0] = p->lo; dims[1] = p->hi; dims[2] = p->Lown; dims[3] = (int64_t)p->segs.size();

@@ -816,13 +816,54 @@ int surfh_wct_expsol(surfh_plan *p, const float *cube, const double *mu_reg, con
     if (dev_upload(&dreg, reg) || dev_alloc(&dmu, (size_t)p->T) || dev_alloc(&dflag, 1)) return done(1);
     if (hipMemcpy(dmu, mu_reg, p->T * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(dflag, 0, sizeof(int)) != hipSuccess) return done(fail("copy failed"));
-    // b = H^T y in the Fourier domain (surfh_wct_adjoint up to the inverse transform)
-    if (hipMemcpyAsync(p->io_cube, cube, (size_t)p->Lc * p->Na * p->Nb * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess)
+    // b = H^T y in the Fourier domain (surfh_wct_adjoint up to the inverse transform).  The mean of every plane is taken out in
+    // float64 before the fp32 transforms and put back into the zero-frequency bin of b afterwards: left in, its rounding leaks
+    // into the other bins of the k_beta = 0 column, small against the mean but not against the bins themselves, and the solve
+    // amplifies it where hth and mu |D|^2 are both small (a band-limited OTF with a small mu)
+    const size_t npl = (size_t)p->Na * p->Nb;
+    std::vector<float> y0((size_t)p->Lc * npl);
+    std::vector<double> mean((size_t)p->Lc);
+    for (int l = 0; l < p->Lc; ++l) {
+        const float *src = cube + (size_t)l * npl;
+        double sum = 0.0;
+        for (size_t i = 0; i < npl; ++i) sum += src[i];
+        mean[l] = sum / (double)npl;
+        for (size_t i = 0; i < npl; ++i) y0[(size_t)l * npl + i] = (float)((double)src[i] - mean[l]);
+    }
+    std::vector<float> h0((size_t)2 * p->LP);       // the OTF at the zero frequency as the kernels read it: (re, im) of every plane
+    if (p->ilv) {
+        if (hipMemcpy(h0.data(), p->sotf, h0.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return done(fail("copy failed"));
+    } else {
+        std::vector<float> re((size_t)p->LP), im((size_t)p->LP);
+        if (hipMemcpy(re.data(), p->sotf, re.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(im.data(), p->sotf + (size_t)p->PL * p->LP, im.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+            return done(fail("copy failed"));
+        for (long l = 0; l < p->LP; ++l) { h0[2 * l] = re[l]; h0[2 * l + 1] = im[l]; }
+    }
+    std::vector<double> dc((size_t)2 * p->T, 0.0);  // sum_l tpl[t][l] conj(H_l(0)) mean_l sqrt(Na Nb): the transforms are unitary
+    const double dcs = std::sqrt((double)npl);
+    for (int t = 0; t < p->T; ++t)
+        for (int l = 0; l < p->Lc; ++l) {
+            const double w = (double)(float)p->tpl_host[(size_t)t * p->Lc + l] * mean[l] * dcs;
+            dc[2 * t] += w * (double)h0[2 * l];
+            dc[2 * t + 1] -= w * (double)h0[2 * l + 1];
+        }
+    if (hipMemcpyAsync(p->io_cube, y0.data(), y0.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess)
         return done(fail("copy failed"));
     int rc = launch_fill_zero(s, p->cube, (long)p->NBP * p->NAP * p->LP);
     if (!rc) rc = launch_cube_to_lam_inner(s, p->io_cube, p->cube, 0, p->Lc, p->Na, p->Nb, p->NAP, p->LP);
     if (rc) return done(fail("launch failed: %s", hipGetErrorString((hipError_t)rc)));
     if (adjoint_tail(p, p->cube)) return done(1);
+    for (int t = 0; t < p->T; ++t)
+        for (int c = 0; c < 2; ++c) {               // bin (0, 0) of mhat [T][2][KAP][KBP]
+            float *bin = p->mhat + ((size_t)t * 2 + c) * p->PL;
+            float v = 0.f;
+            if (hipMemcpyAsync(&v, bin, sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+                return done(fail("copy failed"));
+            v = (float)((double)v + dc[2 * t + c]);
+            if (hipMemcpyAsync(bin, &v, sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+                return done(fail("copy failed"));
+        }
     rc = launch_wct_solve(s, p->hth, dreg, dmu, p->mhat, p->mhat2, p->T, p->PL, dflag);
     if (rc) return done(fail("launch failed: %s", hipGetErrorString((hipError_t)rc)));
     if (irfft2_planes(p, p->mhat2, p->maps_pad, p->T)) return done(1);

@@ -14,6 +14,14 @@ Contents (arrays only):
 * ``full_*``: the default run ``NMF(4, init="random", random_state=0)``: n_iter, reconstruction_err_, components_, and
   ``full_ratio``, violation / violation_init of every iteration (the stopping test's value);
 * ``sweep_*``: K = 1..6 with random_state=0 and the defaults: reconstruction_err_ and n_iter_.
+
+and tests/golden/templates_edges.npz, the tile edges of the batched GEMMs (templates.hip: 64 components per tile column, K steps
+of 16 wavelengths):
+
+* ``sweep_*``: K = 7..11 on the same ``X``, random_state=0 and the defaults (with K = 1..6 the batch holds 66 components);
+* ``Xr``: a float32 [97, 650] matrix of rank 5 plus noise from ``matrix()``: 650 = 512 + 138 and 138 % 16 = 10;
+* ``r_it<n>_W`` / ``r_it<n>_H`` / ``r_it<n>_err``: ``NMF(5, init="random", random_state=0, tol=0, max_iter=n)`` on ``Xr`` for n in
+  1, 5.
 """
 from __future__ import annotations
 
@@ -29,6 +37,10 @@ from sklearn.decomposition._nmf import _initialize_nmf, _update_coordinate_desce
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, "templates.npz")
+OUT_EDGES = os.path.join(HERE, "templates_edges.npz")
+EDGE_KS = (7, 8, 9, 10, 11)
+RAGGED = dict(n=97, m=650, k=5)
+RAGGED_ITERS = (1, 5)
 MODES = ("reflect", "nearest", "mirror")
 SIZES = (1, 3, 4, 11, 15)
 ITERS = (1, 5, 30)
@@ -139,5 +151,30 @@ def main():
           "sweep n_iter", nits)
 
 
+def edges(X):
+    z = {}
+    errs, nits = [], []
+    for k in EDGE_KS:
+        m = NMF(int(k), init="random", random_state=0)
+        m.fit(X)
+        errs.append(m.reconstruction_err_)
+        nits.append(m.n_iter_)
+    z["sweep_k"], z["sweep_err"], z["sweep_n_iter"] = np.array(EDGE_KS), np.array(errs), np.array(nits, dtype=np.int32)
+    Xr = matrix(np.random.default_rng(20261019), **RAGGED)
+    z["Xr"] = Xr
+    for n in RAGGED_ITERS:
+        m = NMF(RAGGED["k"], init="random", random_state=0, tol=0.0, max_iter=n)
+        W = m.fit_transform(Xr)
+        z[f"r_it{n}_W"], z[f"r_it{n}_H"], z[f"r_it{n}_err"] = W, m.components_, np.float64(m.reconstruction_err_)
+    z["meta"] = np.array(json.dumps({"scipy": scipy.__version__, "sklearn": sklearn.__version__}))
+    np.savez_compressed(OUT_EDGES, **z)
+    print(OUT_EDGES, os.path.getsize(OUT_EDGES), "bytes; sweep n_iter", nits)
+
+
 if __name__ == "__main__":
-    main()
+    import sys
+    if "--edges" in sys.argv:          # the tile-edge vectors alone, on the X of the existing file
+        edges(np.load(OUT)["X"])
+    else:
+        main()
+        edges(np.load(OUT)["X"])

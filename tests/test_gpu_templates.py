@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "templates.npz")
+GOLDEN_EDGES = os.path.join(ROOT, "tests", "golden", "templates_edges.npz")
 
 
 @pytest.fixture(scope="module")
@@ -105,6 +106,54 @@ def test_sweep_is_batch_independent_and_deterministic(z):
         R = X.astype(np.float64) - m._W.astype(np.float64) @ m.components_.astype(np.float64)
         ref = np.mean(np.divide(R, X, out=np.zeros_like(R), where=X != 0))
         assert abs(mre - ref) <= 1e-6 * max(1.0, abs(ref))
+
+
+def test_sweep_across_a_tile_column_is_batch_independent(z):
+    """K = 1..11 holds 66 components: the GEMMs (k_gemm_nt, k_gemm_tn) run a second tile column of 64 and the K = 11 model
+    straddles it (components 55..65).  Every model equals its single-model run bit for bit, as templates.hip promises."""
+    X = z["X"]
+    ks = range(1, 12)
+    assert sum(ks) == 66 and sum(range(1, 11)) < 64 < sum(ks)
+    models, info = T.nmf_sweep(X, ks, random_state=0, max_iter=30, tol=0.0)
+    for k, m, err, nit in zip(ks, models, info["error"], info["n_iter"]):
+        one = T.NMF(k, init="random", random_state=0, max_iter=30, tol=0.0)
+        W = one.fit_transform(X)
+        assert one.n_iter_ == m.n_iter_ == nit == 30, k
+        assert np.array_equal(W, m._W) and np.array_equal(one.components_, m.components_), k
+        assert one.reconstruction_err_ == m.reconstruction_err_ == err, k
+
+
+def test_sweep_across_a_tile_column_matches_sklearn(z):
+    """The default sweep with 66 components in the batch against sklearn's errors: K = 1..6 of templates.npz and K = 7..11 of
+    templates_edges.npz, at the rtol of test_sweep_is_batch_independent_and_deterministic."""
+    from test_gpu_parity import note
+    ze = np.load(GOLDEN_EDGES)
+    ref = np.concatenate([z["sweep_err"], ze["sweep_err"]])
+    assert list(z["sweep_k"]) + list(ze["sweep_k"]) == list(range(1, 12))
+    _, info = T.nmf_sweep(z["X"], range(1, 12), random_state=0, max_iter=200, tol=1e-4)
+    e = np.abs(info["error"] - ref) / ref
+    note("nmf_sweep_66_components", worst=float(e.max()), at_k=int(np.argmax(e)) + 1, n_iter=[int(v) for v in info["n_iter"]])
+    print("NMF sweep K = 1..11 against sklearn:", e, "n_iter", info["n_iter"], "sklearn", list(z["sweep_n_iter"]) + list(ze["sweep_n_iter"]))
+    assert np.allclose(info["error"], ref, rtol=2e-3), e
+
+
+@pytest.mark.parametrize("n", [1, 5])
+def test_nmf_ragged_reduction_length_matches_sklearn(n):
+    """97 x 650 with K = 5: 650 = 512 + 138 and 138 % 16 = 10, so the last K step of the reduction over the wavelengths is
+    ragged (the ``k < k1`` guards), and 97 rows leave a ragged last step of the reduction over the pixels."""
+    from test_gpu_parity import note
+    ze = np.load(GOLDEN_EDGES)
+    X = ze["Xr"]
+    assert X.shape == (97, 650) and X.shape[1] % 16 == 10 and X.shape[0] % 16 == 1
+    m = T.NMF(5, init="random", random_state=0, tol=0.0, max_iter=n)
+    W = m.fit_transform(X)
+    assert W.dtype == np.float32 and m.n_iter_ == n
+    tol = {1: 1e-5, 5: 1e-4}[n]
+    e = dict(W=_rel(W, ze[f"r_it{n}_W"]), H=_rel(m.components_, ze[f"r_it{n}_H"]),
+             err=float(abs(m.reconstruction_err_ - ze[f"r_it{n}_err"]) / ze[f"r_it{n}_err"]))
+    note("nmf_ragged", iterations=n, **e)
+    print(f"NMF 97 x 650, K = 5, {n} iterations against sklearn:", e)
+    assert max(e.values()) < tol, e
 
 
 def test_recovers_exact_rank4_templates():

@@ -183,6 +183,45 @@ def test_rectangular_images_and_template_counts(na, nb, T):
         m.close()
 
 
+@pytest.mark.parametrize("T", [5, 8], ids=["first_unfused_count", "max_templates"])
+def test_template_counts_on_the_unfused_mix(T):
+    """T = 5 is the first count on the un-fused spectral mix, T = 8 = SURFH_MAX_TEMPLATES the last one a plan takes: forward and
+    both adjoints on every local measure at TOL, no spectral-domain solver, and five CG iterations against the float64 oracle at
+    the bounds of test_gpu_parity.test_cg_matches_oracle_lcg (iterate 3e-3, every r.r of the trace 2e-4)."""
+    from test_gpu_local_parity import FWD_AXES, MAP_AXES, check_local
+    from test_gpu_parity import note
+    cfg = _variant_problem(66, 66, T)
+    om = problems.oracle_model(cfg, box="direct")
+    m = build_model(cfg)
+    rng = np.random.default_rng(2)
+    try:
+        assert m.ishape == (T, 66, 66) and not m.spec_supported()
+        yo = om.forward(cfg["maps"])
+        check_local("template_count_forward", m.forward(cfg["maps"]).reshape(om.channels[0].oshape), yo.reshape(om.channels[0].oshape),
+                    FWD_AXES, T=T)
+        u = rng.random(om.osize)
+        check_local("template_count_adjoint", m.adjoint(u), om.adjoint(u), MAP_AXES, T=T)
+        check_local("template_count_adjoint_ref", m.adjoint_ref(u), om.adjoint_ref(u), MAP_AXES, T=T)
+        y = yo + np.random.default_rng(1).standard_normal(yo.size) * 1e-2 * np.sqrt(np.mean(yo ** 2))
+        mu, mur, nit = 1.0, 5e3, 5
+        ref = orc.lcg(om, y, mu, mur, np.zeros(om.ishape), tol=1e-12, max_iter=nit)
+        x, gn, n = m.cg(y, mu=mu, mu_reg=mur, x0=None, max_iter=nit, tol=1e-12)
+        gr = np.array(ref["grad_norm"])
+        e, ge = rel(x, ref["x"]), float(np.max(np.abs(gn - gr) / gr))
+        note("template_count_cg", T=T, err_x=e, err_gradnorm=ge, nit=n)
+        print(f"T = {T}: five CG iterations, iterate {e:.2e}, r.r trace {ge:.2e}")
+        assert n == nit and len(gn) == nit + 1
+        assert e < 3e-3 and ge < 2e-4, (e, ge)
+    finally:
+        m.close()
+
+
+def test_nine_templates_are_refused():
+    cfg = _variant_problem(66, 66, 9)
+    with pytest.raises(ValueError, match="at most 8 templates"):
+        build_model(cfg)
+
+
 def test_masked_mixing_model_vs_reference():
     """MixingST (mixing.py:276-337) against the outputs of the reference's own Cython kernels."""
     from surfh_amd.mixing import MixingST

@@ -353,3 +353,23 @@ def test_box_sum_window_alignment_for_every_srf(srf):
     assert np.abs(a - b).max() < 1e-12 * np.abs(b).max()
     at, bt = orc.box_sum_fft_t(t, x), orc.box_sum_direct_t(t, x)
     assert np.abs(at - bt).max() < 1e-12 * np.abs(bt).max()
+
+
+def test_templates_edges_fixture():
+    """tests/golden/templates_edges.npz (make_golden_templates.py) is what tests/test_gpu_templates.py takes it for: the sweep
+    continues the one of templates.npz, the ragged matrix has the lengths that leave ragged K steps, and sklearn's factors
+    reproduce its own reconstruction error."""
+    path = os.path.join(os.path.dirname(__file__), "golden", "templates_edges.npz")
+    assert os.path.getsize(path) < 300 * 1024
+    z, z0 = np.load(path), np.load(os.path.join(os.path.dirname(__file__), "golden", "templates.npz"))
+    assert list(z0["sweep_k"]) + list(z["sweep_k"]) == list(range(1, 12)) and sum(range(1, 12)) == 66
+    errs = np.concatenate([z0["sweep_err"], z["sweep_err"]])
+    assert np.all(np.diff(errs[:4]) < 0) and np.all(np.abs(errs[3:] / errs[3] - 1) < 0.1)   # rank 4 plus noise: from K = 4 on, the noise floor
+    X = z["Xr"]
+    assert X.dtype == np.float32 and X.shape == (97, 650) and X.min() >= 0 and X.shape[1] % 16 == 10
+    for n in (1, 5):
+        W, H = z[f"r_it{n}_W"].astype(np.float64), z[f"r_it{n}_H"].astype(np.float64)
+        assert W.shape == (97, 5) and H.shape == (5, 650) and W.min() >= 0 and H.min() >= 0
+        assert abs(np.linalg.norm(X - W @ H) - z[f"r_it{n}_err"]) < 1e-4 * z[f"r_it{n}_err"]
+    assert z["r_it5_err"] < z["r_it1_err"]
+
