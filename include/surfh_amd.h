@@ -160,6 +160,57 @@ typedef int (*surfh_cg_callback)(void *user, int32_t it, const double *grad_norm
 int surfh_cg_cb(surfh_plan *plan, const float *y, double mu, double mu_reg, const float *x0,
                 int32_t max_iter, double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit,
                 surfh_cg_callback callback, void *user);
+
+/* ---- posterior sampling: per-pixel uncertainty of the maps surfh_cg returns (perturbation-optimisation, Orieux, Feron &
+ * Giovannelli 2012) ----
+ * Convention: the criterion of surfh_cg is the negative log of the Gaussian posterior
+ *     p(x | y)  ~  exp(-x^T Q x / 2 + b^T x),    Q = mu A^T W A + mu_reg (Dr^T Dr + Dc^T Dc),    b = mu A^T W y,
+ * so the precision is Q exactly as surfh_cg defines it (W: surfh_set_data_weights), the maps surfh_cg returns are the mean
+ * Q^-1 b, and the covariance is Q^-1.  It is a statistical statement once the caller passes weights = 1 / sigma^2 (mu = 1) and
+ * a mu_reg they believe in.  A draw b~ ~ N(b, Q) costs three standard normal vectors,
+ *     y~ = y + eps_y / sqrt(mu w)  (samples of weight 0 untouched, NaN included),   eta = sqrt(mu_reg) (Dr^T eps_r + Dc^T eps_c),
+ *     b~ = mu A^T W y~ + eta,
+ * and x~ = Q^-1 b~ is a posterior sample: one CG solve.  The sampler solves for the deviation from the point estimate xhat,
+ *     Q e = b~ - b = mu A^T W (eps_y / sqrt(mu w)) + eta  from e = 0,     x~ = xhat + e,
+ * which is the solve of Q x~ = b~ started at xhat whenever xhat has converged, and keeps every fp32 vector at the scale of the
+ * perturbation (started at xhat the residual would be a small difference of large vectors; DESIGN.md, "Posterior sampling").
+ * A sample is exact only if its solve converges: CG stopped at max_iter leaves the slowly converging directions
+ * under-dispersed, and the standard deviation is a lower bound there (rr_worst below says how far the solves got).
+ *
+ * surfh_randn_dev: out_dev[i] = the standard normal of (seed, stream, sample, i), whatever the launch shape or call order.
+ * Philox4x32-10, key (seed low, seed high), counter (i / 4 low, i / 4 high, stream, sample); the words (a0, a1) and (a2, a3)
+ * give the Box-Muller pairs of elements 4c, 4c+1 and 4c+2, 4c+3:  u = ((a0 >> 8) + 1/2) 2^-24, theta = 2 pi ((a1 >> 8) + 1/2)
+ * 2^-24, z0 = sqrt(-2 ln u) cos theta, z1 = sqrt(-2 ln u) sin theta; |z| <= 5.89.  Streams of the sampler: 0 eps_y, 1 eps_r, 2 eps_c. */
+int surfh_randn_dev(surfh_plan *plan, float *out_dev, int64_t n, uint64_t seed, uint32_t stream, uint32_t sample);
+/* out = y + eps / sqrt(mu w) where w > 0 (w_dev NULL: every weight 1), the bits of y elsewhere; n floats each, on the device.
+ * y_dev NULL: the perturbation alone, eps / sqrt(mu w), and 0 where w = 0. */
+int surfh_po_data_dev(surfh_plan *plan, const float *y_dev, const float *w_dev, const float *eps_dev, int64_t n, double mu, float *out_dev);
+/* out = sqrt(mu_reg) (Dr^T eps_r + Dc^T eps_c) on device maps [T][Na][Nb] (the transposes of the separated circular differences) */
+int surfh_po_prior_dev(surfh_plan *plan, const float *eps_r_dev, const float *eps_c_dev, double mu_reg, float *out_dev);
+/* The moment kernels on their own, host buffers: K samples [K][T][npix] about xhat [T][npix], accumulated in float64 per pixel
+ * in a fixed order; mean [T][npix] = xhat + S1 / K, cov [T (T + 1) / 2][npix] = the unbiased covariance of the pairs t <= u in
+ * row-major order (NULL: not wanted; needs K >= 2).  1 <= T <= 8. */
+int surfh_po_moments(int32_t T, int64_t npix, const float *xhat, const float *samples, int32_t K, double *mean, double *cov,
+                     int32_t device);
+/* btilde [isize] = the perturbed right-hand side b~ of draw `sample` under `seed`, in the maps' layout.  eps NULL: the generator;
+ * else one explicit draw, eps_y [osize] followed by eps_r and eps_c [isize] each (`seed`, `sample` unused).  For statistical
+ * tests of the sampler and for callers that run their own loop.  Refuses what surfh_cg_sample refuses. */
+int surfh_po_rhs(surfh_plan *plan, const float *y, double mu, double mu_reg, uint64_t seed, int32_t sample, const float *eps,
+                 float *btilde);
+/* surfh_cg (same arguments, same bits in x_map, grad_norm and nit), then n_samples solves of Q e = b~ - b from zero with the same
+ * max_iter, tol and refresh, x~ = x_map + e, and the moments of the samples: mean [T][Na][Nb] = x_map + mean of e and cov
+ * [T (T + 1) / 2][Na][Nb] (pairs t <= u, row-major) in float64, either may be NULL.  eps_y [n_samples][osize], eps_r and eps_c [n_samples][isize]: the noise
+ * of every draw, or NULL for the generator under `seed` (sample k = counter word `sample`); eps_r / eps_c are not read when
+ * mu_reg = 0.  rr_worst (may be NULL): the largest final r.r over the sample solves (to be read against their first, |b~ - b|^2).
+ * The callback (may be NULL) receives every
+ * finished sample: its index, the iterations of its solve, its r.r trace (nit + 1 values) and x~ [T][Na][Nb] on the host; a
+ * non-zero return makes the call fail.  Refuses, before any work: plans without templates, the joint prior (surfh_set_prior),
+ * an active imager term, mu <= 0, mu_reg < 0, n_samples < 1, and n_samples < 2 when cov is requested. */
+typedef int (*surfh_sample_callback)(void *user, int32_t sample, int32_t nit, const double *rr, const float *x);
+int surfh_cg_sample(surfh_plan *plan, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
+                    int32_t refresh, int32_t n_samples, uint64_t seed, const float *eps_y, const float *eps_r, const float *eps_c,
+                    float *x_map, double *mean, double *cov, double *grad_norm, int32_t *nit, double *rr_worst,
+                    surfh_sample_callback callback, void *user);
 /* 3MG, the reference's other solver choice (`method != 'lcg'` -> qmm.mmmg, fusion_CT.py:194-198; algorithms.py:69,106),
  * for the same quadratic criterion: every iteration minimises it exactly over span{-gradient, previous move}
  * (the quadratic majorant of a quadratic objective is the objective).  The 2x2 subspace system is solved in a basis

@@ -136,12 +136,12 @@ def create_model(sotf, templates, origin_alpha_axis, origin_beta_axis, wavel_axi
 
 
 def result_dir_name(method, n_channels, n_templates, niter, hyper_parameter, scale_data, delta=None, voxel=False, weighted=False,
-                    data_delta=None, potential='huber', data_potential='huber', spec_potential='huber', imager=0):
+                    data_delta=None, potential='huber', data_potential='huber', spec_potential='huber', imager=0, samples=0):
     """main_fusion.py:182; with a Huber threshold `delta` (not in the reference) `_huber_<delta>` is appended, `_vox` for a
     voxel-wise reconstruction, `_wgt` for a run under data weights, and `_rob_<data_delta>` for a robust data term.  Another
     potential than Huber puts its name in Huber's place (`_<kind>_<delta>`, `_rob_<kind>_<data_delta>`; `_spec_<kind>` for the
-    spectral prior of a voxel-wise run); with Huber the names are unchanged.  `_img_<F>` comes last, for a run with an imager
-    data term of F filters."""
+    spectral prior of a voxel-wise run); with Huber the names are unchanged.  `_img_<F>` follows for a run with an imager
+    data term of F filters, `_po_<K>` for a run that draws K posterior samples."""
     name = f'{method}_MC_{n_channels}_MO_4_Temp_{n_templates}_nit_{str(niter)}_mu_{str("{:.2e}".format(hyper_parameter))}_SD_{scale_data}'
     if delta is not None:
         name += f'_{potential}_{delta:.2e}'
@@ -155,6 +155,8 @@ def result_dir_name(method, n_channels, n_templates, niter, hyper_parameter, sca
         name += f'_rob_{data_delta:g}' if data_potential == 'huber' else f'_rob_{data_potential}_{data_delta:g}'
     if imager:
         name += f'_img_{imager}'
+    if samples:
+        name += f'_po_{samples}'
     return name + '/'
 
 
@@ -208,19 +210,21 @@ def voxel_reconstruction(spectro_model, ndata, result_path, spat_reg, spat_th, s
 
 def reconstruction_method(spectro_model, ndata, templates, result_path, hyper_parameter, niter, method, scale_data,
                           checkpoint_every=0, resume=None, delta=None, weights=None, data_delta=None, potential='huber',
-                          data_potential='huber', imager=None):
+                          data_potential='huber', imager=None, samples=0, seed=0):
     """main_fusion.py:162-206: regularised least squares by CG, then the three result files.  Not in the reference:
     `checkpoint_every` > 0 writes the iterate to checkpoint.npz in the result directory every that many iterations,
     `resume` (such a file) warm-starts from it and runs the iterations that are left; `delta` replaces the quadratic
     priors by Huber potentials of that threshold (3MG only); `weights` `[osize]` weigh the samples of the data term and are
     stored beside the results as weights.npy; `data_delta` makes the data term robust (3MG only) and stores the last iterate's
     robustness weights as robust_weights.npy; `potential` / `data_potential` name the potential under `delta` / `data_delta`;
-    `imager` = (ImagerModel, y_im, mu_imager) adds the imager data term and stores y_im as y_imager.npy."""
+    `imager` = (ImagerModel, y_im, mu_imager) adds the imager data term and stores y_im as y_imager.npy; `samples` = K > 0 (lcg
+    only) draws K posterior samples under `seed` after the solve, each a CG solve of `niter` iterations for its deviation from res_x, and
+    stores their mean, per-pixel standard deviation and covariance [T, T, N, N] as res_mean.npy, res_std.npy and res_cov.npy."""
     value_init = 0
     path = pathlib.Path(result_path) / result_dir_name(method, len(spectro_model.instrs), templates.shape[0], niter,
                                                        hyper_parameter, scale_data, delta, weighted=weights is not None,
                                                        data_delta=data_delta, potential=potential, data_potential=data_potential,
-                                                       imager=imager[0].oshape[0] if imager else 0)
+                                                       imager=imager[0].oshape[0] if imager else 0, samples=samples)
     path.mkdir(parents=True, exist_ok=True)
     im_kw = dict(model_imager=imager[0], y_imager=imager[1], mu_imager=imager[2]) if imager else {}
     crit = QuadCriterion_MRS(mu_spectro=1, y_spectro=np.copy(ndata), model_spectro=spectro_model,
@@ -245,6 +249,13 @@ def reconstruction_method(spectro_model, ndata, templates, result_path, hyper_pa
         np.save(path / 'robust_weights.npy', spectro_model.robust_weights)
     if imager:
         np.save(path / 'y_imager.npy', imager[1])
+    if samples:
+        po = crit.sample(n_samples=samples, seed=seed, maximum_iterations=niter, value_init=value_init)
+        print(f"{samples} posterior samples: worst final r.r {po.rr_worst:.3e} (unperturbed solve: {po.grad_norm[0]:.3e} -> "
+              f"{po.grad_norm[-1]:.3e}); the standard deviation is a lower bound where the solves have not converged")
+        np.save(path / 'res_mean.npy', po.mean)
+        np.save(path / 'res_std.npy', po.std)
+        np.save(path / 'res_cov.npy', po.cov)
     return res, path
 
 
@@ -298,9 +309,25 @@ def synthetic_problem(name, npix):
                    'needs --synthetic). Default: none.')
 @click.option('--mu_imager', default=1., type=float, help='Weight of the imager data term (--imager).')
 @click.option('--imager_decim', default=1, type=int, help='Cube pixels per imager pixel along each axis (--imager).')
+@click.option('--samples', default=0, type=int,
+              help='Draw that many posterior samples after the solve (needs --method lcg; at least 2) and store their mean, '
+                   'standard deviation and covariance per pixel. Default: none.')
+@click.option('--seed', default=None, type=int, help='Seed of the posterior samples (--samples). Default: 0.')
 def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, method, verbose, synthetic, device, checkpoint_every=0,
          resume=None, delta=None, voxel=False, spec_reg=1., spec_delta=1., weights_file=None, mask_nan=False, data_delta=None,
-         potential='huber', data_potential='huber', spec_potential='huber', imager_filters=0, mu_imager=1., imager_decim=1):
+         potential='huber', data_potential='huber', spec_potential='huber', imager_filters=0, mu_imager=1., imager_decim=1,
+         samples=0, seed=None):
+    if samples:
+        if method != 'lcg':
+            raise click.UsageError('--samples draws from the Gaussian posterior of the quadratic criterion; use it with --method lcg')
+        if samples < 2:
+            raise click.BadParameter(f'a covariance needs at least 2 samples, not {samples}', param_hint='--samples')
+        if voxel or imager_filters:
+            raise click.UsageError('--samples: the sampler carries neither the voxel-wise solver (--voxel) nor the imager data term (--imager)')
+        if seed is not None and seed < 0:
+            raise click.BadParameter(f'must be >= 0, not {seed}', param_hint='--seed')
+    elif seed is not None:
+        raise click.UsageError('--seed belongs to --samples')
     if imager_filters:
         if not 1 <= imager_filters <= 16:
             raise click.BadParameter(f'1 to 16 filters, not {imager_filters}', param_hint='--imager')
@@ -396,7 +423,8 @@ def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, meth
         return
     reconstruction_method(model, ndata, templates, paths["result_path"], hyper_parameter, niter, method, scale_data,
                           checkpoint_every=checkpoint_every, resume=resume, delta=delta, weights=weights, data_delta=data_delta,
-                          potential=potential, data_potential=data_potential, imager=imager if synthetic else None)
+                          potential=potential, data_potential=data_potential, imager=imager if synthetic else None, samples=samples,
+                          seed=seed or 0)
     model.close()
 
 

@@ -17,6 +17,8 @@ c_int32_p = C.POINTER(C.c_int32)
 # int cb(void *user, int32_t it, const double *grad_norm, const float *x)   (include/surfh_amd.h:surfh_cg_callback)
 CG_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, c_double_p, c_float_p)
 c_uint8_p = C.POINTER(C.c_uint8)
+# int cb(void *user, int32_t sample, int32_t nit, const double *rr, const float *x)   (include/surfh_amd.h:surfh_sample_callback)
+SAMPLE_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, c_double_p, c_float_p)
 
 
 class ChannelDesc(C.Structure):
@@ -56,6 +58,7 @@ EXPORTS = [
     "surfh_tst_adjoint", "surfh_tst_fwadj", "surfh_tst_last_error", "surfh_cg", "surfh_cg_cb", "surfh_mmmg", "surfh_mmmg_huber", "surfh_huber_prior_dev", "surfh_huber_curv_dev", "surfh_mmmg_huber_vox", "surfh_huber_vox_prior_dev", "surfh_huber_vox_curv_dev", "surfh_mmmg_robust", "surfh_mmmg_robust_vox", "surfh_robust_data_dev", "surfh_robust_curv_dev", "surfh_mmmg_huber_planes", "surfh_huber_planes_prior_dev", "surfh_huber_planes_curv_dev", "surfh_cg_planes", "surfh_mmmg_planes", "surfh_cg_planes_cb", "surfh_mmmg_planes_cb", "surfh_cg_planes_begin_dev", "surfh_cg_planes_step_dev", "surfh_cg_planes_rr", "surfh_maps_to_cube", "surfh_cube_to_maps", "surfh_normal_dev",
     "surfh_prior_add_dev", "surfh_spec_supported", "surfh_spec_size", "surfh_to_spec_dev", "surfh_from_spec_dev", "surfh_forward_spec_dev",
     "surfh_adjoint_spec_dev", "surfh_normal_spec_dev", "surfh_prior_spec_add_dev", "surfh_set_prior", "surfh_set_potential", "surfh_get_potential", "surfh_set_data_weights", "surfh_set_data_weights_dev", "surfh_has_data_weights", "surfh_set_imager", "surfh_imager_osize", "surfh_imager_forward", "surfh_imager_adjoint", "surfh_imager_forward_dev", "surfh_imager_adjoint_dev", "surfh_imager_fwadj", "surfh_set_imager_data", "surfh_has_imager_term", "surfh_dot_dev", "surfh_cg_step_dev", "surfh_cg_dir_dev", "surfh_cg_iter_dev", "surfh_residual_dev",
+    "surfh_randn_dev", "surfh_po_data_dev", "surfh_po_prior_dev", "surfh_po_moments", "surfh_po_rhs", "surfh_cg_sample",
     "surfh_cg_begin_dev", "surfh_cg_iter_nosync_dev", "surfh_cg_xupdate_nosync_dev", "surfh_cg_refresh_nosync_dev", "surfh_cg_trace",
     "surfh_profile_enable", "surfh_profile_filter", "surfh_profile_count", "surfh_profile_get", "surfh_profile_reset", "surfh_debug_copy",
     "surfh_debug_dims", "surfh_gemm_selftest", "surfh_gemm_selftest_ksteps", "surfh_gemm_selftest_ms", "surfh_klist_classify", "surfh_mm_step2",
@@ -100,6 +103,14 @@ def load():
     L.surfh_cg_cb.argtypes = [vp, c_float_p, C.c_double, C.c_double, c_float_p, C.c_int32, C.c_double, C.c_int32,
                               c_float_p, c_double_p, c_int32_p, CG_CALLBACK, vp]
     L.surfh_mmmg.argtypes = L.surfh_cg_cb.argtypes
+    L.surfh_randn_dev.argtypes = [vp, vp, C.c_int64, C.c_uint64, C.c_uint32, C.c_uint32]
+    L.surfh_po_data_dev.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_double, vp]
+    L.surfh_po_prior_dev.argtypes = [vp, vp, vp, C.c_double, vp]
+    L.surfh_po_moments.argtypes = [C.c_int32, C.c_int64, c_float_p, c_float_p, C.c_int32, c_double_p, c_double_p, C.c_int32]
+    L.surfh_po_rhs.argtypes = [vp, c_float_p, C.c_double, C.c_double, C.c_uint64, C.c_int32, c_float_p, c_float_p]
+    L.surfh_cg_sample.argtypes = [vp, c_float_p, C.c_double, C.c_double, c_float_p, C.c_int32, C.c_double, C.c_int32, C.c_int32,
+                                  C.c_uint64, c_float_p, c_float_p, c_float_p, c_float_p, c_double_p, c_double_p, c_double_p,
+                                  c_int32_p, c_double_p, SAMPLE_CALLBACK, vp]
     L.surfh_mmmg_huber.argtypes = [vp, c_float_p, C.c_double, C.c_double, C.c_double, c_float_p, C.c_int32, C.c_double, C.c_int32,
                                    c_float_p, c_double_p, c_int32_p, c_double_p, CG_CALLBACK, vp]
     L.surfh_huber_prior_dev.argtypes = [vp, vp, vp, C.c_double, C.c_double, c_double_p]

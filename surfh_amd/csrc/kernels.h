@@ -146,6 +146,20 @@ int launch_cg_dir(hipStream_t s, float *d, const float *r, long n, const double 
 int launch_residual(hipStream_t s, float *r, const float *b, const float *q, long n);
 // out = a + beta b
 int launch_lincomb(hipStream_t s, float *out, const float *a, const float *b, long n, double beta);
+// ---- posterior sampling (posterior.hip) ----
+// out[i] = standard normal of (seed, stream, sample, i): Philox4x32-10 on the counter (i / 4, stream, sample), Box-Muller; n any
+int launch_randn(hipStream_t s, float *out, long n, uint64_t seed, uint32_t stream, uint32_t sample);
+// out = y + eps / sqrt(mu w) where w > 0 (w NULL: 1), the bits of y elsewhere (y NULL: eps / sqrt(mu w), and 0 elsewhere)
+int launch_po_data(hipStream_t s, const float *y, const float *w, const float *eps, float *out, long n, float mu);
+// out = sqrt_mu_reg (Dr^T er + Dc^T ec) on [T][na][nb], circular
+int launch_po_prior(hipStream_t s, const float *er, const float *ec, float *out, int T, int na, int nb, float sqrt_mu_reg);
+// b += e
+int launch_po_add(hipStream_t s, float *b, const float *e, long n);
+// S [po_moment_planes(T)][npix] float64: S1[t] += e_t, S2[t <= u] += e_t e_u, e = x - xhat (xhat NULL: x); then mean = xhat + S1 / K and
+// cov [T (T + 1) / 2][npix] = (S2 - S1 S1^T / K) / (K - 1) (NULL: skipped).  1 <= T <= SURFH_MAX_TEMPLATES, else hipErrorInvalidValue.
+long po_moment_planes(int T);
+int launch_po_moments(hipStream_t s, const float *x, const float *xhat, double *S, int T, long npix);
+int launch_po_finish(hipStream_t s, const float *xhat, const double *S, int T, long npix, int K, double *mean, double *cov);
 // 3MG move: mv = s0 d + s1 m ; x += mv ; m = mv ; qm = s0 qd + s1 qm ; r -= qm (when update_r)
 int launch_mmmg_update(hipStream_t s, float *x, float *r, const float *d, float *m, float *qm, const float *qd, long n, double s0,
                        double s1, int update_r);

@@ -617,8 +617,9 @@ int surfh_plan_destroy(surfh_plan *p) {
     if (p->stream) hipStreamSynchronize(p->stream);
     for (float *v : {p->sotf, p->tpl, p->mhat, p->spec, p->ycol, p->cube, p->ycol_maps, p->maps_pad, p->Fi, p->Gi, p->Gf,
                      p->Ff, p->GiT, p->GfT, p->Cma, p->Sma, p->Gc, p->Gs, p->Cf, p->Sf, p->io_cube, p->hth, p->mhat2, p->gcube, p->io_x, p->io_y, p->cg_x, p->cg_r, p->cg_d, p->cg_q, p->cg_b, p->cg_y, p->cg_qm, p->cg_dd, p->cg_hg,
-                     p->rb_y, p->rb_u, p->rb_ag, p->rb_am})
+                     p->rb_y, p->rb_u, p->rb_ag, p->rb_am, p->po_y, p->po_eps, p->po_er, p->po_ec, p->po_eta, p->po_xhat})
         hipFree(v);
+    hipFree(p->po_S);
     hipFree(p->h2img);
     if (p->ctB.img != p->ctA.img) dft_ct_plan_destroy(&p->ctB);
     else p->ctB = DftCtPlan();

@@ -235,6 +235,12 @@ struct surfh_plan {
     float *cg_hg = nullptr;                        // surfh_mmmg_huber(_vox): -gradient of the non-quadratic criterion
     float *rb_y = nullptr, *rb_u = nullptr, *rb_ag = nullptr, *rb_am = nullptr;   // surfh_mmmg_robust(_vox): y, A x, A (-g), A m [osize]
     double *dscal = nullptr, *dscratch = nullptr;   // [16] device scalars, partial sums (>= 1024, and what huber_vox.hip and robust_data.hip ask for)
+    // posterior sampling (surfh_cg_sample): an extra right-hand side [isize] in the maps' layout that the set-up of the map and
+    // spectral CG spaces adds to b (null outside a sampling solve: the launches are then exactly those without it); y, the noise
+    // vectors eps_y [osize], eps_r / eps_c [isize], eta and the unperturbed solution [isize]; the moment sums (posterior.hip)
+    const float *cg_extra = nullptr;
+    float *po_y = nullptr, *po_eps = nullptr, *po_er = nullptr, *po_ec = nullptr, *po_eta = nullptr, *po_xhat = nullptr;
+    double *po_S = nullptr;
     double *cg_hist = nullptr;                     // device-resident r.r trace of the no-host-sync CG blocks (CG_HIST_CAP entries)
     int cg_hist_n = 0;
     // plane-wise CG with device-resident data (surfh_cg_planes_begin_dev / _step_dev): per-plane scalars [3][Lc] (the host-buffer

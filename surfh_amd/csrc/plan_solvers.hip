@@ -145,6 +145,7 @@ int solver_setup(surfh_plan *p, const float *y, const float *x, double mu, doubl
     if (adjoint_dev(p, y, p->cg_b, false)) return 1;
     if (mu != 1.0) LAUNCH_OK(launch_scale(p->stream, p->cg_b, p->isize, (float)mu));
     if (imager_active(p) && imager_rhs_add(p, p->cg_b)) return 1;           // + mu_imager A_im^T W_im y_im
+    if (p->cg_extra) LAUNCH_OK(launch_po_add(p->stream, p->cg_b, p->cg_extra, p->isize));   // + eta (surfh_cg_sample)
     if (normal_prior(p, x, p->cg_q, mu, mu_reg)) return 1;
     LAUNCH_OK(launch_residual(p->stream, p->cg_r, p->cg_b, p->cg_q, p->isize));
     return 0;
@@ -273,6 +274,10 @@ CgSpace maps_space(surfh_plan *p, double mu, double mu_reg) {
 int spec_setup(surfh_plan *p, const CgSpace &s, const float *y, const float *x0) {
     const float *wy = weighted_data(p, y);
     if (!wy || surfh_adjoint_spec_dev(p, wy, s.b, s.mu, nullptr, 0.0)) return 1;
+    if (p->cg_extra) {                                                                      // + eta (surfh_cg_sample), s.q still free
+        if (surfh_to_spec_dev(p, p->cg_extra, s.q)) return 1;
+        LAUNCH_OK(launch_po_add(p->stream, s.b, s.q, s.len));
+    }
     if (x0) {
         if (surfh_to_spec_dev(p, x0, s.x) || surfh_normal_spec_dev(p, s.x, s.q, s.mu, s.mu_reg)) return 1;
         LAUNCH_OK(launch_residual(p->stream, s.r, s.b, s.q, s.len));
@@ -448,24 +453,173 @@ int cg_loop(surfh_plan *p, const CgSpace &s, int32_t max_iter, double tol, int32
 }
 }  // namespace
 
+namespace {
+// the vectors of surfh_cg are the maps' spectra unless SURFH_SPECTRAL_CG=0, or an imager term (not diagonal in that basis)
+bool cg_spectral(surfh_plan *p, int32_t max_iter) {
+    return env_on("SURFH_SPECTRAL_CG", true) && !imager_active(p) && surfh_spec_supported(p) && max_iter < (1 << 16) - 1;
+}
+// surfh_cg_cb behind its argument checks; y NULL: the data are in io_y already (the perturbed data of surfh_cg_sample)
+int cg_run(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol, int32_t refresh, float *x,
+           double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
+    HIP_OK(hipSetDevice(p->dev));
+    if (ensure_cg(p)) return 1;
+    const bool spectral = cg_spectral(p, max_iter);
+    const CgSpace s = spectral ? spectral_space(p, mu, mu_reg) : maps_space(p, mu, mu_reg);
+    if (y) HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    if (spectral && x0) HIP_OK(hipMemcpyAsync(s.xc, x0, p->isize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    if ((!spectral && start_iterate(p, x0)) || cg_start(p, s, p->io_y, x0 ? s.xc : nullptr)) return 1;
+    return cg_loop(p, s, max_iter, tol, refresh, spectral ? CG_CHECK : 1, x, grad_norm, nit, callback, user);
+}
+}  // namespace
+
 int surfh_cg_cb(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
                 int32_t refresh, float *x, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
     if (p->T <= 0) return fail("surfh_cg needs templates (the priors act on abundance maps)");
-    HIP_OK(hipSetDevice(p->dev));
-    if (ensure_cg(p)) return 1;
-    // SURFH_SPECTRAL_CG=0, or an imager term (not diagonal in that basis): the vectors are the maps
-    const bool spectral = env_on("SURFH_SPECTRAL_CG", true) && !imager_active(p) && surfh_spec_supported(p) && max_iter < (1 << 16) - 1;
-    const CgSpace s = spectral ? spectral_space(p, mu, mu_reg) : maps_space(p, mu, mu_reg);
-    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, p->stream));
-    if (spectral && x0) HIP_OK(hipMemcpyAsync(s.xc, x0, p->isize * sizeof(float), hipMemcpyHostToDevice, p->stream));
-    if ((!spectral && start_iterate(p, x0)) || cg_start(p, s, p->io_y, x0 ? s.xc : nullptr)) return 1;
-    return cg_loop(p, s, max_iter, tol, refresh, spectral ? CG_CHECK : 1, x, grad_norm, nit, callback, user);
+    return cg_run(p, y, mu, mu_reg, x0, max_iter, tol, refresh, x, grad_norm, nit, callback, user);
 }
 
 int surfh_cg(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
              int32_t refresh, float *x, double *grad_norm, int32_t *nit) {
     return surfh_cg_cb(p, y, mu, mu_reg, x0, max_iter, tol, refresh, x, grad_norm, nit, nullptr, nullptr);
+}
+
+// ---- posterior sampling by perturbation-optimisation (kernels and conventions: posterior.hip) ----
+// The criterion of surfh_cg is the negative log of the Gaussian  p(x | y) ~ exp(-x^T Q x / 2 + b^T x),  Q = mu A^T W A + mu_reg
+// (Dr^T Dr + Dc^T Dc), b = mu A^T W y, and a draw b~ = mu A^T W (y + eps_y / sqrt(mu w)) + eta ~ N(b, Q), eta = sqrt(mu_reg)
+// (Dr^T eps_r + Dc^T eps_c), gives the sample x~ = Q^-1 b~.  The sampler solves for the deviation e = x~ - xhat instead, from
+// zero:  Q e = b~ - b = mu A^T W (eps_y / sqrt(mu w)) + eta  -- the CG of surfh_cg on the perturbation alone as its data (io_y)
+// with eta as the extra right-hand side of its set-up (cg_extra).  In exact arithmetic and at convergence that is the solve of
+// Q x~ = b~ started at xhat; in fp32 it is the one that works: started at xhat, the residual b~ - Q xhat is a difference of two
+// vectors some 1e3 times its size, the operator's 3e-7 comes back as 1e-4 of every r.r (measured: 2.3e-4 to 5.4e-4 on config 1
+// and two_channel_mid, against 2e-5 for a solve from zero), a perturbation below 1e-4 of the data drowns in the rounding of y~,
+// and a solve stopped at max_iter spends its iterations on what xhat left unconverged (r.r 7.0e6 of it against 4.7e5 of the
+// perturbation on config 1 after 10 iterations), which all samples share.  The deviation form has none of the three.
+namespace {
+int po_refuse(const surfh_plan *p, double mu, double mu_reg, const char *who) {
+    if (p->T <= 0) return fail("%s needs templates (the posterior is that of the abundance maps)", who);
+    if (p->T > SURFH_MAX_TEMPLATES) return fail("%s: %d maps, the moment kernels take %d", who, p->T, SURFH_MAX_TEMPLATES);
+    if (p->prior_kind != 0) return fail("%s draws the prior's noise through the separated differences: surfh_set_prior(plan, 0)", who);
+    if (imager_active(p)) return fail("%s does not perturb the imager data term set on this plan (surfh_set_imager_data): clear it", who);
+    if (!(mu > 0.0 && mu <= DBL_MAX)) return fail("%s: mu = %g must be finite and > 0", who, mu);
+    if (!(mu_reg >= 0.0 && mu_reg <= DBL_MAX)) return fail("%s: mu_reg = %g must be finite and >= 0", who, mu_reg);
+    return 0;
+}
+int po_ensure(surfh_plan *p) {
+    if (ensure_cg(p)) return 1;
+    if (!p->po_y && (dev_alloc(&p->po_y, (size_t)p->osize) || dev_alloc(&p->po_eps, (size_t)p->osize))) return 1;
+    for (float **v : {&p->po_er, &p->po_ec, &p->po_eta, &p->po_xhat})
+        if (!*v && dev_alloc(v, (size_t)p->isize)) return 1;
+    return !p->po_S && dev_alloc(&p->po_S, (size_t)(2 * po_moment_planes(p->T)) * p->Na * p->Nb);   // the sums, then mean and cov
+}
+// one noise vector on the device: row `sample` of the caller's, or the generator's stream
+int po_noise(surfh_plan *p, float *dst, long n, const float *host, uint64_t seed, uint32_t stream, int sample) {
+    if (host) {
+        HIP_OK(hipMemcpyAsync(dst, host + (size_t)sample * n, n * sizeof(float), hipMemcpyHostToDevice, p->stream));
+        return 0;
+    }
+    Prof pr(p, "po_randn");
+    LAUNCH_OK(launch_randn(p->stream, dst, n, seed, stream, (uint32_t)sample));
+    return 0;
+}
+// draw `sample`: y + eps_y / sqrt(mu w) to io_y (y on the device, or NULL: the perturbation alone), eta to po_eta; *extra =
+// po_eta, or NULL where mu_reg = 0.  eps_* are the rows [n_samples][...] of the caller's noise (NULL: the generator under `seed`)
+int po_perturb(surfh_plan *p, const float *y, double mu, double mu_reg, uint64_t seed, int sample, const float *eps_y, const float *eps_r,
+               const float *eps_c, const float **extra) {
+    if (po_noise(p, p->po_eps, p->osize, eps_y, seed, 0, sample)) return 1;
+    {
+        Prof pr(p, "po_data");
+        LAUNCH_OK(launch_po_data(p->stream, y, p->dw, p->po_eps, p->io_y, p->osize, (float)mu));
+    }
+    *extra = nullptr;
+    if (mu_reg == 0.0) return 0;
+    if (po_noise(p, p->po_er, p->isize, eps_r, seed, 1, sample) || po_noise(p, p->po_ec, p->isize, eps_c, seed, 2, sample)) return 1;
+    Prof pr(p, "po_prior");
+    LAUNCH_OK(launch_po_prior(p->stream, p->po_er, p->po_ec, p->po_eta, p->T, p->Na, p->Nb, (float)std::sqrt(mu_reg)));
+    *extra = p->po_eta;
+    return 0;
+}
+struct ExtraScope {                    // the extra right-hand side never outlives a solve
+    surfh_plan *p;
+    ExtraScope(surfh_plan *pl, const float *e) : p(pl) { p->cg_extra = e; }
+    ~ExtraScope() { p->cg_extra = nullptr; }
+};
+}  // namespace
+
+int surfh_po_rhs(surfh_plan *p, const float *y, double mu, double mu_reg, uint64_t seed, int32_t sample, const float *eps,
+                 float *btilde) {
+    if (!p || !y || !btilde) return fail("null argument");
+    if (po_refuse(p, mu, mu_reg, "surfh_po_rhs")) return 1;
+    if (sample < 0) return fail("surfh_po_rhs: sample = %d", sample);
+    HIP_OK(hipSetDevice(p->dev));
+    if (po_ensure(p)) return 1;
+    HIP_OK(hipMemcpyAsync(p->po_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    const float *extra = nullptr;
+    // eps: one draw, eps_y [osize] then eps_r, eps_c [isize] each; row 0 of each
+    if (po_perturb(p, p->po_y, mu, mu_reg, seed, eps ? 0 : sample, eps, eps ? eps + p->osize : nullptr, eps ? eps + p->osize + p->isize : nullptr, &extra))
+        return 1;
+    // the right-hand side as the maps' CG sets it up (solver_setup): mu A^T W y~ + eta
+    const float *wy = weighted_data(p, p->io_y);
+    if (!wy || adjoint_dev(p, wy, p->cg_b, false)) return 1;
+    if (mu != 1.0) LAUNCH_OK(launch_scale(p->stream, p->cg_b, p->isize, (float)mu));
+    if (extra) LAUNCH_OK(launch_po_add(p->stream, p->cg_b, extra, p->isize));
+    HIP_OK(hipMemcpyAsync(btilde, p->cg_b, p->isize * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int surfh_cg_sample(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
+                    int32_t refresh, int32_t n_samples, uint64_t seed, const float *eps_y, const float *eps_r, const float *eps_c,
+                    float *x_map, double *mean, double *cov, double *grad_norm, int32_t *nit, double *rr_worst,
+                    surfh_sample_callback callback, void *user) {
+    if (!p || !y || !x_map || !grad_norm || !nit) return fail("null argument");
+    if (po_refuse(p, mu, mu_reg, "surfh_cg_sample")) return 1;
+    if (n_samples < 1 || (cov && n_samples < 2))
+        return fail("surfh_cg_sample: n_samples = %d (at least 1, and at least 2 for a covariance)", n_samples);
+    if (max_iter < 0) return fail("surfh_cg_sample: max_iter = %d", max_iter);
+    HIP_OK(hipSetDevice(p->dev));
+    if (po_ensure(p)) return 1;
+    // the point estimate: surfh_cg itself
+    if (cg_run(p, y, mu, mu_reg, x0, max_iter, tol, refresh, x_map, grad_norm, nit, nullptr, nullptr)) return 1;
+    hipStream_t s = p->stream;
+    const long npix = (long)p->Na * p->Nb;
+    const long planes = po_moment_planes(p->T);
+    const float *xc = cg_spectral(p, max_iter) ? p->io_x : p->cg_x;         // where a solve leaves its result in the maps' layout
+    HIP_OK(hipMemcpyAsync(p->po_xhat, xc, p->isize * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_OK(hipMemsetAsync(p->po_S, 0, (size_t)planes * npix * sizeof(double), s));
+    std::vector<float> xs((size_t)p->isize);
+    std::vector<double> gn((size_t)max_iter + 1);
+    double worst = 0.0;
+    for (int k = 0; k < n_samples; ++k) {
+        const float *extra = nullptr;
+        if (po_perturb(p, nullptr, mu, mu_reg, seed, k, eps_y, eps_r, eps_c, &extra)) return 1;
+        int32_t nk = 0;
+        {
+            ExtraScope sc(p, extra);                                            // Q e = b~ - b from e = 0
+            if (cg_run(p, nullptr, mu, mu_reg, nullptr, max_iter, tol, refresh, xs.data(), gn.data(), &nk, nullptr, nullptr)) return 1;
+        }
+        {
+            Prof pr(p, "po_moments");
+            LAUNCH_OK(launch_po_moments(s, xc, nullptr, p->po_S, p->T, npix));
+        }
+        worst = std::max(worst, gn[nk]);
+        if (callback)
+            for (long i = 0; i < p->isize; ++i) xs[i] += x_map[i];               // x~ = xhat + e
+        if (callback && callback(user, k, nk, gn.data(), xs.data())) return fail("surfh_cg_sample: stopped by the callback at sample %d", k);
+        HIP_OK(hipSetDevice(p->dev));
+    }
+    if (rr_worst) *rr_worst = worst;
+    if (mean || cov) {
+        double *out = p->po_S + planes * npix;
+        {
+            Prof pr(p, "po_moments");
+            LAUNCH_OK(launch_po_finish(s, p->po_xhat, p->po_S, p->T, npix, n_samples, out, cov ? out + p->isize : nullptr));
+        }
+        if (mean) HIP_OK(hipMemcpyAsync(mean, out, p->isize * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (cov) HIP_OK(hipMemcpyAsync(cov, out + p->isize, (size_t)(planes - p->T) * npix * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+    }
+    return 0;
 }
 
 // ---- 3MG (majorize-minimize memory gradient, qmm.mmmg; selected by method != 'lcg' at fusion_CT.py:194-198) ----

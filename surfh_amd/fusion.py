@@ -195,6 +195,29 @@ class QuadCriterion_MRS:
             print(f"Total time needed for {method} :", round(res.time, 3))
         return res
 
+    def sample(self, n_samples=16, seed=0, maximum_iterations=10, tolerance=1e-12, value_init=0.5, perturbations=None, callback=None):
+        """Posterior samples of this criterion read as a Gaussian log-density (not in fusion_CT.py): forwards to
+        ``model_spectro.sample_posterior`` with this criterion's data, weights and hyper-parameters and ``run_method``'s start,
+        and returns its ``PosteriorResult`` (``x_map`` is what ``run_method("lcg", maximum_iterations)`` returns).  ``ValueError``
+        unless the criterion is quadratic with the separated differences and has no imager term."""
+        assert isinstance(self.mu_reg, (int, float))
+        if self.delta is not None or self.data_delta is not None:
+            raise ValueError("sample: the posterior of a Huber prior (delta) or a robust data term (data_delta) is not Gaussian")
+        if self.gradient != "separated":
+            raise ValueError("sample draws the prior's noise through the separated differences: gradient must be 'separated'")
+        if self.imager is not None:
+            raise ValueError("sample does not perturb the imager data term")
+        init = np.ones(self.shape_of_output) * value_init if isinstance(value_init, (int, float)) else value_init
+        assert init.shape == self.shape_of_output
+        prior_before = self.model_spectro.get_prior()
+        self.model_spectro.set_prior(self.gradient)
+        try:
+            return self.model_spectro.sample_posterior(self.y_spectro, mu=self.mu_spectro, mu_reg=self.mu_reg, n_samples=n_samples,
+                                                       seed=seed, x0=init, max_iter=maximum_iterations, tol=tolerance,
+                                                       weights=self.weights, perturbations=perturbations, callback=callback)
+        finally:
+            self.model_spectro.set_prior(prior_before)
+
     def get_crit_val(self, x_hat):
         """(mu |y - A x|^2 + mu_reg (|Dr x|^2 + |Dc x|^2)) / 2   (fusion_CT.py:242-265); with ``delta``
         mu |y - A x|^2 / 2 + mu_reg sum phi(Dr x) + phi(Dc x), phi the Huber potential (that criterion's limit delta -> inf).

@@ -420,6 +420,47 @@ class spectroSigRLSCT(DataWeights, _pot.Potentials, LinOp):
         with self.installed_weights(weights), with_imager:
             return _lib.solve(self, self._L.surfh_cg_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
 
+    # ---- posterior sampling (surfh_amd.posterior; include/surfh_amd.h: surfh_cg_sample) ------------------------------------------
+    def sample_posterior(self, data, mu=1.0, mu_reg=0.0, n_samples=16, seed=0, x0=None, max_iter=10, tol=1e-12, refresh=50,
+                         weights=None, perturbations=None, callback=None):
+        """Per-pixel uncertainty of the maps ``cg`` returns.  The criterion of ``cg`` is the negative log of the Gaussian posterior
+        ``p(x | y) ~ exp(-x^T Q x / 2 + b^T x)``, ``Q = mu A^T W A + mu_reg (Dr^T Dr + Dc^T Dc)``, ``b = mu A^T W y``: the precision
+        is ``Q`` as ``cg`` defines it, a statistical statement once ``weights = 1 / sigma^2`` (``mu = 1``).  Runs ``cg`` (same
+        arguments, same bits), then ``n_samples`` perturbed solves ``Q x~ = b~``, ``b~ ~ N(b, Q)`` -- each as the solve of its deviation
+        ``Q e = b~ - b`` from zero, ``x~ = x_map + e`` -- with the same ``max_iter``, ``tol`` and ``refresh``, and returns a ``PosteriorResult``: ``x_map``, ``mean``, ``cov``
+        ``[T, T, Na, Nb]``, ``std``, ``nit``, ``grad_norm`` (of the unperturbed solve) and ``rr_worst``, the largest final r.r over
+        the sample solves.  A sample is exact only if its solve converges: CG stopped at ``max_iter`` leaves the slowly converging
+        directions under-dispersed and ``std`` is then a lower bound -- compare ``rr_worst`` with the ``rr[0]`` the callback sees.
+
+        ``seed``: the counter-based generator's 64-bit key; the same seed gives the same bits, whatever ran before.
+        ``weights``: as in ``cg``.  ``perturbations=(eps_y [K, osize], eps_r [K, isize], eps_c [K, isize])``: the standard normal
+        vectors of every draw instead of the generator's (what makes a float64 comparison possible).
+        ``callback(k, rr, x)``: every finished sample -- its index, the r.r trace of its solve, ``x~`` ``[T, Na, Nb]``; a truthy
+        return aborts the run (``RuntimeError``).  ``ValueError`` for a model without templates, the joint prior, an active
+        imager term, ``mu <= 0``, ``mu_reg < 0`` and ``n_samples < 2``."""
+        from . import posterior
+        return posterior.sample_posterior(self, data, mu, mu_reg, n_samples, seed, x0, max_iter, tol, refresh, weights, perturbations,
+                                          callback)
+
+    def cube_std(self, cov, planes=None):
+        """``sqrt(s_lambda^T Sigma s_lambda)`` per pixel: the standard deviation of the cube's ``planes`` (None: all) under the
+        maps' covariance ``cov`` ``[T, T, Na, Nb]`` of ``sample_posterior`` (NumPy, on the host)."""
+        from . import posterior
+        return posterior.cube_std(cov, self.templates, planes)
+
+    def randn_dev(self, out_t, n: int, seed: int = 0, stream: int = 0, sample: int = 0):
+        """``n`` standard normals of (seed, stream, sample, element index) into a device tensor (include/surfh_amd.h: surfh_randn_dev)."""
+        _lib.check(self._L.surfh_randn_dev(self._plan, _ptr(out_t), int(n), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(stream), int(sample)))
+
+    def po_data_dev(self, y_t, w_t, eps_t, out_t, n: int, mu: float):
+        """out = y + eps / sqrt(mu w) where w > 0 (``w_t=None``: 1), the bits of y elsewhere; device vectors of ``n`` floats."""
+        _lib.check(self._L.surfh_po_data_dev(self._plan, _ptr(y_t), None if w_t is None else _ptr(w_t), _ptr(eps_t), int(n), float(mu),
+                                             _ptr(out_t)))
+
+    def po_prior_dev(self, er_t, ec_t, out_t, mu_reg: float):
+        """out = sqrt(mu_reg) (Dr^T eps_r + Dc^T eps_c) on device maps ``[T, Na, Nb]``."""
+        _lib.check(self._L.surfh_po_prior_dev(self._plan, _ptr(er_t), _ptr(ec_t), float(mu_reg), _ptr(out_t)))
+
     def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, delta=None, weights=None,
              data_delta=None, potential="huber", data_potential="huber", imager=None):
         """Device-resident 3MG (qmm.mmmg restated for quadratic objectives; the reference's ``method='mmmg'``,
