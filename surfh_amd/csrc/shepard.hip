@@ -9,15 +9,19 @@
 //       num += w * v_k;  den += w                                          float32 accumulators
 //   out[g] = den != 0 ? num / den : 0
 // Every float operation is written with an explicit rounding intrinsic so that the compiler cannot contract a multiply and
-// an add into one FMA: the include / exclude decision of each pair is the reference's, bit for bit.
+// an add into one FMA, and the root is taken in double and stored to a float as the reference's generated C does (which
+// rounds correctly; the float intrinsic __fsqrt_rn is the hardware's approximate root, an ulp off for some arguments):
+// the include / exclude decision of each pair is the reference's, bit for bit.
 //
 // Instead of the reference's O(grid x samples) double loop, the samples of each segment are binned into square cells of
 // the scaled (alpha, lambda) plane with side h >= cutoff * (1 + 1/64) (a counting sort keyed by segment and cell), and a
 // query point tests only the samples of the 3 x 3 cells around its own.  The cell coordinates are computed in double
 // from the float coordinates, so a pair the reference accepts (|scaled difference| <= cutoff * (1 + 1e-6) per axis) is
-// never more than one cell apart: completeness does not depend on rounding at cell edges.  Within a cell the samples are
-// kept in input order, so the result is deterministic; the summation order differs from the reference's (cells, not
-// input order), which moves the float sums by a few ulps.
+// never more than one cell apart: completeness does not depend on rounding at cell edges.  Within every cell, whatever
+// its length, the samples are put back in input order (k_cell_sort for short cells, k_long_sort for the others), so the
+// result does not depend on the order in which the binning's atomics arrive: the same input gives the same bits, alone
+// or inside a batch.  The summation order differs from the reference's (cells, not input order), which moves the float
+// sums by a few ulps.
 //
 // One launch serves any number of segments (every slit of one or several exposures).  A segment has its own samples,
 // its own query points and its own inv_ares / inv_lres.  Query points are either a separable grid
@@ -36,7 +40,15 @@
 namespace {
 
 constexpr int TPB = 256;
-constexpr int SORT_MAX = 64;         // cells longer than this keep their samples in arrival order (see k_cell_sort)
+constexpr int LONG_TPB = 1024;
+// Cells of up to SORT_MAX samples are put in input order by one thread each (insertion sort, at most SORT_MAX^2 / 2 = 2048
+// moves: real slits hold 5-25 samples per cell).  k_cell_sort lists the longer ones and k_long_sort gives each of them a
+// workgroup: a bottom-up merge sort in which every element finds its place in the merged run by a binary search of the
+// sibling run.  For a cell of n samples that is ceil(log2 n) passes of n / LONG_TPB elements per thread and at most
+// log2 n probes each, n log2^2 n / LONG_TPB steps per thread: 12 passes x 4 elements x 12 probes, about 600 steps, for
+// n = 4096, and about 2e5 steps if all 5e5 samples of a full exposure fell into one cell (tens of milliseconds).  Nothing
+// grows as n^2.  An exposure without a long cell pays one counter in k_scan and one comparison per cell.
+constexpr int SORT_MAX = 64;
 
 thread_local std::string g_shep_err;
 int sfail(const char *fmt, ...) {
@@ -154,7 +166,10 @@ __global__ void k_scan(const int *__restrict__ count, int *__restrict__ start, i
     }
     int run = part[t] - sum;
     for (int i = b; i < e; ++i) { start[i] = run; run += count[i]; }
-    if (t == 1023) start[n] = part[1023];
+    if (t == 1023) {
+        start[n] = part[1023];
+        start[n + 1] = 0;                           // the number of long cells, counted by k_cell_sort
+    }
 }
 
 __global__ void k_scatter(const int *__restrict__ cell, long n_pts, const int *__restrict__ start, int *__restrict__ fill,
@@ -166,18 +181,50 @@ __global__ void k_scatter(const int *__restrict__ cell, long n_pts, const int *_
     order[start[c] + atomicAdd(&fill[c], 1)] = (int)i;
 }
 
-// restore input order inside each cell (the atomics above hand out slots in any order)
-__global__ void k_cell_sort(const int *__restrict__ start, int n_cells, int *__restrict__ order) {
+// restore input order inside each cell (the atomics above hand out slots in any order); a cell of more than SORT_MAX
+// samples is appended to long_cells[] (any order), counted in start[n_cells + 1], and left to k_long_sort
+__global__ void k_cell_sort(int *__restrict__ start, int n_cells, int *__restrict__ order, int *__restrict__ long_cells) {
     const int c = blockIdx.x * TPB + threadIdx.x;
     if (c >= n_cells) return;
     const int b = start[c], e = start[c + 1];
-    if (e - b > SORT_MAX) return;
+    if (e - b > SORT_MAX) {
+        long_cells[atomicAdd(&start[n_cells + 1], 1)] = c;
+        return;
+    }
     for (int i = b + 1; i < e; ++i) {
         const int v = order[i];
         int j = i - 1;
         while (j >= b && order[j] > v) { order[j + 1] = order[j]; --j; }
         order[j + 1] = v;
     }
+}
+
+// input order inside one long cell per block: bottom-up merge sort between order[b, b + n) and the same range of tmp[].
+// The sample indices of a cell are distinct, so an element's place in the merged pair of runs is its offset in its own
+// run plus the number of smaller elements in the sibling run.
+__global__ __launch_bounds__(LONG_TPB) void k_long_sort(const int *__restrict__ start, const int *__restrict__ long_cells,
+                                                        int *order, int *tmp) {
+    const int c = long_cells[blockIdx.x];
+    const long b = start[c], n = start[c + 1] - b;
+    int *src = order + b, *dst = tmp + b;
+    for (long w = 1; w < n; w <<= 1) {
+        for (long i = threadIdx.x; i < n; i += LONG_TPB) {
+            const long pair = i / (2 * w) * (2 * w), mid = min(pair + w, n);
+            const bool left = i < mid;
+            long lo = left ? mid : pair, hi = left ? min(mid + w, n) : mid;      // the sibling run
+            const long sib = lo;
+            const int v = src[i];
+            while (lo < hi) {
+                const long m = (lo + hi) >> 1;
+                if (src[m] < v) lo = m + 1; else hi = m;
+            }
+            dst[pair + (i - (left ? pair : mid)) + (lo - sib)] = v;
+        }
+        __syncthreads();
+        int *t = src; src = dst; dst = t;
+    }
+    if (src != order + b)
+        for (long i = threadIdx.x; i < n; i += LONG_TPB) dst[i] = src[i];
 }
 
 __global__ void k_gather(const int *__restrict__ order, int n, const float *__restrict__ pa, const float *__restrict__ pl,
@@ -226,7 +273,9 @@ __global__ __launch_bounds__(TPB) void k_shepard(const Seg *__restrict__ segs, c
                 const float4 pt = sorted[k];
                 const float d1 = __fmul_rn(__fsub_rn(pt.x, ga), s.inv_a);
                 const float d2 = __fmul_rn(__fsub_rn(pt.y, gl), s.inv_l);
-                const float d = __fsqrt_rn(__fadd_rn(__fmul_rn(d1, d1), __fmul_rn(d2, d2)));
+                // the reference's double sqrt stored to a float, which is the correctly rounded float root;
+                // __fsqrt_rn is the hardware's approximate root here and moves d by an ulp
+                const float d = (float)sqrt((double)__fadd_rn(__fmul_rn(d1, d1), __fmul_rn(d2, d2)));
                 const double dist = (double)d + deps;
                 if (dist <= dcut) {
                     const float df = (float)dist;
@@ -347,7 +396,7 @@ int surfh_shepard(int32_t n_seg, const int64_t *pt_off, const float *pt_alpha, c
     int *cell, *count, *start, *fill, *order;
     float4 *sorted;
     S_OK(mem.alloc(&cell, n_pts)); S_OK(mem.alloc(&count, n_cells)); S_OK(mem.alloc(&fill, n_cells));
-    S_OK(mem.alloc(&start, n_cells + 1)); S_OK(mem.alloc(&order, n_pts)); S_OK(mem.alloc(&sorted, n_pts));
+    S_OK(mem.alloc(&start, n_cells + 2)); S_OK(mem.alloc(&order, n_pts)); S_OK(mem.alloc(&sorted, n_pts));
     S_OK(hipMemsetAsync(count, 0, std::max(n_cells, 1L) * sizeof(int), st));
     S_OK(hipMemsetAsync(fill, 0, std::max(n_cells, 1L) * sizeof(int), st));
     if (n_pts) {
@@ -361,13 +410,18 @@ int surfh_shepard(int32_t n_seg, const int64_t *pt_off, const float *pt_alpha, c
         S_OK(hipGetLastError());
     }
     if (n_cells) {
-        k_cell_sort<<<blocks(n_cells), TPB, 0, st>>>(start, (int)n_cells, order);
+        k_cell_sort<<<blocks(n_cells), TPB, 0, st>>>(start, (int)n_cells, order, fill);    // fill[] is free again: the list
         S_OK(hipGetLastError());
     }
     // order[] holds the binned samples only (non-finite ones are left out): gather that many
-    int n_binned = 0;
-    S_OK(hipMemcpyAsync(&n_binned, start + n_cells, sizeof(int), hipMemcpyDeviceToHost, st));
+    int tail[2] = {0, 0};                            // binned samples, long cells
+    S_OK(hipMemcpyAsync(tail, start + n_cells, sizeof tail, hipMemcpyDeviceToHost, st));
     S_OK(hipStreamSynchronize(st));
+    const int n_binned = tail[0], n_long = tail[1];
+    if (n_long) {                                    // cell[] is free after k_scatter: the merge sort's second buffer
+        k_long_sort<<<n_long, LONG_TPB, 0, st>>>(start, fill, order, cell);
+        S_OK(hipGetLastError());
+    }
     if (n_binned) {
         k_gather<<<blocks(n_binned), TPB, 0, st>>>(order, n_binned, da, dl, dv, sorted);
         S_OK(hipGetLastError());

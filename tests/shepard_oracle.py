@@ -21,10 +21,11 @@ def pair_distance(a, l, qa, ql, alpha_res, lambda_res, epsilon=1e-6):
     a, l = np.asarray(a, f32).ravel(), np.asarray(l, f32).ravel()
     qa, ql = np.asarray(qa, f32).ravel(), np.asarray(ql, f32).ravel()
     ia, il = inv_res(alpha_res), inv_res(lambda_res)
-    d1 = (a[None, :] - qa[:, None]) * ia
-    d2 = (l[None, :] - ql[:, None]) * il
-    d = np.sqrt(d1 * d1 + d2 * d2)
-    return d.astype(f64) + f64(f32(epsilon))
+    with np.errstate(invalid="ignore", over="ignore"):       # non-finite coordinates give inf or NaN: no neighbour
+        d1 = (a[None, :] - qa[:, None]) * ia
+        d2 = (l[None, :] - ql[:, None]) * il
+        d = np.sqrt(d1 * d1 + d2 * d2)
+        return d.astype(f64) + f64(f32(epsilon))
 
 
 def neighbour_mask(a, l, qa, ql, alpha_res, lambda_res, pixel_cutoff, epsilon=1e-6):
@@ -40,21 +41,28 @@ def replica(a, l, v, qa, ql, p, pixel_cutoff, alpha_res, lambda_res, alpha=2.0, 
         df = dist.astype(f32).astype(f64)
         value = (-f64(f32(alpha)) * np.exp(f64(f32(p)) * np.log(df))).astype(f32)
         w = np.where(m, np.exp(value.astype(f64)).astype(f32).astype(f64), 0.0)
-    num = w @ np.asarray(v, f32).astype(f64).ravel()
-    den = w.sum(axis=1)
-    out = np.where(den != 0, num / np.where(den != 0, den, 1.0), 0.0)
+        num = _masked_sum(w, v, m)
+        den = w.sum(axis=1)
+        out = np.where(den != 0, num / np.where(den != 0, den, 1.0), 0.0)
     return out, m.sum(axis=1)
+
+
+def _masked_sum(w, v, m):
+    """sum over the neighbours only: a NaN or infinite value outside the cutoff takes no part, as in the reference
+    (0 * NaN inside a matrix product would spread it to every query point)."""
+    return np.where(m, w * np.asarray(v, f32).astype(f64).ravel()[None, :], 0.0).sum(axis=1)
 
 
 def checker(a, l, v, qa, ql, mask, p, pixel_cutoff, alpha_res, lambda_res, alpha=2.0, epsilon=1e-6):
     """float64 brute force over the neighbour set ``mask`` (from ``neighbour_mask``): sum w v / sum w, w = exp(-alpha d^p)."""
     a, l, qa, ql = (np.asarray(x, f32).astype(f64).ravel() for x in (a, l, qa, ql))
-    d = np.hypot((a[None, :] - qa[:, None]) / f64(f32(alpha_res)),
-                 (l[None, :] - ql[:, None]) / f64(f32(lambda_res))) + epsilon
-    w = np.where(mask, np.exp(-alpha * d ** p), 0.0)
-    den = w.sum(axis=1)
-    num = w @ np.asarray(v, f32).astype(f64).ravel()
-    return np.where(den != 0, num / np.where(den != 0, den, 1.0), 0.0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = np.hypot((a[None, :] - qa[:, None]) / f64(f32(alpha_res)),
+                     (l[None, :] - ql[:, None]) / f64(f32(lambda_res))) + epsilon
+        w = np.where(mask, np.exp(-alpha * d ** p), 0.0)
+        den = w.sum(axis=1)
+        num = _masked_sum(w, v, mask)
+        return np.where(den != 0, num / np.where(den != 0, den, 1.0), 0.0)
 
 
 def kernel_cases(z):

@@ -1,6 +1,7 @@
 """Host side of the distortion correction (surfh_amd.preprocessing): labelling and centroid sort against the reference's
 fixture, the float32 pair-test replica and the float64 checker against the reference's kernel, the slit reorder helper
 and the driver's command line.  No GPU."""
+import json
 import os
 import subprocess
 import sys
@@ -64,6 +65,23 @@ def test_fixture_covers_the_cases(z):
     written = [np.count_nonzero(np.abs(z[f"m{m}_slices"]).sum(axis=(1, 2))) for m in range(3)]
     assert z["exp_oshape"][1] == 5 and written == [3, 3, 3]
     assert float(z["ref_slit_seconds"]) > 0
+
+
+def test_edges_fixture_covers_the_cases():
+    """tests/golden/shepard_edges.npz (make_golden_shepard_edges.py) holds what shepard.npz leaves out: parameters other
+    than p in {1, 2}, alpha = 2, epsilon = 1e-6, non-finite inputs and outputs, cutoffs one ulp apart.  Arrays only."""
+    import shepard_cases as sc
+    e = np.load(sc.GOLDEN_EDGES)                         # allow_pickle is off: an object array would raise below
+    assert os.path.getsize(sc.GOLDEN_EDGES) < os.path.getsize(so.GOLDEN) and len(e["raised"]) == 0
+    cases = [sc.load_reference(e, str(n)) for n in e["names"]]
+    assert len(cases) == 28 and all(c["out"].shape == c["ga"].shape for c in cases)
+    assert {c["p"] for c in cases} == {0.5, 2.0, 3.0} and {c["alpha"] for c in cases} == {0.5, 2.0, 8.0}
+    assert {c["eps"] for c in cases} == {0.0, 1e-6, 1e-3} and any(c["ares"] < 0 for c in cases)
+    assert len({c["cutoff"] for c in cases}) >= 9
+    assert any(np.isnan(c["out"]).any() for c in cases) and any(np.isinf(c["out"]).any() for c in cases)
+    assert any(not np.isfinite(c["a"]).any() or not np.isfinite(c["l"]).any() or
+               not (np.isfinite(c["a"]) & np.isfinite(c["l"])).any() for c in cases)
+    assert json.loads(str(e["meta"]))["compiled_with"].startswith("gcc -O3")
 
 
 def test_reorder_corrected_slices():
