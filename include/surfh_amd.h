@@ -161,6 +161,40 @@ int surfh_cg_cb(surfh_plan *plan, const float *y, double mu, double mu_reg, cons
                 int32_t max_iter, double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit,
                 surfh_cg_callback callback, void *user);
 
+/* ---- template refinement: the other half-step of the bilinear model y = A(S) x -- hold the maps x, solve for the spectra S ----
+ * Joint criterion  J(x, S) = [ mu (y - A(S) x)^T W (y - A(S) x) + mu_reg (|Dr x|^2 + |Dc x|^2) + mu_spec |D_l S|^2 ] / 2,  D_l the first
+ * difference along the wavelength with open ends, W the plan's data weights.  For fixed x it is quadratic in S; A_x : S -> A(S) x is
+ * the forward model with S in the templates' place.  Templates and their gradients are [T][Lc] (n_templates x n_lambda) in cube-plane
+ * order; T and Lc are fixed at plan creation.  A plane no channel reads gets a gradient of exactly 0: with mu_spec = 0 it keeps its
+ * starting value.  Spectral features narrower than the detector's wavelength sampling are not recoverable from the data.
+ *
+ * surfh_set_templates: the plan's templates from now on -- uploaded with the rounding and the padding of plan creation; Model_WCT's
+ *   explicit Hessian is dropped and rebuilt on its next use.  Fails while an imager is attached (its transfer functions were built
+ *   from the templates: detach it, set the templates, attach it again).  surfh_get_templates: the templates as given last.         */
+int surfh_set_templates(surfh_plan *plan, const double *templates /*[T][Lc]*/);
+int surfh_get_templates(const surfh_plan *plan, double *templates /*[T][Lc]*/);
+/* y = A_x S: the forward model on `maps` with `templates` in place of the plan's, which are untouched afterwards                     */
+int surfh_forward_templates(surfh_plan *plan, const float *maps, const double *templates, float *y);
+/* g [T][Lc] = A_x^T u: the transpose of the above.  g[t][l] = sum over pixels of maps_t times the cube-space adjoint of u at plane l,
+ * formed in the Fourier domain as a sum over frequency bins (float64 sums in a fixed order: the same inputs give the same bits);
+ * plans on the dense transforms (verification plans among them) and plans with more than 4 templates sum over pixels instead.       */
+int surfh_adjoint_templates(surfh_plan *plan, const float *maps, const float *u, float *g);
+/* the same two on device buffers, asynchronous on the plan's stream; templates_dev and g_dev are floats [T][Lc]                       */
+int surfh_forward_templates_dev(surfh_plan *plan, const float *maps_dev, const float *templates_dev, float *y_dev);
+int surfh_adjoint_templates_dev(surfh_plan *plan, const float *maps_dev, const float *u_dev, float *g_dev);
+/* Linear CG (the loop, stopping test, trace, refresh and callback contract of surfh_cg; the size in the tolerance is T Lc) on
+ *     (mu A_x^T W A_x + mu_spec D_l^T D_l) S = mu A_x^T W y
+ * from s0 [T][Lc] (NULL: the plan's templates) to s_out.  The plan's own templates are back in place on every exit -- normal return,
+ * error, callback stop -- and while the callback runs, which receives the iterate [T][Lc].  Fails while an imager is attached.       */
+int surfh_cg_templates(surfh_plan *plan, const float *y, const float *maps, double mu, double mu_spec, const float *s0,
+                       int32_t max_iter, double tol, int32_t refresh, float *s_out, double *grad_norm, int32_t *nit);
+int surfh_cg_templates_cb(surfh_plan *plan, const float *y, const float *maps, double mu, double mu_spec, const float *s0,
+                          int32_t max_iter, double tol, int32_t refresh, float *s_out, double *grad_norm, int32_t *nit,
+                          surfh_cg_callback callback, void *user);
+/* out[0] = J(maps, the plan's templates); out[1] = (y - A x)^T W (y - A x), out[2] = x^T P x with P the plan's spatial prior
+ * (surfh_set_prior; |Dr x|^2 + |Dc x|^2 by default), out[3] = |D_l S|^2: float64 sums on the device                                  */
+int surfh_joint_criterion(surfh_plan *plan, const float *y, const float *maps, double mu, double mu_reg, double mu_spec, double *out);
+
 /* ---- posterior sampling: per-pixel uncertainty of the maps surfh_cg returns (perturbation-optimisation, Orieux, Feron &
  * Giovannelli 2012) ----
  * Convention: the criterion of surfh_cg is the negative log of the Gaussian posterior

@@ -30,6 +30,12 @@ files ``robust_weights.npy``, the weights ``[osize]`` in (0, 1] the last iterate
 (surfh_amd/potentials.py).  With another potential than Huber the directory's ``_huber_<D>`` becomes ``_<kind>_<D>``, its
 ``_rob_<D>`` ``_rob_<kind>_<D>``, and a voxel-wise run under another spectral potential gains ``_spec_<kind>``.
 
+``--refine_templates K --mu_spec M [--tpl_iter n]`` (``--method lcg`` only) refines the spectra as well: K rounds of ``-ni`` CG
+iterations on the maps and ``n`` (default 10) on the templates, under the first-difference prior of weight ``M`` along the wavelength
+(surfh_amd/fusion.py: refine_templates).  Results go under ``..._tpl_<K>/``: ``res_x.npy``, ``res_templates.npy``,
+``templates_start.npy`` and the joint criterion after every half-step in ``criterion.npy``.  Spectral features narrower than the
+detector's wavelength sampling are not recovered: the data do not hold them.
+
 The FITS reader needs astropy (FITS I/O is outside the hot path and not rebuilt here); when it is not importable the
 same arrays may be given as ``Filtered_slices/<band>_<k>.npz`` with fields ``data`` (raveled ``[Ldet, S, a_out]`` as in
 the FITS primary HDU), ``PA_V3``, ``TARG_RA``, ``TARG_DEC``.  ``--synthetic`` builds one of the benchmark problems
@@ -136,12 +142,13 @@ def create_model(sotf, templates, origin_alpha_axis, origin_beta_axis, wavel_axi
 
 
 def result_dir_name(method, n_channels, n_templates, niter, hyper_parameter, scale_data, delta=None, voxel=False, weighted=False,
-                    data_delta=None, potential='huber', data_potential='huber', spec_potential='huber', imager=0, samples=0):
+                    data_delta=None, potential='huber', data_potential='huber', spec_potential='huber', imager=0, samples=0,
+                    refine=0):
     """main_fusion.py:182; with a Huber threshold `delta` (not in the reference) `_huber_<delta>` is appended, `_vox` for a
     voxel-wise reconstruction, `_wgt` for a run under data weights, and `_rob_<data_delta>` for a robust data term.  Another
     potential than Huber puts its name in Huber's place (`_<kind>_<delta>`, `_rob_<kind>_<data_delta>`; `_spec_<kind>` for the
     spectral prior of a voxel-wise run); with Huber the names are unchanged.  `_img_<F>` follows for a run with an imager
-    data term of F filters, `_po_<K>` for a run that draws K posterior samples."""
+    data term of F filters, `_po_<K>` for a run that draws K posterior samples, `_tpl_<K>` for K rounds of template refinement."""
     name = f'{method}_MC_{n_channels}_MO_4_Temp_{n_templates}_nit_{str(niter)}_mu_{str("{:.2e}".format(hyper_parameter))}_SD_{scale_data}'
     if delta is not None:
         name += f'_{potential}_{delta:.2e}'
@@ -157,6 +164,8 @@ def result_dir_name(method, n_channels, n_templates, niter, hyper_parameter, sca
         name += f'_img_{imager}'
     if samples:
         name += f'_po_{samples}'
+    if refine:
+        name += f'_tpl_{refine}'
     return name + '/'
 
 
@@ -259,6 +268,28 @@ def reconstruction_method(spectro_model, ndata, templates, result_path, hyper_pa
     return res, path
 
 
+def template_refinement(spectro_model, ndata, templates, result_path, hyper_parameter, niter, method, scale_data, rounds, mu_spec,
+                        tpl_iter, weights=None):
+    """`rounds` rounds of (`niter` CG iterations on the maps, `tpl_iter` on the spectra) by surfh_amd.fusion.refine_templates, data
+    weight 1: res_x.npy (maps), res_templates.npy and templates_start.npy [T, Lc], and in criterion.npy the joint criterion at the
+    start and after every half-step.  Features narrower than the detector's wavelength sampling stay what the start had."""
+    from surfh_amd.fusion import refine_templates
+    path = pathlib.Path(result_path) / result_dir_name(method, len(spectro_model.instrs), templates.shape[0], niter, hyper_parameter,
+                                                       scale_data, weighted=weights is not None, refine=rounds)
+    path.mkdir(parents=True, exist_ok=True)
+    res = refine_templates(spectro_model, ndata, 1., hyper_parameter, mu_spec, rounds, niter, tpl_iter, weights=weights)
+    for k, j in enumerate(res.criterion):
+        print(f"half-step {k}: joint criterion {j:.6e}")
+    print(f"Results save in {path}")
+    np.save(path / 'res_x.npy', res.x)
+    np.save(path / 'res_templates.npy', res.templates)
+    np.save(path / 'templates_start.npy', res.templates_start)
+    np.save(path / 'criterion.npy', res.criterion)
+    if weights is not None:
+        np.save(path / 'weights.npy', weights)
+    return res, path
+
+
 def synthetic_problem(name, npix):
     """One of the benchmark problems + simulated data  y = A maps + noise  (SURVEY.md 8d)."""
     if name == 'small':
@@ -313,10 +344,30 @@ def synthetic_problem(name, npix):
               help='Draw that many posterior samples after the solve (needs --method lcg; at least 2) and store their mean, '
                    'standard deviation and covariance per pixel. Default: none.')
 @click.option('--seed', default=None, type=int, help='Seed of the posterior samples (--samples). Default: 0.')
+@click.option('--refine_templates', 'refine_rounds', default=0, type=int,
+              help='Refine the templates too: that many rounds of (-ni CG iterations on the maps, --tpl_iter on the spectra); '
+                   'needs --method lcg. Default: the templates stay as given.')
+@click.option('--mu_spec', default=None, type=float, help='Weight of the first-difference prior along the wavelength of the spectra '
+                                                          '(--refine_templates). Default: 0.')
+@click.option('--tpl_iter', default=None, type=int, help='CG iterations of a template half-step (--refine_templates). Default: 10.')
 def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, method, verbose, synthetic, device, checkpoint_every=0,
          resume=None, delta=None, voxel=False, spec_reg=1., spec_delta=1., weights_file=None, mask_nan=False, data_delta=None,
          potential='huber', data_potential='huber', spec_potential='huber', imager_filters=0, mu_imager=1., imager_decim=1,
-         samples=0, seed=None):
+         samples=0, seed=None, refine_rounds=0, mu_spec=None, tpl_iter=None):
+    if refine_rounds:
+        if refine_rounds < 1:
+            raise click.BadParameter(f'at least one round, not {refine_rounds}', param_hint='--refine_templates')
+        if method != 'lcg':
+            raise click.UsageError('--refine_templates alternates two linear CG solves; use it with --method lcg')
+        if voxel or imager_filters or samples or delta is not None or data_delta is not None or checkpoint_every or resume:
+            raise click.UsageError('--refine_templates runs the quadratic criterion on the maps and the spectra alone: no --voxel, '
+                                   '--imager, --samples, --delta, --data_delta or checkpoints')
+        if mu_spec is not None and not (mu_spec >= 0 and np.isfinite(mu_spec)):
+            raise click.BadParameter(f'must be finite and >= 0, not {mu_spec}', param_hint='--mu_spec')
+        if tpl_iter is not None and tpl_iter < 1:
+            raise click.BadParameter(f'at least one iteration, not {tpl_iter}', param_hint='--tpl_iter')
+    elif mu_spec is not None or tpl_iter is not None:
+        raise click.UsageError('--mu_spec and --tpl_iter belong to --refine_templates')
     if samples:
         if method != 'lcg':
             raise click.UsageError('--samples draws from the Gaussian posterior of the quadratic criterion; use it with --method lcg')
@@ -419,6 +470,11 @@ def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, meth
         voxel_reconstruction(model, ndata, paths["result_path"], hyper_parameter, 1. if delta is None else delta, spec_reg, spec_delta,
                              niter, method, scale_data, weights=weights, data_delta=data_delta, potential=potential,
                              data_potential=data_potential, spec_potential=spec_potential)
+        model.close()
+        return
+    if refine_rounds:
+        template_refinement(model, ndata, templates, paths["result_path"], hyper_parameter, niter, method, scale_data, refine_rounds,
+                            mu_spec or 0., tpl_iter or 10, weights=weights)
         model.close()
         return
     reconstruction_method(model, ndata, templates, paths["result_path"], hyper_parameter, niter, method, scale_data,

@@ -63,6 +63,8 @@ EXPORTS = [
     "surfh_profile_enable", "surfh_profile_filter", "surfh_profile_count", "surfh_profile_get", "surfh_profile_reset", "surfh_debug_copy",
     "surfh_debug_dims", "surfh_gemm_selftest", "surfh_gemm_selftest_ksteps", "surfh_gemm_selftest_ms", "surfh_klist_classify", "surfh_mm_step2",
     "surfh_shepard", "surfh_shepard_last_error", "surfh_spectral_median", "surfh_nmf_cd", "surfh_templates_last_error",
+    "surfh_set_templates", "surfh_get_templates", "surfh_forward_templates", "surfh_adjoint_templates", "surfh_forward_templates_dev",
+    "surfh_adjoint_templates_dev", "surfh_cg_templates", "surfh_cg_templates_cb", "surfh_joint_criterion",
 ]
 
 _lib = None
@@ -192,6 +194,16 @@ def load():
     L.surfh_nmf_cd.argtypes = [c_float_p, C.c_int64, C.c_int64, C.c_int32, c_int32_p, c_float_p, c_float_p, C.c_int32,
                                C.c_double, c_int32_p, c_double_p, c_double_p, c_double_p, C.c_int32, c_float_p]
     L.surfh_templates_last_error.restype = C.c_char_p
+    L.surfh_set_templates.argtypes = [vp, c_double_p]
+    L.surfh_get_templates.argtypes = [vp, c_double_p]
+    L.surfh_forward_templates.argtypes = [vp, c_float_p, c_double_p, c_float_p]
+    L.surfh_adjoint_templates.argtypes = [vp, c_float_p, c_float_p, c_float_p]
+    for n in ("surfh_forward_templates_dev", "surfh_adjoint_templates_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, vp]
+    L.surfh_cg_templates.argtypes = [vp, c_float_p, c_float_p, C.c_double, C.c_double, c_float_p, C.c_int32, C.c_double, C.c_int32,
+                                     c_float_p, c_double_p, c_int32_p]
+    L.surfh_cg_templates_cb.argtypes = L.surfh_cg_templates.argtypes + [CG_CALLBACK, vp]
+    L.surfh_joint_criterion.argtypes = [vp, c_float_p, c_float_p, C.c_double, C.c_double, C.c_double, c_double_p]
     _lib = L
     return L
 

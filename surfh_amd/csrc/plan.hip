@@ -641,6 +641,11 @@ int surfh_plan_destroy(surfh_plan *p) {
     for (float *v : {p->im_g, p->im_xpad, p->im_xhat, p->im_zpad, p->im_zhat, p->im_io, p->im_y, p->im_w, p->im_wy}) hipFree(v);
     hipFree(p->pn_sc);
     hipFree(p->pn_part);
+    hipFree(p->tg_cidx);
+    hipFree(p->tg_pidx);
+    hipFree(p->tg_part);
+    hipFree(p->tg_keep);
+    for (float *v : p->tg_v) hipFree(v);
     for (auto &c : p->ch) {
         for (float *v : {c.W, c.Wt, c.Xs, c.Cpart, c.ymat}) hipFree(v);
         hipFree(c.W16);

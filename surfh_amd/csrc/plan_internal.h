@@ -47,6 +47,7 @@
 #include "dft_ct.h"
 #include "gemm_f32.h"
 #include "kernels.h"
+#include "tplgrad.h"
 
 namespace surfh_impl __attribute__((visibility("hidden"))) {
 
@@ -230,6 +231,17 @@ struct surfh_plan {
     double im_mu = 0.0;
     int ycm_planes = 0;                            // planes ycol_maps holds (max(T, 1); max(T, F) once an imager has been attached)
     std::vector<double> tpl_host;                  // the templates [T][Lc] as given (the imager's streamed set-up reads them)
+    // template refinement (tplgrad.h; surfh_set_templates, surfh_adjoint_templates, surfh_cg_templates), allocated by tpl_ensure:
+    // cube plane -> compact plane index [Lc] and back [LP] (-1: none), the slabs' partial sums, the plan's own templates [T][LP]
+    // while a call has others in their place (TplScope), and the solver's vectors [T][Lc] in cube-plane order: x, r, d, q, b, staging
+    int *tg_cidx = nullptr, *tg_pidx = nullptr;
+    double *tg_part = nullptr;
+    float *tg_keep = nullptr, *tg_v[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // set for the duration of one call: adjoint_dev ends in the template transpose and writes tg_out [T][Lc] (tg_maps: the maps
+    // [T][Na][Nb] on the device, read by the spatial route); forward_dev finds the maps' spectra in mhat already
+    float *tg_out = nullptr;
+    const float *tg_maps = nullptr;
+    bool tg_mhat_ready = false;
     // CG
     float *cg_x = nullptr, *cg_r = nullptr, *cg_d = nullptr, *cg_q = nullptr, *cg_b = nullptr, *cg_y = nullptr, *cg_qm = nullptr, *cg_dd = nullptr;
     float *cg_hg = nullptr;                        // surfh_mmmg_huber(_vox): -gradient of the non-quadratic criterion
@@ -323,5 +335,18 @@ int ensure_cg(surfh_plan *p);
 inline bool imager_active(const surfh_plan *p) { return p->im_g && p->im_y && p->im_mu > 0.0; }
 int imager_normal_add(surfh_plan *p, const float *v, float *q);      // q += mu_imager A_im^T W_im A_im v
 int imager_rhs_add(surfh_plan *p, float *b);                         // b += mu_imager A_im^T W_im y_im
+// template refinement: S, G [T][Lc] floats on the device in cube-plane order, maps [T][Na][Nb] on the device
+int tpl_ensure(surfh_plan *p);                                       // checks the plan (templates, channels) and allocates
+int tpl_maps_spectra(surfh_plan *p, const float *maps);              // mhat = the maps' half spectra
+int tpl_install(surfh_plan *p, const float *S);                      // p->tpl = S in the plan's compact, padded rows
+struct TplScope {                                                    // the plan's own templates come back on every exit
+    surfh_plan *p;
+    bool armed = false;
+    explicit TplScope(surfh_plan *pl) : p(pl) {}
+    int begin();
+    ~TplScope();
+};
+int tpl_normal_dev(surfh_plan *p, const float *maps, float *G);      // G = A_x^T W A_x (the installed templates)
+int tpl_adjoint_dev(surfh_plan *p, const float *maps, const float *u, float *G);       // G = A_x^T u
 
 }  // namespace surfh_impl

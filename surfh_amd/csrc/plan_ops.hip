@@ -378,14 +378,40 @@ int adjoint_tail(surfh_plan *p, const float *cube, bool acols = false) {
     return 0;
 }
 
+// The template transpose's tail (tplgrad.hip): tg_out [T][Lc] = sum over the frequency bins of conj(mhat_t) conj(sotf) rfft2(cube),
+// `cube` the adjoint's accumulator (zero outside the alpha range of the channels' tables), mhat the spectra of the maps.
+//   interleaved spectra, T <= 4: the whole half spectrum from the unfused passes without the OTF-support lists -- the fused tail
+//     never stores the last pass and the listed passes leave bins outside the support unwritten, so neither serves -- then the
+//     reduction over bins;
+//   dense transforms (verification plans among them) and T > 4: the cube-space adjoint through its OTF^T back to pixels, then the
+//     reduction over pixels against the maps themselves (tg_maps).
+int template_tail(surfh_plan *p, const float *cube) {
+    if (p->ilv && !p->dense_dft && p->T <= 4) {
+        if (rfft2_lam_ilv(p, cube, p->spec, nullptr, true, false)) return 1;
+        Prof pr(p, "tplgrad_spec");
+        LAUNCH_OK(launch_tplgrad_spec(p->stream, p->spec, p->sotf, p->mhat, p->tg_part, p->tg_cidx, p->tg_out, p->T, p->Lc, p->Na, p->Nb, p->KBP,
+                                      p->PL, (int)p->LP));
+        return 0;
+    }
+    if (rfft2_cube(p, cube, p->spec)) return 1;
+    {
+        Prof pr(p, "otf_conj_mul");
+        LAUNCH_OK(launch_otf_conj_mul(p->stream, p->spec, p->sotf, p->PL, (int)p->LP, p->ilv));
+    }
+    if (irfft2_cube(p, p->spec, p->cube)) return 1;
+    Prof pr(p, "tplgrad_pix");
+    LAUNCH_OK(launch_tplgrad_pix(p->stream, p->cube, p->tg_maps, p->tg_part, p->tg_cidx, p->tg_out, p->T, p->Lc, p->Na, p->Nb, p->NAP, (int)p->LP));
+    return 0;
+}
+
 }  // namespace
 
 // `hand_over`: the caller is the normal operator -- channels with a spectral-blur GEMM do not write y but leave the adjoint's
 // GEMM operand (fp16 pieces of ymat + row maxima) behind
 int forward_dev(surfh_plan *p, const float *x, float *y, bool hand_over) {
     hipStream_t s = p->stream;
-    if (p->spec_in) {
-        // the maps' spectra are the caller's vector: nothing to transform
+    if (p->spec_in || p->tg_mhat_ready) {
+        // the maps' spectra are the caller's vector, or the template solver has left them in mhat: nothing to transform
     } else if (p->T > 0) {
         {
             Prof pr(p, "pad_planes");
@@ -581,6 +607,7 @@ int adjoint_dev(surfh_plan *p, const float *y, float *x, bool ref, bool handed_o
                 LAUNCH_OK(launch_spmm_rows(s, ref ? c.adjRef.t : c.adjT.t, c.Xs, acc, c.nlam, 1));
         }
     }
+    if (p->tg_out) return template_tail(p, acc);      // the transpose with respect to the templates: the reduction runs over the bins
     if (adjoint_tail(p, acc, true)) return 1;
     if (p->spec_out) return 0;         // the caller's vector is the spectrum
     if (p->T > 0) {
@@ -682,6 +709,73 @@ int ensure_cg(surfh_plan *p) {
     for (float **v : {&p->cg_x, &p->cg_r, &p->cg_d, &p->cg_q, &p->cg_b})
         if (dev_alloc(v, n)) return 1;
     return 0;
+}
+
+// ---- template refinement: the operator as a function of the templates, maps held fixed (kernels: tplgrad.hip) ----
+int tpl_ensure(surfh_plan *p) {
+    if (p->T < 1) return fail("template calls need a plan with templates");
+    if (p->T > SURFH_MAX_TEMPLATES) return fail("template calls take at most %d templates (the plan has %d)", SURFH_MAX_TEMPLATES, p->T);
+    if (p->ch.empty()) return fail("plan has no channel");
+    if (p->LP % 128 != 0) return fail("internal: the plan's planes are not padded to 128");
+    if (p->tg_part) return 0;
+    std::vector<int> cidx((size_t)p->Lc, -1), pidx((size_t)p->LP, -1);
+    for (int c = 0; c < p->Lown; ++c)
+        if (p->planes[c] >= 0) { pidx[c] = p->planes[c]; cidx[p->planes[c]] = c; }
+    int *dc = nullptr, *dp = nullptr;
+    float *keep = nullptr, *v[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    double *part = nullptr;
+    auto done = [&](int rc) {
+        hipFree(dc); hipFree(dp); hipFree(keep); hipFree(part);
+        for (float *w : v) hipFree(w);
+        return rc;
+    };
+    const bool spectral = p->ilv && !p->dense_dft && p->T <= 4;
+    if (dev_upload(&dc, cidx) || dev_upload(&dp, pidx) || dev_alloc(&keep, (size_t)p->T * p->LP) ||
+        dev_alloc(&part, tplgrad_part_doubles(p->T, p->Na, p->Nb, (int)p->LP, spectral)))
+        return done(1);
+    for (float *&w : v)
+        if (dev_alloc(&w, (size_t)p->T * p->Lc)) return done(1);
+    std::swap(p->tg_cidx, dc); std::swap(p->tg_pidx, dp); std::swap(p->tg_keep, keep);
+    for (int i = 0; i < 6; ++i) std::swap(p->tg_v[i], v[i]);
+    std::swap(p->tg_part, part);       // last: the mark of a complete set
+    return done(0);
+}
+int tpl_maps_spectra(surfh_plan *p, const float *maps) {
+    {
+        Prof pr(p, "pad_planes");
+        LAUNCH_OK(launch_pad_planes(p->stream, maps, p->maps_pad, p->T, p->Na, p->Nb, p->NAP, p->NBP));
+    }
+    return rfft2_planes(p, p->maps_pad, p->mhat, p->T);
+}
+int tpl_install(surfh_plan *p, const float *S) {
+    Prof pr(p, "tpl_pack");
+    LAUNCH_OK(launch_tpl_pack(p->stream, S, p->tg_pidx, p->tpl, p->T, p->Lc, (int)p->LP));
+    return 0;
+}
+int TplScope::begin() {
+    HIP_OK(hipMemcpyAsync(p->tg_keep, p->tpl, (size_t)p->T * p->LP * sizeof(float), hipMemcpyDeviceToDevice, p->stream));
+    armed = true;
+    return 0;
+}
+TplScope::~TplScope() {
+    p->tg_out = nullptr; p->tg_maps = nullptr; p->tg_mhat_ready = false;
+    if (armed) hipMemcpyAsync(p->tpl, p->tg_keep, (size_t)p->T * p->LP * sizeof(float), hipMemcpyDeviceToDevice, p->stream);
+}
+namespace {
+struct TplOut {                        // adjoint_dev ends in the template transpose for the duration of one call
+    surfh_plan *p;
+    TplOut(surfh_plan *pl, const float *maps, float *G) : p(pl) { p->tg_maps = maps; p->tg_out = G; }
+    ~TplOut() { p->tg_out = nullptr; p->tg_maps = nullptr; }
+};
+}  // namespace
+int tpl_adjoint_dev(surfh_plan *p, const float *maps, const float *u, float *G) {
+    if (!p->tg_mhat_ready && tpl_maps_spectra(p, maps)) return 1;
+    TplOut out(p, maps, G);
+    return adjoint_dev(p, u, nullptr, false);
+}
+int tpl_normal_dev(surfh_plan *p, const float *maps, float *G) {
+    TplOut out(p, maps, G);            // the forward half leaves the maps' spectra in mhat, where the tail reads them
+    return normal_halves(p, maps, nullptr);
 }
 
 }  // namespace surfh_impl
@@ -995,6 +1089,77 @@ int surfh_maps_to_cube(surfh_plan *p, const double *templates, int32_t T, int32_
 }
 int surfh_cube_to_maps(surfh_plan *p, const double *templates, int32_t T, int32_t L, const float *cube, float *maps) {
     return lmm_host(p, templates, T, L, cube, maps, false);
+}
+
+// ---- the templates as plan state, and as the argument of the operator (template refinement) ----
+int surfh_get_templates(const surfh_plan *p, double *tpl) {
+    if (!p || !tpl) return fail("null argument");
+    if (p->T < 1) return fail("the plan has no templates");
+    std::copy(p->tpl_host.begin(), p->tpl_host.end(), tpl);
+    return 0;
+}
+int surfh_set_templates(surfh_plan *p, const double *tpl) {
+    if (!p || !tpl) return fail("null argument");
+    if (p->T < 1) return fail("the plan has no templates: their number and length are fixed at plan creation");
+    if (p->im_g)
+        return fail("set_templates: an imager is attached, and its transfer functions G[f,t,k] were built from the templates: detach it "
+                    "(surfh_set_imager(plan, NULL)), set the templates, then attach the imager again");
+    const size_t n = (size_t)p->T * p->Lc;
+    for (size_t i = 0; i < n; ++i)
+        if (!(std::fabs(tpl[i]) <= FLT_MAX)) return fail("set_templates: template %ld has %g at plane %ld: templates are finite in float32", (long)(i / p->Lc), tpl[i], (long)(i % p->Lc));
+    HIP_OK(hipSetDevice(p->dev));
+    // the rounding and the padding of plan creation: compact planes, zero in the alignment gaps and beyond the last plane
+    std::vector<float> t((size_t)p->T * p->LP, 0.f);
+    for (int k = 0; k < p->T; ++k)
+        for (int l = 0; l < p->Lown; ++l)
+            if (p->planes[l] >= 0) t[(size_t)k * p->LP + l] = (float)tpl[(size_t)k * p->Lc + p->planes[l]];
+    HIP_OK(hipStreamSynchronize(p->stream));
+    HIP_OK(hipMemcpy(p->tpl, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+    p->tpl_host.assign(tpl, tpl + n);
+    // Model_WCT's explicit Hessian was built from the old templates: ensure_hessian builds it again on the next call
+    hipFree(p->hth);
+    hipFree(p->mhat2);
+    p->hth = p->mhat2 = nullptr;
+    return 0;
+}
+static int tpl_call_check(surfh_plan *p, const void *a, const void *b, const void *c) {
+    if (!p || !a || !b || !c) return fail("null argument");
+    HIP_OK(hipSetDevice(p->dev));
+    return tpl_ensure(p);
+}
+int surfh_forward_templates_dev(surfh_plan *p, const float *maps_dev, const float *tpl_dev, float *y_dev) {
+    if (tpl_call_check(p, maps_dev, tpl_dev, y_dev)) return 1;
+    TplScope sc(p);
+    if (sc.begin() || tpl_install(p, tpl_dev)) return 1;
+    return forward_dev(p, maps_dev, y_dev);
+}
+int surfh_adjoint_templates_dev(surfh_plan *p, const float *maps_dev, const float *u_dev, float *g_dev) {
+    if (tpl_call_check(p, maps_dev, u_dev, g_dev)) return 1;
+    return tpl_adjoint_dev(p, maps_dev, u_dev, g_dev);
+}
+int surfh_forward_templates(surfh_plan *p, const float *maps, const double *tpl, float *y) {
+    if (tpl_call_check(p, maps, tpl, y)) return 1;
+    const size_t n = (size_t)p->T * p->Lc;
+    std::vector<float> t(n);
+    for (size_t i = 0; i < n; ++i) t[i] = (float)tpl[i];
+    HIP_OK(hipMemcpyAsync(p->io_x, maps, p->isize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    HIP_OK(hipMemcpyAsync(p->tg_v[5], t.data(), n * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    {
+        TplScope sc(p);
+        if (sc.begin() || tpl_install(p, p->tg_v[5]) || forward_dev(p, p->io_x, p->io_y)) return 1;
+    }
+    HIP_OK(hipMemcpyAsync(y, p->io_y, p->osize * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+int surfh_adjoint_templates(surfh_plan *p, const float *maps, const float *u, float *g) {
+    if (tpl_call_check(p, maps, u, g)) return 1;
+    HIP_OK(hipMemcpyAsync(p->io_x, maps, p->isize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    HIP_OK(hipMemcpyAsync(p->io_y, u, p->osize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    if (tpl_adjoint_dev(p, p->io_x, p->io_y, p->tg_v[5])) return 1;
+    HIP_OK(hipMemcpyAsync(g, p->tg_v[5], (size_t)p->T * p->Lc * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
 }
 
 }  // extern "C"

@@ -154,10 +154,11 @@ int solver_setup(surfh_plan *p, const float *y, const float *x, double mu, doubl
 // iterations, so the callback may run forward / adjoint on this plan
 enum { CB_GO_ON = 0, CB_ERROR = 1, CB_STOP = 2 };
 int callback_iterate(surfh_plan *p, surfh_cg_callback callback, void *user, int it, const double *grad_norm, const float *x,
-                     std::vector<float> &hx) {
+                     std::vector<float> &hx, long n = 0) {      // n: floats of the iterate (0: isize)
     if (!callback) return CB_GO_ON;
-    hx.resize((size_t)p->isize);
-    HIP_OK(hipMemcpyAsync(hx.data(), x, p->isize * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    if (n == 0) n = p->isize;
+    hx.resize((size_t)n);
+    HIP_OK(hipMemcpyAsync(hx.data(), x, n * sizeof(float), hipMemcpyDeviceToHost, p->stream));
     HIP_OK(hipStreamSynchronize(p->stream));
     if (callback(user, it, grad_norm, hx.data())) return CB_STOP;
     HIP_OK(hipSetDevice(p->dev));
@@ -238,6 +239,7 @@ struct CgSpace {
     int (*dir)(surfh_plan *p, const CgSpace &s);                   // d = r + (rrn / rr) d, rr = rrn
     int (*trace)(surfh_plan *p, const CgSpace &s, double *grad_norm, int it);         // rows 0 .. it of the trace on the host
     int (*to_caller)(surfh_plan *p, const CgSpace &s);                                // xc = x in the caller's layout
+    long clen = 0;                 // floats of xc the caller and the callback get (0: isize)
 };
 int cg_nop(surfh_plan *, const CgSpace &) { return 0; }     // to_caller: the layouts agree; dir: the step's block went on to the direction
 // the maps and the planes keep the current row only: it goes to the host after every iteration
@@ -439,7 +441,7 @@ int cg_loop(surfh_plan *p, const CgSpace &s, int32_t max_iter, double tol, int32
         *nit = it + 1;
         if ((it + 1) % check != 0 && it + 1 != max_iter) continue;
         if (s.trace(p, s, grad_norm, it + 1) || (callback && s.to_caller(p, s))) return 1;
-        if (const int rc = callback_iterate(p, callback, user, it + 1, grad_norm, s.xc, hx)) {
+        if (const int rc = callback_iterate(p, callback, user, it + 1, grad_norm, s.xc, hx, s.clen)) {
             if (rc == CB_STOP) break;
             return 1;
         }
@@ -447,7 +449,7 @@ int cg_loop(surfh_plan *p, const CgSpace &s, int32_t max_iter, double tol, int32
         if (std::sqrt(*std::max_element(gn, gn + s.rows)) < (double)s.n * tol) break;
     }
     if (s.to_caller(p, s)) return 1;
-    HIP_OK(hipMemcpyAsync(x, s.xc, p->isize * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipMemcpyAsync(x, s.xc, (s.clen ? s.clen : p->isize) * sizeof(float), hipMemcpyDeviceToHost, p->stream));
     HIP_OK(hipStreamSynchronize(p->stream));
     return 0;
 }
@@ -482,6 +484,97 @@ int surfh_cg_cb(surfh_plan *p, const float *y, double mu, double mu_reg, const f
 int surfh_cg(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
              int32_t refresh, float *x, double *grad_norm, int32_t *nit) {
     return surfh_cg_cb(p, y, mu, mu_reg, x0, max_iter, tol, refresh, x, grad_norm, nit, nullptr, nullptr);
+}
+
+// ---- template refinement: the CG of surfh_cg on the spectra, maps held fixed ----
+// Q_S = mu A_x^T W A_x + mu_spec D^T D on S [T][Lc] (cube-plane order; D the open first difference along the wavelength), right-hand
+// side mu A_x^T W y: one more CgSpace on the frame above, with the maps' vector kernels on T Lc floats.  The maps stay in cg_x, their
+// spectra in mhat (computed once per solve; again after a callback, which may have run the operators on this plan), and an
+// application of Q_S puts its argument in the templates' place -- the plan's own come back through TplScope on every exit, and
+// before every callback.
+namespace {
+int tpl_apply(surfh_plan *p, const CgSpace &s, const float *v) {
+    if (tpl_install(p, v) || tpl_normal_dev(p, p->cg_x, s.q)) return 1;
+    p->tg_mhat_ready = true;
+    if (s.mu != 1.0) LAUNCH_OK(launch_scale(p->stream, s.q, s.len, (float)s.mu));
+    if (s.mu_reg != 0.0) {
+        Prof pr(p, "tpl_prior_add");
+        LAUNCH_OK(launch_tpl_prior_add(p->stream, v, s.q, p->T, p->Lc, (float)s.mu_reg));
+    }
+    return 0;
+}
+int tpl_setup(surfh_plan *p, const CgSpace &s, const float *y, const float *) {       // s.x holds the start
+    if (!(y = weighted_data(p, y))) return 1;
+    if (tpl_adjoint_dev(p, p->cg_x, y, s.b)) return 1;
+    p->tg_mhat_ready = true;
+    if (s.mu != 1.0) LAUNCH_OK(launch_scale(p->stream, s.b, s.len, (float)s.mu));
+    if (tpl_apply(p, s, s.x)) return 1;
+    LAUNCH_OK(launch_residual(p->stream, s.r, s.b, s.q, s.len));
+    return 0;
+}
+int tpl_to_caller(surfh_plan *p, const CgSpace &) {       // what follows may run the operators on this plan: its own templates, fresh spectra
+    HIP_OK(hipMemcpyAsync(p->tpl, p->tg_keep, (size_t)p->T * p->LP * sizeof(float), hipMemcpyDeviceToDevice, p->stream));
+    p->tg_mhat_ready = false;
+    return 0;
+}
+CgSpace tpl_space(surfh_plan *p, double mu, double mu_spec) {
+    float *const *v = p->tg_v;
+    const long n = (long)p->T * p->Lc;
+    return {v[0], v[1], v[2], v[3], v[4], v[0], n, n, 1, mu, mu_spec, p->dscal + 0, p->dscal + 1, p->dscal + 2,
+            tpl_setup, maps_rr0, tpl_apply, maps_step, maps_refresh, maps_dir, row_trace, tpl_to_caller, n};
+}
+}  // namespace
+
+int surfh_cg_templates_cb(surfh_plan *p, const float *y, const float *maps, double mu, double mu_spec, const float *s0, int32_t max_iter,
+                          double tol, int32_t refresh, float *s_out, double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
+    if (!p || !y || !maps || !s_out || !grad_norm || !nit) return fail("null argument");
+    if (p->im_g)
+        return fail("surfh_cg_templates does not carry the imager data term, and the attached imager was built from the plan's templates: "
+                    "detach it (surfh_set_imager(plan, NULL)) first");
+    if (!(mu >= 0.0 && mu <= DBL_MAX) || !(mu_spec >= 0.0 && mu_spec <= DBL_MAX)) return fail("surfh_cg_templates: mu and mu_spec must be finite and >= 0");
+    HIP_OK(hipSetDevice(p->dev));
+    if (tpl_ensure(p) || ensure_cg(p)) return 1;
+    const CgSpace s = tpl_space(p, mu, mu_spec);
+    std::vector<float> h((size_t)s.len);
+    if (s0) std::copy(s0, s0 + s.len, h.begin());
+    else for (long i = 0; i < s.len; ++i) h[i] = (float)p->tpl_host[i];
+    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    HIP_OK(hipMemcpyAsync(p->cg_x, maps, p->isize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    HIP_OK(hipMemcpyAsync(s.x, h.data(), s.len * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    TplScope sc(p);
+    if (sc.begin() || cg_start(p, s, p->io_y, nullptr)) return 1;
+    return cg_loop(p, s, max_iter, tol, refresh, 1, s_out, grad_norm, nit, callback, user);
+}
+int surfh_cg_templates(surfh_plan *p, const float *y, const float *maps, double mu, double mu_spec, const float *s0, int32_t max_iter,
+                       double tol, int32_t refresh, float *s_out, double *grad_norm, int32_t *nit) {
+    return surfh_cg_templates_cb(p, y, maps, mu, mu_spec, s0, max_iter, tol, refresh, s_out, grad_norm, nit, nullptr, nullptr);
+}
+
+// out[0] = J(x, S) = (mu out[1] + mu_reg out[2] + mu_spec out[3]) / 2 at the plan's templates S: out[1] = (y - A x)^T W (y - A x) under
+// the plan's data weights, out[2] = x^T (the plan's spatial prior) x, out[3] = |D S|^2 along the wavelength -- float64 sums on the device
+int surfh_joint_criterion(surfh_plan *p, const float *y, const float *maps, double mu, double mu_reg, double mu_spec, double *out) {
+    if (!p || !y || !maps || !out) return fail("null argument");
+    HIP_OK(hipSetDevice(p->dev));
+    if (tpl_ensure(p) || ensure_cg(p)) return 1;
+    hipStream_t st = p->stream;
+    const long n = (long)p->T * p->Lc;
+    std::vector<float> h((size_t)n);
+    for (long i = 0; i < n; ++i) h[i] = (float)p->tpl_host[i];
+    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(p->io_x, maps, p->isize * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(p->tg_v[5], h.data(), n * sizeof(float), hipMemcpyHostToDevice, st));
+    if (forward_dev(p, p->io_x, p->cg_y)) return 1;
+    LAUNCH_OK(launch_wres_sq(st, p->io_y, p->cg_y, p->dw, p->osize, p->dscratch, p->dscal + 3));
+    LAUNCH_OK(launch_fill_zero(st, p->cg_q, p->isize));
+    LAUNCH_OK(prior_add(p, st, p->io_x, p->cg_q, p->T, 1.f));
+    LAUNCH_OK(launch_dot(st, p->io_x, p->cg_q, p->isize, p->dscratch, p->dscal + 4));
+    LAUNCH_OK(launch_fill_zero(st, p->tg_v[3], n));
+    LAUNCH_OK(launch_tpl_prior_add(st, p->tg_v[5], p->tg_v[3], p->T, p->Lc, 1.f));
+    LAUNCH_OK(launch_dot(st, p->tg_v[5], p->tg_v[3], n, p->dscratch, p->dscal + 5));
+    HIP_OK(hipMemcpyAsync(out + 1, p->dscal + 3, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    out[0] = 0.5 * (mu * out[1] + mu_reg * out[2] + mu_spec * out[3]);
+    return 0;
 }
 
 // ---- posterior sampling by perturbation-optimisation (kernels and conventions: posterior.hip) ----

@@ -274,6 +274,49 @@ def huber_phi(u, delta):
 
 
 # ------------------------------------------------------------------------------------------------
+# template refinement: alternate the maps' and the spectra's half-steps (surfh_amd.spectra)
+# ------------------------------------------------------------------------------------------------
+@dataclass
+class RefineResult:
+    x: np.ndarray                       # the maps [T, Na, Nb]
+    templates: np.ndarray               # the refined templates [T, Lc]: the model's from now on
+    templates_start: np.ndarray         # the templates the model held on entry
+    criterion: np.ndarray               # J at the start and after every half-step: [1 + 2 rounds]
+    terms: np.ndarray                   # (data, spatial prior, spectral prior) behind every entry of ``criterion``
+
+
+def refine_templates(model, data, mu, mu_reg, mu_spec, rounds, map_iter, tpl_iter, weights=None, x0=None):
+    """Alternating minimisation of the joint criterion of ``surfh_amd.spectra``,
+    ``J(x, S) = [mu (y - A(S) x)^T W (y - A(S) x) + mu_reg (|Dr x|^2 + |Dc x|^2) + mu_spec |D_l S|^2] / 2``:
+    ``rounds`` times ``map_iter`` iterations of ``model.cg`` on the maps from the current maps, then ``tpl_iter`` iterations of
+    ``model.cg_templates`` on the spectra from the current templates, installed with ``model.set_templates``.  Each half-step is a
+    CG on a quadratic from a warm start, so it cannot raise ``J`` in exact arithmetic.  ``J`` is evaluated on the device (the
+    weighted residual norm and the two prior values, ``model.joint_criterion``) at the start and after every half-step.
+
+    There is no rescaling between the steps: the model is invariant under ``s_t -> c s_t``, ``x_t -> x_t / c``, and that scale is
+    left to the two priors.  ``x0`` None: maps of zeros.  The model's templates are left at the refined ones; the ones it held on
+    entry come back in the result."""
+    start = np.array(model.templates, dtype=np.float64, copy=True)
+    x = np.zeros(model.ishape) if x0 is None else np.array(x0, dtype=np.float64).reshape(model.ishape)
+    crit, terms = [], []
+
+    def record():
+        j = model.joint_criterion(data, x, mu, mu_reg, mu_spec, weights)
+        crit.append(j[0])
+        terms.append(j[1:])
+
+    record()
+    for _ in range(int(rounds)):
+        x = model.cg(data, mu=mu, mu_reg=mu_reg, x0=x, max_iter=map_iter, weights=weights)[0]
+        record()
+        S = model.cg_templates(data, x, mu=mu, mu_spec=mu_spec, s0=None, max_iter=tpl_iter, weights=weights)[0]
+        model.set_templates(S)
+        record()
+    return RefineResult(x=x, templates=np.array(model.templates, copy=True), templates_start=start,
+                        criterion=np.asarray(crit, dtype=np.float64), terms=np.asarray(terms, dtype=np.float64))
+
+
+# ------------------------------------------------------------------------------------------------
 # multi-GPU
 # ------------------------------------------------------------------------------------------------
 def save_checkpoint(path, x, it, grad_norm):

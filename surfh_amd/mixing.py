@@ -70,6 +70,13 @@ class Model_WCT(LinOp):
     def fwadj(self, x):
         return self._call(self._L.surfh_wct_fwadj, x, self.ishape, self.ishape)
 
+    def set_specs(self, L_specs):
+        """Replace the spectra ``[n_spec, n_lamb]`` (surfh_set_templates): ``forward`` / ``adjoint`` use them at once, ``fwadj`` and
+        ``expsol`` the explicit Hessian rebuilt from them on their next call.  ``ValueError`` on a wrong shape or a non-finite value."""
+        from .spectra import check_templates
+        a = check_templates(L_specs, (self.n_spec, self.n_lamb))
+        _lib.check(self._L.surfh_set_templates(self._plan, _lib.dptr(a)), ValueError)
+
     def expsol(self, data, L_mu, reg_freq):
         """(H^T H + diag(L_mu) D^T D)^-1 H^T data with |D(f)|^2 = ``reg_freq`` on the half spectrum [Na, Nb/2+1]."""
         assert tuple(np.shape(data)) == tuple(self.oshape)

@@ -23,6 +23,7 @@ from .geometry import ChannelGeometry
 from .linop import LinOp
 from . import potentials as _pot
 from .weights import DataWeights
+from .spectra import TemplateOps
 
 
 def _ptr(t):
@@ -111,7 +112,7 @@ class _InstalledImager:
         return False
 
 
-class spectroSigRLSCT(DataWeights, _pot.Potentials, LinOp):
+class spectroSigRLSCT(DataWeights, TemplateOps, _pot.Potentials, LinOp):
     huber_prior_value = None            # prior value of the last mmmg(delta=...) result (set by mmmg)
     huber_prior_values = None           # (spatial, spectral) prior values of the last mmmg_vox result
     robust_weights = None               # omega(t) [osize] of the last mmmg / mmmg_vox result under data_delta (else None)

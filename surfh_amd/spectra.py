@@ -1,0 +1,120 @@
+"""Template refinement: the other half-step of the bilinear model ``y = A(S) x`` -- hold the maps ``x``, solve for the spectra ``S``.
+
+The joint criterion is ``J(x, S) = [mu (y - A(S) x)^T W (y - A(S) x) + mu_reg (|Dr x|^2 + |Dc x|^2) + mu_spec |D_l S|^2] / 2`` with
+``D_l`` the first difference along the wavelength with open ends; for fixed maps it is quadratic in ``S`` and ``A_x : S -> A(S) x`` is
+the forward model with ``S`` in the templates' place (include/surfh_amd.h: surfh_set_templates ... surfh_cg_templates).  This module
+holds what the Python classes share: the argument check and the plan-state methods of a model that owns a plan.
+
+What the data can say about a spectrum is limited by the detector: a feature narrower than the detector's wavelength sampling
+(config 1 has 48 detector samples for 128 planes) is not recovered, whatever the solver does; ``mu_spec`` fills such planes, and
+the planes no channel reads, from their neighbours."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+
+def check_templates(S, shape) -> np.ndarray:
+    """``S`` as the contiguous float64 ``[T, Lc]`` array the library takes.  ``ValueError`` unless it has the model's shape (the
+    number of templates and of planes are fixed at plan creation) and is finite, in float32 too.  No library call."""
+    a = np.asarray(S, dtype=np.float64)
+    if a.shape != tuple(shape):
+        raise ValueError(f"templates have shape {a.shape}, the model's are {tuple(shape)}: T and Lc are fixed at plan creation")
+    if not np.all(np.abs(a) <= np.finfo(np.float32).max):        # NaN fails the comparison too
+        raise ValueError("templates must be finite (in float32 too)")
+    return np.ascontiguousarray(a)
+
+
+class TemplateOps:
+    """Methods of a model with templates that owns a plan (``self._L``, ``self._plan``, ``self.templates``, ``ishape``, ``osize``)."""
+
+    def _need_templates(self):
+        if getattr(self, "templates", None) is None:
+            raise ValueError("the model has no templates")
+
+    def set_templates(self, S):
+        """Replace the model's templates ``[T, Lc]`` (plan state: every operator and solver uses them from now on, as if the model
+        had been built with them; ``mapsToCube`` and ``cube_std`` read ``self.templates``).  ``ValueError`` on a wrong shape, a
+        non-finite value, or while an imager is attached -- its transfer functions were built from the templates: detach it
+        (``set_imager(None)``), set the templates, attach it again."""
+        self._need_templates()
+        a = check_templates(S, self.templates.shape)
+        _lib.check(self._L.surfh_set_templates(self._plan, _lib.dptr(a)), ValueError)
+        self.templates = a.copy()
+
+    def forward_templates(self, S, maps):
+        """``A_x S``: the forward model on ``maps`` with ``S`` in the templates' place; the model's templates are untouched."""
+        self._need_templates()
+        a = check_templates(S, self.templates.shape)
+        x = np.ascontiguousarray(np.asarray(maps, dtype=np.float32).reshape(-1))
+        if x.size != self.isize:
+            raise ValueError(f"maps have {x.size} elements, expected {self.isize}")
+        y = np.empty(self.osize, dtype=np.float32)
+        _lib.check(self._L.surfh_forward_templates(self._plan, _lib.fptr(x), _lib.dptr(a), _lib.fptr(y)))
+        return y.astype(np.float64).reshape(self.oshape)
+
+    def adjoint_templates(self, u, maps):
+        """``A_x^T u`` ``[T, Lc]``: the transpose of ``forward_templates``; exactly 0 on the planes no channel reads."""
+        self._need_templates()
+        x = np.ascontiguousarray(np.asarray(maps, dtype=np.float32).reshape(-1))
+        v = np.ascontiguousarray(np.asarray(u, dtype=np.float32).reshape(-1))
+        if x.size != self.isize or v.size != self.osize:
+            raise ValueError(f"maps / data have {x.size} / {v.size} elements, expected {self.isize} / {self.osize}")
+        g = np.empty(self.templates.size, dtype=np.float32)
+        _lib.check(self._L.surfh_adjoint_templates(self._plan, _lib.fptr(x), _lib.fptr(v), _lib.fptr(g)))
+        return g.astype(np.float64).reshape(self.templates.shape)
+
+    def cg_templates(self, data, maps, mu=1.0, mu_spec=0.0, s0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, weights=None):
+        """Linear CG on ``(mu A_x^T W A_x + mu_spec D_l^T D_l) S = mu A_x^T W y`` from ``s0`` (None: the model's templates): the
+        loop, stopping test, trace and callback contract of ``cg``, the size in the tolerance being ``T Lc``.  ``callback(it,
+        grad_norm, S)``; ``weights`` as in ``cg``.  Returns ``(S, grad_norm, nit)``; the model's templates are unchanged (the
+        plan's own are back in place on every exit, and while the callback runs).  ``ValueError`` while an imager is attached."""
+        self._need_templates()
+        if getattr(self, "_imager", None) is not None:
+            raise ValueError("cg_templates does not carry the imager data term and the attached imager was built from the model's "
+                             "templates: detach it (set_imager(None)) first")
+        shape = self.templates.shape
+        y = np.ascontiguousarray(np.asarray(data, dtype=np.float32).reshape(-1))
+        x = np.ascontiguousarray(np.asarray(maps, dtype=np.float32).reshape(-1))
+        if y.size != self.osize or x.size != self.isize:
+            raise ValueError("data or maps size mismatch")
+        s0a = None if s0 is None else check_templates(s0, shape).astype(np.float32).reshape(-1)
+        out = np.empty(self.templates.size, dtype=np.float32)
+        gn = np.zeros(max_iter + 1, dtype=np.float64)
+        nit = C.c_int32()
+        err = []
+
+        def tramp(_user, it, gptr, xptr):
+            try:
+                g = np.ctypeslib.as_array(gptr, shape=(it + 1,)).copy()
+                si = np.ctypeslib.as_array(xptr, shape=(out.size,)).astype(np.float64).reshape(shape)
+                return 1 if callback(it, g, si) else 0
+            except BaseException as e:          # never unwind through the C frame
+                err.append(e)
+                return 1
+
+        cb = _lib.CG_CALLBACK(tramp) if callback is not None else _lib.CG_CALLBACK()
+        with self.installed_weights(weights):
+            _lib.check(self._L.surfh_cg_templates_cb(self._plan, _lib.fptr(y), _lib.fptr(x), float(mu), float(mu_spec),
+                                                     _lib.fptr(s0a) if s0a is not None else None, int(max_iter), float(tol),
+                                                     int(refresh), _lib.fptr(out), _lib.dptr(gn), C.byref(nit), cb, None), ValueError)
+        if err:
+            raise err[0]
+        return out.astype(np.float64).reshape(shape), gn[: nit.value + 1].copy(), nit.value
+
+    def joint_criterion(self, data, maps, mu=1.0, mu_reg=0.0, mu_spec=0.0, weights=None):
+        """``(J, data term, spatial prior, spectral prior)`` at ``maps`` and the model's templates, summed on the device in float64:
+        ``J = (mu data + mu_reg spatial + mu_spec spectral) / 2`` (the module's criterion; ``weights`` as in ``cg``)."""
+        self._need_templates()
+        y = np.ascontiguousarray(np.asarray(data, dtype=np.float32).reshape(-1))
+        x = np.ascontiguousarray(np.asarray(maps, dtype=np.float32).reshape(-1))
+        if y.size != self.osize or x.size != self.isize:
+            raise ValueError("data or maps size mismatch")
+        out = np.zeros(4, dtype=np.float64)
+        with self.installed_weights(weights):
+            _lib.check(self._L.surfh_joint_criterion(self._plan, _lib.fptr(y), _lib.fptr(x), float(mu), float(mu_reg), float(mu_spec),
+                                                     _lib.dptr(out)))
+        return tuple(float(v) for v in out)
