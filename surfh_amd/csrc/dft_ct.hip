@@ -2,6 +2,7 @@
 // residue class), combined through LDS by twiddles and an R-point butterfly (see dft_ct.h).
 #include "dft_ct.h"
 #include "lds_attr.h"
+#include "prior_eig.h"
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -115,7 +116,7 @@ __global__ __launch_bounds__(Cfg<R>::NTH) void dft_ct_kernel(DftCtArgs g, const 
         for (int i = tid; i < IMGH / 8; i += NTH) l4[i] = img[i];
         for (int i = tid; i < M * (R - 1) * 2; i += NTH) twl[i] = twg[i];
         if (LD == DFT_CT_PRODADD)
-            for (int i = tid; i < N; i += NTH) awk[i] = g.add_w * (2.f - 2.f * cospif(2.f * (float)i / (float)N));
+            for (int i = tid; i < N; i += NTH) awk[i] = g.add_w * dsq(i, N);
         if (tid < 4) gsync[tid] = 0u;
     }
     // this workgroup's contiguous range of units (NG adjacent tiles of 16 columns, one per group of waves)
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(Cfg<R>::NTH) void dft_ct_kernel(DftCtArgs g, const 
     }                                                                                                           \
     if (LD == DFT_CT_PRODADD) {                                                                                 \
         const int kb = g.batch > 1 ? (t_) / tilesX : (((t_) % tilesX) * 16) / g.LP;                             \
-        awb = g.add_w * (2.f - 2.f * cospif(2.f * (float)kb / (float)g.add_Nb));                                \
+        awb = g.add_w * dsq(kb, g.add_Nb);                                                                      \
     }
 
     // Addressing of the k loop: buffer loads with one descriptor per k-step and direction (scalar 64-bit base: no 4 GB

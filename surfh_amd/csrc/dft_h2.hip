@@ -7,6 +7,7 @@
 // last MFMA group, behind loads that are already in flight.
 #include "dft_h2.h"
 #include "lds_attr.h"
+#include "prior_eig.h"
 #include <cmath>
 #include <cstring>
 
@@ -673,7 +674,7 @@ __global__ __launch_bounds__(256) void dft_h2_adjmix_reduce_kernel(const float *
                                                                    float prior_mu, const int *__restrict__ kbstart) {
     const int kb = blockIdx.x;
     const float osc = (kb == 0 || 2 * kb == Nb) ? out_self : out_pair;
-    const float pcb = prior_src ? 2.f - 2.f * cospif(2.f * (float)kb / (float)Nb) : 0.f;
+    const float pcb = prior_src ? dsq(kb, Nb) : 0.f;
     if (kb >= hb) {
         for (int i = blockIdx.y * 256 + threadIdx.x; i < KAP * 8; i += 256 * gridDim.y) {
             const int row = i >> 3, tc = i & 7, t = tc >> 1, c = tc & 1;
@@ -700,7 +701,7 @@ __global__ __launch_bounds__(256) void dft_h2_adjmix_reduce_kernel(const float *
         if (row < Na) {
             for (int sl = 0; sl < ns; ++sl) s += mpart[((long)kb * nslot + sl) * (256 * 8) + row * 8 + tc];
             s *= osc;
-            if (prior_src) s += prior_mu * (pcb + 2.f - 2.f * cospif(2.f * (float)row / (float)Na)) * prior_src[o];
+            if (prior_src) s += prior_mu * (pcb + dsq(row, Na)) * prior_src[o];
         }
         madj[o] = s;
     }

@@ -2,6 +2,7 @@
 #include "kernels.h"
 #include "huber_dev.h"
 #include "mm_step.h"
+#include "prior_eig.h"
 #include <algorithm>
 #include <cfloat>
 #include <cstdlib>
@@ -221,7 +222,7 @@ __global__ __launch_bounds__(TPB) void specmix_adj_ilv_kernel(const float *__res
         if (o.Nb) {     // the solver's Parseval-scaled half spectrum, mu and the quadratic prior folded in (dft_h2.h DftH2AdjMix)
             v *= (kb == 0 || 2 * kb == o.Nb) ? o.out_self : o.out_pair;
             if (o.prior_src && ka < o.Na && 2 * kb <= o.Nb)
-                v += o.prior_mu * (4.f - 2.f * cospif(2.f * (float)kb / (float)o.Nb) - 2.f * cospif(2.f * (float)ka / (float)o.Na)) * o.prior_src[oo];
+                v += o.prior_mu * (dsq(kb, o.Nb) + dsq(ka, o.Na)) * o.prior_src[oo];
         }
         madj[oo] = v;
     }
@@ -229,7 +230,7 @@ __global__ __launch_bounds__(TPB) void specmix_adj_ilv_kernel(const float *__res
 
 // `out` may hold, on entry, the spectrum of the vector the normal operator was applied to (the forward model left it there): with
 // prior_w != 0 the quadratic prior is added in the same pass, out = mu conj(H) Y + prior_w |D(k)|^2 out_old (circular first
-// differences are diagonal in the Fourier domain: |D|^2 = 4 - 2 cos(2 pi ka / Na) - 2 cos(2 pi kb / Nb))
+// differences are diagonal in the Fourier domain: |D|^2 = dsq(ka, Na) + dsq(kb, Nb), prior_eig.h)
 __global__ __launch_bounds__(TPB) void specmix_adj_plane_ilv_kernel(const float *__restrict__ spec, const float *__restrict__ sotf,
                                                                     float *out, long PL, int LP, float mu, float prior_w, int Na, int Nb, long KBP) {
     const int l2 = (blockIdx.x * TPB + threadIdx.x) * 2;
@@ -240,7 +241,7 @@ __global__ __launch_bounds__(TPB) void specmix_adj_plane_ilv_kernel(const float 
     float4 v = make_float4(hh.x * y.x + hh.y * y.y, hh.x * y.y - hh.y * y.x, hh.z * y.z + hh.w * y.w, hh.z * y.w - hh.w * y.z);
     if (prior_w != 0.f) {
         const int ka = (int)(k / KBP), kb = (int)(k % KBP);
-        const float w = prior_w * (4.f - 2.f * cospif(2.f * (float)ka / (float)Na) - 2.f * cospif(2.f * (float)kb / (float)Nb));
+        const float w = prior_w * (dsq(ka, Na) + dsq(kb, Nb));
         const float4 o = *reinterpret_cast<const float4 *>(out + (k * LP + l2) * 2);
         v = make_float4(mu * v.x + w * o.x, mu * v.y + w * o.y, mu * v.z + w * o.z, mu * v.w + w * o.w);
     }
@@ -862,7 +863,7 @@ __global__ __launch_bounds__(TPB) void spec_prior_add_kernel(const float *__rest
     const int kb = (int)(i % KBP), ka = (int)(i / KBP);
     if (ka >= Na || kb > Nb / 2) return;
     const long o = (long)blockIdx.y * PL + i;
-    q[o] += mu_reg * (4.f - 2.f * cospif(2.f * (float)ka / (float)Na) - 2.f * cospif(2.f * (float)kb / (float)Nb)) * d[o];
+    q[o] += mu_reg * (dsq(ka, Na) + dsq(kb, Nb)) * d[o];
 }
 
 __global__ __launch_bounds__(TPB) void fill_zero_kernel(float *p, long n) {
