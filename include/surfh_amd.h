@@ -195,6 +195,29 @@ int surfh_cg_templates_cb(surfh_plan *plan, const float *y, const float *maps, d
  * (surfh_set_prior; |Dr x|^2 + |Dc x|^2 by default), out[3] = |D_l S|^2: float64 sums on the device                                  */
 int surfh_joint_criterion(surfh_plan *plan, const float *y, const float *maps, double mu, double mu_reg, double mu_spec, double *out);
 
+/* ---- non-negative fusion: ADMM in scaled form around the CG of surfh_cg / surfh_cg_templates ----
+ *     min x^T Q x / 2 - b^T x  subject to  x >= 0,      Q and b those of surfh_cg (the plan's data weights included)
+ * x = x0 (NULL: 0), z = max(x0, 0), u = 0, v = z - u, r = b + rho v - (Q + rho I) x; per outer iteration: d = r and `inner` CG
+ * iterations on Q + rho I (x, r, d carried, no refresh inside); z' = max(x + u, 0), u' = u + x - z', v' = z' - u'; r += rho (v' - v),
+ * or r = b + rho v' - (Q + rho I) x in the outer iterations k with (k + 1) % refresh == 0 (refresh 0: never).  The result is z.
+ * trace [outer + 1][4]: |x - z|^2, rho^2 |z - z_previous|^2 (0 in row 0), r.r of the next inner system, #{z == 0}; row 0 is the start,
+ * rows beyond nit are not written.  Stops after the outer iteration whose row has sqrt(max(rho^2 row[0], row[1])) < isize tol.
+ * An outer iteration costs `inner` applications of the operator, one more where it refreshes.  Vectors are the maps' spectra under
+ * the rule of surfh_cg (SURFH_SPECTRAL_CG), z and u stay on the pixels.  Fails before any work: rho <= 0 or not finite, inner < 1,
+ * outer < 0, a plan without templates, an active imager term.                                                                        */
+int surfh_cg_nonneg(surfh_plan *plan, const float *y, double mu, double mu_reg, double rho, const float *x0, int32_t outer, int32_t inner,
+                    double tol, int32_t refresh, float *x, double *trace, int32_t *nit);
+/* the same on the spectra with the maps held fixed: Q and b those of surfh_cg_templates, s0 NULL: the plan's templates, sizes T Lc.
+ * Fails while an imager is attached.                                                                                                  */
+int surfh_cg_templates_nonneg(surfh_plan *plan, const float *y, const float *maps, double mu, double mu_spec, double rho, const float *s0,
+                              int32_t outer, int32_t inner, double tol, int32_t refresh, float *s_out, double *trace, int32_t *nit);
+/* the projection / dual update of one outer iteration on n device floats, in place in z and u: z' = max(x + u, 0) (never a set sign
+ * bit), u' = u + x - z', and w = rho ((z' - u') - (z - u)) added to r_dev, or written to dv_dev (r_dev NULL), or dropped (both NULL).
+ * sums [4] (host) = |x - z'|^2, |z' - z|^2, #{z' == 0}, r.r of the updated r (0 without r_dev): float64, the same bits for the same
+ * inputs.  Pointers need no alignment.                                                                                                */
+int surfh_nn_project_dev(surfh_plan *plan, const float *x_dev, float *z_dev, float *u_dev, float *r_dev, float *dv_dev, int64_t n,
+                         double rho, double *sums);
+
 /* ---- posterior sampling: per-pixel uncertainty of the maps surfh_cg returns (perturbation-optimisation, Orieux, Feron &
  * Giovannelli 2012) ----
  * Convention: the criterion of surfh_cg is the negative log of the Gaussian posterior

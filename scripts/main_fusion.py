@@ -143,12 +143,13 @@ def create_model(sotf, templates, origin_alpha_axis, origin_beta_axis, wavel_axi
 
 def result_dir_name(method, n_channels, n_templates, niter, hyper_parameter, scale_data, delta=None, voxel=False, weighted=False,
                     data_delta=None, potential='huber', data_potential='huber', spec_potential='huber', imager=0, samples=0,
-                    refine=0):
+                    refine=0, nonneg=False):
     """main_fusion.py:182; with a Huber threshold `delta` (not in the reference) `_huber_<delta>` is appended, `_vox` for a
     voxel-wise reconstruction, `_wgt` for a run under data weights, and `_rob_<data_delta>` for a robust data term.  Another
     potential than Huber puts its name in Huber's place (`_<kind>_<delta>`, `_rob_<kind>_<data_delta>`; `_spec_<kind>` for the
     spectral prior of a voxel-wise run); with Huber the names are unchanged.  `_img_<F>` follows for a run with an imager
-    data term of F filters, `_po_<K>` for a run that draws K posterior samples, `_tpl_<K>` for K rounds of template refinement."""
+    data term of F filters, `_po_<K>` for a run that draws K posterior samples, `_tpl_<K>` for K rounds of template refinement,
+    `_nn` last for a non-negative run (--nonneg)."""
     name = f'{method}_MC_{n_channels}_MO_4_Temp_{n_templates}_nit_{str(niter)}_mu_{str("{:.2e}".format(hyper_parameter))}_SD_{scale_data}'
     if delta is not None:
         name += f'_{potential}_{delta:.2e}'
@@ -166,6 +167,8 @@ def result_dir_name(method, n_channels, n_templates, niter, hyper_parameter, sca
         name += f'_po_{samples}'
     if refine:
         name += f'_tpl_{refine}'
+    if nonneg:
+        name += '_nn'
     return name + '/'
 
 
@@ -269,15 +272,18 @@ def reconstruction_method(spectro_model, ndata, templates, result_path, hyper_pa
 
 
 def template_refinement(spectro_model, ndata, templates, result_path, hyper_parameter, niter, method, scale_data, rounds, mu_spec,
-                        tpl_iter, weights=None):
+                        tpl_iter, weights=None, nonneg=False, rho=None, inner=10):
     """`rounds` rounds of (`niter` CG iterations on the maps, `tpl_iter` on the spectra) by surfh_amd.fusion.refine_templates, data
     weight 1: res_x.npy (maps), res_templates.npy and templates_start.npy [T, Lc], and in criterion.npy the joint criterion at the
-    start and after every half-step.  Features narrower than the detector's wavelength sampling stay what the start had."""
+    start and after every half-step.  Features narrower than the detector's wavelength sampling stay what the start had.
+    `nonneg`: both half-steps under their constraint (`niter` / `tpl_iter` outer iterations of `inner` CG iterations, penalty `rho`
+    or the estimate); the criterion trace may then rise between entries."""
     from surfh_amd.fusion import refine_templates
     path = pathlib.Path(result_path) / result_dir_name(method, len(spectro_model.instrs), templates.shape[0], niter, hyper_parameter,
-                                                       scale_data, weighted=weights is not None, refine=rounds)
+                                                       scale_data, weighted=weights is not None, refine=rounds, nonneg=nonneg)
     path.mkdir(parents=True, exist_ok=True)
-    res = refine_templates(spectro_model, ndata, 1., hyper_parameter, mu_spec, rounds, niter, tpl_iter, weights=weights)
+    res = refine_templates(spectro_model, ndata, 1., hyper_parameter, mu_spec, rounds, niter, tpl_iter, weights=weights,
+                           **(dict(nonneg=True, rho=rho, inner=inner) if nonneg else {}))
     for k, j in enumerate(res.criterion):
         print(f"half-step {k}: joint criterion {j:.6e}")
     print(f"Results save in {path}")
@@ -285,6 +291,25 @@ def template_refinement(spectro_model, ndata, templates, result_path, hyper_para
     np.save(path / 'res_templates.npy', res.templates)
     np.save(path / 'templates_start.npy', res.templates_start)
     np.save(path / 'criterion.npy', res.criterion)
+    if weights is not None:
+        np.save(path / 'weights.npy', weights)
+    return res, path
+
+
+def nonneg_reconstruction(spectro_model, ndata, templates, result_path, hyper_parameter, outer, inner, rho, method, scale_data,
+                          weights=None):
+    """The maps under x >= 0 by `cg_nonneg` (surfh_amd/nonneg.py), data weight 1, from zero: res_x.npy, res_cube.npy, and in
+    nn_trace.npy one row per outer iteration (and one for the start): |x - z|, rho |z - z_previous|, |r|, #{z == 0}."""
+    path = pathlib.Path(result_path) / result_dir_name(method, len(spectro_model.instrs), templates.shape[0], outer, hyper_parameter,
+                                                       scale_data, weighted=weights is not None, nonneg=True)
+    path.mkdir(parents=True, exist_ok=True)
+    res = spectro_model.cg_nonneg(ndata, mu=1., mu_reg=hyper_parameter, rho=rho, outer=outer, inner=inner, weights=weights)
+    print(f"non-negative lcg: rho {res.rho:.3e}, {res.nit} outer iterations of {inner}; primal {res.primal[-1]:.3e}, dual "
+          f"{res.dual[-1]:.3e}, {res.n_active[-1]} of {res.x.size} entries at zero")
+    print(f"Results save in {path}")
+    np.save(path / 'res_x.npy', res.x)
+    np.save(path / 'res_cube.npy', spectro_model.mapsToCube(res.x))
+    np.save(path / 'nn_trace.npy', np.stack([res.primal, res.dual, res.grad_norm, res.n_active.astype(np.float64)], axis=1))
     if weights is not None:
         np.save(path / 'weights.npy', weights)
     return res, path
@@ -350,10 +375,32 @@ def synthetic_problem(name, npix):
 @click.option('--mu_spec', default=None, type=float, help='Weight of the first-difference prior along the wavelength of the spectra '
                                                           '(--refine_templates). Default: 0.')
 @click.option('--tpl_iter', default=None, type=int, help='CG iterations of a template half-step (--refine_templates). Default: 10.')
+@click.option('--nonneg', is_flag=True, default=False,
+              help='Keep the maps non-negative (ADMM around the CG; needs --method lcg), and with --refine_templates the spectra too: '
+                   '-ni and --tpl_iter then count outer iterations. Results go to a directory ending in _nn.')
+@click.option('--rho', default=None, type=float, help='ADMM penalty (--nonneg). Default: estimated, the mean eigenvalue of the operator.')
+@click.option('--outer', default=None, type=int, help='Outer iterations (--nonneg without --refine_templates). Default: -ni.')
+@click.option('--inner', default=None, type=int, help='CG iterations per outer iteration (--nonneg). Default: 10.')
 def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, method, verbose, synthetic, device, checkpoint_every=0,
          resume=None, delta=None, voxel=False, spec_reg=1., spec_delta=1., weights_file=None, mask_nan=False, data_delta=None,
          potential='huber', data_potential='huber', spec_potential='huber', imager_filters=0, mu_imager=1., imager_decim=1,
-         samples=0, seed=None, refine_rounds=0, mu_spec=None, tpl_iter=None):
+         samples=0, seed=None, refine_rounds=0, mu_spec=None, tpl_iter=None, nonneg=False, rho=None, outer=None, inner=None):
+    if nonneg:
+        if method != 'lcg':
+            raise click.UsageError('--nonneg runs ADMM around the linear CG; use it with --method lcg')
+        if voxel or imager_filters or samples or delta is not None or data_delta is not None or checkpoint_every or resume:
+            raise click.UsageError('--nonneg constrains the quadratic criterion on the maps (and the spectra) alone: no --voxel, '
+                                   '--imager, --samples, --delta, --data_delta or checkpoints')
+        if rho is not None and not (rho > 0 and np.isfinite(rho)):
+            raise click.BadParameter(f'must be finite and > 0, not {rho}', param_hint='--rho')
+        if inner is not None and inner < 1:
+            raise click.BadParameter(f'at least one CG iteration, not {inner}', param_hint='--inner')
+        if outer is not None and refine_rounds:
+            raise click.UsageError('--outer: with --refine_templates, -ni and --tpl_iter count the outer iterations')
+        if outer is not None and outer < 1:
+            raise click.BadParameter(f'at least one outer iteration, not {outer}', param_hint='--outer')
+    elif rho is not None or outer is not None or inner is not None:
+        raise click.UsageError('--rho, --outer and --inner belong to --nonneg')
     if refine_rounds:
         if refine_rounds < 1:
             raise click.BadParameter(f'at least one round, not {refine_rounds}', param_hint='--refine_templates')
@@ -474,7 +521,12 @@ def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, meth
         return
     if refine_rounds:
         template_refinement(model, ndata, templates, paths["result_path"], hyper_parameter, niter, method, scale_data, refine_rounds,
-                            mu_spec or 0., tpl_iter or 10, weights=weights)
+                            mu_spec or 0., tpl_iter or 10, weights=weights, nonneg=nonneg, rho=rho, inner=inner or 10)
+        model.close()
+        return
+    if nonneg:
+        nonneg_reconstruction(model, ndata, templates, paths["result_path"], hyper_parameter, outer or niter, inner or 10, rho, method,
+                              scale_data, weights=weights)
         model.close()
         return
     reconstruction_method(model, ndata, templates, paths["result_path"], hyper_parameter, niter, method, scale_data,

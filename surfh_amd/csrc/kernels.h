@@ -160,6 +160,14 @@ int launch_po_add(hipStream_t s, float *b, const float *e, long n);
 long po_moment_planes(int T);
 int launch_po_moments(hipStream_t s, const float *x, const float *xhat, double *S, int T, long npix);
 int launch_po_finish(hipStream_t s, const float *xhat, const double *S, int T, long npix, int K, double *mean, double *cov);
+// ---- non-negative fusion (nonneg.hip) ----
+// the ADMM projection / dual update in one pass: z' = max(x + u, 0) (no set sign bit), u' = u + x - z', in place in z and u, and with
+// w = rho ((z' - u') - (z - u)) either r += w (r given) or dv = w (dv given; neither: z and u only).  sums[0..3] = |x - z'|^2,
+// |z' - z|^2, #{z' == 0}, the new r.r (0 without r): float64 per-block partials in `scratch` (1024 doubles) summed in a fixed order
+int launch_nn_project(hipStream_t s, const float *x, float *z, float *u, float *r, float *dv, long n, float rho, double *scratch,
+                      double *sums);
+// out += c (a - b)   (b NULL: out += c a)
+int launch_nn_add(hipStream_t s, float *out, const float *a, const float *b, long n, float c);
 // 3MG move: mv = s0 d + s1 m ; x += mv ; m = mv ; qm = s0 qd + s1 qm ; r -= qm (when update_r)
 int launch_mmmg_update(hipStream_t s, float *x, float *r, const float *d, float *m, float *qm, const float *qd, long n, double s0,
                        double s1, int update_r);

@@ -1,0 +1,119 @@
+// Non-negative fusion (ADMM in scaled form on the CG frame; the loop: nn_loop, plan_solvers.hip), the device kernels and their launchers.
+//   min x^T Q x / 2 - b^T x  subject to  x >= 0   split as  x = z, z >= 0,  scaled dual u,  v = z - u:
+//   x  <-  (Q + rho I)^-1 (b + rho v)     `inner` CG iterations on the carried residual
+//   z' = max(x + u, 0);  u' = u + x - z';  v' = z' - u'        nn_project, one pass, with the sums of an outer iteration's trace
+// and the residual of the next inner system follows from the carried one: r += rho (v' - v) (fused into the pass, or left in dv
+// where r lives in another basis).  nn_add is the rho I of the operator and every other axpy of the loop.
+#include "plan_internal.h"
+#include "huber_dev.h"
+
+namespace {
+constexpr int NN_MAX_BLOCKS = 256;       // 4 sums x 256 partials: the 1024 doubles every plan's dscratch holds
+
+enum { NN_PLAIN = 0, NN_FUSED = 1, NN_DV = 2 };
+
+// one element: t = x + u, z' = t > 0 ? t : 0 (never a set sign bit; NaN goes to 0), u' = t - z' (0 where t > 0, t elsewhere: exact),
+// w = rho ((z' - u') - (z - u)).  acc: |x - z'|^2, |z' - z|^2, #{z' == 0}, and the new r.r (NN_FUSED), in float64
+template <int MODE>
+__device__ __forceinline__ void nn_element(float x, float &z, float &u, float &w, float rho, double (&acc)[4]) {
+    const float t = x + u;
+    const float zn = t > 0.f ? t : 0.f;
+    const float un = t - zn;
+    const float dv = rho * ((zn - un) - (z - u));
+    const double ex = (double)x - (double)zn, ez = (double)zn - (double)z;
+    acc[0] += ex * ex;
+    acc[1] += ez * ez;
+    acc[2] += zn == 0.f ? 1.0 : 0.0;
+    if constexpr (MODE == NN_FUSED) {
+        w += dv;
+        acc[3] += (double)w * (double)w;
+    } else {
+        w = dv;
+    }
+    z = zn;
+    u = un;
+}
+
+// `vec`: every pointer is 16-byte aligned and the whole groups of four go through 16-byte accesses; the tail, and everything where
+// a pointer is not aligned, takes the scalar path.  w: r (NN_FUSED, read and written), dv (NN_DV, written) or unused.
+// part[k * gridDim.x + block]: the block's sum k
+template <int MODE>
+__global__ __launch_bounds__(RED_TPB) void nn_project_kernel(const float *x, float *z, float *u, float *w, long n, float rho, int vec,
+                                                             double *__restrict__ part) {
+    const long stride = (long)gridDim.x * RED_TPB, tid = (long)blockIdx.x * RED_TPB + threadIdx.x;
+    const long n4 = vec ? n / 4 : 0;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (long c = tid; c < n4; c += stride) {
+        const float4 xv = reinterpret_cast<const float4 *>(x)[c];
+        float4 zv = reinterpret_cast<float4 *>(z)[c], uv = reinterpret_cast<float4 *>(u)[c], wv = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (MODE == NN_FUSED) wv = reinterpret_cast<float4 *>(w)[c];
+        nn_element<MODE>(xv.x, zv.x, uv.x, wv.x, rho, acc);
+        nn_element<MODE>(xv.y, zv.y, uv.y, wv.y, rho, acc);
+        nn_element<MODE>(xv.z, zv.z, uv.z, wv.z, rho, acc);
+        nn_element<MODE>(xv.w, zv.w, uv.w, wv.w, rho, acc);
+        reinterpret_cast<float4 *>(z)[c] = zv;
+        reinterpret_cast<float4 *>(u)[c] = uv;
+        if constexpr (MODE != NN_PLAIN) reinterpret_cast<float4 *>(w)[c] = wv;
+    }
+    for (long i = 4 * n4 + tid; i < n; i += stride) {
+        float zi = z[i], ui = u[i], wi = 0.f;
+        if constexpr (MODE == NN_FUSED) wi = w[i];
+        nn_element<MODE>(x[i], zi, ui, wi, rho, acc);
+        z[i] = zi;
+        u[i] = ui;
+        if constexpr (MODE != NN_PLAIN) w[i] = wi;
+    }
+    block_sums_to<4>(acc, part);
+}
+
+// out += c (a - b)   (b NULL: out += c a)
+__global__ __launch_bounds__(RED_TPB) void nn_add_kernel(float *__restrict__ out, const float *__restrict__ a, const float *__restrict__ b, long n,
+                                                         float c) {
+    const long stride = (long)gridDim.x * RED_TPB;
+    for (long i = (long)blockIdx.x * RED_TPB + threadIdx.x; i < n; i += stride) out[i] += c * (b ? a[i] - b[i] : a[i]);
+}
+
+inline bool aligned16(const void *q) { return reinterpret_cast<uintptr_t>(q) % 16 == 0; }
+}  // namespace
+
+// sums[0..3] (device) = |x - z'|^2, |z' - z|^2, #{z' == 0}, r.r of the updated r (0 without r); scratch: 1024 doubles.  r and dv
+// are alternatives (r wins); with neither only z and u move
+int launch_nn_project(hipStream_t s, const float *x, float *z, float *u, float *r, float *dv, long n, float rho, double *scratch,
+                      double *sums) {
+    if (n < 0) return (int)hipErrorInvalidValue;
+    float *const w = r ? r : dv;
+    const int vec = aligned16(x) && aligned16(z) && aligned16(u) && aligned16(w);
+    const long items = vec ? n / 4 + n % 4 : n;
+    const unsigned grid = (unsigned)std::max<long>(1, std::min<long>((items + RED_TPB - 1) / RED_TPB, NN_MAX_BLOCKS));
+    if (r) hipLaunchKernelGGL(nn_project_kernel<NN_FUSED>, dim3(grid), dim3(RED_TPB), 0, s, x, z, u, w, n, rho, vec, scratch);
+    else if (dv) hipLaunchKernelGGL(nn_project_kernel<NN_DV>, dim3(grid), dim3(RED_TPB), 0, s, x, z, u, w, n, rho, vec, scratch);
+    else hipLaunchKernelGGL(nn_project_kernel<NN_PLAIN>, dim3(grid), dim3(RED_TPB), 0, s, x, z, u, w, n, rho, vec, scratch);
+    if (const int rc = (int)hipGetLastError()) return rc;
+    hipLaunchKernelGGL(parts_reduce_kernel, dim3(4), dim3(RED_TPB), 0, s, scratch, (int)grid, sums);
+    return (int)hipGetLastError();
+}
+int launch_nn_add(hipStream_t s, float *out, const float *a, const float *b, long n, float c) {
+    if (n <= 0) return 0;
+    const unsigned grid = (unsigned)std::max<long>(1, std::min<long>((n + RED_TPB - 1) / RED_TPB, 2048));
+    hipLaunchKernelGGL(nn_add_kernel, dim3(grid), dim3(RED_TPB), 0, s, out, a, b, n, c);
+    return (int)hipGetLastError();
+}
+
+extern "C" {
+
+int surfh_nn_project_dev(surfh_plan *p, const float *x_dev, float *z_dev, float *u_dev, float *r_dev, float *dv_dev, int64_t n, double rho,
+                         double *sums) {
+    if (!p || !x_dev || !z_dev || !u_dev || !sums) return fail("null argument");
+    if (n < 0) return fail("surfh_nn_project_dev: n = %ld", (long)n);
+    if (!(rho > 0.0 && rho <= DBL_MAX)) return fail("surfh_nn_project_dev: rho = %g must be finite and > 0", rho);
+    HIP_OK(hipSetDevice(p->dev));
+    {
+        Prof pr(p, "nn_project");
+        LAUNCH_OK(launch_nn_project(p->stream, x_dev, z_dev, u_dev, r_dev, dv_dev, n, (float)rho, p->dscratch, p->dscal + 8));
+    }
+    HIP_OK(hipMemcpyAsync(sums, p->dscal + 8, 4 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+}  // extern "C"

@@ -253,6 +253,10 @@ struct surfh_plan {
     const float *cg_extra = nullptr;
     float *po_y = nullptr, *po_eps = nullptr, *po_er = nullptr, *po_ec = nullptr, *po_eta = nullptr, *po_xhat = nullptr;
     double *po_S = nullptr;
+    // non-negative fusion (surfh_cg_nonneg, surfh_cg_templates_nonneg), for the duration of one call (NnScope): the penalty -- the
+    // operator of the CG frame is Q + nn_rho I while it is set -- and the split variable, the scaled dual and a work vector
+    double nn_rho = 0.0;
+    float *nn_z = nullptr, *nn_u = nullptr, *nn_w = nullptr;
     double *cg_hist = nullptr;                     // device-resident r.r trace of the no-host-sync CG blocks (CG_HIST_CAP entries)
     int cg_hist_n = 0;
     // plane-wise CG with device-resident data (surfh_cg_planes_begin_dev / _step_dev): per-plane scalars [3][Lc] (the host-buffer

@@ -550,6 +550,177 @@ int surfh_cg_templates(surfh_plan *p, const float *y, const float *maps, double 
     return surfh_cg_templates_cb(p, y, maps, mu, mu_spec, s0, max_iter, tol, refresh, s_out, grad_norm, nit, nullptr, nullptr);
 }
 
+// ---- non-negative fusion: ADMM in scaled form around the CG frame (kernels and conventions: nonneg.hip) ----
+//   min x^T Q x / 2 - b^T x, x >= 0, with Q and b those of the space's own solver:  x = z, z >= 0, scaled dual u, v = z - u, rho fixed.
+//   x = x0, z = max(x0, 0), u = 0;  r = b + rho v - (Q + rho I) x;  per outer iteration:  d = r and `inner` cg_iteration on Q + rho I
+//   (the space's apply, then q += rho d), no refresh inside;  z' = max(x + u, 0), u' = u + x - z' (nn_project);  r += rho (v' - v), or
+//   r = b + rho v' - (Q + rho I) x every `refresh` outer iterations;  trace row = |x - z'|^2, rho^2 |z' - z|^2, r.r, #{z' == 0};
+//   stop when sqrt(max(rho^2 row[0], row[1])) < n tol.  The result is z: feasible by construction.
+// The spectra keep x, r, d in their basis (orthonormal: rho I stays rho I) and z, u on the pixels: x goes there through
+// surfh_from_spec_dev, nn_project leaves dv = rho (v' - v), which comes back through surfh_to_spec_dev.
+namespace {
+struct NnScope {                       // the penalty and the extra vectors never outlive a solve
+    surfh_plan *p;
+    explicit NnScope(surfh_plan *pl) : p(pl) {}
+    int begin(double rho, long n) {
+        const size_t pitch = ((size_t)n + 3) / 4 * 4;      // each vector 16-byte aligned
+        if (dev_alloc(&p->nn_z, 3 * pitch)) return 1;
+        p->nn_u = p->nn_z + pitch;
+        p->nn_w = p->nn_u + pitch;
+        p->nn_rho = rho;
+        return 0;
+    }
+    ~NnScope() {
+        if (p->nn_z) {
+            hipStreamSynchronize(p->stream);
+            hipFree(p->nn_z);
+        }
+        p->nn_z = p->nn_u = p->nn_w = nullptr;
+        p->nn_rho = 0.0;
+    }
+};
+int nn_rho_add(surfh_plan *p, const CgSpace &s, const float *v) {                           // q += rho v: the operator is Q + rho I
+    LAUNCH_OK(launch_nn_add(p->stream, s.q, v, nullptr, s.len, (float)p->nn_rho));
+    return 0;
+}
+int nn_img_apply(surfh_plan *p, const CgSpace &s, const float *v) { return img_apply(p, s, v) || nn_rho_add(p, s, v); }
+int nn_spec_apply(surfh_plan *p, const CgSpace &s, const float *v) { return spec_apply(p, s, v) || nn_rho_add(p, s, v); }
+int nn_tpl_apply(surfh_plan *p, const CgSpace &s, const float *v) { return tpl_apply(p, s, v) || nn_rho_add(p, s, v); }
+int nn_refuse(const char *who, double rho, int32_t outer, int32_t inner) {
+    if (!(rho > 0.0 && rho <= DBL_MAX)) return fail("%s: rho = %g must be finite and > 0", who, rho);
+    if (inner < 1) return fail("%s: inner = %d (at least 1)", who, inner);
+    if (outer < 0) return fail("%s: outer = %d", who, outer);
+    return 0;
+}
+// r += c (a - b) for pixel vectors a, b where r lives in the spectra (through nn_w and s.q, both free between iterations)
+int nn_spec_add(surfh_plan *p, const CgSpace &s, const float *a, const float *b, long m, double c) {
+    Prof pr(p, "nn_spec");
+    LAUNCH_OK(launch_fill_zero(p->stream, p->nn_w, m));
+    LAUNCH_OK(launch_nn_add(p->stream, p->nn_w, a, b, m, 1.f));
+    if (surfh_to_spec_dev(p, p->nn_w, s.q)) return 1;
+    LAUNCH_OK(launch_nn_add(p->stream, s.r, s.q, nullptr, s.len, (float)c));
+    return 0;
+}
+// After cg_start on `s` (r = b - Q x, trace entry 0) inside an NnScope.  `sx`: s with rho v added by its apply; spectral: x, r, d are spectra and
+// s.xc the pixels; h0 [m]: the start on the host (NULL: zeros), m the floats of z.  out [m], trace [outer + 1][4]
+int nn_loop(surfh_plan *p, const CgSpace &s, const CgSpace &sx, bool spectral, const float *h0, long m, int32_t outer, int32_t inner,
+            double tol, int32_t refresh, float *out, double *trace, int32_t *nit) {
+    hipStream_t st = p->stream;
+    const double rho = p->nn_rho;
+    double *const sums = p->dscal + 8;
+    const float *const xp = spectral ? s.xc : s.x;                                         // the iterate on the pixels
+    double pp0 = 0.0, active0 = (double)m;
+    HIP_OK(hipMemsetAsync(p->nn_u, 0, m * sizeof(float), st));
+    if (h0) {
+        std::vector<float> hz((size_t)m);
+        active0 = 0.0;
+        for (long i = 0; i < m; ++i) {
+            hz[i] = h0[i] > 0.f ? h0[i] : 0.f;
+            const double e = (double)h0[i] - (double)hz[i];
+            pp0 += e * e;
+            active0 += hz[i] == 0.f ? 1.0 : 0.0;
+        }
+        HIP_OK(hipMemcpyAsync(p->nn_z, hz.data(), m * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_OK(hipStreamSynchronize(st));                                                   // hz leaves scope
+        if (pp0 > 0.0) {                                                                    // r += rho (z - x): v = z, and the rho x of the operator
+            if (spectral) {
+                if (nn_spec_add(p, s, p->nn_z, xp, m, rho)) return 1;
+            } else LAUNCH_OK(launch_nn_add(st, s.r, p->nn_z, xp, m, (float)rho));
+            if (s.rr0(p, s)) return 1;
+        }
+    } else HIP_OK(hipMemsetAsync(p->nn_z, 0, m * sizeof(float), st));
+    double rr = 0.0;
+    if (s.trace(p, s, &rr, 0)) return 1;
+    trace[0] = pp0; trace[1] = 0.0; trace[2] = rr; trace[3] = active0;
+    *nit = 0;
+    for (int k = 0; k < outer; ++k) {
+        HIP_OK(hipMemcpyAsync(s.d, s.r, s.len * sizeof(float), hipMemcpyDeviceToDevice, st));
+        for (int j = 0; j < inner; ++j)
+            if (cg_iteration(p, sx, j, 0)) return 1;
+        if (spectral) {
+            Prof pr(p, "nn_spec");
+            if (surfh_from_spec_dev(p, s.x, s.xc)) return 1;
+        }
+        {
+            Prof pr(p, "nn_project");
+            LAUNCH_OK(launch_nn_project(st, xp, p->nn_z, p->nn_u, spectral ? nullptr : s.r, spectral ? p->nn_w : nullptr, m, (float)rho,
+                                        p->dscratch, sums));
+        }
+        const bool fresh = refresh_due(refresh, k + 1);
+        if (fresh) {                                                                        // r = b + rho v' - (Q + rho I) x
+            if (sx.apply(p, sx, s.x)) return 1;
+            LAUNCH_OK(launch_residual(st, s.r, s.b, s.q, s.len));
+            if (spectral) {
+                if (nn_spec_add(p, s, p->nn_z, p->nn_u, m, rho)) return 1;
+            } else LAUNCH_OK(launch_nn_add(st, s.r, p->nn_z, p->nn_u, m, (float)rho));
+        } else if (spectral) {                                                              // r += dv in the spectra
+            Prof pr(p, "nn_spec");
+            if (surfh_to_spec_dev(p, p->nn_w, s.q)) return 1;
+            LAUNCH_OK(launch_nn_add(st, s.r, s.q, nullptr, s.len, 1.f));
+        }
+        if (spectral || fresh) {
+            if (s.rr0(p, s)) return 1;
+        } else HIP_OK(hipMemcpyAsync(s.rr, sums + 3, sizeof(double), hipMemcpyDeviceToDevice, st));    // the pass summed the new r.r
+        double h[4];
+        HIP_OK(hipMemcpyAsync(h, sums, sizeof h, hipMemcpyDeviceToHost, st));
+        if (s.trace(p, s, &rr, 0)) return 1;                                                // synchronises
+        double *row = trace + 4 * (size_t)(k + 1);
+        row[0] = h[0]; row[1] = rho * rho * h[1]; row[2] = rr; row[3] = h[2];
+        *nit = k + 1;
+        if (std::sqrt(std::max(rho * rho * row[0], row[1])) < (double)s.n * tol) break;
+    }
+    HIP_OK(hipMemcpyAsync(out, p->nn_z, m * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return 0;
+}
+}  // namespace
+
+int surfh_cg_nonneg(surfh_plan *p, const float *y, double mu, double mu_reg, double rho, const float *x0, int32_t outer, int32_t inner,
+                    double tol, int32_t refresh, float *x, double *trace, int32_t *nit) {
+    if (!p || !y || !x || !trace || !nit) return fail("null argument");
+    if (nn_refuse("surfh_cg_nonneg", rho, outer, inner)) return 1;
+    if (p->T <= 0) return fail("surfh_cg_nonneg needs templates (the constraint is on the abundance maps)");
+    if (imager_refuse(p, "surfh_cg_nonneg")) return 1;
+    HIP_OK(hipSetDevice(p->dev));
+    if (ensure_cg(p)) return 1;
+    const bool spectral = cg_spectral(p, inner);
+    const CgSpace s = spectral ? spectral_space(p, mu, mu_reg) : maps_space(p, mu, mu_reg);
+    CgSpace sx = s;
+    sx.apply = spectral ? nn_spec_apply : nn_img_apply;
+    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    if (spectral && x0) HIP_OK(hipMemcpyAsync(s.xc, x0, p->isize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    if ((!spectral && start_iterate(p, x0)) || cg_start(p, s, p->io_y, x0 ? s.xc : nullptr)) return 1;
+    NnScope sc(p);
+    if (sc.begin(rho, p->isize)) return 1;
+    return nn_loop(p, s, sx, spectral, x0, p->isize, outer, inner, tol, refresh, x, trace, nit);
+}
+
+int surfh_cg_templates_nonneg(surfh_plan *p, const float *y, const float *maps, double mu, double mu_spec, double rho, const float *s0,
+                              int32_t outer, int32_t inner, double tol, int32_t refresh, float *s_out, double *trace, int32_t *nit) {
+    if (!p || !y || !maps || !s_out || !trace || !nit) return fail("null argument");
+    if (nn_refuse("surfh_cg_templates_nonneg", rho, outer, inner)) return 1;
+    if (p->im_g)
+        return fail("surfh_cg_templates_nonneg does not carry the imager data term, and the attached imager was built from the plan's "
+                    "templates: detach it (surfh_set_imager(plan, NULL)) first");
+    if (!(mu >= 0.0 && mu <= DBL_MAX) || !(mu_spec >= 0.0 && mu_spec <= DBL_MAX))
+        return fail("surfh_cg_templates_nonneg: mu and mu_spec must be finite and >= 0");
+    HIP_OK(hipSetDevice(p->dev));
+    if (tpl_ensure(p) || ensure_cg(p)) return 1;
+    const CgSpace s = tpl_space(p, mu, mu_spec);
+    CgSpace sx = s;
+    sx.apply = nn_tpl_apply;
+    std::vector<float> h((size_t)s.len);
+    if (s0) std::copy(s0, s0 + s.len, h.begin());
+    else for (long i = 0; i < s.len; ++i) h[i] = (float)p->tpl_host[i];
+    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    HIP_OK(hipMemcpyAsync(p->cg_x, maps, p->isize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    HIP_OK(hipMemcpyAsync(s.x, h.data(), s.len * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    TplScope tsc(p);
+    NnScope sc(p);
+    if (tsc.begin() || cg_start(p, s, p->io_y, nullptr) || sc.begin(rho, s.len)) return 1;
+    return nn_loop(p, s, sx, false, h.data(), s.len, outer, inner, tol, refresh, s_out, trace, nit);
+}
+
 // out[0] = J(x, S) = (mu out[1] + mu_reg out[2] + mu_spec out[3]) / 2 at the plan's templates S: out[1] = (y - A x)^T W (y - A x) under
 // the plan's data weights, out[2] = x^T (the plan's spatial prior) x, out[3] = |D S|^2 along the wavelength -- float64 sums on the device
 int surfh_joint_criterion(surfh_plan *p, const float *y, const float *maps, double mu, double mu_reg, double mu_spec, double *out) {

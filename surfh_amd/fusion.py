@@ -285,7 +285,8 @@ class RefineResult:
     terms: np.ndarray                   # (data, spatial prior, spectral prior) behind every entry of ``criterion``
 
 
-def refine_templates(model, data, mu, mu_reg, mu_spec, rounds, map_iter, tpl_iter, weights=None, x0=None):
+def refine_templates(model, data, mu, mu_reg, mu_spec, rounds, map_iter, tpl_iter, weights=None, x0=None, nonneg=False, rho=None,
+                     inner=10):
     """Alternating minimisation of the joint criterion of ``surfh_amd.spectra``,
     ``J(x, S) = [mu (y - A(S) x)^T W (y - A(S) x) + mu_reg (|Dr x|^2 + |Dc x|^2) + mu_spec |D_l S|^2] / 2``:
     ``rounds`` times ``map_iter`` iterations of ``model.cg`` on the maps from the current maps, then ``tpl_iter`` iterations of
@@ -295,7 +296,21 @@ def refine_templates(model, data, mu, mu_reg, mu_spec, rounds, map_iter, tpl_ite
 
     There is no rescaling between the steps: the model is invariant under ``s_t -> c s_t``, ``x_t -> x_t / c``, and that scale is
     left to the two priors.  ``x0`` None: maps of zeros.  The model's templates are left at the refined ones; the ones it held on
-    entry come back in the result."""
+    entry come back in the result.
+
+    ``nonneg=True``: both half-steps under their constraint, ``x >= 0`` and ``S >= 0`` -- a non-negative bilinear factorisation of
+    the data: ``map_iter`` outer iterations of ``model.cg_nonneg`` and ``tpl_iter`` of ``model.cg_templates_nonneg``, ``inner`` CG
+    iterations each, every step from the previous feasible result.  ``rho``: the penalty of both steps, a pair (maps, spectra), or
+    None: both estimated once, at the start (``nonneg_rho``, ``nonneg_rho_templates`` at the maps' first result).  A truncated
+    ADMM step returns its feasible iterate, not a minimiser along a descent path, so the "cannot raise ``J``" guarantee above does
+    not carry over: the returned criterion trace is then the evidence."""
+    if nonneg:
+        from .nonneg import check_nonneg_args
+        rho_x, rho_s = rho if isinstance(rho, (tuple, list)) else (rho, rho)
+        for r in (rho_x, rho_s):
+            check_nonneg_args(r, 0, inner, 0, "refine_templates")
+    elif rho is not None:
+        raise ValueError("refine_templates: rho is the penalty of the non-negative steps (nonneg=True)")
     start = np.array(model.templates, dtype=np.float64, copy=True)
     x = np.zeros(model.ishape) if x0 is None else np.array(x0, dtype=np.float64).reshape(model.ishape)
     crit, terms = [], []
@@ -307,6 +322,15 @@ def refine_templates(model, data, mu, mu_reg, mu_spec, rounds, map_iter, tpl_ite
 
     record()
     for _ in range(int(rounds)):
+        if nonneg:
+            res = model.cg_nonneg(data, mu=mu, mu_reg=mu_reg, rho=rho_x, x0=x, outer=map_iter, inner=inner, weights=weights)
+            x, rho_x = res.x, res.rho
+            record()
+            res = model.cg_templates_nonneg(data, x, mu=mu, mu_spec=mu_spec, rho=rho_s, outer=tpl_iter, inner=inner, weights=weights)
+            S, rho_s = res.x, res.rho
+            model.set_templates(S)
+            record()
+            continue
         x = model.cg(data, mu=mu, mu_reg=mu_reg, x0=x, max_iter=map_iter, weights=weights)[0]
         record()
         S = model.cg_templates(data, x, mu=mu, mu_spec=mu_spec, s0=None, max_iter=tpl_iter, weights=weights)[0]

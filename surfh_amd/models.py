@@ -24,6 +24,7 @@ from .linop import LinOp
 from . import potentials as _pot
 from .weights import DataWeights
 from .spectra import TemplateOps
+from .nonneg import NonnegOps
 
 
 def _ptr(t):
@@ -112,7 +113,7 @@ class _InstalledImager:
         return False
 
 
-class spectroSigRLSCT(DataWeights, TemplateOps, _pot.Potentials, LinOp):
+class spectroSigRLSCT(DataWeights, TemplateOps, NonnegOps, _pot.Potentials, LinOp):
     huber_prior_value = None            # prior value of the last mmmg(delta=...) result (set by mmmg)
     huber_prior_values = None           # (spatial, spectral) prior values of the last mmmg_vox result
     robust_weights = None               # omega(t) [osize] of the last mmmg / mmmg_vox result under data_delta (else None)

@@ -105,6 +105,35 @@ class TemplateOps:
             raise err[0]
         return out.astype(np.float64).reshape(shape), gn[: nit.value + 1].copy(), nit.value
 
+    def cg_templates_nonneg(self, data, maps, mu=1.0, mu_spec=0.0, rho=None, s0=None, outer=30, inner=10, tol=0.0, refresh=10,
+                            weights=None):
+        """The spectra of ``cg_templates`` under ``S >= 0``: the ADMM loop of ``cg_nonneg`` (surfh_amd/nonneg.py) around the CG of
+        ``cg_templates``, from ``s0`` (None: the model's templates), sizes ``T Lc``.  ``rho=None``: ``nonneg_rho_templates(maps, mu,
+        mu_spec, weights=weights)``.  Returns a ``NonnegResult`` whose ``x`` is ``S`` ``[T, Lc]``; the model's templates are
+        unchanged.  ``ValueError`` for a bad argument, or while an imager is attached."""
+        from . import nonneg
+        nonneg.check_nonneg_args(rho, outer, inner, refresh, "cg_templates_nonneg")
+        self._need_templates()
+        if getattr(self, "_imager", None) is not None:
+            raise ValueError("cg_templates_nonneg does not carry the imager data term and the attached imager was built from the "
+                             "model's templates: detach it (set_imager(None)) first")
+        shape = self.templates.shape
+        y = np.ascontiguousarray(np.asarray(data, dtype=np.float32).reshape(-1))
+        x = np.ascontiguousarray(np.asarray(maps, dtype=np.float32).reshape(-1))
+        if y.size != self.osize or x.size != self.isize:
+            raise ValueError("data or maps size mismatch")
+        s0a = None if s0 is None else check_templates(s0, shape).astype(np.float32).reshape(-1)
+        if rho is None:
+            rho = self.nonneg_rho_templates(maps, mu, mu_spec, weights=weights)
+        out = np.empty(self.templates.size, dtype=np.float32)
+        trace = np.zeros((int(outer) + 1, 4), dtype=np.float64)
+        nit = C.c_int32()
+        with self.installed_weights(weights):
+            _lib.check(self._L.surfh_cg_templates_nonneg(self._plan, _lib.fptr(y), _lib.fptr(x), float(mu), float(mu_spec), float(rho),
+                                                         _lib.fptr(s0a) if s0a is not None else None, int(outer), int(inner), float(tol),
+                                                         int(refresh), _lib.fptr(out), _lib.dptr(trace), C.byref(nit)), ValueError)
+        return nonneg.result_from_trace(out.astype(np.float64).reshape(shape), trace, rho, nit.value)
+
     def joint_criterion(self, data, maps, mu=1.0, mu_reg=0.0, mu_spec=0.0, weights=None):
         """``(J, data term, spatial prior, spectral prior)`` at ``maps`` and the model's templates, summed on the device in float64:
         ``J = (mu data + mu_reg spatial + mu_spec spectral) / 2`` (the module's criterion; ``weights`` as in ``cg``)."""
