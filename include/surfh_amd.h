@@ -581,6 +581,14 @@ int surfh_gemm_selftest_ms(double *ms);
  * Returns the number of tiles, or a negative error.                                                                     */
 int32_t surfh_klist_classify(const float *B, int32_t n, int32_t k, int64_t ldb, int32_t perm_p, int32_t perm_lin,
                              int32_t *records, int64_t capacity);
+/* host only (no GPU, no plan): the launch geometry of the capped-grid kernels, from the functions their launchers call.
+ * out = { grid x, grid y, partial sums the consumer adds (0: none), most loop trips of one thread }.  which:
+ *   "dot" (dot_partial, cg_step, cg_step_parts), "cg_axpy" (cg_dir, cg_xupdate, residual), "cg_dir_parts", "po_data":  a = n
+ *   "robust": a = n, b = V floats per thread (4, 2, 1);  "nn_project": a = n, b = 1 for the 16-byte path
+ *     (trips of the vector loop; the floats behind the last whole group go one to a thread)
+ *   "huber_maps": a, b, c = T, Na, Nb;  "huber_vox": a, b, c = Lc, Na, Nb, out[3] = the most planes of one chunk,
+ *     chunk k of C = out[1] owning planes [Lc k / C, Lc (k + 1) / C)                                                     */
+int surfh_launch_geometry(const char *which, int64_t a, int64_t b, int64_t c, int64_t out[4]);
 /* host only (no GPU): the 2x2 step solve every 3MG solver shares, step = (s0, s1) with [[dBd, dBm], [dBm, mBm]] step = [dg, mg];
  * (0, 0) without curvature along d (dBd <= 0 or NaN), (dg / dBd, 0) without a memory direction (mBm <= 0) or when the scaled
  * system is singular (1 - dBm^2 / (dBd mBm) <= 1e-12) */

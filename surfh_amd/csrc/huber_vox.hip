@@ -107,15 +107,6 @@ __global__ __launch_bounds__(TPB) void huber_vox_curv_kernel(const float *__rest
     block_sums_to<6>(acc, part, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
 }
 
-// tiles x chunks <= VOX_BLOCKS blocks: every tile of 256 pixels its own block where that leaves room, as many chunks as fit
-inline dim3 march_grid(int Lc, int na, int nb) {
-    const long tiles = ((long)na * nb + TPB - 1) / TPB;
-    const int gx = (int)(tiles > VOX_BLOCKS ? VOX_BLOCKS : tiles);
-    int gy = VOX_BLOCKS / gx;
-    if (gy > Lc) gy = Lc;
-    return dim3(gx, gy < 1 ? 1 : gy);
-}
-
 // pot_dispatch on the spatial kind around one on the spectral kind: f(KS) returns what the inner dispatch returned
 template <class F>
 inline bool vox_dispatch(int ks, F &&f) {
@@ -124,6 +115,16 @@ inline bool vox_dispatch(int ks, F &&f) {
 }
 
 }  // namespace
+
+static_assert(TPB == VEC_TPB, "kernels.h states the block size of the capped grids");
+// tiles x chunks <= VOX_BLOCKS blocks: every tile of 256 pixels its own block where that leaves room, as many chunks as fit
+dim3 march_grid(int Lc, int na, int nb) {
+    const long tiles = ((long)na * nb + TPB - 1) / TPB;
+    const int gx = (int)(tiles > VOX_BLOCKS ? VOX_BLOCKS : tiles);
+    int gy = VOX_BLOCKS / gx;
+    if (gy > Lc) gy = Lc;
+    return dim3(gx, gy < 1 ? 1 : gy);
+}
 
 size_t launch_huber_vox_scratch_doubles() { return (size_t)6 * VOX_BLOCKS; }
 

@@ -120,6 +120,18 @@ int launch_ymat_from_y(hipStream_t s, const float *y, float *ymat, int PS, int L
                        unsigned *rowmax = nullptr, int NP = 0);
 int launch_fill_zero(hipStream_t s, float *p, long n);
 
+// ---- launch geometry of the capped-grid kernels ------------------------------------------------------
+// The streaming kernels below launch at most `cap` blocks of VEC_TPB threads and cover the rest of their vector with a
+// grid-stride loop.  The launchers and the host-only hook surfh_launch_geometry (plan_diag.hip) call the same functions.
+constexpr int VEC_TPB = 256;
+constexpr int DOT_BLOCKS = 512;       // dot_partial, cg_step, cg_step_parts: as many float64 partials, summed by the consumer
+constexpr int HUBER_BLOCKS = 256;     // huber_grad, huber_curv (maps): [3][256] partials fit the plan's 1024-double scratch
+int nblocks(long n, int cap = 2048);                  // kernels.hip
+unsigned rob_grid(long n, int V);                     // robust_data.hip: V floats per thread and trip
+unsigned grid_for(long n, long cap = 4096);           // posterior.hip
+unsigned nn_project_grid(long n, int vec);            // nonneg.hip: vec = the 16-byte path
+dim3 march_grid(int Lc, int na, int nb);              // huber_vox.hip: (pixel tiles, wavelength chunks)
+
 // ---- CG vector kernels (qmm.lcg loop body; fusion_CT.py:16-43 priors) --------------------------
 // q += mu_reg * (Dr^T Dr + Dc^T Dc) d   on [T][na][nb], circular
 int launch_prior_add(hipStream_t s, const float *d, float *q, int T, int na, int nb, float mu_reg);

@@ -1450,14 +1450,14 @@ __global__ __launch_bounds__(TPB) void huber_step_planes_kernel(float *__restric
     }
 }
 
-inline int nblocks(long n, int cap = 2048) {
+}  // namespace
+
+static_assert(TPB == VEC_TPB, "kernels.h states the block size of the capped grids");
+int nblocks(long n, int cap) {
     long b = (n + TPB - 1) / TPB;
     if (b < 1) b = 1;
     return (int)(b > cap ? cap : b);
 }
-constexpr int DOT_BLOCKS = 512;
-
-}  // namespace
 
 int launch_specmix_fwd(hipStream_t s, const float *mhat, const float *sotf, const float *tpl, float *spec, int T,
                        long PL, int LP, int ilv) {
@@ -1892,8 +1892,6 @@ int launch_cg_dir_planes(hipStream_t s, float *d, const float *r, int nplanes, l
     return (int)hipGetLastError();
 }
 
-// 256 blocks at most: [3][256] partials fit the plan's 1024-double scratch
-constexpr int HUBER_BLOCKS = 256;
 int launch_huber_grad(hipStream_t s, const float *x, const float *src, float *out, int T, int na, int nb, float coef, float delta,
                       int kind, double *scratch, double *sums) {
     if (T < 1 || na < 1 || nb < 1) return (int)hipErrorInvalidValue;

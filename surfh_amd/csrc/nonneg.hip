@@ -76,6 +76,13 @@ __global__ __launch_bounds__(RED_TPB) void nn_add_kernel(float *__restrict__ out
 inline bool aligned16(const void *q) { return reinterpret_cast<uintptr_t>(q) % 16 == 0; }
 }  // namespace
 
+static_assert(RED_TPB == VEC_TPB, "kernels.h states the block size of the capped grids");
+// a thread takes one group of four (`vec`) or one float per trip; the n % 4 floats behind the groups go one to a thread
+unsigned nn_project_grid(long n, int vec) {
+    const long items = vec ? n / 4 + n % 4 : n;
+    return (unsigned)std::max<long>(1, std::min<long>((items + RED_TPB - 1) / RED_TPB, NN_MAX_BLOCKS));
+}
+
 // sums[0..3] (device) = |x - z'|^2, |z' - z|^2, #{z' == 0}, r.r of the updated r (0 without r); scratch: 1024 doubles.  r and dv
 // are alternatives (r wins); with neither only z and u move
 int launch_nn_project(hipStream_t s, const float *x, float *z, float *u, float *r, float *dv, long n, float rho, double *scratch,
@@ -83,8 +90,7 @@ int launch_nn_project(hipStream_t s, const float *x, float *z, float *u, float *
     if (n < 0) return (int)hipErrorInvalidValue;
     float *const w = r ? r : dv;
     const int vec = aligned16(x) && aligned16(z) && aligned16(u) && aligned16(w);
-    const long items = vec ? n / 4 + n % 4 : n;
-    const unsigned grid = (unsigned)std::max<long>(1, std::min<long>((items + RED_TPB - 1) / RED_TPB, NN_MAX_BLOCKS));
+    const unsigned grid = nn_project_grid(n, vec);
     if (r) hipLaunchKernelGGL(nn_project_kernel<NN_FUSED>, dim3(grid), dim3(RED_TPB), 0, s, x, z, u, w, n, rho, vec, scratch);
     else if (dv) hipLaunchKernelGGL(nn_project_kernel<NN_DV>, dim3(grid), dim3(RED_TPB), 0, s, x, z, u, w, n, rho, vec, scratch);
     else hipLaunchKernelGGL(nn_project_kernel<NN_PLAIN>, dim3(grid), dim3(RED_TPB), 0, s, x, z, u, w, n, rho, vec, scratch);

@@ -131,6 +131,44 @@ int32_t surfh_klist_classify(const float *B, int32_t n, int32_t k, int64_t ldb, 
     return (int32_t)(kl.size() / (size_t)stride);
 }
 
+int surfh_launch_geometry(const char *which, int64_t a, int64_t b, int64_t c, int64_t out[4]) {
+    if (!which || !out) return fail("null argument");
+    const std::string w(which);
+    const auto trips = [](int64_t items, int64_t blocks) { return (items + blocks * VEC_TPB - 1) / (blocks * VEC_TPB); };
+    const auto flat = [&](int64_t grid, int64_t parts, int64_t items) {
+        out[0] = grid; out[1] = 1; out[2] = parts; out[3] = trips(items, grid);
+    };
+    const bool cube = w == "huber_maps" || w == "huber_vox";
+    if (a < 1 || (cube && (b < 1 || c < 1 || a > INT32_MAX || b > INT32_MAX || c > INT32_MAX || b * c > INT32_MAX)))
+        return fail("surfh_launch_geometry: bad size (%lld, %lld, %lld)", (long long)a, (long long)b, (long long)c);
+    if (w == "dot") {                     // dot_partial, cg_step, cg_step_parts: one partial per block
+        const int g = nblocks(a, DOT_BLOCKS);
+        flat(g, g, a);
+    } else if (w == "cg_axpy") {          // cg_dir, cg_xupdate, residual
+        flat(nblocks(a), 0, a);
+    } else if (w == "cg_dir_parts") {     // every block sums the partials of the dot kernel before it
+        flat(nblocks(a), nblocks(a, DOT_BLOCKS), a);
+    } else if (w == "po_data") {
+        flat(grid_for(a), 0, a);
+    } else if (w == "robust") {           // the vector loop; the a % b floats behind it go one to a thread
+        if (b != 1 && b != 2 && b != 4) return fail("surfh_launch_geometry: V = %lld", (long long)b);
+        const unsigned g = rob_grid(a, (int)b);
+        flat(g, g, a / b);
+    } else if (w == "nn_project") {       // likewise: groups of four on the 16-byte path
+        const unsigned g = nn_project_grid(a, b == 1);
+        flat(g, g, b == 1 ? a / 4 : a);
+    } else if (w == "huber_maps") {
+        const int g = nblocks(a * b * c, HUBER_BLOCKS);
+        flat(g, g, a * b * c);
+    } else if (w == "huber_vox") {        // chunk k owns planes [a k / C, a (k + 1) / C): the longest has ceil(a / C)
+        const dim3 g = march_grid((int)a, (int)b, (int)c);
+        out[0] = g.x; out[1] = g.y; out[2] = (int64_t)g.x * g.y; out[3] = (a + g.y - 1) / g.y;
+    } else {
+        return fail("surfh_launch_geometry: unknown kernel family '%s'", which);
+    }
+    return 0;
+}
+
 int surfh_mm_step2(double dBd, double dBm, double mBm, double dg, double mg, double step[2]) {
     if (!step) return fail("null argument");
     mm_step2(dBd, dBm, mBm, dg, mg, &step[0], &step[1]);

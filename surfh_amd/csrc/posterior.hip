@@ -128,8 +128,6 @@ __global__ __launch_bounds__(TPB) void po_finish_kernel(const float *__restrict_
         }
 }
 
-inline unsigned grid_for(long n, long cap = 4096) { return (unsigned)std::max<long>(1, std::min<long>((n + TPB - 1) / TPB, cap)); }
-
 template <int T>
 int moments_T(hipStream_t s, int Tn, const float *x, const float *xhat, double *S, long npix) {
     if constexpr (T <= SURFH_MAX_TEMPLATES) {
@@ -151,6 +149,9 @@ int finish_T(hipStream_t s, int Tn, const float *xhat, const double *S, long npi
     }
 }
 }  // namespace
+
+static_assert(TPB == VEC_TPB, "kernels.h states the block size of the capped grids");
+unsigned grid_for(long n, long cap) { return (unsigned)std::max<long>(1, std::min<long>((n + TPB - 1) / TPB, cap)); }
 
 int launch_randn(hipStream_t s, float *out, long n, uint64_t seed, uint32_t stream, uint32_t sample) {
     if (n <= 0) return 0;

@@ -171,12 +171,13 @@ inline int vec_width(std::initializer_list<const void *> ptrs) {
     for (const void *q : ptrs) bits |= (uintptr_t)q;
     return (bits & 15) == 0 ? 4 : (bits & 7) == 0 ? 2 : 1;
 }
-inline unsigned rob_grid(long n, int V) {
+}  // namespace
+
+static_assert(TPB == VEC_TPB, "kernels.h states the block size of the capped grids");
+unsigned rob_grid(long n, int V) {
     const long want = (n / V + TPB - 1) / TPB;
     return (unsigned)(want > ROB_BLOCKS ? ROB_BLOCKS : want < 1 ? 1 : want);
 }
-
-}  // namespace
 
 #define ROB_DISPATCH(V, kernel, grid, ...)                                                                   \
     switch (V) {                                                                                             \

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import problems
+from capped_cases import AXPY, CG_OLD, CG_SIZES, EPS, cg_vectors, within
 from helpers import TOL, build_model, local_errs, rel, slice_err
 from oracle import surfh_oracle as orc
 from test_gpu_parity import note, oracle_xs
@@ -438,10 +439,8 @@ def test_transforms_local(shape):
 
 
 # ---- the CG vector kernels against float64 numpy -------------------------------------------------------------------------------
-EPS = 2.0 ** -24          # unit roundoff of fp32
-# x + s d evaluated in fp32 from fp32 x, d and a float64 s: s rounded to fp32, the product, the sum (or one fused rounding) --
-# three roundings of at most EPS each, relative to |x| + |s d|; 4 EPS covers their second-order terms
-AXPY = 4 * EPS
+# EPS (the unit roundoff of fp32), the AXPY bound, the vectors and the element-wise comparison: tests/capped_cases.py, which
+# also names the regime every n below is in (tests/test_capped_grid_host.py asserts it)
 
 
 @pytest.fixture(scope="module")
@@ -449,14 +448,6 @@ def vec_plan():
     m = build_model(problems.config1())
     yield m
     m.close()
-
-
-def cg_vectors(n, seed):
-    rng = np.random.default_rng(seed)
-    x, r, d = (rng.standard_normal(n).astype(np.float32) for _ in range(3))
-    q = ((0.5 + rng.random(n)) * d + 0.1 * rng.standard_normal(n)).astype(np.float32)      # d.q > 0, as under a positive operator
-    b = rng.standard_normal(n).astype(np.float32)
-    return x, r, d, q, b
 
 
 def dev(*arrays):
@@ -470,25 +461,23 @@ def host(t):
     return t.cpu().numpy()
 
 
-def within(got, want, scale, what):
-    """|got - want| <= scale element-wise (float64 ``want``); the failure names the worst element."""
-    d = np.abs(got.astype(np.float64) - want) - scale
-    k = int(np.argmax(d))
-    assert d[k] <= 0, f"{what}: element {k} is {got[k]!r}, float64 gives {want[k]!r}, allowed {scale[k]:.3e}"
-
-
-@pytest.mark.parametrize("n", [1, 255, 1101, 3840, 100003])
+@pytest.mark.parametrize("n", CG_OLD + CG_SIZES)
 def test_cg_vector_kernels(vec_plan, n):
-    """single lane, partial block, an odd detector-axis length, config 1's osize, several blocks with a tail"""
+    """single lane, partial block, an odd detector-axis length, config 1's osize, several blocks with a tail; past the launch
+    caps: the first element of the dot kernels' second trip, ragged second (2048 blocks) and fifth (512 blocks) trips"""
     m = vec_plan
     x, r, d, q, b = cg_vectors(n, 200 + n)
     x64, r64, d64, q64, b64 = (v.astype(np.float64) for v in (x, r, d, q, b))
     # dot
     xt, rt, dt, qt, bt = dev(x, r, d, q, b)
+    dot_errs = []
     for a_t, b_t, want in ((dt, qt, d64 @ q64), (rt, rt, r64 @ r64), (xt, bt, x64 @ b64)):
         got = m.dot_dev(a_t, b_t, n)
         scale = float(np.abs(host(a_t).astype(np.float64)) @ np.abs(host(b_t).astype(np.float64)))
+        dot_errs.append(abs(got - want) / scale)
         assert abs(got - want) <= 1e-6 * abs(want) and abs(got - want) <= 1e-14 * scale, (n, got, want)      # fp64 sums of exact products
+        assert m.dot_dev(a_t, b_t, n) == got                                       # a fixed order: the same bits again
+    note("local_cg_dot", n=n, err_of_sum_abs=dot_errs)
     # residual: one fp32 subtraction
     out = dev(np.full(n, 7.0, dtype=np.float32))[0]
     m.residual_dev(out, bt, qt, n)
@@ -522,10 +511,11 @@ def test_cg_vector_kernels(vec_plan, n):
     assert rrf == rr1 and np.array_equal(host(xf), x1) and np.array_equal(host(rf), r1) and np.array_equal(host(df), d1)
 
 
-@pytest.mark.parametrize("n", [1, 255, 1101, 3840, 100003])
+@pytest.mark.parametrize("n", CG_OLD + CG_SIZES)
 def test_cg_nosync_sequence(vec_plan, n):
     """The device-resident scalars: two iterations and one residual refresh without a host synchronisation leave the vectors of
-    the synchronous calls, bit for bit, and a trace equal to the scalars those calls returned."""
+    the synchronous calls, bit for bit, and a trace equal to the scalars those calls returned.  From n = 131 073 on the
+    direction kernel runs more blocks than it sums partials (513 over 512)."""
     m = vec_plan
     x, r, d, q, b = cg_vectors(n, 300 + n)
     rng = np.random.default_rng(400 + n)
@@ -556,6 +546,7 @@ def test_cg_nosync_sequence(vec_plan, n):
     r3 = host(rn)
     within(r3, r3_64, EPS * np.abs(r3_64), "refresh r")
     own = float(r3.astype(np.float64) @ r3.astype(np.float64))
+    note("local_cg_nosync", n=n, refresh_rr_vs_own_r=abs(tr[3] - own) / own)
     assert abs(tr[3] - own) <= 1e-14 * own
     beta = tr[3] / rr2
     within(host(dn), r3.astype(np.float64) + beta * d2_64, AXPY * (np.abs(r3.astype(np.float64)) + np.abs(beta * d2_64)), "refresh d")

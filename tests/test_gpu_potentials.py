@@ -19,6 +19,11 @@ import potentials_oracle as po
 import problems
 import robust_oracle as ro
 import vox_oracle as vo
+from capped_cases import COEF, DELTA, HUGE, SPAT, TINY
+from capped_cases import curv_err as _curv_err
+from capped_cases import pot_arrays as _arrays
+from capped_cases import spat_want as _spat_want
+from capped_cases import spec_want as _spec_want
 from helpers import build_model, make_ifu, rel
 from oracle import surfh_oracle as orc
 from surfh_amd import potentials as P
@@ -26,8 +31,7 @@ from surfh_amd import potentials as P
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = po.NEW_KINDS
-DELTA, COEF, TINY, HUGE = 0.3, 0.7, 1e-20, 1e5
-SPAT = ((orc.diff_r, orc.diff_r_t), (orc.diff_c, orc.diff_c_t))
+# the arrays (DELTA, COEF, TINY, HUGE are theirs) and the float64 expectations: tests/capped_cases.py, shared with the capped-grid tests
 
 
 def _dev(*arrays):
@@ -62,44 +66,6 @@ def _plane_model(L, na, nb, sotf=None):
         sotf = orc.ir2fr(orc.gaussian_psf(wav, problems.STEP), (na, nb))
     return MRSBlurred(sotf, orc.synthetic_axes(na, s), orc.synthetic_axes(nb, s), make_ifu(hpo.SPEC), s,
                       instru.CoordList([instru.Coord(a, b) for a, b in hpo.PTS]))
-
-
-def _arrays(shape, seed, even_only=False):
-    """x with differences on both sides of DELTA (``even_only``: weights below 1 in the even planes only), g0, p0, p1 -- and the
-    overflow array: constant 8 x 8 blocks of height 0 .. 3e5"""
-    rng = np.random.default_rng(seed)
-    scale = 2 * DELTA
-    if even_only:
-        scale = np.where(np.arange(shape[0]) % 2 == 0, 2 * DELTA, 0.02 * DELTA)[:, None, None]
-    x = (rng.standard_normal(shape) * scale).astype(np.float32)
-    g0, p0, p1 = (rng.standard_normal(shape).astype(np.float32) for _ in range(3))
-    blocks = rng.integers(0, 4, size=(shape[0], -(-shape[1] // 8), -(-shape[2] // 8))).astype(np.float32)
-    xo = (HUGE * np.kron(blocks, np.ones((1, 8, 8), dtype=np.float32)))[:, :shape[1], :shape[2]]
-    return x, g0, p0, p1, np.ascontiguousarray(xo)
-
-
-def _spat_want(x, g0, a, b, coef, delta, kind):
-    """per plane: g0 + coef sum_k D_k^T phi'(D_k x), sum_k sum phi, and the curvature block [L, 3] in float64"""
-    x, a, b = (v.astype(np.float64) for v in (x, a, b))
-    grad = g0.astype(np.float64) + coef * sum(dt(P.dphi(d(x), delta, kind)) for d, dt in SPAT)
-    val = sum(np.sum(P.phi(d(x), delta, kind), axis=(1, 2)) for d, _ in SPAT)
-    curv = np.stack([sum(np.sum(P.weight(d(x), delta, kind) * d(u) * d(v), axis=(1, 2)) for d, _ in SPAT)
-                     for u, v in ((a, a), (a, b), (b, b))], axis=1)
-    return grad, val, curv
-
-
-def _spec_want(x, a, b, coef, delta, kind):
-    x, a, b = (v.astype(np.float64) for v in (x, a, b))
-    if x.shape[0] == 1:
-        return np.zeros_like(x), 0.0, np.zeros(3)
-    grad = coef * vo.diff_l_t(P.dphi(vo.diff_l(x), delta, kind))
-    w = P.weight(vo.diff_l(x), delta, kind)
-    return grad, float(np.sum(P.phi(vo.diff_l(x), delta, kind))), np.array([np.sum(w * vo.diff_l(u) * vo.diff_l(v))
-                                                                             for u, v in ((a, a), (a, b), (b, b))])
-
-
-def _curv_err(got, want):
-    return float(np.max(np.abs(got - want)) / np.max(np.abs(want)))
 
 
 # ---- maps: huber_grad_kernel, huber_curv_kernel -------------------------------------------------------------------------------------

@@ -7,7 +7,9 @@ import pytest
 
 import robust_oracle as ro
 import vox_oracle as vo
+from capped_cases import ROBUST_CALLS, robust_arrays
 from helpers import build_model, rel
+from test_gpu_parity import note
 
 pytestmark = pytest.mark.gpu
 INF = float("inf")
@@ -23,23 +25,14 @@ def setup():
 
 
 # ---- 1. the kernels ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n", [1, 255, 1101, 3840, 100003])
+@pytest.mark.parametrize("n", [1, 255, 1101, 3840, 100003, ROBUST_CALLS[0][0]])
 def test_kernels_match_numpy(setup, n):
-    """single lane, partial block, the odd detector-axis length of the weights test, config 1's osize, multi-block with a tail"""
+    """single lane, partial block, the odd detector-axis length of the weights test, config 1's osize, multi-block with a tail,
+    and 2 100 227: past the 2048 blocks of the 16-byte path, three blocks on a second trip and a tail of 3 (the 8- and 4-byte
+    calls further down are then on their second and fifth trips)"""
     import torch
     _, m = setup
-    rng = np.random.default_rng(100 + n)
-    u = rng.standard_normal(n).astype(np.float32)
-    w = np.exp(rng.uniform(np.log(0.5), np.log(2.0), n)).astype(np.float32)
-    w[rng.random(n) < 0.2] = 0.0
-    if n == 1:
-        w[:] = 1.5
-    t0 = 2 * DD * rng.standard_normal(n)                                      # scaled residuals on both sides of the threshold
-    if n == 1:
-        t0[:] = 2.5 * DD
-    with np.errstate(divide="ignore", invalid="ignore"):
-        y = np.where(w > 0, u + t0 / np.sqrt(w), np.nan).astype(np.float32)   # NaN where the weight is 0
-    p0, p1 = rng.standard_normal(n).astype(np.float32), rng.standard_normal(n).astype(np.float32)
+    u, w, y, p0, p1 = robust_arrays(n)                                        # a fifth masked, NaN there, both sides of the knee
     keep = w > 0
     w64, a, b = w.astype(np.float64), p0.astype(np.float64), p1.astype(np.float64)
     t = np.where(keep, np.sqrt(w64) * (np.where(keep, y, 0.0).astype(np.float64) - u), 0.0)
@@ -64,6 +57,7 @@ def test_kernels_match_numpy(setup, n):
     ep = abs(sums[0][0] - want_s[0]) / want_s[0]
     ec = float(np.max(np.abs(curv[0] - want_c)) / np.max(np.abs(want_c)))
     print(f"n = {n}: beyond {share:.0%}, v {ev:.2e}, sum phi {ep:.2e}, count {sums[0][1]} / {int(want_s[1])}, curvature {ec:.2e}")
+    note("robust_kernels", n=n, v=ev, phi=ep, curv=ec, count_off=abs(sums[0][1] - want_s[1]), near=near)
     assert np.all(np.isfinite(vs[0])) and np.all(vs[0][~keep] == 0.0)
     assert ev < 1e-6 and ep < 1e-6 and ec < 1e-6 and abs(sums[0][1] - want_s[1]) <= near
     assert sums[0] == sums[1] and np.array_equal(vs[0], vs[1]) and np.array_equal(curv[0], curv[1])      # deterministic reductions

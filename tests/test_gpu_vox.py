@@ -20,6 +20,7 @@ from click.testing import CliRunner
 import huber_oracle as ho
 import problems
 import vox_oracle as vo
+from capped_cases import vox_arrays
 from helpers import build_model, rel
 from oracle import surfh_oracle as orc
 
@@ -72,10 +73,8 @@ def _curv_want(x, a, b, ds, dl, weighted=True):
 
 def _check_kernels(m, ds, dl, seed):
     import torch
-    rng = np.random.default_rng(seed)
     Lc, Na, Nb = m.ishape
-    x = (rng.standard_normal(m.ishape) * 2 * ds).astype(np.float32)              # differences on both sides of both thresholds
-    g0, p0, p1 = (rng.standard_normal(m.ishape).astype(np.float32) for _ in range(3))
+    x, g0, p0, p1 = vox_arrays(tuple(m.ishape), ds, seed)                        # differences on both sides of both thresholds
     x64, a, b = x.astype(np.float64), p0.astype(np.float64), p1.astype(np.float64)
     s_spat, s_spec = vo.shares(x64, ds, dl)
     assert 0.1 < s_spat < 0.9 and (Lc == 1 or 0.1 < s_spec < 0.9)
