@@ -1,7 +1,9 @@
 // Internal header of the host side of the C ABI (include/surfh_amd.h), shared by plan.hip (plan build and plan state),
 // plan_ops.hip (operators), plan_solvers.hip (solvers) and plan_diag.hip (diagnostics).  The rule of the split: solvers call the
 // operators, operators read the plan, plan build knows neither operators nor solvers, diagnostics depend on everything and
-// nothing depends on them -- so this header declares only the helpers that cross a file boundary in that direction.
+// nothing depends on them -- so this header declares only the helpers that cross a file boundary in that direction.  What one
+// operator call does beyond the plan -- where its operand comes from, where its result goes -- is its argument (OpCall below):
+// the plan holds what lasts from call to call, never the mode of the next one.
 // Everything shared lives in namespace surfh_impl, which has hidden visibility: the shared object exports the C ABI and nothing else.
 //
 // Data layout: WAVELENGTH IS THE INNERMOST AXIS of every large device array (lambda is the batch
@@ -194,12 +196,6 @@ struct surfh_plan {
     // intermediate in its own buffer, whose columns outside the range stay zero from plan creation on.
     int a_lo = 0, a_hi = 0, b_lo = 0, b_hi = 0;  // (b: the same for the cube rows beta)
     float *ycol_adj = nullptr;
-    // spectral-domain solver calls (surfh_normal_spec_dev ...): the maps' half spectra in Parseval-scaled form go in and out of the
-    // transform passes directly.  Set for the duration of one call.
-    const float *spec_in = nullptr;              // forward: the mix loader reads this instead of mhat
-    float *spec_out = nullptr;                   // adjoint: the fused tail writes this instead of mhat
-    const float *spec_prior_src = nullptr;       // adjoint: + spec_prior_mu * |D|^2 * this (the quadratic prior, world = 1)
-    float spec_mu = 1.f, spec_prior_mu = 0.f;
     float *adjmix_part = nullptr;                // fused adjoint tail (dft_h2_adjmix_kernel): partial sums per (k_beta, slot); null: off
     // Support of the OTF (otf_support below): the (k_beta, chunk of 128 wavelengths) pairs -- super-tiles of the two passes that
     // touch the OTF, index k_beta * (LP / 128) + chunk -- in which some |sotf| exceeds 2^-24 of its plane's largest magnitude.
@@ -237,25 +233,20 @@ struct surfh_plan {
     int *tg_cidx = nullptr, *tg_pidx = nullptr;
     double *tg_part = nullptr;
     float *tg_keep = nullptr, *tg_v[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    // set for the duration of one call: adjoint_dev ends in the template transpose and writes tg_out [T][Lc] (tg_maps: the maps
-    // [T][Na][Nb] on the device, read by the spatial route); forward_dev finds the maps' spectra in mhat already
-    float *tg_out = nullptr;
-    const float *tg_maps = nullptr;
+    // inside one template solve: mhat holds the spectra of the solve's maps (cleared whenever something else may have used mhat);
+    // only the tpl_* callers consult it, to choose the head of their operator calls
     bool tg_mhat_ready = false;
     // CG
     float *cg_x = nullptr, *cg_r = nullptr, *cg_d = nullptr, *cg_q = nullptr, *cg_b = nullptr, *cg_y = nullptr, *cg_qm = nullptr, *cg_dd = nullptr;
     float *cg_hg = nullptr;                        // surfh_mmmg_huber(_vox): -gradient of the non-quadratic criterion
     float *rb_y = nullptr, *rb_u = nullptr, *rb_ag = nullptr, *rb_am = nullptr;   // surfh_mmmg_robust(_vox): y, A x, A (-g), A m [osize]
     double *dscal = nullptr, *dscratch = nullptr;   // [16] device scalars, partial sums (>= 1024, and what huber_vox.hip and robust_data.hip ask for)
-    // posterior sampling (surfh_cg_sample): an extra right-hand side [isize] in the maps' layout that the set-up of the map and
-    // spectral CG spaces adds to b (null outside a sampling solve: the launches are then exactly those without it); y, the noise
-    // vectors eps_y [osize], eps_r / eps_c [isize], eta and the unperturbed solution [isize]; the moment sums (posterior.hip)
-    const float *cg_extra = nullptr;
+    // posterior sampling (surfh_cg_sample): y, the noise vectors eps_y [osize], eps_r / eps_c [isize], eta and the unperturbed
+    // solution [isize]; the moment sums (posterior.hip)
     float *po_y = nullptr, *po_eps = nullptr, *po_er = nullptr, *po_ec = nullptr, *po_eta = nullptr, *po_xhat = nullptr;
     double *po_S = nullptr;
-    // non-negative fusion (surfh_cg_nonneg, surfh_cg_templates_nonneg), for the duration of one call (NnScope): the penalty -- the
-    // operator of the CG frame is Q + nn_rho I while it is set -- and the split variable, the scaled dual and a work vector
-    double nn_rho = 0.0;
+    // non-negative fusion (surfh_cg_nonneg, surfh_cg_templates_nonneg), allocated for one solve (NnScope): the split variable, the
+    // scaled dual and a work vector
     float *nn_z = nullptr, *nn_u = nullptr, *nn_w = nullptr;
     double *cg_hist = nullptr;                     // device-resident r.r trace of the no-host-sync CG blocks (CG_HIST_CAP entries)
     int cg_hist_n = 0;
@@ -267,10 +258,10 @@ struct surfh_plan {
     double pl_mu = 1.0, pl_mu_reg = 0.0;
     int pl_it = 0;
     // ... with its vectors in the cube's wavelength-innermost layout [NBP][NAP][LP] (no layout transpose inside an iteration):
-    // x, r, d, q, b; per-wavelength scalars [3][LP] + partial sums; set while forward_dev / adjoint_dev are called on such vectors
+    // x, r, d, q, b; per-wavelength scalars [3][LP] + partial sums; pn_active: the solve surfh_cg_planes_begin_dev began runs on them
     float *pn_v[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     double *pn_sc = nullptr, *pn_part = nullptr;
-    bool pn_native = false, pn_active = false, pn_fold_prior = false;
+    bool pn_active = false;
     // profiling
     bool prof = false;
     std::string prof_filter;                     // non-empty: only stages whose name starts with it are bracketed by events
@@ -321,6 +312,35 @@ int dev_upload(Tp **p, const std::vector<Tp> &h) {
     return 0;
 }
 
+// ---- the two ends of one operator call ------------------------------------------------------------------------------------------
+// forward_dev reads `head`, adjoint_dev reads `tail`, normal_halves hands both on; the defaults are the plain call on the caller's
+// vectors.  DESIGN.md ("Heads and tails of an operator call") lists which entry point uses which pair.
+struct OpCall {
+    enum Head {
+        H_CALLER,        // x in the caller's layout: the maps as pixels [T][Na][Nb], plane-wise plans (T = 0) the planes [Lc][Na][Nb]
+        H_SPECTRA,       // `spectra_in`: the caller's Parseval-scaled half spectra of the maps, read by the mix loader; x is not read
+        H_MHAT,          // mhat holds the maps' spectra already (inside a template solve); x is not read
+        H_CUBE           // T = 0: x in the cube's wavelength-innermost layout [NBP][NAP][LP]
+    } head = H_CALLER;
+    enum Tail {
+        T_CALLER,        // x in the caller's layout, as H_CALLER
+        T_SPECTRA,       // `spectra_out` = mu * scaled half spectra (+ prior_mu |D|^2 prior_src, the quadratic prior); x is not written
+        T_TEMPLATES,     // the transpose with respect to the templates: `tpl_out` [T][Lc]; `tpl_maps`: the maps on the device
+        T_CUBE           // T = 0: x in the cube's wavelength-innermost layout
+    } tail = T_CALLER;
+    const float *spectra_in = nullptr;
+    float *spectra_out = nullptr, *tpl_out = nullptr;
+    const float *prior_src = nullptr, *tpl_maps = nullptr;
+    // T_SPECTRA, and the T = 0 tails under `fold` -- there mu and the quadratic prior of the plane-wise normal operator go into the
+    // adjoint's OTF product: q = mu A^T A v + prior_mu D^T D v, the spectrum of v still in mhat from the forward half
+    double mu = 1.0, prior_mu = 0.0;
+    bool fold = false;
+    bool ref = false;          // adjoint: the reference's interpolating back-projection (surfh_adjoint_ref)
+    // forward: the caller is the normal operator -- channels with a spectral-blur GEMM do not write y but leave the adjoint's GEMM
+    // operand (fp16 pieces of ymat + row maxima) behind; adjoint: the forward half has just done so.  normal_halves sets it.
+    bool hand_over = false;
+};
+
 // ---- helpers that cross a file boundary (default arguments live here) --------------------------------------------------------
 // plan.hip
 int chain(surfh_plan *p, hipStream_t from, hipStream_t to);
@@ -330,11 +350,11 @@ int build_klist(const float *B, int N, int K, long ldb, int segLinP, int segChun
 // plan_ops.hip
 int prior_add(surfh_plan *p, hipStream_t st, const float *d, float *q, int n_img, float mu_reg);
 bool prod_capable(const surfh_plan *p);
-int forward_dev(surfh_plan *p, const float *x, float *y, bool hand_over = false);
-int adjoint_dev(surfh_plan *p, const float *y, float *x, bool ref, bool handed_over = false);
-int normal_halves(surfh_plan *p, const float *v, float *q);
+int forward_dev(surfh_plan *p, const float *x, float *y, const OpCall &c = {});
+int adjoint_dev(surfh_plan *p, const float *y, float *x, const OpCall &c = {});
+int normal_halves(surfh_plan *p, const float *v, float *q, OpCall c = {});        // A^T W A v, head and tail those of `c`
 const float *weighted_data(surfh_plan *p, const float *y);
-int normal_dev(surfh_plan *p, const float *d, float *q, double mu);
+int normal_dev(surfh_plan *p, const float *d, float *q, double mu, bool cube = false);     // mu A^T W A d; cube: T = 0 vectors in the cube's layout
 int ensure_cg(surfh_plan *p);
 inline bool imager_active(const surfh_plan *p) { return p->im_g && p->im_y && p->im_mu > 0.0; }
 int imager_normal_add(surfh_plan *p, const float *v, float *q);      // q += mu_imager A_im^T W_im A_im v
@@ -343,7 +363,7 @@ int imager_rhs_add(surfh_plan *p, float *b);                         // b += mu_
 int tpl_ensure(surfh_plan *p);                                       // checks the plan (templates, channels) and allocates
 int tpl_maps_spectra(surfh_plan *p, const float *maps);              // mhat = the maps' half spectra
 int tpl_install(surfh_plan *p, const float *S);                      // p->tpl = S in the plan's compact, padded rows
-struct TplScope {                                                    // the plan's own templates come back on every exit
+struct TplScope {                                                    // the plan's own templates come back on every exit (begin() saves them)
     surfh_plan *p;
     bool armed = false;
     explicit TplScope(surfh_plan *pl) : p(pl) {}

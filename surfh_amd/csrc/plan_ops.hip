@@ -122,7 +122,9 @@ int irfft2_lam(surfh_plan *p, const float *src, float *dst) {
 // `acols`: the source cube is zero outside the alpha range [a_lo, a_hi) (the adjoint's accumulator): the first pass
 // transforms only those columns, into ycol_adj whose other columns are zero for good
 // `which`: bit 0 = the pass along beta, bit 1 = the pass along alpha (plans whose axes run on different kernels call one of each)
-int rfft2_lam_h2(surfh_plan *p, const float *src, float *dst, float *madj = nullptr, bool acols = false, int which = 3) {
+// `scaled`: madj is the solver's scaled half spectrum (OpCall::T_SPECTRA): its mu and quadratic prior ride on the tail
+int rfft2_lam_h2(surfh_plan *p, const float *src, float *dst, float *madj = nullptr, bool acols = false, int which = 3,
+                 const OpCall *scaled = nullptr) {
     const long LP = p->LP;
     const int ha = p->Na / 2 + 1, hb = p->Nb / 2 + 1;
     const bool sub = acols && p->ycol_adj && p->a_hi > p->a_lo;
@@ -159,9 +161,9 @@ int rfft2_lam_h2(surfh_plan *p, const float *src, float *dst, float *madj = null
             while (16 * kt0 + 15 < p->a_lo && p->Na - (16 * kt0 + 15) >= p->a_hi && h.KP / 16 - (kt0 + 1) >= 5) ++kt0;
             am.kt0 = kt0;
         }
-        if (p->spec_out && madj == p->spec_out) {      // the solver's scaled half spectrum, mu and the quadratic prior folded in
-            am.out_self = p->spec_mu; am.out_pair = p->spec_mu * 1.41421356237309505f; am.Nb = p->Nb;
-            am.prior_src = p->spec_prior_src; am.prior_mu = p->spec_prior_mu;
+        if (scaled) {
+            am.out_self = (float)scaled->mu; am.out_pair = (float)scaled->mu * 1.41421356237309505f; am.Nb = p->Nb;
+            am.prior_src = scaled->prior_src; am.prior_mu = (float)scaled->prior_mu;
         }
         Prof pr(p, "dft_h2_cols_fwd_adjmix");
         LAUNCH_OK(launch_dft_h2_adjmix(p->stream, h, am, madj, p->PL, p->KBP, p->h2img, p->h2kA[0]));
@@ -176,7 +178,8 @@ int rfft2_lam_h2(surfh_plan *p, const float *src, float *dst, float *madj = null
 
 // spec [KAP][KBP][LP][2] -> cube [NBP][NAP][LP]        (tmp ycol viewed as Y[NAP][KBP][LP][2])
 // `acols`: only the cube columns alpha in [a_lo, a_hi) are wanted (the gathers read nothing else)
-int irfft2_lam_h2(surfh_plan *p, const float *src, float *dst, bool mix, bool acols = false, int which = 3) {
+// `mix`: the maps' spectra the loader of the first pass mixes (null: none) -- the plan's mhat, or the solver's scaled half spectra
+int irfft2_lam_h2(surfh_plan *p, const float *src, float *dst, const float *mix, bool acols = false, int which = 3) {
     const long LP = p->LP;
     const int ha = p->Na / 2 + 1, hb = p->Nb / 2 + 1;
     DftH2Args g;   // c2c along alpha (optionally with the spectral mix formed in the loader)
@@ -185,8 +188,8 @@ int irfft2_lam_h2(surfh_plan *p, const float *src, float *dst, bool mix, bool ac
     g.KP = p->KPa; g.N = (int)(hb * LP);
     g.e[0] = 1.f; g.e[1] = -1.f; g.e[2] = 1.f; g.e[3] = 1.f;
     g.e_alt[0] = 1.f; g.e_alt[1] = 1.f; g.e_alt[2] = 1.f; g.e_alt[3] = -1.f;
-    if (mix) { g.mhat = p->mhat; g.tpl = p->tpl; g.T = p->T; g.LP = (int)p->LP; g.PL = p->PL; g.KBP = p->KBP; }
-    if (mix && p->spec_in) { g.mhat = p->spec_in; g.mhat_self = 1.f; g.mhat_pair = 0.70710678118654752f; g.mix_Nb = p->Nb; }
+    if (mix) { g.mhat = mix; g.tpl = p->tpl; g.T = p->T; g.LP = (int)p->LP; g.PL = p->PL; g.KBP = p->KBP; }
+    if (mix && mix != p->mhat) { g.mhat_self = 1.f; g.mhat_pair = 0.70710678118654752f; g.mix_Nb = p->Nb; }
     // the OTF's support: tiles outside it are neither computed nor stored -- their place in ycol_mix is zero for good
     const bool supp = mix && p->otf_vlist && p->ycol_mix && p->adjmix_part;
     float *const yc = supp ? p->ycol_mix : p->ycol;
@@ -275,7 +278,7 @@ bool prod_capable(const surfh_plan *p) { return p->otf_prod && p->T == 0 && p->i
 namespace {
 
 // spec [KAP][KBP][LP][2] -> cube [NBP][NAP][LP]        (tmp ycol viewed as Y[NAP][KBP][LP][2])
-int irfft2_lam_ct(surfh_plan *p, const float *src, float *dst, bool mix, bool acols = false, int which = 3, const ProdOperand *po = nullptr) {
+int irfft2_lam_ct(surfh_plan *p, const float *src, float *dst, const float *mix, bool acols = false, int which = 3, const ProdOperand *po = nullptr) {
     const long LP = p->LP;
     const int hb = p->Nb / 2 + 1;
     DftCtArgs g;   // c2c along alpha (optionally with the spectral mix formed in the loader)
@@ -284,8 +287,8 @@ int irfft2_lam_ct(surfh_plan *p, const float *src, float *dst, bool mix, bool ac
     g.src = src; g.ldb = 2 * p->KBP * LP;
     g.dst = p->ycol; g.ldc = 2 * p->KBP * LP;
     g.ncols = (int)(hb * LP); g.batch = 1;
-    if (mix) { g.mhat = p->mhat; g.tpl = p->tpl; g.T = p->T; g.LP = (int)p->LP; g.PL = p->PL; g.KBP = p->KBP; }
-    if (mix && p->spec_in) { g.mhat = p->spec_in; g.mhat_self = 1.f; g.mhat_pair = 0.70710678118654752f; g.mix_Nb = p->Nb; }
+    if (mix) { g.mhat = mix; g.tpl = p->tpl; g.T = p->T; g.LP = (int)p->LP; g.PL = p->PL; g.KBP = p->KBP; }
+    if (mix && mix != p->mhat) { g.mhat_self = 1.f; g.mhat_pair = 0.70710678118654752f; g.mix_Nb = p->Nb; }
     if (po && po->prod && !mix) {
         g.loader = DFT_CT_PROD; g.prod = po->prod; g.ldp = g.ldb; g.sP = 0; g.prod_sign = po->sign; g.scale *= po->scale;
         if (po->add && po->add_w != 0.f) {
@@ -323,7 +326,7 @@ int rfft2_lam_ilv(surfh_plan *p, const float *src, float *dst, float *madj = nul
     if (p->ax_b == 1 ? rfft2_lam_h2(p, src, dst, nullptr, acols, 1) : rfft2_lam_ct(p, src, dst, acols, lists, 1)) return 1;
     return p->ax_a == 1 ? rfft2_lam_h2(p, src, dst, nullptr, acols, 2) : rfft2_lam_ct(p, src, dst, acols, lists, 2);
 }
-int irfft2_lam_ilv(surfh_plan *p, const float *src, float *dst, bool mix = false, bool acols = false, const ProdOperand *po = nullptr) {
+int irfft2_lam_ilv(surfh_plan *p, const float *src, float *dst, const float *mix = nullptr, bool acols = false, const ProdOperand *po = nullptr) {
     if (po && p->ax_a != 2) return fail("irfft2: the product loader needs the Cooley-Tukey pass along alpha");
     if (p->h2) return irfft2_lam_h2(p, src, dst, mix, acols);
     if (p->ax_a == 1 ? irfft2_lam_h2(p, src, dst, mix, acols, 2) : irfft2_lam_ct(p, src, dst, mix, acols, 2, po)) return 1;
@@ -334,62 +337,56 @@ int irfft2_lam_ilv(surfh_plan *p, const float *src, float *dst, bool mix = false
 // pipelines on device buffers
 // ---------------------------------------------------------------------------------------------
 int rfft2_cube(surfh_plan *p, const float *src, float *dst) { return p->dense_dft ? rfft2_lam(p, src, dst) : rfft2_lam_ilv(p, src, dst); }
-int irfft2_cube(surfh_plan *p, const float *src, float *dst, bool mix = false, bool acols = false, const ProdOperand *po = nullptr) {
+int irfft2_cube(surfh_plan *p, const float *src, float *dst, const float *mix = nullptr, bool acols = false, const ProdOperand *po = nullptr) {
     if (po && p->dense_dft) return fail("irfft2: the product loader is not part of the dense plan");
     return p->dense_dft ? irfft2_lam(p, src, dst) : irfft2_lam_ilv(p, src, dst, mix, acols, po);
 }
 
 // mhat[t] = sum_l tpl[t][l] conj(sotf[l]) rfft2(cube[l])  (T > 0), or the per-plane product (T == 0)
 // `acols`: the cube is zero outside the alpha range of the channels' tables (the adjoint's accumulator)
-int adjoint_tail(surfh_plan *p, const float *cube, bool acols = false) {
-    if (p->adjmix_part && p->h2 && p->T > 0) return rfft2_lam_h2(p, cube, p->spec, p->spec_out ? p->spec_out : p->mhat, acols);
-    if (p->ct && !p->dense_dft) {
-        if (rfft2_lam_ilv(p, cube, p->spec, nullptr, acols, true)) return 1;
-        if (prod_capable(p)) return 0;      // plane-wise: conj(OTF) x spec is formed by the loader of the inverse transform that follows
-        SpecmixAdjOpt o;
-        o.Na = p->Na; o.KBP = p->KBP;
-        if (p->T > 0 && p->otf_vlist && p->ycol_mix && p->otf_tabs) o.lim = p->otf_tabs + 2 * (p->LP / 128);
-        if (p->spec_out) {      // the solver's scaled half spectrum, mu and the quadratic prior folded in
-            o.Nb = p->Nb; o.out_self = p->spec_mu; o.out_pair = p->spec_mu * 1.41421356237309505f;
-            o.prior_src = p->spec_prior_src; o.prior_mu = p->spec_prior_mu;
-        }
-        Prof pr(p, "specmix_adj");
-        if (p->T == 0 && p->pn_fold_prior) {      // plane-wise normal operator: mu and the quadratic prior in the OTF product (see below)
-            SpecmixAdjOpt o2;
-            o2.Na = p->Na; o2.Nb = p->Nb; o2.KBP = p->KBP; o2.out_self = (float)p->pl_mu; o2.prior_src = p->mhat; o2.prior_mu = (float)p->pl_mu_reg;
-            LAUNCH_OK(launch_specmix_adj(p->stream, p->spec, p->sotf, p->tpl, p->mhat, 0, p->PL, p->LP, false, 1, &o2));
-            return 0;
-        }
-        LAUNCH_OK(launch_specmix_adj(p->stream, p->spec, p->sotf, p->tpl, p->spec_out ? p->spec_out : p->mhat, p->T, p->PL, p->LP, false, 1,
-                                     p->T > 0 ? &o : nullptr));
-        return 0;
-    }
-    if (rfft2_cube(p, cube, p->spec)) return 1;
+// The result goes to mhat, or to the solver's scaled half spectra (c.tail == T_SPECTRA: mu and the quadratic prior folded in).
+int adjoint_tail(surfh_plan *p, const float *cube, bool acols = false, const OpCall &c = {}) {
+    const bool scaled = c.tail == OpCall::T_SPECTRA;
+    float *const out = scaled ? c.spectra_out : p->mhat;
+    if (p->adjmix_part && p->h2 && p->T > 0) return rfft2_lam_h2(p, cube, p->spec, out, acols, 3, scaled ? &c : nullptr);
+    const bool lists = p->ct && !p->dense_dft;      // Cooley-Tukey passes: only the spectrum inside the OTF's support
+    if (lists ? rfft2_lam_ilv(p, cube, p->spec, nullptr, acols, true) : rfft2_cube(p, cube, p->spec)) return 1;
+    if (lists && prod_capable(p)) return 0;         // plane-wise: conj(OTF) x spec is formed by the loader of the inverse transform that follows
+    SpecmixAdjOpt o;
+    o.Na = p->Na; o.KBP = p->KBP;
     Prof pr(p, "specmix_adj");
-    if (p->T == 0 && p->ilv && p->pn_fold_prior) {
+    if (p->T == 0 && p->ilv && c.fold) {
         // plane-wise normal operator: `mhat` still holds the spectrum of the vector the forward half was applied to -- mu and the
         // quadratic prior go into the OTF product, no prior kernel and no scaling pass afterwards
-        SpecmixAdjOpt o;
-        o.Na = p->Na; o.Nb = p->Nb; o.KBP = p->KBP; o.out_self = (float)p->pl_mu; o.prior_src = p->mhat; o.prior_mu = (float)p->pl_mu_reg;
+        o.Nb = p->Nb; o.out_self = (float)c.mu; o.prior_src = p->mhat; o.prior_mu = (float)c.prior_mu;
         LAUNCH_OK(launch_specmix_adj(p->stream, p->spec, p->sotf, p->tpl, p->mhat, 0, p->PL, p->LP, false, 1, &o));
         return 0;
     }
-    LAUNCH_OK(launch_specmix_adj(p->stream, p->spec, p->sotf, p->tpl, p->mhat, p->T, p->PL, p->LP, p->verify, p->ilv));
+    if (!lists) {
+        LAUNCH_OK(launch_specmix_adj(p->stream, p->spec, p->sotf, p->tpl, p->mhat, p->T, p->PL, p->LP, p->verify, p->ilv));
+        return 0;
+    }
+    if (p->T > 0 && p->otf_vlist && p->ycol_mix && p->otf_tabs) o.lim = p->otf_tabs + 2 * (p->LP / 128);
+    if (scaled) {
+        o.Nb = p->Nb; o.out_self = (float)c.mu; o.out_pair = (float)c.mu * 1.41421356237309505f;
+        o.prior_src = c.prior_src; o.prior_mu = (float)c.prior_mu;
+    }
+    LAUNCH_OK(launch_specmix_adj(p->stream, p->spec, p->sotf, p->tpl, out, p->T, p->PL, p->LP, false, 1, p->T > 0 ? &o : nullptr));
     return 0;
 }
 
-// The template transpose's tail (tplgrad.hip): tg_out [T][Lc] = sum over the frequency bins of conj(mhat_t) conj(sotf) rfft2(cube),
+// The template transpose's tail (tplgrad.hip): G [T][Lc] = sum over the frequency bins of conj(mhat_t) conj(sotf) rfft2(cube),
 // `cube` the adjoint's accumulator (zero outside the alpha range of the channels' tables), mhat the spectra of the maps.
 //   interleaved spectra, T <= 4: the whole half spectrum from the unfused passes without the OTF-support lists -- the fused tail
 //     never stores the last pass and the listed passes leave bins outside the support unwritten, so neither serves -- then the
 //     reduction over bins;
 //   dense transforms (verification plans among them) and T > 4: the cube-space adjoint through its OTF^T back to pixels, then the
-//     reduction over pixels against the maps themselves (tg_maps).
-int template_tail(surfh_plan *p, const float *cube) {
+//     reduction over pixels against the maps themselves (`maps`, on the device).
+int template_tail(surfh_plan *p, const float *cube, float *G, const float *maps) {
     if (p->ilv && !p->dense_dft && p->T <= 4) {
         if (rfft2_lam_ilv(p, cube, p->spec, nullptr, true, false)) return 1;
         Prof pr(p, "tplgrad_spec");
-        LAUNCH_OK(launch_tplgrad_spec(p->stream, p->spec, p->sotf, p->mhat, p->tg_part, p->tg_cidx, p->tg_out, p->T, p->Lc, p->Na, p->Nb, p->KBP,
+        LAUNCH_OK(launch_tplgrad_spec(p->stream, p->spec, p->sotf, p->mhat, p->tg_part, p->tg_cidx, G, p->T, p->Lc, p->Na, p->Nb, p->KBP,
                                       p->PL, (int)p->LP));
         return 0;
     }
@@ -400,25 +397,21 @@ int template_tail(surfh_plan *p, const float *cube) {
     }
     if (irfft2_cube(p, p->spec, p->cube)) return 1;
     Prof pr(p, "tplgrad_pix");
-    LAUNCH_OK(launch_tplgrad_pix(p->stream, p->cube, p->tg_maps, p->tg_part, p->tg_cidx, p->tg_out, p->T, p->Lc, p->Na, p->Nb, p->NAP, (int)p->LP));
+    LAUNCH_OK(launch_tplgrad_pix(p->stream, p->cube, maps, p->tg_part, p->tg_cidx, G, p->T, p->Lc, p->Na, p->Nb, p->NAP, (int)p->LP));
     return 0;
 }
 
 }  // namespace
 
-// `hand_over`: the caller is the normal operator -- channels with a spectral-blur GEMM do not write y but leave the adjoint's
-// GEMM operand (fp16 pieces of ymat + row maxima) behind
-int forward_dev(surfh_plan *p, const float *x, float *y, bool hand_over) {
+// y = A x, x where call.head says (OpCall, plan_internal.h)
+int forward_dev(surfh_plan *p, const float *x, float *y, const OpCall &call) {
     hipStream_t s = p->stream;
-    if (p->spec_in || p->tg_mhat_ready) {
+    const bool hand_over = call.hand_over;
+    if (call.head == OpCall::H_SPECTRA || call.head == OpCall::H_MHAT) {
         // the maps' spectra are the caller's vector, or the template solver has left them in mhat: nothing to transform
     } else if (p->T > 0) {
-        {
-            Prof pr(p, "pad_planes");
-            LAUNCH_OK(launch_pad_planes(s, x, p->maps_pad, p->T, p->Na, p->Nb, p->NAP, p->NBP));
-        }
-        if (rfft2_planes(p, p->maps_pad, p->mhat, p->T)) return 1;
-    } else if (p->pn_native) {
+        if (tpl_maps_spectra(p, x)) return 1;
+    } else if (call.head == OpCall::H_CUBE) {
         // plane-wise solver on wavelength-innermost vectors: x is already in the cube's layout [NBP][NAP][LP]
         if (rfft2_cube(p, x, p->mhat)) return 1;
     } else {
@@ -432,12 +425,12 @@ int forward_dev(surfh_plan *p, const float *x, float *y, bool hand_over) {
     if (p->T > 0 && p->T <= 4 && p->fuse_mix && !p->dense_dft) {
         // spectral mix x OTF fused into the loader of the first inverse pass: `spec` is never written
         // (the normal operator needs the blurred cube only where a gather reads it)
-        if (irfft2_cube(p, p->sotf, p->cube, true, hand_over)) return 1;
+        if (irfft2_cube(p, p->sotf, p->cube, call.head == OpCall::H_SPECTRA ? call.spectra_in : p->mhat, hand_over)) return 1;
     } else if (prod_capable(p)) {
         // plane-wise model on the Cooley-Tukey passes: OTF x spectrum in the loader of the first inverse pass, `spec` is never written
         ProdOperand po;
         po.prod = p->sotf;
-        if (irfft2_cube(p, p->mhat, p->cube, false, false, &po)) return 1;
+        if (irfft2_cube(p, p->mhat, p->cube, nullptr, false, &po)) return 1;
     } else {
         {
             Prof pr(p, "specmix_fwd");
@@ -503,9 +496,10 @@ int forward_dev(surfh_plan *p, const float *x, float *y, bool hand_over) {
     return 0;
 }
 
-// `handed_over`: forward_dev(hand_over) has just left the GEMM operands of the channels with a spectral blur behind
-int adjoint_dev(surfh_plan *p, const float *y, float *x, bool ref, bool handed_over) {
+// x = A^T y, x where call.tail says (OpCall, plan_internal.h)
+int adjoint_dev(surfh_plan *p, const float *y, float *x, const OpCall &call) {
     hipStream_t s = p->stream;
+    const bool ref = call.ref, handed_over = call.hand_over;
     // detector-side work (y -> ymat, R^T GEMM) on the second stream, cube-side scatter on the main one: GEMM(c+1)
     // overlaps scatter(c); the scatters stay in channel order on one stream because their windows overlap
     hipStream_t sB = (p->overlap && p->stream2) ? p->stream2 : s;
@@ -550,6 +544,16 @@ int adjoint_dev(surfh_plan *p, const float *y, float *x, bool ref, bool handed_o
     // The two-piece fp16 GEMMs of up to four channels go out as ONE launch (each is 1.5-1.8 rounds of workgroups on its own;
     // their operands and outputs are per channel, so nothing orders them among themselves): detector-side preparation of all
     // of them first, the grouped GEMM, then the scatters in channel order.  SURFH_GEMM_GROUPED=0: one launch per channel.
+    auto scatter = [&](Channel &c) -> int {      // cube side of one channel: acc (+)= G^T Xs
+        Prof pr(p, ref ? "spmm_degrid_ref" : "spmm_scatter_adj");
+        if (p->verify)
+            LAUNCH_OK(launch_spmm_rows_f64acc(s, ref ? c.adjRef.t : c.adjT.t, c.Xs, acc, c.nlam, 1));
+        else if (!ref && c.adjT.g.NG)
+            LAUNCH_OK(launch_spmm_group_scatter(s, c.adjT.g, c.Xs, acc, c.nlam));
+        else
+            LAUNCH_OK(launch_spmm_rows(s, ref ? c.adjRef.t : c.adjT.t, c.Xs, acc, c.nlam, 1));
+        return 0;
+    };
     std::vector<char> gemm_done(p->ch.size(), 0);
     if (p->gemm_grouped && !p->wblur_fp32 && !p->verify) {
         std::vector<GemmArgs> ga;
@@ -580,13 +584,7 @@ int adjoint_dev(surfh_plan *p, const float *y, float *x, bool ref, bool handed_o
                 Prof pr(p, "y_transpose");
                 LAUNCH_OK(launch_cube_to_lam_inner(s, y + c.yoff, c.Xs + c.shift, 0, c.Lin, 1, c.P * c.S * c.aout, 1, c.LinP));
             }
-            Prof pr(p, ref ? "spmm_degrid_ref" : "spmm_scatter_adj");
-            if (p->verify)
-                LAUNCH_OK(launch_spmm_rows_f64acc(s, ref ? c.adjRef.t : c.adjT.t, c.Xs, acc, c.nlam, 1));
-            else if (!ref && c.adjT.g.NG)
-                LAUNCH_OK(launch_spmm_group_scatter(s, c.adjT.g, c.Xs, acc, c.nlam));
-            else
-                LAUNCH_OK(launch_spmm_rows(s, ref ? c.adjRef.t : c.adjT.t, c.Xs, acc, c.nlam, 1));
+            if (scatter(c)) return 1;
             continue;
         }
         if (!gemm_done[ci]) {
@@ -596,51 +594,36 @@ int adjoint_dev(surfh_plan *p, const float *y, float *x, bool ref, bool handed_o
             if (p->wblur_fp32 || !c.W16) LAUNCH_OK(gemm32(p, sB, g));
             else LAUNCH_OK(launch_gemm_nt_f16x2_cc(sB, g));
         }
-        if (chain(p, sB, s)) return 1;
-        {
-            Prof pr(p, ref ? "spmm_degrid_ref" : "spmm_scatter_adj");
-            if (p->verify)
-                LAUNCH_OK(launch_spmm_rows_f64acc(s, ref ? c.adjRef.t : c.adjT.t, c.Xs, acc, c.nlam, 1));
-            else if (!ref && c.adjT.g.NG)
-                LAUNCH_OK(launch_spmm_group_scatter(s, c.adjT.g, c.Xs, acc, c.nlam));
-            else
-                LAUNCH_OK(launch_spmm_rows(s, ref ? c.adjRef.t : c.adjT.t, c.Xs, acc, c.nlam, 1));
-        }
+        if (chain(p, sB, s) || scatter(c)) return 1;
     }
-    if (p->tg_out) return template_tail(p, acc);      // the transpose with respect to the templates: the reduction runs over the bins
-    if (adjoint_tail(p, acc, true)) return 1;
-    if (p->spec_out) return 0;         // the caller's vector is the spectrum
+    if (call.tail == OpCall::T_TEMPLATES) return template_tail(p, acc, call.tpl_out, call.tpl_maps);      // the reduction runs over the bins
+    if (adjoint_tail(p, acc, true, call)) return 1;
+    if (call.tail == OpCall::T_SPECTRA) return 0;         // the caller's vector is the spectrum
     if (p->T > 0) {
         if (irfft2_planes(p, p->mhat, p->maps_pad, p->T)) return 1;
         Prof pr(p, "unpad_planes");
         LAUNCH_OK(launch_unpad_planes(s, p->maps_pad, x, p->T, p->Na, p->Nb, p->NAP, p->NBP));
-    } else if (prod_capable(p)) {
+        return 0;
+    }
+    // plane-wise: straight into the caller's wavelength-innermost vector, or through the work cube into the caller's planes
+    float *const out = call.tail == OpCall::T_CUBE ? x : p->cube;
+    if (prod_capable(p)) {
         // conj(OTF) x spectrum of the accumulated cube in the loader; inside the plane-wise normal operator mu rides on the pass and
         // the quadratic prior comes in as a third operand: `mhat` still holds the spectrum of the vector the forward half was applied to
         ProdOperand po;
-        po.prod = p->sotf; po.sign = -1.f; po.scale = p->pn_fold_prior ? (float)p->pl_mu : 1.f;
-        if (p->pn_fold_prior && p->pl_mu_reg != 0.0 && p->pl_mu != 0.0) {      // q = mu (A^T A d + (mu_r / mu) D^T D d)
-            po.add = p->mhat; po.add_w = (float)(p->pl_mu_reg / p->pl_mu);
+        po.prod = p->sotf; po.sign = -1.f; po.scale = call.fold ? (float)call.mu : 1.f;
+        if (call.fold && call.prior_mu != 0.0 && call.mu != 0.0) {      // q = mu (A^T A d + (mu_r / mu) D^T D d)
+            po.add = p->mhat; po.add_w = (float)(call.prior_mu / call.mu);
         }
-        float *const out = p->pn_native ? x : p->cube;
-        if (irfft2_cube(p, p->spec, out, false, false, &po)) return 1;
-        if (!p->pn_native) {
-            const long pl = (long)p->Na * p->Nb;
-            if (p->Lown < p->Lc) LAUNCH_OK(launch_fill_zero(s, x, (long)p->Lc * pl));   // planes no channel observes
-            Prof pr(p, "cube_transpose");
-            for (auto &g : p->segs)
-                LAUNCH_OK(launch_cube_from_lam_inner(s, p->cube + g.coff, x, g.start, g.len, p->Na, p->Nb, p->NAP, p->LP));
-        }
-    } else if (p->pn_native) {
-        if (irfft2_cube(p, p->mhat, x)) return 1;           // straight into the caller's wavelength-innermost vector
-    } else {
-        if (irfft2_cube(p, p->mhat, p->cube)) return 1;
-        const long pl = (long)p->Na * p->Nb;
-        if (p->Lown < p->Lc) LAUNCH_OK(launch_fill_zero(s, x, (long)p->Lc * pl));   // planes no channel observes
-        Prof pr(p, "cube_transpose");
-        for (auto &g : p->segs)
-            LAUNCH_OK(launch_cube_from_lam_inner(s, p->cube + g.coff, x, g.start, g.len, p->Na, p->Nb, p->NAP, p->LP));
+        if (irfft2_cube(p, p->spec, out, nullptr, false, &po)) return 1;
+    } else if (irfft2_cube(p, p->mhat, out)) {
+        return 1;
     }
+    if (out == x) return 0;
+    if (p->Lown < p->Lc) LAUNCH_OK(launch_fill_zero(s, x, (long)p->Lc * p->Na * p->Nb));   // planes no channel observes
+    Prof pr(p, "cube_transpose");
+    for (auto &g : p->segs)
+        LAUNCH_OK(launch_cube_from_lam_inner(s, p->cube + g.coff, x, g.start, g.len, p->Na, p->Nb, p->NAP, p->LP));
     return 0;
 }
 
@@ -654,15 +637,15 @@ static bool normal_hand_over(const surfh_plan *p) {
 // straight into the adjoint's GEMM operands (SURFH_NORMAL_FUSED=0: through y, as forward() + adjoint() do).  Data weights
 // (surfh_set_data_weights) ride on the hand-over: inside launch_ymat16w_from_cpart where y is never written, as one element-wise
 // pass over the part of y that is (verify plans, SURFH_WBLUR_FP32, SURFH_NORMAL_FUSED=0, channels without a spectral blur).
-int normal_halves(surfh_plan *p, const float *v, float *q) {
-    const bool ho = normal_hand_over(p);
-    if (forward_dev(p, v, p->cg_y, ho)) return 1;
+int normal_halves(surfh_plan *p, const float *v, float *q, OpCall c) {
+    const bool ho = c.hand_over = normal_hand_over(p);
+    if (forward_dev(p, v, p->cg_y, c)) return 1;
     if (p->dw) {
         Prof pr(p, "weight_mul");
         for (auto &c : p->ch)
             if (!(ho && !c.bsum && c.ymat16)) LAUNCH_OK(launch_weight_mul(p->stream, p->cg_y + c.yoff, p->dw + c.yoff, c.ysize));
     }
-    return adjoint_dev(p, p->cg_y, q, false, ho);
+    return adjoint_dev(p, p->cg_y, q, c);
 }
 // the data of the solvers' right-hand side b = mu A^T W y: y itself without weights, else W y formed once per solve by a select
 const float *weighted_data(surfh_plan *p, const float *y) {
@@ -672,11 +655,13 @@ const float *weighted_data(surfh_plan *p, const float *y) {
     return p->dwy;
 }
 
-int normal_dev(surfh_plan *p, const float *d, float *q, double mu) {
-    if (normal_halves(p, d, q)) return 1;
+int normal_dev(surfh_plan *p, const float *d, float *q, double mu, bool cube) {
+    OpCall c;
+    if (cube) { c.head = OpCall::H_CUBE; c.tail = OpCall::T_CUBE; }
+    if (normal_halves(p, d, q, c)) return 1;
     if (mu != 1.0) {
         Prof pr(p, "scale");
-        LAUNCH_OK(launch_scale(p->stream, q, p->pn_native ? (long)p->NBP * p->NAP * p->LP : p->isize, (float)mu));
+        LAUNCH_OK(launch_scale(p->stream, q, cube ? (long)p->NBP * p->NAP * p->LP : p->isize, (float)mu));
     }
     return 0;
 }
@@ -758,24 +743,23 @@ int TplScope::begin() {
     return 0;
 }
 TplScope::~TplScope() {
-    p->tg_out = nullptr; p->tg_maps = nullptr; p->tg_mhat_ready = false;
+    p->tg_mhat_ready = false;
     if (armed) hipMemcpyAsync(p->tpl, p->tg_keep, (size_t)p->T * p->LP * sizeof(float), hipMemcpyDeviceToDevice, p->stream);
 }
 namespace {
-struct TplOut {                        // adjoint_dev ends in the template transpose for the duration of one call
-    surfh_plan *p;
-    TplOut(surfh_plan *pl, const float *maps, float *G) : p(pl) { p->tg_maps = maps; p->tg_out = G; }
-    ~TplOut() { p->tg_out = nullptr; p->tg_maps = nullptr; }
-};
+OpCall tpl_call(const surfh_plan *p, const float *maps, float *G) {      // tail: the template transpose; head: mhat if it holds the maps' spectra
+    OpCall c;
+    c.tail = OpCall::T_TEMPLATES; c.tpl_out = G; c.tpl_maps = maps;
+    if (p->tg_mhat_ready) c.head = OpCall::H_MHAT;
+    return c;
+}
 }  // namespace
 int tpl_adjoint_dev(surfh_plan *p, const float *maps, const float *u, float *G) {
     if (!p->tg_mhat_ready && tpl_maps_spectra(p, maps)) return 1;
-    TplOut out(p, maps, G);
-    return adjoint_dev(p, u, nullptr, false);
+    return adjoint_dev(p, u, nullptr, tpl_call(p, maps, G));
 }
 int tpl_normal_dev(surfh_plan *p, const float *maps, float *G) {
-    TplOut out(p, maps, G);            // the forward half leaves the maps' spectra in mhat, where the tail reads them
-    return normal_halves(p, maps, nullptr);
+    return normal_halves(p, maps, nullptr, tpl_call(p, maps, G));      // the forward half leaves the maps' spectra in mhat, where the tail reads them
 }
 
 }  // namespace surfh_impl
@@ -790,12 +774,14 @@ int surfh_forward_dev(surfh_plan *p, const float *x, float *y) {
 int surfh_adjoint_dev(surfh_plan *p, const float *y, float *x) {
     if (!p) return fail("null plan");
     HIP_OK(hipSetDevice(p->dev));
-    return adjoint_dev(p, y, x, false);
+    return adjoint_dev(p, y, x);
 }
 int surfh_adjoint_ref_dev(surfh_plan *p, const float *y, float *x) {
     if (!p) return fail("null plan");
     HIP_OK(hipSetDevice(p->dev));
-    return adjoint_dev(p, y, x, true);
+    OpCall c;
+    c.ref = true;
+    return adjoint_dev(p, y, x, c);
 }
 int surfh_fwadj_dev(surfh_plan *p, const float *x, float *out) {
     if (!p) return fail("null plan");
@@ -815,8 +801,8 @@ static int host_call(surfh_plan *p, const float *in, long nin, float *outp, long
     HIP_OK(hipMemcpyAsync(din, in, nin * sizeof(float), hipMemcpyHostToDevice, p->stream));
     int rc = 0;
     if (which == 0) rc = forward_dev(p, din, dout);
-    else if (which == 1) rc = adjoint_dev(p, din, dout, false);
-    else if (which == 2) rc = adjoint_dev(p, din, dout, true);
+    else if (which == 1) rc = adjoint_dev(p, din, dout);
+    else if (which == 2) rc = surfh_adjoint_ref_dev(p, din, dout);
     else rc = normal_dev(p, din, dout, 1.0);
     if (rc) return rc;
     HIP_OK(hipMemcpyAsync(outp, dout, nout * sizeof(float), hipMemcpyDeviceToHost, p->stream));
@@ -996,10 +982,12 @@ int spec_check(surfh_plan *p) {
     HIP_OK(hipSetDevice(p->dev));
     return 0;
 }
-struct SpecScope {      // the transient pointers never outlive a call
-    surfh_plan *p;
-    ~SpecScope() { p->spec_in = nullptr; p->spec_out = nullptr; p->spec_prior_src = nullptr; p->spec_mu = 1.f; p->spec_prior_mu = 0.f; }
-};
+// tail of a spectral-domain call: qt = mu * scaled half spectra (+ mu_reg * |D|^2 * dt, the quadratic prior, when dt != NULL)
+OpCall spec_tail(float *qt, double mu, const float *dt, double mu_reg) {
+    OpCall c;
+    c.tail = OpCall::T_SPECTRA; c.spectra_out = qt; c.mu = (float)mu; c.prior_src = dt; c.prior_mu = dt ? (float)mu_reg : 0.f;
+    return c;
+}
 }  // namespace
 
 int surfh_spec_supported(surfh_plan *p) {
@@ -1028,27 +1016,24 @@ int surfh_from_spec_dev(surfh_plan *p, const float *xt, float *x) {
 // y = A maps(dt)
 int surfh_forward_spec_dev(surfh_plan *p, const float *dt, float *y) {
     if (spec_check(p)) return 1;
-    SpecScope sc{p};
-    p->spec_in = dt;
-    return forward_dev(p, nullptr, y);
+    OpCall c;
+    c.head = OpCall::H_SPECTRA; c.spectra_in = dt;
+    return forward_dev(p, nullptr, y, c);
 }
 // qt = mu * spectra(A^T y)  (+ mu_reg * prior(dt) when dt != NULL: only where q is not summed over ranks afterwards)
 int surfh_adjoint_spec_dev(surfh_plan *p, const float *y, float *qt, double mu, const float *dt, double mu_reg) {
     if (spec_check(p)) return 1;
     if (dt && p->prior_kind != 0) return fail("the fused spectral prior is the separated first differences");
-    SpecScope sc{p};
-    p->spec_out = qt; p->spec_mu = (float)mu; p->spec_prior_src = dt; p->spec_prior_mu = dt ? (float)mu_reg : 0.f;
-    return adjoint_dev(p, y, nullptr, false);
+    return adjoint_dev(p, y, nullptr, spec_tail(qt, mu, dt, mu_reg));
 }
 // qt = mu * spectra(A^T A maps(dt)) (+ mu_reg * prior(dt) if mu_reg != 0): the CG's normal operator without a single transform
 // of the maps -- no padding, no small DFTs, no prior kernel
 int surfh_normal_spec_dev(surfh_plan *p, const float *dt, float *qt, double mu, double mu_reg) {
     if (spec_check(p)) return 1;
     if (mu_reg != 0.0 && p->prior_kind != 0) return fail("the fused spectral prior is the separated first differences");
-    SpecScope sc{p};
-    p->spec_in = dt;
-    p->spec_out = qt; p->spec_mu = (float)mu; p->spec_prior_src = mu_reg != 0.0 ? dt : nullptr; p->spec_prior_mu = (float)mu_reg;
-    return normal_halves(p, nullptr, nullptr);
+    OpCall c = spec_tail(qt, mu, mu_reg != 0.0 ? dt : nullptr, mu_reg);
+    c.head = OpCall::H_SPECTRA; c.spectra_in = dt;
+    return normal_halves(p, nullptr, nullptr, c);
 }
 // qt += mu_reg * prior(dt) on scaled half spectra (after an all-reduce of qt over ranks)
 int surfh_prior_spec_add_dev(surfh_plan *p, const float *dt, float *qt, double mu_reg) {

@@ -139,13 +139,13 @@ int imager_refuse(const surfh_plan *p, const char *who) {
                     "surfh_mmmg or surfh_mmmg_huber", who);
     return 0;
 }
-// cg_b = mu A^T W y, cg_q = Q x, cg_r = cg_b - cg_q; y on the device, x already holding the start
-int solver_setup(surfh_plan *p, const float *y, const float *x, double mu, double mu_reg) {
+// cg_b = mu A^T W y (+ extra), cg_q = Q x, cg_r = cg_b - cg_q; y on the device, x already holding the start
+int solver_setup(surfh_plan *p, const float *y, const float *x, double mu, double mu_reg, const float *extra = nullptr) {
     if (!(y = weighted_data(p, y))) return 1;
-    if (adjoint_dev(p, y, p->cg_b, false)) return 1;
+    if (adjoint_dev(p, y, p->cg_b)) return 1;
     if (mu != 1.0) LAUNCH_OK(launch_scale(p->stream, p->cg_b, p->isize, (float)mu));
     if (imager_active(p) && imager_rhs_add(p, p->cg_b)) return 1;           // + mu_imager A_im^T W_im y_im
-    if (p->cg_extra) LAUNCH_OK(launch_po_add(p->stream, p->cg_b, p->cg_extra, p->isize));   // + eta (surfh_cg_sample)
+    if (extra) LAUNCH_OK(launch_po_add(p->stream, p->cg_b, extra, p->isize));               // + eta (surfh_cg_sample)
     if (normal_prior(p, x, p->cg_q, mu, mu_reg)) return 1;
     LAUNCH_OK(launch_residual(p->stream, p->cg_r, p->cg_b, p->cg_q, p->isize));
     return 0;
@@ -240,6 +240,10 @@ struct CgSpace {
     int (*trace)(surfh_plan *p, const CgSpace &s, double *grad_norm, int it);         // rows 0 .. it of the trace on the host
     int (*to_caller)(surfh_plan *p, const CgSpace &s);                                // xc = x in the caller's layout
     long clen = 0;                 // floats of xc the caller and the callback get (0: isize)
+    // surfh_cg_sample: an extra right-hand side [isize] in the maps' layout that the set-up of the map and spectral spaces adds to b
+    // (null: the launches are exactly those without it); surfh_cg_nonneg: the penalty, the operator of the nn_* applies is Q + rho I
+    const float *extra = nullptr;
+    double rho = 0.0;
 };
 int cg_nop(surfh_plan *, const CgSpace &) { return 0; }     // to_caller: the layouts agree; dir: the step's block went on to the direction
 // the maps and the planes keep the current row only: it goes to the host after every iteration
@@ -248,7 +252,7 @@ int row_trace(surfh_plan *p, const CgSpace &s, double *grad_norm, int it) {
     HIP_OK(hipStreamSynchronize(p->stream));
     return 0;
 }
-int img_setup(surfh_plan *p, const CgSpace &s, const float *y, const float *) { return solver_setup(p, y, s.x, s.mu, s.mu_reg); }
+int img_setup(surfh_plan *p, const CgSpace &s, const float *y, const float *) { return solver_setup(p, y, s.x, s.mu, s.mu_reg, s.extra); }
 int img_apply(surfh_plan *p, const CgSpace &s, const float *v) { return normal_prior(p, v, s.q, s.mu, s.mu_reg); }
 int maps_rr0(surfh_plan *p, const CgSpace &s) { LAUNCH_OK(launch_dot(p->stream, s.r, s.r, s.len, p->dscratch, s.rr)); return 0; }
 int maps_step(surfh_plan *p, const CgSpace &s, int update_r) {
@@ -276,8 +280,8 @@ CgSpace maps_space(surfh_plan *p, double mu, double mu_reg) {
 int spec_setup(surfh_plan *p, const CgSpace &s, const float *y, const float *x0) {
     const float *wy = weighted_data(p, y);
     if (!wy || surfh_adjoint_spec_dev(p, wy, s.b, s.mu, nullptr, 0.0)) return 1;
-    if (p->cg_extra) {                                                                      // + eta (surfh_cg_sample), s.q still free
-        if (surfh_to_spec_dev(p, p->cg_extra, s.q)) return 1;
+    if (s.extra) {                                                                          // + eta (surfh_cg_sample), s.q still free
+        if (surfh_to_spec_dev(p, s.extra, s.q)) return 1;
         LAUNCH_OK(launch_po_add(p->stream, s.b, s.q, s.len));
     }
     if (x0) {
@@ -320,25 +324,18 @@ CgSpace planes_space(surfh_plan *p, float *x, double mu, double mu_reg) {
     return {x, p->cg_r, p->cg_d, p->cg_q, p->cg_b, x, p->isize, (long)p->Na * p->Nb, L, mu, mu_reg, p->pl_sc, p->pl_sc + L, p->pl_sc + 2 * L,
             img_setup, planes_rr0, img_apply, planes_step, planes_refresh, planes_dir, row_trace, cg_nop};
 }
-struct PnScope {                       // forward_dev / adjoint_dev read and write wavelength-innermost vectors for the duration of a call
-    surfh_plan *p;
-    explicit PnScope(surfh_plan *pl) : p(pl) { p->pn_native = true; }
-    ~PnScope() { p->pn_native = false; }
-};
 // q = mu A^T A v (+ mu_reg prior, fused with the dot product v . q -> dq) on wavelength-innermost vectors
 int pn_normal(surfh_plan *p, const float *v, float *q, double *dq) {
-    PnScope sc(p);
     // with interleaved spectra and a prior weight the OTF product of the adjoint applies mu and adds the prior (adjoint_tail): the
     // two halves are called directly so that no scaling pass follows
     // (plans whose inverse transform forms the OTF product in its loader -- prod_capable -- take mu and the prior on that pass)
     const bool prod = prod_capable(p) && p->pl_mu != 0.0;
     const bool fold = prod || (p->ilv && !p->dense_dft && p->pl_mu_reg != 0.0);
     if (fold) {
-        p->pn_fold_prior = true;
-        const int rc = normal_halves(p, v, q);
-        p->pn_fold_prior = false;
-        if (rc) return 1;
-    } else if (normal_dev(p, v, q, p->pl_mu)) {
+        OpCall c;
+        c.head = OpCall::H_CUBE; c.tail = OpCall::T_CUBE; c.fold = true; c.mu = p->pl_mu; c.prior_mu = p->pl_mu_reg;
+        if (normal_halves(p, v, q, c)) return 1;
+    } else if (normal_dev(p, v, q, p->pl_mu, true)) {
         return 1;
     }
     Prof pr(p, "pn_prior_dot");
@@ -353,11 +350,10 @@ bool pn_capable(const surfh_plan *p) {
 }
 int pn_setup(surfh_plan *p, const CgSpace &s, const float *y, const float *x0) {     // mu and mu_reg: the plan's pl_mu, pl_mu_reg
     LAUNCH_OK(launch_cube_to_lam_inner(p->stream, x0, s.x, 0, p->Lc, p->Na, p->Nb, p->NAP, p->LP));
-    {
-        const float *wy = weighted_data(p, y);
-        PnScope sc(p);
-        if (!wy || adjoint_dev(p, wy, s.b, false)) return 1;
-    }
+    const float *wy = weighted_data(p, y);
+    OpCall c;
+    c.tail = OpCall::T_CUBE;
+    if (!wy || adjoint_dev(p, wy, s.b, c)) return 1;
     if (s.mu != 1.0) LAUNCH_OK(launch_scale(p->stream, s.b, s.len, (float)s.mu));
     if (pn_normal(p, s.x, s.q, s.dq)) return 1;
     LAUNCH_OK(launch_residual(p->stream, s.r, s.b, s.q, s.len));
@@ -460,13 +456,15 @@ namespace {
 bool cg_spectral(surfh_plan *p, int32_t max_iter) {
     return env_on("SURFH_SPECTRAL_CG", true) && !imager_active(p) && surfh_spec_supported(p) && max_iter < (1 << 16) - 1;
 }
-// surfh_cg_cb behind its argument checks; y NULL: the data are in io_y already (the perturbed data of surfh_cg_sample)
+// surfh_cg_cb behind its argument checks; y NULL: the data are in io_y already (the perturbed data of surfh_cg_sample, `extra` its
+// extra right-hand side on the device)
 int cg_run(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol, int32_t refresh, float *x,
-           double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user) {
+           double *grad_norm, int32_t *nit, surfh_cg_callback callback, void *user, const float *extra = nullptr) {
     HIP_OK(hipSetDevice(p->dev));
     if (ensure_cg(p)) return 1;
     const bool spectral = cg_spectral(p, max_iter);
-    const CgSpace s = spectral ? spectral_space(p, mu, mu_reg) : maps_space(p, mu, mu_reg);
+    CgSpace s = spectral ? spectral_space(p, mu, mu_reg) : maps_space(p, mu, mu_reg);
+    s.extra = extra;
     if (y) HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, p->stream));
     if (spectral && x0) HIP_OK(hipMemcpyAsync(s.xc, x0, p->isize * sizeof(float), hipMemcpyHostToDevice, p->stream));
     if ((!spectral && start_iterate(p, x0)) || cg_start(p, s, p->io_y, x0 ? s.xc : nullptr)) return 1;
@@ -559,15 +557,14 @@ int surfh_cg_templates(surfh_plan *p, const float *y, const float *maps, double 
 // The spectra keep x, r, d in their basis (orthonormal: rho I stays rho I) and z, u on the pixels: x goes there through
 // surfh_from_spec_dev, nn_project leaves dv = rho (v' - v), which comes back through surfh_to_spec_dev.
 namespace {
-struct NnScope {                       // the penalty and the extra vectors never outlive a solve
+struct NnScope {                       // the extra vectors never outlive a solve
     surfh_plan *p;
     explicit NnScope(surfh_plan *pl) : p(pl) {}
-    int begin(double rho, long n) {
+    int begin(long n) {
         const size_t pitch = ((size_t)n + 3) / 4 * 4;      // each vector 16-byte aligned
         if (dev_alloc(&p->nn_z, 3 * pitch)) return 1;
         p->nn_u = p->nn_z + pitch;
         p->nn_w = p->nn_u + pitch;
-        p->nn_rho = rho;
         return 0;
     }
     ~NnScope() {
@@ -576,11 +573,10 @@ struct NnScope {                       // the penalty and the extra vectors neve
             hipFree(p->nn_z);
         }
         p->nn_z = p->nn_u = p->nn_w = nullptr;
-        p->nn_rho = 0.0;
     }
 };
 int nn_rho_add(surfh_plan *p, const CgSpace &s, const float *v) {                           // q += rho v: the operator is Q + rho I
-    LAUNCH_OK(launch_nn_add(p->stream, s.q, v, nullptr, s.len, (float)p->nn_rho));
+    LAUNCH_OK(launch_nn_add(p->stream, s.q, v, nullptr, s.len, (float)s.rho));
     return 0;
 }
 int nn_img_apply(surfh_plan *p, const CgSpace &s, const float *v) { return img_apply(p, s, v) || nn_rho_add(p, s, v); }
@@ -601,12 +597,12 @@ int nn_spec_add(surfh_plan *p, const CgSpace &s, const float *a, const float *b,
     LAUNCH_OK(launch_nn_add(p->stream, s.r, s.q, nullptr, s.len, (float)c));
     return 0;
 }
-// After cg_start on `s` (r = b - Q x, trace entry 0) inside an NnScope.  `sx`: s with rho v added by its apply; spectral: x, r, d are spectra and
+// After cg_start on `s` (r = b - Q x, trace entry 0) inside an NnScope.  `sx`: s with its penalty rho, and rho v added by its apply; spectral: x, r, d are spectra and
 // s.xc the pixels; h0 [m]: the start on the host (NULL: zeros), m the floats of z.  out [m], trace [outer + 1][4]
 int nn_loop(surfh_plan *p, const CgSpace &s, const CgSpace &sx, bool spectral, const float *h0, long m, int32_t outer, int32_t inner,
             double tol, int32_t refresh, float *out, double *trace, int32_t *nit) {
     hipStream_t st = p->stream;
-    const double rho = p->nn_rho;
+    const double rho = sx.rho;
     double *const sums = p->dscal + 8;
     const float *const xp = spectral ? s.xc : s.x;                                         // the iterate on the pixels
     double pp0 = 0.0, active0 = (double)m;
@@ -687,11 +683,12 @@ int surfh_cg_nonneg(surfh_plan *p, const float *y, double mu, double mu_reg, dou
     const CgSpace s = spectral ? spectral_space(p, mu, mu_reg) : maps_space(p, mu, mu_reg);
     CgSpace sx = s;
     sx.apply = spectral ? nn_spec_apply : nn_img_apply;
+    sx.rho = rho;
     HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, p->stream));
     if (spectral && x0) HIP_OK(hipMemcpyAsync(s.xc, x0, p->isize * sizeof(float), hipMemcpyHostToDevice, p->stream));
     if ((!spectral && start_iterate(p, x0)) || cg_start(p, s, p->io_y, x0 ? s.xc : nullptr)) return 1;
     NnScope sc(p);
-    if (sc.begin(rho, p->isize)) return 1;
+    if (sc.begin(p->isize)) return 1;
     return nn_loop(p, s, sx, spectral, x0, p->isize, outer, inner, tol, refresh, x, trace, nit);
 }
 
@@ -709,6 +706,7 @@ int surfh_cg_templates_nonneg(surfh_plan *p, const float *y, const float *maps, 
     const CgSpace s = tpl_space(p, mu, mu_spec);
     CgSpace sx = s;
     sx.apply = nn_tpl_apply;
+    sx.rho = rho;
     std::vector<float> h((size_t)s.len);
     if (s0) std::copy(s0, s0 + s.len, h.begin());
     else for (long i = 0; i < s.len; ++i) h[i] = (float)p->tpl_host[i];
@@ -717,7 +715,7 @@ int surfh_cg_templates_nonneg(surfh_plan *p, const float *y, const float *maps, 
     HIP_OK(hipMemcpyAsync(s.x, h.data(), s.len * sizeof(float), hipMemcpyHostToDevice, p->stream));
     TplScope tsc(p);
     NnScope sc(p);
-    if (tsc.begin() || cg_start(p, s, p->io_y, nullptr) || sc.begin(rho, s.len)) return 1;
+    if (tsc.begin() || cg_start(p, s, p->io_y, nullptr) || sc.begin(s.len)) return 1;
     return nn_loop(p, s, sx, false, h.data(), s.len, outer, inner, tol, refresh, s_out, trace, nit);
 }
 
@@ -753,7 +751,7 @@ int surfh_joint_criterion(surfh_plan *p, const float *y, const float *maps, doub
 // (Dr^T Dr + Dc^T Dc), b = mu A^T W y, and a draw b~ = mu A^T W (y + eps_y / sqrt(mu w)) + eta ~ N(b, Q), eta = sqrt(mu_reg)
 // (Dr^T eps_r + Dc^T eps_c), gives the sample x~ = Q^-1 b~.  The sampler solves for the deviation e = x~ - xhat instead, from
 // zero:  Q e = b~ - b = mu A^T W (eps_y / sqrt(mu w)) + eta  -- the CG of surfh_cg on the perturbation alone as its data (io_y)
-// with eta as the extra right-hand side of its set-up (cg_extra).  In exact arithmetic and at convergence that is the solve of
+// with eta as the extra right-hand side of its set-up (CgSpace::extra).  In exact arithmetic and at convergence that is the solve of
 // Q x~ = b~ started at xhat; in fp32 it is the one that works: started at xhat, the residual b~ - Q xhat is a difference of two
 // vectors some 1e3 times its size, the operator's 3e-7 comes back as 1e-4 of every r.r (measured: 2.3e-4 to 5.4e-4 on config 1
 // and two_channel_mid, against 2e-5 for a solve from zero), a perturbation below 1e-4 of the data drowns in the rounding of y~,
@@ -803,11 +801,6 @@ int po_perturb(surfh_plan *p, const float *y, double mu, double mu_reg, uint64_t
     *extra = p->po_eta;
     return 0;
 }
-struct ExtraScope {                    // the extra right-hand side never outlives a solve
-    surfh_plan *p;
-    ExtraScope(surfh_plan *pl, const float *e) : p(pl) { p->cg_extra = e; }
-    ~ExtraScope() { p->cg_extra = nullptr; }
-};
 }  // namespace
 
 int surfh_po_rhs(surfh_plan *p, const float *y, double mu, double mu_reg, uint64_t seed, int32_t sample, const float *eps,
@@ -824,7 +817,7 @@ int surfh_po_rhs(surfh_plan *p, const float *y, double mu, double mu_reg, uint64
         return 1;
     // the right-hand side as the maps' CG sets it up (solver_setup): mu A^T W y~ + eta
     const float *wy = weighted_data(p, p->io_y);
-    if (!wy || adjoint_dev(p, wy, p->cg_b, false)) return 1;
+    if (!wy || adjoint_dev(p, wy, p->cg_b)) return 1;
     if (mu != 1.0) LAUNCH_OK(launch_scale(p->stream, p->cg_b, p->isize, (float)mu));
     if (extra) LAUNCH_OK(launch_po_add(p->stream, p->cg_b, extra, p->isize));
     HIP_OK(hipMemcpyAsync(btilde, p->cg_b, p->isize * sizeof(float), hipMemcpyDeviceToHost, p->stream));
@@ -858,10 +851,8 @@ int surfh_cg_sample(surfh_plan *p, const float *y, double mu, double mu_reg, con
         const float *extra = nullptr;
         if (po_perturb(p, nullptr, mu, mu_reg, seed, k, eps_y, eps_r, eps_c, &extra)) return 1;
         int32_t nk = 0;
-        {
-            ExtraScope sc(p, extra);                                            // Q e = b~ - b from e = 0
-            if (cg_run(p, nullptr, mu, mu_reg, nullptr, max_iter, tol, refresh, xs.data(), gn.data(), &nk, nullptr, nullptr)) return 1;
-        }
+        if (cg_run(p, nullptr, mu, mu_reg, nullptr, max_iter, tol, refresh, xs.data(), gn.data(), &nk, nullptr, nullptr, extra))
+            return 1;                                                           // Q e = b~ - b from e = 0
         {
             Prof pr(p, "po_moments");
             LAUNCH_OK(launch_po_moments(s, xc, nullptr, p->po_S, p->T, npix));
@@ -1177,7 +1168,7 @@ int mmmg_robust_loop(surfh_plan *p, const HuberPrior &hp, const float *y, double
             Prof pr(p, "robust_data");
             LAUNCH_OK(launch_robust_data(s, yd, u, w, v, nullptr, no, dd, dk, p->dscratch, sc + 0));
         }
-        if (adjoint_dev(p, v, r, false)) return 1;
+        if (adjoint_dev(p, v, r)) return 1;
         if (mu != 1.0) LAUNCH_OK(launch_scale(s, r, n, (float)mu));
         if (hp.grad(p, hp, p->cg_x, r, ng, sc + G)) return 1;
         if (!last) {
