@@ -589,6 +589,12 @@ int32_t surfh_klist_classify(const float *B, int32_t n, int32_t k, int64_t ldb, 
  *   "huber_maps": a, b, c = T, Na, Nb;  "huber_vox": a, b, c = Lc, Na, Nb, out[3] = the most planes of one chunk,
  *     chunk k of C = out[1] owning planes [Lc k / C, Lc (k + 1) / C)                                                     */
 int surfh_launch_geometry(const char *which, int64_t a, int64_t b, int64_t c, int64_t out[4]);
+/* host only: the device allocator's process-wide counters.  live = allocations made and not yet freed, total = allocations
+ * asked for so far -- every device allocation of the library goes through one function, so "no leak" is live == what it was. */
+void surfh_debug_alloc_count(int64_t *live, int64_t *total);
+/* host only: the nth allocation from now on (1-based) is refused once with an out-of-memory error -- it counts in total, the
+ * device is not asked -- and the trigger disarms itself; 0 disarms it.  A refused allocation is an ordinary error return. */
+void surfh_debug_alloc_fail(int64_t nth);
 /* host only (no GPU): the 2x2 step solve every 3MG solver shares, step = (s0, s1) with [[dBd, dBm], [dBm, mBm]] step = [dg, mg];
  * (0, 0) without curvature along d (dBd <= 0 or NaN), (dg / dBd, 0) without a memory direction (mBm <= 0) or when the scaled
  * system is singular (1 - dBm^2 / (dBd mBm) <= 1e-12) */

@@ -62,6 +62,7 @@ EXPORTS = [
     "surfh_cg_begin_dev", "surfh_cg_iter_nosync_dev", "surfh_cg_xupdate_nosync_dev", "surfh_cg_refresh_nosync_dev", "surfh_cg_trace",
     "surfh_profile_enable", "surfh_profile_filter", "surfh_profile_count", "surfh_profile_get", "surfh_profile_reset", "surfh_debug_copy",
     "surfh_debug_dims", "surfh_gemm_selftest", "surfh_gemm_selftest_ksteps", "surfh_gemm_selftest_ms", "surfh_klist_classify", "surfh_launch_geometry", "surfh_mm_step2",
+    "surfh_debug_alloc_count", "surfh_debug_alloc_fail",
     "surfh_shepard", "surfh_shepard_last_error", "surfh_spectral_median", "surfh_nmf_cd", "surfh_templates_last_error",
     "surfh_set_templates", "surfh_get_templates", "surfh_forward_templates", "surfh_adjoint_templates", "surfh_forward_templates_dev",
     "surfh_adjoint_templates_dev", "surfh_cg_templates", "surfh_cg_templates_cb", "surfh_joint_criterion",
@@ -188,6 +189,10 @@ def load():
     L.surfh_klist_classify.restype = C.c_int32
     L.surfh_launch_geometry.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
     L.surfh_mm_step2.argtypes = [C.c_double] * 5 + [c_double_p]
+    L.surfh_debug_alloc_count.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.surfh_debug_alloc_count.restype = None
+    L.surfh_debug_alloc_fail.argtypes = [C.c_int64]
+    L.surfh_debug_alloc_fail.restype = None
     L.surfh_shepard.argtypes = [C.c_int32, C.POINTER(C.c_int64), vp, vp, vp, c_int32_p, c_int32_p, C.c_int32, vp, vp,
                                 c_float_p, c_float_p, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, C.c_int32, vp,
                                 c_float_p]

@@ -33,6 +33,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "dev_buf.h"
+
 enum { DFT_CT_PLAIN = 0, DFT_CT_MIX = 1, DFT_CT_HPACK = 2, DFT_CT_PROD = 3, DFT_CT_PRODADD = 4 };
 enum { DFT_CT_STORE = 0, DFT_CT_HSEP = 1 };
 
@@ -76,13 +78,12 @@ struct DftCtArgs {
 // fp16 pieces, and the twiddles w_N^{n1 k2} (inverse sign) as [M][R - 1] (cos, sin)
 struct DftCtPlan {
     int R = 0, M = 0, N = 0, MT = 0, KT = 0, kA = 0;
-    unsigned short *img = nullptr;
-    float *tw = nullptr;
+    surfh_impl::DevBuf<unsigned short> img;
+    surfh_impl::DevBuf<float> tw;
 };
 
 // factorisation the kernel supports for length n (false: none): R in {4, 3, 2} with n % R == 0, 32 < M = n / R <= 190
 bool dft_ct_factor(int n, int *R, int *M);
 bool dft_ct_supported(int Na, int Nb);
 int dft_ct_plan_create(int n, DftCtPlan *out);
-void dft_ct_plan_destroy(DftCtPlan *p);
 int launch_dft_ct(hipStream_t stream, const DftCtArgs &g, const DftCtPlan &pl);

@@ -625,7 +625,7 @@ int launch_inst(hipStream_t stream, const DftCtArgs &g, const DftCtPlan &pl, int
     if (ldsb > LDS_LIMIT) return (int)hipErrorInvalidValue;
     if (int e = ensure_dynamic_lds(dft_ct_kernel<R, LD, EP>, ldsb, done)) return e;
     const dim3 grid((unsigned)(NU < cus ? NU : cus));
-    hipLaunchKernelGGL((dft_ct_kernel<R, LD, EP>), grid, dim3(Cfg<R>::NTH), ldsb, stream, g, reinterpret_cast<const uint4 *>(pl.img), pl.tw,
+    hipLaunchKernelGGL((dft_ct_kernel<R, LD, EP>), grid, dim3(Cfg<R>::NTH), ldsb, stream, g, reinterpret_cast<const uint4 *>(pl.img.get()), pl.tw.get(),
                        g.vlist, g.ktab, g.rtab, pl.MT, pl.KT, pl.kA, NU);
     return (int)hipGetLastError();
 }
@@ -690,23 +690,12 @@ int dft_ct_plan_create(int n, DftCtPlan *out) {
             tw[((size_t)k2 * (p.R - 1) + n1 - 1) * 2] = (float)std::cos(th);
             tw[((size_t)k2 * (p.R - 1) + n1 - 1) * 2 + 1] = (float)std::sin(th);
         }
-    if (hipMalloc((void **)&p.img, img.size() * 2) != hipSuccess) return (int)hipErrorOutOfMemory;
-    if (hipMalloc((void **)&p.tw, tw.size() * 4) != hipSuccess) { hipFree(p.img); return (int)hipErrorOutOfMemory; }
+    if (p.img.alloc(img.size()) || p.tw.alloc(tw.size())) return (int)hipErrorOutOfMemory;
     if (hipMemcpy(p.img, img.data(), img.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p.tw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        hipFree(p.img);
-        hipFree(p.tw);
+        hipMemcpy(p.tw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
         return (int)hipErrorUnknown;
-    }
-    *out = p;
+    *out = std::move(p);
     return 0;
-}
-
-void dft_ct_plan_destroy(DftCtPlan *p) {
-    if (!p) return;
-    hipFree(p->img);
-    hipFree(p->tw);
-    *p = DftCtPlan();
 }
 
 int launch_dft_ct(hipStream_t stream, const DftCtArgs &g, const DftCtPlan &pl) {

@@ -16,6 +16,9 @@
 #include <vector>
 
 #include "../../include/surfh_amd.h"
+#include "dev_buf.h"
+
+using surfh_impl::DevBuf;
 
 namespace {
 
@@ -98,9 +101,9 @@ __global__ __launch_bounds__(TPB) void tst_fwadj_kernel(const float *__restrict_
 struct surfh_tst {
     int dev = 0, T = 0, L = 0, na = 0, nb = 0;
     long npix = 0, nvox = 0;
-    int *vox = nullptr, *lam = nullptr;
-    long *off = nullptr;
-    float *tpl = nullptr, *TST = nullptr, *maps = nullptr, *cube = nullptr, *out = nullptr;
+    DevBuf<int> vox, lam;
+    DevBuf<long> off;
+    DevBuf<float> tpl, TST, maps, cube, out;
 };
 
 extern "C" {
@@ -110,7 +113,6 @@ const char *surfh_tst_last_error(void) { return g_tst_err.c_str(); }
 int surfh_tst_destroy(surfh_tst *t) {
     if (!t) return 0;
     hipSetDevice(t->dev);
-    hipFree(t->vox); hipFree(t->lam); hipFree(t->off); hipFree(t->tpl); hipFree(t->TST); hipFree(t->maps); hipFree(t->cube); hipFree(t->out);
     delete t;
     return 0;
 }
@@ -143,11 +145,8 @@ int surfh_tst_create(int32_t n_alpha, int32_t n_beta, int32_t n_lambda, int32_t 
     std::vector<float> tp((size_t)n_templates * n_lambda);
     for (size_t k = 0; k < tp.size(); ++k) tp[k] = (float)templates[k];   // the reference casts to float32 (mixing.py:307)
     const size_t nv = (size_t)std::max<int64_t>(n_voxels, 1);
-    if (hipMalloc((void **)&t->vox, nv * 3 * sizeof(int)) != hipSuccess || hipMalloc((void **)&t->lam, nv * sizeof(int)) != hipSuccess ||
-        hipMalloc((void **)&t->off, cnt.size() * sizeof(long)) != hipSuccess || hipMalloc((void **)&t->tpl, tp.size() * 4) != hipSuccess ||
-        hipMalloc((void **)&t->maps, (size_t)n_templates * t->npix * 4) != hipSuccess ||
-        hipMalloc((void **)&t->out, (size_t)n_templates * t->npix * 4) != hipSuccess ||
-        hipMalloc((void **)&t->cube, (size_t)n_lambda * t->npix * 4) != hipSuccess)
+    if (t->vox.alloc(nv * 3) || t->lam.alloc(nv) || t->off.alloc(cnt.size()) || t->tpl.alloc(tp.size()) ||
+        t->maps.alloc((size_t)n_templates * t->npix) || t->out.alloc((size_t)n_templates * t->npix) || t->cube.alloc((size_t)n_lambda * t->npix))
         return bail(tfail("device allocation failed"));
     if (n_voxels) {
         if (hipMemcpy(t->vox, voxels, (size_t)n_voxels * 3 * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
@@ -158,7 +157,7 @@ int surfh_tst_create(int32_t n_alpha, int32_t n_beta, int32_t n_lambda, int32_t 
         hipMemcpy(t->tpl, tp.data(), tp.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
         return bail(tfail("copy failed"));
     if (S) {   // TST from the caller's mask (fast_precompute_TST, mixing.py:319-327)
-        if (hipMalloc((void **)&t->TST, (size_t)n_templates * n_templates * t->npix * 4) != hipSuccess) return bail(tfail("device allocation failed"));
+        if (t->TST.alloc((size_t)n_templates * n_templates * t->npix)) return bail(tfail("device allocation failed"));
         if (hipMemcpy(t->cube, S, (size_t)n_lambda * t->npix * 4, hipMemcpyHostToDevice) != hipSuccess) return bail(tfail("copy failed"));
         dim3 grid((unsigned)((t->npix + TPB - 1) / TPB), (unsigned)(n_templates * n_templates));
         hipLaunchKernelGGL(tst_precompute_kernel, grid, dim3(TPB), 0, 0, t->cube, t->tpl, t->TST, n_templates, n_lambda, t->npix);

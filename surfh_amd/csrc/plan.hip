@@ -5,6 +5,8 @@
 // debug accessors in plan_diag.hip.
 #include "plan_internal.h"
 
+#include <atomic>
+
 namespace surfh_impl {
 
 namespace {
@@ -19,6 +21,33 @@ int fail(const char *fmt, ...) {
     va_end(ap);
     g_err = buf;
     return 1;
+}
+
+// ---- the only two calls of hipMalloc / hipFree in the library (dev_buf.h), counted for surfh_debug_alloc_count ----------------------
+namespace {
+std::atomic<int64_t> g_alloc_live{0}, g_alloc_total{0}, g_alloc_fail_at{0};      // fail_at: value of `total` at which an allocation is refused (0: none)
+}
+int dev_raw_alloc(void **p, size_t bytes) {
+    *p = nullptr;
+    const int64_t nth = ++g_alloc_total;
+    int64_t armed = nth;
+    const hipError_t e = g_alloc_fail_at.compare_exchange_strong(armed, 0) ? hipErrorOutOfMemory : hipMalloc(p, bytes);
+    if (e != hipSuccess) return fail("hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(Tp)) failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+    ++g_alloc_live;
+    return 0;
+}
+void dev_raw_free(void *p) {
+    if (!p) return;
+    hipFree(p);
+    --g_alloc_live;
+}
+int dev_raw_upload(void *dst, const void *src, size_t bytes) {
+    HIP_OK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+    return 0;
+}
+int dev_raw_clear(void *p, size_t bytes, hipStream_t stream, bool async) {
+    if ((async ? hipMemsetAsync(p, 0, bytes, stream) : hipMemset(p, 0, bytes)) != hipSuccess) return fail("memset failed");
+    return 0;
 }
 
 // make stream `to` wait for the work enqueued so far on stream `from`
@@ -70,8 +99,7 @@ int upload_ell(const HostEll &h, DevEll *d) {
             val[(size_t)r * W + e] = h.rows[r][e].second;
         }
     }
-    if (dev_upload(&d->cnt, cnt) || dev_upload(&d->col, col) || dev_upload(&d->val, val) || dev_upload(&d->dst, h.dst))
-        return 1;
+    if (d->cnt.upload(cnt) || d->col.upload(col) || d->val.upload(val) || d->dst.upload(h.dst)) return 1;
     d->t.R = R;
     d->t.W = W;
     d->t.cnt = d->cnt;
@@ -79,21 +107,6 @@ int upload_ell(const HostEll &h, DevEll *d) {
     d->t.val = d->val;
     d->t.dst_off = d->dst;
     return 0;
-}
-
-void free_ell(DevEll *d) {
-    hipFree(d->g_cnt);
-    hipFree(d->g_col);
-    hipFree(d->g_dst);
-    hipFree(d->g_val);
-    hipFree(d->g_rmw);
-    hipFree(d->rmw);
-    hipFree(d->rng);
-    hipFree(d->g_rng);
-    hipFree(d->cnt);
-    hipFree(d->col);
-    hipFree(d->val);
-    hipFree(d->dst);
 }
 
 // rows [r, r + n) of h taken as one group: union of their taps with one weight per member
@@ -140,12 +153,10 @@ int upload_groups(const HostEll &h, const std::vector<std::pair<size_t, size_t>>
             for (int m = 0; m < G; ++m) gval[(gi * W + e) * G + m] = grows[gi][e].second[m];
         }
     }
-    if (dev_upload(&d->g_cnt, gcnt) || dev_upload(&d->g_col, gcol) || dev_upload(&d->g_val, gval) || dev_upload(&d->g_dst, gdst) ||
-        dev_upload(&d->g_rmw, grmw))
-        return 1;
+    if (d->g_cnt.upload(gcnt) || d->g_col.upload(gcol) || d->g_val.upload(gval) || d->g_dst.upload(gdst) || d->g_rmw.upload(grmw)) return 1;
     d->g.NG = (int)NG; d->g.W = W; d->g.G = G; d->g.cnt = d->g_cnt; d->g.col = d->g_col; d->g.val = d->g_val; d->g.dst = d->g_dst; d->g.rmw = d->g_rmw;
     if (ranges) {
-        if (dev_upload(&d->g_rng, grng)) return 1;
+        if (d->g_rng.upload(grng)) return 1;
         d->g.rng = d->g_rng;
     }
     return 0;
@@ -352,15 +363,10 @@ int build_channel(surfh_plan *p, const surfh_channel_desc &d, Channel *c) {
         float wmax = 0.f;
         for (float v : W) wmax = std::max(wmax, std::fabs(v));
         c->sW = gemm_f16x2_scale(wmax);
-        if (dev_upload(&c->W, W) || dev_upload(&c->Wt, Wt)) return 1;
+        if (c->W.upload(W) || c->Wt.upload(Wt)) return 1;
     }
-    if (dev_alloc(&c->Xs, (size_t)c->NP * c->K)) return 1;
-    HIP_OK(hipMemset(c->Xs, 0, (size_t)c->NP * c->K * sizeof(float)));
-    if (!c->bsum) {
-        if (dev_alloc(&c->ymat, (size_t)c->NP * c->LdetP)) return 1;
-        HIP_OK(hipMemset(c->ymat, 0, (size_t)c->NP * c->LdetP * sizeof(float)));
-    }
-    return 0;
+    if (c->Xs.zeros((size_t)c->NP * c->K)) return 1;
+    return !c->bsum && c->ymat.zeros((size_t)c->NP * c->LdetP);
 }
 
 }  // namespace
@@ -575,17 +581,16 @@ int otf_support(surfh_plan *p, const surfh_config *cfg) {
     kbstart[nkb] = (int)vlist.size();
     if (vlist.empty() || (long)vlist.size() == (long)nkb * nch) return 0;       // nothing to drop (or nothing to keep: leave the passes as they are)
     const size_t nyc = (size_t)2 * p->NAP * p->KBP * p->LP;
-    if (dev_upload(&p->otf_vlist, vlist) || dev_upload(&p->otf_kbstart, kbstart) || dev_alloc(&p->ycol_mix, nyc)) return 1;
-    if (hipMemset(p->ycol_mix, 0, nyc * sizeof(float)) != hipSuccess) return fail("memset failed");
+    if (p->otf_vlist.upload(vlist) || p->otf_kbstart.upload(kbstart) || p->ycol_mix.zeros(nyc)) return 1;
     p->otf_nvalid = (int)vlist.size();
     std::vector<int> tabs((size_t)(p->ct ? 4 : 3) * nch);
     for (int j = 0; j < nch; ++j) {
         if (p->ct) {
             // sub-sequence n1 of a length R M: element j stands for the rows R j + n1 and N - (R j - n1); inside the support
             // (folded index <= amax) for j <= (amax + R - 1) / R
-            const int ja = (std::max(amaxk[j], 0) + p->ctA.R - 1) / p->ctA.R, jb = (std::max(bmax[j], 0) + p->ctB.R - 1) / p->ctB.R;
+            const int ja = (std::max(amaxk[j], 0) + p->ctA.R - 1) / p->ctA.R, jb = (std::max(bmax[j], 0) + p->ctB->R - 1) / p->ctB->R;
             tabs[j] = std::min(std::max(ja / 16 + 1, 2), p->ctA.KT);              // forward's complex pass: k-steps in k_alpha
-            tabs[nch + j] = std::min(std::max(jb / 16 + 1, 2), p->ctB.KT);        // forward's pass along beta: k-steps in k_beta
+            tabs[nch + j] = std::min(std::max(jb / 16 + 1, 2), p->ctB->KT);        // forward's pass along beta: k-steps in k_beta
             tabs[2 * nch + j] = bmax[j];                                           // adjoint's first pass: last row k_beta stored; reduction: k_beta limit
             tabs[3 * nch + j] = amaxk[j];                                          // adjoint's complex pass: last folded row k_alpha stored; reduction: limit
             continue;
@@ -595,7 +600,7 @@ int otf_support(surfh_plan *p, const surfh_config *cfg) {
         tabs[2 * nch + j] = bmax[j] + 1;
     }
     const bool ranges = env_on("SURFH_OTF_RANGES", true);
-    if (ranges && dev_upload(&p->otf_tabs, tabs)) return 1;
+    if (ranges && p->otf_tabs.upload(tabs)) return 1;
     return 0;
 }
 
@@ -615,62 +620,7 @@ int surfh_plan_destroy(surfh_plan *p) {
     if (!p) return 0;
     hipSetDevice(p->dev);
     if (p->stream) hipStreamSynchronize(p->stream);
-    for (float *v : {p->sotf, p->tpl, p->mhat, p->spec, p->ycol, p->cube, p->ycol_maps, p->maps_pad, p->Fi, p->Gi, p->Gf,
-                     p->Ff, p->GiT, p->GfT, p->Cma, p->Sma, p->Gc, p->Gs, p->Cf, p->Sf, p->io_cube, p->hth, p->mhat2, p->gcube, p->io_x, p->io_y, p->cg_x, p->cg_r, p->cg_d, p->cg_q, p->cg_b, p->cg_y, p->cg_qm, p->cg_dd, p->cg_hg,
-                     p->rb_y, p->rb_u, p->rb_ag, p->rb_am, p->po_y, p->po_eps, p->po_er, p->po_ec, p->po_eta, p->po_xhat})
-        hipFree(v);
-    hipFree(p->po_S);
-    hipFree(p->h2img);
-    if (p->ctB.img != p->ctA.img) dft_ct_plan_destroy(&p->ctB);
-    else p->ctB = DftCtPlan();
-    dft_ct_plan_destroy(&p->ctA);
-    hipFree(p->adjmix_part);
-    hipFree(p->otf_vlist);
-    hipFree(p->otf_kbstart);
-    hipFree(p->otf_tabs);
-    hipFree(p->ycol_mix);
-    hipFree(p->ycol_adj);
-    hipFree(p->dscal);
-    hipFree(p->dscratch);
-    hipFree(p->cg_hist);
-    hipFree(p->pl_sc);
-    hipFree(p->pl_hsc);
-    for (float *v : p->pn_v) hipFree(v);
-    hipFree(p->dw);
-    hipFree(p->dwy);
-    for (float *v : {p->im_g, p->im_xpad, p->im_xhat, p->im_zpad, p->im_zhat, p->im_io, p->im_y, p->im_w, p->im_wy}) hipFree(v);
-    hipFree(p->pn_sc);
-    hipFree(p->pn_part);
-    hipFree(p->tg_cidx);
-    hipFree(p->tg_pidx);
-    hipFree(p->tg_part);
-    hipFree(p->tg_keep);
-    for (float *v : p->tg_v) hipFree(v);
-    for (auto &c : p->ch) {
-        for (float *v : {c.W, c.Wt, c.Xs, c.Cpart, c.ymat}) hipFree(v);
-        hipFree(c.W16);
-        hipFree(c.Wt16);
-        hipFree(c.klF);
-        hipFree(c.klA);
-        hipFree(c.Xs16);
-        hipFree(c.bscale);
-        hipFree(c.ymat16);
-        hipFree(c.wmat);
-        hipFree(c.amax);
-        hipFree(c.pmax);
-        free_ell(&c.fwd);
-        free_ell(&c.adjT);
-        free_ell(&c.adjRef);
-    }
-    for (auto &r : p->pending) {
-        hipEventDestroy(r.a);
-        hipEventDestroy(r.b);
-    }
-    for (auto e : p->pool) hipEventDestroy(e);
-    for (hipEvent_t e : p->sync_ev) hipEventDestroy(e);
-    if (p->stream2) hipStreamDestroy(p->stream2);
-    if (p->own_stream && p->stream) hipStreamDestroy(p->stream);
-    delete p;
+    delete p;      // the device buffers first (members), then the events and streams (PlanHandles, the base): plan_internal.h
     return 0;
 }
 
@@ -772,8 +722,7 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
     {   // sotf [Lc][Na][Nb/2+1] complex128  ->  [2][KAP][KBP][LP] float (h2: [KAP][KBP][LP][2]), wavelength innermost
         const int nkb = p->Nb / 2 + 1;
         const size_t nsp = (size_t)2 * p->PL * LP;
-        if (dev_alloc(&p->sotf, nsp)) return bail(1);
-        if (hipMemset(p->sotf, 0, nsp * sizeof(float)) != hipSuccess) return bail(fail("memset failed"));
+        if (p->sotf.zeros(nsp)) return bail(1);
         std::vector<float> row((size_t)2 * p->KBP * LP);
         for (int a = 0; a < p->Na; ++a) {
             std::fill(row.begin(), row.end(), 0.f);
@@ -807,15 +756,13 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
         for (int k = 0; k < p->T; ++k)
             for (int l = 0; l < p->Lown; ++l)
                 if (p->planes[l] >= 0) t[(size_t)k * LP + l] = (float)cfg->templates[(size_t)k * p->Lc + p->planes[l]];
-        if (dev_upload(&p->tpl, t)) return bail(1);
+        if (p->tpl.upload(t)) return bail(1);
         p->tpl_host.assign(cfg->templates, cfg->templates + (size_t)p->T * p->Lc);
     }
     {
         std::vector<float> Fi, Gi, Gf, Ff, GiT, GfT;
         build_dft(p, Fi, Gi, Gf, Ff, GiT, GfT);
-        if (dev_upload(&p->Fi, Fi) || dev_upload(&p->Gi, Gi) || dev_upload(&p->Gf, Gf) || dev_upload(&p->Ff, Ff) ||
-            dev_upload(&p->GiT, GiT) || dev_upload(&p->GfT, GfT))
-            return bail(1);
+        if (p->Fi.upload(Fi) || p->Gi.upload(Gi) || p->Gf.upload(Gf) || p->Ff.upload(Ff) || p->GiT.upload(GiT) || p->GfT.upload(GfT)) return bail(1);
     }
     {   // folded-DFT matrices
         p->dense_dft = env_on("SURFH_DFT_DENSE", false);
@@ -852,9 +799,7 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
                 Cf[(size_t)k * p->KPb + b] = (float)(std::cos(th) * sb);         // rows k_beta, cols beta
                 Sf[(size_t)k * p->KPb + b] = (float)(std::sin(th) * sb);
             }
-        if (dev_upload(&p->Cma, Cma) || dev_upload(&p->Sma, Sma) || dev_upload(&p->Gc, Gc) || dev_upload(&p->Gs, Gs) ||
-            dev_upload(&p->Cf, Cf) || dev_upload(&p->Sf, Sf))
-            return bail(1);
+        if (p->Cma.upload(Cma) || p->Sma.upload(Sma) || p->Gc.upload(Gc) || p->Gs.upload(Gs) || p->Cf.upload(Cf) || p->Sf.upload(Sf)) return bail(1);
         if (cfg->verify) {      // verification plan: dense DFT products, unfused spectral mix, fp32-operand spectral blur -- all float64-accumulated
             p->verify = true;
             p->dense_dft = true;
@@ -870,7 +815,7 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
                 p->h2kA[1] = dft_h2_build_image(Gc.data(), Gs.data(), p->MPb, p->KPb, p->KPb, im.data() + DFT_H2_IMAGE_HALFS);
                 p->h2kA[2] = dft_h2_build_image(Cf.data(), Sf.data(), p->MPb, p->KPb, p->KPb, im.data() + 2 * DFT_H2_IMAGE_HALFS);
             }
-            if (dev_upload(&p->h2img, im)) return bail(1);
+            if (p->h2img.upload(im)) return bail(1);
         }
         if (p->h2) {
             // fused adjoint tail: the last pass of rfft2 multiplies by conj(sotf) and reduces over the wavelengths itself
@@ -878,14 +823,14 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
             if (env_on("SURFH_ADJ_FUSED", true) && p->T >= 1 && p->T <= 4 && p->Na >= 127 && p->Na <= 255 && p->LP % 128 == 0) {
                 if (otf_support(p, cfg)) return bail(1);
                 const size_t npart = dft_h2_adjmix_part_floats(p->LP, p->Nb / 2 + 1, p->otf_nvalid);
-                if (npart && dev_alloc(&p->adjmix_part, npart)) return bail(1);
+                if (npart && p->adjmix_part.alloc(npart)) return bail(1);
             }
         }
         if (p->ct) {   // image + twiddles per transform length of the axes that run on dft_ct (dft_ct.h)
             if (p->ax_a == 2 && dft_ct_plan_create(p->Na, &p->ctA)) return bail(fail("dft_ct plan (n_alpha = %d) failed", p->Na));
             if (p->ax_b == 2) {
-                if (p->ax_a == 2 && p->Nb == p->Na) p->ctB = p->ctA;
-                else if (dft_ct_plan_create(p->Nb, &p->ctB)) return bail(fail("dft_ct plan (n_beta = %d) failed", p->Nb));
+                if (p->ax_a == 2 && p->Nb == p->Na) p->ctB = &p->ctA;
+                else if (dft_ct_plan_create(p->Nb, &p->ctB_own)) return bail(fail("dft_ct plan (n_beta = %d) failed", p->Nb));
             }
             if (p->ax_a == 2 && p->ax_b == 2 && p->T >= 1 && p->T <= 4 && otf_support(p, cfg)) return bail(1);      // lists: both axes on dft_ct
         }
@@ -897,15 +842,14 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
     const size_t nmhat = p->T > 0 ? (size_t)p->T * 2 * p->PL : nspec;
     const size_t nmaps = (size_t)std::max(p->T, 1) * p->PLc;
     const size_t nycm = (size_t)std::max(p->T, 1) * 2 * p->NAP * p->KBP;
-    if (dev_alloc(&p->spec, nspec) || dev_alloc(&p->ycol, nycol) || dev_alloc(&p->cube, ncube) ||
-        dev_alloc(&p->mhat, nmhat) || dev_alloc(&p->maps_pad, nmaps) || dev_alloc(&p->ycol_maps, nycm))
+    // all six allocated, then all six cleared: the order of the allocations is part of what keeps the addresses where they were
+    if (p->spec.alloc(nspec) || p->ycol.alloc(nycol) || p->cube.alloc(ncube) || p->mhat.alloc(nmhat) || p->maps_pad.alloc(nmaps) ||
+        p->ycol_maps.alloc(nycm))
         return bail(1);
-    hipMemset(p->spec, 0, nspec * sizeof(float));
-    hipMemset(p->ycol, 0, nycol * sizeof(float));
-    hipMemset(p->cube, 0, ncube * sizeof(float));
-    hipMemset(p->mhat, 0, nmhat * sizeof(float));
-    hipMemset(p->maps_pad, 0, nmaps * sizeof(float));
-    hipMemset(p->ycol_maps, 0, nycm * sizeof(float));
+    if (dev_raw_clear(p->spec, nspec * sizeof(float), nullptr, false) || dev_raw_clear(p->ycol, nycol * sizeof(float), nullptr, false) ||
+        dev_raw_clear(p->cube, ncube * sizeof(float), nullptr, false) || dev_raw_clear(p->mhat, nmhat * sizeof(float), nullptr, false) ||
+        dev_raw_clear(p->maps_pad, nmaps * sizeof(float), nullptr, false) || dev_raw_clear(p->ycol_maps, nycm * sizeof(float), nullptr, false))
+        return bail(1);
     p->ycm_planes = std::max(p->T, 1);
     // ---- channels -------------------------------------------------------------------------
     p->a_lo = p->b_lo = 1 << 30; p->a_hi = p->b_hi = 0;      // alpha / beta range of the pixels the channels' tables touch (build_channel)
@@ -922,14 +866,15 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
         if (f16) {
             const long nw = (long)c.LdetP * c.K;
             const long nwv = ymat_from_y_waves(c.P * c.S, c.Ldet, c.aout);
-            if (dev_alloc(&c.W16, (size_t)2 * nw) || dev_alloc(&c.Wt16, (size_t)2 * nw) || dev_alloc(&c.amax, (size_t)c.NP) ||
-                dev_alloc(&c.pmax, (size_t)nwv) || dev_alloc(&c.ymat16, (size_t)2 * c.NP * c.LdetP) || dev_alloc(&c.Xs16, (size_t)2 * c.NP * c.K))
+            if (c.W16.alloc((size_t)2 * nw) || c.Wt16.alloc((size_t)2 * nw) || c.amax.alloc((size_t)c.NP) || c.pmax.alloc((size_t)nwv) ||
+                c.ymat16.alloc((size_t)2 * c.NP * c.LdetP) || c.Xs16.alloc((size_t)2 * c.NP * c.K))
                 return bail(1);
-            hipMemset(c.pmax, 0, (size_t)nwv * sizeof(unsigned));       // entries of workgroups that exit early stay 0
-            hipMemset(c.amax, 0, (size_t)c.NP * sizeof(unsigned));
-            hipMemset(c.Xs16, 0, (size_t)2 * c.NP * c.K * sizeof(unsigned short));       // padding rows / columns stay zero
+            if (dev_raw_clear(c.pmax, (size_t)nwv * sizeof(unsigned), nullptr, false) ||       // entries of workgroups that exit early stay 0
+                dev_raw_clear(c.amax, (size_t)c.NP * sizeof(unsigned), nullptr, false) ||
+                dev_raw_clear(c.Xs16, (size_t)2 * c.NP * c.K * sizeof(unsigned short), nullptr, false))       // padding rows / columns stay zero
+                return bail(1);
             std::vector<float> ones((size_t)c.nbs * ((c.LinP + 1023) / 1024) * c.NP, 1.f);   // segments never written: scale 1
-            if (dev_upload(&c.bscale, ones)) return bail(1);
+            if (c.bscale.upload(ones)) return bail(1);
             if (launch_split2h(p->stream, c.W, c.W16, nw, nw, c.sW) || launch_split2h(p->stream, c.Wt, c.Wt16, nw, nw, c.sW))
                 return bail(fail("operand split failed"));
             const bool far_steps = !(cfg->exact & 1) && env_on("SURFH_WBLUR_FAR", true);      // read at plan creation
@@ -940,7 +885,7 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
                 std::vector<int> kl;
                 if (hipMemcpy(hw.data(), c.W, (size_t)nw * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return bail(fail("copy failed"));
                 build_klist(hw.data(), c.LdetP, c.K, c.K, c.LinP, segChunks, 1.0 / 256, far_tol2, &kl, &c.klFs, &c.ksteps[0], &c.ksteps[1]);
-                if (c.ksteps[1] > 0 && dev_upload(&c.klF, kl)) return bail(1);
+                if (c.ksteps[1] > 0 && c.klF.upload(kl)) return bail(1);
                 if (hipMemcpy(hw.data(), c.Wt, (size_t)nw * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return bail(fail("copy failed"));
                 // the adjoint's constant operand has one row per (beta column, wavelength): a tile of 64 wavelengths of four
                 // neighbouring columns sees the response's diagonal in 2-3 of its K steps, 256 wavelengths of one column in 9
@@ -948,13 +893,12 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
                 const int pP = perm && c.LinP % 64 == 0 && c.nbs >= 4 ? 4 : 0;
                 build_klist(hw.data(), c.K, KA, c.LdetP, 0, 0, 1.0 / 256, far_tol2, &kl, &c.klAs, &c.ksteps[2], &c.ksteps[3], pP, c.LinP);
                 if (c.ksteps[3] > 0) {
-                    if (dev_upload(&c.klA, kl)) return bail(1);
+                    if (c.klA.upload(kl)) return bail(1);
                     c.permA = pP;
                 }
             }
         }
-        if (dev_alloc(&c.Cpart, (size_t)c.splitK * c.LdetP * c.NP)) return bail(1);
-        hipMemset(c.Cpart, 0, (size_t)c.splitK * c.LdetP * c.NP * sizeof(float));
+        if (c.Cpart.zeros((size_t)c.splitK * c.LdetP * c.NP)) return bail(1);
     }
     p->osize = yoff;
     if (p->a_hi <= p->a_lo) { p->a_lo = 0; p->a_hi = p->Na; }
@@ -963,8 +907,7 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
         if (!env_on("SURFH_ALPHA_RANGE", true)) { p->a_lo = 0; p->a_hi = p->Na; p->b_lo = 0; p->b_hi = p->Nb; }
         if (p->ilv && p->a_hi - p->a_lo < p->Na) {      // the adjoint's intermediate: columns outside the range zero for good
             const size_t nyc = (size_t)2 * p->NAP * p->KBP * p->LP;
-            if (dev_alloc(&p->ycol_adj, nyc)) return bail(1);
-            if (hipMemset(p->ycol_adj, 0, nyc * sizeof(float)) != hipSuccess) return bail(fail("memset failed"));
+            if (p->ycol_adj.zeros(nyc)) return bail(1);
         }
     }
     {   // The adjoint scatters channel after channel into the cleared cube.  A (pixel, 1024-wavelength chunk) of channel c
@@ -1024,7 +967,7 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
                 if (upload_groups(h, runs, &mask, &c.adjT, SCATTER_G, &ranges)) return bail(1);
             }
             c.adjT_host = HostEll();
-            if (dev_upload(&c.adjT.rmw, mask) || dev_upload(&c.adjT.rng, ranges)) return bail(1);
+            if (c.adjT.rmw.upload(mask) || c.adjT.rng.upload(ranges)) return bail(1);
             c.adjT.t.rng = c.adjT.rng;
             if (!env_on("SURFH_SCATTER_RMW_ALL", false)) c.adjT.t.rmw = c.adjT.rmw;        // 1: read-modify-write everywhere (A/B)
             c.adjT.host_dst.clear();
@@ -1032,8 +975,7 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
         }
         if (exact_ok && !p->ch.empty()) {      // dedicated accumulator, cleared once: the exact ranges keep it consistent
             const size_t ncube = (size_t)p->NBP * p->NAP * p->LP;
-            if (dev_alloc(&p->gcube, ncube)) return bail(1);
-            if (hipMemset(p->gcube, 0, ncube * sizeof(float)) != hipSuccess) return bail(fail("memset failed"));
+            if (p->gcube.zeros(ncube)) return bail(1);
         } else {
             for (auto &c : p->ch) {
                 c.adjT.t.rng = nullptr;
@@ -1041,8 +983,8 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
             }
         }
     }
-    if (dev_alloc(&p->io_x, (size_t)p->isize) || dev_alloc(&p->io_y, (size_t)p->osize) || dev_alloc(&p->cg_y, (size_t)p->osize) ||
-        dev_alloc(&p->dscal, 16) || dev_alloc(&p->dscratch, std::max({(size_t)1024, launch_huber_vox_scratch_doubles(), launch_robust_scratch_doubles()})))
+    if (p->io_x.alloc((size_t)p->isize) || p->io_y.alloc((size_t)p->osize) || p->cg_y.alloc((size_t)p->osize) || p->dscal.alloc(16) ||
+        p->dscratch.alloc(std::max({(size_t)1024, launch_huber_vox_scratch_doubles(), launch_robust_scratch_doubles()})))
         return bail(1);
     if (hipDeviceSynchronize() != hipSuccess) return bail(fail("device error during plan creation: %s", hipGetErrorString(hipGetLastError())));
     *out = p;
@@ -1079,33 +1021,26 @@ int surfh_get_potential(const surfh_plan *p, int32_t slot) {
 }
 // ---- data weights: plan state, like the prior ------------------------------------------------------------------------------------
 namespace {
-// installs the validated device weights w_new [osize] (taken over) or, with nullptr, clears the state; on failure the plan keeps what it had
-int install_data_weights(surfh_plan *p, float *w_new) {
-    std::vector<float *> wm(p->ch.size(), nullptr);
-    float *wy = nullptr;
-    auto drop = [&](int rc) {
-        for (float *v : wm) hipFree(v);
-        hipFree(wy);
-        hipFree(w_new);
-        return rc;
-    };
+// installs the validated device weights w_new [osize] (taken over) or, with an empty buffer, clears the state; on failure the
+// plan keeps what it had
+int install_data_weights(surfh_plan *p, DevBuf<float> w_new) {
+    std::vector<DevBuf<float>> wm(p->ch.size());
+    DevBuf<float> wy;
     if (w_new) {
         hipStream_t s = p->stream;
-        if (dev_alloc(&wy, (size_t)p->osize)) return drop(1);
+        if (wy.alloc((size_t)p->osize)) return 1;
         for (size_t i = 0; i < p->ch.size(); ++i) {
             const Channel &c = p->ch[i];
             if (c.bsum || !c.ymat16) continue;
-            const size_t n = (size_t)c.NP * c.LdetP;
-            if (dev_alloc(&wm[i], n)) return drop(1);
-            if (hipMemsetAsync(wm[i], 0, n * sizeof(float), s) != hipSuccess) return drop(fail("memset failed"));
-            if (launch_ymat_from_y(s, w_new + c.yoff, wm[i], c.P * c.S, c.Ldet, c.aout, c.LdetP) != 0) return drop(fail("launch_ymat_from_y failed"));
+            if (wm[i].zeros((size_t)c.NP * c.LdetP, s)) return 1;
+            if (launch_ymat_from_y(s, w_new + c.yoff, wm[i], c.P * c.S, c.Ldet, c.aout, c.LdetP) != 0) return fail("launch_ymat_from_y failed");
         }
     }
-    if (hipStreamSynchronize(p->stream) != hipSuccess) return drop(fail("stream synchronisation failed"));   // nothing in flight reads the old buffers
-    for (size_t i = 0; i < p->ch.size(); ++i) std::swap(p->ch[i].wmat, wm[i]);
-    std::swap(p->dwy, wy);
-    std::swap(p->dw, w_new);
-    return drop(0);
+    if (hipStreamSynchronize(p->stream) != hipSuccess) return fail("stream synchronisation failed");   // nothing in flight reads the old buffers
+    for (size_t i = 0; i < p->ch.size(); ++i) p->ch[i].wmat.swap(wm[i]);
+    p->dwy.swap(wy);
+    p->dw.swap(w_new);
+    return 0;
 }
 int data_weights_check(surfh_plan *p) {
     if (!p) return fail("null plan");
@@ -1117,37 +1052,36 @@ int data_weights_check(surfh_plan *p) {
 
 int surfh_set_data_weights(surfh_plan *p, const float *w) {
     if (data_weights_check(p)) return 1;
-    if (!w) return install_data_weights(p, nullptr);
+    if (!w) return install_data_weights(p, {});
     for (long i = 0; i < p->osize; ++i)
         if (!(w[i] >= 0.f && w[i] <= FLT_MAX)) return fail("data weight %ld is %g: weights are finite and >= 0", i, (double)w[i]);
-    float *wd = nullptr;
-    if (dev_alloc(&wd, (size_t)p->osize)) return 1;
-    if (hipMemcpyAsync(wd, w, p->osize * sizeof(float), hipMemcpyHostToDevice, p->stream) != hipSuccess) {
-        hipFree(wd);
-        return fail("copy failed");
-    }
-    return install_data_weights(p, wd);
+    DevBuf<float> wd;
+    if (wd.alloc((size_t)p->osize)) return 1;
+    if (hipMemcpyAsync(wd, w, p->osize * sizeof(float), hipMemcpyHostToDevice, p->stream) != hipSuccess) return fail("copy failed");
+    return install_data_weights(p, std::move(wd));
 }
 int surfh_set_data_weights_dev(surfh_plan *p, const float *w_dev) {
     if (data_weights_check(p)) return 1;
-    if (!w_dev) return install_data_weights(p, nullptr);
+    if (!w_dev) return install_data_weights(p, {});
     hipStream_t s = p->stream;
-    float *wd = nullptr;
-    unsigned *cnt = nullptr, bad = 0;
-    if (dev_alloc(&wd, (size_t)p->osize) || dev_alloc(&cnt, 1)) {
-        hipFree(wd);
-        return 1;
-    }
+    DevBuf<float> wd;
+    DevBuf<unsigned> cnt;
+    unsigned bad = 0;
+    if (wd.alloc((size_t)p->osize) || cnt.alloc(1)) return 1;
     const bool ok = hipMemcpyAsync(wd, w_dev, p->osize * sizeof(float), hipMemcpyDeviceToDevice, s) == hipSuccess &&
                     hipMemsetAsync(cnt, 0, sizeof(unsigned), s) == hipSuccess && launch_weight_count_bad(s, wd, p->osize, cnt) == 0 &&
                     hipMemcpyAsync(&bad, cnt, sizeof(unsigned), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-    hipFree(cnt);
-    if (!ok || bad) {
-        hipFree(wd);
-        return ok ? fail("%u data weights are negative or not finite: weights are finite and >= 0", bad) : fail("data weight check failed");
-    }
-    return install_data_weights(p, wd);
+    cnt.reset();
+    if (!ok || bad) return ok ? fail("%u data weights are negative or not finite: weights are finite and >= 0", bad) : fail("data weight check failed");
+    return install_data_weights(p, std::move(wd));
 }
 int surfh_has_data_weights(const surfh_plan *p) { return p && p->dw ? 1 : 0; }
+
+// ---- diagnostics of the allocator (host code only) ---------------------------------------------------------------------------------
+void surfh_debug_alloc_count(int64_t *live, int64_t *total) {
+    if (live) *live = g_alloc_live.load();
+    if (total) *total = g_alloc_total.load();
+}
+void surfh_debug_alloc_fail(int64_t nth) { g_alloc_fail_at.store(nth > 0 ? g_alloc_total.load() + nth : 0); }
 
 }  // extern "C"

@@ -193,11 +193,9 @@ int surfh_gemm_selftest_ms(double *ms) {
 int surfh_gemm_selftest(int32_t device, int32_t M, int32_t N, int32_t K, int32_t split_k, const float *A,
                         const float *B, float *C) {
     HIP_OK(hipSetDevice(device));
-    float *dA = nullptr, *dB = nullptr, *dC = nullptr;
+    DevBuf<float> dA, dB, dC;
     const int sk = std::max(1, (int)split_k);
-    HIP_OK(hipMalloc((void **)&dA, (size_t)M * K * 4));
-    HIP_OK(hipMalloc((void **)&dB, (size_t)K * N * 4));
-    HIP_OK(hipMalloc((void **)&dC, (size_t)sk * M * N * 4));
+    if (dA.alloc((size_t)M * K) || dB.alloc((size_t)K * N) || dC.alloc((size_t)sk * M * N)) return 1;
     HIP_OK(hipMemcpy(dA, A, (size_t)M * K * 4, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(dB, B, (size_t)K * N * 4, hipMemcpyHostToDevice));
     GemmArgs g;
@@ -212,8 +210,8 @@ int surfh_gemm_selftest(int32_t device, int32_t M, int32_t N, int32_t K, int32_t
             for (int n = 0; n < N; ++n) bt[(size_t)n * K + k] = B[(size_t)k * N + n];
         HIP_OK(hipMemcpy(dB, bt.data(), bt.size() * 4, hipMemcpyHostToDevice));
         g.ldb = K;
-        unsigned short *dB16 = nullptr, *dA16 = nullptr;
-        unsigned *dmax = nullptr;
+        DevBuf<unsigned short> dB16, dA16;       // two fp16 pieces per element
+        DevBuf<unsigned> dmax;
         float amB = 0.f;
         for (float v : bt) amB = std::max(amB, std::fabs(v));
         std::vector<unsigned> rows((size_t)M, 0u);           // max |A[m][:]| as bit patterns
@@ -222,15 +220,13 @@ int surfh_gemm_selftest(int32_t device, int32_t M, int32_t N, int32_t K, int32_t
             for (int k = 0; k < K; ++k) am = std::max(am, std::fabs(A[(size_t)m * K + k]));
             memcpy(&rows[m], &am, 4);
         }
-        HIP_OK(hipMalloc((void **)&dB16, bt.size() * 4));
-        HIP_OK(hipMalloc((void **)&dmax, rows.size() * sizeof(unsigned)));
-        HIP_OK(hipMalloc((void **)&dA16, (size_t)M * K * 4));
+        if (dB16.alloc(bt.size() * 2) || dmax.alloc(rows.size()) || dA16.alloc((size_t)M * K * 2)) return 1;
         HIP_OK(hipMemcpy(dmax, rows.data(), rows.size() * sizeof(unsigned), hipMemcpyHostToDevice));
         g.sB16 = gemm_f16x2_scale(amB); g.B16 = dB16; g.pB16 = (long)bt.size(); g.amax = dmax;
         rc = launch_split2h(nullptr, dB, dB16, (long)bt.size(), (long)bt.size(), g.sB16);
         if (rc == 0) rc = launch_split_rows2h(nullptr, dA, dmax, dA16, M, K, (long)M * K);
         g.A3 = dA16; g.pA3 = (long)M * K;
-        int *dkl = nullptr;
+        DevBuf<int> dkl;
         g_selftest_ksteps[0] = g_selftest_ksteps[1] = 0;
         if (mode[0] == '2') {      // with K-step lists, classes and tolerances as at plan creation
             std::vector<int> kl;
@@ -240,7 +236,7 @@ int surfh_gemm_selftest(int32_t device, int32_t M, int32_t N, int32_t K, int32_t
             if (lin > 0) { g.permP = 4; g.permLin = lin; }
             build_klist(bt.data(), N, K, K, 0, 0, 1.0 / 256, 1.0 / 1024, &kl, &g.klistStride, &g_selftest_ksteps[0], &g_selftest_ksteps[1], g.permP,
                         g.permLin);
-            if (dev_upload(&dkl, kl)) return 1;
+            if (dkl.upload(kl)) return 1;
             g.klist = dkl;
         }
         if (rc == 0) rc = launch_gemm_nt_f16x2_cc(nullptr, g);
@@ -263,17 +259,12 @@ int surfh_gemm_selftest(int32_t device, int32_t M, int32_t N, int32_t K, int32_t
             hipEventDestroy(ea);
             hipEventDestroy(eb);
         }
-        hipFree(dkl);
-        hipFree(dB16);
-        hipFree(dmax);
-        hipFree(dA16);
     } else {
         rc = launch_gemm_f32(nullptr, g);
     }
     if (rc == 0) rc = (int)hipDeviceSynchronize();
     std::vector<float> h((size_t)sk * M * N);
     if (rc == 0) rc = (int)hipMemcpy(h.data(), dC, h.size() * 4, hipMemcpyDeviceToHost);
-    hipFree(dA); hipFree(dB); hipFree(dC);
     if (rc) return fail("gemm selftest failed: %s", hipGetErrorString((hipError_t)rc));
     for (size_t i = 0; i < (size_t)M * N; ++i) {
         float s = 0.f;

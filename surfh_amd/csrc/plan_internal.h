@@ -45,6 +45,7 @@
 #include <vector>
 
 #include "../../include/surfh_amd.h"
+#include "dev_buf.h"
 #include "dft_h2.h"
 #include "dft_ct.h"
 #include "gemm_f32.h"
@@ -53,8 +54,8 @@
 
 namespace surfh_impl __attribute__((visibility("hidden"))) {
 
-// records the message surfh_last_error() returns and returns 1; defined once, in plan.hip, beside the thread's error string
-int fail(const char *fmt, ...);
+// fail(): records the message surfh_last_error() returns and returns 1 (declared in dev_buf.h; defined once, in plan.hip, beside
+// the thread's error string)
 
 // a boolean SURFH_* switch: `dflt` when the variable is unset or empty; a default-on switch goes off only with a leading '0',
 // a default-off switch goes on only with a leading '1'
@@ -83,19 +84,19 @@ struct HostEll {
 };
 
 struct DevEll {
-    EllTable t;
-    int32_t *cnt = nullptr;
-    int64_t *col = nullptr, *dst = nullptr;
-    float *val = nullptr;
-    uint32_t *rmw = nullptr;            // scatter tables: chunks of a row that need read-modify-write (EllTable::rmw)
-    int2 *rng = nullptr, *g_rng = nullptr;   // ... or the exact wavelength ranges (EllTable::rng, GroupTable::rng)
+    EllTable t;                         // views of the buffers below, as the kernels take them
+    DevBuf<int32_t> cnt;
+    DevBuf<int64_t> col, dst;
+    DevBuf<float> val;
+    DevBuf<uint32_t> rmw;               // scatter tables: chunks of a row that need read-modify-write (EllTable::rmw)
+    DevBuf<int2> rng, g_rng;            // ... or the exact wavelength ranges (EllTable::rng, GroupTable::rng)
     std::vector<int64_t> host_dst;      // kept for the scatter tables until the plan is complete
-    // the same table with its rows grouped SCATTER_G at a time (GroupTable)
+    // the same table with its rows grouped SCATTER_G at a time (GroupTable, views likewise)
     GroupTable g;
-    int32_t *g_cnt = nullptr;
-    int64_t *g_col = nullptr, *g_dst = nullptr;
-    float *g_val = nullptr;
-    uint32_t *g_rmw = nullptr;
+    DevBuf<int32_t> g_cnt;
+    DevBuf<int64_t> g_col, g_dst;
+    DevBuf<float> g_val;
+    DevBuf<uint32_t> g_rmw;
 };
 
 struct Channel {
@@ -108,24 +109,24 @@ struct Channel {
     int nlam = 0;      // LinA rounded up to 4: wavelengths the gather kernels process
     int K = 0, NP = 0, LdetP = 0, splitK = 1;
     long yoff = 0, ysize = 0;
-    float *W = nullptr, *Wt = nullptr, *Xs = nullptr, *Cpart = nullptr, *ymat = nullptr;
-    unsigned short *W16 = nullptr, *Wt16 = nullptr; // ... or into their two fp16 pieces [2][rows][cols] of W / sW (gemm_cc16.hip)
-    unsigned short *Xs16 = nullptr, *ymat16 = nullptr;   // the data operands as fp16 pieces (all-consumer kernel, gemm_cc16.hip)
-    float *bscale = nullptr;                        // Xs16's scales, one per (row, K segment): [nbs * ceil(LinP/1024)][NP]
+    DevBuf<float> W, Wt, Xs, Cpart, ymat;
+    DevBuf<unsigned short> W16, Wt16;               // ... or into their two fp16 pieces [2][rows][cols] of W / sW (gemm_cc16.hip)
+    DevBuf<unsigned short> Xs16, ymat16;            // the data operands as fp16 pieces (all-consumer kernel, gemm_cc16.hip)
+    DevBuf<float> bscale;                           // Xs16's scales, one per (row, K segment): [nbs * ceil(LinP/1024)][NP]
     float sW = 1.f;
     // K-step classes of the two GEMMs (gemm_cc16.hip, build_klist below): per 256-row tile of W16 / Wt16 the steps that keep
     // all three products and the steps kept as h*h only; ksteps = (near, far) of the forward, (near, far) of the adjoint
-    int *klF = nullptr, *klA = nullptr;
+    DevBuf<int> klF, klA;
     int klFs = 0, klAs = 0;
     int permA = 0;                      // adjoint GEMM: a tile takes 256 / permA wavelengths of each of permA neighbouring beta columns (0: 256 consecutive rows)
     long ksteps[4] = {0, 0, 0, 0};
-    unsigned *amax = nullptr;                       // [2][NP] max |row| of the data operands: Xs (forward), ymat (adjoint)
-    unsigned *pmax = nullptr;                       // per-wave maxima of the kernel that wrote the operand (reduced into amax)
+    DevBuf<unsigned> amax;                          // [2][NP] max |row| of the data operands: Xs (forward), ymat (adjoint)
+    DevBuf<unsigned> pmax;                          // per-wave maxima of the kernel that wrote the operand (reduced into amax)
     DevEll fwd, adjT, adjRef;
     HostEll adjT_host;                  // kept until the grouped scatter table is built (plan creation)
     bool has_ref = false;
     bool bsum = false;   // no spectral blur: y[l][(p,s,a)] = sum over the slit's beta columns (MRSBlurred)
-    float *wmat = nullptr;              // data weights of the channel in ymat's layout [NP][LdetP], padding zero (channels with ymat16; surfh_set_data_weights)
+    DevBuf<float> wmat;                 // data weights of the channel in ymat's layout [NP][LdetP], padding zero (channels with ymat16; surfh_set_data_weights)
 };
 
 struct ProfRec {
@@ -137,15 +138,36 @@ struct ProfRec {
 
 using namespace surfh_impl;      // struct surfh_plan is the C ABI's opaque type and stays at global scope
 
-struct surfh_plan {
+// The plan's streams and events, as a base class of the plan: a base is destroyed after the members of the derived class, so
+// `delete p` frees every device buffer (the DevBuf members below) first and destroys the events and streams last -- the order
+// surfh_plan_destroy has always kept.  A destructor body of surfh_plan would run BEFORE its members and reverse it.
+struct PlanHandles {
     int dev = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     // second stream: the spectral-blur GEMMs run here while the gather / scatter of the neighbouring channel runs on
     // `stream` (different units: matrix cores vs L2 bandwidth, and the GEMM leaves registers for them on every SIMD)
     hipStream_t stream2 = nullptr;
-    bool overlap = false;
     std::vector<hipEvent_t> sync_ev;             // dependency events between the two streams (no timing)
+    std::vector<ProfRec> pending;                // profiling: recorded stage brackets, and events free for reuse
+    std::vector<hipEvent_t> pool;
+    PlanHandles() = default;
+    PlanHandles(const PlanHandles &) = delete;
+    PlanHandles &operator=(const PlanHandles &) = delete;
+    ~PlanHandles() {
+        for (auto &r : pending) {
+            hipEventDestroy(r.a);
+            hipEventDestroy(r.b);
+        }
+        for (hipEvent_t e : pool) hipEventDestroy(e);
+        for (hipEvent_t e : sync_ev) hipEventDestroy(e);
+        if (stream2) hipStreamDestroy(stream2);
+        if (own_stream && stream) hipStreamDestroy(stream);
+    }
+};
+
+struct surfh_plan : PlanHandles {
+    bool overlap = false;
     size_t sync_next = 0;
     int Na = 0, Nb = 0, Lc = 0, T = 0, NAP = 0, NBP = 0, KAP = 0, KBP = 0;
     long PL = 0, PLc = 0;
@@ -159,11 +181,11 @@ struct surfh_plan {
         for (auto &g : segs) if (l >= g.start && l <= g.start + g.len) return g.coff + (l - g.start);
         return -1;
     }
-    float *sotf = nullptr, *tpl = nullptr, *mhat = nullptr, *spec = nullptr, *ycol = nullptr, *cube = nullptr,
-          *maps_pad = nullptr, *ycol_maps = nullptr;
-    float *Fi = nullptr, *Gi = nullptr, *Gf = nullptr, *Ff = nullptr, *GiT = nullptr, *GfT = nullptr;
+    // device memory: every DevBuf member owns its buffer (dev_buf.h); the few raw device pointers left are views and say so
+    DevBuf<float> sotf, tpl, mhat, spec, ycol, cube, maps_pad, ycol_maps;
+    DevBuf<float> Fi, Gi, Gf, Ff, GiT, GfT;
     // folded-DFT matrices [MPx][KPx]: cos/sin along alpha; weighted cos/sin for c2r; plain cos/sin for r2c
-    float *Cma = nullptr, *Sma = nullptr, *Gc = nullptr, *Gs = nullptr, *Cf = nullptr, *Sf = nullptr;
+    DevBuf<float> Cma, Sma, Gc, Gs, Cf, Sf;
     int MPa = 0, KPa = 0, MPb = 0, KPb = 0;
     int n_cu = 256;
     bool gather_sorted = true;                   // gather rows ordered by cube location (L2 reuse across pointings)
@@ -182,11 +204,12 @@ struct surfh_plan {
     // two-piece fp16 passes with LDS-resident matrices (dft_h2.h): the plan's complex arrays (sotf, spec, ycol, and
     // mhat when T == 0) are then INTERLEAVED [..][LP][2] instead of planar [2][..][LP]
     bool h2 = false;
-    unsigned short *h2img = nullptr;             // three images: (Cma, Sma), (Gc, Gs), (Cf, Sf)
+    DevBuf<unsigned short> h2img;                // three images: (Cma, Sma), (Gc, Gs), (Cf, Sf)
     // Cooley-Tukey passes (dft_ct.h) for lengths whose folded matrix does not fit LDS (N = R * M: 501, 512, ...); same
     // interleaved layout.  ilv = h2 || ct is the layout flag of the complex arrays.
     bool ct = false, ilv = false;
-    DftCtPlan ctA, ctB;                          // transform lengths Na / Nb (ctB aliases ctA when they are equal)
+    DftCtPlan ctA, ctB_own;                      // transform lengths Na / Nb; ctB_own stays empty when they are equal
+    const DftCtPlan *ctB = &ctB_own;             // view: the plan that serves beta (&ctA when Nb == Na)
     // which kernel transforms an axis: the choice is per axis (a 300 x 64 image runs dft_ct along alpha and dft_h2 along beta);
     // h2 = both axes on dft_h2 (fused adjoint tail, OTF-support lists), ct = at least one axis on dft_ct.  An axis neither covers
     // (a prime factor above 190, fewer than 32 points) puts the plan on the dense fp32 products with planar arrays.
@@ -195,78 +218,77 @@ struct surfh_plan {
     // over alpha skip the rest (forward: the cube outside is never read; adjoint: it is zero).  ycol_adj: the adjoint's
     // intermediate in its own buffer, whose columns outside the range stay zero from plan creation on.
     int a_lo = 0, a_hi = 0, b_lo = 0, b_hi = 0;  // (b: the same for the cube rows beta)
-    float *ycol_adj = nullptr;
-    float *adjmix_part = nullptr;                // fused adjoint tail (dft_h2_adjmix_kernel): partial sums per (k_beta, slot); null: off
+    DevBuf<float> ycol_adj;
+    DevBuf<float> adjmix_part;                   // fused adjoint tail (dft_h2_adjmix_kernel): partial sums per (k_beta, slot); null: off
     // Support of the OTF (otf_support below): the (k_beta, chunk of 128 wavelengths) pairs -- super-tiles of the two passes that
     // touch the OTF, index k_beta * (LP / 128) + chunk -- in which some |sotf| exceeds 2^-24 of its plane's largest magnitude.
     // The forward's complex pass and the fused adjoint tail visit only these; otf_kbstart[kb] = first list position of kb.
     // ycol_mix: the forward's intermediate in its own buffer, whose other tiles stay zero from plan creation on.
-    int *otf_vlist = nullptr, *otf_kbstart = nullptr;
+    DevBuf<int> otf_vlist, otf_kbstart;
     int otf_nvalid = 0;
     // per chunk of 128 wavelengths: k-steps of the forward's complex pass (k_alpha inside the support), k-steps of its pass along
     // beta (k_beta inside: the rest of ycol_mix is zero), rows k_beta the adjoint's first pass has to store: [3][LP / 128]
-    int *otf_tabs = nullptr;
-    float *ycol_mix = nullptr;
+    DevBuf<int> otf_tabs;
+    DevBuf<float> ycol_mix;
     int h2kA[3] = {0, 0, 0};
-    float *io_x = nullptr, *io_y = nullptr, *io_cube = nullptr, *hth = nullptr, *mhat2 = nullptr;
+    DevBuf<float> io_x, io_y, io_cube, hth, mhat2;
     // accumulator of the exact adjoint: cleared ONCE at plan creation.  Every scatter row knows which of its wavelengths an
     // earlier channel has already written in the same pass (read-modify-write) and stores the others, so nothing stale
     // survives a pass and no per-call clear is needed (nullptr: the tables could not express that -- clear `cube` every call)
-    float *gcube = nullptr;
+    DevBuf<float> gcube;
     std::vector<Channel> ch;
     long isize = 0, osize = 0;
     // data weights (surfh_set_data_weights): w [osize] in the layout of y, and room for W y, the data of the solvers' right-hand side;
     // both null = every sample counts 1
-    float *dw = nullptr, *dwy = nullptr;
+    DevBuf<float> dw, dwy;
     // imager data term (surfh_set_imager, surfh_set_imager_data): G [F][T][2][KAP][KBP] and the work buffers of an application --
     // padded maps / images and their half spectra -- then the data y_im, w_im (null: 1) and W y_im [im_osize]; im_g null = no imager
     int im_F = 0, im_d = 0;
     long im_osize = 0;
-    float *im_g = nullptr, *im_xpad = nullptr, *im_xhat = nullptr, *im_zpad = nullptr, *im_zhat = nullptr, *im_io = nullptr;
-    float *im_y = nullptr, *im_w = nullptr, *im_wy = nullptr;
+    DevBuf<float> im_g, im_xpad, im_xhat, im_zpad, im_zhat, im_io;
+    DevBuf<float> im_y, im_w, im_wy;
     double im_mu = 0.0;
     int ycm_planes = 0;                            // planes ycol_maps holds (max(T, 1); max(T, F) once an imager has been attached)
     std::vector<double> tpl_host;                  // the templates [T][Lc] as given (the imager's streamed set-up reads them)
     // template refinement (tplgrad.h; surfh_set_templates, surfh_adjoint_templates, surfh_cg_templates), allocated by tpl_ensure:
     // cube plane -> compact plane index [Lc] and back [LP] (-1: none), the slabs' partial sums, the plan's own templates [T][LP]
     // while a call has others in their place (TplScope), and the solver's vectors [T][Lc] in cube-plane order: x, r, d, q, b, staging
-    int *tg_cidx = nullptr, *tg_pidx = nullptr;
-    double *tg_part = nullptr;
-    float *tg_keep = nullptr, *tg_v[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    DevBuf<int> tg_cidx, tg_pidx;
+    DevBuf<double> tg_part;
+    DevBuf<float> tg_keep, tg_v[6];
     // inside one template solve: mhat holds the spectra of the solve's maps (cleared whenever something else may have used mhat);
     // only the tpl_* callers consult it, to choose the head of their operator calls
     bool tg_mhat_ready = false;
     // CG
-    float *cg_x = nullptr, *cg_r = nullptr, *cg_d = nullptr, *cg_q = nullptr, *cg_b = nullptr, *cg_y = nullptr, *cg_qm = nullptr, *cg_dd = nullptr;
-    float *cg_hg = nullptr;                        // surfh_mmmg_huber(_vox): -gradient of the non-quadratic criterion
-    float *rb_y = nullptr, *rb_u = nullptr, *rb_ag = nullptr, *rb_am = nullptr;   // surfh_mmmg_robust(_vox): y, A x, A (-g), A m [osize]
-    double *dscal = nullptr, *dscratch = nullptr;   // [16] device scalars, partial sums (>= 1024, and what huber_vox.hip and robust_data.hip ask for)
+    DevBuf<float> cg_x, cg_r, cg_d, cg_q, cg_b, cg_y, cg_qm, cg_dd;
+    DevBuf<float> cg_hg;                           // surfh_mmmg_huber(_vox): -gradient of the non-quadratic criterion
+    DevBuf<float> rb_y, rb_u, rb_ag, rb_am;       // surfh_mmmg_robust(_vox): y, A x, A (-g), A m [osize]
+    DevBuf<double> dscal, dscratch;                 // [16] device scalars, partial sums (>= 1024, and what huber_vox.hip and robust_data.hip ask for)
     // posterior sampling (surfh_cg_sample): y, the noise vectors eps_y [osize], eps_r / eps_c [isize], eta and the unperturbed
     // solution [isize]; the moment sums (posterior.hip)
-    float *po_y = nullptr, *po_eps = nullptr, *po_er = nullptr, *po_ec = nullptr, *po_eta = nullptr, *po_xhat = nullptr;
-    double *po_S = nullptr;
+    DevBuf<float> po_y, po_eps, po_er, po_ec, po_eta, po_xhat;
+    DevBuf<double> po_S;
     // non-negative fusion (surfh_cg_nonneg, surfh_cg_templates_nonneg), allocated for one solve (NnScope): the split variable, the
     // scaled dual and a work vector
-    float *nn_z = nullptr, *nn_u = nullptr, *nn_w = nullptr;
-    double *cg_hist = nullptr;                     // device-resident r.r trace of the no-host-sync CG blocks (CG_HIST_CAP entries)
+    DevBuf<float> nn_z;
+    float *nn_u = nullptr, *nn_w = nullptr;        // views: the second and third thirds of nn_z
+    DevBuf<double> cg_hist;                        // device-resident r.r trace of the no-host-sync CG blocks (CG_HIST_CAP entries)
     int cg_hist_n = 0;
     // plane-wise CG with device-resident data (surfh_cg_planes_begin_dev / _step_dev): per-plane scalars [3][Lc] (the host-buffer
     // plane-wise solvers use them too), the caller's iterate
-    double *pl_sc = nullptr;
-    double *pl_hsc = nullptr;                      // surfh_mmmg_huber_planes: [HUBER_PLANES_SCALARS][Lc] per-plane scalars
-    float *pl_x = nullptr;
+    DevBuf<double> pl_sc;
+    DevBuf<double> pl_hsc;                         // surfh_mmmg_huber_planes: [HUBER_PLANES_SCALARS][Lc] per-plane scalars
+    float *pl_x = nullptr;                         // view: the caller's device vector, never freed here
     double pl_mu = 1.0, pl_mu_reg = 0.0;
     int pl_it = 0;
     // ... with its vectors in the cube's wavelength-innermost layout [NBP][NAP][LP] (no layout transpose inside an iteration):
     // x, r, d, q, b; per-wavelength scalars [3][LP] + partial sums; pn_active: the solve surfh_cg_planes_begin_dev began runs on them
-    float *pn_v[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    double *pn_sc = nullptr, *pn_part = nullptr;
+    DevBuf<float> pn_v[5];
+    DevBuf<double> pn_sc, pn_part;
     bool pn_active = false;
     // profiling
     bool prof = false;
     std::string prof_filter;                     // non-empty: only stages whose name starts with it are bracketed by events
-    std::vector<ProfRec> pending;
-    std::vector<hipEvent_t> pool;
     std::map<std::string, std::pair<long, double>> acc;
     std::vector<std::string> acc_names;
 };
@@ -298,19 +320,6 @@ struct Prof {
         p->pending.push_back(r);
     }
 };
-
-template <typename Tp>
-int dev_alloc(Tp **p, size_t n) {
-    HIP_OK(hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(Tp)));
-    return 0;
-}
-
-template <typename Tp>
-int dev_upload(Tp **p, const std::vector<Tp> &h) {
-    if (dev_alloc(p, h.size())) return 1;
-    if (!h.empty()) HIP_OK(hipMemcpy(*p, h.data(), h.size() * sizeof(Tp), hipMemcpyHostToDevice));
-    return 0;
-}
 
 // ---- the two ends of one operator call ------------------------------------------------------------------------------------------
 // forward_dev reads `head`, adjoint_dev reads `tail`, normal_halves hands both on; the defaults are the plain call on the caller's

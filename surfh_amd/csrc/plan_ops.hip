@@ -230,7 +230,7 @@ int rfft2_lam_ct(surfh_plan *p, const float *src, float *dst, bool acols = false
     float *const yc = sub ? p->ycol_adj : p->ycol;
     const int a0 = sub ? p->a_lo : 0, na = sub ? p->a_hi - p->a_lo : p->Na;
     DftCtArgs g;   // r2c along beta: neighbouring wavelengths as packed pairs a + i b, separated in the epilogue
-    g.R = p->ctB.R; g.M = p->ctB.M; g.loader = DFT_CT_PLAIN; g.epi = DFT_CT_HSEP; g.sgn = -1.f;
+    g.R = p->ctB->R; g.M = p->ctB->M; g.loader = DFT_CT_PLAIN; g.epi = DFT_CT_HSEP; g.sgn = -1.f;
     g.scale = (float)(0.5 / std::sqrt((double)p->Nb));
     g.src = src + (long)a0 * LP; g.ldb = p->NAP * LP;
     g.dst = yc + 2 * (long)a0 * LP; g.ldc = 2 * p->NAP * LP;
@@ -240,7 +240,7 @@ int rfft2_lam_ct(surfh_plan *p, const float *src, float *dst, bool acols = false
     if (supp) { g.rtab = p->otf_tabs + 2 * (LP / 128); g.tabLP = (int)(LP / 2); g.tabShift = 6; }
     if (which & 1) {
         Prof pr(p, "dft_ct_rows_fwd");
-        LAUNCH_OK(launch_dft_ct(p->stream, g, p->ctB));
+        LAUNCH_OK(launch_dft_ct(p->stream, g, *p->ctB));
     }
     if (!(which & 2)) return 0;
     DftCtArgs h;   // c2c along alpha, batched over k_beta
@@ -307,7 +307,7 @@ int irfft2_lam_ct(surfh_plan *p, const float *src, float *dst, const float *mix,
     const bool sub = acols && p->a_hi > p->a_lo;
     const int a0 = sub ? p->a_lo : 0, na = sub ? p->a_hi - p->a_lo : p->Na;
     DftCtArgs h;   // c2r along beta, batched over alpha: two neighbouring half spectra as one Hermitian-extended complex sequence
-    h.R = p->ctB.R; h.M = p->ctB.M; h.loader = DFT_CT_HPACK; h.epi = DFT_CT_STORE; h.sgn = 1.f;
+    h.R = p->ctB->R; h.M = p->ctB->M; h.loader = DFT_CT_HPACK; h.epi = DFT_CT_STORE; h.sgn = 1.f;
     h.scale = (float)(1.0 / std::sqrt((double)p->Nb));
     h.src = yc + (long)a0 * 2 * p->KBP * LP; h.ldb = 2 * LP; h.sB = 2 * p->KBP * LP;
     h.dst = dst + (long)a0 * LP; h.ldc = p->NAP * LP; h.sC = LP;
@@ -315,7 +315,7 @@ int irfft2_lam_ct(surfh_plan *p, const float *src, float *dst, const float *mix,
     if (supp) { h.ktab = p->otf_tabs + LP / 128; h.tabLP = (int)(LP / 2); h.tabShift = 6; }      // k_beta beyond the support: zero in ycol_mix
     {
         Prof pr(p, "dft_ct_rows_inv");
-        LAUNCH_OK(launch_dft_ct(p->stream, h, p->ctB));
+        LAUNCH_OK(launch_dft_ct(p->stream, h, *p->ctB));
     }
     return 0;
 }
@@ -666,34 +666,21 @@ int normal_dev(surfh_plan *p, const float *d, float *q, double mu, bool cube) {
     return 0;
 }
 
-// explicit per-frequency Hessian of Model_WCT and its work buffer: published only once both allocations and the launch
-// that fills `hth` have succeeded (a half-built pair would make the next call skip the launch)
+// explicit per-frequency Hessian of Model_WCT and its work buffer: the launch that fills `hth` is the set's set-up step (a pair
+// published without it would make the next call skip the launch)
 static int ensure_hessian(surfh_plan *p) {
-    if (p->hth && p->mhat2) return 0;
-    float *h = nullptr, *m2 = nullptr;
-    if (dev_alloc(&h, (size_t)p->T * p->T * p->PL) || dev_alloc(&m2, (size_t)p->T * 2 * p->PL)) {
-        hipFree(h);
-        hipFree(m2);
-        return 1;
-    }
-    const int rc = launch_wct_hessian(p->stream, p->sotf, p->tpl, h, p->T, p->PL, p->LP, p->ilv);
-    if (rc != 0) {
-        hipFree(h);
-        hipFree(m2);
-        return fail("launch_wct_hessian failed: %s", hipGetErrorString((hipError_t)rc));
-    }
-    p->hth = h;
-    p->mhat2 = m2;
-    return 0;
+    return ensure_set_with(
+        [&](float *h, float *) {
+            const int rc = launch_wct_hessian(p->stream, p->sotf, p->tpl, h, p->T, p->PL, p->LP, p->ilv);
+            return rc ? fail("launch_wct_hessian failed: %s", hipGetErrorString((hipError_t)rc)) : 0;
+        },
+        member(p->hth, (size_t)p->T * p->T * p->PL), member(p->mhat2, (size_t)p->T * 2 * p->PL));
 }
 
 int ensure_cg(surfh_plan *p) {
-    if (p->cg_x) return 0;
     // room for the vectors in either basis: the maps [T][Na][Nb] or their scaled half spectra [T][2][KAP][KBP]
     const size_t n = std::max((size_t)p->isize, (size_t)2 * std::max(p->T, 0) * (size_t)p->PL);
-    for (float **v : {&p->cg_x, &p->cg_r, &p->cg_d, &p->cg_q, &p->cg_b})
-        if (dev_alloc(v, n)) return 1;
-    return 0;
+    return ensure_set(member(p->cg_x, n), member(p->cg_r, n), member(p->cg_d, n), member(p->cg_q, n), member(p->cg_b, n));
 }
 
 // ---- template refinement: the operator as a function of the templates, maps held fixed (kernels: tplgrad.hip) ----
@@ -706,24 +693,11 @@ int tpl_ensure(surfh_plan *p) {
     std::vector<int> cidx((size_t)p->Lc, -1), pidx((size_t)p->LP, -1);
     for (int c = 0; c < p->Lown; ++c)
         if (p->planes[c] >= 0) { pidx[c] = p->planes[c]; cidx[p->planes[c]] = c; }
-    int *dc = nullptr, *dp = nullptr;
-    float *keep = nullptr, *v[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    double *part = nullptr;
-    auto done = [&](int rc) {
-        hipFree(dc); hipFree(dp); hipFree(keep); hipFree(part);
-        for (float *w : v) hipFree(w);
-        return rc;
-    };
     const bool spectral = p->ilv && !p->dense_dft && p->T <= 4;
-    if (dev_upload(&dc, cidx) || dev_upload(&dp, pidx) || dev_alloc(&keep, (size_t)p->T * p->LP) ||
-        dev_alloc(&part, tplgrad_part_doubles(p->T, p->Na, p->Nb, (int)p->LP, spectral)))
-        return done(1);
-    for (float *&w : v)
-        if (dev_alloc(&w, (size_t)p->T * p->Lc)) return done(1);
-    std::swap(p->tg_cidx, dc); std::swap(p->tg_pidx, dp); std::swap(p->tg_keep, keep);
-    for (int i = 0; i < 6; ++i) std::swap(p->tg_v[i], v[i]);
-    std::swap(p->tg_part, part);       // last: the mark of a complete set
-    return done(0);
+    const size_t nv = (size_t)p->T * p->Lc;
+    return ensure_set(member(p->tg_cidx, cidx), member(p->tg_pidx, pidx), member(p->tg_keep, (size_t)p->T * p->LP),
+                      member(p->tg_part, tplgrad_part_doubles(p->T, p->Na, p->Nb, (int)p->LP, spectral)), member(p->tg_v[0], nv),
+                      member(p->tg_v[1], nv), member(p->tg_v[2], nv), member(p->tg_v[3], nv), member(p->tg_v[4], nv), member(p->tg_v[5], nv));
 }
 int tpl_maps_spectra(surfh_plan *p, const float *maps) {
     {
@@ -821,9 +795,7 @@ static int wct_check(surfh_plan *p) {
     if (p->T < 1) return fail("Model_WCT needs templates");
     if (p->segs.size() != 1 || p->segs[0].start != 0 || p->segs[0].len != p->Lc) return fail("Model_WCT needs a plan that owns every cube plane");
     if (hipSetDevice(p->dev) != hipSuccess) return fail("hipSetDevice failed");
-    const size_t n = (size_t)p->Lc * p->Na * p->Nb;
-    if (!p->io_cube && dev_alloc(&p->io_cube, n)) return 1;
-    return 0;
+    return ensure_set(member(p->io_cube, (size_t)p->Lc * p->Na * p->Nb));
 }
 
 int surfh_wct_forward(surfh_plan *p, const float *maps, float *cube) {
@@ -889,13 +861,12 @@ int surfh_wct_expsol(surfh_plan *p, const float *cube, const double *mu_reg, con
             if (!(v >= 0.0)) return fail("reg_freq must be >= 0");
             reg[(size_t)a * p->KBP + b] = (float)v;
         }
-    float *dreg = nullptr;
-    double *dmu = nullptr;
-    int *dflag = nullptr;
-    auto done = [&](int r) { hipFree(dreg); hipFree(dmu); hipFree(dflag); return r; };
-    if (dev_upload(&dreg, reg) || dev_alloc(&dmu, (size_t)p->T) || dev_alloc(&dflag, 1)) return done(1);
+    DevBuf<float> dreg;
+    DevBuf<double> dmu;
+    DevBuf<int> dflag;
+    if (dreg.upload(reg) || dmu.alloc((size_t)p->T) || dflag.alloc(1)) return 1;
     if (hipMemcpy(dmu, mu_reg, p->T * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(dflag, 0, sizeof(int)) != hipSuccess) return done(fail("copy failed"));
+        hipMemset(dflag, 0, sizeof(int)) != hipSuccess) return fail("copy failed");
     // b = H^T y in the Fourier domain (surfh_wct_adjoint up to the inverse transform).  The mean of every plane is taken out in
     // float64 before the fp32 transforms and put back into the zero-frequency bin of b afterwards: left in, its rounding leaks
     // into the other bins of the k_beta = 0 column, small against the mean but not against the bins themselves, and the solve
@@ -912,12 +883,12 @@ int surfh_wct_expsol(surfh_plan *p, const float *cube, const double *mu_reg, con
     }
     std::vector<float> h0((size_t)2 * p->LP);       // the OTF at the zero frequency as the kernels read it: (re, im) of every plane
     if (p->ilv) {
-        if (hipMemcpy(h0.data(), p->sotf, h0.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return done(fail("copy failed"));
+        if (hipMemcpy(h0.data(), p->sotf, h0.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return fail("copy failed");
     } else {
         std::vector<float> re((size_t)p->LP), im((size_t)p->LP);
         if (hipMemcpy(re.data(), p->sotf, re.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(im.data(), p->sotf + (size_t)p->PL * p->LP, im.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
-            return done(fail("copy failed"));
+            return fail("copy failed");
         for (long l = 0; l < p->LP; ++l) { h0[2 * l] = re[l]; h0[2 * l + 1] = im[l]; }
     }
     std::vector<double> dc((size_t)2 * p->T, 0.0);  // sum_l tpl[t][l] conj(H_l(0)) mean_l sqrt(Na Nb): the transforms are unitary
@@ -929,32 +900,32 @@ int surfh_wct_expsol(surfh_plan *p, const float *cube, const double *mu_reg, con
             dc[2 * t + 1] -= w * (double)h0[2 * l + 1];
         }
     if (hipMemcpyAsync(p->io_cube, y0.data(), y0.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess)
-        return done(fail("copy failed"));
+        return fail("copy failed");
     int rc = launch_fill_zero(s, p->cube, (long)p->NBP * p->NAP * p->LP);
     if (!rc) rc = launch_cube_to_lam_inner(s, p->io_cube, p->cube, 0, p->Lc, p->Na, p->Nb, p->NAP, p->LP);
-    if (rc) return done(fail("launch failed: %s", hipGetErrorString((hipError_t)rc)));
-    if (adjoint_tail(p, p->cube)) return done(1);
+    if (rc) return fail("launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (adjoint_tail(p, p->cube)) return 1;
     for (int t = 0; t < p->T; ++t)
         for (int c = 0; c < 2; ++c) {               // bin (0, 0) of mhat [T][2][KAP][KBP]
             float *bin = p->mhat + ((size_t)t * 2 + c) * p->PL;
             float v = 0.f;
             if (hipMemcpyAsync(&v, bin, sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-                return done(fail("copy failed"));
+                return fail("copy failed");
             v = (float)((double)v + dc[2 * t + c]);
             if (hipMemcpyAsync(bin, &v, sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-                return done(fail("copy failed"));
+                return fail("copy failed");
         }
     rc = launch_wct_solve(s, p->hth, dreg, dmu, p->mhat, p->mhat2, p->T, p->PL, dflag);
-    if (rc) return done(fail("launch failed: %s", hipGetErrorString((hipError_t)rc)));
-    if (irfft2_planes(p, p->mhat2, p->maps_pad, p->T)) return done(1);
+    if (rc) return fail("launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (irfft2_planes(p, p->mhat2, p->maps_pad, p->T)) return 1;
     rc = launch_unpad_planes(s, p->maps_pad, p->io_x, p->T, p->Na, p->Nb, p->NAP, p->NBP);
     int flag = 0;
     if (!rc) rc = (int)hipMemcpyAsync(maps, p->io_x, p->isize * sizeof(float), hipMemcpyDeviceToHost, s);
     if (!rc) rc = (int)hipMemcpyAsync(&flag, dflag, sizeof(int), hipMemcpyDeviceToHost, s);
     if (!rc) rc = (int)hipStreamSynchronize(s);
-    if (rc) return done(fail("expsol failed: %s", hipGetErrorString((hipError_t)rc)));
-    if (flag) return done(fail("the regularised normal matrix is singular at some frequency (numpy.linalg.inv would raise LinAlgError)"));
-    return done(0);
+    if (rc) return fail("expsol failed: %s", hipGetErrorString((hipError_t)rc));
+    if (flag) return fail("the regularised normal matrix is singular at some frequency (numpy.linalg.inv would raise LinAlgError)");
+    return 0;
 }
 
 // ---- CG building blocks ---------------------------------------------------------------------
@@ -1051,23 +1022,22 @@ static int lmm_host(surfh_plan *p, const double *templates, int32_t T, int32_t L
     const long npix = (long)p->Na * p->Nb;
     std::vector<float> t((size_t)T * L);
     for (size_t i = 0; i < t.size(); ++i) t[i] = (float)templates[i];
-    float *dt = nullptr, *dm = nullptr, *dc = nullptr;
+    DevBuf<float> dt, dm, dc;
     int rc = 0;
-    auto done = [&](int r) { hipFree(dt); hipFree(dm); hipFree(dc); return r; };
-    if (dev_upload(&dt, t) || dev_alloc(&dm, (size_t)T * npix) || dev_alloc(&dc, (size_t)L * npix)) return done(1);
+    if (dt.upload(t) || dm.alloc((size_t)T * npix) || dc.alloc((size_t)L * npix)) return 1;
     hipStream_t s = p->stream;
     if (to_cube) {
-        if (hipMemcpyAsync(dm, in, (size_t)T * npix * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess) return done(fail("copy failed"));
+        if (hipMemcpyAsync(dm, in, (size_t)T * npix * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess) return fail("copy failed");
         rc = launch_lmm_maps2cube(s, dm, dt, dc, T, L, npix);
         if (!rc) rc = (int)hipMemcpyAsync(out, dc, (size_t)L * npix * sizeof(float), hipMemcpyDeviceToHost, s);
     } else {
-        if (hipMemcpyAsync(dc, in, (size_t)L * npix * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess) return done(fail("copy failed"));
+        if (hipMemcpyAsync(dc, in, (size_t)L * npix * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess) return fail("copy failed");
         rc = launch_lmm_cube2maps(s, dc, dt, dm, T, L, npix);
         if (!rc) rc = (int)hipMemcpyAsync(out, dm, (size_t)T * npix * sizeof(float), hipMemcpyDeviceToHost, s);
     }
     if (!rc) rc = (int)hipStreamSynchronize(s);
-    if (rc) return done(fail("lmm: %s", hipGetErrorString((hipError_t)rc)));
-    return done(0);
+    if (rc) return fail("lmm: %s", hipGetErrorString((hipError_t)rc));
+    return 0;
 }
 int surfh_maps_to_cube(surfh_plan *p, const double *templates, int32_t T, int32_t L, const float *maps, float *cube) {
     return lmm_host(p, templates, T, L, maps, cube, true);
@@ -1102,9 +1072,8 @@ int surfh_set_templates(surfh_plan *p, const double *tpl) {
     HIP_OK(hipMemcpy(p->tpl, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
     p->tpl_host.assign(tpl, tpl + n);
     // Model_WCT's explicit Hessian was built from the old templates: ensure_hessian builds it again on the next call
-    hipFree(p->hth);
-    hipFree(p->mhat2);
-    p->hth = p->mhat2 = nullptr;
+    p->hth.reset();
+    p->mhat2.reset();
     return 0;
 }
 static int tpl_call_check(surfh_plan *p, const void *a, const void *b, const void *c) {
@@ -1202,9 +1171,6 @@ int imager_normal_dev(surfh_plan *p, const float *v, float *q, const float *w, f
     }
     return imager_from_images(p, q, scale, accumulate);
 }
-void imager_free(std::initializer_list<void *> l) {
-    for (void *v : l) hipFree(v);
-}
 }  // namespace
 
 int imager_normal_add(surfh_plan *p, const float *v, float *q) { return imager_normal_dev(p, v, q, p->im_w, (float)p->im_mu, true); }
@@ -1227,8 +1193,7 @@ int surfh_set_imager(surfh_plan *p, const surfh_imager_desc *desc) {
     hipStream_t s = p->stream;
     if (!desc) {
         HIP_OK(hipStreamSynchronize(s));
-        imager_free({p->im_g, p->im_xpad, p->im_xhat, p->im_zpad, p->im_zhat, p->im_io, p->im_y, p->im_w, p->im_wy});
-        p->im_g = p->im_xpad = p->im_xhat = p->im_zpad = p->im_zhat = p->im_io = p->im_y = p->im_w = p->im_wy = nullptr;
+        for (DevBuf<float> *v : {&p->im_g, &p->im_xpad, &p->im_xhat, &p->im_zpad, &p->im_zhat, &p->im_io, &p->im_y, &p->im_w, &p->im_wy}) v->reset();
         p->im_F = p->im_d = 0; p->im_osize = 0; p->im_mu = 0.0;
         return 0;
     }
@@ -1251,39 +1216,33 @@ int surfh_set_imager(surfh_plan *p, const surfh_imager_desc *desc) {
         if (chunk < 32 || chunk > 128 || chunk % 32) return fail("imager: SURFH_IMAGER_CHUNK = %s is not a multiple of 32 in 32..128", e);
     }
     const size_t ng = (size_t)F * T * 2 * p->PL, osz = (size_t)F * (p->Na / d) * (p->Nb / d);
-    float *g = nullptr, *xpad = nullptr, *xhat = nullptr, *zpad = nullptr, *zhat = nullptr, *io = nullptr, *ycm = nullptr;
-    float *otf_in = nullptr, *otf_pl = nullptr, *tplc = nullptr;
-    double *acc = nullptr, *wf = nullptr;
-    auto done = [&](int rc) {
-        imager_free({g, xpad, xhat, zpad, zhat, io, ycm, otf_in, otf_pl, tplc, acc, wf});
-        return rc;
-    };
+    // the new set (g .. io, a larger ycol_maps) and the call's temporaries, all locals: published by the swaps at the end
+    DevBuf<float> g, xpad, xhat, zpad, zhat, io, ycm, otf_in, otf_pl, tplc;
+    DevBuf<double> acc, wf;
     const size_t nycm = (size_t)F * 2 * p->NAP * p->KBP;
-    if (dev_alloc(&g, ng) || dev_alloc(&acc, ng) || dev_alloc(&xpad, (size_t)T * p->PLc) || dev_alloc(&xhat, (size_t)T * 2 * p->PL) ||
-        dev_alloc(&zpad, (size_t)F * p->PLc) || dev_alloc(&zhat, (size_t)F * 2 * p->PL) || dev_alloc(&io, osz) ||
-        (F > p->ycm_planes && dev_alloc(&ycm, nycm)))
-        return done(1);
+    if (g.alloc(ng) || acc.alloc(ng) || xpad.alloc((size_t)T * p->PLc) || xhat.alloc((size_t)T * 2 * p->PL) || zpad.alloc((size_t)F * p->PLc) ||
+        zhat.alloc((size_t)F * 2 * p->PL) || io.alloc(osz) || (F > p->ycm_planes && ycm.alloc(nycm)))
+        return 1;
     if (hipMemsetAsync(acc, 0, ng * sizeof(double), s) != hipSuccess || hipMemsetAsync(xpad, 0, (size_t)T * p->PLc * sizeof(float), s) != hipSuccess ||
         hipMemsetAsync(zpad, 0, (size_t)F * p->PLc * sizeof(float), s) != hipSuccess ||
         (ycm && hipMemsetAsync(ycm, 0, nycm * sizeof(float), s) != hipSuccess))
-        return done(fail("memset failed"));
+        return fail("memset failed");
     if (!desc->sotf) {       // the plan's device OTF and templates: compact plane index = cube plane
         const long LP = p->LP;
         std::vector<double> h((size_t)F * LP, 0.0);
         for (int f = 0; f < F; ++f) std::copy(desc->filters + (size_t)f * Lc, desc->filters + (size_t)(f + 1) * Lc, h.begin() + (size_t)f * LP);
-        if (dev_upload(&wf, h)) return done(1);
+        if (wf.upload(h)) return 1;
         const int rc = p->ilv ? launch_imager_build_g(s, p->sotf, 2 * LP, 2, 1, p->tpl, LP, wf, LP, (int)LP, acc, F, T, p->Na, nkb, p->KBP, p->PL)
                               : launch_imager_build_g(s, p->sotf, LP, 1, p->PL * LP, p->tpl, LP, wf, LP, (int)LP, acc, F, T, p->Na, nkb, p->KBP, p->PL);
-        if (rc) return done(fail("launch_imager_build_g failed: %s", hipGetErrorString((hipError_t)rc)));
+        if (rc) return fail("launch_imager_build_g failed: %s", hipGetErrorString((hipError_t)rc));
     } else {                 // the imager's own OTF, streamed: chunk -> the plan's padded layout (wavelength innermost) -> the same kernel
         const int CHP = (chunk + 63) / 64 * 64;
         const size_t nbin = (size_t)p->Na * nkb;
-        if (dev_alloc(&otf_in, (size_t)chunk * nbin * 2) || dev_alloc(&otf_pl, (size_t)2 * p->PL * CHP) || dev_alloc(&tplc, (size_t)T * CHP) ||
-            dev_alloc(&wf, (size_t)F * CHP))
-            return done(1);
+        if (otf_in.alloc((size_t)chunk * nbin * 2) || otf_pl.alloc((size_t)2 * p->PL * CHP) || tplc.alloc((size_t)T * CHP) || wf.alloc((size_t)F * CHP))
+            return 1;
         std::vector<float> ho((size_t)chunk * nbin * 2), ht((size_t)T * CHP);
         std::vector<double> hw((size_t)F * CHP);
-        if (hipMemsetAsync(otf_pl, 0, (size_t)2 * p->PL * CHP * sizeof(float), s) != hipSuccess) return done(fail("memset failed"));
+        if (hipMemsetAsync(otf_pl, 0, (size_t)2 * p->PL * CHP * sizeof(float), s) != hipSuccess) return fail("memset failed");
         for (int l0 = 0; l0 < Lc; l0 += chunk) {
             const int n = std::min(chunk, Lc - l0);
             const double *src = desc->sotf + (size_t)l0 * nbin * 2;
@@ -1297,24 +1256,22 @@ int surfh_set_imager(surfh_plan *p, const surfh_imager_desc *desc) {
             if (hipMemcpyAsync(otf_in, ho.data(), (size_t)n * nbin * 2 * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
                 hipMemcpyAsync(tplc, ht.data(), ht.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
                 hipMemcpyAsync(wf, hw.data(), hw.size() * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess)
-                return done(fail("imager: OTF upload failed"));
+                return fail("imager: OTF upload failed");
             int rc = launch_imager_otf_chunk(s, otf_in, otf_pl, n, CHP, p->Na, nkb, p->KBP, p->PL);
             if (!rc) rc = launch_imager_build_g(s, otf_pl, CHP, 1, p->PL * CHP, tplc, CHP, wf, CHP, CHP, acc, F, T, p->Na, nkb, p->KBP, p->PL);
-            if (rc) return done(fail("launch_imager_build_g failed: %s", hipGetErrorString((hipError_t)rc)));
-            if (hipStreamSynchronize(s) != hipSuccess) return done(fail("imager: set-up failed on the device"));   // the host buffers are reused
+            if (rc) return fail("launch_imager_build_g failed: %s", hipGetErrorString((hipError_t)rc));
+            if (hipStreamSynchronize(s) != hipSuccess) return fail("imager: set-up failed on the device");   // the host buffers are reused
         }
     }
-    if (const int rc = launch_imager_g_store(s, acc, g, (long)ng)) return done(fail("launch_imager_g_store failed: %s", hipGetErrorString((hipError_t)rc)));
-    if (hipStreamSynchronize(s) != hipSuccess) return done(fail("imager: set-up failed on the device"));
+    if (const int rc = launch_imager_g_store(s, acc, g, (long)ng)) return fail("launch_imager_g_store failed: %s", hipGetErrorString((hipError_t)rc));
+    if (hipStreamSynchronize(s) != hipSuccess) return fail("imager: set-up failed on the device");
     // publish: nothing in flight reads the old buffers; the data of a previous imager go with it (their size is that imager's)
-    std::swap(p->im_g, g); std::swap(p->im_xpad, xpad); std::swap(p->im_xhat, xhat); std::swap(p->im_zpad, zpad);
-    std::swap(p->im_zhat, zhat); std::swap(p->im_io, io);
-    if (ycm) { std::swap(p->ycol_maps, ycm); p->ycm_planes = F; }
-    imager_free({p->im_y, p->im_w, p->im_wy});
-    p->im_y = p->im_w = p->im_wy = nullptr;
+    p->im_g.swap(g); p->im_xpad.swap(xpad); p->im_xhat.swap(xhat); p->im_zpad.swap(zpad); p->im_zhat.swap(zhat); p->im_io.swap(io);
+    if (ycm) { p->ycol_maps.swap(ycm); p->ycm_planes = F; }
+    for (DevBuf<float> *v : {&p->im_y, &p->im_w, &p->im_wy}) v->reset();
     p->im_mu = 0.0;
     p->im_F = F; p->im_d = d; p->im_osize = (long)osz;
-    return done(0);
+    return 0;
 }
 
 int surfh_imager_osize(const surfh_plan *p) { return p && p->im_g ? (int)p->im_osize : 0; }
@@ -1364,11 +1321,7 @@ int surfh_set_imager_data(surfh_plan *p, const float *y_im, const float *w_im, d
     if (!p) return fail("null plan");
     if (!p->im_g) return fail("no imager is attached to this plan (surfh_set_imager)");
     HIP_OK(hipSetDevice(p->dev));
-    float *y = nullptr, *w = nullptr, *wy = nullptr;
-    auto done = [&](int rc) {
-        imager_free({y, w, wy});
-        return rc;
-    };
+    DevBuf<float> y, w, wy;
     double mu = 0.0;
     if (y_im) {
         if (!(mu_imager >= 0.0 && mu_imager <= DBL_MAX)) return fail("imager: mu_imager = %g must be finite and >= 0", mu_imager);
@@ -1376,16 +1329,16 @@ int surfh_set_imager_data(surfh_plan *p, const float *y_im, const float *w_im, d
         if (w_im)
             for (size_t i = 0; i < n; ++i)
                 if (!(w_im[i] >= 0.f && w_im[i] <= FLT_MAX)) return fail("imager: weight %ld is %g: weights are finite and >= 0", (long)i, (double)w_im[i]);
-        if (dev_alloc(&y, n) || (w_im && (dev_alloc(&w, n) || dev_alloc(&wy, n)))) return done(1);
+        if (y.alloc(n) || (w_im && (w.alloc(n) || wy.alloc(n)))) return 1;
         if (hipMemcpyAsync(y, y_im, n * sizeof(float), hipMemcpyHostToDevice, p->stream) != hipSuccess ||
             (w_im && hipMemcpyAsync(w, w_im, n * sizeof(float), hipMemcpyHostToDevice, p->stream) != hipSuccess))
-            return done(fail("copy failed"));
+            return fail("copy failed");
         mu = mu_imager;
     }
-    if (hipStreamSynchronize(p->stream) != hipSuccess) return done(fail("stream synchronisation failed"));
-    std::swap(p->im_y, y); std::swap(p->im_w, w); std::swap(p->im_wy, wy);
+    if (hipStreamSynchronize(p->stream) != hipSuccess) return fail("stream synchronisation failed");
+    p->im_y.swap(y); p->im_w.swap(w); p->im_wy.swap(wy);
     p->im_mu = mu;
-    return done(0);
+    return 0;
 }
 
 }  // extern "C"

@@ -57,7 +57,7 @@ int surfh_cg_iter_dev(surfh_plan *p, float *x, float *r, float *d, const float *
 // the all-reduce, both asynchronous on the plan's stream.
 static constexpr int CG_HIST_CAP = 1 << 16;
 static int cg_hist_room(surfh_plan *p) {
-    if (!p->cg_hist && dev_alloc(&p->cg_hist, (size_t)CG_HIST_CAP)) return 1;
+    if (ensure_set(member(p->cg_hist, (size_t)CG_HIST_CAP))) return 1;
     if (p->cg_hist_n >= CG_HIST_CAP) return fail("CG trace full (%d iterations): read it with surfh_cg_trace", CG_HIST_CAP);
     return 0;
 }
@@ -177,8 +177,8 @@ int start_iterate(surfh_plan *p, const float *x0) {
 int mmmg_begin(surfh_plan *p, bool want_hg, const float *y, float *yd, const float *x0, float *am = nullptr) {
     hipStream_t s = p->stream;
     if (ensure_cg(p)) return 1;
-    if (!am && !p->cg_qm && (dev_alloc(&p->cg_qm, (size_t)p->isize) || dev_alloc(&p->cg_dd, (size_t)p->isize))) return 1;
-    if (want_hg && !p->cg_hg && dev_alloc(&p->cg_hg, (size_t)p->isize)) return 1;
+    if (!am && ensure_set(member(p->cg_qm, (size_t)p->isize), member(p->cg_dd, (size_t)p->isize))) return 1;
+    if (want_hg && ensure_set(member(p->cg_hg, (size_t)p->isize))) return 1;
     HIP_OK(hipMemcpyAsync(yd, y, p->osize * sizeof(float), hipMemcpyHostToDevice, s));
     if (start_iterate(p, x0)) return 1;
     LAUNCH_OK(launch_fill_zero(s, p->cg_d, p->isize));
@@ -390,20 +390,22 @@ int cg_planes_ready(surfh_plan *p, const char *who, bool native) {
     if (p->T != 0) return fail("surfh_cg_planes is the solver of the plane-wise (no template) model; use surfh_cg with templates");
     if (p->ch.empty()) return fail("plan has no channel");
     HIP_OK(hipSetDevice(p->dev));
-    if (!native) return ensure_cg(p) || (!p->pl_sc && dev_alloc(&p->pl_sc, (size_t)3 * p->Lc));
+    if (!native) return ensure_cg(p) || ensure_set(member(p->pl_sc, (size_t)3 * p->Lc));
     // vectors in the cube's layout: the caller's x is transposed in here and out again at the end of every step call
     const size_t nc = (size_t)p->NBP * p->NAP * p->LP;
-    for (float *&v : p->pn_v)
-        if (!v) {
-            if (dev_alloc(&v, nc)) return 1;
-            HIP_OK(hipMemsetAsync(v, 0, nc * sizeof(float), p->stream));       // the padding (rows >= Nb, columns >= Na, planes >= Lc) stays zero
-        }
-    return !p->pn_sc && (dev_alloc(&p->pn_sc, (size_t)3 * p->LP) || dev_alloc(&p->pn_part, pn_part_doubles(p->LP)));
+    return ensure_set_with(
+        [&](float *v0, float *v1, float *v2, float *v3, float *v4, double *, double *) {
+            for (float *v : {v0, v1, v2, v3, v4})       // the padding (rows >= Nb, columns >= Na, planes >= Lc) stays zero
+                if (dev_raw_clear(v, nc * sizeof(float), p->stream, true)) return 1;
+            return 0;
+        },
+        member(p->pn_v[0], nc), member(p->pn_v[1], nc), member(p->pn_v[2], nc), member(p->pn_v[3], nc), member(p->pn_v[4], nc),
+        member(p->pn_sc, (size_t)3 * p->LP), member(p->pn_part, pn_part_doubles(p->LP)));
 }
 // the plane space surfh_cg_planes_begin_dev chose, from what it left in the plan (pn_active, pl_x, pl_mu, pl_mu_reg)
 CgSpace stored_space(surfh_plan *p) {
     if (!p->pn_active) return planes_space(p, p->pl_x, p->pl_mu, p->pl_mu_reg);
-    float *const *v = p->pn_v;
+    const DevBuf<float> *v = p->pn_v;
     return {v[0], v[1], v[2], v[3], v[4], p->pl_x, (long)p->NBP * p->NAP * p->LP, (long)p->Na * p->Nb, p->Lc, p->pl_mu, p->pl_mu_reg,
             p->pn_sc, p->pn_sc + p->LP, p->pn_sc + 2 * p->LP, pn_setup, pn_rr0, pn_apply, pn_step, pn_refresh, pn_dir, row_trace, pn_to_caller};
 }
@@ -516,7 +518,7 @@ int tpl_to_caller(surfh_plan *p, const CgSpace &) {       // what follows may ru
     return 0;
 }
 CgSpace tpl_space(surfh_plan *p, double mu, double mu_spec) {
-    float *const *v = p->tg_v;
+    const DevBuf<float> *v = p->tg_v;
     const long n = (long)p->T * p->Lc;
     return {v[0], v[1], v[2], v[3], v[4], v[0], n, n, 1, mu, mu_spec, p->dscal + 0, p->dscal + 1, p->dscal + 2,
             tpl_setup, maps_rr0, tpl_apply, maps_step, maps_refresh, maps_dir, row_trace, tpl_to_caller, n};
@@ -562,7 +564,7 @@ struct NnScope {                       // the extra vectors never outlive a solv
     explicit NnScope(surfh_plan *pl) : p(pl) {}
     int begin(long n) {
         const size_t pitch = ((size_t)n + 3) / 4 * 4;      // each vector 16-byte aligned
-        if (dev_alloc(&p->nn_z, 3 * pitch)) return 1;
+        if (p->nn_z.alloc(3 * pitch)) return 1;
         p->nn_u = p->nn_z + pitch;
         p->nn_w = p->nn_u + pitch;
         return 0;
@@ -570,9 +572,9 @@ struct NnScope {                       // the extra vectors never outlive a solv
     ~NnScope() {
         if (p->nn_z) {
             hipStreamSynchronize(p->stream);
-            hipFree(p->nn_z);
+            p->nn_z.reset();
         }
-        p->nn_z = p->nn_u = p->nn_w = nullptr;
+        p->nn_u = p->nn_w = nullptr;
     }
 };
 int nn_rho_add(surfh_plan *p, const CgSpace &s, const float *v) {                           // q += rho v: the operator is Q + rho I
@@ -769,10 +771,9 @@ int po_refuse(const surfh_plan *p, double mu, double mu_reg, const char *who) {
 }
 int po_ensure(surfh_plan *p) {
     if (ensure_cg(p)) return 1;
-    if (!p->po_y && (dev_alloc(&p->po_y, (size_t)p->osize) || dev_alloc(&p->po_eps, (size_t)p->osize))) return 1;
-    for (float **v : {&p->po_er, &p->po_ec, &p->po_eta, &p->po_xhat})
-        if (!*v && dev_alloc(v, (size_t)p->isize)) return 1;
-    return !p->po_S && dev_alloc(&p->po_S, (size_t)(2 * po_moment_planes(p->T)) * p->Na * p->Nb);   // the sums, then mean and cov
+    const size_t no = (size_t)p->osize, ni = (size_t)p->isize;
+    return ensure_set(member(p->po_y, no), member(p->po_eps, no), member(p->po_er, ni), member(p->po_ec, ni), member(p->po_eta, ni),
+                      member(p->po_xhat, ni), member(p->po_S, (size_t)(2 * po_moment_planes(p->T)) * p->Na * p->Nb));   // the sums, then mean and cov
 }
 // one noise vector on the device: row `sample` of the caller's, or the generator's stream
 int po_noise(surfh_plan *p, float *dst, long n, const float *host, uint64_t seed, uint32_t stream, int sample) {
@@ -1145,8 +1146,8 @@ int mmmg_robust_loop(surfh_plan *p, const HuberPrior &hp, const float *y, double
     std::vector<float> hx;
     HIP_OK(hipSetDevice(p->dev));
     if (p->ch.empty() || p->osize <= 0) return fail("3MG (%s, robust data term) needs a plan with detector channels", hp.what);
-    for (float **v : {&p->rb_y, &p->rb_u, &p->rb_ag, &p->rb_am})
-        if (!*v && dev_alloc(v, (size_t)p->osize)) return 1;
+    const size_t nrb = (size_t)p->osize;
+    if (ensure_set(member(p->rb_y, nrb), member(p->rb_u, nrb), member(p->rb_ag, nrb), member(p->rb_am, nrb))) return 1;
     if (mmmg_begin(p, true, y, p->rb_y, x0, p->rb_am)) return 1;
     hipStream_t s = p->stream;
     const long n = p->isize, no = p->osize;
@@ -1362,7 +1363,7 @@ int surfh_mmmg_planes_cb(surfh_plan *p, const float *y, double mu, double mu_reg
     HIP_OK(hipSetDevice(p->dev));
     const int L = p->Lc;
     const long npix = (long)p->Na * p->Nb;
-    if (!p->pl_sc && dev_alloc(&p->pl_sc, (size_t)3 * L)) return 1;
+    if (ensure_set(member(p->pl_sc, (size_t)3 * L))) return 1;
     double *rr = p->pl_sc, *mqm = p->pl_sc + L;
     const auto dir = [&] {
         LAUNCH_OK(launch_mmmg_dir_planes(p->stream, p->cg_dd, p->cg_r, p->cg_d, p->cg_qm, L, npix, rr, mqm));
@@ -1392,7 +1393,7 @@ int huber_planes_ready(surfh_plan *p, const char *who) {
     if (p->T != 0) return fail("%s works on the plane-wise (no template) model; the maps of a template model take surfh_mmmg_huber", who);
     if (p->ch.empty()) return fail("plan has no channel");
     HIP_OK(hipSetDevice(p->dev));
-    if (!p->pl_hsc && dev_alloc(&p->pl_hsc, (size_t)HUBER_PLANES_SCALARS * p->Lc)) return 1;
+    if (ensure_set(member(p->pl_hsc, (size_t)HUBER_PLANES_SCALARS * p->Lc))) return 1;
     return 0;
 }
 }  // namespace

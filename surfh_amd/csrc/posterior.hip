@@ -221,24 +221,19 @@ int surfh_po_moments(int32_t T, int64_t npix, const float *xhat, const float *sa
     if (cov && K < 2) return fail("posterior moments: a covariance needs at least 2 samples (got %d)", K);
     HIP_OK(hipSetDevice(device));
     const size_t n = (size_t)T * npix, np = (size_t)po_moment_planes(T) * npix;
-    float *dx = nullptr, *dh = nullptr;
-    double *S = nullptr, *out = nullptr;
-    const auto run = [&]() -> int {
-        if (dev_alloc(&dx, n) || dev_alloc(&dh, n) || dev_alloc(&S, np) || dev_alloc(&out, np)) return 1;
-        HIP_OK(hipMemcpy(dh, xhat, n * sizeof(float), hipMemcpyHostToDevice));
-        HIP_OK(hipMemset(S, 0, np * sizeof(double)));
-        for (int k = 0; k < K; ++k) {
-            HIP_OK(hipMemcpy(dx, samples + (size_t)k * n, n * sizeof(float), hipMemcpyHostToDevice));
-            LAUNCH_OK(launch_po_moments(nullptr, dx, dh, S, T, npix));
-        }
-        LAUNCH_OK(launch_po_finish(nullptr, dh, S, T, npix, K, out, cov ? out + n : nullptr));
-        HIP_OK(hipMemcpy(mean, out, n * sizeof(double), hipMemcpyDeviceToHost));
-        if (cov) HIP_OK(hipMemcpy(cov, out + n, (np - n) * sizeof(double), hipMemcpyDeviceToHost));
-        return 0;
-    };
-    const int rc = run();
-    hipFree(dx); hipFree(dh); hipFree(S); hipFree(out);
-    return rc;
+    DevBuf<float> dx, dh;
+    DevBuf<double> S, out;
+    if (dx.alloc(n) || dh.alloc(n) || S.alloc(np) || out.alloc(np)) return 1;
+    HIP_OK(hipMemcpy(dh, xhat, n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(S, 0, np * sizeof(double)));
+    for (int k = 0; k < K; ++k) {
+        HIP_OK(hipMemcpy(dx, samples + (size_t)k * n, n * sizeof(float), hipMemcpyHostToDevice));
+        LAUNCH_OK(launch_po_moments(nullptr, dx, dh, S, T, npix));
+    }
+    LAUNCH_OK(launch_po_finish(nullptr, dh, S, T, npix, K, out, cov ? out + n : nullptr));
+    HIP_OK(hipMemcpy(mean, out, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (cov) HIP_OK(hipMemcpy(cov, out + n, (np - n) * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 }  // extern "C"

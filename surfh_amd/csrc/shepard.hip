@@ -36,6 +36,9 @@
 #include <vector>
 
 #include "../../include/surfh_amd.h"
+#include "dev_buf.h"
+
+using surfh_impl::DevBuf;
 
 namespace {
 
@@ -293,20 +296,10 @@ __global__ __launch_bounds__(TPB) void k_shepard(const Seg *__restrict__ segs, c
 }
 #pragma clang fp contract(on)
 
-struct DevBuf {            // frees whatever was allocated when the call returns
-    std::vector<void *> p;
-    ~DevBuf() {
-        for (void *x : p) hipFree(x);
-    }
-    template <class T>
-    hipError_t alloc(T **out, size_t n) {
-        void *x = nullptr;
-        const hipError_t e = hipMalloc(&x, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) p.push_back(x);
-        *out = (T *)x;
-        return e;
-    }
-};
+#define S_ALLOC(expr)                                                                              \
+    do {                                                                                           \
+        if (expr) return sfail("%s", surfh_last_error());       /* the allocator's message, in this module's error string */ \
+    } while (0)
 
 inline unsigned blocks(long n) { return (unsigned)((n + TPB - 1) / TPB); }
 
@@ -348,14 +341,14 @@ int surfh_shepard(int32_t n_seg, const int64_t *pt_off, const float *pt_alpha, c
     const long nqa = separable ? ga : n_q, nql = separable ? gl : n_q;
 
     hipStream_t st = (hipStream_t)stream;
-    DevBuf mem;
+    DevBuf<float> a, l, v, xa, xl, sout;         // host arrays staged on the device
+    DevBuf<int> snbr;
     const float *da = pt_alpha, *dl = pt_lambda, *dv = pt_value, *dqa = q_alpha, *dql = q_lambda;
     float *dout = out;
     int *dnbr = neighbours;
     if (!device_ptrs) {        // host arrays: stage them on the device
-        float *a, *l, *v, *xa, *xl;
-        S_OK(mem.alloc(&a, n_pts)); S_OK(mem.alloc(&l, n_pts)); S_OK(mem.alloc(&v, n_pts));
-        S_OK(mem.alloc(&xa, nqa)); S_OK(mem.alloc(&xl, nql)); S_OK(mem.alloc(&dout, n_q));
+        S_ALLOC(a.alloc(n_pts) || l.alloc(n_pts) || v.alloc(n_pts) || xa.alloc(nqa) || xl.alloc(nql) || sout.alloc(n_q));
+        dout = sout;
         if (n_pts) {
             S_OK(hipMemcpyAsync(a, pt_alpha, n_pts * 4, hipMemcpyHostToDevice, st));
             S_OK(hipMemcpyAsync(l, pt_lambda, n_pts * 4, hipMemcpyHostToDevice, st));
@@ -365,11 +358,14 @@ int surfh_shepard(int32_t n_seg, const int64_t *pt_off, const float *pt_alpha, c
         if (nql) S_OK(hipMemcpyAsync(xl, q_lambda, nql * 4, hipMemcpyHostToDevice, st));
         da = a; dl = l; dv = v; dqa = xa; dql = xl;
         dnbr = nullptr;
-        if (neighbours) S_OK(mem.alloc(&dnbr, n_q));
+        if (neighbours) {
+            S_ALLOC(snbr.alloc(n_q));
+            dnbr = snbr;
+        }
     }
-    Seg *dseg;
-    long *dpoff, *dqoff;
-    S_OK(mem.alloc(&dseg, n_seg)); S_OK(mem.alloc(&dpoff, n_seg + 1)); S_OK(mem.alloc(&dqoff, n_seg + 1));
+    DevBuf<Seg> dseg;
+    DevBuf<long> dpoff, dqoff;
+    S_ALLOC(dseg.alloc(n_seg) || dpoff.alloc(n_seg + 1) || dqoff.alloc(n_seg + 1));
     std::vector<long> poff(pt_off, pt_off + n_seg + 1);
     S_OK(hipMemcpyAsync(dseg, segs.data(), n_seg * sizeof(Seg), hipMemcpyHostToDevice, st));
     S_OK(hipMemcpyAsync(dpoff, poff.data(), (n_seg + 1) * sizeof(long), hipMemcpyHostToDevice, st));
@@ -393,10 +389,9 @@ int surfh_shepard(int32_t n_seg, const int64_t *pt_off, const float *pt_alpha, c
     if (n_cells > 0x7fffffffL) return sfail("surfh_shepard: cell list too long (%ld cells)", n_cells);
     S_OK(hipMemcpyAsync(dseg, segs.data(), n_seg * sizeof(Seg), hipMemcpyHostToDevice, st));
 
-    int *cell, *count, *start, *fill, *order;
-    float4 *sorted;
-    S_OK(mem.alloc(&cell, n_pts)); S_OK(mem.alloc(&count, n_cells)); S_OK(mem.alloc(&fill, n_cells));
-    S_OK(mem.alloc(&start, n_cells + 2)); S_OK(mem.alloc(&order, n_pts)); S_OK(mem.alloc(&sorted, n_pts));
+    DevBuf<int> cell, count, start, fill, order;
+    DevBuf<float4> sorted;
+    S_ALLOC(cell.alloc(n_pts) || count.alloc(n_cells) || fill.alloc(n_cells) || start.alloc(n_cells + 2) || order.alloc(n_pts) || sorted.alloc(n_pts));
     S_OK(hipMemsetAsync(count, 0, std::max(n_cells, 1L) * sizeof(int), st));
     S_OK(hipMemsetAsync(fill, 0, std::max(n_cells, 1L) * sizeof(int), st));
     if (n_pts) {

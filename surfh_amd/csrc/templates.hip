@@ -28,6 +28,9 @@
 #include <vector>
 
 #include "../../include/surfh_amd.h"
+#include "dev_buf.h"
+
+using surfh_impl::DevBuf;
 
 namespace {
 
@@ -47,20 +50,10 @@ int tfail(const char *fmt, ...) {
         if (e_ != hipSuccess) return tfail("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-struct DevBuf {            // frees whatever was allocated when the call returns
-    std::vector<void *> p;
-    ~DevBuf() {
-        for (void *x : p) hipFree(x);
-    }
-    template <class T>
-    hipError_t alloc(T **out, size_t n) {
-        void *x = nullptr;
-        const hipError_t e = hipMalloc(&x, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) p.push_back(x);
-        *out = (T *)x;
-        return e;
-    }
-};
+#define T_ALLOC(expr)                                                                              \
+    do {                                                                                           \
+        if (expr) return tfail("%s", surfh_last_error());       /* the allocator's message, in this module's error string */ \
+    } while (0)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // spectral median
@@ -350,10 +343,8 @@ int surfh_spectral_median(const float *src, float *dst, int64_t L, int64_t C, in
     if (C == 0) return 0;
     T_OK(hipSetDevice(device));
     const size_t n = (size_t)L * (size_t)C;
-    DevBuf mem;
-    float *ds, *dd;
-    T_OK(mem.alloc(&ds, n));
-    T_OK(mem.alloc(&dd, n));
+    DevBuf<float> ds, dd;
+    T_ALLOC(ds.alloc(n) || dd.alloc(n));
     T_OK(hipMemcpy(ds, src, n * 4, hipMemcpyHostToDevice));
     const dim3 grid(cdiv(C, 256)), block(256);
     if (size <= 8) k_median<8><<<grid, block>>>(ds, dd, L, C, size, mode);
@@ -387,26 +378,15 @@ int surfh_nmf_cd(const float *X, int64_t P, int64_t L, int32_t n_models, const i
             for (int k = 0; k < models[m].K; ++k) wcat[(size_t)i * N + models[m].off + k] = wm[(size_t)i * models[m].K + k];
     }
     const int S = (int)cdiv(L, KCHUNK);                    // X Hcat^T and Hcat Hcat^T both reduce over L
-    DevBuf mem;
-    float *dX, *dW, *dH, *xht, *hht, *wtx, *wtw, *part;
-    double *vw, *vh, *vinit, *trace;
-    int *done, *dnit;
-    Model *dmod;
-    T_OK(mem.alloc(&dX, (size_t)P * L));
-    T_OK(mem.alloc(&dW, (size_t)P * N));
-    T_OK(mem.alloc(&dH, (size_t)N * L));
-    T_OK(mem.alloc(&xht, (size_t)P * N));
-    T_OK(mem.alloc(&hht, (size_t)N * N));
-    T_OK(mem.alloc(&wtx, (size_t)N * L));
-    T_OK(mem.alloc(&wtw, (size_t)N * N));
-    T_OK(mem.alloc(&part, (size_t)S * std::max<long>(P, N) * N));
-    T_OK(mem.alloc(&vw, (size_t)n_models * P));
-    T_OK(mem.alloc(&vh, (size_t)n_models * L));
-    T_OK(mem.alloc(&vinit, n_models));
-    T_OK(mem.alloc(&trace, (size_t)n_models * std::max(max_iter, 1)));
-    T_OK(mem.alloc(&done, n_models));
-    T_OK(mem.alloc(&dnit, n_models));
-    T_OK(mem.alloc(&dmod, n_models));
+    DevBuf<float> dX, dW, dH, xht, hht, wtx, wtw, part;
+    DevBuf<double> vw, vh, vinit, trace, rpart, rout;
+    DevBuf<int> done, dnit;
+    DevBuf<Model> dmod;
+    T_ALLOC(dX.alloc((size_t)P * L) || dW.alloc((size_t)P * N) || dH.alloc((size_t)N * L) || xht.alloc((size_t)P * N) ||
+            hht.alloc((size_t)N * N) || wtx.alloc((size_t)N * L) || wtw.alloc((size_t)N * N) ||
+            part.alloc((size_t)S * std::max<long>(P, N) * N) || vw.alloc((size_t)n_models * P) || vh.alloc((size_t)n_models * L) ||
+            vinit.alloc(n_models) || trace.alloc((size_t)n_models * std::max(max_iter, 1)) || done.alloc(n_models) ||
+            dnit.alloc(n_models) || dmod.alloc(n_models));
     T_OK(hipMemcpy(dX, X, (size_t)P * L * 4, hipMemcpyHostToDevice));
     T_OK(hipMemcpy(dW, wcat.data(), (size_t)P * N * 4, hipMemcpyHostToDevice));
     T_OK(hipMemcpy(dH, H, (size_t)N * L * 4, hipMemcpyHostToDevice));
@@ -450,9 +430,7 @@ int surfh_nmf_cd(const float *X, int64_t P, int64_t L, int32_t n_models, const i
 
     // ||X - W H||_F and the sum of the relative residuals, per model
     const long nb = (long)cdiv(L, RED) * cdiv(P, ERR_ROWS);
-    double *rpart, *rout;
-    T_OK(mem.alloc(&rpart, (size_t)n_models * 2 * nb));
-    T_OK(mem.alloc(&rout, (size_t)n_models * 2));
+    T_ALLOC(rpart.alloc((size_t)n_models * 2 * nb) || rout.alloc((size_t)n_models * 2));
     k_recon<<<(unsigned)nb, RED>>>(dmod, n_models, dX, dW, dH, P, L, N, rpart);
     k_recon_final<<<n_models, RED>>>(rpart, nb, rout);
     T_OK(hipGetLastError());

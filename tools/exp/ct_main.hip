@@ -10,6 +10,14 @@
 #include "../../surfh_amd/csrc/dft_ct.h"
 #define CK(x) do { hipError_t e_ = (hipError_t)(x); if (e_ != hipSuccess) { printf("hip error %s line %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
 
+// the transform plan owns its device buffers (surfh_amd/csrc/dev_buf.h); the library's allocator is in plan.hip, which this
+// stand-alone program does not link, so it brings its own pair
+namespace surfh_impl {
+int fail(const char *fmt, ...) { printf("%s\n", fmt); return 1; }
+int dev_raw_alloc(void **p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess ? 0 : fail("device allocation failed"); }
+void dev_raw_free(void *p) { hipFree(p); }
+}  // namespace surfh_impl
+
 __global__ void fill_k(float *p, long n, unsigned seed, int mode) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         unsigned x = (unsigned)i * 2654435761u + seed; x ^= x >> 15; x *= 2246822519u; x ^= x >> 13;
@@ -284,6 +292,5 @@ int main(int argc, char **argv) {
         }
         hipFree(a); hipFree(b); hipFree(pr);
     }
-    dft_ct_plan_destroy(&pl);
     return 0;
 }

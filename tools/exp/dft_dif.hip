@@ -262,7 +262,7 @@ int launch_dft_dif(hipStream_t stream, const DftCtArgs &g, const DftCtPlan &pl) 
 #define DIF_GO(R_)                                                                                                                    \
     {                                                                                                                                 \
         hipFuncSetAttribute(reinterpret_cast<const void *>(dft_dif_kernel<R_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb); \
-        hipLaunchKernelGGL((dft_dif_kernel<R_>), grid, dim3(NTH), ldsb, stream, g, reinterpret_cast<const uint4 *>(pl.img), pl.tw, pl.MT, pl.KT,  \
+        hipLaunchKernelGGL((dft_dif_kernel<R_>), grid, dim3(NTH), ldsb, stream, g, reinterpret_cast<const uint4 *>(pl.img.get()), pl.tw.get(), pl.MT, pl.KT,  \
                            pl.kA, NJ);                                                                                                \
     }
     if (g.R == 3) DIF_GO(3) else if (g.R == 4) DIF_GO(4) else if (g.R == 2) DIF_GO(2) else return (int)hipErrorInvalidValue;
