@@ -589,6 +589,16 @@ int32_t surfh_klist_classify(const float *B, int32_t n, int32_t k, int64_t ldb, 
  *   "huber_maps": a, b, c = T, Na, Nb;  "huber_vox": a, b, c = Lc, Na, Nb, out[3] = the most planes of one chunk,
  *     chunk k of C = out[1] owning planes [Lc k / C, Lc (k + 1) / C)                                                     */
 int surfh_launch_geometry(const char *which, int64_t a, int64_t b, int64_t c, int64_t out[4]);
+/* host only (no GPU, no plan): the route plan creation would decide -- which transform kernels run and which fusions ride on
+ * them -- from the function plan creation calls.  lp: the plan's plane pitch (owned planes rounded up to 128).  switches: bit i
+ * set = switch i is on, in the order SURFH_DFT_H2, SURFH_DFT_CT, SURFH_DFT_DENSE, SURFH_NO_FUSED_MIX, SURFH_ADJ_FUSED,
+ * SURFH_OTF_PROD, SURFH_OTF_SUPPORT, SURFH_OTF_RANGES (the defaults: 0xF3).  scan: what the scan of the OTF found, 0 nothing to
+ * drop, 1 support lists, 2 lists and k-ranges (ignored where the route does not scan).
+ * out = { kernel along alpha, along beta (0 dense, 1 dft_h2, 2 dft_ct), mix in the forward's loader, OTF product in the inverse
+ * loader, fused adjoint tail, OTF support in use (0, 1, 2), spectral template tail, spectral-domain calls available }.
+ * surfh_debug_dims(plan, "route") / (plan, "route2") report the first / last four of the route a plan holds.              */
+int surfh_route_decide(int32_t n_alpha, int32_t n_beta, int32_t n_templates, int64_t lp, int32_t verify, int32_t exact,
+                       int32_t has_sotf, uint32_t switches, int32_t scan, int64_t out[8]);
 /* host only: the device allocator's process-wide counters.  live = allocations made and not yet freed, total = allocations
  * asked for so far -- every device allocation of the library goes through one function, so "no leak" is live == what it was. */
 void surfh_debug_alloc_count(int64_t *live, int64_t *total);

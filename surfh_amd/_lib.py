@@ -61,7 +61,7 @@ EXPORTS = [
     "surfh_randn_dev", "surfh_po_data_dev", "surfh_po_prior_dev", "surfh_po_moments", "surfh_po_rhs", "surfh_cg_sample",
     "surfh_cg_begin_dev", "surfh_cg_iter_nosync_dev", "surfh_cg_xupdate_nosync_dev", "surfh_cg_refresh_nosync_dev", "surfh_cg_trace",
     "surfh_profile_enable", "surfh_profile_filter", "surfh_profile_count", "surfh_profile_get", "surfh_profile_reset", "surfh_debug_copy",
-    "surfh_debug_dims", "surfh_gemm_selftest", "surfh_gemm_selftest_ksteps", "surfh_gemm_selftest_ms", "surfh_klist_classify", "surfh_launch_geometry", "surfh_mm_step2",
+    "surfh_debug_dims", "surfh_gemm_selftest", "surfh_gemm_selftest_ksteps", "surfh_gemm_selftest_ms", "surfh_klist_classify", "surfh_launch_geometry", "surfh_route_decide", "surfh_mm_step2",
     "surfh_debug_alloc_count", "surfh_debug_alloc_fail",
     "surfh_shepard", "surfh_shepard_last_error", "surfh_spectral_median", "surfh_nmf_cd", "surfh_templates_last_error",
     "surfh_set_templates", "surfh_get_templates", "surfh_forward_templates", "surfh_adjoint_templates", "surfh_forward_templates_dev",
@@ -188,6 +188,7 @@ def load():
     L.surfh_klist_classify.argtypes = [c_float_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int64]
     L.surfh_klist_classify.restype = C.c_int32
     L.surfh_launch_geometry.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
+    L.surfh_route_decide.argtypes = [C.c_int32] * 3 + [C.c_int64] + [C.c_int32] * 3 + [C.c_uint32, C.c_int32, C.POINTER(C.c_int64)]
     L.surfh_mm_step2.argtypes = [C.c_double] * 5 + [c_double_p]
     L.surfh_debug_alloc_count.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.surfh_debug_alloc_count.restype = None

@@ -74,8 +74,8 @@ class Blurred2D(DataWeights, _pot.Potentials, LinOp):
                               zip(("gt_i0", "gt_i1", "gt_y0", "gt_y1", "gt_inside"), gt,
                                   (np.int32, np.int32, np.float64, np.float64, np.uint8))})
 
-    def _create_plan(self, device=0, stream=None):
-        """One beta-sum channel on the tables of ``_set_tables``."""
+    def _create_plan(self, device=0, stream=None, exact=0):
+        """One beta-sum channel on the tables of ``_set_tables``; ``exact``: ``surfh_config.exact``."""
         t = self._tab
         na, nb = self.local_im_shape
         d = _lib.ChannelDesc()
@@ -95,6 +95,7 @@ class Blurred2D(DataWeights, _pot.Potentials, LinOp):
         cfg.sotf = self._sotf_c.view(np.float64).ctypes.data_as(_lib.c_double_p)
         cfg.n_channels, cfg.channels = 1, C.pointer(d)
         cfg.device, cfg.stream, cfg.split_k_forward = device, (C.c_void_p(stream) if stream else None), 0
+        cfg.exact = int(exact)
         L = _lib.load()
         plan = C.c_void_p()
         _lib.check(L.surfh_plan_create(C.byref(cfg), C.byref(plan)), ValueError)

@@ -541,11 +541,12 @@ void build_dft(const surfh_plan *p, std::vector<float> &Fi, std::vector<float> &
 // Gaussian PSF (utils.py:40-50) falls below 2^-24 of its peak beyond 50-80 % of the k_beta range.  Products with such entries
 // are below the rounding of the plane's leading terms in fp32, so the (k_beta, 128-wavelength chunk) super-tiles in which NO
 // entry of any k_alpha reaches 2^-24 of its plane's largest magnitude are dropped from both passes -- the same set in both, so the
-// adjoint stays the transpose of the forward.  Nothing is dropped when every tile has such an entry (SURFH_OTF_SUPPORT=0: off).
-int otf_support(surfh_plan *p, const surfh_config *cfg) {
-    const bool on = env_on("SURFH_OTF_SUPPORT", true);      // read at plan creation
-    if (cfg->exact & 2) return 0;
-    if (!on || !cfg->sotf || !p->ilv || p->T < 1 || !p->fuse_mix || p->LP % 128) return 0;
+// adjoint stays the transpose of the forward.  Nothing is dropped when every tile has such an entry.  Runs where `r`, the route
+// before the scan, asks for it (Route::scan_otf); `found` is the outcome that completes the route.
+int otf_support(surfh_plan *p, const surfh_config *cfg, const Route &r, bool ranges, OtfSupport *found) {
+    *found = OTF_NONE;
+    if (!r.scan_otf) return 0;
+    const bool ct = r.ax_a == AX_CT;      // both axes on dft_ct (else both on dft_h2)
     const int nkb = p->Nb / 2 + 1, nch = (int)(p->LP / 128);
     std::vector<int> bmax(nch, -1), amaxk(nch, -1);   // largest k_beta / folded k_alpha of the support over a chunk's planes (-1: none)
     std::vector<double> km(nkb), kam(p->Na);
@@ -583,9 +584,10 @@ int otf_support(surfh_plan *p, const surfh_config *cfg) {
     const size_t nyc = (size_t)2 * p->NAP * p->KBP * p->LP;
     if (p->otf_vlist.upload(vlist) || p->otf_kbstart.upload(kbstart) || p->ycol_mix.zeros(nyc)) return 1;
     p->otf_nvalid = (int)vlist.size();
-    std::vector<int> tabs((size_t)(p->ct ? 4 : 3) * nch);
+    *found = ranges ? OTF_LISTS_RANGES : OTF_LISTS;
+    std::vector<int> tabs((size_t)(ct ? 4 : 3) * nch);
     for (int j = 0; j < nch; ++j) {
-        if (p->ct) {
+        if (ct) {
             // sub-sequence n1 of a length R M: element j stands for the rows R j + n1 and N - (R j - n1); inside the support
             // (folded index <= amax) for j <= (amax + R - 1) / R
             const int ja = (std::max(amaxk[j], 0) + p->ctA.R - 1) / p->ctA.R, jb = (std::max(bmax[j], 0) + p->ctB->R - 1) / p->ctB->R;
@@ -599,12 +601,49 @@ int otf_support(surfh_plan *p, const surfh_config *cfg) {
         tabs[nch + j] = std::min(std::max((bmax[j] + 16) / 16, 2), p->KPb / 16);
         tabs[2 * nch + j] = bmax[j] + 1;
     }
-    const bool ranges = env_on("SURFH_OTF_RANGES", true);
     if (ranges && p->otf_tabs.upload(tabs)) return 1;
     return 0;
 }
 
+// the eight switches that feed the route (RouteSwitch), read once at the top of plan creation; DESIGN.md says what each one does
+unsigned read_route_switches() {
+    static const struct { const char *name; bool dflt; } sw[SW_COUNT] = {
+        {"SURFH_DFT_H2", true}, {"SURFH_DFT_CT", true}, {"SURFH_DFT_DENSE", false}, {"SURFH_NO_FUSED_MIX", false},
+        {"SURFH_ADJ_FUSED", true}, {"SURFH_OTF_PROD", true}, {"SURFH_OTF_SUPPORT", true}, {"SURFH_OTF_RANGES", true}};
+    unsigned m = 0;
+    for (int i = 0; i < SW_COUNT; ++i) m |= (unsigned)env_on(sw[i].name, sw[i].dflt) << i;
+    return m;
+}
+
 }  // namespace
+
+// The one decision of a plan's route (Route, plan_internal.h; the table in DESIGN.md).  Pure: no HIP call, no environment.  The
+// kernel is chosen per axis: dft_h2 (16 < n/2+1 <= 128, row offsets below 4 GB), else dft_ct (n = R M), else none -- and that,
+// a verification plan or SURFH_DFT_DENSE=1 put the whole plan on the dense fp32 products.  `scan`: what the OTF scan found.
+Route decide_route(const RouteInput &in, OtfSupport scan) {
+    Route r;
+    auto axis = [&](int n) {
+        if (in.on(SW_DFT_H2) && dft_h2_supported(n, n, in.NAP, in.KBP, in.LP)) return AX_H2;
+        if (in.on(SW_DFT_CT) && dft_ct_factor(n, nullptr, nullptr)) return AX_CT;
+        return AX_DENSE;
+    };
+    const AxisKernel a = axis(in.Na), b = axis(in.Nb);
+    if (in.verify || in.on(SW_DFT_DENSE) || a == AX_DENSE || b == AX_DENSE) return r;       // planar arrays, nothing fused
+    r.ax_a = a; r.ax_b = b;
+    const bool few = in.T >= 1 && in.T <= 4;          // templates the mix loaders and the fused tail hold in registers
+    const bool both_h2 = a == AX_H2 && b == AX_H2, both_ct = a == AX_CT && b == AX_CT;
+    r.mix = few && !in.on(SW_NO_FUSED_MIX);
+    r.prod = in.on(SW_OTF_PROD) && in.T == 0 && a == AX_CT;
+    r.fused_tail = both_h2 && in.on(SW_ADJ_FUSED) && few && in.Na >= 127 && in.Na <= 255;      // the tail's output rows
+    r.tpl_spectral = in.T <= 4;
+    r.spec_calls = r.mix && (r.fused_tail || !both_h2);
+    // the support lists serve the mix loader and the adjoint's tail alike (the same tiles dropped in both, or the adjoint is no
+    // transpose): dft_h2's ride on its fused tail, dft_ct's need both axes; exact & 2 asks for the whole spectrum
+    r.scan_otf = r.mix && in.has_sotf && !(in.exact & 2) && in.on(SW_OTF_SUPPORT) && (r.fused_tail || both_ct);
+    if (r.scan_otf) r.support = scan;
+    if (both_ct && r.support == OTF_LISTS) r.support = OTF_NONE;       // dft_ct's listed passes take the k-ranges with the lists, or neither
+    return r;
+}
 
 }  // namespace surfh_impl
 
@@ -701,23 +740,12 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
     p->isize = (long)(p->T > 0 ? p->T : p->Lc) * p->Na * p->Nb;
     const size_t LP = (size_t)p->LP;
 
-    {   // which transform kernels run decides the layout of the complex arrays: two-piece fp16 passes (default where
-        // the matrices fit LDS) keep them interleaved.  The kernel is chosen per axis: dft_h2 (16 < n/2+1 <= 128, row offsets below
-        // 4 GB), else dft_ct (n = R M), else none -- then the whole plan runs the dense fp32 products on planar arrays.
-        // SURFH_DFT_H2=0 / SURFH_DFT_CT=0 take a kernel out of the choice (A/B), SURFH_DFT_DENSE=1 forces the dense products.
-        const bool h2_on = env_on("SURFH_DFT_H2", true), ct_on = env_on("SURFH_DFT_CT", true);
-        auto axis = [&](int n) {
-            if (h2_on && dft_h2_supported(n, n, p->NAP, p->KBP, p->LP)) return 1;
-            if (ct_on && dft_ct_factor(n, nullptr, nullptr)) return 2;
-            return 0;
-        };
-        p->ax_a = axis(p->Na);
-        p->ax_b = axis(p->Nb);
-        p->ilv = !cfg->verify && !env_on("SURFH_DFT_DENSE", false) && p->LP % 128 == 0 && p->ax_a && p->ax_b;
-        if (!p->ilv) p->ax_a = p->ax_b = 0;
-        p->h2 = p->ilv && p->ax_a == 1 && p->ax_b == 1;
-        p->ct = p->ilv && !p->h2;
-    }
+    // the route before the OTF scan: everything up to the scan reads `r0`; p->route is written once, with the scan's outcome
+    RouteInput rin;
+    rin.Na = p->Na; rin.Nb = p->Nb; rin.T = p->T; rin.NAP = p->NAP; rin.KBP = p->KBP; rin.LP = p->LP;
+    rin.verify = cfg->verify != 0; rin.has_sotf = cfg->sotf != nullptr; rin.exact = cfg->exact; rin.switches = read_route_switches();
+    const Route r0 = decide_route(rin, OTF_NONE);
+    const bool ilv = r0.interleaved();
     // ---- constants ------------------------------------------------------------------------
     {   // sotf [Lc][Na][Nb/2+1] complex128  ->  [2][KAP][KBP][LP] float (h2: [KAP][KBP][LP][2]), wavelength innermost
         const int nkb = p->Nb / 2 + 1;
@@ -731,7 +759,7 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
                 const double *src = cfg->sotf ? cfg->sotf + ((size_t)p->planes[l] * p->Na + a) * nkb * 2 : nullptr;
                 for (int k = 0; k < nkb; ++k) {
                     const float vr = src ? (float)src[2 * k] : 1.f, vi = src ? (float)src[2 * k + 1] : 0.f;
-                    if (p->ilv) {
+                    if (ilv) {
                         row[((size_t)k * LP + l) * 2] = vr;
                         row[((size_t)k * LP + l) * 2 + 1] = vi;
                     } else {
@@ -740,7 +768,7 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
                     }
                 }
             }
-            if (p->ilv) {
+            if (ilv) {
                 if (hipMemcpy(p->sotf + (size_t)a * p->KBP * LP * 2, row.data(), (size_t)2 * p->KBP * LP * sizeof(float),
                               hipMemcpyHostToDevice) != hipSuccess)
                     return bail(fail("sotf upload failed"));
@@ -765,14 +793,11 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
         if (p->Fi.upload(Fi) || p->Gi.upload(Gi) || p->Gf.upload(Gf) || p->Ff.upload(Ff) || p->GiT.upload(GiT) || p->GfT.upload(GfT)) return bail(1);
     }
     {   // folded-DFT matrices
-        p->dense_dft = env_on("SURFH_DFT_DENSE", false);
-        p->fuse_mix = !env_on("SURFH_NO_FUSED_MIX", false);
         p->wblur_fp32 = env_on("SURFH_WBLUR_FP32", false);       // R / R^T on the fp32-input MFMA instead of the split-bf16 path
         // measured on config 3: 7.64 -> 7.53 ms per iteration (+1.5 %), the overlapped kernels slow each other down by
         // almost what they save; off by default so that per-kernel times in profiles stay those of a kernel running alone
         p->overlap = env_on("SURFH_OVERLAP", false);
         if (p->overlap && hipStreamCreateWithFlags(&p->stream2, hipStreamNonBlocking) != hipSuccess) return bail(fail("hipStreamCreate failed"));
-        p->otf_prod = env_on("SURFH_OTF_PROD", true);
         p->gather_grouped = env_on("SURFH_GATHER_GROUPED", true);
         p->gemm_grouped = env_on("SURFH_GEMM_GROUPED", true);
         p->scatter_grouped = env_on("SURFH_SCATTER_GROUPED", true);
@@ -800,41 +825,35 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
                 Sf[(size_t)k * p->KPb + b] = (float)(std::sin(th) * sb);
             }
         if (p->Cma.upload(Cma) || p->Sma.upload(Sma) || p->Gc.upload(Gc) || p->Gs.upload(Gs) || p->Cf.upload(Cf) || p->Sf.upload(Sf)) return bail(1);
-        if (cfg->verify) {      // verification plan: dense DFT products, unfused spectral mix, fp32-operand spectral blur -- all float64-accumulated
+        if (cfg->verify) {      // verification plan: fp32-operand spectral blur, and the route's dense DFT products and unfused mix -- all float64-accumulated
             p->verify = true;
-            p->dense_dft = true;
-            p->fuse_mix = false;
             p->wblur_fp32 = true;
             p->overlap = false;
         }
-        if (p->ax_a == 1 || p->ax_b == 1) {   // LDS images of the matrix pairs of the axes that run on dft_h2 (dft_h2.h)
-            if ((p->ax_a == 1 && p->MPa != 128) || (p->ax_b == 1 && p->MPb != 128)) return bail(fail("internal: dft_h2 needs 128-row folded matrices"));
+        if (r0.ax_a == AX_H2 || r0.ax_b == AX_H2) {   // LDS images of the matrix pairs of the axes that run on dft_h2 (dft_h2.h)
+            if ((r0.ax_a == AX_H2 && p->MPa != 128) || (r0.ax_b == AX_H2 && p->MPb != 128)) return bail(fail("internal: dft_h2 needs 128-row folded matrices"));
             std::vector<unsigned short> im(3 * DFT_H2_IMAGE_HALFS, 0);
-            if (p->ax_a == 1) p->h2kA[0] = dft_h2_build_image(Cma.data(), Sma.data(), p->MPa, p->KPa, p->KPa, im.data());
-            if (p->ax_b == 1) {
+            if (r0.ax_a == AX_H2) p->h2kA[0] = dft_h2_build_image(Cma.data(), Sma.data(), p->MPa, p->KPa, p->KPa, im.data());
+            if (r0.ax_b == AX_H2) {
                 p->h2kA[1] = dft_h2_build_image(Gc.data(), Gs.data(), p->MPb, p->KPb, p->KPb, im.data() + DFT_H2_IMAGE_HALFS);
                 p->h2kA[2] = dft_h2_build_image(Cf.data(), Sf.data(), p->MPb, p->KPb, p->KPb, im.data() + 2 * DFT_H2_IMAGE_HALFS);
             }
             if (p->h2img.upload(im)) return bail(1);
         }
-        if (p->h2) {
-            // fused adjoint tail: the last pass of rfft2 multiplies by conj(sotf) and reduces over the wavelengths itself
-            // (needs T <= 4 templates and 127 <= Na <= 255 output rows; SURFH_ADJ_FUSED=0: separate pass + reduction)
-            if (env_on("SURFH_ADJ_FUSED", true) && p->T >= 1 && p->T <= 4 && p->Na >= 127 && p->Na <= 255 && p->LP % 128 == 0) {
-                if (otf_support(p, cfg)) return bail(1);
-                const size_t npart = dft_h2_adjmix_part_floats(p->LP, p->Nb / 2 + 1, p->otf_nvalid);
-                if (npart && p->adjmix_part.alloc(npart)) return bail(1);
-            }
+        // image + twiddles per transform length of the axes that run on dft_ct (dft_ct.h)
+        if (r0.ax_a == AX_CT && dft_ct_plan_create(p->Na, &p->ctA)) return bail(fail("dft_ct plan (n_alpha = %d) failed", p->Na));
+        if (r0.ax_b == AX_CT) {
+            if (r0.ax_a == AX_CT && p->Nb == p->Na) p->ctB = &p->ctA;
+            else if (dft_ct_plan_create(p->Nb, &p->ctB_own)) return bail(fail("dft_ct plan (n_beta = %d) failed", p->Nb));
         }
-        if (p->ct) {   // image + twiddles per transform length of the axes that run on dft_ct (dft_ct.h)
-            if (p->ax_a == 2 && dft_ct_plan_create(p->Na, &p->ctA)) return bail(fail("dft_ct plan (n_alpha = %d) failed", p->Na));
-            if (p->ax_b == 2) {
-                if (p->ax_a == 2 && p->Nb == p->Na) p->ctB = &p->ctA;
-                else if (dft_ct_plan_create(p->Nb, &p->ctB_own)) return bail(fail("dft_ct plan (n_beta = %d) failed", p->Nb));
-            }
-            if (p->ax_a == 2 && p->ax_b == 2 && p->T >= 1 && p->T <= 4 && otf_support(p, cfg)) return bail(1);      // lists: both axes on dft_ct
+        OtfSupport found;
+        if (otf_support(p, cfg, r0, rin.on(SW_OTF_RANGES), &found)) return bail(1);
+        p->route = decide_route(rin, found);
+        if (p->route.fused_tail) {       // the fused tail's partial sums: as many slots as its workgroups take super-tiles
+            const size_t npart = dft_h2_adjmix_part_floats(p->LP, p->Nb / 2 + 1, p->otf_nvalid);
+            if (!npart) return bail(fail("the fused adjoint tail could not size its partial sums"));
+            if (p->adjmix_part.alloc(npart)) return bail(1);
         }
-        if (!p->ilv) p->dense_dft = true;        // no fast kernel for one of the axes: dense fp32 products
     }
     // ---- work buffers ---------------------------------------------------------------------
     const size_t nspec = (size_t)2 * p->PL * LP, ncube = (size_t)p->NBP * p->NAP * LP;
@@ -905,7 +924,7 @@ int surfh_plan_create(const surfh_config *cfg, surfh_plan **out) {
     if (p->b_hi <= p->b_lo) { p->b_lo = 0; p->b_hi = p->Nb; }
     {   // transform passes batched over alpha skip the columns no table touches (SURFH_ALPHA_RANGE=0: whole cube)
         if (!env_on("SURFH_ALPHA_RANGE", true)) { p->a_lo = 0; p->a_hi = p->Na; p->b_lo = 0; p->b_hi = p->Nb; }
-        if (p->ilv && p->a_hi - p->a_lo < p->Na) {      // the adjoint's intermediate: columns outside the range zero for good
+        if (ilv && p->a_hi - p->a_lo < p->Na) {      // the adjoint's intermediate: columns outside the range zero for good
             const size_t nyc = (size_t)2 * p->NAP * p->KBP * p->LP;
             if (p->ycol_adj.zeros(nyc)) return bail(1);
         }

@@ -48,7 +48,7 @@ static int resolve(surfh_plan *p, const char *which, const float **ptr, int64_t 
         *ptr = (w == "gcube" && p->gcube) ? p->gcube : p->cube; dims[0] = p->NBP; dims[1] = p->NAP; dims[2] = p->LP;
     } else if (w == "spec") {                       // [2][k_alpha][k_beta][lambda]; h2 plans: [k_alpha][k_beta][lambda][2]
         *ptr = p->spec;
-        if (p->ilv) { dims[0] = p->KAP; dims[1] = p->KBP; dims[2] = p->LP; dims[3] = 2; }
+        if (p->route.interleaved()) { dims[0] = p->KAP; dims[1] = p->KBP; dims[2] = p->LP; dims[3] = 2; }
         else { dims[0] = 2; dims[1] = p->KAP; dims[2] = p->KBP; dims[3] = p->LP; }
     } else if (w == "mhat" && p->T > 0) {
         *ptr = p->mhat; dims[0] = p->T; dims[1] = 2; dims[2] = p->KAP; dims[3] = p->KBP;
@@ -75,7 +75,7 @@ static int resolve(surfh_plan *p, const char *which, const float **ptr, int64_t 
     } else if (w == "range") {         // cube columns / rows the channels' tables touch: [a_lo, a_hi) x [b_lo, b_hi)
         dims[0] = p->a_lo; dims[1] = p->a_hi; dims[2] = p->b_lo; dims[3] = p->b_hi;
     } else if (w == "otf") {           // super-tiles (k_beta, 128 wavelengths) inside the OTF's support / all of them
-        dims[0] = p->otf_vlist ? p->otf_nvalid : (long)(p->Nb / 2 + 1) * (p->LP / 128); dims[1] = (long)(p->Nb / 2 + 1) * (p->LP / 128);
+        dims[1] = (long)(p->Nb / 2 + 1) * (p->LP / 128); dims[0] = p->otf_nvalid ? p->otf_nvalid : dims[1];
     } else if (w == "ksteps") {        // (tile, K step) pairs of the spectral-blur GEMMs: near / far of the forward, near / far of the adjoint
         for (auto &c : p->ch)
             for (int i = 0; i < 4; ++i) dims[i] += c.ksteps[i];
@@ -84,7 +84,11 @@ static int resolve(surfh_plan *p, const char *which, const float **ptr, int64_t 
         dims[0] = dims[1] = 0;
         for (auto &c : p->ch) { dims[0] += c.fwd.g.NG; dims[1] += c.adjT.g.NG; }
     } else if (w == "dft") {           // kernel of each transform axis (0: dense, 1: dft_h2, 2: dft_ct), interleaved arrays, fused adjoint tail
-        dims[0] = p->ax_a; dims[1] = p->ax_b; dims[2] = p->ilv ? 1 : 0; dims[3] = p->adjmix_part ? 1 : 0;
+        dims[0] = p->route.ax_a; dims[1] = p->route.ax_b; dims[2] = p->route.interleaved(); dims[3] = p->route.fused_tail;
+    } else if (w == "route" || w == "route2") {       // the plan's route, in the order surfh_route_decide reports it: fields 0-3, 4-7
+        int64_t f[8];
+        route_fields(p->route, f);
+        for (int i = 0; i < 4; ++i) dims[i] = f[(w == "route2" ? 4 : 0) + i];
     } else if (w == "trim") {         // planes the fused transform passes run over, the plane pitch, owned planes
         dims[0] = p->Leff; dims[1] = p->LP; dims[2] = p->Lown;
     } else if (w == "info") {
@@ -129,6 +133,16 @@ int32_t surfh_klist_classify(const float *B, int32_t n, int32_t k, int64_t ldb, 
     if ((int64_t)kl.size() > capacity) return -fail("surfh_klist_classify: capacity too small");
     std::memcpy(records, kl.data(), kl.size() * sizeof(int));
     return (int32_t)(kl.size() / (size_t)stride);
+}
+
+int surfh_route_decide(int32_t n_alpha, int32_t n_beta, int32_t n_templates, int64_t lp, int32_t verify, int32_t exact, int32_t has_sotf,
+                       uint32_t switches, int32_t scan, int64_t out[8]) {
+    if (!out || n_alpha < 2 || n_beta < 2 || n_templates < 0 || lp < 128 || lp % 128 || scan < 0 || scan > 2) return fail("surfh_route_decide: bad arguments");
+    RouteInput in;
+    in.Na = n_alpha; in.Nb = n_beta; in.T = n_templates; in.NAP = pad64(n_alpha); in.KBP = pad64(n_beta / 2 + 1); in.LP = lp;
+    in.verify = verify != 0; in.has_sotf = has_sotf != 0; in.exact = exact; in.switches = switches;
+    route_fields(decide_route(in, (OtfSupport)scan), out);
+    return 0;
 }
 
 int surfh_launch_geometry(const char *which, int64_t a, int64_t b, int64_t c, int64_t out[4]) {

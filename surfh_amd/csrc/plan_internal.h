@@ -134,6 +134,39 @@ struct ProfRec {
     hipEvent_t a, b;
 };
 
+// ---- the route of a plan: which transform kernels run and which fusions ride on them, decided in one place (decide_route, plan.hip).
+// Operators read its fields, never the buffers, to learn their mode.  DESIGN.md ("The route of a plan"): what sets each field and
+// which stages it switches.
+enum AxisKernel { AX_DENSE = 0, AX_H2 = 1, AX_CT = 2 };                 // dense fp32 products, dft_h2.h, dft_ct.h
+enum OtfSupport { OTF_NONE = 0, OTF_LISTS = 1, OTF_LISTS_RANGES = 2 };
+// the SURFH_<name> switches that feed the route, in the order of the bits of RouteInput::switches (and of surfh_route_decide)
+enum RouteSwitch { SW_DFT_H2, SW_DFT_CT, SW_DFT_DENSE, SW_NO_FUSED_MIX, SW_ADJ_FUSED, SW_OTF_PROD, SW_OTF_SUPPORT, SW_OTF_RANGES, SW_COUNT };
+struct RouteInput {
+    int Na = 0, Nb = 0, T = 0, exact = 0;         // exact: surfh_config.exact
+    long NAP = 0, KBP = 0, LP = 0;
+    bool verify = false, has_sotf = false;
+    unsigned switches = 0;
+    bool on(RouteSwitch s) const { return (switches >> s & 1u) != 0; }
+};
+struct Route {
+    AxisKernel ax_a = AX_DENSE, ax_b = AX_DENSE;      // the kernel of each axis; both or neither DENSE
+    bool mix = false;              // forward: spectral mix x OTF in the loader of the first inverse pass
+    bool prod = false;             // plane-wise plans: the OTF products in the loader of the first inverse pass
+    bool fused_tail = false;       // adjoint: conj(OTF) x and the reduction over the wavelengths inside the last forward pass
+    bool scan_otf = false;         // plan creation looks for the OTF's support; what it finds completes the route:
+    OtfSupport support = OTF_NONE; // the mix loader and the adjoint's tail pass over the super-tiles (LISTS) and the k-steps / rows (RANGES) outside
+    bool tpl_spectral = false;     // template transpose: reduction over the frequency bins (else over the pixels)
+    bool spec_calls = false;       // spectral-domain entry points available (surfh_spec_supported adds the run-time prior_kind)
+    bool interleaved() const { return ax_a != AX_DENSE; }
+    bool any_ct() const { return ax_a == AX_CT || ax_b == AX_CT; }
+};
+Route decide_route(const RouteInput &in, OtfSupport scan);
+// the fields as integers, in the order surfh_route_decide and surfh_debug_dims("route" / "route2") report them
+inline void route_fields(const Route &r, int64_t f[8]) {
+    const int64_t v[8] = {r.ax_a, r.ax_b, r.mix, r.prod, r.fused_tail, r.support, r.tpl_spectral, r.spec_calls};
+    std::copy(v, v + 8, f);
+}
+
 }  // namespace surfh_impl
 
 using namespace surfh_impl;      // struct surfh_plan is the C ABI's opaque type and stays at global scope
@@ -191,9 +224,8 @@ struct surfh_plan : PlanHandles {
     bool gather_sorted = true;                   // gather rows ordered by cube location (L2 reuse across pointings)
     bool gemm_grouped = true;                    // the adjoint's spectral-blur GEMMs of up to four channels as one launch (SURFH_GEMM_GROUPED=0: one each)
     bool scatter_grouped = true;                 // adjoint scatter with SCATTER_G neighbouring pixels per workgroup (GroupTable)
-    bool otf_prod = true;                        // plane-wise model: OTF products inside the loader of the inverse transform (SURFH_OTF_PROD=0: own kernels)
     bool gather_grouped = true;                  // forward gather (fp16 output) likewise
-    bool dense_dft = false, fuse_mix = true, wblur_fp32 = false;
+    bool wblur_fp32 = false;
     // surfh_config.verify: every long sum accumulated in float64 (dense DFT products, spectral blur, adjoint spectral mix,
     // gather / scatter rows) -- the strict dot test; storage stays fp32
     bool verify = false;
@@ -201,33 +233,23 @@ struct surfh_plan : PlanHandles {
     // surfh_set_potential: the potential of the spatial prior (maps, planes, the cube's rows / columns), of the cube's spectral
     // prior and of the robust data term; 0 Huber, 1 hyperbolic, 2 Hebert-Leahy (huber_dev.h)
     int pot[3] = {0, 0, 0};
-    // two-piece fp16 passes with LDS-resident matrices (dft_h2.h): the plan's complex arrays (sotf, spec, ycol, and
-    // mhat when T == 0) are then INTERLEAVED [..][LP][2] instead of planar [2][..][LP]
-    bool h2 = false;
-    DevBuf<unsigned short> h2img;                // three images: (Cma, Sma), (Gc, Gs), (Cf, Sf)
-    // Cooley-Tukey passes (dft_ct.h) for lengths whose folded matrix does not fit LDS (N = R * M: 501, 512, ...); same
-    // interleaved layout.  ilv = h2 || ct is the layout flag of the complex arrays.
-    bool ct = false, ilv = false;
-    DftCtPlan ctA, ctB_own;                      // transform lengths Na / Nb; ctB_own stays empty when they are equal
+    // which transform kernels run and which fusions ride on them: written once, by surfh_plan_create from decide_route.  On an
+    // interleaved route the plan's complex arrays (sotf, spec, ycol*, and mhat when T == 0) are [..][LP][2] instead of planar [2][..][LP]
+    Route route;
+    DevBuf<unsigned short> h2img;                // dft_h2's three LDS images: (Cma, Sma), (Gc, Gs), (Cf, Sf)
+    DftCtPlan ctA, ctB_own;                      // dft_ct: transform lengths Na / Nb; ctB_own stays empty when they are equal
     const DftCtPlan *ctB = &ctB_own;             // view: the plan that serves beta (&ctA when Nb == Na)
-    // which kernel transforms an axis: the choice is per axis (a 300 x 64 image runs dft_ct along alpha and dft_h2 along beta);
-    // h2 = both axes on dft_h2 (fused adjoint tail, OTF-support lists), ct = at least one axis on dft_ct.  An axis neither covers
-    // (a prime factor above 190, fewer than 32 points) puts the plan on the dense fp32 products with planar arrays.
-    int ax_a = 0, ax_b = 0;                      // 0: none, 1: dft_h2, 2: dft_ct
     // cube columns alpha in [a_lo, a_hi) hold every pixel any channel's tables touch: the transform passes that are batched
     // over alpha skip the rest (forward: the cube outside is never read; adjoint: it is zero).  ycol_adj: the adjoint's
-    // intermediate in its own buffer, whose columns outside the range stay zero from plan creation on.
+    // intermediate in its own buffer (interleaved routes with a proper sub-range), whose columns outside stay zero from plan creation on.
     int a_lo = 0, a_hi = 0, b_lo = 0, b_hi = 0;  // (b: the same for the cube rows beta)
     DevBuf<float> ycol_adj;
-    DevBuf<float> adjmix_part;                   // fused adjoint tail (dft_h2_adjmix_kernel): partial sums per (k_beta, slot); null: off
-    // Support of the OTF (otf_support below): the (k_beta, chunk of 128 wavelengths) pairs -- super-tiles of the two passes that
-    // touch the OTF, index k_beta * (LP / 128) + chunk -- in which some |sotf| exceeds 2^-24 of its plane's largest magnitude.
-    // The forward's complex pass and the fused adjoint tail visit only these; otf_kbstart[kb] = first list position of kb.
-    // ycol_mix: the forward's intermediate in its own buffer, whose other tiles stay zero from plan creation on.
+    DevBuf<float> adjmix_part;                   // route.fused_tail: partial sums per (k_beta, slot) of dft_h2_adjmix_kernel
+    // route.support (otf_support, plan.hip): the list of super-tiles k_beta * (LP / 128) + chunk inside the OTF's support,
+    // otf_kbstart[kb] = first list position of kb; ycol_mix: the forward's intermediate, whose other tiles stay zero from plan
+    // creation on; otf_tabs (LISTS_RANGES): per chunk of 128 wavelengths the k-steps / last rows inside the support, [3 or 4][LP / 128]
     DevBuf<int> otf_vlist, otf_kbstart;
     int otf_nvalid = 0;
-    // per chunk of 128 wavelengths: k-steps of the forward's complex pass (k_alpha inside the support), k-steps of its pass along
-    // beta (k_beta inside: the rest of ycol_mix is zero), rows k_beta the adjoint's first pass has to store: [3][LP / 128]
     DevBuf<int> otf_tabs;
     DevBuf<float> ycol_mix;
     int h2kA[3] = {0, 0, 0};
@@ -358,7 +380,6 @@ int build_klist(const float *B, int N, int K, long ldb, int segLinP, int segChun
                 int *stride, long *n_near, long *n_far, int permP = 0, int permLin = 0);
 // plan_ops.hip
 int prior_add(surfh_plan *p, hipStream_t st, const float *d, float *q, int n_img, float mu_reg);
-bool prod_capable(const surfh_plan *p);
 int forward_dev(surfh_plan *p, const float *x, float *y, const OpCall &c = {});
 int adjoint_dev(surfh_plan *p, const float *y, float *x, const OpCall &c = {});
 int normal_halves(surfh_plan *p, const float *v, float *q, OpCall c = {});        // A^T W A v, head and tail those of `c`

@@ -115,150 +115,9 @@ int irfft2_lam(surfh_plan *p, const float *src, float *dst) {
     return 0;
 }
 
-// ---- two-piece fp16 passes, matrices resident in LDS, interleaved complex arrays (dft_h2.h) --------
-// cube [NBP][NAP][LP] -> spec [KAP][KBP][LP][2]        (tmp ycol viewed as Z[KBP][NAP][LP][2])
-// `madj` != nullptr: the second pass does not store the spectrum but multiplies it by conj(sotf) and reduces it over the
-// wavelengths with the template weights straight into madj [T][2][KAP][KBP] (the adjoint's tail, spectroModel.py:175-181)
-// `acols`: the source cube is zero outside the alpha range [a_lo, a_hi) (the adjoint's accumulator): the first pass
-// transforms only those columns, into ycol_adj whose other columns are zero for good
-// `which`: bit 0 = the pass along beta, bit 1 = the pass along alpha (plans whose axes run on different kernels call one of each)
-// `scaled`: madj is the solver's scaled half spectrum (OpCall::T_SPECTRA): its mu and quadratic prior ride on the tail
-int rfft2_lam_h2(surfh_plan *p, const float *src, float *dst, float *madj = nullptr, bool acols = false, int which = 3,
-                 const OpCall *scaled = nullptr) {
-    const long LP = p->LP;
-    const int ha = p->Na / 2 + 1, hb = p->Nb / 2 + 1;
-    const bool sub = acols && p->ycol_adj && p->a_hi > p->a_lo;
-    float *const yc = sub ? p->ycol_adj : p->ycol;
-    const int a0 = sub ? p->a_lo : 0, na = sub ? p->a_hi - p->a_lo : p->Na;
-    // in front of the fused tail the pass runs over the planes that exist (Leff, plan_internal.h): the source's planes beyond are
-    // zero and so is their place in the intermediate, for good; the other callers may hand in any vector and get every plane of LP.
-    // The tail itself keeps LP: its workgroups take equal counts of super-tiles and only some ranges hold a padded chunk, so
-    // passing those tiles over (measured) leaves the slowest workgroup, and the launch, where it was.
-    const int Lrun = madj ? p->Leff : (int)LP;
-    DftH2Args g;   // r2c along beta, batched over alpha
-    g.kind = 1; g.src = src + (long)a0 * LP; g.ldb = p->NAP * LP; g.sB = LP; g.Kn = p->Nb;
-    g.dst = yc + 2 * (long)a0 * LP; g.ldc = 2 * p->NAP * LP; g.sC = 2 * LP; g.e[0] = 1.f; g.e[3] = -1.f; g.rvalid = hb;
-    g.KP = p->KPb; g.N = Lrun; g.batch = na;
-    // fused tail with the OTF's support: it reads no k_beta beyond the support of a wavelength chunk, so those rows are not stored
-    if (madj && p->otf_vlist && p->ycol_mix && p->otf_tabs) { g.rtab = p->otf_tabs + 2 * (LP / 128); g.tabLP = (int)LP; }
-    if (which & 1) {
-        Prof pr(p, "dft_h2_rows_fwd");
-        LAUNCH_OK(launch_dft_h2(p->stream, g, p->h2img + 2 * DFT_H2_IMAGE_HALFS, p->h2kA[2]));
-    }
-    if (!(which & 2)) return 0;
-    DftH2Args h;   // c2c along alpha, batched over k_beta
-    h.kind = 0; h.src = yc; h.ldb = 2 * LP; h.sB = 2 * p->NAP * LP; h.Kn = p->Na;
-    h.dst = dst; h.ldc = 2 * p->KBP * LP; h.sC = 2 * LP; h.Rn = p->Na; h.rvalid = ha;
-    h.KP = p->KPa; h.N = (int)LP; h.batch = hb;
-    h.e[0] = 1.f; h.e[1] = 1.f; h.e[2] = 1.f; h.e[3] = -1.f;                 // Re Z[r] = C ae + S bo, Re Z[N-r] = C ae - S bo
-    h.e_alt[0] = 1.f; h.e_alt[1] = -1.f; h.e_alt[2] = 1.f; h.e_alt[3] = 1.f;  // Im Z[r] = C be - S ao, Im Z[N-r] = C be + S ao
-    if (madj) {
-        DftH2AdjMix am;
-        am.hsrc = p->sotf; am.ldh = 2 * p->KBP * LP; am.sH = 2 * LP; am.tpl = p->tpl; am.T = p->T; am.LPt = (int)LP; am.mpart = p->adjmix_part;
-        if (p->otf_vlist && p->ycol_mix) { am.vlist = p->otf_vlist; am.kbstart = p->otf_kbstart; am.nvalid = p->otf_nvalid; }
-        if (sub) {       // rows alpha < a_lo and alpha >= a_hi of the intermediate are zero: leading k-steps (rows k, Na - k) without a non-zero row
-            int kt0 = 0;
-            while (16 * kt0 + 15 < p->a_lo && p->Na - (16 * kt0 + 15) >= p->a_hi && h.KP / 16 - (kt0 + 1) >= 5) ++kt0;
-            am.kt0 = kt0;
-        }
-        if (scaled) {
-            am.out_self = (float)scaled->mu; am.out_pair = (float)scaled->mu * 1.41421356237309505f; am.Nb = p->Nb;
-            am.prior_src = scaled->prior_src; am.prior_mu = (float)scaled->prior_mu;
-        }
-        Prof pr(p, "dft_h2_cols_fwd_adjmix");
-        LAUNCH_OK(launch_dft_h2_adjmix(p->stream, h, am, madj, p->PL, p->KBP, p->h2img, p->h2kA[0]));
-        return 0;
-    }
-    {
-        Prof pr(p, "dft_h2_cols_fwd");
-        LAUNCH_OK(launch_dft_h2(p->stream, h, p->h2img, p->h2kA[0]));
-    }
-    return 0;
-}
-
-// spec [KAP][KBP][LP][2] -> cube [NBP][NAP][LP]        (tmp ycol viewed as Y[NAP][KBP][LP][2])
-// `acols`: only the cube columns alpha in [a_lo, a_hi) are wanted (the gathers read nothing else)
-// `mix`: the maps' spectra the loader of the first pass mixes (null: none) -- the plan's mhat, or the solver's scaled half spectra
-int irfft2_lam_h2(surfh_plan *p, const float *src, float *dst, const float *mix, bool acols = false, int which = 3) {
-    const long LP = p->LP;
-    const int ha = p->Na / 2 + 1, hb = p->Nb / 2 + 1;
-    DftH2Args g;   // c2c along alpha (optionally with the spectral mix formed in the loader)
-    g.kind = 0; g.src = src; g.ldb = 2 * p->KBP * LP; g.Kn = p->Na;
-    g.dst = p->ycol; g.ldc = 2 * p->KBP * LP; g.Rn = p->Na; g.rvalid = ha;
-    g.KP = p->KPa; g.N = (int)(hb * LP);
-    g.e[0] = 1.f; g.e[1] = -1.f; g.e[2] = 1.f; g.e[3] = 1.f;
-    g.e_alt[0] = 1.f; g.e_alt[1] = 1.f; g.e_alt[2] = 1.f; g.e_alt[3] = -1.f;
-    if (mix) { g.mhat = mix; g.tpl = p->tpl; g.T = p->T; g.LP = (int)p->LP; g.PL = p->PL; g.KBP = p->KBP; }
-    if (mix && mix != p->mhat) { g.mhat_self = 1.f; g.mhat_pair = 0.70710678118654752f; g.mix_Nb = p->Nb; }
-    // the OTF's support: tiles outside it are neither computed nor stored -- their place in ycol_mix is zero for good
-    const bool supp = mix && p->otf_vlist && p->ycol_mix && p->adjmix_part;
-    float *const yc = supp ? p->ycol_mix : p->ycol;
-    if (supp) { g.vlist = p->otf_vlist; g.nvalid = p->otf_nvalid; g.dst = yc; }
-    if (supp && p->otf_tabs) { g.ktab = p->otf_tabs; g.tabLP = (int)LP; }          // k_alpha beyond the support: not read
-    // the fused forward runs over the planes that exist (Leff, plan_internal.h): sotf and tpl are zero beyond, the gathers read
-    // nothing there.  The complex pass keeps its super-tiles of 128 planes of one k_beta (one mix table per super-tile) and marks
-    // the tiles beyond Leff as padding; the pass along beta is launched over Leff planes.
-    const int Lrun = mix ? p->Leff : (int)LP;
-    if (Lrun < LP) { g.Nv = Lrun; g.NvP = (int)LP; }
-    if (which & 2) {
-        Prof pr(p, mix ? "dft_h2_cols_inv_mix" : "dft_h2_cols_inv");
-        LAUNCH_OK(launch_dft_h2(p->stream, g, p->h2img, p->h2kA[0]));
-    }
-    if (!(which & 1)) return 0;
-    const bool sub = acols && p->a_hi > p->a_lo;
-    const int a0 = sub ? p->a_lo : 0, na = sub ? p->a_hi - p->a_lo : p->Na;
-    DftH2Args h;   // c2r along beta, batched over alpha: cube[b] = Gc Yr - Gs Yi, cube[N-b] = Gc Yr + Gs Yi
-    h.kind = 2; h.src = yc + (long)a0 * 2 * p->KBP * LP; h.ldb = 2 * LP; h.sB = 2 * p->KBP * LP;
-    h.dst = dst + (long)a0 * LP; h.ldc = p->NAP * LP; h.sC = LP;
-    h.e[0] = 1.f; h.e[1] = -1.f; h.e[2] = 1.f; h.e[3] = 1.f; h.Rn = p->Nb; h.rvalid = hb;
-    h.KP = p->KPb; h.N = Lrun; h.batch = na;
-    if (supp && p->otf_tabs) { h.ktab = p->otf_tabs + LP / 128; h.tabLP = (int)LP; }   // k_beta beyond the support: zero in ycol_mix
-    {
-        Prof pr(p, "dft_h2_rows_inv");
-        LAUNCH_OK(launch_dft_h2(p->stream, h, p->h2img + DFT_H2_IMAGE_HALFS, p->h2kA[1]));
-    }
-    return 0;
-}
-
-// ---- Cooley-Tukey passes (dft_ct.h): the same four passes for N = R * M, interleaved complex arrays ---------------
-// cube [NBP][NAP][LP] -> spec [KAP][KBP][LP][2]        (tmp ycol viewed as Z[KBP][NAP][LP][2])
-// `lists`: the caller is the adjoint's tail, whose reduction reads the spectrum only inside the OTF's support
-int rfft2_lam_ct(surfh_plan *p, const float *src, float *dst, bool acols = false, bool lists = false, int which = 3) {
-    const long LP = p->LP;
-    const int hb = p->Nb / 2 + 1;
-    const bool sub = acols && p->ycol_adj && p->a_hi > p->a_lo;
-    float *const yc = sub ? p->ycol_adj : p->ycol;
-    const int a0 = sub ? p->a_lo : 0, na = sub ? p->a_hi - p->a_lo : p->Na;
-    DftCtArgs g;   // r2c along beta: neighbouring wavelengths as packed pairs a + i b, separated in the epilogue
-    g.R = p->ctB->R; g.M = p->ctB->M; g.loader = DFT_CT_PLAIN; g.epi = DFT_CT_HSEP; g.sgn = -1.f;
-    g.scale = (float)(0.5 / std::sqrt((double)p->Nb));
-    g.src = src + (long)a0 * LP; g.ldb = p->NAP * LP;
-    g.dst = yc + 2 * (long)a0 * LP; g.ldc = 2 * p->NAP * LP;
-    g.ncols = (int)(na * LP / 2); g.batch = 1;
-    // the reduction reads no k_beta beyond the support of a wavelength chunk: those rows are not stored (chunks of 64 packed pairs)
-    const bool supp = lists && p->otf_vlist && p->ycol_mix && p->otf_tabs && p->T > 0;
-    if (supp) { g.rtab = p->otf_tabs + 2 * (LP / 128); g.tabLP = (int)(LP / 2); g.tabShift = 6; }
-    if (which & 1) {
-        Prof pr(p, "dft_ct_rows_fwd");
-        LAUNCH_OK(launch_dft_ct(p->stream, g, *p->ctB));
-    }
-    if (!(which & 2)) return 0;
-    DftCtArgs h;   // c2c along alpha, batched over k_beta
-    h.R = p->ctA.R; h.M = p->ctA.M; h.loader = DFT_CT_PLAIN; h.epi = DFT_CT_STORE; h.sgn = -1.f;
-    h.scale = (float)(1.0 / std::sqrt((double)p->Na));
-    h.src = yc; h.ldb = 2 * LP; h.sB = 2 * p->NAP * LP;
-    h.dst = dst; h.ldc = 2 * p->KBP * LP; h.sC = 2 * LP;
-    h.ncols = (int)LP; h.batch = hb;
-    if (supp) {       // only the (k_beta, wavelength chunk) super-tiles and the rows k_alpha inside the OTF's support
-        h.vlist = p->otf_vlist; h.nvalid = p->otf_nvalid;
-        h.rtab = p->otf_tabs + 3 * (LP / 128); h.tabLP = (int)LP;
-    }
-    {
-        Prof pr(p, "dft_ct_cols_fwd");
-        LAUNCH_OK(launch_dft_ct(p->stream, h, p->ctA));
-    }
-    return 0;
-}
+// ---- the 2-D transforms on interleaved complex arrays: a pass along beta and a pass along alpha, each on the kernel of its axis
+// (Route::ax_a / ax_b) -- dft_h2 (two-piece fp16, matrices resident in LDS, dft_h2.h) or dft_ct (Cooley-Tukey, N = R M, dft_ct.h).
+// One pass function per (kernel, axis, direction); rfft2_cube / irfft2_cube work out what the two passes share and compose them.
 
 // element-wise product formed in the loader of the first inverse pass (dft_ct.h, loader PROD): src * prod (sign +1) or
 // src * conj(prod) (-1), times `scale` -- the plane-wise path's OTF product without its own kernel and array
@@ -270,103 +129,242 @@ struct ProdOperand {
     const float *add = nullptr;
     float add_w = 0.f;
 };
-}  // namespace
 
-// the complex pass along alpha runs on the kernel that has the PROD loader (SURFH_OTF_PROD=0: the separate product kernels)
-bool prod_capable(const surfh_plan *p) { return p->otf_prod && p->T == 0 && p->ilv && !p->dense_dft && p->ax_a == 2; }
+// what a caller asks of cube [NBP][NAP][LP] -> spec [KAP][KBP][LP][2]; the defaults are the plain transform
+struct RfftCall {
+    bool zero_outside_alpha = false;        // the source is zero outside the alpha range [a_lo, a_hi) (the adjoint's accumulator)
+    bool support_only = false;              // only the OTF's support of the spectrum is read afterwards (the adjoint's reductions)
+    // fused tail (Route::fused_tail): the pass along alpha does not store the spectrum but multiplies it by conj(sotf) and reduces
+    // it over the wavelengths with the template weights straight into tail_out [T][2][KAP][KBP] (spectroModel.py:175-181);
+    // tail_scaled: tail_out is the solver's scaled half spectrum (OpCall::T_SPECTRA), its mu and quadratic prior ride on the tail
+    float *tail_out = nullptr;
+    const OpCall *tail_scaled = nullptr;
+};
+// what a caller asks of spec [KAP][KBP][LP][2] -> cube [NBP][NAP][LP]
+struct IrfftCall {
+    const float *mix = nullptr;             // the maps' spectra the loader of the first pass mixes: the plan's mhat, or the solver's scaled half spectra
+    const ProdOperand *prod = nullptr;      // ... or the product it forms (Route::prod)
+    bool alpha_range_only = false;          // only the cube columns alpha in [a_lo, a_hi) are wanted (the gathers read nothing else)
+};
+// what the two passes of one transform share
+struct PassShare {
+    float *mid = nullptr;       // the intermediate: ycol, or ycol_adj / ycol_mix with their parts that are zero for good (plan_internal.h)
+    int a0 = 0, na = 0;         // the alpha columns [a0, a0 + na) the pass along beta is batched over
+    // planes the dft_h2 passes beside a fusion run over: Leff (plan_internal.h) in front of the fused tail and behind the mix loader,
+    // every plane for any other caller.  The tail itself keeps LP: its workgroups take equal counts of super-tiles and only some
+    // ranges hold a padded chunk, so passing those tiles over (measured) leaves the slowest workgroup, and the launch, where it was.
+    int Lrun = 0;
+    bool lists = false;         // the OTF's support applies: super-tiles outside it are neither computed nor stored
+    bool ranges = false;        // ... and the k-steps / rows beyond the support of a wavelength chunk are not read / stored (otf_tabs)
+};
 
-namespace {
-
-// spec [KAP][KBP][LP][2] -> cube [NBP][NAP][LP]        (tmp ycol viewed as Y[NAP][KBP][LP][2])
-int irfft2_lam_ct(surfh_plan *p, const float *src, float *dst, const float *mix, bool acols = false, int which = 3, const ProdOperand *po = nullptr) {
+// r2c along beta, batched over alpha
+int h2_rows_fwd(surfh_plan *p, const float *src, const PassShare &s) {
+    const long LP = p->LP;
+    DftH2Args g;
+    g.kind = 1; g.src = src + (long)s.a0 * LP; g.ldb = p->NAP * LP; g.sB = LP; g.Kn = p->Nb;
+    g.dst = s.mid + 2 * (long)s.a0 * LP; g.ldc = 2 * p->NAP * LP; g.sC = 2 * LP; g.e[0] = 1.f; g.e[3] = -1.f; g.rvalid = p->Nb / 2 + 1;
+    g.KP = p->KPb; g.N = s.Lrun; g.batch = s.na;
+    if (s.ranges) { g.rtab = p->otf_tabs + 2 * (LP / 128); g.tabLP = (int)LP; }
+    Prof pr(p, "dft_h2_rows_fwd");
+    LAUNCH_OK(launch_dft_h2(p->stream, g, p->h2img + 2 * DFT_H2_IMAGE_HALFS, p->h2kA[2]));
+    return 0;
+}
+// c2c along alpha, batched over k_beta -- or the fused tail in its place
+int h2_cols_fwd(surfh_plan *p, float *dst, const PassShare &s, const RfftCall &c) {
+    const long LP = p->LP;
+    DftH2Args h;
+    h.kind = 0; h.src = s.mid; h.ldb = 2 * LP; h.sB = 2 * p->NAP * LP; h.Kn = p->Na;
+    h.dst = dst; h.ldc = 2 * p->KBP * LP; h.sC = 2 * LP; h.Rn = p->Na; h.rvalid = p->Na / 2 + 1;
+    h.KP = p->KPa; h.N = (int)LP; h.batch = p->Nb / 2 + 1;
+    h.e[0] = 1.f; h.e[1] = 1.f; h.e[2] = 1.f; h.e[3] = -1.f;                 // Re Z[r] = C ae + S bo, Re Z[N-r] = C ae - S bo
+    h.e_alt[0] = 1.f; h.e_alt[1] = -1.f; h.e_alt[2] = 1.f; h.e_alt[3] = 1.f;  // Im Z[r] = C be - S ao, Im Z[N-r] = C be + S ao
+    if (!c.tail_out) {
+        Prof pr(p, "dft_h2_cols_fwd");
+        LAUNCH_OK(launch_dft_h2(p->stream, h, p->h2img, p->h2kA[0]));
+        return 0;
+    }
+    DftH2AdjMix am;
+    am.hsrc = p->sotf; am.ldh = 2 * p->KBP * LP; am.sH = 2 * LP; am.tpl = p->tpl; am.T = p->T; am.LPt = (int)LP; am.mpart = p->adjmix_part;
+    if (s.lists) { am.vlist = p->otf_vlist; am.kbstart = p->otf_kbstart; am.nvalid = p->otf_nvalid; }
+    if (s.na < p->Na) {      // rows alpha < a_lo and alpha >= a_hi of the intermediate are zero: leading k-steps (rows k, Na - k) without a non-zero row
+        int kt0 = 0;
+        while (16 * kt0 + 15 < p->a_lo && p->Na - (16 * kt0 + 15) >= p->a_hi && h.KP / 16 - (kt0 + 1) >= 5) ++kt0;
+        am.kt0 = kt0;
+    }
+    if (c.tail_scaled) {
+        am.out_self = (float)c.tail_scaled->mu; am.out_pair = (float)c.tail_scaled->mu * 1.41421356237309505f; am.Nb = p->Nb;
+        am.prior_src = c.tail_scaled->prior_src; am.prior_mu = (float)c.tail_scaled->prior_mu;
+    }
+    Prof pr(p, "dft_h2_cols_fwd_adjmix");
+    LAUNCH_OK(launch_dft_h2_adjmix(p->stream, h, am, c.tail_out, p->PL, p->KBP, p->h2img, p->h2kA[0]));
+    return 0;
+}
+// c2c along alpha (optionally with the spectral mix formed in the loader)
+int h2_cols_inv(surfh_plan *p, const float *src, const PassShare &s, const IrfftCall &c) {
     const long LP = p->LP;
     const int hb = p->Nb / 2 + 1;
-    DftCtArgs g;   // c2c along alpha (optionally with the spectral mix formed in the loader)
-    g.R = p->ctA.R; g.M = p->ctA.M; g.loader = mix ? DFT_CT_MIX : DFT_CT_PLAIN; g.epi = DFT_CT_STORE; g.sgn = 1.f;
-    g.scale = (float)(1.0 / std::sqrt((double)p->Na));
-    g.src = src; g.ldb = 2 * p->KBP * LP;
-    g.dst = p->ycol; g.ldc = 2 * p->KBP * LP;
-    g.ncols = (int)(hb * LP); g.batch = 1;
-    if (mix) { g.mhat = mix; g.tpl = p->tpl; g.T = p->T; g.LP = (int)p->LP; g.PL = p->PL; g.KBP = p->KBP; }
-    if (mix && mix != p->mhat) { g.mhat_self = 1.f; g.mhat_pair = 0.70710678118654752f; g.mix_Nb = p->Nb; }
-    if (po && po->prod && !mix) {
-        g.loader = DFT_CT_PROD; g.prod = po->prod; g.ldp = g.ldb; g.sP = 0; g.prod_sign = po->sign; g.scale *= po->scale;
-        if (po->add && po->add_w != 0.f) {
-            g.loader = DFT_CT_PRODADD; g.add = po->add; g.add_w = po->add_w; g.add_Nb = p->Nb; g.LP = (int)p->LP;
-        }
-    }
-    // the OTF's support: tiles outside it are neither computed nor stored -- their place in ycol_mix is zero for good
-    const bool supp = mix && p->otf_vlist && p->ycol_mix && p->otf_tabs;
-    float *const yc = supp ? p->ycol_mix : p->ycol;
-    if (supp) { g.vlist = p->otf_vlist; g.nvalid = p->otf_nvalid; g.dst = yc; g.ktab = p->otf_tabs; g.tabLP = (int)LP; }
-    if (which & 2) {
-        Prof pr(p, mix ? "dft_ct_cols_inv_mix" : (g.loader == DFT_CT_PROD ? "dft_ct_cols_inv_prod" : g.loader == DFT_CT_PRODADD ? "dft_ct_cols_inv_prodadd" : "dft_ct_cols_inv"));
-        LAUNCH_OK(launch_dft_ct(p->stream, g, p->ctA));
-    }
-    if (!(which & 1)) return 0;
-    const bool sub = acols && p->a_hi > p->a_lo;
-    const int a0 = sub ? p->a_lo : 0, na = sub ? p->a_hi - p->a_lo : p->Na;
-    DftCtArgs h;   // c2r along beta, batched over alpha: two neighbouring half spectra as one Hermitian-extended complex sequence
-    h.R = p->ctB->R; h.M = p->ctB->M; h.loader = DFT_CT_HPACK; h.epi = DFT_CT_STORE; h.sgn = 1.f;
-    h.scale = (float)(1.0 / std::sqrt((double)p->Nb));
-    h.src = yc + (long)a0 * 2 * p->KBP * LP; h.ldb = 2 * LP; h.sB = 2 * p->KBP * LP;
-    h.dst = dst + (long)a0 * LP; h.ldc = p->NAP * LP; h.sC = LP;
-    h.ncols = (int)(LP / 2); h.batch = na;
-    if (supp) { h.ktab = p->otf_tabs + LP / 128; h.tabLP = (int)(LP / 2); h.tabShift = 6; }      // k_beta beyond the support: zero in ycol_mix
-    {
-        Prof pr(p, "dft_ct_rows_inv");
-        LAUNCH_OK(launch_dft_ct(p->stream, h, *p->ctB));
-    }
+    DftH2Args g;
+    g.kind = 0; g.src = src; g.ldb = 2 * p->KBP * LP; g.Kn = p->Na;
+    g.dst = s.mid; g.ldc = 2 * p->KBP * LP; g.Rn = p->Na; g.rvalid = p->Na / 2 + 1;
+    g.KP = p->KPa; g.N = (int)(hb * LP);
+    g.e[0] = 1.f; g.e[1] = -1.f; g.e[2] = 1.f; g.e[3] = 1.f;
+    g.e_alt[0] = 1.f; g.e_alt[1] = 1.f; g.e_alt[2] = 1.f; g.e_alt[3] = -1.f;
+    if (c.mix) { g.mhat = c.mix; g.tpl = p->tpl; g.T = p->T; g.LP = (int)p->LP; g.PL = p->PL; g.KBP = p->KBP; }
+    if (c.mix && c.mix != p->mhat) { g.mhat_self = 1.f; g.mhat_pair = 0.70710678118654752f; g.mix_Nb = p->Nb; }
+    if (s.lists) { g.vlist = p->otf_vlist; g.nvalid = p->otf_nvalid; }
+    if (s.ranges) { g.ktab = p->otf_tabs; g.tabLP = (int)LP; }          // k_alpha beyond the support: not read
+    // the pass keeps its super-tiles of 128 planes of one k_beta (one mix table per super-tile): tiles beyond Lrun are padding
+    if (s.Lrun < LP) { g.Nv = s.Lrun; g.NvP = (int)LP; }
+    Prof pr(p, c.mix ? "dft_h2_cols_inv_mix" : "dft_h2_cols_inv");
+    LAUNCH_OK(launch_dft_h2(p->stream, g, p->h2img, p->h2kA[0]));
+    return 0;
+}
+// c2r along beta, batched over alpha: cube[b] = Gc Yr - Gs Yi, cube[N-b] = Gc Yr + Gs Yi
+int h2_rows_inv(surfh_plan *p, float *dst, const PassShare &s) {
+    const long LP = p->LP;
+    DftH2Args h;
+    h.kind = 2; h.src = s.mid + (long)s.a0 * 2 * p->KBP * LP; h.ldb = 2 * LP; h.sB = 2 * p->KBP * LP;
+    h.dst = dst + (long)s.a0 * LP; h.ldc = p->NAP * LP; h.sC = LP;
+    h.e[0] = 1.f; h.e[1] = -1.f; h.e[2] = 1.f; h.e[3] = 1.f; h.Rn = p->Nb; h.rvalid = p->Nb / 2 + 1;
+    h.KP = p->KPb; h.N = s.Lrun; h.batch = s.na;
+    if (s.ranges) { h.ktab = p->otf_tabs + LP / 128; h.tabLP = (int)LP; }   // k_beta beyond the support: zero in ycol_mix
+    Prof pr(p, "dft_h2_rows_inv");
+    LAUNCH_OK(launch_dft_h2(p->stream, h, p->h2img + DFT_H2_IMAGE_HALFS, p->h2kA[1]));
     return 0;
 }
 
-// the two transforms on interleaved arrays, each pass on the kernel of its axis (surfh_plan::ax_a / ax_b)
-int rfft2_lam_ilv(surfh_plan *p, const float *src, float *dst, float *madj = nullptr, bool acols = false, bool lists = false) {
-    if (p->h2) return rfft2_lam_h2(p, src, dst, madj, acols);
-    if (p->ax_b == 1 ? rfft2_lam_h2(p, src, dst, nullptr, acols, 1) : rfft2_lam_ct(p, src, dst, acols, lists, 1)) return 1;
-    return p->ax_a == 1 ? rfft2_lam_h2(p, src, dst, nullptr, acols, 2) : rfft2_lam_ct(p, src, dst, acols, lists, 2);
+// r2c along beta: neighbouring wavelengths as packed pairs a + i b, separated in the epilogue
+int ct_rows_fwd(surfh_plan *p, const float *src, const PassShare &s) {
+    const long LP = p->LP;
+    DftCtArgs g;
+    g.R = p->ctB->R; g.M = p->ctB->M; g.loader = DFT_CT_PLAIN; g.epi = DFT_CT_HSEP; g.sgn = -1.f;
+    g.scale = (float)(0.5 / std::sqrt((double)p->Nb));
+    g.src = src + (long)s.a0 * LP; g.ldb = p->NAP * LP;
+    g.dst = s.mid + 2 * (long)s.a0 * LP; g.ldc = 2 * p->NAP * LP;
+    g.ncols = (int)(s.na * LP / 2); g.batch = 1;
+    // the reduction reads no k_beta beyond the support of a wavelength chunk: those rows are not stored (chunks of 64 packed pairs)
+    if (s.ranges) { g.rtab = p->otf_tabs + 2 * (LP / 128); g.tabLP = (int)(LP / 2); g.tabShift = 6; }
+    Prof pr(p, "dft_ct_rows_fwd");
+    LAUNCH_OK(launch_dft_ct(p->stream, g, *p->ctB));
+    return 0;
 }
-int irfft2_lam_ilv(surfh_plan *p, const float *src, float *dst, const float *mix = nullptr, bool acols = false, const ProdOperand *po = nullptr) {
-    if (po && p->ax_a != 2) return fail("irfft2: the product loader needs the Cooley-Tukey pass along alpha");
-    if (p->h2) return irfft2_lam_h2(p, src, dst, mix, acols);
-    if (p->ax_a == 1 ? irfft2_lam_h2(p, src, dst, mix, acols, 2) : irfft2_lam_ct(p, src, dst, mix, acols, 2, po)) return 1;
-    return p->ax_b == 1 ? irfft2_lam_h2(p, src, dst, mix, acols, 1) : irfft2_lam_ct(p, src, dst, mix, acols, 1);
+// c2c along alpha, batched over k_beta
+int ct_cols_fwd(surfh_plan *p, float *dst, const PassShare &s) {
+    const long LP = p->LP;
+    DftCtArgs h;
+    h.R = p->ctA.R; h.M = p->ctA.M; h.loader = DFT_CT_PLAIN; h.epi = DFT_CT_STORE; h.sgn = -1.f;
+    h.scale = (float)(1.0 / std::sqrt((double)p->Na));
+    h.src = s.mid; h.ldb = 2 * LP; h.sB = 2 * p->NAP * LP;
+    h.dst = dst; h.ldc = 2 * p->KBP * LP; h.sC = 2 * LP;
+    h.ncols = (int)LP; h.batch = p->Nb / 2 + 1;
+    // only the (k_beta, wavelength chunk) super-tiles and the rows k_alpha inside the OTF's support
+    if (s.lists) { h.vlist = p->otf_vlist; h.nvalid = p->otf_nvalid; }
+    if (s.ranges) { h.rtab = p->otf_tabs + 3 * (LP / 128); h.tabLP = (int)LP; }
+    Prof pr(p, "dft_ct_cols_fwd");
+    LAUNCH_OK(launch_dft_ct(p->stream, h, p->ctA));
+    return 0;
+}
+// c2c along alpha (optionally with the spectral mix, or the product, formed in the loader)
+int ct_cols_inv(surfh_plan *p, const float *src, const PassShare &s, const IrfftCall &c) {
+    const long LP = p->LP;
+    DftCtArgs g;
+    g.R = p->ctA.R; g.M = p->ctA.M; g.loader = c.mix ? DFT_CT_MIX : DFT_CT_PLAIN; g.epi = DFT_CT_STORE; g.sgn = 1.f;
+    g.scale = (float)(1.0 / std::sqrt((double)p->Na));
+    g.src = src; g.ldb = 2 * p->KBP * LP;
+    g.dst = s.mid; g.ldc = 2 * p->KBP * LP;
+    g.ncols = (int)((p->Nb / 2 + 1) * LP); g.batch = 1;
+    if (c.mix) { g.mhat = c.mix; g.tpl = p->tpl; g.T = p->T; g.LP = (int)p->LP; g.PL = p->PL; g.KBP = p->KBP; }
+    if (c.mix && c.mix != p->mhat) { g.mhat_self = 1.f; g.mhat_pair = 0.70710678118654752f; g.mix_Nb = p->Nb; }
+    if (c.prod && c.prod->prod && !c.mix) {
+        g.loader = DFT_CT_PROD; g.prod = c.prod->prod; g.ldp = g.ldb; g.sP = 0; g.prod_sign = c.prod->sign; g.scale *= c.prod->scale;
+        if (c.prod->add && c.prod->add_w != 0.f) {
+            g.loader = DFT_CT_PRODADD; g.add = c.prod->add; g.add_w = c.prod->add_w; g.add_Nb = p->Nb; g.LP = (int)p->LP;
+        }
+    }
+    if (s.lists) { g.vlist = p->otf_vlist; g.nvalid = p->otf_nvalid; }
+    if (s.ranges) { g.ktab = p->otf_tabs; g.tabLP = (int)LP; }
+    Prof pr(p, c.mix ? "dft_ct_cols_inv_mix" : (g.loader == DFT_CT_PROD ? "dft_ct_cols_inv_prod" : g.loader == DFT_CT_PRODADD ? "dft_ct_cols_inv_prodadd" : "dft_ct_cols_inv"));
+    LAUNCH_OK(launch_dft_ct(p->stream, g, p->ctA));
+    return 0;
+}
+// c2r along beta, batched over alpha: two neighbouring half spectra as one Hermitian-extended complex sequence
+int ct_rows_inv(surfh_plan *p, float *dst, const PassShare &s) {
+    const long LP = p->LP;
+    DftCtArgs h;
+    h.R = p->ctB->R; h.M = p->ctB->M; h.loader = DFT_CT_HPACK; h.epi = DFT_CT_STORE; h.sgn = 1.f;
+    h.scale = (float)(1.0 / std::sqrt((double)p->Nb));
+    h.src = s.mid + (long)s.a0 * 2 * p->KBP * LP; h.ldb = 2 * LP; h.sB = 2 * p->KBP * LP;
+    h.dst = dst + (long)s.a0 * LP; h.ldc = p->NAP * LP; h.sC = LP;
+    h.ncols = (int)(LP / 2); h.batch = s.na;
+    if (s.ranges) { h.ktab = p->otf_tabs + LP / 128; h.tabLP = (int)(LP / 2); h.tabShift = 6; }      // k_beta beyond the support: zero in ycol_mix
+    Prof pr(p, "dft_ct_rows_inv");
+    LAUNCH_OK(launch_dft_ct(p->stream, h, *p->ctB));
+    return 0;
 }
 
-// ---------------------------------------------------------------------------------------------
-// pipelines on device buffers
-// ---------------------------------------------------------------------------------------------
-int rfft2_cube(surfh_plan *p, const float *src, float *dst) { return p->dense_dft ? rfft2_lam(p, src, dst) : rfft2_lam_ilv(p, src, dst); }
-int irfft2_cube(surfh_plan *p, const float *src, float *dst, const float *mix = nullptr, bool acols = false, const ProdOperand *po = nullptr) {
-    if (po && p->dense_dft) return fail("irfft2: the product loader is not part of the dense plan");
-    return p->dense_dft ? irfft2_lam(p, src, dst) : irfft2_lam_ilv(p, src, dst, mix, acols, po);
+// ---- pipelines on device buffers ----------------------------------------------------------------
+// cube [NBP][NAP][LP] -> the plan's spectrum layout: along beta, then along alpha
+int rfft2_cube(surfh_plan *p, const float *src, float *dst, const RfftCall &c = {}) {
+    const Route &r = p->route;
+    if (!r.interleaved()) return rfft2_lam(p, src, dst);
+    const bool sub = c.zero_outside_alpha && p->a_hi - p->a_lo < p->Na;       // the range is a proper one: ycol_adj exists
+    PassShare s;
+    s.mid = sub ? p->ycol_adj : p->ycol;
+    s.a0 = sub ? p->a_lo : 0; s.na = sub ? p->a_hi - p->a_lo : p->Na;
+    s.Lrun = c.tail_out ? p->Leff : (int)p->LP;
+    s.lists = c.support_only && r.support != OTF_NONE;
+    s.ranges = c.support_only && r.support == OTF_LISTS_RANGES;
+    if (r.ax_b == AX_H2 ? h2_rows_fwd(p, src, s) : ct_rows_fwd(p, src, s)) return 1;
+    return r.ax_a == AX_H2 ? h2_cols_fwd(p, dst, s, c) : ct_cols_fwd(p, dst, s);
+}
+// the plan's spectrum layout -> cube [NBP][NAP][LP]: along alpha, then along beta
+int irfft2_cube(surfh_plan *p, const float *src, float *dst, const IrfftCall &c = {}) {
+    const Route &r = p->route;
+    if (c.prod && r.ax_a != AX_CT) return fail("irfft2: the product loader needs the Cooley-Tukey pass along alpha");
+    if (!r.interleaved()) return irfft2_lam(p, src, dst);
+    PassShare s;
+    s.lists = c.mix && r.support != OTF_NONE;
+    s.ranges = c.mix && r.support == OTF_LISTS_RANGES;
+    s.mid = s.lists ? p->ycol_mix : p->ycol;
+    s.a0 = c.alpha_range_only ? p->a_lo : 0; s.na = c.alpha_range_only ? p->a_hi - p->a_lo : p->Na;
+    s.Lrun = c.mix ? p->Leff : (int)p->LP;
+    if (r.ax_a == AX_H2 ? h2_cols_inv(p, src, s, c) : ct_cols_inv(p, src, s, c)) return 1;
+    return r.ax_b == AX_H2 ? h2_rows_inv(p, dst, s) : ct_rows_inv(p, dst, s);
 }
 
 // mhat[t] = sum_l tpl[t][l] conj(sotf[l]) rfft2(cube[l])  (T > 0), or the per-plane product (T == 0)
-// `acols`: the cube is zero outside the alpha range of the channels' tables (the adjoint's accumulator)
+// `src`: what the caller knows of the cube (the adjoint's accumulator is zero outside the alpha range of the channels' tables)
 // The result goes to mhat, or to the solver's scaled half spectra (c.tail == T_SPECTRA: mu and the quadratic prior folded in).
-int adjoint_tail(surfh_plan *p, const float *cube, bool acols = false, const OpCall &c = {}) {
+int adjoint_tail(surfh_plan *p, const float *cube, const OpCall &c = {}, RfftCall src = {}) {
+    const Route &r = p->route;
     const bool scaled = c.tail == OpCall::T_SPECTRA;
     float *const out = scaled ? c.spectra_out : p->mhat;
-    if (p->adjmix_part && p->h2 && p->T > 0) return rfft2_lam_h2(p, cube, p->spec, out, acols, 3, scaled ? &c : nullptr);
-    const bool lists = p->ct && !p->dense_dft;      // Cooley-Tukey passes: only the spectrum inside the OTF's support
-    if (lists ? rfft2_lam_ilv(p, cube, p->spec, nullptr, acols, true) : rfft2_cube(p, cube, p->spec)) return 1;
-    if (lists && prod_capable(p)) return 0;         // plane-wise: conj(OTF) x spec is formed by the loader of the inverse transform that follows
+    // the fused tail and the reduction behind a dft_ct pass read the spectrum only inside the OTF's support; the reduction behind
+    // two plain dft_h2 passes and the dense one take the transform of the whole cube
+    if (r.fused_tail || r.any_ct()) src.support_only = true;
+    else src = RfftCall();
+    if (r.fused_tail) {
+        src.tail_out = out; src.tail_scaled = scaled ? &c : nullptr;
+        return rfft2_cube(p, cube, p->spec, src);
+    }
+    if (rfft2_cube(p, cube, p->spec, src)) return 1;
+    if (r.prod) return 0;         // plane-wise: conj(OTF) x spec is formed by the loader of the inverse transform that follows
     SpecmixAdjOpt o;
     o.Na = p->Na; o.KBP = p->KBP;
     Prof pr(p, "specmix_adj");
-    if (p->T == 0 && p->ilv && c.fold) {
+    if (p->T == 0 && r.interleaved() && c.fold) {
         // plane-wise normal operator: `mhat` still holds the spectrum of the vector the forward half was applied to -- mu and the
         // quadratic prior go into the OTF product, no prior kernel and no scaling pass afterwards
         o.Nb = p->Nb; o.out_self = (float)c.mu; o.prior_src = p->mhat; o.prior_mu = (float)c.prior_mu;
         LAUNCH_OK(launch_specmix_adj(p->stream, p->spec, p->sotf, p->tpl, p->mhat, 0, p->PL, p->LP, false, 1, &o));
         return 0;
     }
-    if (!lists) {
-        LAUNCH_OK(launch_specmix_adj(p->stream, p->spec, p->sotf, p->tpl, p->mhat, p->T, p->PL, p->LP, p->verify, p->ilv));
+    if (!r.any_ct()) {
+        LAUNCH_OK(launch_specmix_adj(p->stream, p->spec, p->sotf, p->tpl, p->mhat, p->T, p->PL, p->LP, p->verify, r.interleaved()));
         return 0;
     }
-    if (p->T > 0 && p->otf_vlist && p->ycol_mix && p->otf_tabs) o.lim = p->otf_tabs + 2 * (p->LP / 128);
+    if (r.support == OTF_LISTS_RANGES) o.lim = p->otf_tabs + 2 * (p->LP / 128);
     if (scaled) {
         o.Nb = p->Nb; o.out_self = (float)c.mu; o.out_pair = (float)c.mu * 1.41421356237309505f;
         o.prior_src = c.prior_src; o.prior_mu = (float)c.prior_mu;
@@ -377,14 +375,14 @@ int adjoint_tail(surfh_plan *p, const float *cube, bool acols = false, const OpC
 
 // The template transpose's tail (tplgrad.hip): G [T][Lc] = sum over the frequency bins of conj(mhat_t) conj(sotf) rfft2(cube),
 // `cube` the adjoint's accumulator (zero outside the alpha range of the channels' tables), mhat the spectra of the maps.
-//   interleaved spectra, T <= 4: the whole half spectrum from the unfused passes without the OTF-support lists -- the fused tail
-//     never stores the last pass and the listed passes leave bins outside the support unwritten, so neither serves -- then the
-//     reduction over bins;
-//   dense transforms (verification plans among them) and T > 4: the cube-space adjoint through its OTF^T back to pixels, then the
-//     reduction over pixels against the maps themselves (`maps`, on the device).
+//   Route::tpl_spectral: the whole half spectrum from the unfused passes without the OTF-support lists -- the fused tail never
+//     stores the last pass and the listed passes leave bins outside the support unwritten -- then the reduction over bins;
+//   else: the cube-space adjoint through its OTF^T back to pixels, then the reduction over pixels against `maps` (on the device).
 int template_tail(surfh_plan *p, const float *cube, float *G, const float *maps) {
-    if (p->ilv && !p->dense_dft && p->T <= 4) {
-        if (rfft2_lam_ilv(p, cube, p->spec, nullptr, true, false)) return 1;
+    if (p->route.tpl_spectral) {
+        RfftCall src;
+        src.zero_outside_alpha = true;
+        if (rfft2_cube(p, cube, p->spec, src)) return 1;
         Prof pr(p, "tplgrad_spec");
         LAUNCH_OK(launch_tplgrad_spec(p->stream, p->spec, p->sotf, p->mhat, p->tg_part, p->tg_cidx, G, p->T, p->Lc, p->Na, p->Nb, p->KBP,
                                       p->PL, (int)p->LP));
@@ -393,7 +391,7 @@ int template_tail(surfh_plan *p, const float *cube, float *G, const float *maps)
     if (rfft2_cube(p, cube, p->spec)) return 1;
     {
         Prof pr(p, "otf_conj_mul");
-        LAUNCH_OK(launch_otf_conj_mul(p->stream, p->spec, p->sotf, p->PL, (int)p->LP, p->ilv));
+        LAUNCH_OK(launch_otf_conj_mul(p->stream, p->spec, p->sotf, p->PL, (int)p->LP, p->route.interleaved()));
     }
     if (irfft2_cube(p, p->spec, p->cube)) return 1;
     Prof pr(p, "tplgrad_pix");
@@ -422,19 +420,23 @@ int forward_dev(surfh_plan *p, const float *x, float *y, const OpCall &call) {
         }
         if (rfft2_cube(p, p->cube, p->mhat)) return 1;
     }
-    if (p->T > 0 && p->T <= 4 && p->fuse_mix && !p->dense_dft) {
+    IrfftCall inv;
+    if (p->route.mix) {
         // spectral mix x OTF fused into the loader of the first inverse pass: `spec` is never written
         // (the normal operator needs the blurred cube only where a gather reads it)
-        if (irfft2_cube(p, p->sotf, p->cube, call.head == OpCall::H_SPECTRA ? call.spectra_in : p->mhat, hand_over)) return 1;
-    } else if (prod_capable(p)) {
+        inv.mix = call.head == OpCall::H_SPECTRA ? call.spectra_in : p->mhat;
+        inv.alpha_range_only = hand_over;
+        if (irfft2_cube(p, p->sotf, p->cube, inv)) return 1;
+    } else if (p->route.prod) {
         // plane-wise model on the Cooley-Tukey passes: OTF x spectrum in the loader of the first inverse pass, `spec` is never written
         ProdOperand po;
         po.prod = p->sotf;
-        if (irfft2_cube(p, p->mhat, p->cube, nullptr, false, &po)) return 1;
+        inv.prod = &po;
+        if (irfft2_cube(p, p->mhat, p->cube, inv)) return 1;
     } else {
         {
             Prof pr(p, "specmix_fwd");
-            LAUNCH_OK(launch_specmix_fwd(s, p->mhat, p->sotf, p->tpl, p->spec, p->T, p->PL, p->LP, p->ilv));
+            LAUNCH_OK(launch_specmix_fwd(s, p->mhat, p->sotf, p->tpl, p->spec, p->T, p->PL, p->LP, p->route.interleaved()));
         }
         if (irfft2_cube(p, p->spec, p->cube)) return 1;
     }
@@ -597,7 +599,9 @@ int adjoint_dev(surfh_plan *p, const float *y, float *x, const OpCall &call) {
         if (chain(p, sB, s) || scatter(c)) return 1;
     }
     if (call.tail == OpCall::T_TEMPLATES) return template_tail(p, acc, call.tpl_out, call.tpl_maps);      // the reduction runs over the bins
-    if (adjoint_tail(p, acc, true, call)) return 1;
+    RfftCall acc_is;
+    acc_is.zero_outside_alpha = true;
+    if (adjoint_tail(p, acc, call, acc_is)) return 1;
     if (call.tail == OpCall::T_SPECTRA) return 0;         // the caller's vector is the spectrum
     if (p->T > 0) {
         if (irfft2_planes(p, p->mhat, p->maps_pad, p->T)) return 1;
@@ -607,7 +611,7 @@ int adjoint_dev(surfh_plan *p, const float *y, float *x, const OpCall &call) {
     }
     // plane-wise: straight into the caller's wavelength-innermost vector, or through the work cube into the caller's planes
     float *const out = call.tail == OpCall::T_CUBE ? x : p->cube;
-    if (prod_capable(p)) {
+    if (p->route.prod) {
         // conj(OTF) x spectrum of the accumulated cube in the loader; inside the plane-wise normal operator mu rides on the pass and
         // the quadratic prior comes in as a third operand: `mhat` still holds the spectrum of the vector the forward half was applied to
         ProdOperand po;
@@ -615,7 +619,9 @@ int adjoint_dev(surfh_plan *p, const float *y, float *x, const OpCall &call) {
         if (call.fold && call.prior_mu != 0.0 && call.mu != 0.0) {      // q = mu (A^T A d + (mu_r / mu) D^T D d)
             po.add = p->mhat; po.add_w = (float)(call.prior_mu / call.mu);
         }
-        if (irfft2_cube(p, p->spec, out, nullptr, false, &po)) return 1;
+        IrfftCall inv;
+        inv.prod = &po;
+        if (irfft2_cube(p, p->spec, out, inv)) return 1;
     } else if (irfft2_cube(p, p->mhat, out)) {
         return 1;
     }
@@ -671,7 +677,7 @@ int normal_dev(surfh_plan *p, const float *d, float *q, double mu, bool cube) {
 static int ensure_hessian(surfh_plan *p) {
     return ensure_set_with(
         [&](float *h, float *) {
-            const int rc = launch_wct_hessian(p->stream, p->sotf, p->tpl, h, p->T, p->PL, p->LP, p->ilv);
+            const int rc = launch_wct_hessian(p->stream, p->sotf, p->tpl, h, p->T, p->PL, p->LP, p->route.interleaved());
             return rc ? fail("launch_wct_hessian failed: %s", hipGetErrorString((hipError_t)rc)) : 0;
         },
         member(p->hth, (size_t)p->T * p->T * p->PL), member(p->mhat2, (size_t)p->T * 2 * p->PL));
@@ -688,15 +694,13 @@ int tpl_ensure(surfh_plan *p) {
     if (p->T < 1) return fail("template calls need a plan with templates");
     if (p->T > SURFH_MAX_TEMPLATES) return fail("template calls take at most %d templates (the plan has %d)", SURFH_MAX_TEMPLATES, p->T);
     if (p->ch.empty()) return fail("plan has no channel");
-    if (p->LP % 128 != 0) return fail("internal: the plan's planes are not padded to 128");
     if (p->tg_part) return 0;
     std::vector<int> cidx((size_t)p->Lc, -1), pidx((size_t)p->LP, -1);
     for (int c = 0; c < p->Lown; ++c)
         if (p->planes[c] >= 0) { pidx[c] = p->planes[c]; cidx[p->planes[c]] = c; }
-    const bool spectral = p->ilv && !p->dense_dft && p->T <= 4;
     const size_t nv = (size_t)p->T * p->Lc;
     return ensure_set(member(p->tg_cidx, cidx), member(p->tg_pidx, pidx), member(p->tg_keep, (size_t)p->T * p->LP),
-                      member(p->tg_part, tplgrad_part_doubles(p->T, p->Na, p->Nb, (int)p->LP, spectral)), member(p->tg_v[0], nv),
+                      member(p->tg_part, tplgrad_part_doubles(p->T, p->Na, p->Nb, (int)p->LP, p->route.tpl_spectral)), member(p->tg_v[0], nv),
                       member(p->tg_v[1], nv), member(p->tg_v[2], nv), member(p->tg_v[3], nv), member(p->tg_v[4], nv), member(p->tg_v[5], nv));
 }
 int tpl_maps_spectra(surfh_plan *p, const float *maps) {
@@ -805,7 +809,7 @@ int surfh_wct_forward(surfh_plan *p, const float *maps, float *cube) {
     HIP_OK(hipMemcpyAsync(p->io_x, maps, p->isize * sizeof(float), hipMemcpyHostToDevice, s));
     LAUNCH_OK(launch_pad_planes(s, p->io_x, p->maps_pad, p->T, p->Na, p->Nb, p->NAP, p->NBP));
     if (rfft2_planes(p, p->maps_pad, p->mhat, p->T)) return 1;
-    LAUNCH_OK(launch_specmix_fwd(s, p->mhat, p->sotf, p->tpl, p->spec, p->T, p->PL, p->LP, p->ilv));
+    LAUNCH_OK(launch_specmix_fwd(s, p->mhat, p->sotf, p->tpl, p->spec, p->T, p->PL, p->LP, p->route.interleaved()));
     if (irfft2_cube(p, p->spec, p->cube)) return 1;
     LAUNCH_OK(launch_cube_from_lam_inner(s, p->cube, p->io_cube, 0, p->Lc, p->Na, p->Nb, p->NAP, p->LP));
     HIP_OK(hipMemcpyAsync(cube, p->io_cube, (size_t)p->Lc * p->Na * p->Nb * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -882,7 +886,7 @@ int surfh_wct_expsol(surfh_plan *p, const float *cube, const double *mu_reg, con
         for (size_t i = 0; i < npl; ++i) y0[(size_t)l * npl + i] = (float)((double)src[i] - mean[l]);
     }
     std::vector<float> h0((size_t)2 * p->LP);       // the OTF at the zero frequency as the kernels read it: (re, im) of every plane
-    if (p->ilv) {
+    if (p->route.interleaved()) {
         if (hipMemcpy(h0.data(), p->sotf, h0.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return fail("copy failed");
     } else {
         std::vector<float> re((size_t)p->LP), im((size_t)p->LP);
@@ -948,7 +952,7 @@ int surfh_prior_add_dev(surfh_plan *p, const float *d, float *q, double mu_reg) 
 namespace {
 int spec_check(surfh_plan *p) {
     if (!p) return fail("null plan");
-    if (!(((p->adjmix_part && p->h2) || p->ct) && p->T > 0 && p->T <= 4 && p->fuse_mix && !p->dense_dft && !p->verify))
+    if (!p->route.spec_calls)
         return fail("spectral-domain calls need the fused transform passes (dft_h2 with the fused adjoint tail, or dft_ct)");
     HIP_OK(hipSetDevice(p->dev));
     return 0;
@@ -962,7 +966,7 @@ OpCall spec_tail(float *qt, double mu, const float *dt, double mu_reg) {
 }  // namespace
 
 int surfh_spec_supported(surfh_plan *p) {
-    return p && ((p->adjmix_part && p->h2) || p->ct) && p->T > 0 && p->T <= 4 && p->fuse_mix && !p->dense_dft && !p->verify && p->prior_kind == 0;
+    return p && p->route.spec_calls && p->prior_kind == 0;
 }
 int64_t surfh_spec_size(surfh_plan *p) { return p ? (int64_t)2 * p->T * p->PL : 0; }
 
@@ -1232,7 +1236,7 @@ int surfh_set_imager(surfh_plan *p, const surfh_imager_desc *desc) {
         std::vector<double> h((size_t)F * LP, 0.0);
         for (int f = 0; f < F; ++f) std::copy(desc->filters + (size_t)f * Lc, desc->filters + (size_t)(f + 1) * Lc, h.begin() + (size_t)f * LP);
         if (wf.upload(h)) return 1;
-        const int rc = p->ilv ? launch_imager_build_g(s, p->sotf, 2 * LP, 2, 1, p->tpl, LP, wf, LP, (int)LP, acc, F, T, p->Na, nkb, p->KBP, p->PL)
+        const int rc = p->route.interleaved() ? launch_imager_build_g(s, p->sotf, 2 * LP, 2, 1, p->tpl, LP, wf, LP, (int)LP, acc, F, T, p->Na, nkb, p->KBP, p->PL)
                               : launch_imager_build_g(s, p->sotf, LP, 1, p->PL * LP, p->tpl, LP, wf, LP, (int)LP, acc, F, T, p->Na, nkb, p->KBP, p->PL);
         if (rc) return fail("launch_imager_build_g failed: %s", hipGetErrorString((hipError_t)rc));
     } else {                 // the imager's own OTF, streamed: chunk -> the plan's padded layout (wavelength innermost) -> the same kernel

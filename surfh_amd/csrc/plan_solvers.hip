@@ -328,9 +328,9 @@ CgSpace planes_space(surfh_plan *p, float *x, double mu, double mu_reg) {
 int pn_normal(surfh_plan *p, const float *v, float *q, double *dq) {
     // with interleaved spectra and a prior weight the OTF product of the adjoint applies mu and adds the prior (adjoint_tail): the
     // two halves are called directly so that no scaling pass follows
-    // (plans whose inverse transform forms the OTF product in its loader -- prod_capable -- take mu and the prior on that pass)
-    const bool prod = prod_capable(p) && p->pl_mu != 0.0;
-    const bool fold = prod || (p->ilv && !p->dense_dft && p->pl_mu_reg != 0.0);
+    // (plans whose inverse transform forms the OTF product in its loader -- Route::prod -- take mu and the prior on that pass)
+    const bool prod = p->route.prod && p->pl_mu != 0.0;
+    const bool fold = prod || (p->route.interleaved() && p->pl_mu_reg != 0.0);
     if (fold) {
         OpCall c;
         c.head = OpCall::H_CUBE; c.tail = OpCall::T_CUBE; c.fold = true; c.mu = p->pl_mu; c.prior_mu = p->pl_mu_reg;

@@ -30,7 +30,7 @@ class MRSBlurred(Blurred2D):
     ``instr.fov.angle`` is (a rotated field of view is ``spectro_blind.MRSBlurred``)."""
 
     def __init__(self, sotf, alpha_axis, beta_axis, instr: instru.IFU, step_degree: float,
-                 pointings: instru.CoordList, *, device: int = 0, stream=None):
+                 pointings: instru.CoordList, *, device: int = 0, stream=None, exact: int = 0):
         super().__init__(sotf, alpha_axis, beta_axis, instr, step_degree, pointings)
         slices, weights = self._slit_tables()
         na, nb = self.local_im_shape
@@ -52,7 +52,7 @@ class MRSBlurred(Blurred2D):
             la, lb = np.minimum(ra, self.imshape[0] - 2), np.minimum(rb, self.imshape[1] - 2)
             i0[p], i1[p], y0[p], y1[p] = la, lb, ra - la, rb - lb
         self._set_tables(slices, weights, i0, i1, y0, y1)
-        self._create_plan(device, stream)
+        self._create_plan(device, stream, exact)
 
     def data_to_img(self, data):
         """The reference's quick-look back-projection of slit data (spectro_blind_rectangle.py:240-283; the reference's scripts

@@ -7,7 +7,9 @@ names its head (where the operand comes from: pixels, the caller's scaled half s
 template transpose, plane-wise with or without the folded prior) and everything between.  The tables below are recorded runs: they
 are the specification of which route a call takes, and a change of how the operators are told their mode (``OpCall``,
 plan_internal.h) must leave them as they are.  Each row asserts the property of its plan that puts it on its route, so that a row
-cannot quietly test another one.  Needs a real MI355X (`-m gpu`)."""
+cannot quietly test another one, and that the route the plan holds (``surfh_debug_dims(plan, "route" / "route2")``) is the one
+``surfh_route_decide`` -- the host-only call of the function plan creation calls, tests/test_route_host.py -- gives for the
+plan's shape, switches and scan outcome.  Needs a real MI355X (`-m gpu`)."""
 import ctypes as C
 import os
 import sys
@@ -69,6 +71,25 @@ def _spectral_small():
     return build_model(spec_problem("A"), with_ref=False)
 
 
+def _blurred_exact2():
+    """blurred_case(L=5, N=300) of test_gpu_variants.py with surfh_config.exact = 2."""
+    from surfh_amd import instru
+    from surfh_amd.spectro_blind_rectangle import MRSBlurred
+    from oracle import surfh_oracle as orc
+    from helpers import make_ifu
+    N, s = 300, problems.STEP_DEG
+    ax = orc.synthetic_axes(N, s)
+    spec = orc.ChannelSpec(1.0 / 3600, 1.2 / 3600, (0.0, 0.0), 0.0, 0.196, 12, 3000.0, np.linspace(7, 8, 10), "R")
+    sotf = orc.ir2fr(orc.gaussian_psf(np.linspace(7.0, 8.2, 5), problems.STEP), (N, N))
+    pts = [(0.0, 0.0), (2 * s, -3 * s), (-4 * s, 1 * s)]
+    return MRSBlurred(sotf, ax, ax, make_ifu(spec), s, instru.CoordList([instru.Coord(a, b) for a, b in pts]), exact=2)
+
+
+def _spectral_small_exact2():
+    from test_gpu_spec_vectors import spec_problem
+    return build_model(spec_problem("A"), with_ref=False, exact=2)
+
+
 def _is_mid(m):
     assert dims(m, "dft") == (1, 1, 1, 1) and m.spec_supported()       # dft_h2 on both axes, the fused adjoint tail
     assert len(m.channels) == 2 and dims(m, "groups")[1] > 0            # two channels (grouped GEMM), grouped scatter
@@ -110,6 +131,60 @@ def _is_spectral_small(m):
     assert dims(m, "dft") == (1, 1, 1, 1) and m.spec_supported() and m.ishape == (4, 127, 48)
 
 
+def _whole_spectrum(m):
+    assert dims(m, "otf")[0] in (0, dims(m, "otf")[1])                  # no super-tile of the OTF is dropped
+
+
+def _is_mid_whole_spectrum(m):
+    assert dims(m, "dft") == (1, 1, 1, 1) and m.spec_supported()        # SURFH_OTF_SUPPORT=0: the fused passes over every tile
+    _whole_spectrum(m)
+
+
+def _is_mid_lists_only(m):
+    _is_mid(m)                                                          # SURFH_OTF_RANGES=0: the lists stay, the k-ranges go
+    assert route(m)[5] == 1
+
+
+def _is_mid_tail_separate(m):
+    assert dims(m, "dft") == (1, 1, 1, 0) and not m.spec_supported()    # SURFH_ADJ_FUSED=0: no fused tail, so no lists either
+    _whole_spectrum(m)
+
+
+def _is_mid_unfused_mix(m):
+    assert dims(m, "dft") == (1, 1, 1, 1) and not m.spec_supported()    # SURFH_NO_FUSED_MIX=1: the tail stays fused, the mix does not
+    _whole_spectrum(m)
+
+
+def _is_mid_on_ct(m):
+    assert dims(m, "dft") == (2, 2, 1, 0) and m.spec_supported()        # SURFH_DFT_H2=0: 128 = 2 x 64 on dft_ct
+    assert dims(m, "otf")[0] < dims(m, "otf")[1]
+
+
+def _is_ct300_lists_only(m):
+    _is_ct300(m)
+    assert dims(m, "otf")[0] < dims(m, "otf")[1] and route(m)[5] == 0   # dft_ct takes its k-ranges with the lists, or neither
+
+
+def _is_ct300_whole_spectrum(m):
+    _is_ct300(m)
+    _whole_spectrum(m)
+
+
+def _is_mixed_planar(m):
+    _is_planar(m)                                                       # SURFH_DFT_CT=0: 300 loses its kernel, the plan goes planar
+    assert m.ishape == (4, 300, 64)
+
+
+def _is_blurred_ct_exact2(m):
+    _is_blurred_ct(m)                                                   # exact = 2 concerns the OTF's support: nothing for T = 0
+    assert route(m)[3] == 1
+
+
+def _is_spectral_small_exact2(m):
+    assert dims(m, "dft") == (1, 1, 1, 1) and m.spec_supported() and m.ishape == (4, 127, 48)
+    _whole_spectrum(m)
+
+
 PLANS = {
     "mid": ({}, _mid, _is_mid),
     "ct300": ({}, _ct300, _is_ct300),
@@ -122,7 +197,45 @@ PLANS = {
     "blurred_300": ({}, lambda: _blurred(300), _is_blurred_ct),
     "blurred_300_own_products": ({"SURFH_OTF_PROD": "0"}, lambda: _blurred(300), _is_blurred_ct),
     "spectral_small": ({}, _spectral_small, _is_spectral_small),
+    # the switch plans (every switch that feeds the route, on a plan where it changes the route)
+    "mid_whole_spectrum": ({"SURFH_OTF_SUPPORT": "0"}, _mid, _is_mid_whole_spectrum),
+    "mid_lists_only": ({"SURFH_OTF_RANGES": "0"}, _mid, _is_mid_lists_only),
+    "mid_tail_separate": ({"SURFH_ADJ_FUSED": "0"}, _mid, _is_mid_tail_separate),
+    "mid_unfused_mix": ({"SURFH_NO_FUSED_MIX": "1"}, _mid, _is_mid_unfused_mix),
+    "mid_on_dft_ct": ({"SURFH_DFT_H2": "0"}, _mid, _is_mid_on_ct),
+    "ct300_lists_only": ({"SURFH_OTF_RANGES": "0"}, _ct300, _is_ct300_lists_only),
+    "ct300_whole_spectrum": ({"SURFH_OTF_SUPPORT": "0"}, _ct300, _is_ct300_whole_spectrum),
+    "mixed_300x64_no_dft_ct": ({"SURFH_DFT_CT": "0"}, _mixed, _is_mixed_planar),
+    "blurred_300_exact2": ({}, _blurred_exact2, _is_blurred_ct_exact2),
+    "spectral_small_exact2": ({}, _spectral_small_exact2, _is_spectral_small_exact2),
 }
+CONFIG = {"config1_verify": dict(verify=1), "blurred_300_exact2": dict(exact=2), "spectral_small_exact2": dict(exact=2)}
+
+# ---- the route: what the plan holds against what the host-only decision gives for the plan's shape, switches and scan outcome ---
+SWITCHES = ("SURFH_DFT_H2", "SURFH_DFT_CT", "SURFH_DFT_DENSE", "SURFH_NO_FUSED_MIX", "SURFH_ADJ_FUSED", "SURFH_OTF_PROD",
+            "SURFH_OTF_SUPPORT", "SURFH_OTF_RANGES")                   # bit i of the mask: switch i is on
+SWITCH_DEFAULTS = 0b11110011
+
+
+def route(m):
+    """(axis alpha, axis beta, mix loader, product loader, fused tail, support, spectral template tail, spectral-domain calls)"""
+    return dims(m, "route") + dims(m, "route2")
+
+
+def check_route(name, m):
+    env = PLANS[name][0]
+    mask = SWITCH_DEFAULTS
+    for i, k in enumerate(SWITCHES):
+        if k in env:
+            mask = (mask | 1 << i) if env[k] == "1" else (mask & ~(1 << i))
+    planes = getattr(m, "templates", None) is None
+    otf = dims(m, "otf")
+    scan = 0 if otf[0] in (0, otf[1]) else (2 if mask & 1 << 7 else 1)
+    cfg = CONFIG.get(name, {})
+    out = (C.c_int64 * 8)()
+    assert m._L.surfh_route_decide(m.ishape[-2], m.ishape[-1], 0 if planes else m.ishape[0], dims(m, "trim")[1], cfg.get("verify", 0),
+                                   cfg.get("exact", 0), 1, mask, scan, out) == 0
+    assert route(m) == tuple(int(v) for v in out), (name, route(m), tuple(out))
 _plans = {}
 
 
@@ -289,12 +402,17 @@ ROWS.update({
     "disjoint_planes-fwadj": ("disjoint_planes", fwadj),
     "spectral_small-cg_nonneg": ("spectral_small", cg_nonneg),
 })
+for _p in ("mid_whole_spectrum", "mid_lists_only", "mid_on_dft_ct", "ct300_lists_only", "ct300_whole_spectrum", "spectral_small_exact2"):
+    ROWS.update({f"{_p}-forward": (_p, forward), f"{_p}-adjoint": (_p, adjoint), f"{_p}-fwadj": (_p, fwadj),
+                 f"{_p}-normal_spec_prior": (_p, lambda m: normal_spec(m, MU_REG))})
+for _p in ("mid_tail_separate", "mid_unfused_mix", "mixed_300x64_no_dft_ct"):
+    ROWS.update({f"{_p}-forward": (_p, forward), f"{_p}-adjoint": (_p, adjoint), f"{_p}-fwadj": (_p, fwadj)})
 for _p in ("config1", "config1_dense", "config1_verify"):
     ROWS.update({f"{_p}-forward": (_p, forward), f"{_p}-adjoint": (_p, adjoint), f"{_p}-adjoint_ref": (_p, adjoint_ref), f"{_p}-fwadj": (_p, fwadj),
                  f"{_p}-adjoint_templates": (_p, adjoint_templates), f"{_p}-cg_templates": (_p, cg_templates)})
-for _p in ("blurred_96", "blurred_300", "blurred_300_own_products"):
+for _p in ("blurred_96", "blurred_300", "blurred_300_own_products", "blurred_300_exact2"):
     ROWS.update({f"{_p}-forward": (_p, forward), f"{_p}-adjoint": (_p, adjoint)})
-    for _native in ("1", "0"):
+    for _native in ("1", "0") if _p != "blurred_300_exact2" else ("1",):
         for _tag, _mur in (("", 0.0), ("_prior", PL_MU_REG)):
             ROWS[f"{_p}-planes_cg_native{_native}{_tag}"] = (_p, lambda m, mp, n=_native, r=_mur: planes_cg(m, n, r, mp))
 
@@ -304,6 +422,7 @@ def run_row(row, monkeypatch):
     name, call = ROWS[row]
     m = plan(name, monkeypatch)
     PLANS[name][2](m)
+    check_route(name, m)
     try:
         out = call(m, monkeypatch) if "planes_cg" in row else call(m)
         prof = m.profile()
@@ -376,6 +495,44 @@ EXPECTED = {
     "blurred_300_own_products-planes_cg_native1_prior": {"dft_ct_cols_fwd": 7, "dft_ct_cols_inv": 7, "dft_ct_rows_fwd": 7, "dft_ct_rows_inv": 7, "pn_dir": 1, "pn_prior_dot": 3, "specmix_adj": 4, "specmix_fwd": 3, "spmm_gather_fwd": 3, "spmm_scatter_adj": 4, "y_transpose": 7},
     "blurred_300_own_products-planes_cg_native0": {"cube_transpose": 7, "dft_ct_cols_fwd": 7, "dft_ct_cols_inv": 7, "dft_ct_rows_fwd": 7, "dft_ct_rows_inv": 7, "scale": 3, "specmix_adj": 4, "specmix_fwd": 3, "spmm_gather_fwd": 3, "spmm_scatter_adj": 4, "y_transpose": 7},
     "blurred_300_own_products-planes_cg_native0_prior": {"cube_transpose": 7, "dft_ct_cols_fwd": 7, "dft_ct_cols_inv": 7, "dft_ct_rows_fwd": 7, "dft_ct_rows_inv": 7, "prior_add": 3, "scale": 3, "specmix_adj": 4, "specmix_fwd": 3, "spmm_gather_fwd": 3, "spmm_scatter_adj": 4, "y_transpose": 7},
+    # the switch plans
+    "mid_whole_spectrum-forward": {"dft_h2_cols_inv_mix": 1, "dft_h2_rows_inv": 1, "gemm_dft_cols_fwd_maps": 1, "gemm_dft_rows_fwd_maps": 1, "gemm_wblur_fwd": 2, "pad_planes": 1, "spmm_gather_fwd": 2, "y_from_cpart": 2},
+    "mid_whole_spectrum-adjoint": {"dft_h2_cols_fwd_adjmix": 1, "dft_h2_rows_fwd": 1, "gemm_dft_cols_inv_maps": 1, "gemm_dft_rows_inv_maps": 1, "gemm_wblur_adj": 1, "spmm_scatter_adj": 2, "unpad_planes": 1, "ymat_from_y": 2},
+    "mid_whole_spectrum-fwadj": {"dft_h2_cols_fwd_adjmix": 1, "dft_h2_cols_inv_mix": 1, "dft_h2_rows_fwd": 1, "dft_h2_rows_inv": 1, "gemm_dft_cols_fwd_maps": 1, "gemm_dft_cols_inv_maps": 1, "gemm_dft_rows_fwd_maps": 1, "gemm_dft_rows_inv_maps": 1, "gemm_wblur_adj": 1, "gemm_wblur_fwd": 2, "pad_planes": 1, "spmm_gather_fwd": 2, "spmm_scatter_adj": 2, "unpad_planes": 1, "ymat16_from_cpart": 2},
+    "mid_whole_spectrum-normal_spec_prior": {"dft_h2_cols_fwd_adjmix": 1, "dft_h2_cols_inv_mix": 1, "dft_h2_rows_fwd": 1, "dft_h2_rows_inv": 1, "gemm_wblur_adj": 1, "gemm_wblur_fwd": 2, "spmm_gather_fwd": 2, "spmm_scatter_adj": 2, "ymat16_from_cpart": 2},
+    "mid_lists_only-forward": {"dft_h2_cols_inv_mix": 1, "dft_h2_rows_inv": 1, "gemm_dft_cols_fwd_maps": 1, "gemm_dft_rows_fwd_maps": 1, "gemm_wblur_fwd": 2, "pad_planes": 1, "spmm_gather_fwd": 2, "y_from_cpart": 2},
+    "mid_lists_only-adjoint": {"dft_h2_cols_fwd_adjmix": 1, "dft_h2_rows_fwd": 1, "gemm_dft_cols_inv_maps": 1, "gemm_dft_rows_inv_maps": 1, "gemm_wblur_adj": 1, "spmm_scatter_adj": 2, "unpad_planes": 1, "ymat_from_y": 2},
+    "mid_lists_only-fwadj": {"dft_h2_cols_fwd_adjmix": 1, "dft_h2_cols_inv_mix": 1, "dft_h2_rows_fwd": 1, "dft_h2_rows_inv": 1, "gemm_dft_cols_fwd_maps": 1, "gemm_dft_cols_inv_maps": 1, "gemm_dft_rows_fwd_maps": 1, "gemm_dft_rows_inv_maps": 1, "gemm_wblur_adj": 1, "gemm_wblur_fwd": 2, "pad_planes": 1, "spmm_gather_fwd": 2, "spmm_scatter_adj": 2, "unpad_planes": 1, "ymat16_from_cpart": 2},
+    "mid_lists_only-normal_spec_prior": {"dft_h2_cols_fwd_adjmix": 1, "dft_h2_cols_inv_mix": 1, "dft_h2_rows_fwd": 1, "dft_h2_rows_inv": 1, "gemm_wblur_adj": 1, "gemm_wblur_fwd": 2, "spmm_gather_fwd": 2, "spmm_scatter_adj": 2, "ymat16_from_cpart": 2},
+    "mid_on_dft_ct-forward": {"dft_ct_cols_inv_mix": 1, "dft_ct_rows_inv": 1, "gemm_dft_cols_fwd_maps": 1, "gemm_dft_rows_fwd_maps": 1, "gemm_wblur_fwd": 2, "pad_planes": 1, "spmm_gather_fwd": 2, "y_from_cpart": 2},
+    "mid_on_dft_ct-adjoint": {"dft_ct_cols_fwd": 1, "dft_ct_rows_fwd": 1, "gemm_dft_cols_inv_maps": 1, "gemm_dft_rows_inv_maps": 1, "gemm_wblur_adj": 1, "specmix_adj": 1, "spmm_scatter_adj": 2, "unpad_planes": 1, "ymat_from_y": 2},
+    "mid_on_dft_ct-fwadj": {"dft_ct_cols_fwd": 1, "dft_ct_cols_inv_mix": 1, "dft_ct_rows_fwd": 1, "dft_ct_rows_inv": 1, "gemm_dft_cols_fwd_maps": 1, "gemm_dft_cols_inv_maps": 1, "gemm_dft_rows_fwd_maps": 1, "gemm_dft_rows_inv_maps": 1, "gemm_wblur_adj": 1, "gemm_wblur_fwd": 2, "pad_planes": 1, "specmix_adj": 1, "spmm_gather_fwd": 2, "spmm_scatter_adj": 2, "unpad_planes": 1, "ymat16_from_cpart": 2},
+    "mid_on_dft_ct-normal_spec_prior": {"dft_ct_cols_fwd": 1, "dft_ct_cols_inv_mix": 1, "dft_ct_rows_fwd": 1, "dft_ct_rows_inv": 1, "gemm_wblur_adj": 1, "gemm_wblur_fwd": 2, "specmix_adj": 1, "spmm_gather_fwd": 2, "spmm_scatter_adj": 2, "ymat16_from_cpart": 2},
+    "ct300_lists_only-forward": {"dft_ct_cols_inv_mix": 1, "dft_ct_rows_inv": 1, "gemm_dft_cols_fwd_maps": 1, "gemm_dft_rows_fwd_maps": 1, "gemm_wblur_fwd": 2, "pad_planes": 1, "spmm_gather_fwd": 2, "y_from_cpart": 2},
+    "ct300_lists_only-adjoint": {"dft_ct_cols_fwd": 1, "dft_ct_rows_fwd": 1, "gemm_dft_cols_inv_maps": 1, "gemm_dft_rows_inv_maps": 1, "gemm_wblur_adj": 1, "specmix_adj": 1, "spmm_scatter_adj": 2, "unpad_planes": 1, "ymat_from_y": 2},
+    "ct300_lists_only-fwadj": {"dft_ct_cols_fwd": 1, "dft_ct_cols_inv_mix": 1, "dft_ct_rows_fwd": 1, "dft_ct_rows_inv": 1, "gemm_dft_cols_fwd_maps": 1, "gemm_dft_cols_inv_maps": 1, "gemm_dft_rows_fwd_maps": 1, "gemm_dft_rows_inv_maps": 1, "gemm_wblur_adj": 1, "gemm_wblur_fwd": 2, "pad_planes": 1, "specmix_adj": 1, "spmm_gather_fwd": 2, "spmm_scatter_adj": 2, "unpad_planes": 1, "ymat16_from_cpart": 2},
+    "ct300_lists_only-normal_spec_prior": {"dft_ct_cols_fwd": 1, "dft_ct_cols_inv_mix": 1, "dft_ct_rows_fwd": 1, "dft_ct_rows_inv": 1, "gemm_wblur_adj": 1, "gemm_wblur_fwd": 2, "specmix_adj": 1, "spmm_gather_fwd": 2, "spmm_scatter_adj": 2, "ymat16_from_cpart": 2},
+    "ct300_whole_spectrum-forward": {"dft_ct_cols_inv_mix": 1, "dft_ct_rows_inv": 1, "gemm_dft_cols_fwd_maps": 1, "gemm_dft_rows_fwd_maps": 1, "gemm_wblur_fwd": 2, "pad_planes": 1, "spmm_gather_fwd": 2, "y_from_cpart": 2},
+    "ct300_whole_spectrum-adjoint": {"dft_ct_cols_fwd": 1, "dft_ct_rows_fwd": 1, "gemm_dft_cols_inv_maps": 1, "gemm_dft_rows_inv_maps": 1, "gemm_wblur_adj": 1, "specmix_adj": 1, "spmm_scatter_adj": 2, "unpad_planes": 1, "ymat_from_y": 2},
+    "ct300_whole_spectrum-fwadj": {"dft_ct_cols_fwd": 1, "dft_ct_cols_inv_mix": 1, "dft_ct_rows_fwd": 1, "dft_ct_rows_inv": 1, "gemm_dft_cols_fwd_maps": 1, "gemm_dft_cols_inv_maps": 1, "gemm_dft_rows_fwd_maps": 1, "gemm_dft_rows_inv_maps": 1, "gemm_wblur_adj": 1, "gemm_wblur_fwd": 2, "pad_planes": 1, "specmix_adj": 1, "spmm_gather_fwd": 2, "spmm_scatter_adj": 2, "unpad_planes": 1, "ymat16_from_cpart": 2},
+    "ct300_whole_spectrum-normal_spec_prior": {"dft_ct_cols_fwd": 1, "dft_ct_cols_inv_mix": 1, "dft_ct_rows_fwd": 1, "dft_ct_rows_inv": 1, "gemm_wblur_adj": 1, "gemm_wblur_fwd": 2, "specmix_adj": 1, "spmm_gather_fwd": 2, "spmm_scatter_adj": 2, "ymat16_from_cpart": 2},
+    "spectral_small_exact2-forward": {"dft_h2_cols_inv_mix": 1, "dft_h2_rows_inv": 1, "gemm_dft_cols_fwd_maps": 1, "gemm_dft_rows_fwd_maps": 1, "gemm_wblur_fwd": 1, "pad_planes": 1, "spmm_gather_fwd": 1, "y_from_cpart": 1},
+    "spectral_small_exact2-adjoint": {"dft_h2_cols_fwd_adjmix": 1, "dft_h2_rows_fwd": 1, "gemm_dft_cols_inv_maps": 1, "gemm_dft_rows_inv_maps": 1, "gemm_wblur_adj": 1, "spmm_scatter_adj": 1, "unpad_planes": 1, "ymat_from_y": 1},
+    "spectral_small_exact2-fwadj": {"dft_h2_cols_fwd_adjmix": 1, "dft_h2_cols_inv_mix": 1, "dft_h2_rows_fwd": 1, "dft_h2_rows_inv": 1, "gemm_dft_cols_fwd_maps": 1, "gemm_dft_cols_inv_maps": 1, "gemm_dft_rows_fwd_maps": 1, "gemm_dft_rows_inv_maps": 1, "gemm_wblur_adj": 1, "gemm_wblur_fwd": 1, "pad_planes": 1, "spmm_gather_fwd": 1, "spmm_scatter_adj": 1, "unpad_planes": 1, "ymat16_from_cpart": 1},
+    "spectral_small_exact2-normal_spec_prior": {"dft_h2_cols_fwd_adjmix": 1, "dft_h2_cols_inv_mix": 1, "dft_h2_rows_fwd": 1, "dft_h2_rows_inv": 1, "gemm_wblur_adj": 1, "gemm_wblur_fwd": 1, "spmm_gather_fwd": 1, "spmm_scatter_adj": 1, "ymat16_from_cpart": 1},
+    "mid_tail_separate-forward": {"dft_h2_cols_inv_mix": 1, "dft_h2_rows_inv": 1, "gemm_dft_cols_fwd_maps": 1, "gemm_dft_rows_fwd_maps": 1, "gemm_wblur_fwd": 2, "pad_planes": 1, "spmm_gather_fwd": 2, "y_from_cpart": 2},
+    "mid_tail_separate-adjoint": {"dft_h2_cols_fwd": 1, "dft_h2_rows_fwd": 1, "gemm_dft_cols_inv_maps": 1, "gemm_dft_rows_inv_maps": 1, "gemm_wblur_adj": 1, "specmix_adj": 1, "spmm_scatter_adj": 2, "unpad_planes": 1, "ymat_from_y": 2},
+    "mid_tail_separate-fwadj": {"dft_h2_cols_fwd": 1, "dft_h2_cols_inv_mix": 1, "dft_h2_rows_fwd": 1, "dft_h2_rows_inv": 1, "gemm_dft_cols_fwd_maps": 1, "gemm_dft_cols_inv_maps": 1, "gemm_dft_rows_fwd_maps": 1, "gemm_dft_rows_inv_maps": 1, "gemm_wblur_adj": 1, "gemm_wblur_fwd": 2, "pad_planes": 1, "specmix_adj": 1, "spmm_gather_fwd": 2, "spmm_scatter_adj": 2, "unpad_planes": 1, "ymat16_from_cpart": 2},
+    "mid_unfused_mix-forward": {"dft_h2_cols_inv": 1, "dft_h2_rows_inv": 1, "gemm_dft_cols_fwd_maps": 1, "gemm_dft_rows_fwd_maps": 1, "gemm_wblur_fwd": 2, "pad_planes": 1, "specmix_fwd": 1, "spmm_gather_fwd": 2, "y_from_cpart": 2},
+    "mid_unfused_mix-adjoint": {"dft_h2_cols_fwd_adjmix": 1, "dft_h2_rows_fwd": 1, "gemm_dft_cols_inv_maps": 1, "gemm_dft_rows_inv_maps": 1, "gemm_wblur_adj": 1, "spmm_scatter_adj": 2, "unpad_planes": 1, "ymat_from_y": 2},
+    "mid_unfused_mix-fwadj": {"dft_h2_cols_fwd_adjmix": 1, "dft_h2_cols_inv": 1, "dft_h2_rows_fwd": 1, "dft_h2_rows_inv": 1, "gemm_dft_cols_fwd_maps": 1, "gemm_dft_cols_inv_maps": 1, "gemm_dft_rows_fwd_maps": 1, "gemm_dft_rows_inv_maps": 1, "gemm_wblur_adj": 1, "gemm_wblur_fwd": 2, "pad_planes": 1, "specmix_fwd": 1, "spmm_gather_fwd": 2, "spmm_scatter_adj": 2, "unpad_planes": 1, "ymat16_from_cpart": 2},
+    "mixed_300x64_no_dft_ct-forward": {"gemm_dft_cols_fwd_maps": 1, "gemm_dft_cols_inv": 1, "gemm_dft_rows_fwd_maps": 1, "gemm_dft_rows_inv": 1, "gemm_wblur_fwd": 1, "pad_planes": 1, "specmix_fwd": 1, "spmm_gather_fwd": 1, "y_from_cpart": 1},
+    "mixed_300x64_no_dft_ct-adjoint": {"gemm_dft_cols_fwd": 1, "gemm_dft_cols_inv_maps": 1, "gemm_dft_rows_fwd": 1, "gemm_dft_rows_inv_maps": 1, "gemm_wblur_adj": 1, "specmix_adj": 1, "spmm_scatter_adj": 1, "unpad_planes": 1, "ymat_from_y": 1},
+    "mixed_300x64_no_dft_ct-fwadj": {"gemm_dft_cols_fwd": 1, "gemm_dft_cols_fwd_maps": 1, "gemm_dft_cols_inv": 1, "gemm_dft_cols_inv_maps": 1, "gemm_dft_rows_fwd": 1, "gemm_dft_rows_fwd_maps": 1, "gemm_dft_rows_inv": 1, "gemm_dft_rows_inv_maps": 1, "gemm_wblur_adj": 1, "gemm_wblur_fwd": 1, "pad_planes": 1, "specmix_adj": 1, "specmix_fwd": 1, "spmm_gather_fwd": 1, "spmm_scatter_adj": 1, "unpad_planes": 1, "ymat16_from_cpart": 1},
+    "blurred_300_exact2-forward": {"cube_transpose": 1, "dft_ct_cols_fwd": 1, "dft_ct_cols_inv_prod": 1, "dft_ct_rows_fwd": 1, "dft_ct_rows_inv": 1, "spmm_gather_fwd": 1, "y_transpose": 1},
+    "blurred_300_exact2-adjoint": {"cube_transpose": 1, "dft_ct_cols_fwd": 1, "dft_ct_cols_inv_prod": 1, "dft_ct_rows_fwd": 1, "dft_ct_rows_inv": 1, "spmm_scatter_adj": 1, "y_transpose": 1},
+    "blurred_300_exact2-planes_cg_native1": {"dft_ct_cols_fwd": 7, "dft_ct_cols_inv_prod": 7, "dft_ct_rows_fwd": 7, "dft_ct_rows_inv": 7, "pn_dir": 1, "pn_prior_dot": 3, "spmm_gather_fwd": 3, "spmm_scatter_adj": 4, "y_transpose": 7},
+    "blurred_300_exact2-planes_cg_native1_prior": {"dft_ct_cols_fwd": 7, "dft_ct_cols_inv_prod": 4, "dft_ct_cols_inv_prodadd": 3, "dft_ct_rows_fwd": 7, "dft_ct_rows_inv": 7, "pn_dir": 1, "pn_prior_dot": 3, "spmm_gather_fwd": 3, "spmm_scatter_adj": 4, "y_transpose": 7},
 }
 
 
