@@ -217,6 +217,26 @@ int surfh_cg_templates_nonneg(surfh_plan *plan, const float *y, const float *map
  * inputs.  Pointers need no alignment.                                                                                                */
 int surfh_nn_project_dev(surfh_plan *plan, const float *x_dev, float *z_dev, float *u_dev, float *r_dev, float *dv_dev, int64_t n,
                          double rho, double *sums);
+/* Non-negative plane-wise deconvolution: the Lc independent problems of surfh_cg_planes (same Q_l and b_l: data weights, the
+ * separated circular first-difference prior) under x_l >= 0, by the scheme of surfh_cg_nonneg per plane -- rho [Lc] one fixed penalty
+ * each, `inner` CG iterations on Q_l + rho_l I per outer iteration (the plane-wise CG's own kernels, every plane with its own step
+ * scalars), z_l' = max(x_l + u_l, 0), u_l' = u_l + x_l - z_l', r_l += rho_l (v_l' - v_l), or r recomputed every `refresh` outer
+ * iterations (0: never).  y [osize], x0 [Lc][Na][Nb] or NULL (zeros), x [Lc][Na][Nb] = z: every entry >= 0, no set sign bit.
+ * trace [outer + 1][4][Lc]: entry 0 the start, then one per outer iteration run; the four rows of an entry are, per plane,
+ * |x - z'|^2, rho_l^2 |z' - z|^2, r.r of the next inner system, #{z' == 0}.  *nit: outer iterations run.  The loop ends once EVERY
+ * plane has sqrt(max(rho_l^2 |x - z'|^2, rho_l^2 |z' - z|^2)) < Na Nb tol (0: never); a plane that met the test earlier keeps
+ * iterating with the others, nothing is frozen.  A plane with no data from a zero start stays at rest: zeros, a finite trace.
+ * The vectors are those of surfh_cg_planes (the caller's layout); the wavelength-innermost space of surfh_cg_planes_begin_dev is
+ * not used.  Fails before any work: a null argument, a rho_l that is not finite and > 0, inner < 1, outer < 0, a plan with
+ * templates, an imager term.                                                                                                       */
+int surfh_cg_planes_nonneg(surfh_plan *plan, const float *y, double mu, double mu_reg, const double *rho, const float *x0, int32_t outer,
+                           int32_t inner, double tol, int32_t refresh, float *x, double *trace, int32_t *nit);
+/* the projection / dual update of one outer iteration of it on device vectors [L][npix] (plane-major), in place in z, u and r (the
+ * fused form of surfh_nn_project_dev, r += rho_l (v' - v)); rho [L] on the host.  sums [4][L] (host) = per plane |x - z'|^2,
+ * |z' - z|^2, #{z' == 0}, r.r of the updated r: float64, two stages in a fixed order, the same bits for the same inputs.  A plane
+ * whose four base pointers are 16-byte aligned goes through 16-byte accesses, the others (npix % 4 != 0) through the scalar path.   */
+int surfh_nn_project_planes_dev(surfh_plan *plan, const float *x_dev, float *z_dev, float *u_dev, float *r_dev, int32_t L, int64_t npix,
+                                const double *rho, double *sums);
 
 /* ---- posterior sampling: per-pixel uncertainty of the maps surfh_cg returns (perturbation-optimisation, Orieux, Feron &
  * Giovannelli 2012) ----

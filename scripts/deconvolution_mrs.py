@@ -25,6 +25,13 @@ exact transpose of that operator.  ``--data_to_img`` also writes the quick-look 
 priors of threshold D on the row and column differences, minimised by 3MG (``-m`` anything but ``lcg``); the results then go to
 ``<--out>_huber_<D>``.  ``--potential`` (with ``--delta``) replaces Huber's potential by ``hyperbolic`` or ``hebert_leahy``
 (surfh_amd/potentials.py); the results then go to ``<--out>_<kind>_<D>``.
+
+``--nonneg`` (with ``-m lcg``; not in the reference either): the same quadratic criterion under ``x >= 0``, every plane its own
+problem, by ``MRSBlurred.cg_nonneg`` (ADMM around the CG, surfh_amd/nonneg.py) from ``--value_init``: ``--outer`` outer iterations
+(default ``-ni``) of ``--inner`` CG iterations (default 10), penalties ``--rho`` (default: estimated per plane).  The results go to
+``<--out>_nn``: the files above, ``criterion.npy`` holding the criterion at the start and at the result, plus ``nn_trace.npy``
+``[outer iterations run + 1, 4, planes]``: ``|x - z|``, ``rho |z - z_previous|``, ``|r|``, ``#{z == 0}`` per plane.  Works with
+``--angle``.
 """
 from __future__ import annotations
 
@@ -100,8 +107,27 @@ def result_dir(out, delta, potential="huber"):
               help="Huber threshold of the priors (needs -m other than lcg); results go to <out>_huber_<delta>")
 @click.option("--potential", default="huber", type=click.Choice(["huber", "hyperbolic", "hebert_leahy"]),
               help="potential of the priors under --delta; other than huber: results go to <out>_<potential>_<delta>")
+@click.option("--nonneg", is_flag=True, default=False,
+              help="solve under x >= 0 (ADMM around the CG, -m lcg); results go to <out>_nn, with nn_trace.npy")
+@click.option("--rho", default=None, type=float, help="ADMM penalty of every plane (--nonneg); default: estimated per plane")
+@click.option("--outer", default=None, type=int, help="outer iterations (--nonneg); default: -ni")
+@click.option("--inner", default=None, type=int, help="CG iterations per outer iteration (--nonneg); default: 10")
 def main(npix, hyper_parameter, niter, method, value_init, planes, inp, out, quiet, seed, device, angle, data_to_img, delta,
-         potential="huber"):
+         potential="huber", nonneg=False, rho=None, outer=None, inner=None):
+    if nonneg:
+        if method != "lcg":
+            raise click.UsageError("--nonneg runs ADMM around the linear CG; use it with -m lcg")
+        if delta is not None:
+            raise click.UsageError("--nonneg constrains the quadratic criterion: no --delta")
+        if rho is not None and not (np.isfinite(rho) and rho > 0):
+            raise click.BadParameter(f"must be finite and > 0, not {rho}", param_hint="--rho")
+        if inner is not None and inner < 1:
+            raise click.BadParameter(f"at least one CG iteration, not {inner}", param_hint="--inner")
+        if outer is not None and outer < 1:
+            raise click.BadParameter(f"at least one outer iteration, not {outer}", param_hint="--outer")
+        out = out + "_nn"
+    elif rho is not None or outer is not None or inner is not None:
+        raise click.UsageError("--rho, --outer and --inner belong to --nonneg")
     if potential != "huber" and delta is None:
         raise click.UsageError("--potential needs --delta: a potential of the quadratic prior means nothing")
     if delta is not None:
@@ -121,7 +147,18 @@ def main(npix, hyper_parameter, niter, method, value_init, planes, inp, out, qui
     crit = QuadCriterion_MRS_2D(mu_spectro=1, y_spectro=np.copy(simulated_data), model_spectro=model, mu_reg=hyper_parameter,
                                 printing=True, gradient="separated", delta=delta, potential=potential)
     t0 = time.time()
-    if quiet:
+    nn = None
+    if nonneg:
+        from surfh_amd.fusion import OptimizeResult
+        x0 = np.full(model.ishape, value_init)
+        nn = model.cg_nonneg(np.copy(simulated_data), mu=1, mu_reg=hyper_parameter, rho=rho, x0=x0, outer=outer or niter, inner=inner or 10)
+        res = OptimizeResult(x=nn.x.ravel(), grad_norm=list(nn.grad_norm), nit=nn.nit, success=True, time=time.time() - t0)
+        crit.L_crit_val = [crit.get_crit_val(x0), crit.get_crit_val(nn.x)]
+        if not quiet:
+            for k in range(nn.nit + 1):
+                print(f"Outer iteration n°{k}: |x - z| = {np.max(nn.primal[k]):.4e}, rho |z - z_prev| = {np.max(nn.dual[k]):.4e}, "
+                      f"|r| = {np.max(nn.grad_norm[k]):.4e}, entries at zero = {int(np.sum(nn.n_active[k]))}")
+    elif quiet:
         res = crit.run_method(method, niter, value_init=value_init)
         crit.L_crit_val = [crit.get_crit_val(np.full(model.ishape, value_init)), crit.get_crit_val(res.x)]
     else:
@@ -135,6 +172,9 @@ def main(npix, hyper_parameter, niter, method, value_init, planes, inp, out, qui
     np.save(os.path.join(out, "res_x.npy"), x)
     np.save(os.path.join(out, "criterion.npy"), np.asarray(crit.L_crit_val))
     np.save(os.path.join(out, "data.npy"), simulated_data)
+    if nn is not None:
+        tr = np.stack([nn.primal, nn.dual, nn.grad_norm, nn.n_active.astype(np.float64)], axis=1)
+        np.save(os.path.join(out, "nn_trace.npy"), tr.reshape(nn.nit + 1, 4, planes))
     if data_to_img:
         for suffix, d in (("", simulated_data), ("_fit", model.forward(x))):
             adj_mean, adj = model.data_to_img(np.copy(d))

@@ -66,7 +66,7 @@ EXPORTS = [
     "surfh_shepard", "surfh_shepard_last_error", "surfh_spectral_median", "surfh_nmf_cd", "surfh_templates_last_error",
     "surfh_set_templates", "surfh_get_templates", "surfh_forward_templates", "surfh_adjoint_templates", "surfh_forward_templates_dev",
     "surfh_adjoint_templates_dev", "surfh_cg_templates", "surfh_cg_templates_cb", "surfh_joint_criterion",
-    "surfh_cg_nonneg", "surfh_cg_templates_nonneg", "surfh_nn_project_dev",
+    "surfh_cg_nonneg", "surfh_cg_templates_nonneg", "surfh_nn_project_dev", "surfh_cg_planes_nonneg", "surfh_nn_project_planes_dev",
 ]
 
 _lib = None
@@ -217,6 +217,9 @@ def load():
     L.surfh_cg_templates_nonneg.argtypes = [vp, c_float_p, c_float_p, C.c_double, C.c_double, C.c_double, c_float_p, C.c_int32, C.c_int32,
                                             C.c_double, C.c_int32, c_float_p, c_double_p, c_int32_p]
     L.surfh_nn_project_dev.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, C.c_double, c_double_p]
+    L.surfh_cg_planes_nonneg.argtypes = [vp, c_float_p, C.c_double, C.c_double, c_double_p, c_float_p, C.c_int32, C.c_int32, C.c_double,
+                                         C.c_int32, c_float_p, c_double_p, c_int32_p]
+    L.surfh_nn_project_planes_dev.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int64, c_double_p, c_double_p]
     _lib = L
     return L
 

@@ -22,7 +22,8 @@ import numpy as np
 from . import _lib, instru
 from .linop import LinOp
 from . import potentials as _pot
-from .weights import DataWeights
+from .nonneg import NonnegResult, check_nonneg_args, result_from_planes_trace
+from .weights import DataWeights, check_data_weights
 
 
 class Blurred2D(DataWeights, _pot.Potentials, LinOp):
@@ -214,6 +215,69 @@ class Blurred2D(DataWeights, _pot.Potentials, LinOp):
         with self.installed_weights(weights):
             return _lib.solve(self, self._L.surfh_cg_planes_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback,
                               planes=self.n_planes, squeeze=not self.batched)
+
+    # ---- the same criterion under x >= 0: ADMM around the CG above, plane by plane (surfh_amd/nonneg.py) ----------
+    def nonneg_rho(self, mu=1.0, mu_reg=0.0, seed=0, weights=None):
+        """The default penalties of ``cg_nonneg``: per plane ``v_l^T Q_l v_l / v_l^T v_l`` for one standard normal probe ``v``
+        (``default_rng(seed)``, drawn in the model's input shape), ``Q_l = mu A_l^T W_l A_l + mu_reg (Dr^T Dr + Dc^T Dc)`` -- the mean
+        eigenvalue of every plane's operator from one batched forward application.  ``weights`` as in ``cg`` (None: the model's
+        own).  Returns ``[n_planes]``, a float for a single image."""
+        v = np.random.default_rng(seed).standard_normal(self.ishape)
+        av = np.asarray(self.forward(v), dtype=np.float64).reshape(self.n_planes, -1)
+        w = self.data_weights if weights is None else check_data_weights(weights, self.osize)
+        sq = av * av if w is None else np.where(w.reshape(av.shape) > 0, w.reshape(av.shape).astype(np.float64) * av * av, 0.0)
+        vp = v.reshape((self.n_planes,) + self.imshape)
+        prior = np.sum((vp - np.roll(vp, 1, axis=1)) ** 2 + (vp - np.roll(vp, 1, axis=2)) ** 2, axis=(1, 2)) if mu_reg else 0.0
+        rho = (mu * np.sum(sq, axis=1) + mu_reg * prior) / np.sum(vp * vp, axis=(1, 2))
+        return rho if self.batched else float(rho[0])
+
+    def cg_nonneg(self, data, mu=1.0, mu_reg=0.0, rho=None, x0=None, outer=30, inner=10, tol=0.0, refresh=10, weights=None) -> NonnegResult:
+        """The images of ``cg`` under ``x >= 0``: every plane its own problem ``min x_l^T Q_l x_l / 2 - b_l^T x_l, x_l >= 0`` with its
+        own penalty, step sizes, trace and stopping test (include/surfh_amd.h: surfh_cg_planes_nonneg).  ``outer`` ADMM iterations
+        of ``inner`` CG iterations each, from ``x0`` (None: zeros); the carried residual is recomputed every ``refresh`` outer
+        iterations (0: never).  ``rho``: None (``nonneg_rho(mu, mu_reg, weights=weights)``), a number (every plane) or ``[n_planes]``.
+        Returns a ``NonnegResult`` whose traces are ``[nit+1, n_planes]`` (``[nit+1]`` for a single image, as ``cg``'s
+        ``grad_norm``) and whose ``rho`` is the array used (a float for a single image).  Stops early once every plane has
+        ``max(rho_l primal_l, dual_l) < Na Nb tol``; the planes that met the test earlier keep iterating until then.
+        ``ValueError`` for a bad argument."""
+        if rho is not None:
+            rho = np.asarray(rho, dtype=np.float64)
+            if rho.ndim > 1 or (rho.ndim == 1 and rho.size != self.n_planes):
+                raise ValueError(f"cg_nonneg: rho has shape {rho.shape}, expected a number or [{self.n_planes}]")
+        for r in ([None] if rho is None else np.atleast_1d(rho)):
+            check_nonneg_args(r, outer, inner, refresh)
+        y = np.ascontiguousarray(np.asarray(data, dtype=np.float32).reshape(-1))
+        if y.size != self.osize:
+            raise ValueError(f"data have {y.size} elements, expected {self.osize}")
+        x0a = None if x0 is None else np.ascontiguousarray(np.asarray(x0, dtype=np.float32).reshape(-1))
+        if x0a is not None and x0a.size != self.isize:
+            raise ValueError(f"x0 has {x0a.size} elements, expected {self.isize}")
+        if rho is None:
+            rho = self.nonneg_rho(mu, mu_reg, weights=weights)
+        rho = np.ascontiguousarray(np.broadcast_to(np.asarray(rho, dtype=np.float64), (self.n_planes,)))
+        out = np.empty(self.isize, dtype=np.float32)
+        trace = np.zeros((int(outer) + 1, 4, self.n_planes), dtype=np.float64)
+        nit = C.c_int32()
+        with self.installed_weights(weights):
+            _lib.check(self._L.surfh_cg_planes_nonneg(self._plan, _lib.fptr(y), float(mu), float(mu_reg), _lib.dptr(rho),
+                                                      None if x0a is None else _lib.fptr(x0a), int(outer), int(inner), float(tol),
+                                                      int(refresh), _lib.fptr(out), _lib.dptr(trace), C.byref(nit)), ValueError)
+        return result_from_planes_trace(out.astype(np.float64).reshape(self.ishape), trace, rho, nit.value, squeeze=not self.batched)
+
+    def nn_project_planes_dev(self, x_t, z_t, u_t, r_t, n_planes: int, npix: int, rho) -> np.ndarray:
+        """The projection / dual update of one outer iteration on device tensors ``[n_planes, npix]`` (or raw device addresses),
+        in place in ``z_t``, ``u_t`` and ``r_t`` (include/surfh_amd.h: surfh_nn_project_planes_dev); ``rho`` ``[n_planes]``.
+        Returns ``[4, n_planes]``: ``|x - z'|^2, |z' - z|^2, #{z' == 0}, r.r`` per plane (synchronises)."""
+        def ptr(t):
+            return C.c_void_p(int(t)) if isinstance(t, int) else C.c_void_p(t.data_ptr())
+
+        rho = np.ascontiguousarray(rho, dtype=np.float64)
+        if rho.shape != (int(n_planes),):
+            raise ValueError(f"rho has shape {rho.shape}, expected ({int(n_planes)},)")
+        sums = np.zeros((4, int(n_planes)), dtype=np.float64)
+        _lib.check(self._L.surfh_nn_project_planes_dev(self._plan, ptr(x_t), ptr(z_t), ptr(u_t), ptr(r_t), int(n_planes), int(npix),
+                                                       _lib.dptr(rho), _lib.dptr(sums)), ValueError)
+        return sums
 
     # ---- instrumentation (HIP events on the plan's stream, as spectroSigRLSCT) -----------------------------
     def profile_enable(self, on=True):

@@ -180,6 +180,15 @@ int launch_nn_project(hipStream_t s, const float *x, float *z, float *u, float *
                       double *sums);
 // out += c (a - b)   (b NULL: out += c a)
 int launch_nn_add(hipStream_t s, float *out, const float *a, const float *b, long n, float c);
+// the same pass on L independent planes ([L][npix] vectors, plane-major) with one penalty per plane, rho_l [L] floats on the device,
+// in the fused form (r += w): sums [4][L] (device) per plane, from nn_planes_part_doubles(L, npix) partial sums added in a fixed
+// order.  The 16-byte path is chosen plane by plane, from the plane's own base pointers.
+unsigned nn_planes_split(long npix);                  // blocks per plane of the two plane kernels
+size_t nn_planes_part_doubles(int L, long npix);
+int launch_nn_project_planes(hipStream_t s, const float *x, float *z, float *u, float *r, int L, long npix, const float *rho_l, double *part,
+                             double *sums);
+// out_l += (scale c_l) (a_l - b_l) per plane, c_l [L] floats on the device   (b NULL: out_l += (scale c_l) a_l)
+int launch_nn_add_planes(hipStream_t s, float *out, const float *a, const float *b, int L, long npix, const float *c_l, float scale);
 // 3MG move: mv = s0 d + s1 m ; x += mv ; m = mv ; qm = s0 qd + s1 qm ; r -= qm (when update_r)
 int launch_mmmg_update(hipStream_t s, float *x, float *r, const float *d, float *m, float *qm, const float *qd, long n, double s0,
                        double s1, int update_r);

@@ -294,6 +294,11 @@ struct surfh_plan : PlanHandles {
     // scaled dual and a work vector
     DevBuf<float> nn_z;
     float *nn_u = nullptr, *nn_w = nullptr;        // views: the second and third thirds of nn_z
+    // ... on independent planes (surfh_cg_planes_nonneg): the penalties [Lc], the partial sums of nn_project_planes and, behind
+    // them, its sums [4][Lc] (view)
+    DevBuf<float> nn_rho;
+    DevBuf<double> nn_part;
+    double *nn_sums = nullptr;
     DevBuf<double> cg_hist;                        // device-resident r.r trace of the no-host-sync CG blocks (CG_HIST_CAP entries)
     int cg_hist_n = 0;
     // plane-wise CG with device-resident data (surfh_cg_planes_begin_dev / _step_dev): per-plane scalars [3][Lc] (the host-buffer

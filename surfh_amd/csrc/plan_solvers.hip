@@ -244,6 +244,7 @@ struct CgSpace {
     // (null: the launches are exactly those without it); surfh_cg_nonneg: the penalty, the operator of the nn_* applies is Q + rho I
     const float *extra = nullptr;
     double rho = 0.0;
+    const float *rho_l = nullptr;  // surfh_cg_planes_nonneg: one penalty per problem, `rows` floats on the device
 };
 int cg_nop(surfh_plan *, const CgSpace &) { return 0; }     // to_caller: the layouts agree; dir: the step's block went on to the direction
 // the maps and the planes keep the current row only: it goes to the host after every iteration
@@ -569,12 +570,25 @@ struct NnScope {                       // the extra vectors never outlive a solv
         p->nn_w = p->nn_u + pitch;
         return 0;
     }
+    // the plane-wise solve: z and u [L][npix] (no work vector: the pass is the fused one), the penalties as floats, the partial
+    // sums of the pass with its [4][L] sums behind them
+    int begin_planes(int L, long npix, const double *rho) {
+        const size_t pitch = ((size_t)L * npix + 3) / 4 * 4, parts = nn_planes_part_doubles(L, npix);
+        std::vector<float> h(rho, rho + L);
+        if (p->nn_z.alloc(2 * pitch) || p->nn_part.alloc(parts + (size_t)4 * L) || p->nn_rho.upload(h)) return 1;
+        p->nn_u = p->nn_z + pitch;
+        p->nn_sums = p->nn_part + parts;
+        return 0;
+    }
     ~NnScope() {
-        if (p->nn_z) {
+        if (p->nn_z || p->nn_part || p->nn_rho) {
             hipStreamSynchronize(p->stream);
             p->nn_z.reset();
+            p->nn_part.reset();
+            p->nn_rho.reset();
         }
         p->nn_u = p->nn_w = nullptr;
+        p->nn_sums = nullptr;
     }
 };
 int nn_rho_add(surfh_plan *p, const CgSpace &s, const float *v) {                           // q += rho v: the operator is Q + rho I
@@ -719,6 +733,115 @@ int surfh_cg_templates_nonneg(surfh_plan *p, const float *y, const float *maps, 
     NnScope sc(p);
     if (tsc.begin() || cg_start(p, s, p->io_y, nullptr) || sc.begin(s.len)) return 1;
     return nn_loop(p, s, sx, false, h.data(), s.len, outer, inner, tol, refresh, s_out, trace, nit);
+}
+
+// ---- the same on independent planes: s.rows problems min x_l^T Q_l x_l / 2 - b_l^T x_l, x_l >= 0 on planes_space, each with its own
+// penalty rho_l, its own trace and its own stopping test.  nn_loop stays as it is (one rho, one trace row, the launches of the single
+// problem); this sibling differs in what is per plane: nn_project_planes sums per plane, nn_add_planes scales per plane, the host
+// reads one [4][rows] block per outer iteration.  The loop ends when EVERY plane meets sqrt(max(rho_l^2 row0_l, row1_l)) < n tol;
+// a plane that met it earlier keeps iterating with the others (nothing is frozen: the batched operator runs on all planes anyway,
+// so stopping one plane would save nothing).  A plane with b_l = 0 from x0_l = 0 has r = d = 0: the step kernels' d.q = 0 and rr = 0
+// guards keep it at rest, the pass returns zeros, its trace is finite.
+namespace {
+int nn_planes_apply(surfh_plan *p, const CgSpace &s, const float *v) {                     // q_l = Q_l v_l + rho_l v_l
+    if (img_apply(p, s, v)) return 1;
+    Prof pr(p, "nn_rho_add");
+    LAUNCH_OK(launch_nn_add_planes(p->stream, s.q, v, nullptr, s.rows, s.n, s.rho_l, 1.f));
+    return 0;
+}
+// After cg_start on planes_space (r = b - Q x, trace entry 0) inside an NnScope begun with begin_planes.  `s`: that space with its
+// penalties rho_l and nn_planes_apply; h0: the start on the host (NULL: zeros); out [len]; trace [outer + 1][4][rows], the four
+// rows in nn_loop's order: |x - z'|^2, rho^2 |z' - z|^2, r.r, #{z' == 0}
+int nn_planes_loop(surfh_plan *p, const CgSpace &s, const double *rho, const float *h0, int32_t outer, int32_t inner,
+                   double tol, int32_t refresh, float *out, double *trace, int32_t *nit) {
+    hipStream_t st = p->stream;
+    const int L = s.rows;
+    const long npix = s.n, m = s.len;
+    double *const sums = p->nn_sums;
+    std::vector<double> h((size_t)4 * L, 0.0);             // row 0 in the trace's order, then the pass's sums in theirs (count before r.r)
+    for (int l = 0; l < L; ++l) h[3 * (size_t)L + l] = (double)npix;                       // row 0: nothing of z = 0 is positive
+    HIP_OK(hipMemsetAsync(p->nn_u, 0, m * sizeof(float), st));
+    if (h0) {
+        std::vector<float> hz((size_t)m);
+        bool infeasible = false;
+        for (int l = 0; l < L; ++l) {
+            double pp = 0.0, active = 0.0;
+            for (long i = (long)l * npix; i < (long)(l + 1) * npix; ++i) {
+                hz[i] = h0[i] > 0.f ? h0[i] : 0.f;
+                const double e = (double)h0[i] - (double)hz[i];
+                pp += e * e;
+                active += hz[i] == 0.f ? 1.0 : 0.0;
+            }
+            h[l] = pp;
+            h[3 * (size_t)L + l] = active;
+            infeasible = infeasible || pp > 0.0;
+        }
+        HIP_OK(hipMemcpyAsync(p->nn_z, hz.data(), m * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_OK(hipStreamSynchronize(st));                                                   // hz leaves scope
+        if (infeasible) {                                                                   // r_l += rho_l (z_l - x_l), 0 where x0_l >= 0
+            LAUNCH_OK(launch_nn_add_planes(st, s.r, p->nn_z, s.x, L, npix, s.rho_l, 1.f));
+            if (s.rr0(p, s)) return 1;
+        }
+    } else HIP_OK(hipMemsetAsync(p->nn_z, 0, m * sizeof(float), st));
+    if (s.trace(p, s, h.data() + 2 * (size_t)L, 0)) return 1;                               // r.r per plane; synchronises
+    std::copy(h.begin(), h.end(), trace);
+    *nit = 0;
+    for (int k = 0; k < outer; ++k) {
+        HIP_OK(hipMemcpyAsync(s.d, s.r, m * sizeof(float), hipMemcpyDeviceToDevice, st));
+        for (int j = 0; j < inner; ++j)
+            if (cg_iteration(p, s, j, 0)) return 1;
+        {
+            Prof pr(p, "nn_project");
+            LAUNCH_OK(launch_nn_project_planes(st, s.x, p->nn_z, p->nn_u, s.r, L, npix, s.rho_l, p->nn_part, sums));
+        }
+        if (refresh_due(refresh, k + 1)) {                                                  // r = b + rho v' - (Q + rho I) x, its r.r to the sums
+            if (s.apply(p, s, s.x)) return 1;
+            LAUNCH_OK(launch_residual(st, s.r, s.b, s.q, m));
+            LAUNCH_OK(launch_nn_add_planes(st, s.r, p->nn_z, p->nn_u, L, npix, s.rho_l, 1.f));
+            if (s.rr0(p, s)) return 1;
+            HIP_OK(hipMemcpyAsync(sums + 3 * (size_t)L, s.rr, L * sizeof(double), hipMemcpyDeviceToDevice, st));
+        } else HIP_OK(hipMemcpyAsync(s.rr, sums + 3 * (size_t)L, L * sizeof(double), hipMemcpyDeviceToDevice, st));   // the pass summed the new r.r
+        HIP_OK(hipMemcpyAsync(h.data(), sums, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));      // the one read of the iteration
+        HIP_OK(hipStreamSynchronize(st));
+        double *row = trace + (size_t)(k + 1) * 4 * L;
+        bool met = true;
+        for (int l = 0; l < L; ++l) {
+            row[l] = h[l];
+            row[L + l] = rho[l] * rho[l] * h[(size_t)L + l];
+            row[2 * (size_t)L + l] = h[3 * (size_t)L + l];
+            row[3 * (size_t)L + l] = h[2 * (size_t)L + l];
+            met = met && std::sqrt(std::max(rho[l] * rho[l] * row[l], row[L + l])) < (double)s.n * tol;
+        }
+        *nit = k + 1;
+        if (met) break;
+    }
+    HIP_OK(hipMemcpyAsync(out, p->nn_z, m * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return 0;
+}
+}  // namespace
+
+int surfh_cg_planes_nonneg(surfh_plan *p, const float *y, double mu, double mu_reg, const double *rho, const float *x0, int32_t outer,
+                           int32_t inner, double tol, int32_t refresh, float *x, double *trace, int32_t *nit) {
+    if (!p || !y || !rho || !x || !trace || !nit) return fail("null argument");
+    if (imager_refuse(p, "surfh_cg_planes_nonneg")) return 1;
+    if (p->T != 0) return fail("surfh_cg_planes_nonneg is the solver of the plane-wise (no template) model; use surfh_cg_nonneg with templates");
+    for (int l = 0; l < p->Lc; ++l) {
+        const float rf = (float)rho[l];
+        if (!(rho[l] > 0.0 && rho[l] <= DBL_MAX) || !(rf > 0.f && rf <= FLT_MAX))
+            return fail("surfh_cg_planes_nonneg: rho[%d] = %g must be finite and > 0 (as a float too)", l, rho[l]);
+    }
+    if (nn_refuse("surfh_cg_planes_nonneg", 1.0, outer, inner)) return 1;
+    if (cg_planes_ready(p, "surfh_cg_planes_nonneg", false)) return 1;
+    const CgSpace s = planes_space(p, p->cg_x, mu, mu_reg);
+    HIP_OK(hipMemcpyAsync(p->io_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    if (start_iterate(p, x0) || cg_start(p, s, p->io_y, s.xc)) return 1;
+    NnScope sc(p);
+    if (sc.begin_planes(p->Lc, s.n, rho)) return 1;
+    CgSpace sx = s;
+    sx.apply = nn_planes_apply;
+    sx.rho_l = p->nn_rho;
+    return nn_planes_loop(p, sx, rho, x0, outer, inner, tol, refresh, x, trace, nit);
 }
 
 // out[0] = J(x, S) = (mu out[1] + mu_reg out[2] + mu_spec out[3]) / 2 at the plan's templates S: out[1] = (y - A x)^T W (y - A x) under

@@ -20,7 +20,8 @@ from . import _lib
 class NonnegResult(NamedTuple):
     """``x``: the feasible iterate ``z`` (min >= 0 exactly).  One trace entry for the start and one per outer iteration run:
     ``primal`` ``|x - z|``, ``dual`` ``rho |z - z_previous|`` (0 at the start), ``grad_norm`` ``|r|`` of the next inner system,
-    ``n_active`` the number of entries of ``z`` at 0.  ``rho``: the penalty used; ``nit``: outer iterations run."""
+    ``n_active`` the number of entries of ``z`` at 0.  ``rho``: the penalty used; ``nit``: outer iterations run.  The plane-wise
+    solver (``Blurred2D.cg_nonneg``) returns every trace per plane, ``[nit+1, n_planes]``, and ``rho`` as the array ``[n_planes]``."""
     x: np.ndarray
     primal: np.ndarray
     dual: np.ndarray
@@ -46,6 +47,16 @@ def check_nonneg_args(rho, outer, inner, refresh=0, what="cg_nonneg"):
 def result_from_trace(x, trace, rho, nit) -> NonnegResult:
     t = trace[: nit + 1]
     return NonnegResult(x, np.sqrt(t[:, 0]), np.sqrt(t[:, 1]), np.sqrt(t[:, 2]), np.rint(t[:, 3]).astype(np.int64), float(rho), int(nit))
+
+
+def result_from_planes_trace(x, trace, rho, nit, squeeze=False) -> NonnegResult:
+    """The plane-wise solver's trace ``[outer+1, 4, n_planes]`` (include/surfh_amd.h: surfh_cg_planes_nonneg) as a ``NonnegResult``
+    whose traces are ``[nit+1, n_planes]`` and whose ``rho`` is the array used; ``squeeze`` (a single image): ``[nit+1]`` and a float."""
+    t = trace[: nit + 1]
+    cols = [np.sqrt(t[:, 0]), np.sqrt(t[:, 1]), np.sqrt(t[:, 2]), np.rint(t[:, 3]).astype(np.int64)]
+    if squeeze:
+        cols = [c[:, 0].copy() for c in cols]
+    return NonnegResult(x, *cols, float(rho[0]) if squeeze else np.array(rho, dtype=np.float64), int(nit))
 
 
 def rayleigh_rho(quad, shape, seed=0) -> float:
