@@ -481,6 +481,24 @@ int surfh_set_prior(surfh_plan *plan, int32_t kind);
  * slot or kind (message in surfh_last_error) and leaves the plan as it was; get returns the kind, or -1 on an unknown slot. */
 int surfh_set_potential(surfh_plan *plan, int32_t slot, int32_t kind);
 int surfh_get_potential(const surfh_plan *plan, int32_t slot);
+/* ---- prior coupling: plan state, like the potentials and orthogonal to them ----
+ * How the spatial prior of the MAPS groups the circular first differences u_r = Dr x, u_c = Dc x under its potential phi (slot 0):
+ *   coupling 0  none       sum_t sum_ij phi(u_r) + phi(u_c)                one potential per difference (the default: the kernels,
+ *                                                                          launches and bits of a plan that never heard of couplings)
+ *   coupling 1  isotropic  sum_t sum_ij phi(sqrt(u_r^2 + u_c^2))           an edge pays the same whatever its angle to the pixel grid
+ *   coupling 2  vector     sum_ij phi(sqrt(sum_t u_r^2 + u_c^2))           one edge per pixel for all T maps: edges co-locate across maps
+ * delta is then the threshold on the GROUP MAGNITUDE m = the square root above: for comparable behaviour it grows like sqrt(2)
+ * under isotropic and like sqrt(2 T) under vector.  phi(sqrt(.)) is concave for every kind, so the half-quadratic majorant of
+ * surfh_mmmg_huber holds with every difference of a group weighted by w(m) = phi'(m) / m: the gradient is
+ * sum_k D_k^T (w(m) D_k x), the curvature sums are sum_k sum w(m) (D_k p0)^2, (D_k p0)(D_k p1), (D_k p1)^2 and the prior value is
+ * sum phi(m).  delta = +inf is the quadratic prior under every coupling; T = 1 makes vector the same as isotropic.
+ * surfh_mmmg_huber, surfh_mmmg_robust, surfh_huber_prior_dev and surfh_huber_curv_dev honour the coupling (the imager term and the
+ * data weights compose as before); they fail on a plan whose quadratic prior is the joint Laplacian (surfh_set_prior).  The
+ * plane-wise and voxel-wise solvers and passes (surfh_mmmg_huber_planes, surfh_mmmg_huber_vox, surfh_mmmg_robust_vox, the
+ * _planes_ and _vox_ *_dev passes) fail with a message naming the coupling while it is not 0; the quadratic surfh_mmmg and
+ * the CG solvers ignore it.  set fails on an unknown code and on a NULL plan and leaves the plan as it was; get stores the code. */
+int surfh_set_prior_coupling(surfh_plan *plan, int32_t coupling);
+int surfh_get_prior_coupling(const surfh_plan *plan, int32_t *coupling);
 /* ---- data weights: plan state, like the prior ----
  * With weights w [osize] (the layout of y; every w[i] finite and >= 0) the data term of every solver is
  *   mu (y - A x)^T W (y - A x) / 2,  W = diag(w):
@@ -609,6 +627,13 @@ int32_t surfh_klist_classify(const float *B, int32_t n, int32_t k, int64_t ldb, 
  *   "huber_maps": a, b, c = T, Na, Nb;  "huber_vox": a, b, c = Lc, Na, Nb, out[3] = the most planes of one chunk,
  *     chunk k of C = out[1] owning planes [Lc k / C, Lc (k + 1) / C)                                                     */
 int surfh_launch_geometry(const char *which, int64_t a, int64_t b, int64_t c, int64_t out[4]);
+/* diagnostic: the prior passes of the maps on device arrays of ANY shape [T][na][nb] (every extent >= 1; a plan cannot have an
+ * axis of length 1), under an explicit potential kind and prior coupling -- the launchers surfh_huber_prior_dev and
+ * surfh_huber_curv_dev call, on the plan's stream and scratch; the plan's own shape, kind and coupling are not consulted.
+ * g += mu_reg sum_k D_k^T phi'(D_k x) (under a coupling: D_k^T (w(m) D_k x)); sums [5] on the host = g.g, the prior value and the
+ * curvature block of (p0, p1).  Synchronises. */
+int surfh_debug_prior_passes(surfh_plan *plan, int32_t T, int32_t na, int32_t nb, int32_t kind, int32_t coupling, const float *x_dev,
+                             float *g_dev, const float *p0_dev, const float *p1_dev, double mu_reg, double delta, double *sums);
 /* host only (no GPU, no plan): the route plan creation would decide -- which transform kernels run and which fusions ride on
  * them -- from the function plan creation calls.  lp: the plan's plane pitch (owned planes rounded up to 128).  switches: bit i
  * set = switch i is on, in the order SURFH_DFT_H2, SURFH_DFT_CT, SURFH_DFT_DENSE, SURFH_NO_FUSED_MIX, SURFH_ADJ_FUSED,

@@ -29,6 +29,9 @@ files ``robust_weights.npy``, the weights ``[osize]`` in (0, 1] the last iterate
 ``--delta``, ``--data_delta`` and ``--spec_delta``: ``huber`` (the default), ``hyperbolic`` or ``hebert_leahy``
 (surfh_amd/potentials.py).  With another potential than Huber the directory's ``_huber_<D>`` becomes ``_<kind>_<D>``, its
 ``_rob_<D>`` ``_rob_<kind>_<D>``, and a voxel-wise run under another spectral potential gains ``_spec_<kind>``.
+``--coupling isotropic|vector`` (``--method mmmg --delta D``, not with ``--voxel``) lets the row and column difference of a
+pixel, or those of all maps at a pixel, share one potential; ``D`` is then the threshold on the group magnitude and the
+directory gains ``_cpl_<coupling>`` behind the threshold.  ``none`` (the default) keeps today's prior and directory.
 
 ``--refine_templates K --mu_spec M [--tpl_iter n]`` (``--method lcg`` only) refines the spectra as well: K rounds of ``-ni`` CG
 iterations on the maps and ``n`` (default 10) on the templates, under the first-difference prior of weight ``M`` along the wavelength
@@ -53,6 +56,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from surfh_amd import instru, synth                                   # noqa: E402
 from surfh_amd.fusion import QuadCriterion_MRS, weights_from_data     # noqa: E402
 from surfh_amd.weights import check_data_weights                      # noqa: E402
+from surfh_amd.potentials import COUPLING_NAMES as COUPLINGS           # noqa: E402
 from surfh_amd.potentials import NAMES as POTENTIALS                  # noqa: E402
 from surfh_amd.models import spectroSigRLSCT                          # noqa: E402
 
@@ -143,16 +147,19 @@ def create_model(sotf, templates, origin_alpha_axis, origin_beta_axis, wavel_axi
 
 def result_dir_name(method, n_channels, n_templates, niter, hyper_parameter, scale_data, delta=None, voxel=False, weighted=False,
                     data_delta=None, potential='huber', data_potential='huber', spec_potential='huber', imager=0, samples=0,
-                    refine=0, nonneg=False):
+                    refine=0, nonneg=False, coupling='none'):
     """main_fusion.py:182; with a Huber threshold `delta` (not in the reference) `_huber_<delta>` is appended, `_vox` for a
     voxel-wise reconstruction, `_wgt` for a run under data weights, and `_rob_<data_delta>` for a robust data term.  Another
     potential than Huber puts its name in Huber's place (`_<kind>_<delta>`, `_rob_<kind>_<data_delta>`; `_spec_<kind>` for the
-    spectral prior of a voxel-wise run); with Huber the names are unchanged.  `_img_<F>` follows for a run with an imager
+    spectral prior of a voxel-wise run); with Huber the names are unchanged.  A prior coupling other than `none` appends
+    `_cpl_<coupling>` behind the threshold.  `_img_<F>` follows for a run with an imager
     data term of F filters, `_po_<K>` for a run that draws K posterior samples, `_tpl_<K>` for K rounds of template refinement,
     `_nn` last for a non-negative run (--nonneg)."""
     name = f'{method}_MC_{n_channels}_MO_4_Temp_{n_templates}_nit_{str(niter)}_mu_{str("{:.2e}".format(hyper_parameter))}_SD_{scale_data}'
     if delta is not None:
         name += f'_{potential}_{delta:.2e}'
+        if coupling != 'none':
+            name += f'_cpl_{coupling}'
     if voxel:
         name += '_vox'
         if spec_potential != 'huber':
@@ -222,13 +229,14 @@ def voxel_reconstruction(spectro_model, ndata, result_path, spat_reg, spat_th, s
 
 def reconstruction_method(spectro_model, ndata, templates, result_path, hyper_parameter, niter, method, scale_data,
                           checkpoint_every=0, resume=None, delta=None, weights=None, data_delta=None, potential='huber',
-                          data_potential='huber', imager=None, samples=0, seed=0):
+                          data_potential='huber', imager=None, samples=0, seed=0, coupling='none'):
     """main_fusion.py:162-206: regularised least squares by CG, then the three result files.  Not in the reference:
     `checkpoint_every` > 0 writes the iterate to checkpoint.npz in the result directory every that many iterations,
     `resume` (such a file) warm-starts from it and runs the iterations that are left; `delta` replaces the quadratic
     priors by Huber potentials of that threshold (3MG only); `weights` `[osize]` weigh the samples of the data term and are
     stored beside the results as weights.npy; `data_delta` makes the data term robust (3MG only) and stores the last iterate's
     robustness weights as robust_weights.npy; `potential` / `data_potential` name the potential under `delta` / `data_delta`;
+    `coupling` names the differences that share one potential under `delta` (`surfh_amd.potentials`);
     `imager` = (ImagerModel, y_im, mu_imager) adds the imager data term and stores y_im as y_imager.npy; `samples` = K > 0 (lcg
     only) draws K posterior samples under `seed` after the solve, each a CG solve of `niter` iterations for its deviation from res_x, and
     stores their mean, per-pixel standard deviation and covariance [T, T, N, N] as res_mean.npy, res_std.npy and res_cov.npy."""
@@ -236,12 +244,14 @@ def reconstruction_method(spectro_model, ndata, templates, result_path, hyper_pa
     path = pathlib.Path(result_path) / result_dir_name(method, len(spectro_model.instrs), templates.shape[0], niter,
                                                        hyper_parameter, scale_data, delta, weighted=weights is not None,
                                                        data_delta=data_delta, potential=potential, data_potential=data_potential,
-                                                       imager=imager[0].oshape[0] if imager else 0, samples=samples)
+                                                       imager=imager[0].oshape[0] if imager else 0, samples=samples,
+                                                       coupling=coupling)
     path.mkdir(parents=True, exist_ok=True)
     im_kw = dict(model_imager=imager[0], y_imager=imager[1], mu_imager=imager[2]) if imager else {}
     crit = QuadCriterion_MRS(mu_spectro=1, y_spectro=np.copy(ndata), model_spectro=spectro_model,
                              mu_reg=hyper_parameter, printing=True, gradient="separated", delta=delta, weights=weights,
-                             data_delta=data_delta, potential=potential, data_potential=data_potential, **im_kw)
+                             data_delta=data_delta, potential=potential, data_potential=data_potential, coupling=coupling,
+                             **im_kw)
     if resume:
         from surfh_amd.fusion import load_checkpoint
         x_saved, it_done, _ = load_checkpoint(resume)
@@ -360,6 +370,10 @@ def synthetic_problem(name, npix):
               help='Potential of the robust data term under --data_delta (needs --method mmmg and --data_delta).')
 @click.option('--spec_potential', default='huber', type=click.Choice(POTENTIALS),
               help='Potential of the spectral prior under --spec_delta (--voxel).')
+@click.option('--coupling', default='none', type=click.Choice(COUPLINGS),
+              help='Differences that share one potential under --delta: none (each its own), isotropic (row and column of a '
+                   'pixel) or vector (those of all maps at a pixel); needs --method mmmg and --delta, not with --voxel. --delta is '
+                   'then the threshold on the group magnitude.')
 @click.option('--imager', 'imager_filters', default=0, type=int,
               help='Add the data term of a synthetic imager with that many Gaussian filters tiling the wavelength axis (1..16; '
                    'needs --synthetic). Default: none.')
@@ -384,7 +398,8 @@ def synthetic_problem(name, npix):
 def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, method, verbose, synthetic, device, checkpoint_every=0,
          resume=None, delta=None, voxel=False, spec_reg=1., spec_delta=1., weights_file=None, mask_nan=False, data_delta=None,
          potential='huber', data_potential='huber', spec_potential='huber', imager_filters=0, mu_imager=1., imager_decim=1,
-         samples=0, seed=None, refine_rounds=0, mu_spec=None, tpl_iter=None, nonneg=False, rho=None, outer=None, inner=None):
+         samples=0, seed=None, refine_rounds=0, mu_spec=None, tpl_iter=None, nonneg=False, rho=None, outer=None, inner=None,
+         coupling='none'):
     if nonneg:
         if method != 'lcg':
             raise click.UsageError('--nonneg runs ADMM around the linear CG; use it with --method lcg')
@@ -443,6 +458,13 @@ def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, meth
         raise click.UsageError('--mu_imager and --imager_decim belong to --imager')
     if (potential != 'huber' or data_potential != 'huber') and method != 'mmmg':
         raise click.UsageError('--potential and --data_potential choose a non-quadratic term; use them with --method mmmg')
+    if coupling != 'none':
+        if method != 'mmmg':
+            raise click.UsageError('--coupling groups the differences of a non-quadratic prior; use it with --method mmmg and --delta')
+        if voxel:
+            raise click.UsageError('--coupling acts on the maps: the voxel-wise solver (--voxel) does not carry it')
+        if delta is None:
+            raise click.UsageError('--coupling needs --delta: a coupling of the quadratic prior means nothing')
     if potential != 'huber' and delta is None and not voxel:
         raise click.UsageError('--potential needs --delta: a potential of the quadratic prior means nothing')
     if data_potential != 'huber' and data_delta is None:
@@ -532,6 +554,7 @@ def main(fusion_dir, npix, hyper_parameter, niter, n_templates, scale_data, meth
     reconstruction_method(model, ndata, templates, paths["result_path"], hyper_parameter, niter, method, scale_data,
                           checkpoint_every=checkpoint_every, resume=resume, delta=delta, weights=weights, data_delta=data_delta,
                           potential=potential, data_potential=data_potential, imager=imager if synthetic else None, samples=samples,
+                          coupling=coupling,
                           seed=seed or 0)
     model.close()
 

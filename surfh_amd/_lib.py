@@ -57,12 +57,12 @@ EXPORTS = [
     "surfh_wct_fwadj", "surfh_wct_expsol", "surfh_tst_create", "surfh_tst_destroy", "surfh_tst_forward",
     "surfh_tst_adjoint", "surfh_tst_fwadj", "surfh_tst_last_error", "surfh_cg", "surfh_cg_cb", "surfh_mmmg", "surfh_mmmg_huber", "surfh_huber_prior_dev", "surfh_huber_curv_dev", "surfh_mmmg_huber_vox", "surfh_huber_vox_prior_dev", "surfh_huber_vox_curv_dev", "surfh_mmmg_robust", "surfh_mmmg_robust_vox", "surfh_robust_data_dev", "surfh_robust_curv_dev", "surfh_mmmg_huber_planes", "surfh_huber_planes_prior_dev", "surfh_huber_planes_curv_dev", "surfh_cg_planes", "surfh_mmmg_planes", "surfh_cg_planes_cb", "surfh_mmmg_planes_cb", "surfh_cg_planes_begin_dev", "surfh_cg_planes_step_dev", "surfh_cg_planes_rr", "surfh_maps_to_cube", "surfh_cube_to_maps", "surfh_normal_dev",
     "surfh_prior_add_dev", "surfh_spec_supported", "surfh_spec_size", "surfh_to_spec_dev", "surfh_from_spec_dev", "surfh_forward_spec_dev",
-    "surfh_adjoint_spec_dev", "surfh_normal_spec_dev", "surfh_prior_spec_add_dev", "surfh_set_prior", "surfh_set_potential", "surfh_get_potential", "surfh_set_data_weights", "surfh_set_data_weights_dev", "surfh_has_data_weights", "surfh_set_imager", "surfh_imager_osize", "surfh_imager_forward", "surfh_imager_adjoint", "surfh_imager_forward_dev", "surfh_imager_adjoint_dev", "surfh_imager_fwadj", "surfh_set_imager_data", "surfh_has_imager_term", "surfh_dot_dev", "surfh_cg_step_dev", "surfh_cg_dir_dev", "surfh_cg_iter_dev", "surfh_residual_dev",
+    "surfh_adjoint_spec_dev", "surfh_normal_spec_dev", "surfh_prior_spec_add_dev", "surfh_set_prior", "surfh_set_potential", "surfh_get_potential", "surfh_set_prior_coupling", "surfh_get_prior_coupling", "surfh_set_data_weights", "surfh_set_data_weights_dev", "surfh_has_data_weights", "surfh_set_imager", "surfh_imager_osize", "surfh_imager_forward", "surfh_imager_adjoint", "surfh_imager_forward_dev", "surfh_imager_adjoint_dev", "surfh_imager_fwadj", "surfh_set_imager_data", "surfh_has_imager_term", "surfh_dot_dev", "surfh_cg_step_dev", "surfh_cg_dir_dev", "surfh_cg_iter_dev", "surfh_residual_dev",
     "surfh_randn_dev", "surfh_po_data_dev", "surfh_po_prior_dev", "surfh_po_moments", "surfh_po_rhs", "surfh_cg_sample",
     "surfh_cg_begin_dev", "surfh_cg_iter_nosync_dev", "surfh_cg_xupdate_nosync_dev", "surfh_cg_refresh_nosync_dev", "surfh_cg_trace",
     "surfh_profile_enable", "surfh_profile_filter", "surfh_profile_count", "surfh_profile_get", "surfh_profile_reset", "surfh_debug_copy",
     "surfh_debug_dims", "surfh_gemm_selftest", "surfh_gemm_selftest_ksteps", "surfh_gemm_selftest_ms", "surfh_klist_classify", "surfh_launch_geometry", "surfh_route_decide", "surfh_mm_step2",
-    "surfh_debug_alloc_count", "surfh_debug_alloc_fail",
+    "surfh_debug_alloc_count", "surfh_debug_alloc_fail", "surfh_debug_prior_passes",
     "surfh_shepard", "surfh_shepard_last_error", "surfh_spectral_median", "surfh_nmf_cd", "surfh_templates_last_error",
     "surfh_set_templates", "surfh_get_templates", "surfh_forward_templates", "surfh_adjoint_templates", "surfh_forward_templates_dev",
     "surfh_adjoint_templates_dev", "surfh_cg_templates", "surfh_cg_templates_cb", "surfh_joint_criterion",
@@ -154,6 +154,9 @@ def load():
     L.surfh_set_prior.argtypes = [vp, C.c_int32]
     L.surfh_set_potential.argtypes = [vp, C.c_int32, C.c_int32]
     L.surfh_get_potential.argtypes = [vp, C.c_int32]
+    L.surfh_set_prior_coupling.argtypes = [vp, C.c_int32]
+    L.surfh_debug_prior_passes.argtypes = [vp] + [C.c_int32] * 5 + [vp] * 4 + [C.c_double, C.c_double, c_double_p]
+    L.surfh_get_prior_coupling.argtypes = [vp, c_int32_p]
     L.surfh_set_data_weights.argtypes = [vp, c_float_p]
     L.surfh_set_data_weights_dev.argtypes = [vp, vp]
     L.surfh_has_data_weights.argtypes = [vp]

@@ -35,7 +35,7 @@ from .weights import weighted_sq_residual
 
 def lmm_reconstruction(data, data_model, spat_reg: float = 1.0, spat_th: float = 1.0, init=None, max_iter: int = 500,
                        tol: float = 1e-4, callback=None, weights=None, data_th=None, spat_potential="huber",
-                       data_potential="huber") -> OptimizeResult:
+                       data_potential="huber", coupling="none") -> OptimizeResult:
     """Edge-preserving reconstruction of the abundance maps (algorithms.py:73-106).
 
     ``data_model`` is a template model (``spectroSigRLSCT``); ``init=None`` starts from ``data_model.adjoint(data)``, the exact
@@ -48,13 +48,15 @@ def lmm_reconstruction(data, data_model, spat_reg: float = 1.0, spat_th: float =
     quadratic one (``spectroSigRLSCT.mmmg(data_delta=...)``); ``None``: quadratic.
     ``spat_potential`` / ``data_potential`` (the reference builds qmm.Huber; qmm takes any potential): "huber", "hyperbolic" or
     "hebert_leahy" (``surfh_amd.potentials``) under ``spat_th`` and ``data_th``; a data potential other than Huber needs ``data_th``.
+    ``coupling`` (not in the reference): "none", "isotropic" or "vector" -- which differences share one potential, ``spat_th`` then
+    the threshold on the group magnitude (``spectroSigRLSCT.mmmg(coupling=...)``).
     Returns the ``OptimizeResult`` of ``fusion.py`` (x raveled, |grad| of every iterate)."""
     if init is None:
         init = _weighted_start(data, data_model, weights)
     t0 = time.time()
     x, gn, nit = data_model.mmmg(data, mu=1.0, mu_reg=float(spat_reg), x0=init, max_iter=int(max_iter), tol=float(tol),
                                  callback=callback, delta=float(spat_th), weights=weights, potential=spat_potential,
-                                 data_potential=data_potential, **_robust_kw(data_th))
+                                 data_potential=data_potential, coupling=coupling, **_robust_kw(data_th))
     return OptimizeResult(x=x.ravel(), grad_norm=list(gn), nit=nit, success=bool(gn[-1] < x.size * tol), time=time.time() - t0)
 
 

@@ -203,6 +203,18 @@ int launch_huber_grad(hipStream_t s, const float *x, const float *src, float *ou
 // sums[0..2] = sum_k sum w(D_k x) (D_k p0)^2, (D_k p0)(D_k p1), (D_k p1)^2: the prior block of the half-quadratic majorant
 int launch_huber_curv(hipStream_t s, const float *x, const float *p0, const float *p1, int T, int na, int nb, float delta,
                       int kind, double *scratch, double *sums);
+// The same prior with one potential per group of differences (coupled_prior.hip; surfh_set_prior_coupling): `coupling` 1 isotropic,
+// m = sqrt(u_r^2 + u_c^2) per (t, i, j); 2 vector, m = sqrt(sum_t u_r^2 + u_c^2) per (i, j); anything else is hipErrorInvalidValue.
+// w = the weight field w(m) = phi'(m) / m, coupled_weights_floats() floats ([T][na][nb] or [na][nb]); phi_sum[0] = sum phi(m)
+size_t coupled_weights_floats(int coupling, int T, int na, int nb);
+int launch_coupled_weights(hipStream_t s, const float *x, float *w, int T, int na, int nb, float delta, int kind, int coupling,
+                           double *scratch, double *phi_sum);
+// out = src + coef * sum_k D_k^T (w D_k x) under the field `w` of x (out may alias src); gg_sum[0] = out.out
+int launch_coupled_grad(hipStream_t s, const float *x, const float *w, const float *src, float *out, int T, int na, int nb, float coef,
+                        int coupling, double *scratch, double *gg_sum);
+// sums[0..2] = sum_k sum w (D_k p0)^2, (D_k p0)(D_k p1), (D_k p1)^2 under the field `w`
+int launch_coupled_curv(hipStream_t s, const float *w, const float *p0, const float *p1, int T, int na, int nb, int coupling,
+                        double *scratch, double *sums);
 // The same potentials on the cube [Lc][na][nb] (huber_vox.hip): the in-plane circular differences under the threshold ds and the
 // open wavelength difference u_l = x[l+1] - x[l], l = 0 .. Lc-2, under dl.  `scratch` holds launch_huber_vox_scratch_doubles().
 // out = src + cs sum_{k in r,c} D_k^T phi'_ds(D_k x) + cl Dl^T phi'_dl(Dl x) in one pass (out may alias src);

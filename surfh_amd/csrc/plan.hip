@@ -1038,6 +1038,17 @@ int surfh_get_potential(const surfh_plan *p, int32_t slot) {
     }
     return p->pot[slot];
 }
+int surfh_set_prior_coupling(surfh_plan *p, int32_t coupling) {
+    if (coupling < 0 || coupling > 2) return fail("prior coupling %d: 0 = none, 1 = isotropic, 2 = vector", (int)coupling);
+    if (!p) return fail("null plan");
+    p->coupling = coupling;
+    return 0;
+}
+int surfh_get_prior_coupling(const surfh_plan *p, int32_t *coupling) {
+    if (!p || !coupling) return fail("null argument");
+    *coupling = p->coupling;
+    return 0;
+}
 // ---- data weights: plan state, like the prior ------------------------------------------------------------------------------------
 namespace {
 // installs the validated device weights w_new [osize] (taken over) or, with an empty buffer, clears the state; on failure the

@@ -233,6 +233,9 @@ struct surfh_plan : PlanHandles {
     // surfh_set_potential: the potential of the spatial prior (maps, planes, the cube's rows / columns), of the cube's spectral
     // prior and of the robust data term; 0 Huber, 1 hyperbolic, 2 Hebert-Leahy (huber_dev.h)
     int pot[3] = {0, 0, 0};
+    // surfh_set_prior_coupling: how the maps' spatial prior groups its differences; 0 none (one potential per difference),
+    // 1 isotropic, 2 vector (coupled_prior.hip)
+    int coupling = 0;
     // which transform kernels run and which fusions ride on them: written once, by surfh_plan_create from decide_route.  On an
     // interleaved route the plan's complex arrays (sotf, spec, ycol*, and mhat when T == 0) are [..][LP][2] instead of planar [2][..][LP]
     Route route;
@@ -284,6 +287,7 @@ struct surfh_plan : PlanHandles {
     // CG
     DevBuf<float> cg_x, cg_r, cg_d, cg_q, cg_b, cg_y, cg_qm, cg_dd;
     DevBuf<float> cg_hg;                           // surfh_mmmg_huber(_vox): -gradient of the non-quadratic criterion
+    DevBuf<float> cpl_w;                           // coupled prior: the weight field of the current iterate [isize], allocated on first use
     DevBuf<float> rb_y, rb_u, rb_ag, rb_am;       // surfh_mmmg_robust(_vox): y, A x, A (-g), A m [osize]
     DevBuf<double> dscal, dscratch;                 // [16] device scalars, partial sums (>= 1024, and what huber_vox.hip and robust_data.hip ask for)
     // posterior sampling (surfh_cg_sample): y, the noise vectors eps_y [osize], eps_r / eps_c [isize], eta and the unperturbed

@@ -139,6 +139,13 @@ int imager_refuse(const surfh_plan *p, const char *who) {
                     "surfh_mmmg or surfh_mmmg_huber", who);
     return 0;
 }
+// the prior coupling acts on the maps' spatial prior only: the solvers and passes of the planes and of the cube say so
+int coupling_refuse(const surfh_plan *p, const char *who) {
+    if (p && p->coupling != 0)
+        return fail("%s does not carry the prior coupling set on this plan (surfh_set_prior_coupling: %d): set it to 0, or use "
+                    "surfh_mmmg_huber or surfh_mmmg_robust", who, p->coupling);
+    return 0;
+}
 // cg_b = mu A^T W y (+ extra), cg_q = Q x, cg_r = cg_b - cg_q; y on the device, x already holding the start
 int solver_setup(surfh_plan *p, const float *y, const float *x, double mu, double mu_reg, const float *extra = nullptr) {
     if (!(y = weighted_data(p, y))) return 1;
@@ -1034,13 +1041,52 @@ int huber_args(double mu_reg, double delta) {
     if (!(delta >= (double)FLT_MIN)) return fail("Huber prior: delta must be at least %g (fp32 kernels; got %g)", (double)FLT_MIN, delta);
     return 0;
 }
+
+// ---- the coupled prior of the maps (surfh_set_prior_coupling; coupled_prior.hip): w(m) of the group magnitudes is computed once
+// per iterate into cpl_w and read by the gradient pass and by the curvature pass.
+// the plan can run its coupling (0: nothing to do): the separated differences, and room for the weight field
+int coupling_ready(surfh_plan *p, const char *who) {
+    if (p->coupling == 0) return 0;
+    if (p->prior_kind != 0)
+        return fail("%s: the prior coupling (surfh_set_prior_coupling: %d) groups the separated differences; the plan is on the joint "
+                    "Laplacian prior (surfh_set_prior)", who, p->coupling);
+    HIP_OK(hipSetDevice(p->dev));
+    return ensure_set(member(p->cpl_w, (size_t)p->isize));
+}
+// cpl_w = the weight field of x; phi_sum[0] = the prior value sum phi(m)
+int coupled_field(surfh_plan *p, const float *x, float delta, int kind, int coupling, double *phi_sum) {
+    Prof pr(p, "coupled_weights");
+    LAUNCH_OK(launch_coupled_weights(p->stream, x, p->cpl_w, p->T, p->Na, p->Nb, delta, kind, coupling, p->dscratch, phi_sum));
+    return 0;
+}
+// out = src + coef sum_k D_k^T (w D_k x) with the field of x computed first; sums[0] = out.out, sums[1] = sum phi(m)
+int coupled_grad(surfh_plan *p, const float *x, const float *src, float *out, float coef, float delta, int kind, int coupling,
+                 double *sums) {
+    if (coupled_field(p, x, delta, kind, coupling, sums + 1)) return 1;
+    Prof pr(p, "coupled_grad");
+    LAUNCH_OK(launch_coupled_grad(p->stream, x, p->cpl_w, src, out, p->T, p->Na, p->Nb, coef, coupling, p->dscratch, sums));
+    return 0;
+}
+// sums[0..2] = the prior block of (p0, p1) under the field cpl_w holds
+int coupled_curv(surfh_plan *p, const float *p0, const float *p1, int coupling, double *sums) {
+    Prof pr(p, "coupled_curv");
+    LAUNCH_OK(launch_coupled_curv(p->stream, p->cpl_w, p0, p1, p->T, p->Na, p->Nb, coupling, p->dscratch, sums));
+    return 0;
+}
 }  // namespace
 
 int surfh_huber_prior_dev(surfh_plan *p, const float *x_dev, float *g_dev, double mu_reg, double delta, double *value) {
     if (!p || !x_dev || !g_dev) return fail("null argument");
     if (p->T <= 0) return fail("prior is defined on abundance maps (needs templates)");
-    if (huber_args(mu_reg, delta)) return 1;
+    if (huber_args(mu_reg, delta) || coupling_ready(p, "surfh_huber_prior_dev")) return 1;
     double h[2];
+    if (p->coupling) {
+        if (coupled_grad(p, x_dev, g_dev, g_dev, (float)mu_reg, (float)delta, p->pot[0], p->coupling, p->dscal)) return 1;
+        HIP_OK(hipMemcpyAsync(h, p->dscal, 2 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+        HIP_OK(hipStreamSynchronize(p->stream));
+        if (value) *value = h[1];
+        return 0;
+    }
     const auto pass = [&] {
         return launch_huber_grad(p->stream, x_dev, g_dev, g_dev, p->T, p->Na, p->Nb, (float)mu_reg, (float)delta, p->pot[0], p->dscratch,
                                  p->dscal);
@@ -1052,11 +1098,48 @@ int surfh_huber_prior_dev(surfh_plan *p, const float *x_dev, float *g_dev, doubl
 int surfh_huber_curv_dev(surfh_plan *p, const float *x_dev, const float *p0_dev, const float *p1_dev, double delta, double *sums) {
     if (!p || !x_dev || !p0_dev || !p1_dev || !sums) return fail("null argument");
     if (p->T <= 0) return fail("prior is defined on abundance maps (needs templates)");
-    if (huber_args(0.0, delta)) return 1;
+    if (huber_args(0.0, delta) || coupling_ready(p, "surfh_huber_curv_dev")) return 1;
+    if (p->coupling) {                                     // the field of x first (its prior value lands behind the block)
+        if (coupled_field(p, x_dev, (float)delta, p->pot[0], p->coupling, p->dscal + 3) ||
+            coupled_curv(p, p0_dev, p1_dev, p->coupling, p->dscal))
+            return 1;
+        HIP_OK(hipMemcpyAsync(sums, p->dscal, 3 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+        HIP_OK(hipStreamSynchronize(p->stream));
+        return 0;
+    }
     const auto pass = [&] {
         return launch_huber_curv(p->stream, x_dev, p0_dev, p1_dev, p->T, p->Na, p->Nb, (float)delta, p->pot[0], p->dscratch, p->dscal);
     };
     return diag_pass(p, "huber_curv", pass, p->dscal, sums, 3);
+}
+
+// The maps' prior passes on arrays of any shape [T][na][nb], whatever the plan's own (a plan cannot have an axis of length 1):
+// the launchers surfh_huber_prior_dev / surfh_huber_curv_dev call, under an explicit kind and coupling, on the plan's stream and
+// scratch.  sums [5] (host) = g.g, the prior value, the curvature block.
+int surfh_debug_prior_passes(surfh_plan *p, int32_t T, int32_t na, int32_t nb, int32_t kind, int32_t coupling, const float *x_dev,
+                             float *g_dev, const float *p0_dev, const float *p1_dev, double mu_reg, double delta, double *sums) {
+    if (!p || !x_dev || !g_dev || !p0_dev || !p1_dev || !sums) return fail("null argument");
+    if (T < 1 || na < 1 || nb < 1 || (double)T * na * nb > 2147483647.0) return fail("surfh_debug_prior_passes: shape %d x %d x %d", (int)T, (int)na, (int)nb);
+    if (kind < 0 || kind > 2 || coupling < 0 || coupling > 2) return fail("surfh_debug_prior_passes: kind %d, coupling %d", (int)kind, (int)coupling);
+    if (huber_args(mu_reg, delta)) return 1;
+    HIP_OK(hipSetDevice(p->dev));
+    hipStream_t s = p->stream;
+    double *sc = p->dscal;
+    DevBuf<float> w;
+    if (coupling) {
+        if (w.alloc(coupled_weights_floats(coupling, T, na, nb))) return 1;
+        LAUNCH_OK(launch_coupled_weights(s, x_dev, w, T, na, nb, (float)delta, kind, coupling, p->dscratch, sc + 1));
+        LAUNCH_OK(launch_coupled_grad(s, x_dev, w, g_dev, g_dev, T, na, nb, (float)mu_reg, coupling, p->dscratch, sc));
+        LAUNCH_OK(launch_coupled_curv(s, w, p0_dev, p1_dev, T, na, nb, coupling, p->dscratch, sc + 2));
+    } else {
+        LAUNCH_OK(launch_huber_grad(s, x_dev, g_dev, g_dev, T, na, nb, (float)mu_reg, (float)delta, kind, p->dscratch, sc));
+        LAUNCH_OK(launch_huber_curv(s, x_dev, p0_dev, p1_dev, T, na, nb, (float)delta, kind, p->dscratch, sc + 2));
+    }
+    const hipError_t e = hipMemcpyAsync(sums, sc, 5 * sizeof(double), hipMemcpyDeviceToHost, s);
+    const hipError_t e2 = hipStreamSynchronize(s);          // before `w` goes away
+    HIP_OK(e);
+    HIP_OK(e2);
+    return 0;
 }
 
 namespace {
@@ -1064,6 +1147,7 @@ namespace {
 // vectors.  grad: out = src - sum_f reg[f] D_f^T phi'(D_f x), sums[0] = out.out, sums[1 + f] = sum phi of family f;
 // curv: sums[3 f ..] = the (p0, p0), (p0, p1), (p1, p1) block of family f under w(D_f x).  The weights enter on the host, in float64.
 // nfam = 0 is the quadratic solver: out is src itself (grad leaves sums[0] = src.src), the prior is quad_reg's, in the operator.
+// Every loop calls grad on the iterate and then curv on the same iterate: under a coupling, curv reads the weight field grad left.
 struct HuberPrior {
     int nfam;
     double reg[2];
@@ -1073,6 +1157,7 @@ struct HuberPrior {
     float delta[2];
     int kind[2];                                                            // the potential of each family (surfh_set_potential)
     double quad_reg;                                                        // weight of the quadratic prior the operator carries
+    int coupling;                                                           // the maps' family: surfh_set_prior_coupling (0: none)
 };
 
 // the loop of the map and cube solvers; prior_values receives nfam doubles (may be NULL)
@@ -1157,11 +1242,13 @@ int quad_grad(surfh_plan *p, const HuberPrior &, const float *, const float *src
 int quad_curv(surfh_plan *, const HuberPrior &, const float *, const float *, const float *, double *) { return 0; }
 // the maps' prior: one family (rows and columns under one weight and one threshold)
 int maps_grad(surfh_plan *p, const HuberPrior &h, const float *x, const float *src, float *out, double *sums) {
+    if (h.coupling) return coupled_grad(p, x, src, out, -(float)h.reg[0], h.delta[0], h.kind[0], h.coupling, sums);
     Prof pr(p, "huber_grad");
     LAUNCH_OK(launch_huber_grad(p->stream, x, src, out, p->T, p->Na, p->Nb, -(float)h.reg[0], h.delta[0], h.kind[0], p->dscratch, sums));
     return 0;
 }
 int maps_curv(surfh_plan *p, const HuberPrior &h, const float *x, const float *p0, const float *p1, double *sums) {
+    if (h.coupling) return coupled_curv(p, p0, p1, h.coupling, sums);
     Prof pr(p, "huber_curv");
     LAUNCH_OK(launch_huber_curv(p->stream, x, p0, p1, p->T, p->Na, p->Nb, h.delta[0], h.kind[0], p->dscratch, sums));
     return 0;
@@ -1186,8 +1273,8 @@ int surfh_mmmg_huber(surfh_plan *p, const float *y, double mu, double mu_reg, do
                      surfh_cg_callback callback, void *user) {
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
     if (p->T <= 0) return fail("surfh_mmmg_huber needs templates (the priors act on abundance maps)");
-    if (huber_args(mu_reg, delta)) return 1;
-    const HuberPrior hp = {1, {mu_reg, 0.0}, "Huber", maps_grad, maps_curv, {(float)delta, 0.f}, {p->pot[0], 0}};
+    if (huber_args(mu_reg, delta) || coupling_ready(p, "surfh_mmmg_huber")) return 1;
+    const HuberPrior hp = {1, {mu_reg, 0.0}, "Huber", maps_grad, maps_curv, {(float)delta, 0.f}, {p->pot[0], 0}, 0.0, p->coupling};
     return mmmg_huber_loop(p, hp, y, mu, x0, max_iter, tol, refresh, x, grad_norm, nit, prior_value, callback, user);
 }
 
@@ -1206,7 +1293,7 @@ int surfh_huber_vox_prior_dev(surfh_plan *p, const float *x_dev, float *g_dev, d
                               double spec_delta, double *values) {
     if (!p || !x_dev || !g_dev) return fail("null argument");
     if (p->T > 0) return fail("the voxel-wise prior is defined on the cube (needs a plan without templates)");
-    if (huber_args(spat_reg, spat_delta) || huber_args(spec_reg, spec_delta)) return 1;
+    if (huber_args(spat_reg, spat_delta) || huber_args(spec_reg, spec_delta) || coupling_refuse(p, "surfh_huber_vox_prior_dev")) return 1;
     double h[3];
     const auto pass = [&] {
         return launch_huber_vox_grad(p->stream, x_dev, g_dev, g_dev, p->Lc, p->Na, p->Nb, (float)spat_reg, (float)spat_delta,
@@ -1223,7 +1310,7 @@ int surfh_huber_vox_curv_dev(surfh_plan *p, const float *x_dev, const float *p0_
                              double spec_delta, double *sums) {
     if (!p || !x_dev || !p0_dev || !p1_dev || !sums) return fail("null argument");
     if (p->T > 0) return fail("the voxel-wise prior is defined on the cube (needs a plan without templates)");
-    if (huber_args(0.0, spat_delta) || huber_args(0.0, spec_delta)) return 1;
+    if (huber_args(0.0, spat_delta) || huber_args(0.0, spec_delta) || coupling_refuse(p, "surfh_huber_vox_curv_dev")) return 1;
     const auto pass = [&] {
         return launch_huber_vox_curv(p->stream, x_dev, p0_dev, p1_dev, p->Lc, p->Na, p->Nb, (float)spat_delta, (float)spec_delta,
                                      p->pot[0], p->pot[1], p->dscratch, p->dscal);
@@ -1235,7 +1322,7 @@ int surfh_mmmg_huber_vox(surfh_plan *p, const float *y, double mu, double spat_r
                          double spec_delta, const float *x0, int32_t max_iter, double tol, int32_t refresh, float *x,
                          double *grad_norm, int32_t *nit, double *prior_values, surfh_cg_callback callback, void *user) {
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
-    if (imager_refuse(p, "surfh_mmmg_huber_vox")) return 1;
+    if (imager_refuse(p, "surfh_mmmg_huber_vox") || coupling_refuse(p, "surfh_mmmg_huber_vox")) return 1;
     if (p->T > 0) return fail("surfh_mmmg_huber_vox reconstructs the cube: it needs a plan without templates (n_templates = 0)");
     if (huber_args(spat_reg, spat_delta) || huber_args(spec_reg, spec_delta)) return 1;
     const HuberPrior hp = {2, {spat_reg, spec_reg}, "Huber, voxel-wise", vox_grad, vox_curv, {(float)spat_delta, (float)spec_delta},
@@ -1351,8 +1438,8 @@ int surfh_mmmg_robust(surfh_plan *p, const float *y, double mu, double data_delt
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
     if (imager_refuse(p, "surfh_mmmg_robust")) return 1;
     if (p->T <= 0) return fail("surfh_mmmg_robust needs templates (the priors act on abundance maps)");
-    if (robust_args(data_delta) || huber_args(mu_reg, delta)) return 1;
-    const HuberPrior hp = {1, {mu_reg, 0.0}, "Huber", maps_grad, maps_curv, {(float)delta, 0.f}, {p->pot[0], 0}};
+    if (robust_args(data_delta) || huber_args(mu_reg, delta) || coupling_ready(p, "surfh_mmmg_robust")) return 1;
+    const HuberPrior hp = {1, {mu_reg, 0.0}, "Huber", maps_grad, maps_curv, {(float)delta, 0.f}, {p->pot[0], 0}, 0.0, p->coupling};
     return mmmg_robust_loop(p, hp, y, mu, data_delta, x0, max_iter, tol, refresh, x, grad_norm, nit, values, omega_out, callback, user);
 }
 
@@ -1361,7 +1448,7 @@ int surfh_mmmg_robust_vox(surfh_plan *p, const float *y, double mu, double data_
                           float *x, double *grad_norm, int32_t *nit, double *values, float *omega_out, surfh_cg_callback callback,
                           void *user) {
     if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
-    if (imager_refuse(p, "surfh_mmmg_robust_vox")) return 1;
+    if (imager_refuse(p, "surfh_mmmg_robust_vox") || coupling_refuse(p, "surfh_mmmg_robust_vox")) return 1;
     if (p->T > 0) return fail("surfh_mmmg_robust_vox reconstructs the cube: it needs a plan without templates (n_templates = 0)");
     if (robust_args(data_delta) || huber_args(spat_reg, spat_delta) || huber_args(spec_reg, spec_delta)) return 1;
     const HuberPrior hp = {2, {spat_reg, spec_reg}, "Huber, voxel-wise", vox_grad, vox_curv, {(float)spat_delta, (float)spec_delta},
@@ -1512,7 +1599,7 @@ int surfh_mmmg_planes(surfh_plan *p, const float *y, double mu, double mu_reg, c
 // (d_l, m_l) by linearity in float64, solves and moves.
 namespace {
 int huber_planes_ready(surfh_plan *p, const char *who) {
-    if (imager_refuse(p, who)) return 1;
+    if (imager_refuse(p, who) || coupling_refuse(p, who)) return 1;
     if (p->T != 0) return fail("%s works on the plane-wise (no template) model; the maps of a template model take surfh_mmmg_huber", who);
     if (p->ch.empty()) return fail("plan has no channel");
     HIP_OK(hipSetDevice(p->dev));

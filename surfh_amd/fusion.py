@@ -20,7 +20,7 @@ import numpy as np
 
 from . import instru
 from .models import spectroSigRLSCT
-from .potentials import kind_name, need_delta
+from .potentials import coupling_code, coupling_name, kind_name, need_delta, need_delta_coupling
 from .weights import check_data_weights, weighted_sq_residual, weights_from_data  # noqa: F401  (weights_from_data: public here)
 
 
@@ -36,7 +36,7 @@ class OptimizeResult:
 class QuadCriterion_MRS:
     def __init__(self, mu_spectro, y_spectro, model_spectro, mu_reg, printing=False, gradient="separated", delta=None, weights=None,
                  data_delta=None, potential="huber", data_potential="huber", mu_imager=None, y_imager=None, model_imager=None,
-                 weights_imager=None):
+                 weights_imager=None, coupling="none"):
         """``gradient="joint"`` regularises with the Laplacian of ``Difference_Operator_Joint`` (fusion_CT.py:45-62); udft's
         ``laplacian(2)`` is absent from the reference tree, the 3 x 3 kernel [[0,-1,0],[-1,4,-1],[0,-1,0]] is restated: parity
         unpinned for that option (the operator is checked against the oracle's Fourier-domain form of the same kernel).
@@ -56,6 +56,10 @@ class QuadCriterion_MRS:
         ``potential`` / ``data_potential`` (Hebert-Leahy is what fusion_CT.py imports beside Huber): the potential under ``delta``
         and under ``data_delta``, "huber" (the default), "hyperbolic" or "hebert_leahy" (``surfh_amd.potentials``); another one
         than Huber needs its threshold.
+        ``coupling`` (not in fusion_CT.py): which differences share one potential under ``delta`` -- "none" (each its own, the
+        default), "isotropic" (phi(sqrt(u_r^2 + u_c^2)) per pixel and map) or "vector" (phi(sqrt(sum_t u_r^2 + u_c^2)) per pixel:
+        edges co-locate across maps); ``delta`` is then the threshold on the group magnitude (``surfh_amd.potentials``).  A
+        coupling needs ``delta``.
         ``mu_imager`` / ``y_imager`` / ``model_imager`` (the names fusion_CT.py reserves, :68, :243-261): the second instrument,
         an ``ImagerModel`` built on ``model_spectro``, its data ``[F, Na//d, Nb//d]`` and weight: the criterion gains
         mu_imager (y_im - A_im x)^T W_im (y_im - A_im x) / 2 (``weights_imager``, not in fusion_CT.py: ``W_im``, 1 by default;
@@ -77,6 +81,8 @@ class QuadCriterion_MRS:
         self.potential, self.data_potential = kind_name(potential), kind_name(data_potential)
         need_delta(potential, delta, "delta")
         need_delta(data_potential, data_delta, "data_delta")
+        self.coupling = coupling_name(coupling)
+        need_delta_coupling(coupling, delta)
         assert isinstance(mu_reg, (float, int, list, np.ndarray))
         if gradient not in ("separated", "joint"):
             raise ValueError(f"gradient must be 'separated' or 'joint', not {gradient!r}")
@@ -179,6 +185,8 @@ class QuadCriterion_MRS:
                 kw["potential"] = self.potential
             if self.data_potential != "huber":
                 kw["data_potential"] = self.data_potential
+            if self.coupling != "none":
+                kw["coupling"] = self.coupling
             if self.imager is not None:
                 if self.model_spectro.imager is not self.model_imager:
                     self.model_spectro.set_imager(self.model_imager)
@@ -220,7 +228,8 @@ class QuadCriterion_MRS:
 
     def get_crit_val(self, x_hat):
         """(mu |y - A x|^2 + mu_reg (|Dr x|^2 + |Dc x|^2)) / 2   (fusion_CT.py:242-265); with ``delta``
-        mu |y - A x|^2 / 2 + mu_reg sum phi(Dr x) + phi(Dc x), phi the Huber potential (that criterion's limit delta -> inf).
+        mu |y - A x|^2 / 2 + mu_reg sum phi(Dr x) + phi(Dc x), phi the Huber potential (that criterion's limit delta -> inf);
+        under a ``coupling`` the prior is mu_reg sum phi(m) over the group magnitudes (``potentials.prior_value``).
         Under data weights (this criterion's, else the model's) |y - A x|^2 is sum w (y - A x)^2 over the samples with w > 0.
         With ``data_delta`` the data term is mu sum phi(sqrt(w) (y - A x)) over those samples instead of mu |y - A x|^2 / 2."""
         x_hat = np.asarray(x_hat).reshape(self.shape_of_output)
@@ -235,6 +244,9 @@ class QuadCriterion_MRS:
                 self.model_spectro.set_imager(self.model_imager)
             y_im, w_im, mu_im = self.imager
             data = data + mu_im * weighted_sq_residual(y_im, self.model_imager.forward(x_hat), w_im)
+        if self.delta is not None and self.coupling != "none":
+            from .potentials import prior_value
+            return data / 2 + self.mu_reg * prior_value(x_hat, self.delta, self.potential, self.coupling)
         if self.delta is not None:
             return data / 2 + self.mu_reg * (_phi(np.roll(x_hat, 1, axis=1) - x_hat, self.delta, self.potential).sum() +
                                              _phi(np.roll(x_hat, 1, axis=2) - x_hat, self.delta, self.potential).sum())

@@ -464,7 +464,7 @@ class spectroSigRLSCT(DataWeights, TemplateOps, NonnegOps, _pot.Potentials, LinO
         _lib.check(self._L.surfh_po_prior_dev(self._plan, _ptr(er_t), _ptr(ec_t), float(mu_reg), _ptr(out_t)))
 
     def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, delta=None, weights=None,
-             data_delta=None, potential="huber", data_potential="huber", imager=None):
+             data_delta=None, potential="huber", data_potential="huber", imager=None, coupling="none"):
         """Device-resident 3MG (qmm.mmmg restated for quadratic objectives; the reference's ``method='mmmg'``,
         fusion_CT.py:194-198).  Same arguments as ``cg``; ``grad_norm`` holds |grad| (not squared) of every iterate.
 
@@ -488,13 +488,25 @@ class spectroSigRLSCT(DataWeights, TemplateOps, NonnegOps, _pot.Potentials, LinO
         samples past the knee, |t| > data_delta, whatever the potential.
 
         ``imager=(y_im, mu_imager[, w_im])``: the imager's data term for this solve, as in ``cg``; not with ``data_delta``
-        (``ValueError`` before the library is reached)."""
+        (``ValueError`` before the library is reached).
+
+        ``coupling``: which differences share one potential under ``delta``, for this call -- "none" (the default: each its own),
+        "isotropic" (the row and the column difference of a pixel, ``phi(sqrt(u_r^2 + u_c^2))``) or "vector" (those of all ``T``
+        maps at a pixel, ``phi(sqrt(sum_t u_r^2 + u_c^2))``: edges co-locate across maps); ``surfh_amd.potentials``.  ``delta`` is
+        then the threshold on the **group magnitude**: for comparable behaviour it grows like ``sqrt(2)``, and like
+        ``sqrt(2 T)`` for "vector".  It composes with ``potential``, ``data_delta``, ``weights`` and ``imager``; the plan's
+        coupling (``set_prior_coupling``) is put back afterwards.  ``ValueError`` for a coupling without ``delta`` and on a model
+        whose prior is the joint Laplacian (``set_prior('joint')``)."""
         _pot.need_delta(potential, delta, "delta")
+        _pot.need_delta_coupling(coupling, delta)
+        if _pot.coupling_code(coupling) != 0 and self.get_prior() != "separated":
+            raise ValueError("a prior coupling groups the separated differences: set_prior('separated')")
         _pot.need_delta(data_potential, data_delta, "data_delta")
         if data_delta is not None:
             self._refuse_imager("the robust data term (data_delta)", imager)
         with_imager = self.installed_imager(imager)             # checked here, before any library call
-        with _pot.installed(self, spatial=potential, data=data_potential), with_imager:
+        with_coupling = _pot.installed_coupling(self, coupling if delta is not None else None)
+        with _pot.installed(self, spatial=potential, data=data_potential), with_coupling, with_imager:
             return self._mmmg(data, mu, mu_reg, x0, max_iter, tol, refresh, callback, delta, weights, data_delta)
 
     def _mmmg(self, data, mu, mu_reg, x0, max_iter, tol, refresh, callback, delta, weights, data_delta):
@@ -516,7 +528,9 @@ class spectroSigRLSCT(DataWeights, TemplateOps, NonnegOps, _pot.Potentials, LinO
         return x, gn, nit
 
     def huber_curv_dev(self, x_t, p0_t, p1_t, delta: float) -> np.ndarray:
-        """sum_k sum w(D_k x) (D_k p0)^2, (D_k p0)(D_k p1), (D_k p1)^2 on device maps: the prior block of the Huber majorant."""
+        """sum_k sum w(D_k x) (D_k p0)^2, (D_k p0)(D_k p1), (D_k p1)^2 on device maps: the prior block of the Huber majorant.
+        Under a coupling of the plan (``set_prior_coupling``) w is the weight of the difference's group, w(m), and ``delta`` the
+        threshold on the group magnitude m."""
         out = np.zeros(3, dtype=np.float64)
         _lib.check(self._L.surfh_huber_curv_dev(self._plan, _ptr(x_t), _ptr(p0_t), _ptr(p1_t), float(delta), _lib.dptr(out)))
         return out
@@ -537,10 +551,23 @@ class spectroSigRLSCT(DataWeights, TemplateOps, NonnegOps, _pot.Potentials, LinO
         return out
 
     def huber_prior_dev(self, x_t, g_t, mu_reg: float, delta: float) -> float:
-        """g += mu_reg sum_k D_k^T phi'(D_k x) on device maps [T, Na, Nb]; returns sum_k sum phi(D_k x) (synchronises)."""
+        """g += mu_reg sum_k D_k^T phi'(D_k x) on device maps [T, Na, Nb]; returns sum_k sum phi(D_k x) (synchronises).  Under a
+        coupling of the plan (``set_prior_coupling``): g += mu_reg sum_k D_k^T (w(m) D_k x), returns sum phi(m) over the groups,
+        ``delta`` the threshold on the group magnitude m (``potentials.group_magnitude``)."""
         out = C.c_double()
         _lib.check(self._L.surfh_huber_prior_dev(self._plan, _ptr(x_t), _ptr(g_t), float(mu_reg), float(delta), C.byref(out)))
         return out.value
+
+    def prior_passes_dev(self, x_t, g_t, p0_t, p1_t, mu_reg: float, delta: float, potential="huber", coupling="none"):
+        """Diagnostic: ``huber_prior_dev`` and ``huber_curv_dev`` in one call on device arrays of any shape ``[T, Na, Nb]`` (every
+        extent >= 1, whatever the model's own shape), under an explicit potential and coupling; the plan's state is not consulted.
+        Returns (g.g, prior value, curvature block [3]) (synchronises)."""
+        T, na, nb = (int(v) for v in x_t.shape)
+        out = np.zeros(5, dtype=np.float64)
+        _lib.check(self._L.surfh_debug_prior_passes(self._plan, T, na, nb, _pot.kind_code(potential), _pot.coupling_code(coupling),
+                                                    _ptr(x_t), _ptr(g_t), _ptr(p0_t), _ptr(p1_t), float(mu_reg), float(delta),
+                                                    _lib.dptr(out)))
+        return float(out[0]), float(out[1]), out[2:].copy()
 
     # ---- the cube itself under Huber priors (models without templates) -----------------------
     def mmmg_vox(self, data, mu=1.0, spat_reg=1.0, spat_delta=1.0, spec_reg=1.0, spec_delta=1.0, x0=None, max_iter=10, tol=1e-12,

@@ -12,6 +12,17 @@ The right-hand forms carry no ``delta^2`` factor, so ``delta = inf`` gives ``u^2
 ``u w``.  Every ``w`` is in (0, 1] and non-increasing in |u|: ``phi(sqrt(.))`` is concave, the Geman-Reynolds majorant holds.
 Hebert-Leahy is not convex: 3MG still descends, to a local minimum that depends on the start.
 
+The spatial prior of the maps also has a **coupling** (include/surfh_amd.h: surfh_set_prior_coupling), orthogonal to the potential:
+which circular first differences ``u_r = Dr x``, ``u_c = Dc x`` share one ``phi``:
+
+    none (0)       sum_t sum_ij phi(u_r) + phi(u_c)              one potential per difference (the default)
+    isotropic (1)  sum_t sum_ij phi(sqrt(u_r^2 + u_c^2))         edges pay the same at every angle to the pixel grid
+    vector (2)     sum_ij phi(sqrt(sum_t u_r^2 + u_c^2))         one edge per pixel for all maps: edges co-locate across maps
+
+``delta`` is then the threshold on the **group magnitude** (the square root): for comparable behaviour it grows like ``sqrt(2)``
+under "isotropic" and like ``sqrt(2 T)`` under "vector".  ``group_magnitude`` and ``prior_value`` restate both in float64;
+``installed_coupling`` sets the coupling for one call.
+
 A model's potentials are plan state in three slots (``SLOTS``); ``installed(model, spatial=..., spectral=..., data=...)`` sets them
 for the duration of a solve and puts back what the plan held, the way ``installed_weights`` treats the data weights.
 """
@@ -37,6 +48,29 @@ def kind_code(potential) -> int:
 
 def kind_name(potential) -> str:
     return NAMES[kind_code(potential)]
+
+
+COUPLINGS = {"none": 0, "isotropic": 1, "vector": 2}
+COUPLING_NAMES = tuple(COUPLINGS)                          # COUPLING_NAMES[code] is the name
+
+
+def coupling_code(coupling) -> int:
+    """The C ABI's code of a prior coupling given by name (or by code).  ``ValueError`` on anything else."""
+    if isinstance(coupling, str) and coupling in COUPLINGS:
+        return COUPLINGS[coupling]
+    if isinstance(coupling, (int, np.integer)) and not isinstance(coupling, bool) and 0 <= int(coupling) < len(COUPLING_NAMES):
+        return int(coupling)
+    raise ValueError(f"coupling must be one of {', '.join(COUPLING_NAMES)}, not {coupling!r}")
+
+
+def coupling_name(coupling) -> str:
+    return COUPLING_NAMES[coupling_code(coupling)]
+
+
+def need_delta_coupling(coupling, delta):
+    """A coupling of the quadratic prior means nothing (every coupling of it is the same prior): ``ValueError``."""
+    if coupling_code(coupling) != 0 and delta is None:
+        raise ValueError(f"coupling {coupling_name(coupling)!r} needs delta: a coupling of the quadratic prior means nothing")
 
 
 def need_delta(potential, delta, what="delta"):
@@ -89,6 +123,55 @@ def phi(u, delta, potential="huber"):
     return 0.5 * u * u * ratio
 
 
+def group_magnitude(x, coupling="none"):
+    """The magnitudes the potential is applied to, in float64, for maps ``x`` ``[T, Na, Nb]`` and the circular differences
+    ``u_r = roll(x, 1, axis 1) - x``, ``u_c = roll(x, 1, axis 2) - x``: "none" ``[2, T, Na, Nb]`` (|u_r|, |u_c|), "isotropic"
+    ``[T, Na, Nb]`` (sqrt(u_r^2 + u_c^2)), "vector" ``[Na, Nb]`` (sqrt(sum_t u_r^2 + u_c^2))."""
+    c = coupling_code(coupling)
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 3:
+        raise ValueError(f"group_magnitude takes maps [T, Na, Nb], not an array of shape {x.shape}")
+    ur, uc = np.roll(x, 1, axis=1) - x, np.roll(x, 1, axis=2) - x
+    if c == 0:
+        return np.abs(np.stack([ur, uc]))
+    m2 = ur * ur + uc * uc
+    return np.sqrt(m2 if c == 1 else m2.sum(axis=0))
+
+
+def prior_value(x, delta, potential="huber", coupling="none"):
+    """``sum phi(m)`` over the magnitudes of ``group_magnitude(x, coupling)`` in float64: the value of the maps' spatial prior
+    (before ``mu_reg``); ``delta`` is the threshold on the group magnitude."""
+    return float(np.sum(phi(group_magnitude(x, coupling), delta, potential)))
+
+
+class installed_coupling:
+    """``with installed_coupling(model, coupling):`` -- the plan's prior coupling is ``coupling`` inside and what the plan held
+    before afterwards, as ``installed`` does for the kinds.  ``None`` leaves it alone.  The name is checked before any library
+    call."""
+
+    def __init__(self, model, coupling=None):
+        self.model = model
+        self.want = None if coupling is None else coupling_code(coupling)
+
+    def __enter__(self):
+        self.saved = None
+        if self.want is not None:
+            self.saved = get_coupling_code(self.model)
+            _lib.check(self.model._L.surfh_set_prior_coupling(self.model._plan, self.want))
+
+    def __exit__(self, *exc):
+        if self.saved is not None:
+            _lib.check(self.model._L.surfh_set_prior_coupling(self.model._plan, self.saved))
+        return False
+
+
+def get_coupling_code(model) -> int:
+    import ctypes as C
+    out = C.c_int32(-1)
+    _lib.check(model._L.surfh_get_prior_coupling(model._plan, C.byref(out)))
+    return int(out.value)
+
+
 class installed:
     """``with installed(model, spatial=..., spectral=..., data=...):`` -- the plan's potential slots hold the given kinds inside
     and what they held before afterwards.  ``None`` leaves a slot alone.  The names are checked before any library call."""
@@ -132,3 +215,13 @@ class Potentials:
         if slot not in SLOTS:
             raise ValueError(f"slot must be one of {', '.join(SLOTS)}, not {slot!r}")
         return NAMES[get_slot(self, slot)]
+
+    def set_prior_coupling(self, coupling="none"):
+        """The coupling of the maps' spatial prior from now on: "none" (one potential per difference, the default of a new
+        model), "isotropic" or "vector" (module docstring).  ``mmmg(delta=...)``, ``mmmg(data_delta=...)``, ``huber_prior_dev`` and
+        ``huber_curv_dev`` follow it, their ``delta`` then the threshold on the group magnitude; the plane-wise and voxel-wise
+        solvers refuse a plan whose coupling is not "none".  ``mmmg(coupling=...)`` sets it for one call only."""
+        _lib.check(self._L.surfh_set_prior_coupling(self._plan, coupling_code(coupling)))
+
+    def get_prior_coupling(self) -> str:
+        return COUPLING_NAMES[get_coupling_code(self)]
