@@ -435,6 +435,30 @@ int surfh_huber_planes_prior_dev(surfh_plan *plan, const float *x_dev, float *g_
                                  double *values_host);
 int surfh_huber_planes_curv_dev(surfh_plan *plan, const float *x_dev, const float *p0_dev, const float *p1_dev, double delta,
                                 double *sums_host);
+/* The same solver and passes with every plane's own weight and threshold, and a coupling of the row and the column difference of
+ * a pixel.  mu_reg [Lc] and delta [Lc] (host arrays): plane l minimises
+ *   J_l(x_l) = mu |y_l - A_l x_l|^2 / 2 + mu_reg[l] sum phi_delta[l](.)
+ * -- a cube's flux changes by orders of magnitude along the wavelength, and one threshold in absolute flux units leaves its faint
+ * planes fully quadratic.  Every delta[l] follows the rule of surfh_mmmg_huber (positive, at least FLT_MIN, +inf allowed), every
+ * mu_reg[l] must be >= 0.  coupling is a per-call argument, not plan state (the plan's slot, surfh_set_prior_coupling, is the maps'
+ * and is still refused here while it is not 0):
+ *   0  none       sum_ij phi(u_r) + phi(u_c): with Lc copies of one mu_reg and one delta, the arithmetic and the bits of the entry
+ *                 points above, which forward here
+ *   1  isotropic  sum_ij phi(sqrt(u_r^2 + u_c^2)): total variation for Huber's phi; an edge pays the same whatever its angle to the
+ *                 pixel grid.  delta[l] is then the threshold on the group magnitude (sqrt(2) times larger for comparable behaviour);
+ *                 the majorant weights every difference of a pixel by w(m) = phi'(m) / m, recomputed in place from a 7-point
+ *                 stencil (no weight field is stored); prior_values / values_host receive sum_ij phi(m)
+ *   2  vector     refused (the message names "vector"): it would tie the independent planes together under one trace and one
+ *                 stopping test, which is a different solver.
+ * The planes stay independent: plane l of a run on arrays equals, bit for bit, plane l of a run on the scalars mu_reg[l], delta[l]
+ * that takes as many iterations.  curv_dev takes no mu_reg. */
+int surfh_mmmg_huber_planes_ex(surfh_plan *plan, const float *y, double mu, const double *mu_reg, const double *delta, int32_t coupling,
+                               const float *x0, int32_t max_iter, double tol, int32_t refresh, float *x, double *grad_norm,
+                               int32_t *nit, double *prior_values, surfh_cg_callback callback, void *user);
+int surfh_huber_planes_prior_dev_ex(surfh_plan *plan, const float *x_dev, float *g_dev, const double *mu_reg, const double *delta,
+                                    int32_t coupling, double *sq_host, double *values_host);
+int surfh_huber_planes_curv_dev_ex(surfh_plan *plan, const float *x_dev, const float *p0_dev, const float *p1_dev, const double *delta,
+                                   int32_t coupling, double *sums_host);
 
 /* CG building blocks on device vectors, for the multi-GPU driver (one plan per rank,
  * RCCL all-reduce of `q` between surfh_normal_dev and surfh_cg_step_dev).            */
@@ -493,10 +517,12 @@ int surfh_get_potential(const surfh_plan *plan, int32_t slot);
  * sum_k D_k^T (w(m) D_k x), the curvature sums are sum_k sum w(m) (D_k p0)^2, (D_k p0)(D_k p1), (D_k p1)^2 and the prior value is
  * sum phi(m).  delta = +inf is the quadratic prior under every coupling; T = 1 makes vector the same as isotropic.
  * surfh_mmmg_huber, surfh_mmmg_robust, surfh_huber_prior_dev and surfh_huber_curv_dev honour the coupling (the imager term and the
- * data weights compose as before); they fail on a plan whose quadratic prior is the joint Laplacian (surfh_set_prior).  The
- * plane-wise and voxel-wise solvers and passes (surfh_mmmg_huber_planes, surfh_mmmg_huber_vox, surfh_mmmg_robust_vox, the
- * _planes_ and _vox_ *_dev passes) fail with a message naming the coupling while it is not 0; the quadratic surfh_mmmg and
- * the CG solvers ignore it.  set fails on an unknown code and on a NULL plan and leaves the plan as it was; get stores the code. */
+ * data weights compose as before); they fail on a plan whose quadratic prior is the joint Laplacian (surfh_set_prior).  This
+ * slot is the maps': the plane-wise and voxel-wise solvers and passes (surfh_mmmg_huber_planes(_ex), surfh_mmmg_huber_vox,
+ * surfh_mmmg_robust_vox, the _planes_ and _vox_ *_dev passes) fail with a message naming the coupling while it is not 0.  The
+ * plane-wise solver carries the isotropic coupling as a per-call argument instead (surfh_mmmg_huber_planes_ex and the _ex passes);
+ * the cube's solvers carry none.  The quadratic surfh_mmmg and the CG solvers ignore the slot.  set fails on an unknown code and on
+ * a NULL plan and leaves the plan as it was; get stores the code. */
 int surfh_set_prior_coupling(surfh_plan *plan, int32_t coupling);
 int surfh_get_prior_coupling(const surfh_plan *plan, int32_t *coupling);
 /* ---- data weights: plan state, like the prior ----
@@ -634,6 +660,15 @@ int surfh_launch_geometry(const char *which, int64_t a, int64_t b, int64_t c, in
  * curvature block of (p0, p1).  Synchronises. */
 int surfh_debug_prior_passes(surfh_plan *plan, int32_t T, int32_t na, int32_t nb, int32_t kind, int32_t coupling, const float *x_dev,
                              float *g_dev, const float *p0_dev, const float *p1_dev, double mu_reg, double delta, double *sums);
+/* diagnostic: the same for the PLANE passes (surfh_huber_planes_prior_dev_ex / _curv_dev_ex) on device arrays of any shape
+ * [L][na][nb] (every extent >= 1; no slit geometry gives a plan an axis of length 1 or 2), one workgroup per plane, under an
+ * explicit kind, a plane-wise coupling (0 or 1; 2 fails naming "vector") and per-plane mu_reg [L] and delta [L] (host arrays, the
+ * rules of the _ex entry points).  g += mu_reg[l] sum_k D_k^T (w D_k x) per plane; sums [5][L] on the host = g.g, the prior value
+ * and the curvature block of (p0, p1) of every plane.  The plan gives its stream only; the scratch is the call's own.
+ * Synchronises. */
+int surfh_debug_planes_passes(surfh_plan *plan, int32_t L, int32_t na, int32_t nb, int32_t kind, int32_t coupling, const float *x_dev,
+                              float *g_dev, const float *p0_dev, const float *p1_dev, const double *mu_reg, const double *delta,
+                              double *sums);
 /* host only (no GPU, no plan): the route plan creation would decide -- which transform kernels run and which fusions ride on
  * them -- from the function plan creation calls.  lp: the plan's plane pitch (owned planes rounded up to 128).  switches: bit i
  * set = switch i is on, in the order SURFH_DFT_H2, SURFH_DFT_CT, SURFH_DFT_DENSE, SURFH_NO_FUSED_MIX, SURFH_ADJ_FUSED,

@@ -24,7 +24,9 @@ exact transpose of that operator.  ``--data_to_img`` also writes the quick-look 
 ``--delta D`` (not in the reference, whose criterion_2D.py imports qmm's ``Huber`` without building it): edge-preserving Huber
 priors of threshold D on the row and column differences, minimised by 3MG (``-m`` anything but ``lcg``); the results then go to
 ``<--out>_huber_<D>``.  ``--potential`` (with ``--delta``) replaces Huber's potential by ``hyperbolic`` or ``hebert_leahy``
-(surfh_amd/potentials.py); the results then go to ``<--out>_<kind>_<D>``.
+(surfh_amd/potentials.py); the results then go to ``<--out>_<kind>_<D>``.  ``--coupling isotropic`` (with ``--delta``) gives a
+pixel's row and column difference one potential, on sqrt(u_r^2 + u_c^2) -- isotropic total variation under Huber's potential, D then
+the threshold on that magnitude; the directory gains ``_cpl_isotropic``.  ``none`` (the default) keeps today's prior and directory.
 
 ``--nonneg`` (with ``-m lcg``; not in the reference either): the same quadratic criterion under ``x >= 0``, every plane its own
 problem, by ``MRSBlurred.cg_nonneg`` (ADMM around the CG, surfh_amd/nonneg.py) from ``--value_init``: ``--outer`` outer iterations
@@ -83,9 +85,10 @@ def build_problem(npix: int, planes: int, seed: int, inp: str | None, angle: flo
                 pointings=instru.CoordList([instru.Coord(a, b) for a, b in pts]), truth=truth)
 
 
-def result_dir(out, delta, potential="huber"):
-    """<out>_huber_<delta> as before; another potential puts its name in Huber's place"""
-    return f"{out}_{potential}_{delta:g}"
+def result_dir(out, delta, potential="huber", coupling="none"):
+    """<out>_huber_<delta> as before; another potential puts its name in Huber's place, a coupling appends _cpl_<coupling>"""
+    name = f"{out}_{potential}_{delta:g}"
+    return name if coupling == "none" else f"{name}_cpl_{coupling}"
 
 
 @click.command()
@@ -107,13 +110,16 @@ def result_dir(out, delta, potential="huber"):
               help="Huber threshold of the priors (needs -m other than lcg); results go to <out>_huber_<delta>")
 @click.option("--potential", default="huber", type=click.Choice(["huber", "hyperbolic", "hebert_leahy"]),
               help="potential of the priors under --delta; other than huber: results go to <out>_<potential>_<delta>")
+@click.option("--coupling", default="none", type=click.Choice(["none", "isotropic"]),
+              help="coupling of a pixel's row and column difference under --delta (isotropic: total variation); "
+                   "other than none: results go to <out>_<potential>_<delta>_cpl_<coupling>")
 @click.option("--nonneg", is_flag=True, default=False,
               help="solve under x >= 0 (ADMM around the CG, -m lcg); results go to <out>_nn, with nn_trace.npy")
 @click.option("--rho", default=None, type=float, help="ADMM penalty of every plane (--nonneg); default: estimated per plane")
 @click.option("--outer", default=None, type=int, help="outer iterations (--nonneg); default: -ni")
 @click.option("--inner", default=None, type=int, help="CG iterations per outer iteration (--nonneg); default: 10")
 def main(npix, hyper_parameter, niter, method, value_init, planes, inp, out, quiet, seed, device, angle, data_to_img, delta,
-         potential="huber", nonneg=False, rho=None, outer=None, inner=None):
+         potential="huber", coupling="none", nonneg=False, rho=None, outer=None, inner=None):
     if nonneg:
         if method != "lcg":
             raise click.UsageError("--nonneg runs ADMM around the linear CG; use it with -m lcg")
@@ -130,10 +136,12 @@ def main(npix, hyper_parameter, niter, method, value_init, planes, inp, out, qui
         raise click.UsageError("--rho, --outer and --inner belong to --nonneg")
     if potential != "huber" and delta is None:
         raise click.UsageError("--potential needs --delta: a potential of the quadratic prior means nothing")
+    if coupling != "none" and delta is None:
+        raise click.UsageError("--coupling needs --delta: a coupling of the quadratic prior means nothing")
     if delta is not None:
         if method == "lcg":
             raise ValueError("lcg minimises quadratic criteria only: a Huber prior (delta) needs method='mmmg'")
-        out = result_dir(out, delta, potential)
+        out = result_dir(out, delta, potential, coupling)
     if angle:
         from surfh_amd.spectro_blind import MRSBlurred, QuadCriterion_MRS_2D
     else:
@@ -145,7 +153,7 @@ def main(npix, hyper_parameter, niter, method, value_init, planes, inp, out, qui
                        device=device)
     simulated_data = model.forward(prob["truth"])
     crit = QuadCriterion_MRS_2D(mu_spectro=1, y_spectro=np.copy(simulated_data), model_spectro=model, mu_reg=hyper_parameter,
-                                printing=True, gradient="separated", delta=delta, potential=potential)
+                                printing=True, gradient="separated", delta=delta, potential=potential, coupling=coupling)
     t0 = time.time()
     nn = None
     if nonneg:

@@ -63,6 +63,7 @@ EXPORTS = [
     "surfh_profile_enable", "surfh_profile_filter", "surfh_profile_count", "surfh_profile_get", "surfh_profile_reset", "surfh_debug_copy",
     "surfh_debug_dims", "surfh_gemm_selftest", "surfh_gemm_selftest_ksteps", "surfh_gemm_selftest_ms", "surfh_klist_classify", "surfh_launch_geometry", "surfh_route_decide", "surfh_mm_step2",
     "surfh_debug_alloc_count", "surfh_debug_alloc_fail", "surfh_debug_prior_passes",
+    "surfh_mmmg_huber_planes_ex", "surfh_huber_planes_prior_dev_ex", "surfh_huber_planes_curv_dev_ex", "surfh_debug_planes_passes",
     "surfh_shepard", "surfh_shepard_last_error", "surfh_spectral_median", "surfh_nmf_cd", "surfh_templates_last_error",
     "surfh_set_templates", "surfh_get_templates", "surfh_forward_templates", "surfh_adjoint_templates", "surfh_forward_templates_dev",
     "surfh_adjoint_templates_dev", "surfh_cg_templates", "surfh_cg_templates_cb", "surfh_joint_criterion",
@@ -132,6 +133,11 @@ def load():
     L.surfh_mmmg_huber_planes.argtypes = L.surfh_mmmg_huber.argtypes
     L.surfh_huber_planes_prior_dev.argtypes = [vp, vp, vp, C.c_double, C.c_double, c_double_p, c_double_p]
     L.surfh_huber_planes_curv_dev.argtypes = [vp, vp, vp, vp, C.c_double, c_double_p]
+    L.surfh_mmmg_huber_planes_ex.argtypes = [vp, c_float_p, C.c_double, c_double_p, c_double_p, C.c_int32, c_float_p, C.c_int32,
+                                             C.c_double, C.c_int32, c_float_p, c_double_p, c_int32_p, c_double_p, CG_CALLBACK, vp]
+    L.surfh_huber_planes_prior_dev_ex.argtypes = [vp, vp, vp, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p]
+    L.surfh_huber_planes_curv_dev_ex.argtypes = [vp, vp, vp, vp, c_double_p, C.c_int32, c_double_p]
+    L.surfh_debug_planes_passes.argtypes = [vp] + [C.c_int32] * 5 + [vp] * 4 + [c_double_p, c_double_p, c_double_p]
     L.surfh_mmmg_planes.argtypes = L.surfh_cg_planes.argtypes
     L.surfh_cg_planes_begin_dev.argtypes = [vp, vp, C.c_double, C.c_double, vp]
     L.surfh_cg_planes_step_dev.argtypes = [vp, C.c_int32, C.c_int32]
@@ -258,7 +264,8 @@ def _solve(model, fn, data, lead, x0, max_iter, tol, refresh, outs, callback, pl
             return 1
 
     cb = CG_CALLBACK(tramp) if callback is not None else CG_CALLBACK()
-    check(fn(model._plan, fptr(y), *map(float, lead), fptr(x0a) if x0a is not None else None, int(max_iter), float(tol),
+    lead = [v if isinstance(v, (C._Pointer, C._SimpleCData)) else float(v) for v in lead]       # ctypes arguments pass as they are
+    check(fn(model._plan, fptr(y), *lead, fptr(x0a) if x0a is not None else None, int(max_iter), float(tol),
              int(refresh), fptr(x), dptr(gn), C.byref(nit), *outs, cb, None))
     if err:
         raise err[0]
@@ -284,6 +291,14 @@ def solve_huber_planes(model, data, mu, mu_reg, delta, x0, max_iter, tol, refres
     pv = np.zeros(planes, dtype=np.float64)
     return _solve(model, load().surfh_mmmg_huber_planes, data, (mu, mu_reg, delta), x0, max_iter, tol, refresh, (dptr(pv),), callback,
                   planes, squeeze) + (pv,)
+
+
+def solve_huber_planes_ex(model, data, mu, mu_reg, delta, coupling, x0, max_iter, tol, refresh, callback, planes, squeeze):
+    """``surfh_mmmg_huber_planes_ex``: ``mu_reg`` and ``delta`` float64 arrays ``[planes]``, ``coupling`` the code (0 or 1).  Returns as
+    ``solve_huber_planes``; prior_values[l] = sum phi over the groups of the coupling."""
+    pv = np.zeros(planes, dtype=np.float64)
+    return _solve(model, load().surfh_mmmg_huber_planes_ex, data, (mu, dptr(mu_reg), dptr(delta), C.c_int32(int(coupling))), x0, max_iter,
+                  tol, refresh, (dptr(pv),), callback, planes, squeeze) + (pv,)
 
 
 def solve_huber_vox(model, data, mu, spat_reg, spat_delta, spec_reg, spec_delta, x0, max_iter, tol, refresh, callback):

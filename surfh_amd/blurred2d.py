@@ -26,6 +26,49 @@ from .nonneg import NonnegResult, check_nonneg_args, result_from_planes_trace
 from .weights import DataWeights, check_data_weights
 
 
+PLANE_COUPLINGS = ("none", "isotropic")
+
+
+def plane_coupling_code(coupling) -> int:
+    """The code of a plane-wise prior coupling, "none" or "isotropic".  ``ValueError`` for "vector" -- it would tie the independent
+    planes together (one trace, one stopping test: a different solver) -- and for anything that is no coupling at all."""
+    code = _pot.coupling_code(coupling)
+    if _pot.COUPLING_NAMES[code] not in PLANE_COUPLINGS:
+        raise ValueError(f"coupling {_pot.COUPLING_NAMES[code]!r} would tie the independent planes together; the plane-wise solver "
+                         f"takes one of {', '.join(PLANE_COUPLINGS)}")
+    return code
+
+
+def per_plane(value, n_planes: int, what: str) -> np.ndarray:
+    """``value`` (a number, or an array ``[n_planes]``) as a contiguous float64 array ``[n_planes]``; ``ValueError`` on another
+    shape."""
+    a = np.asarray(value, dtype=np.float64)
+    if a.ndim > 1 or (a.ndim == 1 and a.size != n_planes):
+        raise ValueError(f"{what} has shape {a.shape}, expected a number or [{n_planes}]")
+    return np.ascontiguousarray(np.broadcast_to(a, (n_planes,)))
+
+
+def plane_prior_args(n_planes: int, mu_reg, delta, coupling="none"):
+    """The argument rules of the plane-wise priors, checked before any library call.  Returns ``(mu_reg, delta, code, extended)``:
+    ``extended`` False -- numbers and no coupling, the arguments of the scalar entry points, returned as they came (the library
+    checks them) -- or True: ``mu_reg`` and ``delta`` float64 arrays ``[n_planes]`` for the ``_ex`` entry points, every delta positive
+    and every mu_reg >= 0."""
+    code = plane_coupling_code(coupling)
+    _pot.need_delta_coupling(code, delta)
+    if delta is None:
+        if np.ndim(mu_reg) > 0:
+            raise ValueError("a per-plane mu_reg needs delta: the quadratic solvers take one mu_reg for all planes")
+        return mu_reg, None, code, False
+    if code == 0 and np.ndim(mu_reg) == 0 and np.ndim(delta) == 0:
+        return mu_reg, delta, code, False
+    r, d = per_plane(mu_reg, n_planes, "mu_reg"), per_plane(delta, n_planes, "delta")
+    if not np.all(d > 0.0):
+        raise ValueError(f"delta must be positive, not {delta!r}")
+    if not np.all(r >= 0.0):
+        raise ValueError(f"mu_reg must be >= 0, not {mu_reg!r}")
+    return r, d, code, True
+
+
 class Blurred2D(DataWeights, _pot.Potentials, LinOp):
     def __init__(self, sotf, alpha_axis, beta_axis, instr: instru.IFU, step_degree: float, pointings: instru.CoordList):
         self.sotf = sotf
@@ -317,7 +360,7 @@ class Blurred2D(DataWeights, _pot.Potentials, LinOp):
     last_prior_values = None            # per-plane prior values of the last mmmg(delta=...) result (None after a quadratic run)
 
     def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, delta=None, weights=None,
-             potential="huber"):
+             potential="huber", coupling="none"):
         """Device-resident 3MG on the same criterion (`qmm.mmmg` restated for quadratic objectives) -- what the 2-D
         deconvolution driver's ``method = "qmm"`` runs (scripts/deconvolution_mrs_noRotation.py:199-212).  Same returns as
         ``cg`` except that ``grad_norm`` holds |grad| (not squared).  ``weights`` as in ``cg``.
@@ -326,28 +369,70 @@ class Blurred2D(DataWeights, _pot.Potentials, LinOp):
         mu |y - A x|^2 / 2 + mu_reg sum_k sum phi(D_k x)  (include/surfh_amd.h: surfh_mmmg_huber_planes); same returns, and the
         prior values sum_k sum phi(D_k x_l) of the returned iterate are left in ``self.last_prior_values`` ([n_planes]).
         ``potential``: the potential under ``delta`` for this call, "huber" (the default), "hyperbolic" or "hebert_leahy"
-        (``surfh_amd.potentials``); ``ValueError`` for another one than Huber without ``delta``."""
+        (``surfh_amd.potentials``); ``ValueError`` for another one than Huber without ``delta``.
+        With ``delta``, ``mu_reg`` and ``delta`` may each be an array ``[n_planes]``, every plane its own weight and threshold (a
+        cube's flux changes by orders of magnitude along the wavelength); the planes stay independent, plane l of such a run is
+        bit for bit plane l of the run on the numbers ``mu_reg[l]``, ``delta[l]`` that takes as many iterations.
+        ``coupling`` (with ``delta``): "none" (the default: one potential per difference) or "isotropic" -- one potential per
+        pixel on sqrt(u_r^2 + u_c^2), total variation under Huber's phi: an edge pays the same at every angle to the pixel grid.
+        ``delta`` is then the threshold on that magnitude (sqrt(2) times larger for comparable behaviour) and
+        ``last_prior_values`` holds sum phi(m), ``potentials.prior_value(x_l[None], delta, potential, "isotropic")``.  It is an
+        argument of this call, not the plan's slot (``set_prior_coupling`` is the maps' and is refused here while it is set).
+        ``ValueError``: a coupling without ``delta``, "vector" (it would tie the planes together), an array of another length, and
+        on arrays or under a coupling a ``delta`` that is not positive or a negative ``mu_reg`` (numbers without a coupling are
+        checked by the library, as before).  (include/surfh_amd.h: surfh_mmmg_huber_planes_ex)"""
         self.last_prior_values = None
         _pot.need_delta(potential, delta, "delta")
+        mu_reg, delta, code, extended = plane_prior_args(self.n_planes, mu_reg, delta, coupling)
         with _pot.installed(self, spatial=potential), self.installed_weights(weights):
             if delta is None:
                 return _lib.solve(self, self._L.surfh_mmmg_planes_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback,
                                   planes=self.n_planes, squeeze=not self.batched)
-            x, gn, nit, self.last_prior_values = _lib.solve_huber_planes(self, data, mu, mu_reg, delta, x0, max_iter, tol, refresh,
-                                                                         callback, self.n_planes, not self.batched)
+            if extended:
+                x, gn, nit, self.last_prior_values = _lib.solve_huber_planes_ex(self, data, mu, mu_reg, delta, code, x0, max_iter, tol,
+                                                                                refresh, callback, self.n_planes, not self.batched)
+            else:
+                x, gn, nit, self.last_prior_values = _lib.solve_huber_planes(self, data, mu, mu_reg, delta, x0, max_iter, tol, refresh,
+                                                                             callback, self.n_planes, not self.batched)
             return x, gn, nit
 
-    def huber_planes_prior_dev(self, x_t, g_t, mu_reg: float, delta: float):
+    def huber_planes_prior_dev(self, x_t, g_t, mu_reg, delta, coupling="none"):
         """g_t += mu_reg sum_k D_k^T phi'(D_k x_t) on device tensors [n_planes, Na, Nb] (float32, contiguous); returns
-        (|g_l|^2 of the result, sum_k sum phi(D_k x_l)), each [n_planes]: the gradient pass of ``mmmg(delta=...)`` alone."""
+        (|g_l|^2 of the result, sum_k sum phi(D_k x_l)), each [n_planes]: the gradient pass of ``mmmg(delta=...)`` alone.
+        ``mu_reg``, ``delta`` (numbers or ``[n_planes]``) and ``coupling`` as in ``mmmg``; under "isotropic"
+        g_t += mu_reg sum_k D_k^T (w(m) D_k x_t) and the values are sum phi(m)."""
+        mu_reg, delta, code, extended = plane_prior_args(self.n_planes, mu_reg, delta, coupling)
         sq, val = np.zeros(self.n_planes), np.zeros(self.n_planes)
-        _lib.check(self._L.surfh_huber_planes_prior_dev(self._plan, C.c_void_p(x_t.data_ptr()), C.c_void_p(g_t.data_ptr()),
-                                                        float(mu_reg), float(delta), _lib.dptr(sq), _lib.dptr(val)))
+        x_p, g_p = C.c_void_p(x_t.data_ptr()), C.c_void_p(g_t.data_ptr())
+        if extended:
+            _lib.check(self._L.surfh_huber_planes_prior_dev_ex(self._plan, x_p, g_p, _lib.dptr(mu_reg), _lib.dptr(delta), code,
+                                                               _lib.dptr(sq), _lib.dptr(val)))
+        else:
+            _lib.check(self._L.surfh_huber_planes_prior_dev(self._plan, x_p, g_p, float(mu_reg), float(delta), _lib.dptr(sq), _lib.dptr(val)))
         return sq, val
 
-    def huber_planes_curv_dev(self, x_t, p0_t, p1_t, delta: float) -> np.ndarray:
-        """[n_planes, 3]: sum_k sum w(D_k x_l) (D_k p0_l)^2, (D_k p0_l)(D_k p1_l), (D_k p1_l)^2, the prior block of the majorant."""
+    def huber_planes_curv_dev(self, x_t, p0_t, p1_t, delta, coupling="none") -> np.ndarray:
+        """[n_planes, 3]: sum_k sum w(D_k x_l) (D_k p0_l)^2, (D_k p0_l)(D_k p1_l), (D_k p1_l)^2, the prior block of the majorant;
+        ``delta`` (a number or ``[n_planes]``) and ``coupling`` as in ``mmmg`` (under "isotropic" w = w(m) for both differences)."""
+        _, delta, code, extended = plane_prior_args(self.n_planes, 0.0, delta, coupling)
         out = np.zeros((3, self.n_planes))
-        _lib.check(self._L.surfh_huber_planes_curv_dev(self._plan, C.c_void_p(x_t.data_ptr()), C.c_void_p(p0_t.data_ptr()),
-                                                       C.c_void_p(p1_t.data_ptr()), float(delta), _lib.dptr(out)))
+        ptrs = [C.c_void_p(t.data_ptr()) for t in (x_t, p0_t, p1_t)]
+        if extended:
+            _lib.check(self._L.surfh_huber_planes_curv_dev_ex(self._plan, *ptrs, _lib.dptr(delta), code, _lib.dptr(out)))
+        else:
+            _lib.check(self._L.surfh_huber_planes_curv_dev(self._plan, *ptrs, float(delta), _lib.dptr(out)))
         return np.ascontiguousarray(out.T)
+
+    def planes_passes_dev(self, x_t, g_t, p0_t, p1_t, mu_reg, delta, potential="huber", coupling="none"):
+        """Diagnostic: the two passes in one call on device arrays of any shape ``[L, Na, Nb]`` (every extent >= 1, whatever the
+        model's own shape), under an explicit potential and coupling, ``mu_reg`` and ``delta`` numbers or ``[L]``; the plan's
+        state is not consulted.  g_t += mu_reg_l sum_k D_k^T (w D_k x_t).  Returns (g.g, prior values, curvature blocks), shapes
+        ``[L]``, ``[L]``, ``[L, 3]`` (synchronises).  (include/surfh_amd.h: surfh_debug_planes_passes)"""
+        L, na, nb = (int(v) for v in x_t.shape)
+        code = plane_coupling_code(coupling)
+        r, d = per_plane(mu_reg, L, "mu_reg"), per_plane(delta, L, "delta")
+        out = np.zeros((5, L), dtype=np.float64)
+        _lib.check(self._L.surfh_debug_planes_passes(self._plan, L, na, nb, _pot.kind_code(potential), code, C.c_void_p(x_t.data_ptr()),
+                                                     C.c_void_p(g_t.data_ptr()), C.c_void_p(p0_t.data_ptr()), C.c_void_p(p1_t.data_ptr()),
+                                                     _lib.dptr(r), _lib.dptr(d), _lib.dptr(out)))
+        return out[0].copy(), out[1].copy(), np.ascontiguousarray(out[2:].T)

@@ -258,17 +258,21 @@ int launch_mmmg_step_planes(hipStream_t s, float *x, float *r, const float *d, f
 // nplanes doubles: |g|^2, sum_k sum phi(D_k x), beta, m.Bm, and the prior block c00, c01, c11 of (g, m) under w(D x).
 // dir: g = r - mu_reg sum_k D_k^T phi'(D_k x), those scalars (B = Q_D + mu_reg W, Q_D m carried in qm), d = g + beta m
 // step: the 2x2 majorant step in [d, m] with qd = Q_D d; a plane without positive curvature keeps still
+// `par` holds HUBER_PLANES_PARAMS arrays of nplanes doubles, every plane's own: the coefficient of the prior gradient (dir: -mu_reg
+// as fp32) and delta, both fp32 values widened, and reg = mu_reg in float64.  `coupling`: 0 the separated prior, 1 isotropic
+// (one potential per pixel on sqrt(u_r^2 + u_c^2), the weights recomputed from a 7-point stencil); chosen on the host.
 constexpr int HUBER_PLANES_SCALARS = 7;
+constexpr int HUBER_PLANES_PARAMS = 3;
 int launch_huber_dir_planes(hipStream_t s, const float *x, const float *r, float *g, const float *m, const float *qm, float *d,
-                            int nplanes, int na, int nb, double mu_reg, float delta, int kind, double *sc);
+                            int nplanes, int na, int nb, const double *par, int kind, int coupling, double *sc);
 int launch_huber_step_planes(hipStream_t s, float *x, float *r, const float *d, float *m, float *qm, const float *qd, const float *g,
-                             int nplanes, long npix, double mu_reg, const double *sc, int update_r);
+                             int nplanes, long npix, const double *par, const double *sc, int update_r);
 // the two passes of the dir kernel alone: out = src + coef sum_k D_k^T phi'(D_k x) (out may alias src) with sc[0], sc[1] = |out|^2 and
 // sum phi per plane; sc[4..6] = the prior block of (p0, p1) per plane
-int launch_huber_planes_grad(hipStream_t s, const float *x, const float *src, float *out, int nplanes, int na, int nb, float coef,
-                             float delta, int kind, double *sc);
-int launch_huber_planes_curv(hipStream_t s, const float *x, const float *p0, const float *p1, int nplanes, int na, int nb, float delta,
-                             int kind, double *sc);
+int launch_huber_planes_grad(hipStream_t s, const float *x, const float *src, float *out, int nplanes, int na, int nb, const double *par,
+                             int kind, int coupling, double *sc);
+int launch_huber_planes_curv(hipStream_t s, const float *x, const float *p0, const float *p1, int nplanes, int na, int nb,
+                             const double *par, int kind, int coupling, double *sc);
 // (hth + diag(mu reg)) z = in per frequency bin (reg < 0 marks padding bins); *flag |= 1 on a non-positive pivot
 int launch_wct_solve(hipStream_t s, const float *hth, const float *reg, const double *mu, const float *in, float *out, int T,
                      long PL, int *flag);

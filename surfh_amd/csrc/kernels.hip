@@ -1346,14 +1346,29 @@ struct PlaneWalk {   // element e = i * nb + j of a [na][nb] plane, e = threadId
 //   (huber_curv_kernel's arithmetic, weights recomputed).
 // PHASES == 3, the solver's launch (src = r, coef = -mu_reg, g = -gradient): also g.Q_D m and m.Q_D m from the carried image
 //   qm, beta = -(g.Bm) / (m.Bm) with B = Q_D + reg W, d = g + beta m; sc[HP_BETA] = the fp32 beta that formed d, sc[HP_MBM] = m.Bm.
-template <int PHASES, int KIND>
+// coef, delta and reg are the plane's own: par[k * L + l], k = HPP_* (coef and delta hold fp32 values).
+// COUPLING 1, the isotropic prior sum phi(m), m^2 = u_r^2 + u_c^2 per pixel (coupled_prior.hip's conventions: m^2 in float64, m
+//   rounded to fp32 once, w = pot_w(m) in fp32, phi in float64, phi' formed as u w): the gradient of pixel (i, j) takes the weights
+//   of the groups (i, j), (i+1, j) and (i, j+1), recomputed here from a 7-point stencil (a stored field would be one more array of
+//   the planes' size through HBM in every pass: 2 GB on 2048 x 512 x 512); both differences of a pixel take w(m) in the curvature
+//   pass.  COUPLING 0 is the separated prior, as it always was.
+enum { HPP_COEF = 0, HPP_DELTA, HPP_REG };
+static_assert(HPP_REG + 1 == HUBER_PLANES_PARAMS, "kernels.h sizes the callers' parameter arrays");
+
+__device__ __forceinline__ float group_magnitude(float ur, float uc) {
+    return (float)sqrt((double)ur * (double)ur + (double)uc * (double)uc);
+}
+
+template <int PHASES, int KIND, int COUPLING>
 __global__ __launch_bounds__(TPB) void huber_dir_planes_kernel(const float *__restrict__ x, const float *src, float *g,
                                                                const float *__restrict__ m, const float *__restrict__ qm,
-                                                               float *__restrict__ d, int na, int nb, float coef, float delta,
-                                                               double reg, double *__restrict__ sc) {
+                                                               float *__restrict__ d, int na, int nb, const double *__restrict__ par,
+                                                               double *__restrict__ sc) {
     const int l = blockIdx.x, L = gridDim.x, npix = na * nb;
     const long off = (long)l * npix;
     const float *px = x + off;
+    const float coef = (float)par[HPP_COEF * L + l], delta = (float)par[HPP_DELTA * L + l];
+    const double reg = par[HPP_REG * L + l];
     if constexpr ((PHASES & 1) != 0) {
         double v[2] = {0.0, 0.0};
         for (PlaneWalk q(nb); q.e < npix; q.next(nb)) {
@@ -1362,11 +1377,23 @@ __global__ __launch_bounds__(TPB) void huber_dir_planes_kernel(const float *__re
             const float c = px[q.e];
             const float ur = px[im] - c, uc = px[jm] - c;              // (Dr x)[i][j], (Dc x)[i][j]
             const float urn = c - px[ip], ucn = c - px[jp];            // (Dr x)[i+1][j], (Dc x)[i][j+1]
-            const float pg = (pot_dphi<KIND>(urn, delta) - pot_dphi<KIND>(ur, delta)) + (pot_dphi<KIND>(ucn, delta) - pot_dphi<KIND>(uc, delta));
+            float pg, m0 = 0.f;
+            if constexpr (COUPLING == 0) {
+                pg = (pot_dphi<KIND>(urn, delta) - pot_dphi<KIND>(ur, delta)) + (pot_dphi<KIND>(ucn, delta) - pot_dphi<KIND>(uc, delta));
+            } else {
+                // the groups of (i, j), (i+1, j) and (i, j+1): the column difference of the row below, the row difference of the
+                // column to the right (jm - e and jp - e are the same offsets in every row)
+                m0 = group_magnitude(ur, uc);
+                const float m1 = group_magnitude(urn, px[ip + (jm - q.e)] - px[ip]);
+                const float m2 = group_magnitude(px[im + (jp - q.e)] - px[jp], ucn);
+                const float w0 = pot_w<KIND>(m0, delta);
+                pg = (pot_w<KIND>(m1, delta) * urn - w0 * ur) + (pot_w<KIND>(m2, delta) * ucn - w0 * uc);
+            }
             const float gv = src[off + q.e] + coef * pg;
             g[off + q.e] = gv;
             v[0] += (double)gv * (double)gv;
-            v[1] += pot_phi<KIND>(ur, delta) + pot_phi<KIND>(uc, delta);
+            if constexpr (COUPLING == 0) v[1] += pot_phi<KIND>(ur, delta) + pot_phi<KIND>(uc, delta);
+            else v[1] += pot_phi<KIND>(m0, delta);
         }
         block_sum_bcast<2>(v);
         if (threadIdx.x == 0) {
@@ -1387,7 +1414,9 @@ __global__ __launch_bounds__(TPB) void huber_dir_planes_kernel(const float *__re
         for (PlaneWalk q(nb); q.e < npix; q.next(nb)) {
             const int im = q.e - nb + (q.i == 0 ? npix : 0), jm = q.e - 1 + (q.j == 0 ? nb : 0);
             const float c = px[q.e], ac = a[q.e], bc = b[q.e];
-            const double wr = pot_w<KIND>(px[im] - c, delta), wc = pot_w<KIND>(px[jm] - c, delta);
+            double wr, wc;                                             // COUPLING 1: both differences take the group's weight
+            if constexpr (COUPLING == 0) wr = pot_w<KIND>(px[im] - c, delta), wc = pot_w<KIND>(px[jm] - c, delta);
+            else wr = wc = pot_w<KIND>(group_magnitude(px[im] - c, px[jm] - c), delta);
             const double ar = a[im] - ac, acl = a[jm] - ac, br = b[im] - bc, bcl = b[jm] - bc;
             v[0] += wr * ar * ar + wc * acl * acl;
             v[1] += wr * ar * br + wc * acl * bcl;
@@ -1422,9 +1451,11 @@ __global__ __launch_bounds__(TPB) void huber_dir_planes_kernel(const float *__re
 __global__ __launch_bounds__(TPB) void huber_step_planes_kernel(float *__restrict__ x, float *__restrict__ r, const float *__restrict__ d,
                                                                 float *__restrict__ m, float *__restrict__ qm,
                                                                 const float *__restrict__ qd, const float *__restrict__ g, long npix,
-                                                                double reg, const double *__restrict__ sc, int update_r) {
+                                                                const double *__restrict__ par, const double *__restrict__ sc,
+                                                                int update_r) {
     const int l = blockIdx.x, L = gridDim.x;
     const long off = (long)l * npix;
+    const double reg = par[HPP_REG * L + l];
     double v[4] = {0.0, 0.0, 0.0, 0.0};                    // d.Q_D d, d.Q_D m, d.g, m.g
     for (long i = threadIdx.x; i < npix; i += TPB) {
         const double di = d[off + i], gi = g[off + i];
@@ -1846,44 +1877,52 @@ size_t pn_part_doubles(long LP) { return (size_t)PN_SPLIT * (size_t)LP; }
 
 namespace {
 inline bool plane_fits(int nplanes, int na, int nb) { return nplanes > 0 && na > 0 && nb > 0 && (long)na * nb <= 0x7fffffffL - TPB; }
+// calls f(std::integral_constant<int, kind>(), std::integral_constant<int, coupling>()) for a potential and a plane-wise coupling
+// (0 separated, 1 isotropic); false on anything else
+template <class F>
+inline bool planes_dispatch(int kind, int coupling, F &&f) {
+    if (coupling == 0) return pot_dispatch(kind, [&](auto K) { f(K, std::integral_constant<int, 0>()); });
+    if (coupling == 1) return pot_dispatch(kind, [&](auto K) { f(K, std::integral_constant<int, 1>()); });
+    return false;
+}
 }  // namespace
 
 int launch_huber_dir_planes(hipStream_t s, const float *x, const float *r, float *g, const float *m, const float *qm, float *d,
-                            int nplanes, int na, int nb, double mu_reg, float delta, int kind, double *sc) {
+                            int nplanes, int na, int nb, const double *par, int kind, int coupling, double *sc) {
     if (!plane_fits(nplanes, na, nb)) return (int)hipErrorInvalidValue;
-    const auto go = [&](auto K) {
-        hipLaunchKernelGGL((huber_dir_planes_kernel<3, decltype(K)::value>), dim3(nplanes), dim3(TPB), 0, s, x, r, g, m, qm, d, na, nb,
-                           -(float)mu_reg, delta, mu_reg, sc);
+    const auto go = [&](auto K, auto C) {
+        hipLaunchKernelGGL((huber_dir_planes_kernel<3, decltype(K)::value, decltype(C)::value>), dim3(nplanes), dim3(TPB), 0, s, x, r, g,
+                           m, qm, d, na, nb, par, sc);
     };
-    if (!pot_dispatch(kind, go)) return (int)hipErrorInvalidValue;
+    if (!planes_dispatch(kind, coupling, go)) return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
 }
 
-int launch_huber_planes_grad(hipStream_t s, const float *x, const float *src, float *out, int nplanes, int na, int nb, float coef,
-                             float delta, int kind, double *sc) {
+int launch_huber_planes_grad(hipStream_t s, const float *x, const float *src, float *out, int nplanes, int na, int nb, const double *par,
+                             int kind, int coupling, double *sc) {
     if (!plane_fits(nplanes, na, nb)) return (int)hipErrorInvalidValue;
-    const auto go = [&](auto K) {
-        hipLaunchKernelGGL((huber_dir_planes_kernel<1, decltype(K)::value>), dim3(nplanes), dim3(TPB), 0, s, x, src, out,
-                           (const float *)nullptr, (const float *)nullptr, (float *)nullptr, na, nb, coef, delta, 0.0, sc);
+    const auto go = [&](auto K, auto C) {
+        hipLaunchKernelGGL((huber_dir_planes_kernel<1, decltype(K)::value, decltype(C)::value>), dim3(nplanes), dim3(TPB), 0, s, x, src,
+                           out, (const float *)nullptr, (const float *)nullptr, (float *)nullptr, na, nb, par, sc);
     };
-    if (!pot_dispatch(kind, go)) return (int)hipErrorInvalidValue;
+    if (!planes_dispatch(kind, coupling, go)) return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
 }
 
-int launch_huber_planes_curv(hipStream_t s, const float *x, const float *p0, const float *p1, int nplanes, int na, int nb, float delta,
-                             int kind, double *sc) {
+int launch_huber_planes_curv(hipStream_t s, const float *x, const float *p0, const float *p1, int nplanes, int na, int nb,
+                             const double *par, int kind, int coupling, double *sc) {
     if (!plane_fits(nplanes, na, nb)) return (int)hipErrorInvalidValue;
-    const auto go = [&](auto K) {
-        hipLaunchKernelGGL((huber_dir_planes_kernel<2, decltype(K)::value>), dim3(nplanes), dim3(TPB), 0, s, x, (const float *)nullptr,
-                           const_cast<float *>(p0), p1, (const float *)nullptr, (float *)nullptr, na, nb, 0.f, delta, 0.0, sc);
+    const auto go = [&](auto K, auto C) {
+        hipLaunchKernelGGL((huber_dir_planes_kernel<2, decltype(K)::value, decltype(C)::value>), dim3(nplanes), dim3(TPB), 0, s, x,
+                           (const float *)nullptr, const_cast<float *>(p0), p1, (const float *)nullptr, (float *)nullptr, na, nb, par, sc);
     };
-    if (!pot_dispatch(kind, go)) return (int)hipErrorInvalidValue;
+    if (!planes_dispatch(kind, coupling, go)) return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
 }
 
 int launch_huber_step_planes(hipStream_t s, float *x, float *r, const float *d, float *m, float *qm, const float *qd, const float *g,
-                             int nplanes, long npix, double mu_reg, const double *sc, int update_r) {
-    hipLaunchKernelGGL(huber_step_planes_kernel, dim3(nplanes), dim3(TPB), 0, s, x, r, d, m, qm, qd, g, npix, mu_reg, sc, update_r);
+                             int nplanes, long npix, const double *par, const double *sc, int update_r) {
+    hipLaunchKernelGGL(huber_step_planes_kernel, dim3(nplanes), dim3(TPB), 0, s, x, r, d, m, qm, qd, g, npix, par, sc, update_r);
     return (int)hipGetLastError();
 }
 

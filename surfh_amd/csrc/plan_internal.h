@@ -309,6 +309,7 @@ struct surfh_plan : PlanHandles {
     // plane-wise solvers use them too), the caller's iterate
     DevBuf<double> pl_sc;
     DevBuf<double> pl_hsc;                         // surfh_mmmg_huber_planes: [HUBER_PLANES_SCALARS][Lc] per-plane scalars
+    DevBuf<double> pl_hpar;                        // ... and [HUBER_PLANES_PARAMS][Lc] per-plane coefficient, delta, mu_reg of a call
     float *pl_x = nullptr;                         // view: the caller's device vector, never freed here
     double pl_mu = 1.0, pl_mu_reg = 0.0;
     int pl_it = 0;

@@ -1596,59 +1596,93 @@ int surfh_mmmg_planes(surfh_plan *p, const float *y, double mu, double mu_reg, c
 //   J_l(x_l) = mu |y_l - A_l x_l|^2 / 2 + mu_reg sum_k sum phi(D_k x_l),
 // minimised by mmmg_planes_loop: huber_dir_planes gives -g_l, |g_l|^2, the prior value, the prior block of (-g_l, m_l), beta_l
 // and d_l = -g_l + beta_l m_l; the operator is the data part Q_D = mu A^T A alone; huber_step_planes forms the block of
-// (d_l, m_l) by linearity in float64, solves and moves.
+// (d_l, m_l) by linearity in float64, solves and moves.  The _ex entry points give every plane its own mu_reg_l and delta_l and
+// take a coupling of a pixel's two differences (0 none, 1 isotropic) as an argument of the call; the scalar entry points forward
+// to the same code with Lc copies of their value and coupling 0.
 namespace {
 int huber_planes_ready(surfh_plan *p, const char *who) {
     if (imager_refuse(p, who) || coupling_refuse(p, who)) return 1;
     if (p->T != 0) return fail("%s works on the plane-wise (no template) model; the maps of a template model take surfh_mmmg_huber", who);
     if (p->ch.empty()) return fail("plan has no channel");
     HIP_OK(hipSetDevice(p->dev));
-    if (ensure_set(member(p->pl_hsc, (size_t)HUBER_PLANES_SCALARS * p->Lc))) return 1;
+    if (ensure_set(member(p->pl_hsc, (size_t)HUBER_PLANES_SCALARS * p->Lc), member(p->pl_hpar, (size_t)HUBER_PLANES_PARAMS * p->Lc))) return 1;
     return 0;
 }
-}  // namespace
 
-int surfh_huber_planes_prior_dev(surfh_plan *p, const float *x_dev, float *g_dev, double mu_reg, double delta, double *sq_host,
-                                 double *values_host) {
-    if (!p || !x_dev || !g_dev) return fail("null argument");
-    if (huber_args(mu_reg, delta) || huber_planes_ready(p, "surfh_huber_planes_prior_dev")) return 1;
+// The per-call coupling of the plane-wise passes: 0 (none) or 1 (isotropic: one potential per pixel on sqrt(u_r^2 + u_c^2)).  It
+// is an argument, not plan state -- the plan's slot (surfh_set_prior_coupling) stays the maps' and is refused by coupling_refuse.
+int planes_coupling_arg(const char *who, int32_t coupling) {
+    if (coupling == 2)
+        return fail("%s: the vector coupling (2) would tie the independent planes together -- one trace, one stopping test, a different "
+                    "solver; the planes take coupling 0 (none) or 1 (isotropic)", who);
+    if (coupling != 0 && coupling != 1) return fail("%s: coupling %d; the planes take 0 (none) or 1 (isotropic)", who, (int)coupling);
+    return 0;
+}
+// The rules of the per-plane arrays of the *_ex entry points: every delta[l] as huber_args asks, every mu_reg[l] >= 0.
+int planes_array_args(const char *who, int L, const double *mu_reg, const double *delta) {
+    if (!delta) return fail("null argument");
+    for (int l = 0; l < L; ++l) {
+        if (huber_args(mu_reg ? mu_reg[l] : 0.0, delta[l])) return 1;
+        if (mu_reg && !(mu_reg[l] >= 0.0)) return fail("%s: mu_reg[%d] = %g must be >= 0", who, l, mu_reg[l]);
+    }
+    return 0;
+}
+// The parameter table of the plane kernels (kernels.h: HUBER_PLANES_PARAMS) for L planes, on the host: the coefficient of the prior
+// gradient sign * (float)mu_reg[l], (float)delta[l], and mu_reg[l] in float64 -- the values the scalar kernels took as arguments.
+void planes_param_table(int L, const double *mu_reg, const double *delta, float sign, std::vector<double> &par) {
+    par.assign((size_t)HUBER_PLANES_PARAMS * L, 0.0);
+    for (int l = 0; l < L; ++l) {
+        par[l] = mu_reg ? (double)(sign * (float)mu_reg[l]) : 0.0;
+        par[(size_t)L + l] = (double)(float)delta[l];
+        par[(size_t)2 * L + l] = mu_reg ? mu_reg[l] : 0.0;
+    }
+}
+// ... in the plan's table.  Every entry point synchronises the plan's stream before it returns: no kernel reads the table now.
+int planes_params(surfh_plan *p, const double *mu_reg, const double *delta, float sign) {
+    std::vector<double> par;
+    planes_param_table(p->Lc, mu_reg, delta, sign, par);
+    return dev_raw_upload(p->pl_hpar, par.data(), par.size() * sizeof(double));
+}
+
+// the three entry points on per-plane arrays (already checked) under a coupling; the scalar ones hand in Lc copies of their value
+int planes_prior_dev(surfh_plan *p, const float *x_dev, float *g_dev, const double *mu_reg, const double *delta, int coupling,
+                     double *sq_host, double *values_host) {
     const int L = p->Lc;
+    if (planes_params(p, mu_reg, delta, 1.f)) return 1;
     {
         Prof pr(p, "huber_planes_grad");
-        LAUNCH_OK(launch_huber_planes_grad(p->stream, x_dev, g_dev, g_dev, L, p->Na, p->Nb, (float)mu_reg, (float)delta, p->pot[0], p->pl_hsc));
+        LAUNCH_OK(launch_huber_planes_grad(p->stream, x_dev, g_dev, g_dev, L, p->Na, p->Nb, p->pl_hpar, p->pot[0], coupling, p->pl_hsc));
     }
     if (sq_host) HIP_OK(hipMemcpyAsync(sq_host, p->pl_hsc, L * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     if (values_host) HIP_OK(hipMemcpyAsync(values_host, p->pl_hsc + L, L * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     HIP_OK(hipStreamSynchronize(p->stream));
     return 0;
 }
-
-int surfh_huber_planes_curv_dev(surfh_plan *p, const float *x_dev, const float *p0_dev, const float *p1_dev, double delta,
-                                double *sums_host) {
-    if (!p || !x_dev || !p0_dev || !p1_dev || !sums_host) return fail("null argument");
-    if (huber_args(0.0, delta) || huber_planes_ready(p, "surfh_huber_planes_curv_dev")) return 1;
+int planes_curv_dev(surfh_plan *p, const float *x_dev, const float *p0_dev, const float *p1_dev, const double *delta, int coupling,
+                    double *sums_host) {
     const int L = p->Lc;
-    const auto pass = [&] { return launch_huber_planes_curv(p->stream, x_dev, p0_dev, p1_dev, L, p->Na, p->Nb, (float)delta, p->pot[0], p->pl_hsc); };
+    if (planes_params(p, nullptr, delta, 0.f)) return 1;
+    const auto pass = [&] {
+        return launch_huber_planes_curv(p->stream, x_dev, p0_dev, p1_dev, L, p->Na, p->Nb, p->pl_hpar, p->pot[0], coupling, p->pl_hsc);
+    };
     return diag_pass(p, "huber_planes_curv", pass, p->pl_hsc + (size_t)(HUBER_PLANES_SCALARS - 3) * L, sums_host, (size_t)3 * L);
 }
-
-int surfh_mmmg_huber_planes(surfh_plan *p, const float *y, double mu, double mu_reg, double delta, const float *x0, int32_t max_iter,
-                            double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit, double *prior_values,
-                            surfh_cg_callback callback, void *user) {
-    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
-    if (huber_args(mu_reg, delta) || huber_planes_ready(p, "surfh_mmmg_huber_planes")) return 1;
+int planes_mmmg_huber(surfh_plan *p, const float *y, double mu, const double *mu_reg, const double *delta, int coupling, const float *x0,
+                      int32_t max_iter, double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit, double *prior_values,
+                      surfh_cg_callback callback, void *user) {
     const int L = p->Lc;
     const long npix = (long)p->Na * p->Nb;
     double *sc = p->pl_hsc;
+    if (planes_params(p, mu_reg, delta, -1.f)) return 1;
     const auto dir = [&] {
         Prof pr(p, "huber_dir_planes");
-        LAUNCH_OK(launch_huber_dir_planes(p->stream, p->cg_x, p->cg_r, p->cg_hg, p->cg_d, p->cg_qm, p->cg_dd, L, p->Na, p->Nb, mu_reg,
-                                          (float)delta, p->pot[0], sc));
+        LAUNCH_OK(launch_huber_dir_planes(p->stream, p->cg_x, p->cg_r, p->cg_hg, p->cg_d, p->cg_qm, p->cg_dd, L, p->Na, p->Nb, p->pl_hpar,
+                                          p->pot[0], coupling, sc));
         return 0;
     };
     const auto step = [&](int update_r) {
         Prof pr(p, "huber_step_planes");
-        LAUNCH_OK(launch_huber_step_planes(p->stream, p->cg_x, p->cg_r, p->cg_dd, p->cg_d, p->cg_qm, p->cg_q, p->cg_hg, L, npix, mu_reg,
+        LAUNCH_OK(launch_huber_step_planes(p->stream, p->cg_x, p->cg_r, p->cg_dd, p->cg_d, p->cg_qm, p->cg_q, p->cg_hg, L, npix, p->pl_hpar,
                                            sc, update_r));
         return 0;
     };
@@ -1656,6 +1690,85 @@ int surfh_mmmg_huber_planes(surfh_plan *p, const float *y, double mu, double mu_
     // the last launch of the dir kernel ran on the returned iterate: its prior values are the result's
     if (prior_values) HIP_OK(hipMemcpyAsync(prior_values, sc + L, L * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     return mmmg_finish(p, x);
+}
+}  // namespace
+
+int surfh_huber_planes_prior_dev(surfh_plan *p, const float *x_dev, float *g_dev, double mu_reg, double delta, double *sq_host,
+                                 double *values_host) {
+    if (!p || !x_dev || !g_dev) return fail("null argument");
+    if (huber_args(mu_reg, delta) || huber_planes_ready(p, "surfh_huber_planes_prior_dev")) return 1;
+    const std::vector<double> r((size_t)p->Lc, mu_reg), d((size_t)p->Lc, delta);
+    return planes_prior_dev(p, x_dev, g_dev, r.data(), d.data(), 0, sq_host, values_host);
+}
+int surfh_huber_planes_prior_dev_ex(surfh_plan *p, const float *x_dev, float *g_dev, const double *mu_reg, const double *delta,
+                                    int32_t coupling, double *sq_host, double *values_host) {
+    const char *who = "surfh_huber_planes_prior_dev_ex";
+    if (!p || !x_dev || !g_dev || !mu_reg || !delta) return fail("null argument");
+    if (planes_coupling_arg(who, coupling) || planes_array_args(who, p->Lc, mu_reg, delta) || huber_planes_ready(p, who)) return 1;
+    return planes_prior_dev(p, x_dev, g_dev, mu_reg, delta, coupling, sq_host, values_host);
+}
+
+int surfh_huber_planes_curv_dev(surfh_plan *p, const float *x_dev, const float *p0_dev, const float *p1_dev, double delta,
+                                double *sums_host) {
+    if (!p || !x_dev || !p0_dev || !p1_dev || !sums_host) return fail("null argument");
+    if (huber_args(0.0, delta) || huber_planes_ready(p, "surfh_huber_planes_curv_dev")) return 1;
+    const std::vector<double> d((size_t)p->Lc, delta);
+    return planes_curv_dev(p, x_dev, p0_dev, p1_dev, d.data(), 0, sums_host);
+}
+int surfh_huber_planes_curv_dev_ex(surfh_plan *p, const float *x_dev, const float *p0_dev, const float *p1_dev, const double *delta,
+                                   int32_t coupling, double *sums_host) {
+    const char *who = "surfh_huber_planes_curv_dev_ex";
+    if (!p || !x_dev || !p0_dev || !p1_dev || !delta || !sums_host) return fail("null argument");
+    if (planes_coupling_arg(who, coupling) || planes_array_args(who, p->Lc, nullptr, delta) || huber_planes_ready(p, who)) return 1;
+    return planes_curv_dev(p, x_dev, p0_dev, p1_dev, delta, coupling, sums_host);
+}
+
+int surfh_mmmg_huber_planes(surfh_plan *p, const float *y, double mu, double mu_reg, double delta, const float *x0, int32_t max_iter,
+                            double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit, double *prior_values,
+                            surfh_cg_callback callback, void *user) {
+    if (!p || !y || !x || !grad_norm || !nit) return fail("null argument");
+    if (huber_args(mu_reg, delta) || huber_planes_ready(p, "surfh_mmmg_huber_planes")) return 1;
+    const std::vector<double> r((size_t)p->Lc, mu_reg), d((size_t)p->Lc, delta);
+    return planes_mmmg_huber(p, y, mu, r.data(), d.data(), 0, x0, max_iter, tol, refresh, x, grad_norm, nit, prior_values, callback, user);
+}
+int surfh_mmmg_huber_planes_ex(surfh_plan *p, const float *y, double mu, const double *mu_reg, const double *delta, int32_t coupling,
+                               const float *x0, int32_t max_iter, double tol, int32_t refresh, float *x, double *grad_norm, int32_t *nit,
+                               double *prior_values, surfh_cg_callback callback, void *user) {
+    const char *who = "surfh_mmmg_huber_planes_ex";
+    if (!p || !y || !mu_reg || !delta || !x || !grad_norm || !nit) return fail("null argument");
+    if (planes_coupling_arg(who, coupling) || planes_array_args(who, p->Lc, mu_reg, delta) || huber_planes_ready(p, who)) return 1;
+    return planes_mmmg_huber(p, y, mu, mu_reg, delta, coupling, x0, max_iter, tol, refresh, x, grad_norm, nit, prior_values, callback, user);
+}
+
+// The plane passes on arrays of any shape [L][na][nb] (every extent >= 1; a slit geometry cannot give a plan an axis of length 1 or
+// 2): the launchers of the entry points above under an explicit kind and coupling and per-plane mu_reg / delta, on the plan's
+// stream, with scratch of the call's own.  g += mu_reg_l sum_k D_k^T (w D_k x); sums [5][L] (host) = g.g, the prior value, the
+// curvature block of (p0, p1), per plane.
+int surfh_debug_planes_passes(surfh_plan *p, int32_t L, int32_t na, int32_t nb, int32_t kind, int32_t coupling, const float *x_dev,
+                              float *g_dev, const float *p0_dev, const float *p1_dev, const double *mu_reg, const double *delta,
+                              double *sums) {
+    const char *who = "surfh_debug_planes_passes";
+    if (!p || !x_dev || !g_dev || !p0_dev || !p1_dev || !mu_reg || !delta || !sums) return fail("null argument");
+    if (L < 1 || na < 1 || nb < 1 || (double)L * na * nb > 2147483647.0) return fail("%s: shape %d x %d x %d", who, (int)L, (int)na, (int)nb);
+    if (kind < 0 || kind > 2) return fail("%s: kind %d", who, (int)kind);
+    if (planes_coupling_arg(who, coupling) || planes_array_args(who, L, mu_reg, delta)) return 1;
+    HIP_OK(hipSetDevice(p->dev));
+    hipStream_t s = p->stream;
+    std::vector<double> table;
+    planes_param_table(L, mu_reg, delta, 1.f, table);
+    DevBuf<double> par, sc;
+    if (par.upload(table) || sc.alloc((size_t)HUBER_PLANES_SCALARS * L)) return 1;
+    LAUNCH_OK(launch_huber_planes_grad(s, x_dev, g_dev, g_dev, L, na, nb, par, kind, coupling, sc));
+    LAUNCH_OK(launch_huber_planes_curv(s, x_dev, p0_dev, p1_dev, L, na, nb, par, kind, coupling, sc));
+    // rows 0, 1 (g.g, the value) and the last three (the block); the buffers go away after the synchronisation
+    const hipError_t e0 = hipMemcpyAsync(sums, sc, (size_t)2 * L * sizeof(double), hipMemcpyDeviceToHost, s);
+    const hipError_t e1 = hipMemcpyAsync(sums + (size_t)2 * L, sc + (size_t)(HUBER_PLANES_SCALARS - 3) * L, (size_t)3 * L * sizeof(double),
+                                         hipMemcpyDeviceToHost, s);
+    const hipError_t e2 = hipStreamSynchronize(s);
+    HIP_OK(e0);
+    HIP_OK(e1);
+    HIP_OK(e2);
+    return 0;
 }
 
 }  // extern "C"

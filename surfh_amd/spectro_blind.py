@@ -108,11 +108,12 @@ class MRSBlurred(Blurred2D):
         return super().cg(data, mu, mu_reg, x0, max_iter, tol, refresh, callback)
 
     def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, delta=None, weights=None,
-             potential="huber"):
+             potential="huber", coupling="none"):
         """Device-resident 3MG on the criterion of ``cg``, with the exact transpose likewise; ``delta``: Huber priors (or those of
-        ``potential``), and
+        ``potential``), per-plane ``mu_reg`` / ``delta`` arrays, ``coupling`` ("none" or "isotropic") and
         ``weights``, as ``Blurred2D.mmmg``."""
-        return super().mmmg(data, mu, mu_reg, x0, max_iter, tol, refresh, callback, delta=delta, weights=weights, potential=potential)
+        return super().mmmg(data, mu, mu_reg, x0, max_iter, tol, refresh, callback, delta=delta, weights=weights, potential=potential,
+                            coupling=coupling)
 
     # ---- reference helpers on the host ------------------------------------------------------------------
     def data_to_img(self, data):

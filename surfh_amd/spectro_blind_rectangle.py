@@ -20,8 +20,8 @@ from __future__ import annotations
 import numpy as np
 
 from . import instru
-from .blurred2d import Blurred2D
-from .potentials import kind_name, need_delta, phi as potential_phi
+from .blurred2d import Blurred2D, plane_coupling_code
+from .potentials import COUPLING_NAMES, kind_name, need_delta, need_delta_coupling, phi as potential_phi, prior_value
 from .weights import check_data_weights, weighted_sq_residual
 
 
@@ -77,7 +77,7 @@ class QuadCriterion_MRS_2D:
     and ``get_crit_val``, on ``MRSBlurred`` (one image, or a stack of independent images solved together)."""
 
     def __init__(self, mu_spectro, y_spectro, model_spectro, mu_reg, printing=False, gradient="separated", weights=None, delta=None,
-                 potential="huber"):
+                 potential="huber", coupling="none"):
         """``weights`` (not in criterion_2D.py): per-sample data weights in the layout of ``y_spectro``, data term
         mu (y - A x)^T diag(w) (y - A x) / 2 (``MRSBlurred.set_data_weights``); data of weight 0 are ignored whatever they hold.
         ``None``: the weights the model holds, if any.
@@ -86,10 +86,14 @@ class QuadCriterion_MRS_2D:
         (include/surfh_amd.h: surfh_mmmg_huber_planes), as ``fusion.QuadCriterion_MRS``; only a method other than ``"lcg"``
         minimises it.  ``None``: the quadratic criterion.
         ``potential``: the potential under ``delta``, "huber" (the default), "hyperbolic" or "hebert_leahy"
-        (``surfh_amd.potentials``); another one than Huber needs ``delta``."""
+        (``surfh_amd.potentials``); another one than Huber needs ``delta``.
+        ``coupling``: "none" (the default) or "isotropic", one potential per pixel on sqrt((Dr x)^2 + (Dc x)^2) with ``delta`` the
+        threshold on that magnitude (``MRSBlurred.mmmg``); it needs ``delta``, and "vector" is refused."""
         assert isinstance(mu_reg, (float, int, list, np.ndarray))
         self.potential = kind_name(potential)
         need_delta(potential, delta, "delta")
+        self.coupling = COUPLING_NAMES[plane_coupling_code(coupling)]
+        need_delta_coupling(self.coupling, delta)
         if delta is not None:
             if gradient != "separated":
                 raise ValueError("the Huber prior (delta) acts on the separated differences: gradient must be 'separated'")
@@ -147,6 +151,8 @@ class QuadCriterion_MRS_2D:
         kw = {} if self.delta is None else {"delta": self.delta}
         if self.potential != "huber":
             kw["potential"] = self.potential
+        if self.coupling != "none":
+            kw["coupling"] = self.coupling
         if self.weights is not None:
             kw["weights"] = self.weights
         x, gn, nit = solver(self.y_spectro, mu=self.mu_spectro, mu_reg=self.mu_reg, x0=init,
@@ -161,13 +167,17 @@ class QuadCriterion_MRS_2D:
 
     def get_crit_val(self, x_hat):
         """(mu |y - A x|^2 + mu_reg (|Dr x|^2 + |Dc x|^2)) / 2   (criterion_2D.py:252-275), summed over the planes; with ``delta``
-        mu |y - A x|^2 / 2 + mu_reg sum phi(Dr x) + phi(Dc x), phi the criterion's potential (Huber by default).  Under data weights (this criterion's,
+        mu |y - A x|^2 / 2 + mu_reg sum phi(Dr x) + phi(Dc x), phi the criterion's potential (Huber by default); under a coupling
+        mu_reg ``potentials.prior_value`` of the planes, sum phi(sqrt((Dr x)^2 + (Dc x)^2)).  Under data weights (this criterion's,
         else the model's) |y - A x|^2 is sum w (y - A x)^2 over the samples with w > 0."""
         x_hat = np.asarray(x_hat).reshape(self.shape_of_output)
         w = self.weights if self.weights is not None else getattr(self.model_spectro, "data_weights", None)
         data = self.mu_spectro * weighted_sq_residual(self.y_spectro, self.model_spectro.forward(x_hat), w)
         dr = np.roll(x_hat, 1, axis=-2) - x_hat
         dc = np.roll(x_hat, 1, axis=-1) - x_hat
+        if self.delta is not None and self.coupling != "none":
+            planes = x_hat.reshape((-1,) + x_hat.shape[-2:])
+            return data / 2 + self.mu_reg * prior_value(planes, self.delta, self.potential, self.coupling)
         if self.delta is not None:
             return data / 2 + self.mu_reg * (potential_phi(dr, self.delta, self.potential).sum() +
                                              potential_phi(dc, self.delta, self.potential).sum())
