@@ -669,6 +669,27 @@ int surfh_debug_prior_passes(surfh_plan *plan, int32_t T, int32_t na, int32_t nb
 int surfh_debug_planes_passes(surfh_plan *plan, int32_t L, int32_t na, int32_t nb, int32_t kind, int32_t coupling, const float *x_dev,
                               float *g_dev, const float *p0_dev, const float *p1_dev, const double *mu_reg, const double *delta,
                               double *sums);
+/* diagnostic: ONE vector kernel of the plane-wise CG / 3MG loops (surfh_cg_planes, surfh_mmmg_planes, surfh_cg_planes_begin_dev /
+ * _step_dev) on device arrays of explicit extents, through the launcher the solvers call.  The plan gives its stream only; the
+ * scalars and the partial sums live in buffers of the call's own.  Synchronises.  which, its vectors v0.. and its scalar rows:
+ *   plane-major, arrays [L][npix], ext = { L, npix }, one scalar per plane (rows of L doubles):
+ *     "dot"        a, b                      out: a.b
+ *     "cg_step"    x, r, d, q                in: rr, d.q   out: r'.r' (update_r; left as it came otherwise)   x += s d, r -= s q
+ *     "cg_dir"     d, r                      in: rr', rr   out: rr <- rr'                                    d = r + (rr' / rr) d
+ *     "mmmg_dir"   d, r, m, qm               out: r.r, m.Qm                                                  d = r + beta m
+ *     "mmmg_step"  x, r, d, m, qm, qd        in: m.Qm                                                        the 2x2 step (surfh_mm_step2)
+ *   wavelength-innermost, arrays [Nb][NAP][LP], ext = { Na, Nb, NAP, LP, L, l0 } (L <= LP owned wavelengths, l0 = 0), one scalar
+ *   per wavelength (rows of LP doubles):
+ *     "pn_prior_dot"  d, q                   out: d.q      q += mu_reg (Dr^T Dr + Dc^T Dc) d (circular)
+ *     "pn_dot"        x, y                   out: x.y
+ *     "pn_step"       x, r, d, q             in: rr, d.q   out: r'.r' (update_r)
+ *     "pn_dir"        d, r                   in: rr', rr
+ *   transposes, same ext: "to_lam_inner" src [l0 + L][Na][Nb] -> dst [Nb][NAP][LP] (planes 0 .. L-1), "from_lam_inner" the way back.
+ * Vectors a kernel does not take are NULL.  sc_in / sc_out: host arrays of the rows listed, in that order; sc_out is uploaded
+ * before the launch, so an entry the kernel does not write comes back unchanged.  Extents below 1, NAP < Na, L > LP, arrays of
+ * 2^31 floats or more, LP % 64 != 0, an unknown name and a missing pointer fail with a message and launch nothing. */
+int surfh_debug_planes_cg(surfh_plan *plan, const char *which, const int64_t *ext, float *v0, float *v1, float *v2, float *v3,
+                          float *v4, float *v5, double mu_reg, int32_t update_r, const double *sc_in, double *sc_out);
 /* host only (no GPU, no plan): the route plan creation would decide -- which transform kernels run and which fusions ride on
  * them -- from the function plan creation calls.  lp: the plan's plane pitch (owned planes rounded up to 128).  switches: bit i
  * set = switch i is on, in the order SURFH_DFT_H2, SURFH_DFT_CT, SURFH_DFT_DENSE, SURFH_NO_FUSED_MIX, SURFH_ADJ_FUSED,

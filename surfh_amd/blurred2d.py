@@ -436,3 +436,20 @@ class Blurred2D(DataWeights, _pot.Potentials, LinOp):
                                                      C.c_void_p(g_t.data_ptr()), C.c_void_p(p0_t.data_ptr()), C.c_void_p(p1_t.data_ptr()),
                                                      _lib.dptr(r), _lib.dptr(d), _lib.dptr(out)))
         return out[0].copy(), out[1].copy(), np.ascontiguousarray(out[2:].T)
+
+    def planes_cg_dev(self, which, ext, vectors, sc_in=None, sc_out=None, mu_reg=0.0, update_r=1):
+        """Diagnostic: one vector kernel of the plane-wise CG / 3MG loops on device tensors of explicit extents ``ext`` (``(L, npix)``
+        or ``(Na, Nb, NAP, LP, L, l0)``), through the solvers' launcher; the plan's state is not consulted.  ``vectors``: the
+        kernel's device tensors in its order, ``sc_in`` the rows of float64 scalars it reads, ``sc_out`` the rows it writes
+        (filled in place, entries it leaves alone unchanged; returned).  Synchronises.
+        (include/surfh_amd.h: surfh_debug_planes_cg)"""
+        e = np.zeros(6, dtype=np.int64)
+        e[:len(ext)] = ext
+        ptrs = [C.c_void_p(t.data_ptr()) for t in vectors] + [None] * (6 - len(vectors))
+        sc_in = None if sc_in is None else np.ascontiguousarray(sc_in, dtype=np.float64)
+        if sc_out is not None and not (isinstance(sc_out, np.ndarray) and sc_out.dtype == np.float64 and sc_out.flags.c_contiguous):
+            raise ValueError("sc_out must be a contiguous float64 array (it is filled in place)")
+        _lib.check(self._L.surfh_debug_planes_cg(self._plan, which.encode(), e.ctypes.data_as(C.POINTER(C.c_int64)), *ptrs, float(mu_reg),
+                                                 int(update_r), None if sc_in is None else _lib.dptr(sc_in),
+                                                 None if sc_out is None else _lib.dptr(sc_out)))
+        return sc_out

@@ -1771,4 +1771,77 @@ int surfh_debug_planes_passes(surfh_plan *p, int32_t L, int32_t na, int32_t nb, 
     return 0;
 }
 
+// One vector kernel of the plane-wise CG / 3MG loops on arrays of explicit extents: the launchers the solvers call, on the plan's
+// stream, with scalars and the pn_part_doubles(LP) partial sums in buffers of the call's own.  ext = { L, npix } for the plane-major
+// kernels (one scalar per plane), { Na, Nb, NAP, LP, L, l0 } for the wavelength-innermost ones (one scalar per wavelength of LP) and
+// the two transposes.  sc_in: the rows of scalars the kernel reads, sc_out: the rows it writes (uploaded first, so that an entry the
+// kernel leaves alone comes back as it went in).
+int surfh_debug_planes_cg(surfh_plan *p, const char *which, const int64_t *ext, float *v0, float *v1, float *v2, float *v3, float *v4,
+                          float *v5, double mu_reg, int32_t update_r, const double *sc_in, double *sc_out) {
+    const char *who = "surfh_debug_planes_cg";
+    enum { PLANES, PN, TRANSPOSE };
+    struct Kind { const char *name; int family, nvec, nin, nout; };
+    static const Kind kinds[] = {{"dot", PLANES, 2, 0, 1},      {"cg_step", PLANES, 4, 2, 1},      {"cg_dir", PLANES, 2, 2, 1},
+                                 {"mmmg_dir", PLANES, 4, 0, 2}, {"mmmg_step", PLANES, 6, 1, 0},    {"pn_prior_dot", PN, 2, 0, 1},
+                                 {"pn_dot", PN, 2, 0, 1},       {"pn_step", PN, 4, 2, 1},          {"pn_dir", PN, 2, 2, 0},
+                                 {"to_lam_inner", TRANSPOSE, 2, 0, 0}, {"from_lam_inner", TRANSPOSE, 2, 0, 0}};
+    if (!p || !which || !ext) return fail("null argument");
+    const Kind *k = nullptr;
+    for (const Kind &c : kinds)
+        if (!std::strcmp(which, c.name)) k = &c;
+    if (!k) return fail("%s: unknown kernel '%s'", who, which);
+    float *const v[6] = {v0, v1, v2, v3, v4, v5};
+    for (int i = 0; i < k->nvec; ++i)
+        if (!v[i]) return fail("%s: %s takes %d vectors, vector %d is null", who, which, k->nvec, i);
+    if ((k->nin && !sc_in) || (k->nout && !sc_out)) return fail("%s: %s needs its scalar arrays (null argument)", who, which);
+    if (!std::isfinite(mu_reg) || std::fabs(mu_reg) > 3e38) return fail("%s: mu_reg %g", who, mu_reg);
+    if (update_r != 0 && update_r != 1) return fail("%s: update_r %d", who, (int)update_r);
+    const double lim = 2147483647.0;
+    long n = 0;                                   // scalars of one row
+    if (k->family == PLANES) {
+        if (ext[0] < 1 || ext[1] < 1 || (double)ext[0] * (double)ext[1] > lim)
+            return fail("%s: %s on %lld planes of %lld pixels", who, which, (long long)ext[0], (long long)ext[1]);
+        n = (long)ext[0];
+    } else {
+        const int64_t Na = ext[0], Nb = ext[1], NAP = ext[2], LP = ext[3], L = ext[4], l0 = ext[5];
+        if (Na < 1 || Nb < 1 || NAP < Na || LP < 64 || L < 1 || L > LP || l0 < 0 || Na > 65535 || (double)Nb * (double)NAP * (double)LP > lim ||
+            (double)(l0 + L) * (double)Na * (double)Nb > lim || (k->family == PN && l0 != 0))
+            return fail("%s: %s on Na %lld, Nb %lld, NAP %lld, LP %lld, L %lld, l0 %lld", who, which, (long long)Na, (long long)Nb,
+                        (long long)NAP, (long long)LP, (long long)L, (long long)l0);
+        if (LP % 64) return fail("%s: LP %lld is no multiple of 64", who, (long long)LP);
+        n = (long)LP;
+    }
+    HIP_OK(hipSetDevice(p->dev));
+    hipStream_t s = p->stream;
+    DevBuf<double> in, out, part;
+    if (k->nin && in.upload(std::vector<double>(sc_in, sc_in + (size_t)k->nin * n))) return 1;
+    if (k->nout && out.upload(std::vector<double>(sc_out, sc_out + (size_t)k->nout * n))) return 1;
+    if (k->family == PN && part.alloc(pn_part_doubles(n))) return 1;
+    const double *result = out;                   // the rows that go back
+    const int L = (int)ext[0];
+    const long npix = (long)ext[1];
+    const int Na = (int)ext[0], Nb = (int)ext[1], NAP = k->family == PLANES ? 0 : (int)ext[2], Lc = k->family == PLANES ? 0 : (int)ext[4];
+    const int l0 = k->family == PLANES ? 0 : (int)ext[5];
+    const std::string w(which);
+    if (w == "dot") LAUNCH_OK(launch_dot_planes(s, v0, v1, L, npix, out));
+    else if (w == "cg_step") LAUNCH_OK(launch_cg_step_planes(s, v0, v1, v2, v3, L, npix, in, in + n, out, update_r));
+    else if (w == "cg_dir") {                     // rr is read and written: the second row of the scalars that came in
+        LAUNCH_OK(launch_cg_dir_planes(s, v0, v1, L, npix, in, in + n));
+        result = in + n;
+    } else if (w == "mmmg_dir") LAUNCH_OK(launch_mmmg_dir_planes(s, v0, v1, v2, v3, L, npix, out, out + n));
+    else if (w == "mmmg_step") LAUNCH_OK(launch_mmmg_step_planes(s, v0, v1, v2, v3, v4, v5, L, npix, in, update_r));
+    else if (w == "pn_prior_dot") LAUNCH_OK(launch_pn_prior_dot(s, v0, v1, Na, Nb, NAP, n, (float)mu_reg, part, out));
+    else if (w == "pn_dot") LAUNCH_OK(launch_pn_dot(s, v0, v1, Na, Nb, NAP, n, part, out));
+    else if (w == "pn_step") LAUNCH_OK(launch_pn_step(s, v0, v1, v2, v3, Na, Nb, NAP, n, in, in + n, part, out, update_r));
+    else if (w == "pn_dir") LAUNCH_OK(launch_pn_dir(s, v0, v1, Na, Nb, NAP, n, in, in + n));
+    else if (w == "to_lam_inner") LAUNCH_OK(launch_cube_to_lam_inner(s, v0, v1, l0, Lc, Na, Nb, NAP, (int)n));
+    else LAUNCH_OK(launch_cube_from_lam_inner(s, v0, v1, l0, Lc, Na, Nb, NAP, (int)n));
+    // the buffers go away after the synchronisation
+    const hipError_t e0 = k->nout ? hipMemcpyAsync(sc_out, result, (size_t)k->nout * n * sizeof(double), hipMemcpyDeviceToHost, s) : hipSuccess;
+    const hipError_t e1 = hipStreamSynchronize(s);
+    HIP_OK(e0);
+    HIP_OK(e1);
+    return 0;
+}
+
 }  // extern "C"
