@@ -1,5 +1,5 @@
 // Coupled priors of the maps (surfh_set_prior_coupling): one potential per GROUP of circular first differences instead of one
-// per difference.  With u_r = x[i-1][j] - x[i][j] and u_c = x[i][j-1] - x[i][j] (kernels.hip: huber_grad_kernel's differences):
+// per difference.  With u_r = x[i-1][j] - x[i][j] and u_c = x[i][j-1] - x[i][j] (huber_kernels.hip: huber_grad_kernel's differences):
 //   COUPLING 1, isotropic   group = (t, i, j):  m^2 = u_r^2 + u_c^2               prior sum_t sum_ij phi(m)
 //   COUPLING 2, vector      group = (i, j):     m^2 = sum_t u_r^2 + u_c^2         prior sum_ij phi(m)
 // phi(sqrt(.)) is concave for every kind of huber_dev.h, so the Geman-Reynolds majorant of the separated prior holds with the
@@ -13,11 +13,12 @@
 // host synchronisation.  Only the weight pass depends on the potential: it is instantiated per <KIND, COUPLING>, the two
 // readers per <COUPLING>; there is no per-element branch on a runtime value.
 // Conventions of the separated pair: TPB = RED_TPB threads, at most HUBER_BLOCKS blocks and a grid-stride loop, float64 block
-// sums in a fixed order (block_sums_to, parts_reduce_kernel: the same inputs give the same bits), differences and w in fp32,
+// sums in a fixed order (block_sums_to, parts_reduce_kernel of reduce_dev.h: the same inputs give the same bits), differences and w in fp32,
 // phi in float64, phi' formed as u w so that the gradient and the curvature see the same weight; src and out may alias.
 // m^2 is accumulated in float64 (no overflow for any fp32 differences, any T) and m rounded to fp32 once.
 #include "huber_dev.h"
 #include "kernels.h"
+#include "reduce_dev.h"
 
 namespace {
 

@@ -1,16 +1,12 @@
 // DFT pass of length N = R * M: R sub-transforms of length M on the matrix cores (the k loop of dft_h2.hip, one wave per
 // residue class), combined through LDS by twiddles and an R-point butterfly (see dft_ct.h).
 #include "dft_ct.h"
+#include "dft_split.h"
 #include "lds_attr.h"
 #include "prior_eig.h"
 #include <cmath>
 #include <cstring>
 #include <vector>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 #ifndef CT_EXP
 #define CT_EXP 0        // tools/exp: 2 no stores (and no combine: dead code), 4 no MFMAs, 16 no group synchronisation (wrong results), 32 no loads,
@@ -22,7 +18,7 @@ namespace {
 
 constexpr int BK = 16;
 constexpr int MAXMT = 3;                               // row tiles of 32 of the folded sub-transform (M / 2 + 1 <= 96)
-constexpr int E_TARGET = 10, E_LIMIT = 15;             // per-column block exponent of the fp16 pieces (dft_h2.hip)
+// E_TARGET, E_LIMIT (per-column block exponent of the fp16 pieces), MFMA3, split8h, pair_swap: dft_split.h
 constexpr int XFLOATS = 1024;                          // one wave's exchange slot: 32 rows x 32 lanes
 constexpr size_t LDS_LIMIT = 160 * 1024;
 
@@ -40,30 +36,6 @@ template <int R> __device__ __forceinline__ constexpr float wr_cos(int q) {
 }
 template <int R> __device__ __forceinline__ constexpr float wr_sin(int q) {
     return R == 2 ? 0.f : R == 3 ? (q == 0 ? 0.f : q == 1 ? 0.86602540378443865f : -0.86602540378443865f) : (q == 1 ? 1.f : q == 3 ? -1.f : 0.f);
-}
-
-#define MFMA3(acc_, ah_, al_, bh_, bl_)                                             \
-    {                                                                               \
-        f32x16 c_ = acc_;                                                           \
-        c_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(al_, bh_, c_, 0, 0, 0);         \
-        c_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah_, bl_, c_, 0, 0, 0);         \
-        c_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah_, bh_, c_, 0, 0, 0);         \
-        acc_ = c_;                                                                  \
-    }
-
-__device__ __forceinline__ void split8h(const float (&x)[8], int e, f16x8 &fh, f16x8 &fl) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float xs = __builtin_amdgcn_ldexpf(x[j], e);
-        const _Float16 hh = (_Float16)xs;
-        fh[j] = hh;
-        fl[j] = (_Float16)(xs - (float)hh);
-    }
-}
-
-// the value held by the neighbouring lane (lane ^ 1): the other component of the same complex column
-__device__ __forceinline__ float pair_swap(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, false));
 }
 
 // workgroup barrier that waits for LDS traffic only: global loads of the next tile and stores of the previous phase stay in flight

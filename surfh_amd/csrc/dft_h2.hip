@@ -6,15 +6,11 @@
 // steps ahead, fold / scale / split one step ahead, MFMAs on the current step; a tile's stores are issued after its
 // last MFMA group, behind loads that are already in flight.
 #include "dft_h2.h"
+#include "dft_split.h"
 #include "lds_attr.h"
 #include "prior_eig.h"
 #include <cmath>
 #include <cstring>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 #ifndef H2_EXP
 #define H2_EXP 0        // tools/exp: 2 no stores, 4 no MFMAs, 8 no loads
@@ -33,32 +29,7 @@ constexpr size_t LDS_MIX = (size_t)2 * MIX_ROWS * 2 * sizeof(float4);
 #define H2_WAVES 8
 #endif
 constexpr int NWAVES = H2_WAVES, NTHREADS = 64 * NWAVES;
-constexpr int E_TARGET = 10, E_LIMIT = 15;            // a column's largest scaled magnitude: set below 2^10, rescaled at 2^15
-
-#define MFMA3(acc_, ah_, al_, bh_, bl_)                                             \
-    {                                                                               \
-        f32x16 c_ = acc_;                                                           \
-        c_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(al_, bh_, c_, 0, 0, 0);         \
-        c_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah_, bl_, c_, 0, 0, 0);         \
-        c_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah_, bh_, c_, 0, 0, 0);         \
-        acc_ = c_;                                                                  \
-    }
-
-// 8 scaled values -> (hi, lo) fp16 fragments
-__device__ __forceinline__ void split8h(const float (&x)[8], int e, f16x8 &fh, f16x8 &fl) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float xs = __builtin_amdgcn_ldexpf(x[j], e);
-        const _Float16 hh = (_Float16)xs;
-        fh[j] = hh;
-        fl[j] = (_Float16)(xs - (float)hh);
-    }
-}
-
-// the value held by the neighbouring lane (lane ^ 1): the other component of the same complex column
-__device__ __forceinline__ float pair_swap(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, false));
-}
+// E_TARGET, E_LIMIT, MFMA3, split8h, pair_swap: dft_split.h
 
 template <int KIND, bool MIX>
 __global__ __launch_bounds__(NTHREADS) void dft_h2_kernel(DftH2Args g, const uint4 *__restrict__ img, int kA, int NS, long NT) {
@@ -375,7 +346,10 @@ __global__ __launch_bounds__(NTHREADS) void dft_h2_kernel(DftH2Args g, const uin
 // adds the slots in a fixed order (deterministic, no atomics).
 // Measured (config 3, 251 x 251 x 4096 planes): 0.59 ms against 0.42 + 0.42 ms for the pass and the separate reduction
 // (0.49 ms with the OTF replaced by a constant; 0.90 ms with the OTF read straight from memory, lane = row).
-__device__ __forceinline__ float wave_max(float m) {
+
+// The wave's maximum in every lane, the value of wave_max (reduce_dev.h), in this kernel's own instruction sequence: four DPP
+// steps and two lane swaps, no LDS crossbar traffic beside the kernel's fragment reads.
+__device__ __forceinline__ float wave_max_dpp(float m) {
 #define H2_DPPMAX(ctrl_) m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, m), ctrl_, 0xF, 0xF, false)))
     H2_DPPMAX(0xB1);     // quad_perm [1,0,3,2]
     H2_DPPMAX(0x4E);     // quad_perm [2,3,0,1]
@@ -464,7 +438,7 @@ __global__ __launch_bounds__(NTHREADS) void dft_h2_adjmix_kernel(DftH2Args g, Df
     {                                                                                                           \
         float m_ = 0.f;                                                                                         \
         _Pragma("unroll") for (int j = 0; j < 8; ++j) m_ = fmaxf(m_, fmaxf(fabsf(x0[j]), fabsf(x1[j])));        \
-        m_ = wave_max(m_);                                                                                      \
+        m_ = wave_max_dpp(m_);                                                                                  \
         p_ = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_frexp_expf(m_));                                   \
     }
     // partial sums of one k_beta leave the wave: the two lane halves (different wavelengths of the same rows) are added,

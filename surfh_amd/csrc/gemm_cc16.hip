@@ -15,6 +15,7 @@
 // two 64 KB stages.  (A 128 x 256 producer / consumer tile needs 48 KB per K step for half the flops: 60 B/clk per CU, the
 // width of the L1 fill path.)
 #include "gemm_f32.h"
+#include "f16_split.h"
 #include "lds_attr.h"
 #include <cmath>
 #include <cstdlib>
@@ -32,20 +33,12 @@ constexpr int PIECE = ROWS * BK;              // one fp16 piece of one stage (el
 constexpr int STAGE = 2 * PIECE;              // 64 KB
 constexpr size_t LDS_BYTES = (size_t)2 * STAGE * sizeof(unsigned short);
 
-// power of two that brings `amax` to [2^13, 2^14); 1 for an all-zero row (the gather uses the same function: f16x2_block_scale, kernels.hip)
-__device__ __forceinline__ float f16x2_scale_of(float amax) {
-    if (!(amax > 0.f)) return 1.f;
-    const int e = (int)((__float_as_uint(amax) >> 23) & 0xFF) - 127;
-    int s = e - 13;
-    s = s < -126 ? -126 : (s > 127 ? 127 : s);
-    return __uint_as_float((unsigned)(s + 127) << 23);
-}
-
-// dst[q*plane + row*ld + k] = fp16 piece q of src[row*ld + k] / scale(rowmax[row]), round to nearest; ld multiple of 4
+// dst[q*plane + row*ld + k] = fp16 piece q of src[row*ld + k] / scale(rowmax[row]), round to nearest; ld multiple of 4.  The scale is
+// f16x2_scale (f16_split.h): the function the gather and the ymat16 kernels (gather_kernels.hip) write their pieces under.
 __global__ __launch_bounds__(256) void split_rows2h_kernel(const float *__restrict__ src, const unsigned *__restrict__ rowmax,
                                                            unsigned short *__restrict__ dst, int ld, long plane) {
     const int row = blockIdx.y;
-    const float inv = 1.f / f16x2_scale_of(__uint_as_float(rowmax[row]));
+    const float inv = 1.f / f16x2_scale(__uint_as_float(rowmax[row]));
     const int k4 = (blockIdx.x * 256 + threadIdx.x) * 4;
     if (k4 >= ld) return;
     const long o = (long)row * ld + k4;
@@ -84,7 +77,7 @@ __device__ __forceinline__ int cc2_seg_end(int k, int segLinP) {
     const int e1 = col * segLinP + (in / 1024 + 1) * 1024, e2 = (col + 1) * segLinP;
     return __builtin_amdgcn_readfirstlane(e1 < e2 ? e1 : e2);
 }
-// old / new for two power-of-two scales (f16x2_scale_of) given by their exponent fields, exact; difference clamped to the normal range
+// old / new for two power-of-two scales (f16x2_scale) given by their exponent fields, exact; difference clamped to the normal range
 __device__ __forceinline__ float cc2_pow2_ratio(unsigned eo, unsigned en) {
     int e = (int)eo - (int)en + 127;
     e = e < 1 ? 1 : (e > 254 ? 254 : e);
@@ -424,7 +417,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_f16x2_cc_kernel(GemmGroup grp)
                 const int lr = srow + i * 16 + r;
                 int row = m0 + lr;
                 row = row < g.M ? row : g.M - 1;
-                rsc[r] = bs ? (seg >= 0 ? __uint_as_float((unsigned)sctab[(seg - seg0) * BM + lr] << 23) : 1.f) : f16x2_scale_of(__uint_as_float(g.amax[(long)b * g.M + row]));
+                rsc[r] = bs ? (seg >= 0 ? __uint_as_float((unsigned)sctab[(seg - seg0) * BM + lr] << 23) : 1.f) : f16x2_scale(__uint_as_float(g.amax[(long)b * g.M + row]));
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {

@@ -1,5 +1,5 @@
-// What the prior kernels of the maps (kernels.hip) and of the cube (huber_vox.hip) share: the Huber potential in one arithmetic,
-// and the fixed-order float64 reductions that make repeated calls give the same bits.
+// What the prior kernels of the maps and planes (huber_kernels.hip, coupled_prior.hip), of the cube (huber_vox.hip) and the robust data
+// term (robust_data.hip) share: the Huber potential and its two siblings, each in one arithmetic.
 // phi(u) = u^2 / 2 (|u| <= delta), delta (|u| - delta / 2) beyond; phi'(u) = u or delta sign(u); w(u) = phi'(u) / u, w(0) = 1.
 // Differences and phi' in fp32, phi in float64 (it is only ever summed); delta = +inf is the quadratic potential.
 // The other potentials of the 3MG solvers (surfh_set_potential), normalised alike (phi ~ u^2 / 2 at 0, w(0) = 1), t = u / delta:
@@ -14,8 +14,6 @@
 #include <type_traits>
 
 namespace {
-
-constexpr int RED_TPB = 256;          // block size of every kernel that uses the reductions below
 
 __device__ __forceinline__ float huber_dphi(float u, float delta) { return fabsf(u) <= delta ? u : copysignf(delta, u); }
 __device__ __forceinline__ float huber_w(float u, float delta) { return fabsf(u) <= delta ? 1.f : delta / fabsf(u); }
@@ -58,48 +56,6 @@ inline bool pot_dispatch(int kind, F &&f) {
     case POT_HEBERT_LEAHY: f(std::integral_constant<int, POT_HEBERT_LEAHY>()); return true;
     default: return false;
     }
-}
-
-__device__ inline double block_sum(double v) {
-    __shared__ double sm[RED_TPB / 64];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) sm[w] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0)
-        for (int k = 0; k < RED_TPB / 64; ++k) s += sm[k];
-    return s;   // valid in thread 0
-}
-
-// K block sums in a fixed order; part[k * nparts + b] = sum over block b of v[k]
-template <int K>
-__device__ inline void block_sums_to(double (&v)[K], double *__restrict__ part, int b, int nparts) {
-    __shared__ double sm[K][RED_TPB / 64];
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_down(v[k], o, 64);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) sm[k][threadIdx.x >> 6] = v[k];
-    __syncthreads();
-    if (threadIdx.x < K) {
-        double s = 0.0;
-        for (int w = 0; w < RED_TPB / 64; ++w) s += sm[threadIdx.x][w];
-        part[(long)threadIdx.x * nparts + b] = s;
-    }
-}
-template <int K>
-__device__ inline void block_sums_to(double (&v)[K], double *__restrict__ part) {
-    block_sums_to<K>(v, part, blockIdx.x, gridDim.x);
-}
-
-// out[k] = sum_i part[k * nparts + i], one block per k, reduce_final_kernel's order
-__global__ __launch_bounds__(RED_TPB) void parts_reduce_kernel(const double *__restrict__ part, int nparts, double *__restrict__ out) {
-    double s = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += RED_TPB) s += part[(long)blockIdx.x * nparts + i];
-    s = block_sum(s);
-    if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
 
 }  // namespace

@@ -10,9 +10,10 @@
 // the memory traffic).  No 16-byte accesses: with an odd plane size (251 x 251, 501 x 501) neither the rows nor the planes
 // l - 1, l + 1 are 16-byte aligned with respect to each other.
 // Reductions: float64 per thread, per block in a fixed order into `scratch` [K][blocks], then one block per sum -- the same
-// inputs give the same bits (huber_dev.h).
+// inputs give the same bits (reduce_dev.h).
 #include "huber_dev.h"
 #include "kernels.h"
+#include "reduce_dev.h"
 
 namespace {
 

@@ -1,4 +1,4 @@
-// The float64 scalar algebra every 3MG step shares, on the host (plan_solvers.hip) and in the plane kernels (kernels.hip).
+// The float64 scalar algebra every 3MG step shares, on the host (plan_solvers.hip) and in the plane kernels (cg_kernels.hip, huber_kernels.hip).
 // A plain C++ compiler may include this header: the qualifiers exist only under a HIP compiler.
 #pragma once
 #include <cmath>

@@ -9,7 +9,7 @@
 // per plane in a fixed order by a second kernel: no atomics, the same bits for the same inputs), nn_add_planes the axpy with a
 // per-plane coefficient.  Both choose the 16-byte path plane by plane: a plane base is aligned only when npix % 4 == 0, or by chance.
 #include "plan_internal.h"
-#include "huber_dev.h"
+#include "reduce_dev.h"
 
 namespace {
 constexpr int NN_MAX_BLOCKS = 256;       // 4 sums x 256 partials: the 1024 doubles every plan's dscratch holds

@@ -2,7 +2,7 @@
 // on device buffers, and the entry points that only wrap them (surfh_forward* / surfh_adjoint* / surfh_fwadj*, Model_WCT,
 // surfh_normal_dev, surfh_prior_add_dev, the spectral-domain operator, the LMM helpers).  They read the plan that plan.hip builds;
 // the solvers in plan_solvers.hip call them.  Plan struct and data layout: plan_internal.h.  All device work goes through
-// gemm_f32.hip, dft_h2.hip, dft_ct.hip and kernels.hip on the plan's stream.
+// gemm_f32.hip, dft_h2.hip, dft_ct.hip and the *_kernels.hip files on the plan's stream.
 #include "plan_internal.h"
 
 namespace surfh_impl {

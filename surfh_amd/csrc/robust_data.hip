@@ -9,12 +9,13 @@
 // the widest access every operand's address allows (16 / 8 / 4 bytes), so a wavefront reads 1 KiB contiguous per operand and
 // step with V = 4; the n % V last elements go to the first threads of the grid, one each.  At most ROB_BLOCKS blocks of 256.
 // Reductions: float64 per thread, per block in a fixed order into `scratch` [K][blocks], then one block per sum -- the same
-// inputs give the same bits (huber_dev.h).
+// inputs give the same bits (reduce_dev.h).
 #include <cstdint>
 #include <initializer_list>
 
 #include "huber_dev.h"
 #include "kernels.h"
+#include "reduce_dev.h"
 
 namespace {
 
