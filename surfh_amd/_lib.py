@@ -84,6 +84,9 @@ def load():
                            "(the HIP path has no CPU fallback)")
     L = C.CDLL(LIB_PATH)
     vp = C.c_void_p
+    tail = [c_float_p, C.c_int32, C.c_double, C.c_int32, c_float_p, c_double_p, c_int32_p]     # x0, max_iter, tol, refresh, x, grad_norm, nit
+    admm = [c_float_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, c_float_p, c_double_p, c_int32_p]  # start, outer, inner, tol, refresh, out, trace, nit
+    cb = [CG_CALLBACK, vp]                                                                       # callback, user
     L.surfh_last_error.restype = C.c_char_p
     L.surfh_version.restype = C.c_int
     L.surfh_plan_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
@@ -96,18 +99,15 @@ def load():
         getattr(L, n).argtypes = [vp, c_float_p, c_float_p]
     for n in ("surfh_forward_dev", "surfh_adjoint_dev", "surfh_adjoint_ref_dev", "surfh_fwadj_dev"):
         getattr(L, n).argtypes = [vp, vp, vp]
-    L.surfh_cg.argtypes = [vp, c_float_p, C.c_double, C.c_double, c_float_p, C.c_int32, C.c_double, C.c_int32,
-                           c_float_p, c_double_p, c_int32_p]
+    L.surfh_cg.argtypes = [vp, c_float_p, C.c_double, C.c_double] + tail
     L.surfh_tst_create.argtypes = [C.c_int32] * 4 + [c_double_p, c_int32_p, C.c_int64, c_float_p, C.c_int32, C.POINTER(vp)]
     L.surfh_tst_destroy.argtypes = [vp]
     for n in ("surfh_tst_forward", "surfh_tst_adjoint", "surfh_tst_fwadj"):
         getattr(L, n).argtypes = [vp, c_float_p, c_float_p]
     L.surfh_tst_last_error.restype = C.c_char_p
     L.surfh_wct_expsol.argtypes = [vp, c_float_p, c_double_p, c_double_p, c_float_p]
-    L.surfh_cg_planes.argtypes = [vp, c_float_p, C.c_double, C.c_double, c_float_p, C.c_int32, C.c_double, C.c_int32,
-                                  c_float_p, c_double_p, c_int32_p]
-    L.surfh_cg_cb.argtypes = [vp, c_float_p, C.c_double, C.c_double, c_float_p, C.c_int32, C.c_double, C.c_int32,
-                              c_float_p, c_double_p, c_int32_p, CG_CALLBACK, vp]
+    L.surfh_cg_planes.argtypes = L.surfh_cg.argtypes
+    L.surfh_cg_cb.argtypes = L.surfh_cg.argtypes + cb
     L.surfh_mmmg.argtypes = L.surfh_cg_cb.argtypes
     L.surfh_randn_dev.argtypes = [vp, vp, C.c_int64, C.c_uint64, C.c_uint32, C.c_uint32]
     L.surfh_po_data_dev.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_double, vp]
@@ -117,25 +117,20 @@ def load():
     L.surfh_cg_sample.argtypes = [vp, c_float_p, C.c_double, C.c_double, c_float_p, C.c_int32, C.c_double, C.c_int32, C.c_int32,
                                   C.c_uint64, c_float_p, c_float_p, c_float_p, c_float_p, c_double_p, c_double_p, c_double_p,
                                   c_int32_p, c_double_p, SAMPLE_CALLBACK, vp]
-    L.surfh_mmmg_huber.argtypes = [vp, c_float_p, C.c_double, C.c_double, C.c_double, c_float_p, C.c_int32, C.c_double, C.c_int32,
-                                   c_float_p, c_double_p, c_int32_p, c_double_p, CG_CALLBACK, vp]
+    L.surfh_mmmg_huber.argtypes = [vp, c_float_p] + [C.c_double] * 3 + tail + [c_double_p] + cb
     L.surfh_huber_prior_dev.argtypes = [vp, vp, vp, C.c_double, C.c_double, c_double_p]
     L.surfh_huber_curv_dev.argtypes = [vp, vp, vp, vp, C.c_double, c_double_p]
-    L.surfh_mmmg_huber_vox.argtypes = [vp, c_float_p] + [C.c_double] * 5 + [c_float_p, C.c_int32, C.c_double, C.c_int32,
-                                                                            c_float_p, c_double_p, c_int32_p, c_double_p, CG_CALLBACK, vp]
+    L.surfh_mmmg_huber_vox.argtypes = [vp, c_float_p] + [C.c_double] * 5 + tail + [c_double_p] + cb
     L.surfh_huber_vox_prior_dev.argtypes = [vp, vp, vp] + [C.c_double] * 4 + [c_double_p]
     L.surfh_huber_vox_curv_dev.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, c_double_p]
-    L.surfh_mmmg_robust.argtypes = [vp, c_float_p] + [C.c_double] * 4 + [c_float_p, C.c_int32, C.c_double, C.c_int32,
-                                                                         c_float_p, c_double_p, c_int32_p, c_double_p, c_float_p, CG_CALLBACK, vp]
-    L.surfh_mmmg_robust_vox.argtypes = [vp, c_float_p] + [C.c_double] * 6 + [c_float_p, C.c_int32, C.c_double, C.c_int32,
-                                                                             c_float_p, c_double_p, c_int32_p, c_double_p, c_float_p, CG_CALLBACK, vp]
+    L.surfh_mmmg_robust.argtypes = [vp, c_float_p] + [C.c_double] * 4 + tail + [c_double_p, c_float_p] + cb
+    L.surfh_mmmg_robust_vox.argtypes = [vp, c_float_p] + [C.c_double] * 6 + tail + [c_double_p, c_float_p] + cb
     L.surfh_robust_data_dev.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_double, vp, c_double_p]
     L.surfh_robust_curv_dev.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, C.c_double, c_double_p]
     L.surfh_mmmg_huber_planes.argtypes = L.surfh_mmmg_huber.argtypes
     L.surfh_huber_planes_prior_dev.argtypes = [vp, vp, vp, C.c_double, C.c_double, c_double_p, c_double_p]
     L.surfh_huber_planes_curv_dev.argtypes = [vp, vp, vp, vp, C.c_double, c_double_p]
-    L.surfh_mmmg_huber_planes_ex.argtypes = [vp, c_float_p, C.c_double, c_double_p, c_double_p, C.c_int32, c_float_p, C.c_int32,
-                                             C.c_double, C.c_int32, c_float_p, c_double_p, c_int32_p, c_double_p, CG_CALLBACK, vp]
+    L.surfh_mmmg_huber_planes_ex.argtypes = [vp, c_float_p, C.c_double, c_double_p, c_double_p, C.c_int32] + tail + [c_double_p] + cb
     L.surfh_huber_planes_prior_dev_ex.argtypes = [vp, vp, vp, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p]
     L.surfh_huber_planes_curv_dev_ex.argtypes = [vp, vp, vp, vp, c_double_p, C.c_int32, c_double_p]
     L.surfh_debug_planes_passes.argtypes = [vp] + [C.c_int32] * 5 + [vp] * 4 + [c_double_p, c_double_p, c_double_p]
@@ -219,17 +214,13 @@ def load():
     L.surfh_adjoint_templates.argtypes = [vp, c_float_p, c_float_p, c_float_p]
     for n in ("surfh_forward_templates_dev", "surfh_adjoint_templates_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, vp]
-    L.surfh_cg_templates.argtypes = [vp, c_float_p, c_float_p, C.c_double, C.c_double, c_float_p, C.c_int32, C.c_double, C.c_int32,
-                                     c_float_p, c_double_p, c_int32_p]
-    L.surfh_cg_templates_cb.argtypes = L.surfh_cg_templates.argtypes + [CG_CALLBACK, vp]
+    L.surfh_cg_templates.argtypes = [vp, c_float_p, c_float_p, C.c_double, C.c_double] + tail
+    L.surfh_cg_templates_cb.argtypes = L.surfh_cg_templates.argtypes + cb
     L.surfh_joint_criterion.argtypes = [vp, c_float_p, c_float_p, C.c_double, C.c_double, C.c_double, c_double_p]
-    L.surfh_cg_nonneg.argtypes = [vp, c_float_p, C.c_double, C.c_double, C.c_double, c_float_p, C.c_int32, C.c_int32, C.c_double,
-                                  C.c_int32, c_float_p, c_double_p, c_int32_p]
-    L.surfh_cg_templates_nonneg.argtypes = [vp, c_float_p, c_float_p, C.c_double, C.c_double, C.c_double, c_float_p, C.c_int32, C.c_int32,
-                                            C.c_double, C.c_int32, c_float_p, c_double_p, c_int32_p]
+    L.surfh_cg_nonneg.argtypes = [vp, c_float_p, C.c_double, C.c_double, C.c_double] + admm
+    L.surfh_cg_templates_nonneg.argtypes = [vp, c_float_p, c_float_p, C.c_double, C.c_double, C.c_double] + admm
     L.surfh_nn_project_dev.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, C.c_double, c_double_p]
-    L.surfh_cg_planes_nonneg.argtypes = [vp, c_float_p, C.c_double, C.c_double, c_double_p, c_float_p, C.c_int32, C.c_int32, C.c_double,
-                                         C.c_int32, c_float_p, c_double_p, c_int32_p]
+    L.surfh_cg_planes_nonneg.argtypes = [vp, c_float_p, C.c_double, C.c_double, c_double_p] + admm
     L.surfh_nn_project_planes_dev.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int64, c_double_p, c_double_p]
     _lib = L
     return L
@@ -240,39 +231,132 @@ def check(rc: int, exc=RuntimeError):
         raise exc(load().surfh_last_error().decode("utf-8", "replace"))
 
 
-def _solve(model, fn, data, lead, x0, max_iter, tol, refresh, outs, callback, planes=1, squeeze=True):
-    """Run one host-buffer solver of the C ABI on ``model``'s plan:
-    ``fn(plan, y, *lead, x0, max_iter, tol, refresh, x, grad_norm, nit, *outs, callback, NULL)``, ``lead`` the solver's doubles
-    (weights, thresholds) and ``outs`` its further out-buffers.  ``grad_norm`` has one column per plane, or is ``[nit+1]`` when
-    ``squeeze`` (a single image).  Returns ``(x, grad_norm, nit)``."""
-    y = np.ascontiguousarray(np.asarray(data, dtype=np.float32).reshape(-1))
-    if y.size != model.osize:
-        raise ValueError("data size mismatch")
-    x0a = None if x0 is None else np.ascontiguousarray(np.asarray(x0, dtype=np.float32).reshape(-1))
-    if x0a is not None and x0a.size != model.isize:
-        raise ValueError("x0 size mismatch")
-    x = np.empty(model.isize, dtype=np.float32)
-    gn = np.zeros((max_iter + 1, planes), dtype=np.float64)
-    nit = C.c_int32()
-    err = []
+def fptr(a: np.ndarray):
+    return a.ctypes.data_as(c_float_p)
 
-    def tramp(_user, it, gptr, xptr):
+
+def dptr(a: np.ndarray):
+    return a.ctypes.data_as(c_double_p)
+
+
+def iptr(a: np.ndarray):
+    return a.ctypes.data_as(c_int32_p)
+
+
+def u8ptr(a: np.ndarray):
+    return a.ctypes.data_as(c_uint8_p)
+
+
+# ---- marshalling: what every wrapper hands to a ``float *``, a ``void *`` or a ``uint64_t`` ---------------------------------------
+def f32_vec(a, n, message, optional=False):
+    """``a`` as the flat contiguous float32 vector a ``float *`` argument takes (``a`` itself where it already is one, a copy
+    otherwise); ``ValueError(message)`` unless it has ``n`` elements.  ``optional``: ``None`` passes through (``x0``, ``s0``)."""
+    if a is None and optional:
+        return None
+    v = np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1))
+    if v.size != n:
+        raise ValueError(message)
+    return v
+
+
+def opt_fptr(a):
+    return None if a is None else fptr(a)
+
+
+def dev_ptr(t):
+    """The ``void *`` of a device argument: a tensor (anything with a ``data_ptr`` method), a raw address (``int``), or ``None`` (NULL)."""
+    if t is None:
+        return None
+    return C.c_void_p(t if isinstance(t, int) else t.data_ptr())
+
+
+def seed64(seed):
+    """A Python integer as the generator's 64-bit key (its low 64 bits)."""
+    return C.c_uint64(int(seed) & (2 ** 64 - 1))
+
+
+def host_call(fn, plan, x, nin, shape_out):
+    """``fn(plan, in, out)`` on host arrays: ``x`` (``nin`` elements) in, float64 ``shape_out`` out."""
+    a = f32_vec(x, nin, f"input has {np.size(x)} elements, expected {nin}")
+    out = np.empty(int(np.prod(shape_out)), dtype=np.float32)
+    check(fn(plan, fptr(a), fptr(out)))
+    return out.astype(np.float64).reshape(shape_out)
+
+
+# ---- callbacks ------------------------------------------------------------------------------------------------------------------
+def trampoline(cbtype, callback, convert):
+    """The C callable of a Python ``callback`` (``cbtype``: ``CG_CALLBACK`` or ``SAMPLE_CALLBACK``; the NULL callback for ``None``) and
+    ``finish(rc, exc)``, to be called with the entry point's return code once it has returned.  The callback runs as
+    ``callback(*convert(*raw))``, ``raw`` the C arguments after ``user``; a truthy return gives the library 1 (stop).  An exception
+    in the callback (or in ``convert``) never unwinds through the C frame: it is held, the library is told to stop, and ``finish``
+    raises it -- before it looks at the return code, which it turns into ``exc`` through ``check``."""
+    held = []
+
+    def tramp(_user, *raw):
         try:
-            g = np.ctypeslib.as_array(gptr, shape=(it + 1, planes)).copy()
-            xi = np.ctypeslib.as_array(xptr, shape=(model.isize,)).astype(np.float64).reshape(model.ishape)
-            return 1 if callback(it, g[:, 0] if squeeze else g, xi) else 0
-        except BaseException as e:          # never unwind through the C frame
-            err.append(e)
+            return 1 if callback(*convert(*raw)) else 0
+        except BaseException as e:
+            held.append(e)
             return 1
 
-    cb = CG_CALLBACK(tramp) if callback is not None else CG_CALLBACK()
+    def finish(rc, exc=RuntimeError):
+        if held:
+            raise held[0]
+        check(rc, exc)
+
+    return (cbtype(tramp) if callback is not None else cbtype()), finish
+
+
+def iterate_args(size, shape, planes=1, squeeze=True):
+    """The ``convert`` of both callback types, ``(it, trace, x)`` and ``(sample, nit, trace, x)`` -> ``(it or sample, trace, x)``:
+    copies of the trace so far (``[n+1, planes]`` for the count ``n`` in front of it, ``[n+1]`` when ``squeeze``) and of the
+    iterate (``size`` floats) as float64 ``shape``."""
+    def convert(*raw):
+        t = np.ctypeslib.as_array(raw[-2], shape=(raw[-3] + 1, planes)).copy()
+        x = np.ctypeslib.as_array(raw[-1], shape=(size,)).astype(np.float64).reshape(shape)
+        return raw[0], (t[:, 0] if squeeze else t), x
+
+    return convert
+
+
+# ---- host-buffer solvers --------------------------------------------------------------------------------------------------------
+def _solve(model, fn, data, lead, x0, max_iter, tol, refresh, outs, callback, planes=1, squeeze=True, size=None, shape=None,
+           exc=RuntimeError):
+    """Run one host-buffer solver of the C ABI on ``model``'s plan:
+    ``fn(plan, y, *lead, x0, max_iter, tol, refresh, x, grad_norm, nit, *outs, callback, NULL)``, ``lead`` the solver's leading
+    arguments (numbers: weights, thresholds; ctypes values pass as they are) and ``outs`` its further out-buffers.  The iterate has
+    ``size`` elements and comes back as ``shape`` (default: ``model.isize``, ``model.ishape``).  ``grad_norm`` has one column per
+    plane, or is ``[nit+1]`` when ``squeeze`` (a single image).  A failure of the library raises ``exc``.  Returns
+    ``(x, grad_norm, nit)``."""
+    size, shape = (model.isize, model.ishape) if size is None else (size, shape)
+    y = f32_vec(data, model.osize, "data size mismatch")
+    x0a = f32_vec(x0, size, "x0 size mismatch", optional=True)
+    x = np.empty(size, dtype=np.float32)
+    gn = np.zeros((max_iter + 1, planes), dtype=np.float64)
+    nit = C.c_int32()
+    cb, finish = trampoline(CG_CALLBACK, callback, iterate_args(size, shape, planes, squeeze))
     lead = [v if isinstance(v, (C._Pointer, C._SimpleCData)) else float(v) for v in lead]       # ctypes arguments pass as they are
-    check(fn(model._plan, fptr(y), *lead, fptr(x0a) if x0a is not None else None, int(max_iter), float(tol),
-             int(refresh), fptr(x), dptr(gn), C.byref(nit), *outs, cb, None))
-    if err:
-        raise err[0]
+    finish(fn(model._plan, fptr(y), *lead, opt_fptr(x0a), int(max_iter), float(tol), int(refresh), fptr(x), dptr(gn), C.byref(nit),
+              *outs, cb, None), exc)
     gn = gn[: nit.value + 1]
-    return x.astype(np.float64).reshape(model.ishape), (gn[:, 0] if squeeze else gn).copy(), nit.value
+    return x.astype(np.float64).reshape(shape), (gn[:, 0] if squeeze else gn).copy(), nit.value
+
+
+def _solve_nonneg(model, fn, data, lead, start, outer, inner, tol, refresh, size=None, shape=None, planes=None):
+    """Run one ADMM solver of the C ABI on ``model``'s plan:
+    ``fn(plan, y, *lead, start, outer, inner, tol, refresh, out, trace, nit)``, ``lead`` as in ``_solve`` (the penalty last: a number,
+    or the pointer to one per plane), ``start`` optional.  The trace is ``[outer+1, 4]``, or ``[outer+1, 4, planes]`` for the
+    plane-wise solver.  A failure of the library raises ``ValueError``.  Returns ``(out, trace, nit)``, the trace whole."""
+    size, shape = (model.isize, model.ishape) if size is None else (size, shape)
+    y = f32_vec(data, model.osize, "data size mismatch")
+    s = f32_vec(start, size, "x0 size mismatch", optional=True)
+    out = np.empty(size, dtype=np.float32)
+    trace = np.zeros((int(outer) + 1, 4) + (() if planes is None else (planes,)), dtype=np.float64)
+    nit = C.c_int32()
+    lead = [v if isinstance(v, (C._Pointer, C._SimpleCData)) else float(v) for v in lead]
+    check(fn(model._plan, fptr(y), *lead, opt_fptr(s), int(outer), int(inner), float(tol), int(refresh), fptr(out), dptr(trace),
+             C.byref(nit)), ValueError)
+    return out.astype(np.float64).reshape(shape), trace, nit.value
 
 
 def solve(model, fn, data, mu, mu_reg, x0, max_iter, tol, refresh, callback, planes=1, squeeze=True):
@@ -287,20 +371,27 @@ def solve_huber(model, data, mu, mu_reg, delta, x0, max_iter, tol, refresh, call
     return _solve(model, load().surfh_mmmg_huber, data, (mu, mu_reg, delta), x0, max_iter, tol, refresh, (pv,), callback) + (pv[0],)
 
 
-def solve_huber_planes(model, data, mu, mu_reg, delta, x0, max_iter, tol, refresh, callback, planes, squeeze):
-    """``surfh_mmmg_huber_planes``.  Returns ``(x, grad_norm, nit, prior_values)``, prior_values[l] = sum_k sum phi(D_k x_l) of
-    the returned iterate."""
+def planes_entry(name, coupling, *values):
+    """The entry point of a plane-wise prior call and its prior arguments.  ``coupling`` None: the scalar entry point ``name``, the
+    ``values`` (``mu_reg``, ``delta``) as numbers, left to the library to check.  A coupling code (0 or 1): ``name + "_ex"``, the values
+    float64 arrays ``[planes]`` (checked by ``blurred2d.plane_prior_args``), then the code."""
+    if coupling is None:
+        return getattr(load(), name), tuple(float(v) for v in values)
+    return getattr(load(), name + "_ex"), tuple(dptr(v) for v in values) + (C.c_int32(int(coupling)),)
+
+
+def solve_huber_planes(model, data, mu, mu_reg, delta, x0, max_iter, tol, refresh, callback, planes, squeeze, coupling=None):
+    """``surfh_mmmg_huber_planes``, or with ``coupling`` (the code, 0 or 1) ``surfh_mmmg_huber_planes_ex`` on ``mu_reg`` and ``delta``
+    float64 arrays ``[planes]``.  Returns ``(x, grad_norm, nit, prior_values)``, prior_values[l] = sum_k sum phi(D_k x_l) of the
+    returned iterate (sum phi over the groups of the coupling)."""
+    fn, prior = planes_entry("surfh_mmmg_huber_planes", coupling, mu_reg, delta)
     pv = np.zeros(planes, dtype=np.float64)
-    return _solve(model, load().surfh_mmmg_huber_planes, data, (mu, mu_reg, delta), x0, max_iter, tol, refresh, (dptr(pv),), callback,
-                  planes, squeeze) + (pv,)
+    return _solve(model, fn, data, (mu,) + prior, x0, max_iter, tol, refresh, (dptr(pv),), callback, planes, squeeze) + (pv,)
 
 
 def solve_huber_planes_ex(model, data, mu, mu_reg, delta, coupling, x0, max_iter, tol, refresh, callback, planes, squeeze):
-    """``surfh_mmmg_huber_planes_ex``: ``mu_reg`` and ``delta`` float64 arrays ``[planes]``, ``coupling`` the code (0 or 1).  Returns as
-    ``solve_huber_planes``; prior_values[l] = sum phi over the groups of the coupling."""
-    pv = np.zeros(planes, dtype=np.float64)
-    return _solve(model, load().surfh_mmmg_huber_planes_ex, data, (mu, dptr(mu_reg), dptr(delta), C.c_int32(int(coupling))), x0, max_iter,
-                  tol, refresh, (dptr(pv),), callback, planes, squeeze) + (pv,)
+    """``solve_huber_planes`` with its ``coupling`` in the place it has in ``surfh_mmmg_huber_planes_ex``."""
+    return solve_huber_planes(model, data, mu, mu_reg, delta, x0, max_iter, tol, refresh, callback, planes, squeeze, int(coupling))
 
 
 def solve_huber_vox(model, data, mu, spat_reg, spat_delta, spec_reg, spec_delta, x0, max_iter, tol, refresh, callback):
@@ -325,19 +416,3 @@ def solve_robust_vox(model, data, mu, data_delta, spat_reg, spat_delta, spec_reg
     vals, omega = (C.c_double * 4)(), np.zeros(model.osize, dtype=np.float32)
     return _solve(model, load().surfh_mmmg_robust_vox, data, (mu, data_delta, spat_reg, spat_delta, spec_reg, spec_delta), x0, max_iter,
                   tol, refresh, (vals, fptr(omega)), callback) + (tuple(vals), omega)
-
-
-def fptr(a: np.ndarray):
-    return a.ctypes.data_as(c_float_p)
-
-
-def dptr(a: np.ndarray):
-    return a.ctypes.data_as(c_double_p)
-
-
-def iptr(a: np.ndarray):
-    return a.ctypes.data_as(c_int32_p)
-
-
-def u8ptr(a: np.ndarray):
-    return a.ctypes.data_as(c_uint8_p)

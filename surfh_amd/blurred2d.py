@@ -20,7 +20,9 @@ from math import ceil, floor
 import numpy as np
 
 from . import _lib, instru
+from ._lib import dev_ptr
 from .linop import LinOp
+from .plan_owner import PlanOwner
 from . import potentials as _pot
 from .nonneg import NonnegResult, check_nonneg_args, result_from_planes_trace
 from .weights import DataWeights, check_data_weights
@@ -69,7 +71,7 @@ def plane_prior_args(n_planes: int, mu_reg, delta, coupling="none"):
     return r, d, code, True
 
 
-class Blurred2D(DataWeights, _pot.Potentials, LinOp):
+class Blurred2D(DataWeights, _pot.Potentials, PlanOwner, LinOp):
     def __init__(self, sotf, alpha_axis, beta_axis, instr: instru.IFU, step_degree: float, pointings: instru.CoordList):
         self.sotf = sotf
         self.alpha_axis = np.asarray(alpha_axis, dtype=np.float64)
@@ -147,17 +149,6 @@ class Blurred2D(DataWeights, _pot.Potentials, LinOp):
         del self._sotf_c                             # the plan holds its own copy
         assert L.surfh_isize(plan) == self.isize and L.surfh_osize(plan) == self.osize
 
-    def close(self):
-        if getattr(self, "_plan", None):
-            self._L.surfh_plan_destroy(self._plan)
-            self._plan = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     # ---- geometry (same rules as the reference classes) ---------------------------------------------
     @property
     def npix_slit_alpha_width(self) -> int:
@@ -234,19 +225,11 @@ class Blurred2D(DataWeights, _pot.Potentials, LinOp):
         return np.asarray(data, dtype=np.float64).reshape(self.slices_shape)
 
     # ---- operator -------------------------------------------------------------------------------------
-    def _call(self, fn, x, nin, shape_out):
-        a = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
-        if a.size != nin:
-            raise ValueError(f"input has {a.size} elements, expected {nin}")
-        out = np.empty(int(np.prod(shape_out)), dtype=np.float32)
-        _lib.check(fn(self._plan, _lib.fptr(a), _lib.fptr(out)))
-        return out.astype(np.float64).reshape(shape_out)
-
     def forward(self, x):
-        return self._call(self._L.surfh_forward, x, self.isize, self.oshape)
+        return self._host(self._L.surfh_forward, x, self.isize, self.oshape)
 
     def adjoint(self, data):
-        return self._call(self._L.surfh_adjoint, data, self.osize, self.ishape)
+        return self._host(self._L.surfh_adjoint, data, self.osize, self.ishape)
 
     # ---- solver: regularised least squares by CG, one independent 2-D problem per plane -------------------
     def cg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, weights=None):
@@ -289,65 +272,36 @@ class Blurred2D(DataWeights, _pot.Potentials, LinOp):
                 raise ValueError(f"cg_nonneg: rho has shape {rho.shape}, expected a number or [{self.n_planes}]")
         for r in ([None] if rho is None else np.atleast_1d(rho)):
             check_nonneg_args(r, outer, inner, refresh)
-        y = np.ascontiguousarray(np.asarray(data, dtype=np.float32).reshape(-1))
-        if y.size != self.osize:
-            raise ValueError(f"data have {y.size} elements, expected {self.osize}")
-        x0a = None if x0 is None else np.ascontiguousarray(np.asarray(x0, dtype=np.float32).reshape(-1))
-        if x0a is not None and x0a.size != self.isize:
-            raise ValueError(f"x0 has {x0a.size} elements, expected {self.isize}")
+        y = _lib.f32_vec(data, self.osize, f"data have {np.size(data)} elements, expected {self.osize}")
+        x0a = _lib.f32_vec(x0, self.isize, f"x0 has {np.size(x0)} elements, expected {self.isize}", optional=True)
         if rho is None:
             rho = self.nonneg_rho(mu, mu_reg, weights=weights)
         rho = np.ascontiguousarray(np.broadcast_to(np.asarray(rho, dtype=np.float64), (self.n_planes,)))
-        out = np.empty(self.isize, dtype=np.float32)
-        trace = np.zeros((int(outer) + 1, 4, self.n_planes), dtype=np.float64)
-        nit = C.c_int32()
         with self.installed_weights(weights):
-            _lib.check(self._L.surfh_cg_planes_nonneg(self._plan, _lib.fptr(y), float(mu), float(mu_reg), _lib.dptr(rho),
-                                                      None if x0a is None else _lib.fptr(x0a), int(outer), int(inner), float(tol),
-                                                      int(refresh), _lib.fptr(out), _lib.dptr(trace), C.byref(nit)), ValueError)
-        return result_from_planes_trace(out.astype(np.float64).reshape(self.ishape), trace, rho, nit.value, squeeze=not self.batched)
+            x, trace, nit = _lib._solve_nonneg(self, self._L.surfh_cg_planes_nonneg, y, (mu, mu_reg, _lib.dptr(rho)), x0a, outer, inner,
+                                               tol, refresh, planes=self.n_planes)
+        return result_from_planes_trace(x, trace, rho, nit, squeeze=not self.batched)
 
     def nn_project_planes_dev(self, x_t, z_t, u_t, r_t, n_planes: int, npix: int, rho) -> np.ndarray:
         """The projection / dual update of one outer iteration on device tensors ``[n_planes, npix]`` (or raw device addresses),
         in place in ``z_t``, ``u_t`` and ``r_t`` (include/surfh_amd.h: surfh_nn_project_planes_dev); ``rho`` ``[n_planes]``.
         Returns ``[4, n_planes]``: ``|x - z'|^2, |z' - z|^2, #{z' == 0}, r.r`` per plane (synchronises)."""
-        def ptr(t):
-            return C.c_void_p(int(t)) if isinstance(t, int) else C.c_void_p(t.data_ptr())
-
         rho = np.ascontiguousarray(rho, dtype=np.float64)
         if rho.shape != (int(n_planes),):
             raise ValueError(f"rho has shape {rho.shape}, expected ({int(n_planes)},)")
         sums = np.zeros((4, int(n_planes)), dtype=np.float64)
-        _lib.check(self._L.surfh_nn_project_planes_dev(self._plan, ptr(x_t), ptr(z_t), ptr(u_t), ptr(r_t), int(n_planes), int(npix),
-                                                       _lib.dptr(rho), _lib.dptr(sums)), ValueError)
+        _lib.check(self._L.surfh_nn_project_planes_dev(self._plan, dev_ptr(x_t), dev_ptr(z_t), dev_ptr(u_t), dev_ptr(r_t), int(n_planes),
+                                                       int(npix), _lib.dptr(rho), _lib.dptr(sums)), ValueError)
         return sums
 
-    # ---- instrumentation (HIP events on the plan's stream, as spectroSigRLSCT) -----------------------------
-    def profile_enable(self, on=True):
-        _lib.check(self._L.surfh_profile_enable(self._plan, 1 if on else 0))
-
-    def profile_reset(self):
-        _lib.check(self._L.surfh_profile_reset(self._plan))
-
-    def profile(self) -> dict:
-        out = {}
-        for i in range(self._L.surfh_profile_count(self._plan)):
-            name, cnt, ms = C.c_char_p(), C.c_int64(), C.c_double()
-            _lib.check(self._L.surfh_profile_get(self._plan, i, C.byref(name), C.byref(cnt), C.byref(ms)))
-            out[name.value.decode()] = (cnt.value, ms.value)
-        return out
-
     # the same loop on device tensors (torch), no host synchronisation inside: see include/surfh_amd.h
-    def forward_dev(self, x_t, y_t):
-        _lib.check(self._L.surfh_forward_dev(self._plan, C.c_void_p(x_t.data_ptr()), C.c_void_p(y_t.data_ptr())))
-
     def cg_begin_dev(self, y_t, x_t, mu=1.0, mu_reg=0.0, weights=None):
         """``x_t`` [n_planes, Na, Nb] float32 on the plan's device: the start, then the current iterate (updated in place).
         ``weights`` (a host array): installed with ``set_data_weights`` before the loop begins and left in the plan, since the
         ``cg_step_dev`` calls that follow apply them; None: the model's own state."""
         if weights is not None:
             self.set_data_weights(weights)
-        _lib.check(self._L.surfh_cg_planes_begin_dev(self._plan, C.c_void_p(y_t.data_ptr()), float(mu), float(mu_reg), C.c_void_p(x_t.data_ptr())))
+        _lib.check(self._L.surfh_cg_planes_begin_dev(self._plan, dev_ptr(y_t), float(mu), float(mu_reg), dev_ptr(x_t)))
 
     def cg_step_dev(self, iters=1, refresh=50):
         _lib.check(self._L.surfh_cg_planes_step_dev(self._plan, int(iters), int(refresh)))
@@ -388,12 +342,8 @@ class Blurred2D(DataWeights, _pot.Potentials, LinOp):
             if delta is None:
                 return _lib.solve(self, self._L.surfh_mmmg_planes_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback,
                                   planes=self.n_planes, squeeze=not self.batched)
-            if extended:
-                x, gn, nit, self.last_prior_values = _lib.solve_huber_planes_ex(self, data, mu, mu_reg, delta, code, x0, max_iter, tol,
-                                                                                refresh, callback, self.n_planes, not self.batched)
-            else:
-                x, gn, nit, self.last_prior_values = _lib.solve_huber_planes(self, data, mu, mu_reg, delta, x0, max_iter, tol, refresh,
-                                                                             callback, self.n_planes, not self.batched)
+            x, gn, nit, self.last_prior_values = _lib.solve_huber_planes(self, data, mu, mu_reg, delta, x0, max_iter, tol, refresh, callback,
+                                                                         self.n_planes, not self.batched, code if extended else None)
             return x, gn, nit
 
     def huber_planes_prior_dev(self, x_t, g_t, mu_reg, delta, coupling="none"):
@@ -403,12 +353,8 @@ class Blurred2D(DataWeights, _pot.Potentials, LinOp):
         g_t += mu_reg sum_k D_k^T (w(m) D_k x_t) and the values are sum phi(m)."""
         mu_reg, delta, code, extended = plane_prior_args(self.n_planes, mu_reg, delta, coupling)
         sq, val = np.zeros(self.n_planes), np.zeros(self.n_planes)
-        x_p, g_p = C.c_void_p(x_t.data_ptr()), C.c_void_p(g_t.data_ptr())
-        if extended:
-            _lib.check(self._L.surfh_huber_planes_prior_dev_ex(self._plan, x_p, g_p, _lib.dptr(mu_reg), _lib.dptr(delta), code,
-                                                               _lib.dptr(sq), _lib.dptr(val)))
-        else:
-            _lib.check(self._L.surfh_huber_planes_prior_dev(self._plan, x_p, g_p, float(mu_reg), float(delta), _lib.dptr(sq), _lib.dptr(val)))
+        fn, prior = _lib.planes_entry("surfh_huber_planes_prior_dev", code if extended else None, mu_reg, delta)
+        _lib.check(fn(self._plan, dev_ptr(x_t), dev_ptr(g_t), *prior, _lib.dptr(sq), _lib.dptr(val)))
         return sq, val
 
     def huber_planes_curv_dev(self, x_t, p0_t, p1_t, delta, coupling="none") -> np.ndarray:
@@ -416,11 +362,8 @@ class Blurred2D(DataWeights, _pot.Potentials, LinOp):
         ``delta`` (a number or ``[n_planes]``) and ``coupling`` as in ``mmmg`` (under "isotropic" w = w(m) for both differences)."""
         _, delta, code, extended = plane_prior_args(self.n_planes, 0.0, delta, coupling)
         out = np.zeros((3, self.n_planes))
-        ptrs = [C.c_void_p(t.data_ptr()) for t in (x_t, p0_t, p1_t)]
-        if extended:
-            _lib.check(self._L.surfh_huber_planes_curv_dev_ex(self._plan, *ptrs, _lib.dptr(delta), code, _lib.dptr(out)))
-        else:
-            _lib.check(self._L.surfh_huber_planes_curv_dev(self._plan, *ptrs, float(delta), _lib.dptr(out)))
+        fn, prior = _lib.planes_entry("surfh_huber_planes_curv_dev", code if extended else None, delta)
+        _lib.check(fn(self._plan, dev_ptr(x_t), dev_ptr(p0_t), dev_ptr(p1_t), *prior, _lib.dptr(out)))
         return np.ascontiguousarray(out.T)
 
     def planes_passes_dev(self, x_t, g_t, p0_t, p1_t, mu_reg, delta, potential="huber", coupling="none"):
@@ -432,8 +375,8 @@ class Blurred2D(DataWeights, _pot.Potentials, LinOp):
         code = plane_coupling_code(coupling)
         r, d = per_plane(mu_reg, L, "mu_reg"), per_plane(delta, L, "delta")
         out = np.zeros((5, L), dtype=np.float64)
-        _lib.check(self._L.surfh_debug_planes_passes(self._plan, L, na, nb, _pot.kind_code(potential), code, C.c_void_p(x_t.data_ptr()),
-                                                     C.c_void_p(g_t.data_ptr()), C.c_void_p(p0_t.data_ptr()), C.c_void_p(p1_t.data_ptr()),
+        _lib.check(self._L.surfh_debug_planes_passes(self._plan, L, na, nb, _pot.kind_code(potential), code, dev_ptr(x_t),
+                                                     dev_ptr(g_t), dev_ptr(p0_t), dev_ptr(p1_t),
                                                      _lib.dptr(r), _lib.dptr(d), _lib.dptr(out)))
         return out[0].copy(), out[1].copy(), np.ascontiguousarray(out[2:].T)
 
@@ -445,7 +388,7 @@ class Blurred2D(DataWeights, _pot.Potentials, LinOp):
         (include/surfh_amd.h: surfh_debug_planes_cg)"""
         e = np.zeros(6, dtype=np.int64)
         e[:len(ext)] = ext
-        ptrs = [C.c_void_p(t.data_ptr()) for t in vectors] + [None] * (6 - len(vectors))
+        ptrs = [dev_ptr(t) for t in vectors] + [None] * (6 - len(vectors))
         sc_in = None if sc_in is None else np.ascontiguousarray(sc_in, dtype=np.float64)
         if sc_out is not None and not (isinstance(sc_out, np.ndarray) and sc_out.dtype == np.float64 and sc_out.flags.c_contiguous):
             raise ValueError("sc_out must be a contiguous float64 array (it is filled in place)")

@@ -131,12 +131,7 @@ class ImagerModel(LinOp):
 
     def _host(self, fn, x, nin, shape_out):
         m = self._attached()
-        a = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
-        if a.size != nin:
-            raise ValueError(f"input has {a.size} elements, expected {nin}")
-        out = np.empty(int(np.prod(shape_out)), dtype=np.float32)
-        _lib.check(getattr(m._L, fn)(m._plan, _lib.fptr(a), _lib.fptr(out)))
-        return out.astype(np.float64).reshape(shape_out)
+        return _lib.host_call(getattr(m._L, fn), m._plan, x, nin, shape_out)
 
     def forward(self, maps):
         return self._host("surfh_imager_forward", maps, self.isize, self.oshape)
@@ -159,9 +154,7 @@ def _owns_every_plane(m) -> bool:
 def check_imager_data(y_im, mu_imager, weights, osize: int):
     """``(y, w, mu)`` as the library takes them; ``ValueError`` on a wrong size, a negative or non-finite weight or
     ``mu_imager``.  No library call."""
-    y = np.ascontiguousarray(np.asarray(y_im, dtype=np.float32).reshape(-1))
-    if y.size != osize:
-        raise ValueError(f"imager data have {y.size} elements, the imager {osize}")
+    y = _lib.f32_vec(y_im, osize, f"imager data have {np.size(y_im)} elements, the imager {osize}")
     mu = float(mu_imager)
     if not (np.isfinite(mu) and mu >= 0):
         raise ValueError(f"mu_imager must be finite and >= 0, not {mu_imager!r}")

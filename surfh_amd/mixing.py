@@ -56,7 +56,7 @@ class Model_WCT(LinOp):
 
     def _call(self, fn, x, shape_in, shape_out):
         assert tuple(np.shape(x)) == tuple(shape_in)          # mixing.py:233,248,271
-        a = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
+        a = _lib.f32_vec(x, int(np.prod(shape_in)), "input size mismatch")
         out = np.empty(int(np.prod(shape_out)), dtype=np.float32)
         _lib.check(fn(self._plan, _lib.fptr(a), _lib.fptr(out)))
         return out.astype(np.float64).reshape(shape_out)
@@ -84,7 +84,7 @@ class Model_WCT(LinOp):
         reg = np.ascontiguousarray(reg_freq, dtype=np.float64)
         if mu.shape != (self.n_spec,) or reg.shape != (self.shape_target[0], self.shape_target[1] // 2 + 1):
             raise ValueError("L_mu must have one entry per map and reg_freq the half-spectrum shape")
-        a = np.ascontiguousarray(np.asarray(data, dtype=np.float32).reshape(-1))
+        a = _lib.f32_vec(data, self.osize, "data size mismatch")
         out = np.empty(int(np.prod(self.ishape)), dtype=np.float32)
         _lib.check(self._L.surfh_wct_expsol(self._plan, _lib.fptr(a), _lib.dptr(mu), _lib.dptr(reg), _lib.fptr(out)),
                    np.linalg.LinAlgError)
@@ -174,7 +174,7 @@ class MixingST(LinOp):
     def _run(self, fn, x, shape_in, shape_out):
         if tuple(np.shape(x)) != tuple(shape_in):
             raise ValueError(f"expected shape {tuple(shape_in)}, got {tuple(np.shape(x))}")
-        a = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
+        a = _lib.f32_vec(x, int(np.prod(shape_in)), "input size mismatch")
         out = np.empty(int(np.prod(shape_out)), dtype=np.float32)
         if fn(self._h, _lib.fptr(a), _lib.fptr(out)):
             raise RuntimeError(self._L.surfh_tst_last_error().decode())

@@ -19,19 +19,14 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib, instru
+from ._lib import dev_ptr
 from .geometry import ChannelGeometry
 from .linop import LinOp
+from .plan_owner import PlanOwner
 from . import potentials as _pot
 from .weights import DataWeights
 from .spectra import TemplateOps
 from .nonneg import NonnegOps
-
-
-def _ptr(t):
-    """Device pointer of a torch tensor (or a raw int)."""
-    if isinstance(t, int):
-        return C.c_void_p(t)
-    return C.c_void_p(t.data_ptr())
 
 
 class Channel(ChannelGeometry):
@@ -113,7 +108,7 @@ class _InstalledImager:
         return False
 
 
-class spectroSigRLSCT(DataWeights, TemplateOps, NonnegOps, _pot.Potentials, LinOp):
+class spectroSigRLSCT(DataWeights, TemplateOps, NonnegOps, _pot.Potentials, PlanOwner, LinOp):
     huber_prior_value = None            # prior value of the last mmmg(delta=...) result (set by mmmg)
     huber_prior_values = None           # (spatial, spectral) prior values of the last mmmg_vox result
     robust_weights = None               # omega(t) [osize] of the last mmmg / mmmg_vox result under data_delta (else None)
@@ -208,17 +203,9 @@ class spectroSigRLSCT(DataWeights, TemplateOps, NonnegOps, _pot.Potentials, LinO
 
     # ---- life cycle -----------------------------------------------------------------------
     def close(self):
-        for c in getattr(self, "all_channels", []):
+        for c in getattr(self, "all_channels", []):         # the channels' auxiliary plans first
             c.close()
-        if getattr(self, "_plan", None):
-            self._L.surfh_plan_destroy(self._plan)
-            self._plan = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
     @property
     def alpha_step(self) -> float:
@@ -228,19 +215,7 @@ class spectroSigRLSCT(DataWeights, TemplateOps, NonnegOps, _pot.Potentials, LinO
     def beta_step(self) -> float:
         return self.beta_axis[1] - self.beta_axis[0]
 
-    @property
-    def stream(self) -> int:
-        return int(self._L.surfh_stream(self._plan) or 0)
-
     # ---- host-array API (reference calling convention) --------------------------------------
-    def _host(self, fn, x, nin, shape_out):
-        a = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
-        if a.size != nin:
-            raise ValueError(f"input has {a.size} elements, expected {nin}")
-        out = np.empty(int(np.prod(shape_out)), dtype=np.float32)
-        _lib.check(fn(self._plan, _lib.fptr(a), _lib.fptr(out)))
-        return out.astype(np.float64).reshape(shape_out)
-
     def forward(self, maps):
         return self._host(self._L.surfh_forward, maps, self.isize, self.oshape)
 
@@ -253,18 +228,9 @@ class spectroSigRLSCT(DataWeights, TemplateOps, NonnegOps, _pot.Potentials, LinO
     def fwadj(self, x):
         return self._host(self._L.surfh_fwadj, x, self.isize, self.ishape)
 
-    # ---- device-pointer API (asynchronous on self.stream) ----------------------------------
-    def forward_dev(self, maps_t, y_t):
-        _lib.check(self._L.surfh_forward_dev(self._plan, _ptr(maps_t), _ptr(y_t)))
-
-    def adjoint_dev(self, y_t, maps_t):
-        _lib.check(self._L.surfh_adjoint_dev(self._plan, _ptr(y_t), _ptr(maps_t)))
-
-    def adjoint_ref_dev(self, y_t, maps_t):
-        _lib.check(self._L.surfh_adjoint_ref_dev(self._plan, _ptr(y_t), _ptr(maps_t)))
-
+    # ---- device-pointer API (asynchronous on self.stream; forward_dev ... fwadj_dev: PlanOwner) ------
     def normal_dev(self, d_t, q_t, mu: float = 1.0):
-        _lib.check(self._L.surfh_normal_dev(self._plan, _ptr(d_t), _ptr(q_t), float(mu)))
+        _lib.check(self._L.surfh_normal_dev(self._plan, dev_ptr(d_t), dev_ptr(q_t), float(mu)))
 
     # ---- the same with the solver's vectors in the Fourier domain of the maps (include/surfh_amd.h: surfh_normal_spec_dev) ----
     def spec_supported(self) -> bool:
@@ -275,59 +241,59 @@ class spectroSigRLSCT(DataWeights, TemplateOps, NonnegOps, _pot.Potentials, LinO
         return int(self._L.surfh_spec_size(self._plan))
 
     def to_spec_dev(self, x_t, xt_t):
-        _lib.check(self._L.surfh_to_spec_dev(self._plan, _ptr(x_t), _ptr(xt_t)))
+        _lib.check(self._L.surfh_to_spec_dev(self._plan, dev_ptr(x_t), dev_ptr(xt_t)))
 
     def from_spec_dev(self, xt_t, x_t):
-        _lib.check(self._L.surfh_from_spec_dev(self._plan, _ptr(xt_t), _ptr(x_t)))
+        _lib.check(self._L.surfh_from_spec_dev(self._plan, dev_ptr(xt_t), dev_ptr(x_t)))
 
     def forward_spec_dev(self, dt_t, y_t):
-        _lib.check(self._L.surfh_forward_spec_dev(self._plan, _ptr(dt_t), _ptr(y_t)))
+        _lib.check(self._L.surfh_forward_spec_dev(self._plan, dev_ptr(dt_t), dev_ptr(y_t)))
 
     def adjoint_spec_dev(self, y_t, qt_t, mu: float = 1.0, dt_t=None, mu_reg: float = 0.0):
-        _lib.check(self._L.surfh_adjoint_spec_dev(self._plan, _ptr(y_t), _ptr(qt_t), float(mu), _ptr(dt_t) if dt_t is not None else None,
+        _lib.check(self._L.surfh_adjoint_spec_dev(self._plan, dev_ptr(y_t), dev_ptr(qt_t), float(mu), dev_ptr(dt_t),
                                                   float(mu_reg)))
 
     def normal_spec_dev(self, dt_t, qt_t, mu: float = 1.0, mu_reg: float = 0.0):
-        _lib.check(self._L.surfh_normal_spec_dev(self._plan, _ptr(dt_t), _ptr(qt_t), float(mu), float(mu_reg)))
+        _lib.check(self._L.surfh_normal_spec_dev(self._plan, dev_ptr(dt_t), dev_ptr(qt_t), float(mu), float(mu_reg)))
 
     def prior_spec_add_dev(self, dt_t, qt_t, mu_reg: float):
-        _lib.check(self._L.surfh_prior_spec_add_dev(self._plan, _ptr(dt_t), _ptr(qt_t), float(mu_reg)))
+        _lib.check(self._L.surfh_prior_spec_add_dev(self._plan, dev_ptr(dt_t), dev_ptr(qt_t), float(mu_reg)))
 
     def prior_add_dev(self, d_t, q_t, mu_reg: float):
-        _lib.check(self._L.surfh_prior_add_dev(self._plan, _ptr(d_t), _ptr(q_t), float(mu_reg)))
+        _lib.check(self._L.surfh_prior_add_dev(self._plan, dev_ptr(d_t), dev_ptr(q_t), float(mu_reg)))
 
     def dot_dev(self, a_t, b_t, n: int) -> float:
         out = C.c_double()
-        _lib.check(self._L.surfh_dot_dev(self._plan, _ptr(a_t), _ptr(b_t), int(n), C.byref(out)))
+        _lib.check(self._L.surfh_dot_dev(self._plan, dev_ptr(a_t), dev_ptr(b_t), int(n), C.byref(out)))
         return out.value
 
     def cg_step_dev(self, x_t, r_t, d_t, q_t, n: int, rr: float) -> float:
         out = C.c_double()
-        _lib.check(self._L.surfh_cg_step_dev(self._plan, _ptr(x_t), _ptr(r_t), _ptr(d_t), _ptr(q_t), int(n), float(rr),
+        _lib.check(self._L.surfh_cg_step_dev(self._plan, dev_ptr(x_t), dev_ptr(r_t), dev_ptr(d_t), dev_ptr(q_t), int(n), float(rr),
                                              C.byref(out)))
         return out.value
 
     def cg_iter_dev(self, x_t, r_t, d_t, q_t, n: int, rr: float) -> float:
         """cg_step_dev + cg_dir_dev with one host synchronisation; returns the new r.r."""
         out = C.c_double()
-        _lib.check(self._L.surfh_cg_iter_dev(self._plan, _ptr(x_t), _ptr(r_t), _ptr(d_t), _ptr(q_t), int(n), float(rr), C.byref(out)))
+        _lib.check(self._L.surfh_cg_iter_dev(self._plan, dev_ptr(x_t), dev_ptr(r_t), dev_ptr(d_t), dev_ptr(q_t), int(n), float(rr), C.byref(out)))
         return out.value
 
     def cg_dir_dev(self, d_t, r_t, n: int, beta: float):
-        _lib.check(self._L.surfh_cg_dir_dev(self._plan, _ptr(d_t), _ptr(r_t), int(n), float(beta)))
+        _lib.check(self._L.surfh_cg_dir_dev(self._plan, dev_ptr(d_t), dev_ptr(r_t), int(n), float(beta)))
 
     # device-resident CG scalars: nothing below synchronises with the host (include/surfh_amd.h)
     def cg_begin_dev(self, r_t, n: int):
-        _lib.check(self._L.surfh_cg_begin_dev(self._plan, _ptr(r_t), int(n)))
+        _lib.check(self._L.surfh_cg_begin_dev(self._plan, dev_ptr(r_t), int(n)))
 
     def cg_iter_nosync_dev(self, x_t, r_t, d_t, q_t, n: int):
-        _lib.check(self._L.surfh_cg_iter_nosync_dev(self._plan, _ptr(x_t), _ptr(r_t), _ptr(d_t), _ptr(q_t), int(n)))
+        _lib.check(self._L.surfh_cg_iter_nosync_dev(self._plan, dev_ptr(x_t), dev_ptr(r_t), dev_ptr(d_t), dev_ptr(q_t), int(n)))
 
     def cg_xupdate_nosync_dev(self, x_t, d_t, q_t, n: int):
-        _lib.check(self._L.surfh_cg_xupdate_nosync_dev(self._plan, _ptr(x_t), _ptr(d_t), _ptr(q_t), int(n)))
+        _lib.check(self._L.surfh_cg_xupdate_nosync_dev(self._plan, dev_ptr(x_t), dev_ptr(d_t), dev_ptr(q_t), int(n)))
 
     def cg_refresh_nosync_dev(self, r_t, b_t, q_t, d_t, n: int):
-        _lib.check(self._L.surfh_cg_refresh_nosync_dev(self._plan, _ptr(r_t), _ptr(b_t), _ptr(q_t), _ptr(d_t), int(n)))
+        _lib.check(self._L.surfh_cg_refresh_nosync_dev(self._plan, dev_ptr(r_t), dev_ptr(b_t), dev_ptr(q_t), dev_ptr(d_t), int(n)))
 
     def cg_trace(self, cap: int = 1 << 16) -> np.ndarray:
         """r.r of every iterate since ``cg_begin_dev`` (synchronises the plan's stream)."""
@@ -338,7 +304,7 @@ class spectroSigRLSCT(DataWeights, TemplateOps, NonnegOps, _pot.Potentials, LinO
         return out[:n].copy()
 
     def residual_dev(self, r_t, b_t, q_t, n: int):
-        _lib.check(self._L.surfh_residual_dev(self._plan, _ptr(r_t), _ptr(b_t), _ptr(q_t), int(n)))
+        _lib.check(self._L.surfh_residual_dev(self._plan, dev_ptr(r_t), dev_ptr(b_t), dev_ptr(q_t), int(n)))
 
     def set_prior(self, gradient: str = "separated"):
         """The regulariser of ``cg`` / ``mmmg`` / ``prior_add_dev``: "separated" (NpDiff_r / NpDiff_c, the default) or "joint"
@@ -452,16 +418,16 @@ class spectroSigRLSCT(DataWeights, TemplateOps, NonnegOps, _pot.Potentials, LinO
 
     def randn_dev(self, out_t, n: int, seed: int = 0, stream: int = 0, sample: int = 0):
         """``n`` standard normals of (seed, stream, sample, element index) into a device tensor (include/surfh_amd.h: surfh_randn_dev)."""
-        _lib.check(self._L.surfh_randn_dev(self._plan, _ptr(out_t), int(n), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(stream), int(sample)))
+        _lib.check(self._L.surfh_randn_dev(self._plan, dev_ptr(out_t), int(n), _lib.seed64(seed), int(stream), int(sample)))
 
     def po_data_dev(self, y_t, w_t, eps_t, out_t, n: int, mu: float):
         """out = y + eps / sqrt(mu w) where w > 0 (``w_t=None``: 1), the bits of y elsewhere; device vectors of ``n`` floats."""
-        _lib.check(self._L.surfh_po_data_dev(self._plan, _ptr(y_t), None if w_t is None else _ptr(w_t), _ptr(eps_t), int(n), float(mu),
-                                             _ptr(out_t)))
+        _lib.check(self._L.surfh_po_data_dev(self._plan, dev_ptr(y_t), dev_ptr(w_t), dev_ptr(eps_t), int(n), float(mu),
+                                             dev_ptr(out_t)))
 
     def po_prior_dev(self, er_t, ec_t, out_t, mu_reg: float):
         """out = sqrt(mu_reg) (Dr^T eps_r + Dc^T eps_c) on device maps ``[T, Na, Nb]``."""
-        _lib.check(self._L.surfh_po_prior_dev(self._plan, _ptr(er_t), _ptr(ec_t), float(mu_reg), _ptr(out_t)))
+        _lib.check(self._L.surfh_po_prior_dev(self._plan, dev_ptr(er_t), dev_ptr(ec_t), float(mu_reg), dev_ptr(out_t)))
 
     def mmmg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, delta=None, weights=None,
              data_delta=None, potential="huber", data_potential="huber", imager=None, coupling="none"):
@@ -532,22 +498,22 @@ class spectroSigRLSCT(DataWeights, TemplateOps, NonnegOps, _pot.Potentials, LinO
         Under a coupling of the plan (``set_prior_coupling``) w is the weight of the difference's group, w(m), and ``delta`` the
         threshold on the group magnitude m."""
         out = np.zeros(3, dtype=np.float64)
-        _lib.check(self._L.surfh_huber_curv_dev(self._plan, _ptr(x_t), _ptr(p0_t), _ptr(p1_t), float(delta), _lib.dptr(out)))
+        _lib.check(self._L.surfh_huber_curv_dev(self._plan, dev_ptr(x_t), dev_ptr(p0_t), dev_ptr(p1_t), float(delta), _lib.dptr(out)))
         return out
 
     def robust_data_dev(self, y_t, u_t, w_t, v_t, n: int, data_delta: float):
         """v = sqrt(w) phi'(t), t = sqrt(w) (y - u), on device vectors of ``n`` floats (``w_t=None``: every weight 1; a weight of 0
         takes its sample out whatever y holds); returns (sum phi(t), number of |t| > data_delta) (synchronises)."""
         out = np.zeros(2, dtype=np.float64)
-        _lib.check(self._L.surfh_robust_data_dev(self._plan, _ptr(y_t), _ptr(u_t), None if w_t is None else _ptr(w_t), int(n),
-                                                 float(data_delta), _ptr(v_t), _lib.dptr(out)))
+        _lib.check(self._L.surfh_robust_data_dev(self._plan, dev_ptr(y_t), dev_ptr(u_t), dev_ptr(w_t), int(n),
+                                                 float(data_delta), dev_ptr(v_t), _lib.dptr(out)))
         return float(out[0]), int(round(out[1]))
 
     def robust_curv_dev(self, y_t, u_t, w_t, p0_t, p1_t, n: int, data_delta: float) -> np.ndarray:
         """sum w omega(t) p0^2, p0 p1, p1^2 on device vectors of ``n`` floats: the data block of the robust majorant."""
         out = np.zeros(3, dtype=np.float64)
-        _lib.check(self._L.surfh_robust_curv_dev(self._plan, _ptr(y_t), _ptr(u_t), None if w_t is None else _ptr(w_t), _ptr(p0_t),
-                                                 _ptr(p1_t), int(n), float(data_delta), _lib.dptr(out)))
+        _lib.check(self._L.surfh_robust_curv_dev(self._plan, dev_ptr(y_t), dev_ptr(u_t), dev_ptr(w_t), dev_ptr(p0_t),
+                                                 dev_ptr(p1_t), int(n), float(data_delta), _lib.dptr(out)))
         return out
 
     def huber_prior_dev(self, x_t, g_t, mu_reg: float, delta: float) -> float:
@@ -555,7 +521,7 @@ class spectroSigRLSCT(DataWeights, TemplateOps, NonnegOps, _pot.Potentials, LinO
         coupling of the plan (``set_prior_coupling``): g += mu_reg sum_k D_k^T (w(m) D_k x), returns sum phi(m) over the groups,
         ``delta`` the threshold on the group magnitude m (``potentials.group_magnitude``)."""
         out = C.c_double()
-        _lib.check(self._L.surfh_huber_prior_dev(self._plan, _ptr(x_t), _ptr(g_t), float(mu_reg), float(delta), C.byref(out)))
+        _lib.check(self._L.surfh_huber_prior_dev(self._plan, dev_ptr(x_t), dev_ptr(g_t), float(mu_reg), float(delta), C.byref(out)))
         return out.value
 
     def prior_passes_dev(self, x_t, g_t, p0_t, p1_t, mu_reg: float, delta: float, potential="huber", coupling="none"):
@@ -565,7 +531,7 @@ class spectroSigRLSCT(DataWeights, TemplateOps, NonnegOps, _pot.Potentials, LinO
         T, na, nb = (int(v) for v in x_t.shape)
         out = np.zeros(5, dtype=np.float64)
         _lib.check(self._L.surfh_debug_prior_passes(self._plan, T, na, nb, _pot.kind_code(potential), _pot.coupling_code(coupling),
-                                                    _ptr(x_t), _ptr(g_t), _ptr(p0_t), _ptr(p1_t), float(mu_reg), float(delta),
+                                                    dev_ptr(x_t), dev_ptr(g_t), dev_ptr(p0_t), dev_ptr(p1_t), float(mu_reg), float(delta),
                                                     _lib.dptr(out)))
         return float(out[0]), float(out[1]), out[2:].copy()
 
@@ -616,7 +582,7 @@ class spectroSigRLSCT(DataWeights, TemplateOps, NonnegOps, _pot.Potentials, LinO
         """g += spat_reg sum_k D_k^T phi'(D_k x) + spec_reg D_l^T phi'(D_l x) on device cubes [Lc, Na, Nb]; returns the spatial
         and the spectral sum of phi (synchronises)."""
         out = np.zeros(2, dtype=np.float64)
-        _lib.check(self._L.surfh_huber_vox_prior_dev(self._plan, _ptr(x_t), _ptr(g_t), float(spat_reg), float(spat_delta),
+        _lib.check(self._L.surfh_huber_vox_prior_dev(self._plan, dev_ptr(x_t), dev_ptr(g_t), float(spat_reg), float(spat_delta),
                                                      float(spec_reg), float(spec_delta), _lib.dptr(out)))
         return float(out[0]), float(out[1])
 
@@ -624,7 +590,7 @@ class spectroSigRLSCT(DataWeights, TemplateOps, NonnegOps, _pot.Potentials, LinO
         """[2, 3]: sum w (D p0)^2, (D p0)(D p1), (D p1)^2 under the spatial weights (row 0: rows and columns together) and under
         the spectral weights (row 1), on device cubes: the prior blocks of the majorant before spat_reg / spec_reg."""
         out = np.zeros(6, dtype=np.float64)
-        _lib.check(self._L.surfh_huber_vox_curv_dev(self._plan, _ptr(x_t), _ptr(p0_t), _ptr(p1_t), float(spat_delta),
+        _lib.check(self._L.surfh_huber_vox_curv_dev(self._plan, dev_ptr(x_t), dev_ptr(p0_t), dev_ptr(p1_t), float(spat_delta),
                                                     float(spec_delta), _lib.dptr(out)))
         return out.reshape(2, 3)
 
@@ -659,27 +625,7 @@ class spectroSigRLSCT(DataWeights, TemplateOps, NonnegOps, _pot.Potentials, LinO
             out[self._idx[k]: self._idx[k + 1]] = d.ravel()
         return out
 
-    # ---- instrumentation ---------------------------------------------------------------------
-    def profile_filter(self, prefix=None):
-        """Time only the stages whose name starts with ``prefix`` (None: all)."""
-        _lib.check(self._L.surfh_profile_filter(self._plan, prefix.encode() if prefix else None))
-
-    def profile_enable(self, on=True):
-        _lib.check(self._L.surfh_profile_enable(self._plan, 1 if on else 0))
-
-    def profile_reset(self):
-        _lib.check(self._L.surfh_profile_reset(self._plan))
-
-    def profile(self) -> dict:
-        """{kernel name: (launches, total ms)} measured with HIP events on the plan's stream."""
-        n = self._L.surfh_profile_count(self._plan)
-        out = {}
-        for i in range(n):
-            name, cnt, ms = C.c_char_p(), C.c_int64(), C.c_double()
-            _lib.check(self._L.surfh_profile_get(self._plan, i, C.byref(name), C.byref(cnt), C.byref(ms)))
-            out[name.value.decode()] = (cnt.value, ms.value)
-        return out
-
+    # ---- instrumentation (profile_*: PlanOwner) ------------------------------------------------
     def debug_buffer(self, which: str) -> np.ndarray:
         dims = (C.c_int64 * 4)()
         _lib.check(self._L.surfh_debug_dims(self._plan, which.encode(), dims))

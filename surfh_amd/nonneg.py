@@ -9,7 +9,6 @@ The penalty is fixed for a run; there is no residual balancing.  This module hol
 the argument checks, and the methods of a model with templates that owns a plan."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import NamedTuple
 
 import numpy as np
@@ -67,7 +66,7 @@ def rayleigh_rho(quad, shape, seed=0) -> float:
 
 
 class NonnegOps:
-    """Methods of a model with templates that owns a plan (``forward``, ``ishape``, ``installed_weights``, ``_L``, ``_plan``)."""
+    """Methods of a ``PlanOwner`` with templates (``forward``, ``ishape``, ``installed_weights``)."""
 
     def _weighted_sq(self, av, weights):
         w = self.data_weights if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
@@ -98,22 +97,13 @@ class NonnegOps:
         if getattr(self, "templates", None) is None:
             raise ValueError("cg_nonneg needs templates (the constraint is on the abundance maps)")
         self._refuse_imager("cg_nonneg")
-        y = np.ascontiguousarray(np.asarray(data, dtype=np.float32).reshape(-1))
-        if y.size != self.osize:
-            raise ValueError(f"data have {y.size} elements, expected {self.osize}")
-        x0a = None if x0 is None else np.ascontiguousarray(np.asarray(x0, dtype=np.float32).reshape(-1))
-        if x0a is not None and x0a.size != self.isize:
-            raise ValueError(f"x0 has {x0a.size} elements, expected {self.isize}")
+        y = _lib.f32_vec(data, self.osize, f"data have {np.size(data)} elements, expected {self.osize}")
+        x0a = _lib.f32_vec(x0, self.isize, f"x0 has {np.size(x0)} elements, expected {self.isize}", optional=True)
         if rho is None:
             rho = self.nonneg_rho(mu, mu_reg, weights=weights)
-        out = np.empty(self.isize, dtype=np.float32)
-        trace = np.zeros((int(outer) + 1, 4), dtype=np.float64)
-        nit = C.c_int32()
         with self.installed_weights(weights):
-            _lib.check(self._L.surfh_cg_nonneg(self._plan, _lib.fptr(y), float(mu), float(mu_reg), float(rho),
-                                               None if x0a is None else _lib.fptr(x0a), int(outer), int(inner), float(tol), int(refresh),
-                                               _lib.fptr(out), _lib.dptr(trace), C.byref(nit)), ValueError)
-        return result_from_trace(out.astype(np.float64).reshape(self.ishape), trace, rho, nit.value)
+            x, trace, nit = _lib._solve_nonneg(self, self._L.surfh_cg_nonneg, y, (mu, mu_reg, rho), x0a, outer, inner, tol, refresh)
+        return result_from_trace(x, trace, rho, nit)
 
     def nonneg_rho_templates(self, maps, mu=1.0, mu_spec=0.0, seed=0, weights=None) -> float:
         """``nonneg_rho`` for the operator of ``cg_templates`` at ``maps``: ``mu A_x^T W A_x + mu_spec D_l^T D_l``."""
@@ -126,9 +116,7 @@ class NonnegOps:
         """The projection / dual update of one outer iteration on device vectors of ``n`` floats, in place in ``z_t`` and ``u_t``
         (include/surfh_amd.h: surfh_nn_project_dev); returns ``|x - z'|^2, |z' - z|^2, #{z' == 0}, r.r`` (synchronises).  The
         arguments are device tensors or raw device addresses."""
-        def ptr(t):
-            return None if t is None else (C.c_void_p(int(t)) if isinstance(t, int) else C.c_void_p(t.data_ptr()))
-
+        ptr = _lib.dev_ptr
         sums = np.zeros(4, dtype=np.float64)
         _lib.check(self._L.surfh_nn_project_dev(self._plan, ptr(x_t), ptr(z_t), ptr(u_t), ptr(r_t), ptr(dv_t), int(n), float(rho),
                                                 _lib.dptr(sums)), ValueError)

@@ -110,37 +110,21 @@ def sample_posterior(model, data, mu=1.0, mu_reg=0.0, n_samples=16, seed=0, x0=N
     check_args(model, mu, mu_reg, n_samples)
     K, T = int(n_samples), model.ishape[0]
     npix = model.isize // T
-    y = np.ascontiguousarray(np.asarray(data, dtype=np.float32).reshape(-1))
-    if y.size != model.osize:
-        raise ValueError("data size mismatch")
-    x0a = None if x0 is None else np.ascontiguousarray(np.asarray(x0, dtype=np.float32).reshape(-1))
-    if x0a is not None and x0a.size != model.isize:
-        raise ValueError("x0 size mismatch")
+    y = _lib.f32_vec(data, model.osize, "data size mismatch")
+    x0a = _lib.f32_vec(x0, model.isize, "x0 size mismatch", optional=True)
     ey, er, ec = _noise(perturbations, K, model.osize, model.isize, float(mu_reg))
     x_map = np.empty(model.isize, dtype=np.float32)
     mean = np.empty(model.isize, dtype=np.float64)
     cov = np.empty((T * (T + 1) // 2, npix), dtype=np.float64)
     gn = np.zeros(int(max_iter) + 1, dtype=np.float64)
-    nit, worst, err = C.c_int32(), C.c_double(), []
-
-    def tramp(_user, k, nk, rptr, xptr):
-        try:
-            rr = np.ctypeslib.as_array(rptr, shape=(nk + 1,)).copy()
-            xk = np.ctypeslib.as_array(xptr, shape=(model.isize,)).astype(np.float64).reshape(model.ishape)
-            return 1 if callback(k, rr, xk) else 0
-        except BaseException as e:          # never unwind through the C frame
-            err.append(e)
-            return 1
-
-    cb = _lib.SAMPLE_CALLBACK(tramp) if callback is not None else _lib.SAMPLE_CALLBACK()
-    opt = lambda a: None if a is None else _lib.fptr(a)
+    nit, worst = C.c_int32(), C.c_double()
+    cb, finish = _lib.trampoline(_lib.SAMPLE_CALLBACK, callback, _lib.iterate_args(model.isize, model.ishape))
+    opt = _lib.opt_fptr
     with model.installed_weights(weights):
         rc = model._L.surfh_cg_sample(model._plan, _lib.fptr(y), float(mu), float(mu_reg), opt(x0a), int(max_iter), float(tol),
-                                      int(refresh), K, C.c_uint64(int(seed) & (2 ** 64 - 1)), opt(ey), opt(er), opt(ec), _lib.fptr(x_map),
+                                      int(refresh), K, _lib.seed64(seed), opt(ey), opt(er), opt(ec), _lib.fptr(x_map),
                                       _lib.dptr(mean), _lib.dptr(cov), _lib.dptr(gn), C.byref(nit), C.byref(worst), cb, None)
-    if err:
-        raise err[0]
-    _lib.check(rc)
+    finish(rc)
     cov = unpack_cov(cov.reshape((-1,) + tuple(model.ishape[1:])), T)
     std = np.sqrt(np.maximum(cov[np.arange(T), np.arange(T)], 0.0))
     return PosteriorResult(x_map=x_map.astype(np.float64).reshape(model.ishape), mean=mean.reshape(model.ishape), cov=cov, std=std,
@@ -150,17 +134,15 @@ def sample_posterior(model, data, mu=1.0, mu_reg=0.0, n_samples=16, seed=0, x0=N
 def po_rhs(model, data, mu, mu_reg, seed=0, sample=0, perturbation=None):
     """``surfh_po_rhs``: the perturbed right-hand side ``b~ = mu A^T W y~ + eta`` ``[T, Na, Nb]`` of draw ``sample`` under
     ``seed`` and the model's data weights; ``perturbation=(eps_y, eps_r, eps_c)`` replaces the generator."""
-    y = np.ascontiguousarray(np.asarray(data, dtype=np.float32).reshape(-1))
-    if y.size != model.osize:
-        raise ValueError("data size mismatch")
+    y = _lib.f32_vec(data, model.osize, "data size mismatch")
     eps = None
     if perturbation is not None:
         eps = np.ascontiguousarray(np.concatenate([np.asarray(e, dtype=np.float32).reshape(-1) for e in perturbation]))
         if eps.size != model.osize + 2 * model.isize:
             raise ValueError("perturbation must be (eps_y [osize], eps_r [isize], eps_c [isize])")
     out = np.empty(model.isize, dtype=np.float32)
-    _lib.check(model._L.surfh_po_rhs(model._plan, _lib.fptr(y), float(mu), float(mu_reg), C.c_uint64(int(seed) & (2 ** 64 - 1)),
-                                     int(sample), None if eps is None else _lib.fptr(eps), _lib.fptr(out)))
+    _lib.check(model._L.surfh_po_rhs(model._plan, _lib.fptr(y), float(mu), float(mu_reg), _lib.seed64(seed), int(sample),
+                                     _lib.opt_fptr(eps), _lib.fptr(out)))
     return out.astype(np.float64).reshape(model.ishape)
 
 

@@ -200,7 +200,7 @@ def get_slot(model, slot) -> int:
 
 
 class Potentials:
-    """The plan-state methods of a model that owns a plan (``self._L``, ``self._plan``)."""
+    """The plan-state methods of a ``PlanOwner``."""
 
     def set_potential(self, slot, potential="huber"):
         """The potential of one of the plan's slots from now on: ``slot`` "spatial" (the priors of the maps, of the planes and of

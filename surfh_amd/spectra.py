@@ -10,8 +10,6 @@ What the data can say about a spectrum is limited by the detector: a feature nar
 the planes no channel reads, from their neighbours."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
@@ -29,7 +27,7 @@ def check_templates(S, shape) -> np.ndarray:
 
 
 class TemplateOps:
-    """Methods of a model with templates that owns a plan (``self._L``, ``self._plan``, ``self.templates``, ``ishape``, ``osize``)."""
+    """Methods of a ``PlanOwner`` with templates (``self.templates``, ``ishape``, ``osize``)."""
 
     def _need_templates(self):
         if getattr(self, "templates", None) is None:
@@ -49,9 +47,7 @@ class TemplateOps:
         """``A_x S``: the forward model on ``maps`` with ``S`` in the templates' place; the model's templates are untouched."""
         self._need_templates()
         a = check_templates(S, self.templates.shape)
-        x = np.ascontiguousarray(np.asarray(maps, dtype=np.float32).reshape(-1))
-        if x.size != self.isize:
-            raise ValueError(f"maps have {x.size} elements, expected {self.isize}")
+        x = _lib.f32_vec(maps, self.isize, f"maps have {np.size(maps)} elements, expected {self.isize}")
         y = np.empty(self.osize, dtype=np.float32)
         _lib.check(self._L.surfh_forward_templates(self._plan, _lib.fptr(x), _lib.dptr(a), _lib.fptr(y)))
         return y.astype(np.float64).reshape(self.oshape)
@@ -59,13 +55,15 @@ class TemplateOps:
     def adjoint_templates(self, u, maps):
         """``A_x^T u`` ``[T, Lc]``: the transpose of ``forward_templates``; exactly 0 on the planes no channel reads."""
         self._need_templates()
-        x = np.ascontiguousarray(np.asarray(maps, dtype=np.float32).reshape(-1))
-        v = np.ascontiguousarray(np.asarray(u, dtype=np.float32).reshape(-1))
-        if x.size != self.isize or v.size != self.osize:
-            raise ValueError(f"maps / data have {x.size} / {v.size} elements, expected {self.isize} / {self.osize}")
+        message = f"maps / data have {np.size(maps)} / {np.size(u)} elements, expected {self.isize} / {self.osize}"
+        x, v = _lib.f32_vec(maps, self.isize, message), _lib.f32_vec(u, self.osize, message)
         g = np.empty(self.templates.size, dtype=np.float32)
         _lib.check(self._L.surfh_adjoint_templates(self._plan, _lib.fptr(x), _lib.fptr(v), _lib.fptr(g)))
         return g.astype(np.float64).reshape(self.templates.shape)
+
+    def _data_and_maps(self, data, maps):
+        message = "data or maps size mismatch"
+        return _lib.f32_vec(data, self.osize, message), _lib.f32_vec(maps, self.isize, message)
 
     def cg_templates(self, data, maps, mu=1.0, mu_spec=0.0, s0=None, max_iter=10, tol=1e-12, refresh=50, callback=None, weights=None):
         """Linear CG on ``(mu A_x^T W A_x + mu_spec D_l^T D_l) S = mu A_x^T W y`` from ``s0`` (None: the model's templates): the
@@ -77,33 +75,11 @@ class TemplateOps:
             raise ValueError("cg_templates does not carry the imager data term and the attached imager was built from the model's "
                              "templates: detach it (set_imager(None)) first")
         shape = self.templates.shape
-        y = np.ascontiguousarray(np.asarray(data, dtype=np.float32).reshape(-1))
-        x = np.ascontiguousarray(np.asarray(maps, dtype=np.float32).reshape(-1))
-        if y.size != self.osize or x.size != self.isize:
-            raise ValueError("data or maps size mismatch")
+        y, x = self._data_and_maps(data, maps)
         s0a = None if s0 is None else check_templates(s0, shape).astype(np.float32).reshape(-1)
-        out = np.empty(self.templates.size, dtype=np.float32)
-        gn = np.zeros(max_iter + 1, dtype=np.float64)
-        nit = C.c_int32()
-        err = []
-
-        def tramp(_user, it, gptr, xptr):
-            try:
-                g = np.ctypeslib.as_array(gptr, shape=(it + 1,)).copy()
-                si = np.ctypeslib.as_array(xptr, shape=(out.size,)).astype(np.float64).reshape(shape)
-                return 1 if callback(it, g, si) else 0
-            except BaseException as e:          # never unwind through the C frame
-                err.append(e)
-                return 1
-
-        cb = _lib.CG_CALLBACK(tramp) if callback is not None else _lib.CG_CALLBACK()
         with self.installed_weights(weights):
-            _lib.check(self._L.surfh_cg_templates_cb(self._plan, _lib.fptr(y), _lib.fptr(x), float(mu), float(mu_spec),
-                                                     _lib.fptr(s0a) if s0a is not None else None, int(max_iter), float(tol),
-                                                     int(refresh), _lib.fptr(out), _lib.dptr(gn), C.byref(nit), cb, None), ValueError)
-        if err:
-            raise err[0]
-        return out.astype(np.float64).reshape(shape), gn[: nit.value + 1].copy(), nit.value
+            return _lib._solve(self, self._L.surfh_cg_templates_cb, y, (_lib.fptr(x), mu, mu_spec), s0a, max_iter, tol, refresh, (),
+                               callback, size=self.templates.size, shape=shape, exc=ValueError)
 
     def cg_templates_nonneg(self, data, maps, mu=1.0, mu_spec=0.0, rho=None, s0=None, outer=30, inner=10, tol=0.0, refresh=10,
                             weights=None):
@@ -118,30 +94,20 @@ class TemplateOps:
             raise ValueError("cg_templates_nonneg does not carry the imager data term and the attached imager was built from the "
                              "model's templates: detach it (set_imager(None)) first")
         shape = self.templates.shape
-        y = np.ascontiguousarray(np.asarray(data, dtype=np.float32).reshape(-1))
-        x = np.ascontiguousarray(np.asarray(maps, dtype=np.float32).reshape(-1))
-        if y.size != self.osize or x.size != self.isize:
-            raise ValueError("data or maps size mismatch")
+        y, x = self._data_and_maps(data, maps)
         s0a = None if s0 is None else check_templates(s0, shape).astype(np.float32).reshape(-1)
         if rho is None:
             rho = self.nonneg_rho_templates(maps, mu, mu_spec, weights=weights)
-        out = np.empty(self.templates.size, dtype=np.float32)
-        trace = np.zeros((int(outer) + 1, 4), dtype=np.float64)
-        nit = C.c_int32()
         with self.installed_weights(weights):
-            _lib.check(self._L.surfh_cg_templates_nonneg(self._plan, _lib.fptr(y), _lib.fptr(x), float(mu), float(mu_spec), float(rho),
-                                                         _lib.fptr(s0a) if s0a is not None else None, int(outer), int(inner), float(tol),
-                                                         int(refresh), _lib.fptr(out), _lib.dptr(trace), C.byref(nit)), ValueError)
-        return nonneg.result_from_trace(out.astype(np.float64).reshape(shape), trace, rho, nit.value)
+            S, trace, nit = _lib._solve_nonneg(self, self._L.surfh_cg_templates_nonneg, y, (_lib.fptr(x), mu, mu_spec, rho), s0a, outer,
+                                               inner, tol, refresh, size=self.templates.size, shape=shape)
+        return nonneg.result_from_trace(S, trace, rho, nit)
 
     def joint_criterion(self, data, maps, mu=1.0, mu_reg=0.0, mu_spec=0.0, weights=None):
         """``(J, data term, spatial prior, spectral prior)`` at ``maps`` and the model's templates, summed on the device in float64:
         ``J = (mu data + mu_reg spatial + mu_spec spectral) / 2`` (the module's criterion; ``weights`` as in ``cg``)."""
         self._need_templates()
-        y = np.ascontiguousarray(np.asarray(data, dtype=np.float32).reshape(-1))
-        x = np.ascontiguousarray(np.asarray(maps, dtype=np.float32).reshape(-1))
-        if y.size != self.osize or x.size != self.isize:
-            raise ValueError("data or maps size mismatch")
+        y, x = self._data_and_maps(data, maps)
         out = np.zeros(4, dtype=np.float64)
         with self.installed_weights(weights):
             _lib.check(self._L.surfh_joint_criterion(self._plan, _lib.fptr(y), _lib.fptr(x), float(mu), float(mu_reg), float(mu_spec),

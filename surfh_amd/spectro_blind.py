@@ -15,11 +15,9 @@ image at the image grid (``gridding_t``, :303-323) and is not G_p^T.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _lib, instru
+from . import instru
 from .blurred2d import Blurred2D
 from .geometry import find_indices
 from .spectro_blind_rectangle import QuadCriterion_MRS_2D  # noqa: F401  (criterion_2D.QuadCriterion_MRS_2D, duck-typed)
@@ -85,20 +83,11 @@ class MRSBlurred(Blurred2D):
     # ---- operator -------------------------------------------------------------------------------------
     def adjoint_ref(self, data):
         """The reference's ``MRSBlurred.adjoint`` (interpolating back-projection, not the transpose of ``forward``)."""
-        return self._call(self._L.surfh_adjoint_ref, data, self.osize, self.ishape)
+        return self._host(self._L.surfh_adjoint_ref, data, self.osize, self.ishape)
 
     def fwadj(self, x):
         """A^T A x (exact transpose) in one call."""
-        return self._call(self._L.surfh_fwadj, x, self.isize, self.ishape)
-
-    def adjoint_dev(self, y_t, x_t):
-        _lib.check(self._L.surfh_adjoint_dev(self._plan, C.c_void_p(y_t.data_ptr()), C.c_void_p(x_t.data_ptr())))
-
-    def adjoint_ref_dev(self, y_t, x_t):
-        _lib.check(self._L.surfh_adjoint_ref_dev(self._plan, C.c_void_p(y_t.data_ptr()), C.c_void_p(x_t.data_ptr())))
-
-    def fwadj_dev(self, x_t, out_t):
-        _lib.check(self._L.surfh_fwadj_dev(self._plan, C.c_void_p(x_t.data_ptr()), C.c_void_p(out_t.data_ptr())))
+        return self._host(self._L.surfh_fwadj, x, self.isize, self.ishape)
 
     def cg(self, data, mu=1.0, mu_reg=0.0, x0=None, max_iter=10, tol=1e-12, refresh=50, callback=None):
         """Device-resident linear CG on  mu |y - A x|^2 + mu_reg (|Dr x|^2 + |Dc x|^2), one problem per plane, as

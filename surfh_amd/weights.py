@@ -51,7 +51,7 @@ def weighted_sq_residual(y, ax, weights=None):
 
 
 class DataWeights:
-    """The plan-state methods of a model that owns a plan (``self._L``, ``self._plan``, ``self.osize``)."""
+    """The plan-state methods of a ``PlanOwner`` (``self.osize``)."""
     _data_weights = None
 
     def set_data_weights(self, weights=None):

@@ -49,6 +49,34 @@ def test_cg_callback_trace(setup):
         m.cg(y, mu=1.0, mu_reg=5e3, max_iter=2, callback=lambda it, g, xx: 1 / 0)
 
 
+@pytest.mark.parametrize("solver", ["cg", "mmmg", "mmmg_delta", "cg_templates", "sample_posterior"])
+def test_callback_exception_propagates_and_leaves_the_plan_usable(setup, solver):
+    """A callback that raises at its second call: the library's loop stops there, the exception comes out of the solver as it
+    is (not wrapped, whatever the library returned), and the plan, its templates included, solves as before."""
+    cfg, om, m, y = setup
+    kw = dict(mu=1.0, mu_reg=5e3, max_iter=3)
+    x_ref, gn_ref, nit_ref = m.cg(y, **kw)
+    calls = []
+
+    def cb(k, trace, x):
+        calls.append(k)
+        if len(calls) == 2:
+            raise KeyError("second call")
+        return False
+
+    run = {"cg": lambda: m.cg(y, callback=cb, **kw),
+           "mmmg": lambda: m.mmmg(y, callback=cb, **kw),
+           "mmmg_delta": lambda: m.mmmg(y, callback=cb, delta=0.05, **kw),
+           "cg_templates": lambda: m.cg_templates(y, cfg["maps"], mu=1.0, mu_spec=1.0, max_iter=3, callback=cb),
+           "sample_posterior": lambda: m.sample_posterior(y, n_samples=2, seed=3, callback=cb, **kw)}[solver]
+    with pytest.raises(KeyError, match="second call"):
+        run()
+    assert len(calls) == 2                                                               # nothing ran past the exception
+    x, gn, nit = m.cg(y, **kw)
+    assert nit == nit_ref == 3 and np.array_equal(x, x_ref) and np.array_equal(gn, gn_ref)
+    assert np.array_equal(m.templates, cfg["templates"])
+
+
 def test_mmmg_matches_oracle_and_cg(setup, capsys):
     """The reference's other solver choice (fusion_CT.py:194-198 -> qmm.mmmg) against the oracle's restatement, and against
     CG: on this quadratic criterion both produce the same iterates."""
