@@ -690,6 +690,20 @@ int surfh_debug_planes_passes(surfh_plan *plan, int32_t L, int32_t na, int32_t n
  * 2^31 floats or more, LP % 64 != 0, an unknown name and a missing pointer fail with a message and launch nothing. */
 int surfh_debug_planes_cg(surfh_plan *plan, const char *which, const int64_t *ext, float *v0, float *v1, float *v2, float *v3,
                           float *v4, float *v5, double mu_reg, int32_t update_r, const double *sc_in, double *sc_out);
+/* diagnostic: ONE application of the normal operator of the device-resident plane-wise CG (surfh_cg_planes_begin_dev / _step_dev
+ * on wavelength-innermost vectors), q = mu A^T W A v + mu_reg (Dr^T Dr + Dc^T Dc) v, through the function the loop calls, on the
+ * loop's own buffers: v_dev [Lc][Na][Nb] is transposed into the cube's layout [NBP][NAP][LP] as the begin call transposes x0, the
+ * operator runs under the given mu / mu_reg -- on the plan's route: with mu and the prior folded into the adjoint's OTF product
+ * (interleaved spectra) or into the loader of the inverse transform (the product loader), or as the unfolded operator followed by
+ * the prior kernel (dense plans, mu_reg = 0) -- with the plan's data weights, and q_dev [Lc][Na][Nb] is transposed back as the
+ * step call brings the iterate back.  dq_host [Lc]: v_l . q_l per plane, the sum the operator's last kernel leaves for the step.
+ * q_raw_dev (or NULL): the padded vector itself, [NBP][NAP][LP] floats (surfh_debug_dims "blurred": NBP, NAP, LP).  Synchronises.
+ * The call leaves the plan's mu / mu_reg as they were, but it overwrites the loop's vectors: a loop begun with
+ * surfh_cg_planes_begin_dev has to be begun again after it (surfh_cg_planes_step_dev fails until then).
+ * A plan with templates, a plan that does not run the wavelength-innermost loop (SURFH_PLANES_NATIVE=0), a null plan, v_dev, q_dev
+ * or dq_host and a negative or non-finite mu or mu_reg fail with a message naming the argument and launch nothing. */
+int surfh_debug_planes_normal(surfh_plan *plan, const float *v_dev, float *q_dev, double mu, double mu_reg, double *dq_host,
+                              float *q_raw_dev);
 /* host only (no GPU, no plan): the route plan creation would decide -- which transform kernels run and which fusions ride on
  * them -- from the function plan creation calls.  lp: the plan's plane pitch (owned planes rounded up to 128).  switches: bit i
  * set = switch i is on, in the order SURFH_DFT_H2, SURFH_DFT_CT, SURFH_DFT_DENSE, SURFH_NO_FUSED_MIX, SURFH_ADJ_FUSED,

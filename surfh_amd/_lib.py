@@ -64,7 +64,7 @@ EXPORTS = [
     "surfh_debug_dims", "surfh_gemm_selftest", "surfh_gemm_selftest_ksteps", "surfh_gemm_selftest_ms", "surfh_klist_classify", "surfh_launch_geometry", "surfh_route_decide", "surfh_mm_step2",
     "surfh_debug_alloc_count", "surfh_debug_alloc_fail", "surfh_debug_prior_passes",
     "surfh_mmmg_huber_planes_ex", "surfh_huber_planes_prior_dev_ex", "surfh_huber_planes_curv_dev_ex", "surfh_debug_planes_passes",
-    "surfh_debug_planes_cg",
+    "surfh_debug_planes_cg", "surfh_debug_planes_normal",
     "surfh_shepard", "surfh_shepard_last_error", "surfh_spectral_median", "surfh_nmf_cd", "surfh_templates_last_error",
     "surfh_set_templates", "surfh_get_templates", "surfh_forward_templates", "surfh_adjoint_templates", "surfh_forward_templates_dev",
     "surfh_adjoint_templates_dev", "surfh_cg_templates", "surfh_cg_templates_cb", "surfh_joint_criterion",
@@ -135,6 +135,7 @@ def load():
     L.surfh_huber_planes_curv_dev_ex.argtypes = [vp, vp, vp, vp, c_double_p, C.c_int32, c_double_p]
     L.surfh_debug_planes_passes.argtypes = [vp] + [C.c_int32] * 5 + [vp] * 4 + [c_double_p, c_double_p, c_double_p]
     L.surfh_debug_planes_cg.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)] + [vp] * 6 + [C.c_double, C.c_int32, c_double_p, c_double_p]
+    L.surfh_debug_planes_normal.argtypes = [vp, vp, vp, C.c_double, C.c_double, c_double_p, vp]
     L.surfh_mmmg_planes.argtypes = L.surfh_cg_planes.argtypes
     L.surfh_cg_planes_begin_dev.argtypes = [vp, vp, C.c_double, C.c_double, vp]
     L.surfh_cg_planes_step_dev.argtypes = [vp, C.c_int32, C.c_int32]

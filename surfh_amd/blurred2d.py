@@ -396,3 +396,15 @@ class Blurred2D(DataWeights, _pot.Potentials, PlanOwner, LinOp):
                                                  int(update_r), None if sc_in is None else _lib.dptr(sc_in),
                                                  None if sc_out is None else _lib.dptr(sc_out)))
         return sc_out
+
+    def planes_normal_dev(self, v_t, q_t, mu=1.0, mu_reg=0.0, raw_t=None) -> np.ndarray:
+        """Diagnostic: one application of the normal operator of the device-resident loop (``cg_begin_dev`` / ``cg_step_dev`` on
+        wavelength-innermost vectors) on device tensors ``[n_planes, Na, Nb]`` (float32, contiguous):
+        q_t = mu A^T W A v_t + mu_reg (Dr^T Dr + Dc^T Dc) v_t on the plan's route, with the model's data weights.  Returns
+        ``v_l . q_l`` per plane ``[n_planes]``, the sums the operator leaves for the step.  ``raw_t``: a device tensor of the padded
+        vector's size (``surfh_debug_dims(plan, "blurred")``) that receives it as the loop holds it.  Synchronises; a loop begun with
+        ``cg_begin_dev`` has to be begun again afterwards.  (include/surfh_amd.h: surfh_debug_planes_normal)"""
+        dq = np.zeros(self.n_planes, dtype=np.float64)
+        _lib.check(self._L.surfh_debug_planes_normal(self._plan, dev_ptr(v_t), dev_ptr(q_t), float(mu), float(mu_reg), _lib.dptr(dq),
+                                                     None if raw_t is None else dev_ptr(raw_t)))
+        return dq

@@ -337,8 +337,11 @@ int pn_normal(surfh_plan *p, const float *v, float *q, double *dq) {
     // with interleaved spectra and a prior weight the OTF product of the adjoint applies mu and adds the prior (adjoint_tail): the
     // two halves are called directly so that no scaling pass follows
     // (plans whose inverse transform forms the OTF product in its loader -- Route::prod -- take mu and the prior on that pass)
-    const bool prod = p->route.prod && p->pl_mu != 0.0;
-    const bool fold = prod || (p->route.interleaved() && p->pl_mu_reg != 0.0);
+    // The fold is decided on what the folding kernel sees, in fp32: the OTF product applies mu only beside a prior weight that is
+    // non-zero, and the loader scales by mu and carries the prior as (mu_reg / mu) times its third operand, which needs a non-zero
+    // mu and a finite ratio.  Every other call takes the unfolded operator, the scaling pass and the prior kernel.
+    const bool prod = p->route.prod && (float)p->pl_mu != 0.f && p->pl_mu_reg / p->pl_mu <= 3.4028234e38;
+    const bool fold = prod || (!p->route.prod && p->route.interleaved() && (float)p->pl_mu_reg != 0.f);
     if (fold) {
         OpCall c;
         c.head = OpCall::H_CUBE; c.tail = OpCall::T_CUBE; c.fold = true; c.mu = p->pl_mu; c.prior_mu = p->pl_mu_reg;
@@ -403,7 +406,11 @@ int cg_planes_ready(surfh_plan *p, const char *who, bool native) {
     const size_t nc = (size_t)p->NBP * p->NAP * p->LP;
     return ensure_set_with(
         [&](float *v0, float *v1, float *v2, float *v3, float *v4, double *, double *) {
-            for (float *v : {v0, v1, v2, v3, v4})       // the padding (rows >= Nb, columns >= Na, planes >= Lc) stays zero
+            // The padding (rows >= Nb, columns >= Na, planes >= Lc) starts at zero.  It stays zero where beta runs on dft_h2 or dense;
+            // where beta runs on dft_ct the real passes transform the planes (l, l ^ 1) as one complex column, and the separation
+            // leaves a plane some 1e-7 of its partner: the padding plane beside an odd Lc, and q of an all-zero plane, hold such
+            // values (finite; the sums of the padding wavelengths are never read)
+            for (float *v : {v0, v1, v2, v3, v4})
                 if (dev_raw_clear(v, nc * sizeof(float), p->stream, true)) return 1;
             return 0;
         },
@@ -1841,6 +1848,38 @@ int surfh_debug_planes_cg(surfh_plan *p, const char *which, const int64_t *ext, 
     const hipError_t e1 = hipStreamSynchronize(s);
     HIP_OK(e0);
     HIP_OK(e1);
+    return 0;
+}
+
+// The normal operator of the device-resident plane-wise CG on its own: v goes into the cube's layout as pn_setup takes x0 there,
+// pn_normal runs on the loop's own buffers under the given mu / mu_reg, q comes back as pn_to_caller brings the iterate.  Every
+// argument is checked before the buffers are asked for; the plan's mu / mu_reg are put back, and the loop a begin call left is over.
+int surfh_debug_planes_normal(surfh_plan *p, const float *v_dev, float *q_dev, double mu, double mu_reg, double *dq_host, float *q_raw_dev) {
+    const char *who = "surfh_debug_planes_normal";
+    if (!p) return fail("%s: plan is null", who);
+    if (!v_dev) return fail("%s: v_dev is null", who);
+    if (!q_dev) return fail("%s: q_dev is null", who);
+    if (!dq_host) return fail("%s: dq_host is null", who);
+    if (!std::isfinite(mu) || mu < 0.0) return fail("%s: mu %g", who, mu);
+    if (!std::isfinite(mu_reg) || mu_reg < 0.0) return fail("%s: mu_reg %g", who, mu_reg);
+    if (p->T != 0) return fail("%s: the plan has %d templates, the plane-wise normal operator belongs to the no-template model", who, (int)p->T);
+    if (!pn_capable(p)) return fail("%s: the plan does not run the wavelength-innermost loop (SURFH_PLANES_NATIVE=0, a Huber prior or split planes)", who);
+    if (cg_planes_ready(p, who, true)) return 1;
+    p->pn_active = false;                         // the loop's vectors are overwritten: it has to be begun again
+    p->pl_x = nullptr;
+    hipStream_t s = p->stream;
+    float *const v = p->pn_v[0], *const q = p->pn_v[3];
+    double *const dq = p->pn_sc + p->LP;
+    LAUNCH_OK(launch_cube_to_lam_inner(s, v_dev, v, 0, p->Lc, p->Na, p->Nb, p->NAP, p->LP));
+    const double mu0 = p->pl_mu, mu_reg0 = p->pl_mu_reg;
+    p->pl_mu = mu; p->pl_mu_reg = mu_reg;
+    const int rc = pn_normal(p, v, q, dq);
+    p->pl_mu = mu0; p->pl_mu_reg = mu_reg0;
+    if (rc) return 1;
+    LAUNCH_OK(launch_cube_from_lam_inner(s, q, q_dev, 0, p->Lc, p->Na, p->Nb, p->NAP, p->LP));
+    HIP_OK(hipMemcpyAsync(dq_host, dq, (size_t)p->Lc * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (q_raw_dev) HIP_OK(hipMemcpyAsync(q_raw_dev, q, (size_t)p->NBP * p->NAP * p->LP * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_OK(hipStreamSynchronize(s));
     return 0;
 }
 
