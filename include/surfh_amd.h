@@ -269,6 +269,11 @@ int surfh_po_prior_dev(surfh_plan *plan, const float *eps_r_dev, const float *ep
  * row-major order (NULL: not wanted; needs K >= 2).  1 <= T <= 8. */
 int surfh_po_moments(int32_t T, int64_t npix, const float *xhat, const float *samples, int32_t K, double *mean, double *cov,
                      int32_t device);
+/* The plane moments of surfh_cg_planes_sample on their own, host buffers: K samples [K][L][npix] about xhat [L][npix]; the planes are
+ * independent, so the second moment is the variance alone.  S1 += e, S2 += e e in float64 per element in a fixed order, then in
+ * place mean [L][npix] = xhat + S1 / K and var [L][npix] = (S2 - S1^2 / K) / (K - 1), clamped at 0 (NULL: not wanted; needs K >= 2). */
+int surfh_po_planes_moments(int32_t L, int64_t npix, const float *xhat, const float *samples, int32_t K, double *mean, double *var,
+                            int32_t device);
 /* btilde [isize] = the perturbed right-hand side b~ of draw `sample` under `seed`, in the maps' layout.  eps NULL: the generator;
  * else one explicit draw, eps_y [osize] followed by eps_r and eps_c [isize] each (`seed`, `sample` unused).  For statistical
  * tests of the sampler and for callers that run their own loop.  Refuses what surfh_cg_sample refuses. */
@@ -288,6 +293,32 @@ int surfh_cg_sample(surfh_plan *plan, const float *y, double mu, double mu_reg, 
                     int32_t refresh, int32_t n_samples, uint64_t seed, const float *eps_y, const float *eps_r, const float *eps_c,
                     float *x_map, double *mean, double *cov, double *grad_norm, int32_t *nit, double *rr_worst,
                     surfh_sample_callback callback, void *user);
+/* ---- ... of the plane-wise 2-D deconvolution: per-pixel uncertainty of the planes surfh_cg_planes returns ----
+ * The same perturbation-optimisation on the Lc independent problems Q_l x_l = b_l of surfh_cg_planes (plans without templates; the
+ * data weights are the plan's).  surfh_cg_planes itself (same arguments, same bits in x_map, grad_norm [nit + 1][Lc] and nit), then
+ * n_samples solves of Q_l e_l = b~_l - b_l from zero with the same max_iter, tol and refresh: the perturbation eps_y / sqrt(mu w) alone
+ * is the data of the solve and eta its extra right-hand side.  mean and var [Lc][Na][Nb] float64 (either may be NULL): x_map + the mean
+ * of e, and the unbiased variance of e per pixel -- the planes are independent, so there is no covariance.
+ * Generator (eps_* NULL): eps_y is stream 0 over the flat index of y, eps_r / eps_c are streams 1 / 2 over the flat index of
+ * [Lc][Na][Nb], counter = index / 4, sample k = counter word `sample` -- the streams surfh_randn_dev writes -- but generated in
+ * registers by the kernels that consume them: no noise vector is stored, and beside the solver's vectors the call holds eta and x_map
+ * [isize] floats and two float64 sums per element, which the finish turns into mean and var in place.  Explicit draws (eps_y
+ * [n_samples][osize], eps_r / eps_c [n_samples][isize]; eps_r / eps_c not read when mu_reg = 0, one of them NULL: generated) go
+ * through the staged kernels of surfh_cg_sample on buffers allocated on that first use.
+ * rr_first, rr_last [Lc] (may be NULL): per plane the largest first and the largest final r.r over the sample solves; a plane whose
+ * rr_first is exactly 0 drew no perturbation at all (no data weight and mu_reg = 0: its posterior is improper, its var of 0 means
+ * "unknown", not "certain").  The callback (may be NULL) receives every finished sample: its index, the iterations of its solve, its
+ * r.r trace [nit + 1][Lc] and x~ = x_map + e [Lc][Na][Nb] on the host; without one no sample is copied to the host.  The plan is left
+ * as surfh_cg_planes leaves it.  Refuses, before any work: plans with templates, an active imager term, the joint prior, mu not
+ * finite and > 0, mu_reg not finite and >= 0, n_samples < 1 (< 2 when var is requested), max_iter < 0, and what surfh_cg_planes refuses. */
+int surfh_cg_planes_sample(surfh_plan *plan, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
+                           int32_t refresh, int32_t n_samples, uint64_t seed, const float *eps_y, const float *eps_r, const float *eps_c,
+                           float *x_map, double *mean, double *var, double *grad_norm, int32_t *nit, double *rr_first, double *rr_last,
+                           surfh_sample_callback callback, void *user);
+/* btilde [Lc][Na][Nb] = b~ = mu A^T W y~ + eta of draw `sample` under `seed`, the twin of surfh_po_rhs for the planes: eps NULL: the
+ * generator; else one explicit draw, eps_y [osize] followed by eps_r and eps_c [isize] each.  Refuses what surfh_cg_planes_sample refuses. */
+int surfh_po_planes_rhs(surfh_plan *plan, const float *y, double mu, double mu_reg, uint64_t seed, int32_t sample, const float *eps,
+                        float *btilde);
 /* 3MG, the reference's other solver choice (`method != 'lcg'` -> qmm.mmmg, fusion_CT.py:194-198; algorithms.py:69,106),
  * for the same quadratic criterion: every iteration minimises it exactly over span{-gradient, previous move}
  * (the quadratic majorant of a quadratic objective is the objective).  The 2x2 subspace system is solved in a basis
@@ -690,6 +721,13 @@ int surfh_debug_planes_passes(surfh_plan *plan, int32_t L, int32_t na, int32_t n
  * 2^31 floats or more, LP % 64 != 0, an unknown name and a missing pointer fail with a message and launch nothing. */
 int surfh_debug_planes_cg(surfh_plan *plan, const char *which, const int64_t *ext, float *v0, float *v1, float *v2, float *v3,
                           float *v4, float *v5, double mu_reg, int32_t update_r, const double *sc_in, double *sc_out);
+/* diagnostic: ONE fused perturbation kernel of surfh_cg_planes_sample on a device array of explicit extents, through the sampler's
+ * launcher (the plan gives its stream only; synchronises).  which = "eta": out_dev [L][na][nb] = sqrt(mu_reg) (Dr^T eps_r + Dc^T eps_c)
+ * of draw (seed, sample) -- surfh_randn_dev on streams 1 and 2 followed by surfh_po_prior_dev on T = L maps, bit for bit (n_out, mu,
+ * w_dev unused).  which = "data": out_dev [n_out] = eps_y / sqrt(mu w), 0 where w = 0 (w_dev NULL: 1) -- surfh_randn_dev on stream 0
+ * followed by surfh_po_data_dev(y_dev = NULL), bit for bit (L, na, nb, mu_reg unused).  Any alignment of out_dev and w_dev. */
+int surfh_debug_po_planes(surfh_plan *plan, const char *which, int32_t L, int32_t na, int32_t nb, int64_t n_out, uint64_t seed,
+                          int32_t sample, double mu, double mu_reg, const float *w_dev, float *out_dev);
 /* diagnostic: ONE application of the normal operator of the device-resident plane-wise CG (surfh_cg_planes_begin_dev / _step_dev
  * on wavelength-innermost vectors), q = mu A^T W A v + mu_reg (Dr^T Dr + Dc^T Dc) v, through the function the loop calls, on the
  * loop's own buffers: v_dev [Lc][Na][Nb] is transposed into the cube's layout [NBP][NAP][LP] as the begin call transposes x0, the

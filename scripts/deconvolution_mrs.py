@@ -34,6 +34,12 @@ problem, by ``MRSBlurred.cg_nonneg`` (ADMM around the CG, surfh_amd/nonneg.py) f
 ``<--out>_nn``: the files above, ``criterion.npy`` holding the criterion at the start and at the result, plus ``nn_trace.npy``
 ``[outer iterations run + 1, 4, planes]``: ``|x - z|``, ``rho |z - z_previous|``, ``|r|``, ``#{z == 0}`` per plane.  Works with
 ``--angle``.
+
+``--samples K --sample_seed S`` (with ``-m lcg``; not in the reference): per-pixel uncertainty of the result by
+``MRSBlurred.sample_posterior`` -- the CG solve, then K perturbed solves with as many iterations (perturbation-optimisation sampling,
+surfh_amd/posterior.py; ``--seed`` stays the data's seed).  The results go to ``<--out>_po_<K>``: the files above (``res_x.npy`` the
+point estimate), plus ``res_mean.npy`` and ``res_std.npy`` in its shape and ``po_trace.npy`` ``[2, planes]``: per plane the largest
+first and the largest final r.r of the sample solves (``rr_first``, ``rr_last``).  Works with ``--angle``.
 """
 from __future__ import annotations
 
@@ -91,6 +97,11 @@ def result_dir(out, delta, potential="huber", coupling="none"):
     return name if coupling == "none" else f"{name}_cpl_{coupling}"
 
 
+def samples_dir(out, samples):
+    """<out>_po_<K>"""
+    return f"{out}_po_{samples}"
+
+
 @click.command()
 @click.option("-np", "--npix", default=251, type=int, help="image size (the reference's maps are 251 x 251)")
 @click.option("-hp", "--hyper_parameter", default=5.0, type=float, help="mu_reg (reference: 5)")
@@ -118,8 +129,20 @@ def result_dir(out, delta, potential="huber", coupling="none"):
 @click.option("--rho", default=None, type=float, help="ADMM penalty of every plane (--nonneg); default: estimated per plane")
 @click.option("--outer", default=None, type=int, help="outer iterations (--nonneg); default: -ni")
 @click.option("--inner", default=None, type=int, help="CG iterations per outer iteration (--nonneg); default: 10")
+@click.option("--samples", default=None, type=int,
+              help="posterior samples for a per-pixel error bar (-m lcg, at least 2); results go to <out>_po_<samples>")
+@click.option("--sample_seed", default=0, type=int, help="key of the sampler's generator (--samples); --seed is the data's")
 def main(npix, hyper_parameter, niter, method, value_init, planes, inp, out, quiet, seed, device, angle, data_to_img, delta,
-         potential="huber", coupling="none", nonneg=False, rho=None, outer=None, inner=None):
+         potential="huber", coupling="none", nonneg=False, rho=None, outer=None, inner=None, samples=None, sample_seed=0):
+    if samples is not None:
+        if method != "lcg":
+            raise click.UsageError("--samples draws from the Gaussian posterior of the quadratic criterion: use it with -m lcg, not qmm / 3MG")
+        if delta is not None:
+            raise click.UsageError("--samples: the posterior of a Huber prior (--delta) is not Gaussian")
+        if nonneg:
+            raise click.UsageError("--samples: the posterior under --nonneg is not Gaussian")
+        if samples < 2:
+            raise click.UsageError(f"--samples: a standard deviation needs at least 2 samples, not {samples}")
     if nonneg:
         if method != "lcg":
             raise click.UsageError("--nonneg runs ADMM around the linear CG; use it with -m lcg")
@@ -142,6 +165,8 @@ def main(npix, hyper_parameter, niter, method, value_init, planes, inp, out, qui
         if method == "lcg":
             raise ValueError("lcg minimises quadratic criteria only: a Huber prior (delta) needs method='mmmg'")
         out = result_dir(out, delta, potential, coupling)
+    if samples is not None:
+        out = samples_dir(out, samples)
     if angle:
         from surfh_amd.spectro_blind import MRSBlurred, QuadCriterion_MRS_2D
     else:
@@ -155,8 +180,17 @@ def main(npix, hyper_parameter, niter, method, value_init, planes, inp, out, qui
     crit = QuadCriterion_MRS_2D(mu_spectro=1, y_spectro=np.copy(simulated_data), model_spectro=model, mu_reg=hyper_parameter,
                                 printing=True, gradient="separated", delta=delta, potential=potential, coupling=coupling)
     t0 = time.time()
-    nn = None
-    if nonneg:
+    nn = po = None
+    if samples is not None:
+        from surfh_amd.fusion import OptimizeResult
+        po = crit.sample(n_samples=samples, seed=sample_seed, maximum_iterations=niter, value_init=value_init)
+        res = OptimizeResult(x=po.x_map.ravel(), grad_norm=list(po.grad_norm), nit=po.nit, success=True, time=time.time() - t0)
+        crit.L_crit_val = [crit.get_crit_val(np.full(model.ishape, value_init)), crit.get_crit_val(po.x_map)]
+        if not quiet:
+            first, last = np.atleast_1d(po.rr_first), np.atleast_1d(po.rr_last)
+            print(f"{samples} samples: median std {np.median(po.std):.4e}, worst final r.r / first r.r over the planes = "
+                  f"{np.max(last / np.where(first > 0, first, 1.0)):.3e}")
+    elif nonneg:
         from surfh_amd.fusion import OptimizeResult
         x0 = np.full(model.ishape, value_init)
         nn = model.cg_nonneg(np.copy(simulated_data), mu=1, mu_reg=hyper_parameter, rho=rho, x0=x0, outer=outer or niter, inner=inner or 10)
@@ -180,6 +214,10 @@ def main(npix, hyper_parameter, niter, method, value_init, planes, inp, out, qui
     np.save(os.path.join(out, "res_x.npy"), x)
     np.save(os.path.join(out, "criterion.npy"), np.asarray(crit.L_crit_val))
     np.save(os.path.join(out, "data.npy"), simulated_data)
+    if po is not None:
+        np.save(os.path.join(out, "res_mean.npy"), po.mean)
+        np.save(os.path.join(out, "res_std.npy"), po.std)
+        np.save(os.path.join(out, "po_trace.npy"), np.stack([np.atleast_1d(po.rr_first), np.atleast_1d(po.rr_last)]))
     if nn is not None:
         tr = np.stack([nn.primal, nn.dual, nn.grad_norm, nn.n_active.astype(np.float64)], axis=1)
         np.save(os.path.join(out, "nn_trace.npy"), tr.reshape(nn.nit + 1, 4, planes))

@@ -59,6 +59,7 @@ EXPORTS = [
     "surfh_prior_add_dev", "surfh_spec_supported", "surfh_spec_size", "surfh_to_spec_dev", "surfh_from_spec_dev", "surfh_forward_spec_dev",
     "surfh_adjoint_spec_dev", "surfh_normal_spec_dev", "surfh_prior_spec_add_dev", "surfh_set_prior", "surfh_set_potential", "surfh_get_potential", "surfh_set_prior_coupling", "surfh_get_prior_coupling", "surfh_set_data_weights", "surfh_set_data_weights_dev", "surfh_has_data_weights", "surfh_set_imager", "surfh_imager_osize", "surfh_imager_forward", "surfh_imager_adjoint", "surfh_imager_forward_dev", "surfh_imager_adjoint_dev", "surfh_imager_fwadj", "surfh_set_imager_data", "surfh_has_imager_term", "surfh_dot_dev", "surfh_cg_step_dev", "surfh_cg_dir_dev", "surfh_cg_iter_dev", "surfh_residual_dev",
     "surfh_randn_dev", "surfh_po_data_dev", "surfh_po_prior_dev", "surfh_po_moments", "surfh_po_rhs", "surfh_cg_sample",
+    "surfh_cg_planes_sample", "surfh_po_planes_rhs", "surfh_po_planes_moments", "surfh_debug_po_planes",
     "surfh_cg_begin_dev", "surfh_cg_iter_nosync_dev", "surfh_cg_xupdate_nosync_dev", "surfh_cg_refresh_nosync_dev", "surfh_cg_trace",
     "surfh_profile_enable", "surfh_profile_filter", "surfh_profile_count", "surfh_profile_get", "surfh_profile_reset", "surfh_debug_copy",
     "surfh_debug_dims", "surfh_gemm_selftest", "surfh_gemm_selftest_ksteps", "surfh_gemm_selftest_ms", "surfh_klist_classify", "surfh_launch_geometry", "surfh_route_decide", "surfh_mm_step2",
@@ -117,6 +118,10 @@ def load():
     L.surfh_cg_sample.argtypes = [vp, c_float_p, C.c_double, C.c_double, c_float_p, C.c_int32, C.c_double, C.c_int32, C.c_int32,
                                   C.c_uint64, c_float_p, c_float_p, c_float_p, c_float_p, c_double_p, c_double_p, c_double_p,
                                   c_int32_p, c_double_p, SAMPLE_CALLBACK, vp]
+    L.surfh_cg_planes_sample.argtypes = L.surfh_cg_sample.argtypes[:-3] + [c_double_p, c_double_p, SAMPLE_CALLBACK, vp]  # rr_first, rr_last
+    L.surfh_po_planes_rhs.argtypes = L.surfh_po_rhs.argtypes
+    L.surfh_po_planes_moments.argtypes = L.surfh_po_moments.argtypes
+    L.surfh_debug_po_planes.argtypes = [vp, C.c_char_p] + [C.c_int32] * 3 + [C.c_int64, C.c_uint64, C.c_int32, C.c_double, C.c_double, vp, vp]
     L.surfh_mmmg_huber.argtypes = [vp, c_float_p] + [C.c_double] * 3 + tail + [c_double_p] + cb
     L.surfh_huber_prior_dev.argtypes = [vp, vp, vp, C.c_double, C.c_double, c_double_p]
     L.surfh_huber_curv_dev.argtypes = [vp, vp, vp, vp, C.c_double, c_double_p]

@@ -242,6 +242,40 @@ class Blurred2D(DataWeights, _pot.Potentials, PlanOwner, LinOp):
             return _lib.solve(self, self._L.surfh_cg_planes_cb, data, mu, mu_reg, x0, max_iter, tol, refresh, callback,
                               planes=self.n_planes, squeeze=not self.batched)
 
+    # ---- per-pixel uncertainty of what cg returns: perturbation-optimisation sampling, plane by plane (surfh_amd/posterior.py) ----
+    def sample_posterior(self, data, mu=1.0, mu_reg=0.0, n_samples=16, seed=0, x0=None, max_iter=10, tol=1e-12, refresh=50,
+                         weights=None, perturbations=None, callback=None):
+        """Per-pixel uncertainty of the images ``cg`` returns.  The criterion of ``cg`` is, plane by plane, the negative log of a
+        Gaussian posterior ``p(x_l | y_l) ~ exp(-x_l^T Q_l x_l / 2 + b_l^T x_l)``, ``Q_l = mu A_l^T W_l A_l + mu_reg (Dr^T Dr + Dc^T Dc)``,
+        ``b_l = mu A_l^T W_l y_l`` -- a statistical statement once ``weights = 1 / sigma^2`` (``mu = 1``).  Runs ``cg`` (same
+        arguments, same bits), then ``n_samples`` perturbed solves ``Q_l e_l = b~_l - b_l`` from zero (``b~ ~ N(b, Q)``,
+        ``x~ = x_map + e``) with the same ``max_iter``, ``tol`` and ``refresh``, and returns a ``posterior.PlanesPosteriorResult``:
+        ``x_map``, ``mean``, ``var``, ``std``, ``nit``, ``grad_norm``, ``rr_first``, ``rr_last``, ``n_samples`` (include/surfh_amd.h:
+        surfh_cg_planes_sample).  The noise is generated on the device, in the registers of the kernels that use it: beside the
+        solver's vectors a run holds two float32 and two float64 vectors of the planes' size.
+
+        A sample is exact only if its solve converges: where ``rr_last`` is not small against ``rr_first`` the plane's ``std`` is a
+        lower bound.  A plane whose ``rr_first`` is exactly 0 -- no data weight and ``mu_reg = 0`` -- has no proper posterior and
+        reports ``var = std = +inf``, not 0.
+
+        ``seed``: the counter-based generator's 64-bit key; the same seed gives the same bits, whatever ran before.  ``weights``:
+        as in ``cg``.  ``perturbations=(eps_y [K, osize], eps_r [K, isize], eps_c [K, isize])``: the standard normal vectors of
+        every draw instead of the generator's (what makes a float64 comparison possible; ``eps_r`` / ``eps_c`` may be None with
+        ``mu_reg = 0``).  ``callback(k, rr, x)``: every finished sample -- its index, the r.r trace of its solve (``[nit_k+1,
+        n_planes]``) and ``x~``; a truthy return stops the run with an error.  ``ValueError``: ``mu`` not finite and > 0,
+        ``mu_reg`` not one finite number >= 0, ``n_samples < 2``, ``max_iter < 0``, arrays of the wrong size."""
+        from . import posterior
+        return posterior.sample_posterior_planes(self, data, mu, mu_reg, n_samples, seed, x0, max_iter, tol, refresh, weights,
+                                                 perturbations, callback)
+
+    def po_planes_dev(self, which, out_t, shape=None, n_out=0, seed=0, sample=0, mu=1.0, mu_reg=0.0, w_t=None):
+        """Diagnostic: one fused perturbation kernel of ``sample_posterior`` into the device tensor ``out_t`` (or a raw address), on
+        explicit extents whatever the model's own: ``which="eta"`` with ``shape=(L, na, nb)``, ``which="data"`` with ``n_out``
+        floats and the weights ``w_t`` (None: 1).  Synchronises.  (include/surfh_amd.h: surfh_debug_po_planes)"""
+        L, na, nb = (int(v) for v in (shape if shape is not None else (1, 1, 1)))
+        _lib.check(self._L.surfh_debug_po_planes(self._plan, which.encode(), L, na, nb, int(n_out), _lib.seed64(seed), int(sample),
+                                                 float(mu), float(mu_reg), dev_ptr(w_t), dev_ptr(out_t)), ValueError)
+
     # ---- the same criterion under x >= 0: ADMM around the CG above, plane by plane (surfh_amd/nonneg.py) ----------
     def nonneg_rho(self, mu=1.0, mu_reg=0.0, seed=0, weights=None):
         """The default penalties of ``cg_nonneg``: per plane ``v_l^T Q_l v_l / v_l^T v_l`` for one standard normal probe ``v``

@@ -270,6 +270,15 @@ int launch_po_add(hipStream_t s, float *b, const float *e, long n);
 long po_moment_planes(int T);
 int launch_po_moments(hipStream_t s, const float *x, const float *xhat, double *S, int T, long npix);
 int launch_po_finish(hipStream_t s, const float *xhat, const double *S, int T, long npix, int K, double *mean, double *cov);
+// the plane-wise sampler (surfh_cg_planes_sample), the noise generated in registers: out [L][na][nb] = sqrt_mu_reg (Dr^T eps_r + Dc^T eps_c),
+// eps_r / eps_c the streams 1 / 2 of (seed, sample) over the flat index -- launch_randn twice and launch_po_prior(T = L), bit for bit;
+// out [n] = eps_y / sqrt(mu w), 0 where w = 0 (w NULL: 1), eps_y the stream 0 -- launch_randn and launch_po_data(y NULL), bit for bit
+int launch_po_planes_eta(hipStream_t s, float *out, int L, int na, int nb, float sqrt_mu_reg, uint64_t seed, uint32_t sample);
+int launch_po_planes_data(hipStream_t s, const float *w, float *out, long n, float mu, uint64_t seed, uint32_t sample);
+// S1 [n] += e, S2 [n] += e e in float64, e = x - xhat (xhat NULL: x); then, in place, S1 <- xhat + S1 / K and (want_var) S2 <- the
+// unbiased variance (S2 - S1^2 / K) / (K - 1), clamped at 0
+int launch_po_planes_moments(hipStream_t s, const float *x, const float *xhat, double *S1, double *S2, long n);
+int launch_po_planes_finish(hipStream_t s, const float *xhat, double *S1, double *S2, long n, int K, int want_var);
 
 // ---- nonneg.hip: non-negative fusion ----
 // the ADMM projection / dual update in one pass: z' = max(x + u, 0) (no set sign bit), u' = u + x - z', in place in z and u, and with

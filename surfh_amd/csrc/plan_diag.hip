@@ -183,6 +183,57 @@ int surfh_launch_geometry(const char *which, int64_t a, int64_t b, int64_t c, in
     return 0;
 }
 
+// ---- the plane-wise posterior sampler's kernels on their own (posterior.hip; the loop: surfh_cg_planes_sample) ----
+// One fused perturbation kernel on a device array of explicit extents, through the sampler's launcher; the plan gives its stream only.
+int surfh_debug_po_planes(surfh_plan *p, const char *which, int32_t L, int32_t na, int32_t nb, int64_t n_out, uint64_t seed, int32_t sample,
+                          double mu, double mu_reg, const float *w_dev, float *out_dev) {
+    const char *who = "surfh_debug_po_planes";
+    if (!p || !which || !out_dev) return fail("null argument");
+    if (sample < 0) return fail("%s: sample = %d", who, (int)sample);
+    const std::string w(which);
+    HIP_OK(hipSetDevice(p->dev));
+    if (w == "eta") {
+        if (L < 1 || na < 1 || nb < 1 || (double)L * (double)na * (double)nb > 2147483647.0)
+            return fail("%s: eta on %d planes of %d x %d", who, (int)L, (int)na, (int)nb);
+        if (!(mu_reg >= 0.0 && mu_reg <= DBL_MAX)) return fail("%s: mu_reg = %g must be finite and >= 0", who, mu_reg);
+        Prof pr(p, "po_planes_eta");
+        LAUNCH_OK(launch_po_planes_eta(p->stream, out_dev, L, na, nb, (float)std::sqrt(mu_reg), seed, (uint32_t)sample));
+    } else if (w == "data") {
+        if (n_out < 0) return fail("%s: n_out = %lld", who, (long long)n_out);
+        if (!(mu > 0.0 && mu <= DBL_MAX)) return fail("%s: mu = %g must be finite and > 0", who, mu);
+        Prof pr(p, "po_planes_data");
+        LAUNCH_OK(launch_po_planes_data(p->stream, w_dev, out_dev, (long)n_out, (float)mu, seed, (uint32_t)sample));
+    } else {
+        return fail("%s: unknown kernel '%s' (eta, data)", who, which);
+    }
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+// The plane moments on host buffers: K samples [K][L][npix] about xhat [L][npix]; mean [L][npix] and var [L][npix] (NULL: not wanted;
+// needs K >= 2) in float64 -- the accumulation and the in-place finish of surfh_cg_planes_sample.
+int surfh_po_planes_moments(int32_t L, int64_t npix, const float *xhat, const float *samples, int32_t K, double *mean, double *var,
+                            int32_t device) {
+    if (!xhat || !samples || !mean) return fail("null argument");
+    if (L < 1 || npix < 1 || K < 1) return fail("plane moments: L = %d, npix = %ld, K = %d", (int)L, (long)npix, (int)K);
+    if (var && K < 2) return fail("plane moments: a variance needs at least 2 samples (got %d)", (int)K);
+    HIP_OK(hipSetDevice(device));
+    const size_t n = (size_t)L * npix;
+    DevBuf<float> dx, dh;
+    DevBuf<double> S;
+    if (dx.alloc(n) || dh.alloc(n) || S.alloc(2 * n)) return 1;
+    HIP_OK(hipMemcpy(dh, xhat, n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(S, 0, 2 * n * sizeof(double)));
+    for (int k = 0; k < K; ++k) {
+        HIP_OK(hipMemcpy(dx, samples + (size_t)k * n, n * sizeof(float), hipMemcpyHostToDevice));
+        LAUNCH_OK(launch_po_planes_moments(nullptr, dx, dh, S, S + n, (long)n));
+    }
+    LAUNCH_OK(launch_po_planes_finish(nullptr, dh, S, S + n, (long)n, K, var ? 1 : 0));
+    HIP_OK(hipMemcpy(mean, S, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (var) HIP_OK(hipMemcpy(var, S + n, n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int surfh_mm_step2(double dBd, double dBm, double mBm, double dg, double mg, double step[2]) {
     if (!step) return fail("null argument");
     mm_step2(dBd, dBm, mBm, dg, mg, &step[0], &step[1]);

@@ -291,7 +291,8 @@ struct surfh_plan : PlanHandles {
     DevBuf<float> rb_y, rb_u, rb_ag, rb_am;       // surfh_mmmg_robust(_vox): y, A x, A (-g), A m [osize]
     DevBuf<double> dscal, dscratch;                 // [16] device scalars, partial sums (>= 1024, and what huber_vox.hip and robust_data.hip ask for)
     // posterior sampling (surfh_cg_sample): y, the noise vectors eps_y [osize], eps_r / eps_c [isize], eta and the unperturbed
-    // solution [isize]; the moment sums (posterior.hip)
+    // solution [isize]; the moment sums (posterior.hip).  surfh_cg_planes_sample (T = 0) holds po_eta, po_xhat and po_S [2 isize]
+    // only; its staging buffers po_eps, po_er / po_ec come with a caller's explicit draws, po_y with surfh_po_planes_rhs
     DevBuf<float> po_y, po_eps, po_er, po_ec, po_eta, po_xhat;
     DevBuf<double> po_S;
     // non-negative fusion (surfh_cg_nonneg, surfh_cg_templates_nonneg), allocated for one solve (NnScope): the split variable, the

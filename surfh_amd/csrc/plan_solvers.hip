@@ -462,7 +462,7 @@ int cg_loop(surfh_plan *p, const CgSpace &s, int32_t max_iter, double tol, int32
         if (std::sqrt(*std::max_element(gn, gn + s.rows)) < (double)s.n * tol) break;
     }
     if (s.to_caller(p, s)) return 1;
-    HIP_OK(hipMemcpyAsync(x, s.xc, (s.clen ? s.clen : p->isize) * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    if (x) HIP_OK(hipMemcpyAsync(x, s.xc, (s.clen ? s.clen : p->isize) * sizeof(float), hipMemcpyDeviceToHost, p->stream));   // NULL: it stays in s.xc
     HIP_OK(hipStreamSynchronize(p->stream));
     return 0;
 }
@@ -1525,6 +1525,132 @@ int surfh_cg_planes_rr(surfh_plan *p, double *rr_host) {
     HIP_OK(hipSetDevice(p->dev));
     const CgSpace s = stored_space(p);
     return s.trace(p, s, rr_host, 0);
+}
+
+// ---- posterior sampling of the planes: surfh_cg_sample's perturbation-optimisation on the Lc independent problems of surfh_cg_planes.
+// At the driver's size a vector of the planes is gigabytes, so the map-domain staging does not carry over: with the generator the
+// perturbation of the data is written straight into io_y and eta straight into po_eta (po_planes_data / po_planes_eta: the noise lives
+// in registers), and the moments are two float64 sums per element that the finish turns into mean and variance in place.  Allocated:
+// po_eta, po_xhat [isize] and po_S [2 isize] doubles; the staging buffers po_eps [osize] / po_er, po_ec [isize] only once a caller
+// passes explicit draws, which go through the unfused kernels of surfh_cg_sample.
+namespace {
+int po_planes_refuse(const surfh_plan *p, double mu, double mu_reg, const char *who) {
+    if (imager_refuse(p, who)) return 1;
+    if (p->T != 0) return fail("%s samples the plane-wise (no template) model, the plan has %d templates: use surfh_cg_sample", who, p->T);
+    if (p->prior_kind != 0) return fail("%s draws the prior's noise through the separated differences: surfh_set_prior(plan, 0)", who);
+    if (!(mu > 0.0 && mu <= DBL_MAX)) return fail("%s: mu = %g must be finite and > 0", who, mu);
+    if (!(mu_reg >= 0.0 && mu_reg <= DBL_MAX)) return fail("%s: mu_reg = %g must be finite and >= 0", who, mu_reg);
+    return 0;
+}
+int po_planes_ensure(surfh_plan *p, bool explicit_y, bool explicit_prior) {
+    const size_t no = (size_t)p->osize, ni = (size_t)p->isize;
+    if (ensure_set(member(p->po_eta, ni), member(p->po_xhat, ni), member(p->po_S, 2 * ni))) return 1;       // S1, S2: then mean, var
+    if (explicit_y && ensure_set(member(p->po_eps, no))) return 1;
+    return explicit_prior ? ensure_set(member(p->po_er, ni), member(p->po_ec, ni)) : 0;
+}
+// draw `sample`: the perturbation eps_y / sqrt(mu w) to io_y (`y` NULL) or y + it (y on the device), eta to po_eta; *extra = po_eta, or
+// NULL where mu_reg = 0.  eps_* as in po_perturb; eps_r or eps_c given: both prior vectors are staged (the missing one generated)
+int po_planes_perturb(surfh_plan *p, const float *y, double mu, double mu_reg, uint64_t seed, int sample, const float *eps_y, const float *eps_r,
+                      const float *eps_c, const float **extra) {
+    hipStream_t s = p->stream;
+    if (eps_y || y) {
+        if (po_noise(p, p->po_eps, p->osize, eps_y, seed, 0, sample)) return 1;
+        Prof pr(p, "po_data");
+        LAUNCH_OK(launch_po_data(s, y, p->dw, p->po_eps, p->io_y, p->osize, (float)mu));
+    } else {
+        Prof pr(p, "po_planes_data");
+        LAUNCH_OK(launch_po_planes_data(s, p->dw, p->io_y, p->osize, (float)mu, seed, (uint32_t)sample));
+    }
+    *extra = nullptr;
+    if (mu_reg == 0.0) return 0;
+    const float sq = (float)std::sqrt(mu_reg);
+    if (eps_r || eps_c) {
+        if (po_noise(p, p->po_er, p->isize, eps_r, seed, 1, sample) || po_noise(p, p->po_ec, p->isize, eps_c, seed, 2, sample)) return 1;
+        Prof pr(p, "po_prior");
+        LAUNCH_OK(launch_po_prior(s, p->po_er, p->po_ec, p->po_eta, p->Lc, p->Na, p->Nb, sq));
+    } else {
+        Prof pr(p, "po_planes_eta");
+        LAUNCH_OK(launch_po_planes_eta(s, p->po_eta, p->Lc, p->Na, p->Nb, sq, seed, (uint32_t)sample));
+    }
+    *extra = p->po_eta;
+    return 0;
+}
+}  // namespace
+
+int surfh_po_planes_rhs(surfh_plan *p, const float *y, double mu, double mu_reg, uint64_t seed, int32_t sample, const float *eps,
+                        float *btilde) {
+    const char *who = "surfh_po_planes_rhs";
+    if (!p || !y || !btilde) return fail("null argument");
+    if (po_planes_refuse(p, mu, mu_reg, who)) return 1;
+    if (sample < 0) return fail("%s: sample = %d", who, sample);
+    // y~ = y + eps_y / sqrt(mu w) needs y beside the noise: the data part goes through the staged kernel (po_y, po_eps)
+    if (cg_planes_ready(p, who, false) || po_planes_ensure(p, true, mu_reg != 0.0 && eps) || ensure_set(member(p->po_y, (size_t)p->osize))) return 1;
+    HIP_OK(hipMemcpyAsync(p->po_y, y, p->osize * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    const float *extra = nullptr;
+    if (po_planes_perturb(p, p->po_y, mu, mu_reg, seed, eps ? 0 : sample, eps, eps ? eps + p->osize : nullptr,
+                          eps ? eps + p->osize + p->isize : nullptr, &extra))
+        return 1;
+    const float *wy = weighted_data(p, p->io_y);                                    // as solver_setup: mu A^T W y~ + eta
+    if (!wy || adjoint_dev(p, wy, p->cg_b)) return 1;
+    if (mu != 1.0) LAUNCH_OK(launch_scale(p->stream, p->cg_b, p->isize, (float)mu));
+    if (extra) LAUNCH_OK(launch_po_add(p->stream, p->cg_b, extra, p->isize));
+    HIP_OK(hipMemcpyAsync(btilde, p->cg_b, p->isize * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int surfh_cg_planes_sample(surfh_plan *p, const float *y, double mu, double mu_reg, const float *x0, int32_t max_iter, double tol,
+                           int32_t refresh, int32_t n_samples, uint64_t seed, const float *eps_y, const float *eps_r, const float *eps_c,
+                           float *x_map, double *mean, double *var, double *grad_norm, int32_t *nit, double *rr_first, double *rr_last,
+                           surfh_sample_callback callback, void *user) {
+    const char *who = "surfh_cg_planes_sample";
+    if (!p || !y || !x_map || !grad_norm || !nit) return fail("null argument");
+    if (po_planes_refuse(p, mu, mu_reg, who)) return 1;
+    if (n_samples < 1 || (var && n_samples < 2)) return fail("%s: n_samples = %d (at least 1, and at least 2 for a variance)", who, n_samples);
+    if (max_iter < 0) return fail("%s: max_iter = %d", who, max_iter);
+    if (cg_planes_ready(p, who, false) || po_planes_ensure(p, eps_y != nullptr, mu_reg != 0.0 && (eps_r || eps_c))) return 1;
+    // the point estimate: surfh_cg_planes itself
+    if (surfh_cg_planes_cb(p, y, mu, mu_reg, x0, max_iter, tol, refresh, x_map, grad_norm, nit, nullptr, nullptr)) return 1;
+    hipStream_t s = p->stream;
+    const int L = p->Lc;
+    double *const S1 = p->po_S, *const S2 = S1 + p->isize;
+    HIP_OK(hipMemcpyAsync(p->po_xhat, p->cg_x, p->isize * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_OK(hipMemsetAsync(S1, 0, 2 * (size_t)p->isize * sizeof(double), s));
+    std::vector<float> xs(callback ? (size_t)p->isize : 0);
+    std::vector<double> gn(((size_t)max_iter + 1) * L), first((size_t)L, 0.0), last((size_t)L, 0.0);
+    for (int k = 0; k < n_samples; ++k) {
+        CgSpace sp = planes_space(p, p->cg_x, mu, mu_reg);                          // Q_l e_l = b~_l - b_l from e = 0
+        if (po_planes_perturb(p, nullptr, mu, mu_reg, seed, k, eps_y, eps_r, eps_c, &sp.extra)) return 1;
+        int32_t nk = 0;
+        if (start_iterate(p, nullptr) || cg_start(p, sp, p->io_y, sp.xc)) return 1;
+        if (cg_loop(p, sp, max_iter, tol, refresh, 1, callback ? xs.data() : nullptr, gn.data(), &nk, nullptr, nullptr)) return 1;
+        {
+            Prof pr(p, "po_planes_moments");
+            LAUNCH_OK(launch_po_planes_moments(s, p->cg_x, nullptr, S1, S2, p->isize));
+        }
+        for (int l = 0; l < L; ++l) {
+            first[l] = std::max(first[l], gn[l]);
+            last[l] = std::max(last[l], gn[(size_t)nk * L + l]);
+        }
+        if (callback) {
+            for (long i = 0; i < p->isize; ++i) xs[i] += x_map[i];                  // x~ = xhat + e
+            if (callback(user, k, nk, gn.data(), xs.data())) return fail("%s: stopped by the callback at sample %d", who, k);
+            HIP_OK(hipSetDevice(p->dev));
+        }
+    }
+    if (rr_first) std::copy(first.begin(), first.end(), rr_first);
+    if (rr_last) std::copy(last.begin(), last.end(), rr_last);
+    if (mean || var) {
+        {
+            Prof pr(p, "po_planes_finish");
+            LAUNCH_OK(launch_po_planes_finish(s, p->po_xhat, S1, S2, p->isize, n_samples, var ? 1 : 0));
+        }
+        if (mean) HIP_OK(hipMemcpyAsync(mean, S1, p->isize * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (var) HIP_OK(hipMemcpyAsync(var, S2, p->isize * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    HIP_OK(hipMemcpyAsync(p->cg_x, p->po_xhat, p->isize * sizeof(float), hipMemcpyDeviceToDevice, s));   // the plan as surfh_cg_planes leaves it
+    HIP_OK(hipStreamSynchronize(s));
+    return 0;
 }
 
 // ---- 3MG on independent planes: every plane's beta, 2x2 system and step on the device, so the host reads one thing per

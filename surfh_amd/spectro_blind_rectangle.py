@@ -165,6 +165,20 @@ class QuadCriterion_MRS_2D:
             print(f"Total time needed for {method} :", round(res.time, 3))
         return res
 
+    def sample(self, n_samples=16, seed=0, maximum_iterations=10, tolerance=1e-12, value_init=0.5, perturbations=None, callback=None):
+        """Posterior samples of this criterion read as a Gaussian log-density (not in criterion_2D.py): forwards to
+        ``model_spectro.sample_posterior`` with this criterion's data, weights and hyper-parameters and ``run_method``'s start, and
+        returns its ``PlanesPosteriorResult`` (``x_map`` is what ``run_method("lcg", maximum_iterations)`` returns).
+        ``ValueError`` for a criterion with a Huber prior (``delta``): its posterior is not Gaussian."""
+        assert isinstance(self.mu_reg, (int, float))
+        if self.delta is not None:
+            raise ValueError("sample: the posterior of a Huber prior (delta) is not Gaussian")
+        init = np.ones(self.shape_of_output) * value_init if isinstance(value_init, (int, float)) else value_init
+        assert tuple(np.shape(init)) == self.shape_of_output
+        return self.model_spectro.sample_posterior(self.y_spectro, mu=self.mu_spectro, mu_reg=self.mu_reg, n_samples=n_samples, seed=seed,
+                                                   x0=init, max_iter=maximum_iterations, tol=tolerance, weights=self.weights,
+                                                   perturbations=perturbations, callback=callback)
+
     def get_crit_val(self, x_hat):
         """(mu |y - A x|^2 + mu_reg (|Dr x|^2 + |Dc x|^2)) / 2   (criterion_2D.py:252-275), summed over the planes; with ``delta``
         mu |y - A x|^2 / 2 + mu_reg sum phi(Dr x) + phi(Dc x), phi the criterion's potential (Huber by default); under a coupling
